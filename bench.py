@@ -81,6 +81,50 @@ def kernel_sources_sha():
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 63 << 20  # --dump-outputs: the arrays written, in all (under 64 MB with the .npy headers)
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, whole, groups):
+    """--dump-outputs DIR: write what the timed path computed in its last step as DIR/<name>.npy (float64; every value is
+    an integer below 2^32, so the conversion is exact).  `whole`: small arrays, written as they are.  `groups`: {group:
+    {name: array}}, the arrays of a group (numpy or device tensors) sharing a leading axis of proofs.  When everything would
+    not fit under DUMP_LIMIT_BYTES, every group keeps the same fraction of its proofs, a fixed, seeded sample (the same for
+    every array of the group, written as <group>_sample.npy), taken on the device before the download."""
+    def host(a):
+        return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+    os.makedirs(out_dir, exist_ok=True)
+    out = {k: host(v) for k, v in whole.items()}
+    room = DUMP_LIMIT_BYTES - sum(a.size * 8 for a in out.values())
+    shape = {g: (int(next(iter(arrs.values())).shape[0]), sum(int(np.prod(a.shape[1:])) * 8 for a in arrs.values()))
+             for g, arrs in groups.items() if arrs}
+    sampled = sum(n * rb for n, rb in shape.values()) > room
+    for g, (n, rb) in shape.items():
+        k = n
+        if sampled:  # + 8 bytes per kept proof: its index in <group>_sample.npy
+            k = min(n, max(0, room * n // max(sum(m * (r + 8) for m, r in shape.values()), 1)))
+        if k == n:
+            out.update({name: host(a) for name, a in groups[g].items()})
+            continue
+        sample = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+        out[g + "_sample"] = sample
+        for name, a in groups[g].items():
+            if isinstance(a, np.ndarray):
+                a = a[sample]
+            else:
+                import torch
+                a = a[torch.from_numpy(sample).to(a.device)]
+            out[name] = host(a)
+    total = sum(a.size * 8 for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in out.items():
+        if a.dtype.kind == "i" and a.dtype.itemsize == 4:
+            a = a.view(np.uint32)  # 32-bit words (hashes, field elements) held in int32 tensors
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+
+
 def job_fixture_index(i, n_fixtures, order="round_robin", n_total=None):
     """Which fixture proof i of the job is a copy of.  round_robin: i mod F (the bench mixes).  level: the job in the order
     the reference's driver produces it (examples/multi-proofs/src/main.rs:198-295): all copies of level 1, then level 2, ...
@@ -301,7 +345,14 @@ def main():
     ap.add_argument("--emit-flow", action="store_true",
                     help="also emit the PoseidonFlow of every proof's verification circuit (SURVEY 8f.1, second half: 128 B + "
                          "1 B per Poseidon invocation, ~0.7 MB per standard proof) from the verifying pass; any workload")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0: its accept and reason bytes, the "
+                         "job's gathered accept vector and count, every hint output) as DIR/<name>.npy, float64, at most 64 MB "
+                         "in all (arrays over proofs cut to a fixed, seeded sample of proofs if needed: <group>_sample.npy); with "
+                         "the same arguments the inputs are the same on every run, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # ---- plain `python bench.py --gpus N`: start the N ranks as child processes and wait.  This process loads neither
     # torch nor the HIP library (sharding.py is imported by path; it needs only the standard library and numpy).
@@ -387,8 +438,10 @@ def main():
             hdr = np.frombuffer(read_fixture(f)[:64], dtype=np.uint32)
             stride = max(stride, rsv.poseidon_flow_count(int(hdr[0]), int(hdr[1]), rsv.PcsConfig(int(hdr[10]), int(hdr[11]), int(hdr[12]), int(hdr[13]))))
         hints = dict(hints or {})
-        hints.update(d_flow=torch.empty((n, stride, 32), dtype=torch.int32, device=dev),
-                     d_flow_swap=torch.empty((n, stride), dtype=torch.uint8, device=dev),
+        # zeros: the kernel writes the first d_flow_count[p] records of proof p, and the rows past them (a proof of a smaller
+        # shape than the widest) must read the same from run to run (--dump-outputs)
+        hints.update(d_flow=torch.zeros((n, stride, 32), dtype=torch.int32, device=dev),
+                     d_flow_swap=torch.zeros((n, stride), dtype=torch.uint8, device=dev),
                      d_flow_count=torch.zeros(n, dtype=torch.int32, device=dev))
 
     # --inflight K: K - 1 further contexts with their own copy of the batch and of the outputs, driven by K - 1 threads
@@ -433,6 +486,13 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cpu" if rehearsal else dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        # before the checks below: a build that computes something else still leaves its outputs to compare
+        dump_outputs(args.dump_outputs, {"accepted_count": np.array([sv.exchange.total_accepted()])},
+                     {"proof": dict({"accept": sv.d_accept[:n], "reason": sv.d_reason[:n]},
+                                    **{k[2:]: v for k, v in (hints or {}).items() if k.startswith("d_")}),
+                      "job": {"job_accept": sv.exchange.assemble()}})
 
     # correctness of what was just timed: every untampered proof accepted, every tampered one rejected
     acc = sv.d_accept[:n].cpu().numpy()
@@ -806,6 +866,10 @@ def run_one_process(args):
     dt = time.perf_counter() - t0
     job_want = (np.arange(n_total) % 17 != 5).astype(np.uint8)
     job = np.unpackbits(bitmap.view(np.uint8), bitorder="little")[:n_total]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accepted_count": np.array([count])},
+                     {"proof": {"accept": np.concatenate([sh["d_accept"][: sh["n"]].cpu().numpy() for sh in shards])},
+                      "job": {"job_accept": job}})
     if not np.array_equal(job, job_want) or count != int(job_want.sum()):
         raise SystemExit("one-process path: the job's bitmap or count differs from the expected accept map")
     for r, sh in enumerate(shards):

@@ -116,3 +116,96 @@ def test_committed_profile_holds_the_large_batch_line():
         sys.path.insert(0, ROOT)
         import bench
         assert bench.kernel_sources_sha() == prof["kernel_sources_sha"], "profiles/ were taken on other kernel sources than the committed ones"
+
+
+def test_dump_outputs_writes_a_fixed_bounded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files, exact 32-bit words, within the size limit; every group of arrays over proofs that
+    does not fit is cut to one seeded sample of its proofs (<group>_sample.npy), the same on every call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 16)
+    n = 1024
+    accept = (np.arange(n) % 17 != 5).astype(np.uint8)
+    words = np.random.default_rng(1).integers(-2 ** 31, 2 ** 31, size=(n, 3, 2), dtype=np.int32)
+    job = np.tile(accept, 4)
+    samples = []
+    for k in range(2):
+        d = str(tmp_path / f"out{k}")
+        bench.dump_outputs(d, {"accepted_count": np.array([int(job.sum())])},
+                           {"proof": {"accept": accept, "flow": words}, "job": {"job_accept": job}})
+        files = sorted(os.listdir(d))
+        assert files == ["accept.npy", "accepted_count.npy", "flow.npy", "job_accept.npy", "job_sample.npy", "proof_sample.npy"]
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert sum(a.size * 8 for a in got.values()) <= 1 << 16
+        s, j = got["proof_sample"].astype(np.int64), got["job_sample"].astype(np.int64)
+        assert 0 < len(s) < n and np.all(np.diff(s) > 0) and 0 < len(j) < len(job) and np.all(np.diff(j) > 0)
+        assert np.array_equal(got["accept"], accept[s]) and np.array_equal(got["flow"], words[s].view(np.uint32))
+        assert np.array_equal(got["job_accept"], job[j]) and got["accepted_count"].tolist() == [job.sum()]
+        samples.append((s, j))
+    assert all(np.array_equal(x, y) for x, y in zip(*samples))
+    # what fits is written whole, without a sample
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    d = str(tmp_path / "whole")
+    bench.dump_outputs(d, {}, {"proof": {"accept": accept, "flow": words}, "job": {"job_accept": job}})
+    assert sorted(os.listdir(d)) == ["accept.npy", "flow.npy", "job_accept.npy"]
+    assert np.array_equal(np.load(os.path.join(d, "flow.npy")), words.view(np.uint32))
+
+
+# a fresh child process: bench.main() with ShardedVerifier.step counted, then the number of calls on the last line
+_COUNT_STEPS = """
+import sys
+sys.path.insert(0, sys.argv[1])
+import rsvload
+rsvload.load_package()
+from recursive_stwo_amd import sharding
+calls = [0]
+step = sharding.ShardedVerifier.step
+def counted(self, *a, **k):
+    calls[0] += 1
+    return step(self, *a, **k)
+sharding.ShardedVerifier.step = counted
+import bench
+sys.argv = ["bench.py"] + sys.argv[2:]
+bench.main()
+print("step calls", calls[0])
+"""
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", [["--emit-flow"], ["--workload", "copies", "--emit-paths"]], ids=["flow", "paths"])
+def test_bench_dump_outputs_are_the_timed_steps_outputs(tmp_path, extra):
+    """--steps K --warmup W runs the verifying step K + W times; --dump-outputs DIR then holds the last step's accept / reason
+    bytes, the job's gathered accept vector and the hint outputs, identical from run to run with the same arguments (with
+    --emit-flow on the mixed-shape workload, the flow rows past a proof's own count included)."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = str(tmp_path / f"out{k}")
+        out = subprocess.run([sys.executable, "-c", _COUNT_STEPS, ROOT, "--proofs", "512", "--steps", "3", "--warmup", "2",
+                              "--cpu-sample", "0", "--perm-log2", "0", "--no-single-proof", "--dump-outputs", d] + extra,
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert out.stdout.strip().splitlines()[-1] == "step calls 5", out.stdout[-500:]
+        line = _check_line(out.stdout, 1)
+        assert line["steps"] == 3 and line["warmup"] == 2
+        got = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64 << 20
+        assert all(a.dtype == np.float64 for a in got.values())
+        s = got["proof_sample"].astype(np.int64) if "proof_sample" in got else np.arange(512)
+        j = got["job_sample"].astype(np.int64) if "job_sample" in got else np.arange(512)
+        want = (np.arange(512) % 17 != 5).astype(np.float64)
+        assert np.array_equal(got["accept"], want[s]) and np.array_equal(got["job_accept"], want[j])
+        assert got["accepted_count"].tolist() == [want.sum()] and np.all((got["reason"] == 0) == (want[s] == 1))
+        if "flow" in got:
+            count = got["flow_count"].astype(np.int64)
+            assert count.max() > 0 and count.min() < got["flow"].shape[1]  # mixed shapes: rows past the count exist
+            past = np.arange(got["flow"].shape[1])[None, :] >= count[:, None]
+            assert not got["flow"][past].any() and not got["flow_swap"][past].any()
+        else:
+            assert {"transcript", "trace_sib", "fri_sib"} <= set(got)
+        runs.append(got)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
