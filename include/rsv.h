@@ -166,7 +166,8 @@ int rsv_stream_wait_ctx(rsv_ctx* ctx, void* hip_stream);
  * RSV_E_RANGE for a value outside the listed range. */
 typedef enum rsv_option {
     RSV_OPT_TRANSCRIPT_FORM = 1,  /* 0 auto (by batch size), 1 one proof per 16-lane DPP row, 2 one proof per lane */
-    RSV_OPT_TRANSCRIPT_SPLIT = 2, /* 0 auto, 1 one launch, 2 front half beside the parser + back half (row form only) */
+    RSV_OPT_TRANSCRIPT_SPLIT = 2, /* row form only: 0 auto, 1 one launch, 2 front half beside the parser + back half; a lane-form
+                                     batch runs its transcript as one launch whatever this says */
     RSV_OPT_OODS_FORM = 3,        /* 0 auto, 1 row, 2 lane */
     RSV_OPT_QCONST_FORM = 4,      /* 0 auto (<= 4 096 proofs: four 16-lane rows per proof, <= 24 576: one row, else lane), 1 one row per proof, 2 lane */
     RSV_OPT_PLAN_FORM = 5,        /* 0 / 1 one lane per (proof, query), 2 one lane per proof */
@@ -180,9 +181,6 @@ typedef enum rsv_option {
     RSV_OPT_CRITICAL_CHAIN = 13,  /* 0 auto, 1 the step's chain of dependent kernels on one stream, 2 the two-stream layout */
     RSV_OPT_DEVICE_ORDER = 14,    /* 0 / 1 batches under one configuration: slot order by shape on the device, no host round
                                      trip inside the call; 2 the host-side bucketing of multi-configuration batches */
-    RSV_OPT_GRAPH = 15,           /* 0 / 2 off; 1 (experiment) a call repeated with identical arguments — same buffers, sizes,
-                                     configuration, public inputs — is captured into a HIP graph on its second sighting
-                                     and replayed afterwards; rsv_last_stage_times then reports the last plain call */
     RSV_OPT_WITNESS_LAYOUT = 16,  /* rsv_witness_eval_dev's d_variables: 0 / 1 [proof][variable] (the reference's vector per
                                      proof); 2 [variable][proof] — what the level kernels write: no transpose (a third of
                                      the traffic) and no second copy in scratch, for consumers that gather for many proofs */
@@ -208,13 +206,7 @@ typedef enum rsv_option {
     RSV_OPT_CAP_MID = 26,         /* with the cap's top in kernels of its own (RSV_OPT_CAP_TOP): 0 auto — a bucket of proofs whose dense cap levels
                                      fill the tree kernels' waves badly (80, 27, 11, 10 queries) hands its nodes over at the cap level, a
                                      lane per subtree walks the middle levels (k_cap_mid), k_cap_top the rest; 1 every bucket does, 2 none */
-    RSV_OPT_PERM_FORM = 27,       /* rsv_poseidon2_permute_dev, experiments: 0 production (the out-of-line instance the verify kernels call), 1 the same
-                                     inlined, 2 inlined without wait states (recursive-stwo_amd/csrc/primitives.hpp: k_permute) */
-    RSV_OPT_OODS_EARLY = 28,      /* chain layout, experiments: 0 / 2 the OODS check behind the trace trees on the side stream; 1 on a third
-                                     stream right behind the transcript (measured: slower from 1 024 to 4 096 proofs, not taken) */
-    RSV_OPT_TREE_ORDER = 29,      /* workgroup order of the lane-form Merkle kernels: 0 / 2 tree by tree (grid row y = tree); 1 (measured, slower:
-                                     less HBM traffic, more time) the trees of a workgroup of proofs side by side and on one XCD, so that
-                                     their plan tables are fetched once per L2, not once per tree */
+    /* 15, 27, 28, 29: retired; rsv_ctx_set_option answers RSV_E_SIZE */
     RSV_OPT_CAP_TOP = 19          /* 0 auto (batches of >= 1 024 proofs), 1 the last two or three levels of every Merkle tree in a
                                      kernel of their own (one lane per tree), 2 inside the tree kernels (dense top-of-tree cap) */
 } rsv_option;

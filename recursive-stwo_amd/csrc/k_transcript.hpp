@@ -13,19 +13,15 @@ namespace rsv {
 // PACE: the permutation instance of the channel (poseidon2.hpp): unpaced while the launch leaves a wave alone on its SIMD
 // (up to 49 152 proofs: 32 768 proofs 17.6 -> 17.3 ms), paced beyond (131 072 proofs are two waves per SIMD: 68.4 against
 // 69.3 ms unpaced; 65 536: 34.25 against 34.3-34.5).
-template <bool FLOW, int PHASE = 0, bool PACE = true>
+template <bool FLOW, bool PACE = true>
 __global__ __launch_bounds__(64) void k_transcript(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ offsets,
                                                    uint32_t n, const ProofMeta* __restrict__ metas,
                                                    ProofCtx* __restrict__ ctxs, FlowArgs fa) {
-    static_assert(!FLOW || PHASE == 0, "the PoseidonFlow records are written by the unsplit kernel");
     RSV_TAG(1);
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const ProofMeta& m = metas[p];
-    if (PHASE == 1) {  // next to the parser, as k_transcript_row<1> below: its first checks, enough to read the fixed-offset part
-        const uint64_t o0 = offsets[p], o1 = offsets[p + 1];
-        if (o1 < o0 || ((o0 | o1) & 3) || (o1 - o0) > (1ull << 30) || ((o1 - o0) >> 2) < SAMPLES.end + 8) return;
-    } else if (m.reason != R_OK) return;
+    if (m.reason != R_OK) return;
     ProofCtx& c = ctxs[p];
     const uint32_t* w = reinterpret_cast<const uint32_t*>(blob + offsets[p]);
     Channel<PACE> ch;
@@ -45,7 +41,6 @@ __global__ __launch_bounds__(64) void k_transcript(const uint8_t* __restrict__ b
         over |= (v.a.a >= P) | (v.a.b >= P) | (v.b.a >= P) | (v.b.b >= P);
         return v;
     };
-    if (PHASE != 2) {
     ch.mix(load_hash_chk(w + W_COMMIT0, over));
     ch.mix_one(q_from_m(w[W_LP]));  // statement 0: data_structures/src/lib.rs:52-55 (== m.lp, m.lq once the parser has run)
     ch.mix_one(q_from_m(w[W_LQ]));
@@ -71,16 +66,6 @@ __global__ __launch_bounds__(64) void k_transcript(const uint8_t* __restrict__ b
         ch.mix_two(ldq_chk(w + SAMPLES.off[k]), ldq_chk(w + SAMPLES.off[k + 1]));
     d = ch.draw();
     stq(c.after, q_lo(d));
-    if (PHASE == 1) {  // hand the digest (and what the canonicity check found) to the back half
-        store_hash(c.pow_digest, ch.digest);
-        c.front_over = over;
-        return;
-    }
-    }  // PHASE != 2
-    if (PHASE == 2) {
-        ch.digest = load_hash(c.pow_digest);
-        over = c.front_over;
-    }
     ch.mix(load_hash_chk(w + m.first.commit_off, over));
     d = ch.draw();
     stq(c.fri_alpha[0], q_lo(d));

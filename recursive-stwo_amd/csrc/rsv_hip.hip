@@ -33,19 +33,17 @@ using namespace rsv;
 // rsv_ctx_set_option, on one context or (ctx == NULL) as the process default that contexts created later inherit.
 struct Options {
     int transcript_form = 0;   // 0 auto (by batch size), 1 row, 2 lane
-    int transcript_split = 0;  // 0 auto, 1 one launch, 2 front + back
+    int transcript_split = 0;  // row form: 0 auto, 1 one launch, 2 front + back
     int oods_form = 0, qconst_form = 0;  // 0 auto, 1 row, 2 lane
     int plan_form = 0;         // 0 / 1 one lane per (proof, query), 2 one lane per proof (the original)
     int tree_cap = 0;          // 0 / 1 dense top-of-tree cap, 2 every path walks to the root
     int overlap_trees = 0;     // 0 / 1 FRI trees beside the trace trees, 2 behind them
     long long ws_budget_mb = 8192;
     int perm_wg_per_cu = 24;
-    int perm_form = 0;         // experiment: instance / launch bound of k_permute (primitives.hpp)
     long long host_chunk_mb = 256;
     int host_threads = 0;      // 0 = min(cores, 4)
     int critical_chain = 0;    // 0 auto, 1 the chain of dependent kernels on ONE stream, 2 the round-2 stream layout
     int device_order = 0;      // 0 / 1 single-configuration batches: slot order on the device, no host round trip; 2 host
-    int graph = 0;             // 0 / 2 off, 1 replay repeated identical calls as a HIP graph (experiment)
     int witness_layout = 0;    // 0 / 1 d_variables [proof][variable], 2 [variable][proof]
     int flow_cap = 0;          // PoseidonFlow passes: 0 / 1 top-of-tree cap (shared nodes hashed once), 2 every lane walks to the root
     int query_form = 0;        // 0 auto (by batch size), 1 k_query with a row of 16 threads per query, 2 with one lane per query
@@ -53,8 +51,6 @@ struct Options {
     int tree_pace = 0;         // 0 auto (by batch size), 1 the tree kernels on the paced permutation instances, 2 on the unpaced ones, 3 in the row form (16 threads per path)
     int pair_order = 0;        // 0 / 1 the FRI trees of a small launch dealt out over the compute units, 2 grid row y = tree y
     int cap_mid = 0;           // 0 auto (buckets whose in-kernel cap levels fill their waves badly), 1 every bucket hands over at the cap level (k_cap_mid + k_cap_top), 2 none
-    int oods_early = 0;        // 0 / 2 the OODS check behind the trace trees (side stream), 1 (experiment) right behind the transcript on the aux stream
-    int tree_order = 0;        // 0 / 2 the tree kernels' grid row y = tree, 1 (measured, slower) their workgroups in the XCD-aware interleaved order
     int cap_top = 0;           // 0 auto (batches of >= 1 024 proofs), 1 the last levels of every tree in k_cap_top, 2 inside the Merkle kernels
     long long witness_small_max = 0;  // 0 default, else 1 + the largest batch that runs the program in one launch
     int witness_small_log = 0;        // 0 default, else 1 + log2(proofs per workgroup) of that form
@@ -80,8 +76,6 @@ void destroy_verify_state(VerifyState*);
 struct HostPipe;                          // pinned staging ring of rsv_verify_batch_host (host_stream.inc)
 void destroy_host_pipe(HostPipe*);
 }  // namespace
-struct GraphCache;                        // RSV_OPT_GRAPH (verify_api.inc)
-static void destroy_graph_cache(GraphCache*);
 
 struct rsv_ctx {
     int device = 0;
@@ -90,7 +84,7 @@ struct rsv_ctx {
     hipStream_t side = nullptr;  // row hashes, quotient constants, k_query, FRI trees: underneath the main stream
     hipStream_t aux = nullptr;   // the front half of a small batch's transcript, next to the parser
     hipEvent_t ev_begin = nullptr, ev_front = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_scan = nullptr, ev_plan = nullptr, ev_query = nullptr, ev_tr = nullptr, ev_ids = nullptr, ev_ext = nullptr, ev_oods = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_scan = nullptr, ev_plan = nullptr, ev_query = nullptr, ev_tr = nullptr, ev_ids = nullptr, ev_ext = nullptr;
     // reusable HBM workspace for rsv_verify_batch_dev
     void* ws = nullptr;        // per-query stages (plan, FRI leaf values)
     size_t ws_bytes = 0;
@@ -105,7 +99,6 @@ struct rsv_ctx {
     rsv_public_input* d_pi = nullptr;
     size_t d_pi_cap = 0;
     HostPipe* host_pipe = nullptr;
-    GraphCache* graphs = nullptr;
     Options opt;
 };
 
@@ -191,7 +184,6 @@ int rsv_ctx_create(int device, rsv_ctx** out) {
         hipEventCreateWithFlags(&c->ev_tr, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_ids, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_ext, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ev_oods, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming) != hipSuccess) {
         rsv_ctx_destroy(c);
         return RSV_E_DEVICE;
@@ -214,14 +206,12 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ev_ids) (void)hipEventDestroy(c->ev_ids);
     if (c->ev_query) (void)hipEventDestroy(c->ev_query);
     if (c->ev_ext) (void)hipEventDestroy(c->ev_ext);
-    if (c->ev_oods) (void)hipEventDestroy(c->ev_oods);
     if (c->side) (void)hipStreamDestroy(c->side);
     if (c->aux) (void)hipStreamDestroy(c->aux);
     if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->vs) destroy_verify_state(c->vs);
     if (c->host_pipe) destroy_host_pipe(c->host_pipe);
-    if (c->graphs) destroy_graph_cache(c->graphs);
     if (c->ws) (void)hipFree(c->ws);
     if (c->ws_fixed) (void)hipFree(c->ws_fixed);
     if (c->ws_rows) (void)hipFree(c->ws_rows);
@@ -257,7 +247,6 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_OVERLAP_TREES: return tri(&o.overlap_trees);
         case RSV_OPT_CRITICAL_CHAIN: return tri(&o.critical_chain);
         case RSV_OPT_DEVICE_ORDER: return tri(&o.device_order);
-        case RSV_OPT_GRAPH: return tri(&o.graph);
         case RSV_OPT_WITNESS_LAYOUT: return tri(&o.witness_layout);
         case RSV_OPT_CAP_TOP: return tri(&o.cap_top);
         case RSV_OPT_FLOW_CAP: return tri(&o.flow_cap);
@@ -266,8 +255,6 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_STAGE_TIMES: return tri(&o.stage_times);
         case RSV_OPT_QUERY_FORM: return tri(&o.query_form);
         case RSV_OPT_CAP_MID: return tri(&o.cap_mid);
-        case RSV_OPT_TREE_ORDER: return tri(&o.tree_order);
-        case RSV_OPT_OODS_EARLY: return tri(&o.oods_early);
         case RSV_OPT_WITNESS_WALK_LOG:
             if (value < 0 || value > 7) return RSV_E_RANGE;
             o.witness_walk_log = (int)value; return RSV_OK;
@@ -280,9 +267,6 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_WS_BUDGET_MB:
             if (value < 1 || value > (1ll << 20)) return RSV_E_RANGE;
             o.ws_budget_mb = value; return RSV_OK;
-        case RSV_OPT_PERM_FORM:
-            if (value < 0 || value > 2) return RSV_E_RANGE;
-            o.perm_form = (int)value; return RSV_OK;
         case RSV_OPT_PERM_WG_PER_CU:
             if (value < 1 || value > 32) return RSV_E_RANGE;
             o.perm_wg_per_cu = (int)value; return RSV_OK;
@@ -323,16 +307,8 @@ int rsv_poseidon2_permute_dev(rsv_ctx* c, const uint32_t* d_in, uint32_t* d_out,
     if (n > ((size_t)1 << 31)) return RSV_E_SIZE;
     if (((uintptr_t)d_in & 15) || ((uintptr_t)d_out & 15)) return RSV_E_SIZE;
     HIP_TRY(hipSetDevice(c->device));
-    {
-        const dim3 grid(permute_grid(n, c->opt.perm_wg_per_cu));
-        const uint4* pin = reinterpret_cast<const uint4*>(d_in);
-        uint4* pout = reinterpret_cast<uint4*>(d_out);
-        switch (c->opt.perm_form) {  // RSV_OPT_PERM_FORM: an experiment's knob
-            case 1: hipLaunchKernelGGL((k_permute<1, 1>), grid, dim3(256), 0, c->stream, pin, pout, n, d_bad); break;
-            case 2: hipLaunchKernelGGL((k_permute<2, 1>), grid, dim3(256), 0, c->stream, pin, pout, n, d_bad); break;
-            default: hipLaunchKernelGGL((k_permute<0, 1>), grid, dim3(256), 0, c->stream, pin, pout, n, d_bad); break;
-        }
-    }
+    hipLaunchKernelGGL(k_permute, dim3(permute_grid(n, c->opt.perm_wg_per_cu)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint4*>(d_in), reinterpret_cast<uint4*>(d_out), n, d_bad);
     HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
@@ -349,7 +325,7 @@ int rsv_poseidon2_permute(const uint32_t* in16, uint32_t* out16, size_t n, int d
     HIP_TRY(dbad.alloc(4));
     HIP_TRY(hipMemset(dbad.p, 0, 4));
     HIP_TRY(hipMemcpy(din.p, in16, 64 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL((k_permute<0, 1>), dim3(permute_grid(n, default_options().perm_wg_per_cu)), dim3(256), 0, 0, din.as<const uint4>(),
+    hipLaunchKernelGGL(k_permute, dim3(permute_grid(n, default_options().perm_wg_per_cu)), dim3(256), 0, 0, din.as<const uint4>(),
                        dout.as<uint4>(), n, dbad.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     uint32_t bad = 0;

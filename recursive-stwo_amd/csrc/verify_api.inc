@@ -150,7 +150,7 @@ static void launch_oods_probe(const uint32_t* d_prefix, uint32_t prefix_words, c
 
 static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                        const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept,
-                       uint8_t* d_reason, const PathsOut* po, bool capturing = false) {
+                       uint8_t* d_reason, const PathsOut* po) {
     if (!c) return RSV_E_NULL;
     CfgSet co;
     {
@@ -174,9 +174,9 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     // Stage clock: opt-in (RSV_OPT_STAGE_TIMES).  Two event records around a stage cost ~8 us of queue time EACH STAGE
     // (tools/chain_lab.hip: 5.3 us per dependent empty launch, 13.3 with the two records) — on a small batch's chain of
     // seven stages that was 4 % of the call, paid by every caller for a diagnostic only bench.py reads.
-    const bool timing = !capturing && opt.stage_times == 1;
+    const bool timing = opt.stage_times == 1;
     auto begin_on = [&](int stage, hipStream_t on) {
-        if (!timing) return;  // (and timing events are never recorded into a graph)
+        if (!timing) return;
         hipEvent_t b = vs->clock.next();
         if (b) (void)hipEventRecord(b, on);
         vs->spans.push_back({stage, b, nullptr});
@@ -200,8 +200,7 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         HIP_TRY(hipMalloc((void**)&c->d_pi, sizeof(rsv_public_input) * (n_pi + 16)));
         c->d_pi_cap = n_pi + 16;
     }
-    if (n_pi && !capturing) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
-    // (a captured call finds the public inputs of the capture's key already in c->d_pi: verify_graphed)
+    if (n_pi) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
     // rsv_hints_out::d_query_values: "absent groups and rejected proofs are zero" holds for the caller's buffer as it is
     if (po && po->d_count) HIP_TRY(hipMemsetAsync(po->d_count, 0, 8, st));
     if (po && po->d_qv)
@@ -241,13 +240,9 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     // Up to one wave per SIMD (4 096 proofs) the row form runs as two launches: the front half needs nothing from the
     // parser and starts next to it on the aux stream (k_transcript.hpp): 1 024 proofs 1.67 -> 1.63 ms, 4 096 2.89 -> 2.82;
     // at 8 192 it is a wash and beyond that the two halves and the parser get in each other's way (12 288: +12 %).
-    // RSV_OPT_TRANSCRIPT_SPLIT overrides (tests).
-    // The lane form (large batches) can be split the same way on request; measured at 65 536 proofs it changes nothing
-    // (35.46 vs 35.20 ms, inside run-to-run noise): the stretch up to the trees is bound by permutation throughput
-    // (transcript + row hashes = 3.7 ms of work in 3.9 ms), not by the chain, so moving 85 permutations under the parser
-    // only moves them.
-    bool split = row && N <= 4096 && !flow;  // the flow's records are written by the unsplit kernels
-    if (opt.transcript_split) split = !flow && opt.transcript_split == 2;
+    // RSV_OPT_TRANSCRIPT_SPLIT overrides (tests).  The lane form (large batches) always runs as one launch (split the same
+    // way, it measured 35.46 vs 35.20 ms at 65 536 proofs: inside run-to-run noise), and so does a pass that writes the flow.
+    const bool split = row && !flow && (opt.transcript_split ? opt.transcript_split == 2 : N <= 4096);
     // Split: the PARSER goes to the aux stream and the front half stays on the main stream, in front of the back half — the
     // parser (0.04-0.1 ms) is long over when the front half (0.16-0.19 ms) ends, so the back half's wait for it is a wait
     // for an event signalled long ago, and front -> back is a boundary inside one stream (~5 us) instead of a fresh
@@ -266,17 +261,12 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     // (and, for mixed batches, the shape words) travel back through the side stream while it runs.
     HIP_TRY(hipEventRecord(c->ev_fork, parse_on));
     if (split) {
-        if (row)
-            hipLaunchKernelGGL(k_transcript_row<1>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-        else
-            hipLaunchKernelGGL((k_transcript<false, 1>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
+        hipLaunchKernelGGL(k_transcript_row<1>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
         HIP_TRY(hipStreamWaitEvent(st, c->ev_fork, 0));  // everything behind this on the main stream may read the parser's tables
     }
     begin(1);
-    if (split && row)
+    if (split)
         hipLaunchKernelGGL(k_transcript_row<2>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else if (split)
-        hipLaunchKernelGGL((k_transcript<false, 2>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
     else if (row && flow)
         hipLaunchKernelGGL((k_transcript_row<0, true>), dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
     else if (row)
@@ -284,9 +274,9 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     else if (flow)
         hipLaunchKernelGGL(k_transcript<true>, dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
     else if (N <= 49152)  // (one wave per SIMD: the unpaced channel, k_transcript.hpp)
-        hipLaunchKernelGGL((k_transcript<false, 0, false>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
+        hipLaunchKernelGGL((k_transcript<false, false>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
     else
-        hipLaunchKernelGGL((k_transcript<false, 0, true>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
+        hipLaunchKernelGGL((k_transcript<false, true>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
     end();
     HIP_TRY(hipEventRecord(c->ev_tr, st));
     HIP_TRY(hipGetLastError());
@@ -328,7 +318,6 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         if (flow && tree_form == 0) tree_form = 1;  // (the FLOW instantiations: paced lane form and row form)
     }
     const bool small_trees = tree_form != 1;  // (the row hashes: lane forms only; they run underneath the transcript)
-    bool oods_aux_pending = false;  // the OODS check was enqueued on the aux stream: the verdict kernel waits for it
     if (sum[0] > 0) {
         // shape buckets: one launch geometry per distinct n_queries (host_logic.hpp)
         using rsv::host::Bucket;
@@ -467,16 +456,6 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         for (const std::vector<Entry>& grp : groups)
             for (const Entry& en : grp)
                 if (en.G > (uint32_t)kRowTreeBlock / 16u) query_row = false;
-        // RSV_OPT_OODS_EARLY = 1 (an experiment; measured and not taken): in the chain layout the OODS check — 256 registers a
-        // wave: it needs SIMDs the tree kernels have not filled — on the AUX stream right behind the transcript, the only thing it
-        // needs, instead of behind the trace trees.  It then competes with the plan, k_query and the first tree levels on the
-        // verdict's own chain: 2 048 proofs 1.70 -> 1.81 ms, 4 096: 2.63 -> 2.70, 8 192: 4.77 -> 4.74 (gpurun_out/r5_i/sweep.txt).
-        if (chain && !capturing && opt.oods_early == 1) {
-            HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_tr, 0));
-            launch_oods(c->aux);
-            HIP_TRY(hipEventRecord(c->ev_oods, c->aux));
-            oods_aux_pending = true;
-        }
         const bool qconst_in_plan = chain && !serial_plan && (opt.qconst_form ? opt.qconst_form == 1 : N <= 24576);
         if (qconst_in_plan) {
         } else if (chain) launch_qconst(st);
@@ -598,29 +577,20 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
             end();
             HIP_TRY(hipEventRecord(c->ev_plan, st));
             HIP_TRY(hipStreamWaitEvent(c->side, c->ev_plan, 0));
-            // Workgroup order of the tree kernels (k_plan.hpp: RSV_TREE_BLOCK).  RSV_OPT_TREE_ORDER = 1 (measured, NOT the default): the
-            // XCD-aware interleaved order fetches the plan tables once per L2 instead of once per tree — HBM traffic of the step
-            // 16.8 -> 15.1 GB (k_pair_merkle 6.35 -> 5.13, k_trace_merkle 3.25 -> 2.82) — and costs TIME: 65 536 standard proofs
-            // 34.1 -> 34.8 ms, the mixed chain 52.6 -> 62.3 (k_pair_merkle 38.7 -> 47.5: gpurun_out/r5_u).  The kernels are bound by
-            // instruction issue, not by bytes, and a level's dependent loads are served faster when a launch streams ONE tree's
-            // witnesses than when thirteen trees' are in flight at once.  Traffic is not what this step pays for: row y = tree stays.
-            const bool interleave = tree_form == 1 && !flow && !(po && po->paths()) && opt.tree_order == 1;
-            fm.interleave = interleave ? 1u : 0u;
-            const uint32_t grid_m = interleave ? (blocks_m + 7u) / 8u * 8u : blocks_m;
             const size_t pair_lds = ((po && po->d_pair_sib) || flow) ? (size_t)kBlock * 32 : 0;
             auto launch_pair = [&](hipStream_t on) {
                 if (flow && tree_form == 2) hipLaunchKernelGGL((k_pair_merkle<kRowTreeBlock, true, FORM_ROW>), dim3(blocks_m, 1 + max_inner), dim3(kRowTreeBlock), pair_lds, on, fm, fargs);
                 else if (flow) hipLaunchKernelGGL((k_pair_merkle<kBlock, true>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
                 else if (tree_form == 2) hipLaunchKernelGGL((k_pair_merkle<kRowTreeBlock, false, FORM_ROW>), dim3(blocks_m, 1 + max_inner), dim3(kRowTreeBlock), pair_lds, on, fm, fargs);
                 else if (tree_form == 0) hipLaunchKernelGGL((k_pair_merkle<kBlock, false, 0>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
-                else hipLaunchKernelGGL((k_pair_merkle<kBlock, false, 1>), dim3(grid_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
+                else hipLaunchKernelGGL((k_pair_merkle<kBlock, false, 1>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
             };
             auto launch_trace = [&](hipStream_t on) {
                 if (flow && tree_form == 2) hipLaunchKernelGGL((k_trace_merkle<kRowTreeBlock, true, FORM_ROW>), dim3(blocks_m, 4), dim3(kRowTreeBlock), 0, on, fm, fargs);
                 else if (flow) hipLaunchKernelGGL((k_trace_merkle<kBlock, true>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
                 else if (tree_form == 2) hipLaunchKernelGGL((k_trace_merkle<kRowTreeBlock, false, FORM_ROW>), dim3(blocks_m, 4), dim3(kRowTreeBlock), 0, on, fm, fargs);
                 else if (tree_form == 0) hipLaunchKernelGGL((k_trace_merkle<kBlock, false, 0>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
-                else hipLaunchKernelGGL((k_trace_merkle<kBlock, false, 1>), dim3(grid_m, 4), dim3(kBlock), 0, on, fm, fargs);
+                else hipLaunchKernelGGL((k_trace_merkle<kBlock, false, 1>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
             };
             // the last levels of the trees of a kernel, right behind it on its stream (stage 8)
             auto launch_top = [&](hipStream_t on, bool pair) {
@@ -696,7 +666,6 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         HIP_TRY(hipEventRecord(c->ev_scan, c->side));
     }
     if (sum[0] > 0) HIP_TRY(hipStreamWaitEvent(st, c->ev_scan, 0));
-    if (oods_aux_pending) HIP_TRY(hipStreamWaitEvent(st, c->ev_oods, 0));
     // verdicts (+ the canonicity fallback for proofs whose witness lists some stage found of the wrong length, + the
     // accept bitmap when the caller asked for it): ONE launch behind the Merkle stages
     begin(7);
@@ -731,89 +700,12 @@ struct DevCfgSet {
 };
 }  // namespace
 
-// RSV_OPT_GRAPH (experiment, off by default): a verify call that takes no host round trip (one configuration, no
-// per-query path output) is a fixed sequence of launches on three streams.  The second call with the SAME arguments
-// (buffers, sizes, configuration, public inputs, outputs: a caller that reuses its buffers batch after batch) is
-// captured into a HIP graph, the following ones replay it with one hipGraphLaunch.  Measured: see DESIGN §5.1.
-struct GraphKey {
-    const void *blob, *offsets, *accept, *reason;
-    size_t n, n_pi;
-    uint32_t cfg[4];
-    PathsOut po;
-    bool has_po;
-    unsigned long long pi_hash;
-    Options opt;
-};
-struct GraphCache {
-    GraphKey key{};
-    int seen = 0;  // calls with this key so far
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    void drop() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr; graph = nullptr; seen = 0;
-    }
-};
-static void destroy_graph_cache(GraphCache* g) { if (g) { g->drop(); delete g; } }
-
-static int verify_graphed(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
-                          const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept, uint8_t* d_reason, const PathsOut* po) {
-    const bool eligible = c && c->opt.graph == 1 && cfg && cfg->cfgs && cfg->n_cfgs == 1 && !cfg->cfg_of && n > 0 && !(po && po->paths()) &&
-                          c->opt.device_order != 2 && n_pi <= 64;
-    if (!eligible) return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    GraphKey k;
-    memset(&k, 0, sizeof k);
-    k.blob = d_blob; k.offsets = d_offsets; k.accept = d_accept; k.reason = d_reason; k.n = n; k.n_pi = n_pi;
-    k.cfg[0] = cfg->cfgs[0].pow_bits; k.cfg[1] = cfg->cfgs[0].log_blowup_factor;
-    k.cfg[2] = cfg->cfgs[0].log_last_layer_degree_bound; k.cfg[3] = cfg->cfgs[0].n_queries;
-    if (po) { memcpy(&k.po, po, sizeof(PathsOut)); k.has_po = true; }
-    unsigned long long h = 1469598103934665603ull;
-    for (size_t i = 0; i < n_pi * sizeof(rsv_public_input); i++) h = (h ^ reinterpret_cast<const uint8_t*>(pi)[i]) * 1099511628211ull;
-    k.pi_hash = h;
-    memcpy(&k.opt, &c->opt, sizeof(Options));
-    if (!c->graphs) c->graphs = new (std::nothrow) GraphCache();
-    GraphCache* g = c->graphs;
-    if (!g) return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    if (memcmp(&g->key, &k, sizeof k) != 0) { g->drop(); g->key = k; }
-    g->seen++;
-    if (g->exec) {
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipGraphLaunch(g->exec, c->stream));
-        return RSV_OK;
-    }
-    if (g->seen < 2)  // first sighting: the plain path (it also grows the workspaces and uploads the public inputs)
-        return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    HIP_TRY(hipSetDevice(c->device));
-    // the public inputs of this key are in c->d_pi since the first sighting, and stay: the key pins their hash
-    if (hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal) != hipSuccess)
-        return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    int rc = verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po, true);
-    hipGraph_t graph = nullptr;
-    const hipError_t e = hipStreamEndCapture(c->stream, &graph);
-    if (rc != RSV_OK || e != hipSuccess || !graph) {
-        if (graph) (void)hipGraphDestroy(graph);
-        g->drop();
-        g->seen = -1000000;  // never again for this key
-        return rc != RSV_OK ? rc : verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    }
-    if (hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-        (void)hipGraphDestroy(graph);
-        g->exec = nullptr;
-        g->seen = -1000000;
-        return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, po);
-    }
-    g->graph = graph;
-    HIP_TRY(hipGraphLaunch(g->exec, c->stream));
-    return RSV_OK;
-}
-
 extern "C" {
 
 int rsv_verify_batch_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept,
                          uint8_t* d_reason) {
-    return verify_graphed(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, nullptr);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, nullptr);
 }
 
 int rsv_trace_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
@@ -886,7 +778,7 @@ int rsv_verify_hints_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_of
     if (po.paths() && (po.n_queries < 4 || po.n_queries > (uint32_t)MAXQ || po.max_log > (uint32_t)MAX_LOG ||
                        po.n_inner > (uint32_t)MAX_INNER))
         return RSV_E_SIZE;
-    return verify_graphed(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, &po);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, &po);
 }
 
 int rsv_verify_hints(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,

@@ -65,14 +65,20 @@ def test_argument_validation(rsv):
     assert rsv.lib.rsv_ctx_create(0, None) == -1
 
 
-def test_options_are_explicit_and_validated(rsv):
+def test_options_are_explicit_validated_and_retired_ids_refused(rsv):
     """The library reads no environment variable: every knob goes through rsv_ctx_set_option (ctx = NULL: process
-    default), unknown options and out-of-range values are refused — no device needed for any of this."""
+    default), unknown options and out-of-range values are refused, and so are the ids of the retired knobs (15, 27, 28,
+    29: include/rsv.h) — no device needed for any of this."""
     lib = rsv.lib
     assert lib.rsv_ctx_set_option(None, 999, 1) == -2          # RSV_E_SIZE: unknown option
     assert lib.rsv_ctx_set_option(None, 0, 1) == -2
+    for retired in (15, 27, 28, 29):                            # removed knobs: their ids are unknown options now
+        for v in (0, 1, 2):
+            assert lib.rsv_ctx_set_option(None, retired, v) == -2, retired
+    assert not {"graph", "perm_form", "oods_early", "tree_order"} & set(rsv.OPTIONS)
+    assert not {15, 27, 28, 29} & set(rsv.OPTIONS.values())
     for name in ("transcript_form", "transcript_split", "oods_form", "qconst_form", "plan_form", "tree_cap", "overlap_trees",
-                 "critical_chain", "device_order", "graph", "witness_layout", "cap_top", "flow_cap", "pair_order", "stage_times", "query_form", "cap_mid", "oods_early", "tree_order"):
+                 "critical_chain", "device_order", "witness_layout", "cap_top", "flow_cap", "pair_order", "stage_times", "query_form", "cap_mid"):
         assert lib.rsv_ctx_set_option(None, rsv.OPTIONS[name], 3) == -5, name   # RSV_E_RANGE
         assert lib.rsv_ctx_set_option(None, rsv.OPTIONS[name], -1) == -5, name
         for v in (2, 1, 0):

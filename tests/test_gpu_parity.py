@@ -680,11 +680,10 @@ def test_canonicity_is_checked_where_words_are_read(rsv):
         assert (int(a1[0]), int(r1[0])) == (int(oa), int(orr))
 
 
-@pytest.mark.parametrize("form", ["row", "lane"])
-@pytest.mark.parametrize("split", ["whole", "split"])
+@pytest.mark.parametrize("split, form", [("whole", "row"), ("whole", "lane"), ("split", "row")])
 def test_transcript_in_one_piece_and_split(rsv, knobs, split, form):
-    """Either transcript form as one launch and as front (next to the parser, before any section offset is known) +
-    back: the same verdicts, reasons and transcript rows, also for buffers the front half has to leave alone
+    """Either transcript form as one launch, and the row form as front (next to the parser, before any section offset is
+    known) + back: the same verdicts, reasons and transcript rows, also for buffers the front half has to leave alone
     (empty, truncated inside the fixed-offset part, cut right behind it, misaligned length), and a non-canonical word
     in the front's part of the proof, whose finding travels to the back half."""
     knobs.set("transcript_form", form)
@@ -1312,17 +1311,14 @@ def test_many_distinct_query_counts_in_one_batch(rsv):
     ctx.close()
 
 
-@pytest.mark.parametrize("order", [1, 2])
 @pytest.mark.parametrize("top", ["on", "off"])
-def test_tree_workgroup_orders_match_oracle(rsv, knobs, order, top):
-    """The two workgroup orders of the lane-form tree kernels (RSV_OPT_TREE_ORDER: tree by tree — what production runs — or the
-    trees of a workgroup of proofs side by side on one XCD: less HBM traffic, more time), forced on a mixed batch of every chain shape
-    (several buckets in one launch, grid x padded to a multiple of 8, a ragged last workgroup) and on one configuration per
-    call; tampered copies among them.  Verdicts and reasons == the oracle's."""
+def test_paced_lane_tree_kernels_match_oracle(rsv, knobs, top):
+    """The paced lane form of the tree kernels (what production runs on large batches), forced on a mixed batch of every
+    chain shape (several buckets in one launch, a ragged last workgroup) and on one configuration per call; tampered copies
+    among them.  Verdicts and reasons == the oracle's."""
     names = ["level1-5.bin", "level2-1.bin", "level3-1.bin", "level4-5.bin", "level5-1.bin", "level6-1.bin", "level7-1.bin",
              "level8-1.bin", "level9-1.bin", "level10-1.bin", "level11-1.bin", "level12-1.bin", "level13-1.bin"]
     knobs.set("tree_pace", "paced")
-    knobs.set("tree_order", order)
     knobs.set("cap_top", top)
     batch, cfgs = [], []
     for k in range(13 * 9 + 4):
@@ -1548,36 +1544,3 @@ def test_slot_order_on_the_device_and_on_the_host(rsv, knobs, order):
     oacc, oreason = ob.verify_batch(batch, cfg)
     assert acc.tolist() == oacc.tolist() and reason.tolist() == oreason.tolist()
     assert int(acc.sum()) > 400 and acc[-1] == 1 and 1 in reason.tolist() and 2 in reason.tolist()
-
-
-def test_graph_replay_of_repeated_calls(rsv):
-    """RSV_OPT_GRAPH (experiment): a call repeated with identical arguments is captured into a HIP graph on its second
-    sighting and replayed afterwards.  The replay reads the buffers as they are THEN: the blob is tampered in place
-    between calls and the verdicts must follow; a call with other arguments drops the graph."""
-    import torch
-    dev = torch.device("cuda:0")
-    proof = read_proof("recursive_proof_16_15.bin")
-    n = 1500
-    blob, offsets = rsv.pack([proof] * n)
-    d_blob = torch.from_numpy(blob.copy()).to(dev)
-    d_off = torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
-    d_reason = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ctx = rsv.Context(0)
-    ctx.set_option("graph", "on")
-    cfg = rsv.PreparedCfg([fixture_cfg("recursive_proof_16_15.bin")])
-    want = np.ones(n, np.uint8)
-    for rep in range(6):
-        if rep >= 2:  # tamper one more proof in place: plain call, capture, replays all see the bytes of the moment
-            k = 100 * rep + 7
-            d_blob[int(offsets[k]) + 5000] ^= 1
-            want[k] = 0
-        d_acc.fill_(9)
-        ctx.verify_batch(d_blob, d_off, n, d_acc, d_reason, cfg=cfg)
-        ctx.synchronize()
-        assert np.array_equal(d_acc.cpu().numpy(), want), rep
-    d_acc2 = torch.zeros(n - 1, dtype=torch.uint8, device=dev)  # other arguments: the cached graph is dropped
-    ctx.verify_batch(d_blob, d_off, n - 1, d_acc2, None, cfg=cfg)
-    ctx.synchronize()
-    assert np.array_equal(d_acc2.cpu().numpy(), want[:n - 1])
-    ctx.close()
