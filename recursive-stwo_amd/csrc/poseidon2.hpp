@@ -232,16 +232,21 @@ struct PermT {
     }
 
     // Round constant + canonicalisation in one step.  t = fold2(V) with V the doubled accumulator of a linear layer
-    // WITHOUT its round constant: t <= P + HI where HI bounds the accumulator's high word (160 after a full-round
-    // layer, < 2^19 after a partial-round one).  With c = P - rc (a compile-time literal):
-    //     t >= c :  t - c in [0, P - 1]  (needs c > HI; every constant of this parameter set is < P - 2^19, asserted below)
+    // WITHOUT its round constant: t <= P + HI where HI bounds the accumulator's high word at the call site (HI_FULL after a
+    // full-round layer, HI_PARTIAL after a partial round or pair).  With c = P - rc (a compile-time literal):
+    //     t >= c :  t - c in [0, P - 1]  (needs c > HI: asserted per call site below)
     //               and t - c + P in [P, 2P - 1]: the minimum is t - c  = t + rc - P
     //     t <  c :  t - c wraps to >= 2^32 - P > 2^31 and t - c + P = t + rc in [0, P - 1]: the minimum is t + rc
     // so min(t - c, t - c + P) is the CANONICAL t + rc mod P in two literal adds (fast class, 2.5 cycles each) and a
     // v_min — against v_mad_u64_u32 (2 * rc folded into V, 5.1) + a literal add + v_min for the unfused form.
-    template <uint32_t RC>
+    // The high words that reach canon_rc (tests/test_partial_pairs.py proves both over the whole schedule):
+    //   HI_FULL    the fold of a full-round layer: the rows of circ(2M4, M4, M4, M4) sum to at most 80, so V < 160 * 2^32;
+    //   HI_PARTIAL word 0 after a single partial round or a pair (at most 165 492), and every word after a single round (at
+    //              most 65 561): V < 2^50 with a small addend.
+    static constexpr uint32_t HI_FULL = 160, HI_PARTIAL = 1u << 18;
+    template <uint32_t RC, uint32_t HI>
     static __device__ __forceinline__ uint32_t canon_rc(uint32_t t) {
-        static_assert(RC < P - (1u << 19), "round constant too close to P for the fused reduction");
+        static_assert(HI < P - RC, "round constant too close to P for the fused reduction");
         constexpr uint32_t c = P - RC;
         uint32_t r = min(t - c, t + (P - c));
         if constexpr (PACE) asm volatile("s_nop 0" : "+v"(r));
@@ -250,19 +255,20 @@ struct PermT {
 
     template <int R, int I>
     static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s) {
-        s[I] = pow5(canon_rc<RC_FULL_K[R][I]>(fold2(V[I])));
+        s[I] = pow5(canon_rc<RC_FULL_K[R][I], HI_FULL>(fold2(V[I])));
         if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s);
     }
-    // the first full round of the second half takes its inputs already folded (from the last partial round)
+    // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
     static __device__ __forceinline__ void sbox_full4(uint32_t* s) {
-        s[I] = pow5(canon_rc<RC_FULL_K[4][I]>(s[I]));
+        s[I] = pow5(canon_rc<RC_FULL_K[4][I], HI_PARTIAL>(s[I]));
         if constexpr (I + 1 < 16) sbox_full4<I + 1>(s);
     }
 
+    // Inputs: any u32 words, s[0] <= P + HI_PARTIAL.
     template <int R>
     static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd) {
-        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R]>(s[0]));                 // s[0] <= P + 2^19
+        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]));
         // sum2 = 2 * (u0 + s[1] + ... + s[15]) < 2^37, two chains
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
@@ -272,6 +278,37 @@ struct PermT {
         s[0] = fold2(mad64(u0, k6, sum2));
     #pragma unroll
         for (int i = 1; i < 16; i++) s[i] = fold2(mad64(s[i], kd[i], sum2));
+    }
+
+    // Partial rounds R and R + 1 in one pass.  With S = u0 + s_1 + ... + s_15 the sum of round R and d_i = 2^(i+1), round
+    // R's words are s_i' = d_i s_i + S, and only word 0 of them is needed on its own (the next S-box input).  Round R + 1
+    // takes the rest straight from round R's inputs:
+    //     S'     = u0' + sum_i s_i' = u0' + sum_i d_i s_i + 15 S
+    //     s_i''  = d_i s_i' + S'    = (d_i^2 mod P) s_i + d_i S + S'
+    // so a word costs two multiply-accumulates and ONE fold over the pair instead of two and two.  kq[i] = 2 (d_i^2 mod P)
+    // = 2^((2i + 2) mod 31 + 1), k30 = 2 * 15.  Inputs: any u32 words with s[0] <= P + HI_PARTIAL and s_14 < 2^32 - 2^24
+    // (its multiplier is 2^31); tests/test_partial_pairs.py proves the bounds over the schedule.
+    template <int R>
+    static __device__ __forceinline__ void partial_pair(uint32_t* s, uint32_t k2, uint32_t k6, uint32_t k30, const uint32_t* kd,
+                                                        const uint32_t* kq) {
+        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]));
+        uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
+    #pragma unroll
+        for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
+        uint64_t sum2 = add64(a, b);                                          // 2S < 2^37
+        const uint32_t s0 = fold2(mad64(u0, k6, sum2));                       // round R's word 0, <= P + 2^6
+        const uint32_t sf = fold2(sum2);                                      // S, <= P + 2^5
+        u0 = pow5(canon_rc<RC_PARTIAL_K[R + 1], HI_PARTIAL>(s0));
+        // sum2 = 2S' = 2 u0' + sum_i 2 d_i s_i + 30 S < 2^50 + 2^37, two chains
+        a = mul64(u0, k2, 0); b = mul64(s[1], kd[1], 0);
+    #pragma unroll
+        for (int i = 2; i < 16; i += 2) { a = mad64(s[i], kd[i], a); b = mad64(s[i + 1], kd[i + 1], b); }
+        a = mad64(sf, k30, a);
+        sum2 = add64(a, b);
+        s[0] = fold2(mad64(u0, k6, sum2));                                    // <= P + HI_PARTIAL
+        // 2 s_i'' < 2^63 (the largest term: 2^31 s_14), so the fold is exact
+    #pragma unroll
+        for (int i = 1; i < 16; i++) s[i] = fold2(mad64(s[i], kq[i], mad64(sf, kd[i], sum2)));
     }
 
     // Everything up to and including the S-box layer of the last full round: s = that layer's outputs (range L2).
@@ -284,7 +321,8 @@ struct PermT {
         sbox_full<1, 0>(V, s); mds16_2x(k2, k4, s, V);
         sbox_full<2, 0>(V, s); mds16_2x(k2, k4, s, V);
         sbox_full<3, 0>(V, s); mds16_2x(k2, k4, s, V);
-        // partial rounds: every lane lazily folded (<= P + 2^18), lane 0 goes through the S-box
+        // partial rounds: every lane lazily folded (any u32 inside the pairs, <= P + 2^18 after a single round), lane 0 goes
+        // through the S-box
     #pragma unroll
         for (int i = 0; i < 16; i++) s[i] = fold2(V[i]);
         // 2 * diag: 2^(i+2) for lanes 1..15, as opaque wave-uniform multipliers
@@ -294,11 +332,22 @@ struct PermT {
         RSV_KD(1) RSV_KD(2) RSV_KD(3) RSV_KD(4) RSV_KD(5) RSV_KD(6) RSV_KD(7) RSV_KD(8)
         RSV_KD(9) RSV_KD(10) RSV_KD(11) RSV_KD(12) RSV_KD(13) RSV_KD(14) RSV_KD(15)
     #undef RSV_KD
-        partial_round<0>(s, k2, k6, kd);  partial_round<1>(s, k2, k6, kd);  partial_round<2>(s, k2, k6, kd);
-        partial_round<3>(s, k2, k6, kd);  partial_round<4>(s, k2, k6, kd);  partial_round<5>(s, k2, k6, kd);
-        partial_round<6>(s, k2, k6, kd);  partial_round<7>(s, k2, k6, kd);  partial_round<8>(s, k2, k6, kd);
-        partial_round<9>(s, k2, k6, kd);  partial_round<10>(s, k2, k6, kd); partial_round<11>(s, k2, k6, kd);
-        partial_round<12>(s, k2, k6, kd); partial_round<13>(s, k2, k6, kd);
+        // 2 (d_i^2 mod P) = 2^(2i + 3) for lanes 1..14 (= kd[2i + 1] up to lane 7), 4 for lane 15
+        uint32_t kq[16];
+        kq[0] = 0;
+    #pragma unroll
+        for (int i = 1; i < 8; i++) kq[i] = kd[2 * i + 1];
+    #define RSV_KQ(i) kq[i] = opaque(8u << (2 * (i)));
+        RSV_KQ(8) RSV_KQ(9) RSV_KQ(10) RSV_KQ(11) RSV_KQ(12) RSV_KQ(13) RSV_KQ(14)
+    #undef RSV_KQ
+        kq[15] = k4;
+        const uint32_t k30 = opaque(30);
+        // 14 = 1 + 6 x 2 + 1.  The last round must be a single one: the pairs leave word 14 near 2^32 and word 13 above 2^31
+        // (multipliers 2^31 and 2^29); a single round brings every word back to <= P + 2^18, within what sbox_full4 takes
+        partial_round<0>(s, k2, k6, kd);
+        partial_pair<1>(s, k2, k6, k30, kd, kq);  partial_pair<3>(s, k2, k6, k30, kd, kq);  partial_pair<5>(s, k2, k6, k30, kd, kq);
+        partial_pair<7>(s, k2, k6, k30, kd, kq);  partial_pair<9>(s, k2, k6, k30, kd, kq);  partial_pair<11>(s, k2, k6, k30, kd, kq);
+        partial_round<13>(s, k2, k6, kd);
         sbox_full4<0>(s);      mds16_2x(k2, k4, s, V);
         sbox_full<5, 0>(V, s); mds16_2x(k2, k4, s, V);
         sbox_full<6, 0>(V, s); mds16_2x(k2, k4, s, V);

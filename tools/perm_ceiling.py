@@ -10,19 +10,25 @@ Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 perm
   full-round linear layer mds16_2x (9 of them; none carries round constants: they are literals of the S-box reduction)
       per 4-word group 2 mad (no addend) + 4 mad (addend) + 2 lshl_add_u64 + 2 lshl_add_u64 (plain adds)        = 40
       column sums 12 + 16 lshl_add_u64                                                                          = 28
-  partial round (14): 2 mad (no addend) + 14 + 1 + 15 mad (addend) + 1 lshl_add_u64, 16 fold2 = 32 fast
+  partial rounds (14 = single 0, pairs (1,2) .. (11,12), single 13; a pair forms round R + 1's words straight from
+  round R's inputs, so 15 words are folded once per pair instead of twice)
+      single: 2 mad (no addend) + 14 + 1 + 15 mad (addend) + 1 lshl_add_u64, 16 fold2 = 32 fast
+      pair:   4 mad (no addend) + 28 + 2 + 1 + 30 mad (addend) + 2 lshl_add_u64, 18 fold2 = 36 fast
+              (against two singles: -28 fast, +1 mad with addend — the round's sum S folded once and added as 30 S)
   output: 16 x (lshr, add, add-literal, min)
 
   class                      count   cycles/instr at 4 waves/SIMD, expressed at 2.4 GHz (tools/valu_lab.hip, measured r2)
-  fast  (add/sub/lshr/and)    2456   2.50     (a 32-bit literal operand does not change the class: 2.52)
+  fast  (add/sub/lshr/and)    2288   2.50     (a 32-bit literal operand does not change the class: 2.52)
   v_min_u32                    442   4.27
   v_mad_u64_u32, no addend     526   4.54
   v_lshl_add_u64               410   4.48
-  v_mad_u64_u32, with addend   564   5.10     (SGPR multiplier or live 64-bit addend: 5.05-5.15)
-  total                       4398            = the static count: the function is straight-line code since the constants
-                                              became literals (before: 4 428 with 736 addend-mads, 15 650 cycles, 10.05 G/s)
+  v_mad_u64_u32, with addend   570   5.10     (SGPR multiplier or live 64-bit addend: 5.05-5.15)
+  total                       4236            = the static count: the function is straight-line code since the constants
+                                              became literals (before: 4 428 with 736 addend-mads, 15 650 cycles, 10.05 G/s;
+                                              before the paired partial rounds: 4 398, 2 456 fast and 564 addend-mads,
+                                              15 129 cycles, 10.40 G/s)
 
-=> 15 129 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 15 129 x 64 = 10.40 G permutations/s.
+=> 14 739 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 14 739 x 64 = 10.67 G permutations/s.
 (The lab's "cycles at 2.4 GHz" are wall time x 2.4 GHz.  Round 5 separated clock from issue cost (tools/valu_clock.sh,
 profiles/r5_valu_lab_*): under the lab's dense VALU load GRBM_GUI_ACTIVE holds 2.35-2.40 GHz — v_and_b32 at 4 waves per
 SIMD: 2.242 ms at 2.383 GHz for 2 097 152 wave-instructions per SIMD = 2.55 REAL cycles each — so the fast class's 2.5
@@ -36,8 +42,8 @@ import collections
 import re
 import sys
 
-MIX = [("fast", 2456, 2.50), ("v_min_u32", 442, 4.27), ("v_mad_u64_u32 (no addend)", 526, 4.54),
-       ("v_lshl_add_u64", 410, 4.48), ("v_mad_u64_u32 (addend)", 564, 5.10)]
+MIX = [("fast", 2288, 2.50), ("v_min_u32", 442, 4.27), ("v_mad_u64_u32 (no addend)", 526, 4.54),
+       ("v_lshl_add_u64", 410, 4.48), ("v_mad_u64_u32 (addend)", 570, 5.10)]
 SIMDS, LAB_GHZ = 1024, 2.4
 
 
