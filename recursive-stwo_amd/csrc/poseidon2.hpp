@@ -113,6 +113,7 @@ __device__ __forceinline__ void poseidon2_ref_inline(uint32_t* s) {
 //   ~4.3-4.6    : v_min_u32 v_lshlrev_b32 v_alignbit_b32 v_and_or_b32 v_mul_lo/hi_u32 v_lshl_add_u64
 //                 v_mad_u64_u32 (4.55; 5.05 with a live 64-bit addend)   -- the 32x32->64 multiply is
 //                 NOT quarter rate on gfx950, so the cost of a modular multiply is its reduction.
+//                 v_mad_i64_i32 without an addend 4.34, v_mad_u64_u32 with an SGPR-pair addend 4.48 (pow5)
 // Consequences used below:
 //   * linear layers accumulate UNREDUCED in 64 bits (one v_lshl_add_u64 / v_mad_u64_u32 per term,
 //     shifts by 1..4 and small multipliers are free), and are folded once per round;
@@ -157,6 +158,11 @@ struct PermT {
         asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "n"(k));
         return r;
     }
+    // the same for a 64-bit constant, in an SGPR pair (the S-box's addend: see pow5)
+    static __device__ __forceinline__ uint64_t opaque64(uint64_t k) {
+        return (uint64_t)opaque((uint32_t)(k >> 32)) << 32 | opaque((uint32_t)k);
+    }
+    static constexpr uint64_t KP = 0 - ((uint64_t)P << 32);  // 2^64 - P * 2^32
     // The asm form (instead of `(uint64_t)a * b + c`) also keeps hipcc from re-associating
     // x0*k + x1*k into (x0 + x1)*k, which costs a 64-bit add, a 64x32 multiply and zero-extension moves.
     static __device__ __forceinline__ uint64_t mul64(uint32_t a, uint32_t b) {
@@ -177,6 +183,19 @@ struct PermT {
         else asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "s"(b_uniform), "v"(c));
         return d;
     }
+    static __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c_uniform, int) {  // a * b + c, c in an SGPR pair
+        uint64_t d, carry;
+        if constexpr (PACE) asm("v_mad_u64_u32 %0, %1, %2, %3, %4\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
+        else asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
+        return d;
+    }
+    // signed 32x32 -> 64 square (v_mad_i64_i32): |a| <= P gives a^2 <= P^2 < 2^62
+    static __device__ __forceinline__ uint64_t sqr64s(int32_t a) {
+        uint64_t d, carry;
+        if constexpr (PACE) asm("v_mad_i64_i32 %0, %1, %2, %2, 0\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a));
+        else asm("v_mad_i64_i32 %0, %1, %2, %2, 0" : "=v"(d), "=s"(carry) : "v"(a));
+        return d;
+    }
     static __device__ __forceinline__ uint32_t dbl32(uint32_t x) {  // x + x as a fast-class add (not a shift)
         uint32_t d;
         asm("v_add_u32 %0, %1, %1" : "=v"(d) : "v"(x));
@@ -194,11 +213,17 @@ struct PermT {
         return r;
     }
 
-    // x in C  ->  x^5 in L2
-    static __device__ __forceinline__ uint32_t pow5(uint32_t x) {
+    // x in C  ->  x^5 in L2.  x^2 is squared in SIGNED form instead of being canonicalised and doubled: with the addend
+    // kp = 2^64 - P * 2^32 (an SGPR pair, see opaque64()) the first product is 2x^2 - P * 2^32 mod 2^64 (the carry-out is
+    // dropped), so its fold is t1 - P with t1 = fold2(2x^2) in [0, 2P - 1]: s1 in [-P, P - 1], congruent to x^2.  Then
+    // s1^2 <= P^2 < 2^62 is folded undoubled.  13 instructions instead of 15 (one v_min and one fast-class doubling fewer);
+    // tests/test_sbox_signed_square.py proves the ranges at their extremes.
+    static __device__ __forceinline__ uint32_t pow5(uint32_t x, uint64_t kp) {
         const uint32_t xx = dbl32(x);                         // 2x <= 2P, used by the first and the last product
-        uint32_t c2 = canon(fold2(mul64(xx, x)));             // 2x^2 < 2^63; fold <= 2P-1
-        uint32_t c4 = canon(fold2(mul64(dbl32(c2), c2)));
+        const int32_t s1 = (int32_t)fold2(mad64(xx, x, kp, 0));  // 2x^2 < 2^63; t1 - P in [-P, P - 1]
+        const uint64_t V2 = sqr64s(s1);                       // [0, P^2]
+        // (V2 >> 31) + (V2 & P) <= (P - 1) + P
+        const uint32_t c4 = canon(__builtin_amdgcn_alignbit((uint32_t)(V2 >> 32), (uint32_t)V2, 31) + ((uint32_t)V2 & P));
         return fold2(mul64(xx, c4));                          // 2x*c4: hi <= P, lo>>1 <= P
     }
 
@@ -254,21 +279,21 @@ struct PermT {
     }
 
     template <int R, int I>
-    static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s) {
-        s[I] = pow5(canon_rc<RC_FULL_K[R][I], HI_FULL>(fold2(V[I])));
-        if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s);
+    static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, uint64_t kp) {
+        s[I] = pow5(canon_rc<RC_FULL_K[R][I], HI_FULL>(fold2(V[I])), kp);
+        if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, kp);
     }
     // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
-    static __device__ __forceinline__ void sbox_full4(uint32_t* s) {
-        s[I] = pow5(canon_rc<RC_FULL_K[4][I], HI_PARTIAL>(s[I]));
-        if constexpr (I + 1 < 16) sbox_full4<I + 1>(s);
+    static __device__ __forceinline__ void sbox_full4(uint32_t* s, uint64_t kp) {
+        s[I] = pow5(canon_rc<RC_FULL_K[4][I], HI_PARTIAL>(s[I]), kp);
+        if constexpr (I + 1 < 16) sbox_full4<I + 1>(s, kp);
     }
 
     // Inputs: any u32 words, s[0] <= P + HI_PARTIAL.
     template <int R>
-    static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd) {
-        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]));
+    static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd, uint64_t kp) {
+        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]), kp);
         // sum2 = 2 * (u0 + s[1] + ... + s[15]) < 2^37, two chains
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
@@ -290,15 +315,15 @@ struct PermT {
     // (its multiplier is 2^31); tests/test_partial_pairs.py proves the bounds over the schedule.
     template <int R>
     static __device__ __forceinline__ void partial_pair(uint32_t* s, uint32_t k2, uint32_t k6, uint32_t k30, const uint32_t* kd,
-                                                        const uint32_t* kq) {
-        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]));
+                                                        const uint32_t* kq, uint64_t kp) {
+        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]), kp);
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
         uint64_t sum2 = add64(a, b);                                          // 2S < 2^37
         const uint32_t s0 = fold2(mad64(u0, k6, sum2));                       // round R's word 0, <= P + 2^6
         const uint32_t sf = fold2(sum2);                                      // S, <= P + 2^5
-        u0 = pow5(canon_rc<RC_PARTIAL_K[R + 1], HI_PARTIAL>(s0));
+        u0 = pow5(canon_rc<RC_PARTIAL_K[R + 1], HI_PARTIAL>(s0), kp);
         // sum2 = 2S' = 2 u0' + sum_i 2 d_i s_i + 30 S < 2^50 + 2^37, two chains
         a = mul64(u0, k2, 0); b = mul64(s[1], kd[1], 0);
     #pragma unroll
@@ -315,12 +340,13 @@ struct PermT {
     static __device__ __forceinline__ void poseidon2_rounds(uint32_t* s, uint32_t k2, uint32_t k4) {
         uint64_t V[16];
         const uint32_t k6 = opaque(6);
+        const uint64_t kp = opaque64(KP);
         // s: canonical input.  V never carries a round constant: the constants are literals of the fused reductions.
         mds16_2x(k2, k4, s, V);
-        sbox_full<0, 0>(V, s); mds16_2x(k2, k4, s, V);
-        sbox_full<1, 0>(V, s); mds16_2x(k2, k4, s, V);
-        sbox_full<2, 0>(V, s); mds16_2x(k2, k4, s, V);
-        sbox_full<3, 0>(V, s); mds16_2x(k2, k4, s, V);
+        sbox_full<0, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<1, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<2, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<3, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
         // partial rounds: every lane lazily folded (any u32 inside the pairs, <= P + 2^18 after a single round), lane 0 goes
         // through the S-box
     #pragma unroll
@@ -344,14 +370,14 @@ struct PermT {
         const uint32_t k30 = opaque(30);
         // 14 = 1 + 6 x 2 + 1.  The last round must be a single one: the pairs leave word 14 near 2^32 and word 13 above 2^31
         // (multipliers 2^31 and 2^29); a single round brings every word back to <= P + 2^18, within what sbox_full4 takes
-        partial_round<0>(s, k2, k6, kd);
-        partial_pair<1>(s, k2, k6, k30, kd, kq);  partial_pair<3>(s, k2, k6, k30, kd, kq);  partial_pair<5>(s, k2, k6, k30, kd, kq);
-        partial_pair<7>(s, k2, k6, k30, kd, kq);  partial_pair<9>(s, k2, k6, k30, kd, kq);  partial_pair<11>(s, k2, k6, k30, kd, kq);
-        partial_round<13>(s, k2, k6, kd);
-        sbox_full4<0>(s);      mds16_2x(k2, k4, s, V);
-        sbox_full<5, 0>(V, s); mds16_2x(k2, k4, s, V);
-        sbox_full<6, 0>(V, s); mds16_2x(k2, k4, s, V);
-        sbox_full<7, 0>(V, s);
+        partial_round<0>(s, k2, k6, kd, kp);
+        partial_pair<1>(s, k2, k6, k30, kd, kq, kp);  partial_pair<3>(s, k2, k6, k30, kd, kq, kp);  partial_pair<5>(s, k2, k6, k30, kd, kq, kp);
+        partial_pair<7>(s, k2, k6, k30, kd, kq, kp);  partial_pair<9>(s, k2, k6, k30, kd, kq, kp);  partial_pair<11>(s, k2, k6, k30, kd, kq, kp);
+        partial_round<13>(s, k2, k6, kd, kp);
+        sbox_full4<0>(s, kp);      mds16_2x(k2, k4, s, V);
+        sbox_full<5, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<6, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<7, 0>(V, s, kp);
     }
 
     static __device__ __forceinline__ void poseidon2_inline(uint32_t* s) {

@@ -5,8 +5,12 @@ Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 perm
 
   S-box with its pre-reduction, x -> x^5 (142 of them: 8 full rounds x 16 + 14 partial rounds x 1)
       fold2 (lshr, add) + round constant and canonicalisation in one (2 add-literal, min)
-      + pow5 (2 x [add, mad, lshr, add, add-literal, min] + [mad, lshr, add])
-      = 14 fast, 3 v_min_u32, 3 v_mad_u64_u32 without addend            (the partial-round S-box has no fold2: 12 fast)
+      + pow5, the middle square signed: [add, mad (SGPR-pair addend 2^64 - P * 2^32), lshr, add]
+             + [v_mad_i64_i32, alignbit, and-literal, add, add-literal, min] + [mad, lshr, add]
+      = 12 fast, 2 v_min_u32, 1 v_mad_u64_u32 without addend, 1 with an SGPR-pair addend, 1 v_mad_i64_i32, 1 v_alignbit_b32
+                                                                        (the partial-round S-box has no fold2: 10 fast)
+      (before the signed square: pow5 = 2 x [add, mad, lshr, add, add-literal, min] + [mad, lshr, add], 14 fast, 3 min,
+      3 mads without addend per pow5, 47.2 cycles against 42.0 now)
   full-round linear layer mds16_2x (9 of them; none carries round constants: they are literals of the S-box reduction)
       per 4-word group 2 mad (no addend) + 4 mad (addend) + 2 lshl_add_u64 + 2 lshl_add_u64 (plain adds)        = 40
       column sums 12 + 16 lshl_add_u64                                                                          = 28
@@ -17,18 +21,23 @@ Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 perm
               (against two singles: -28 fast, +1 mad with addend — the round's sum S folded once and added as 30 S)
   output: 16 x (lshr, add, add-literal, min)
 
-  class                      count   cycles/instr at 4 waves/SIMD, expressed at 2.4 GHz (tools/valu_lab.hip, measured r2)
-  fast  (add/sub/lshr/and)    2288   2.50     (a 32-bit literal operand does not change the class: 2.52)
-  v_min_u32                    442   4.27
-  v_mad_u64_u32, no addend     526   4.54
+  class                      count   cycles/instr at 4 waves/SIMD, expressed at 2.4 GHz (tools/valu_lab.hip, measured r2;
+                                     the three rows of the signed square measured with it, 8 waves/SIMD in brackets)
+  fast  (add/sub/lshr/and)    2004   2.50     (a 32-bit literal operand does not change the class: 2.52)
+  v_min_u32                    300   4.27
+  v_mad_u64_u32, no addend     242   4.54
   v_lshl_add_u64               410   4.48
   v_mad_u64_u32, with addend   570   5.10     (SGPR multiplier or live 64-bit addend: 5.05-5.15)
-  total                       4236            = the static count: the function is straight-line code since the constants
+  v_mad_i64_i32, no addend     142   4.34     (4.23; v_mad_u64_u32 without addend in the same run: 4.51 (4.38))
+  v_mad_u64_u32, SGPR pair     142   4.48     (4.35; the addend is an SGPR pair, not a live VGPR pair: that costs 4.90)
+  v_alignbit_b32               142   4.40     (4.20)
+  total                       3952            = the static count: the function is straight-line code since the constants
                                               became literals (before: 4 428 with 736 addend-mads, 15 650 cycles, 10.05 G/s;
                                               before the paired partial rounds: 4 398, 2 456 fast and 564 addend-mads,
-                                              15 129 cycles, 10.40 G/s)
+                                              15 129 cycles, 10.40 G/s; before the signed square: 4 236, 2 288 fast, 442
+                                              v_min, 526 mads without addend, 14 739 cycles, 10.67 G/s)
 
-=> 14 739 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 14 739 x 64 = 10.67 G permutations/s.
+=> 14 011 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 14 011 x 64 = 11.23 G permutations/s.
 (The lab's "cycles at 2.4 GHz" are wall time x 2.4 GHz.  Round 5 separated clock from issue cost (tools/valu_clock.sh,
 profiles/r5_valu_lab_*): under the lab's dense VALU load GRBM_GUI_ACTIVE holds 2.35-2.40 GHz — v_and_b32 at 4 waves per
 SIMD: 2.242 ms at 2.383 GHz for 2 097 152 wave-instructions per SIMD = 2.55 REAL cycles each — so the fast class's 2.5
@@ -42,8 +51,9 @@ import collections
 import re
 import sys
 
-MIX = [("fast", 2288, 2.50), ("v_min_u32", 442, 4.27), ("v_mad_u64_u32 (no addend)", 526, 4.54),
-       ("v_lshl_add_u64", 410, 4.48), ("v_mad_u64_u32 (addend)", 570, 5.10)]
+MIX = [("fast", 2004, 2.50), ("v_min_u32", 300, 4.27), ("v_mad_u64_u32 (no addend)", 242, 4.54),
+       ("v_lshl_add_u64", 410, 4.48), ("v_mad_u64_u32 (addend)", 570, 5.10), ("v_mad_i64_i32 (no addend)", 142, 4.34),
+       ("v_mad_u64_u32 (SGPR-pair addend)", 142, 4.48), ("v_alignbit_b32", 142, 4.40)]
 SIMDS, LAB_GHZ = 1024, 2.4
 
 
@@ -60,6 +70,7 @@ def main():
         m = re.search(r"\n_ZN3rsv9poseidon2ENS_7State16E:.*?s_setpc_b64", s, re.S)
         ops = collections.Counter(l.split()[0] for l in m.group(0).splitlines() if l.startswith("\t") and not l.strip().startswith((".", ";")))
         print("static histogram of rsv::poseidon2 (straight-line code: equals the dynamic count):", ops.most_common(12))
+        print(f"static VALU instructions: {sum(n for op, n in ops.items() if op.startswith('v_'))} (the mix: {insts})")
 
 
 if __name__ == "__main__":
