@@ -575,6 +575,53 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
                      const rsv_public_input* pi, size_t n_pi, uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept,
                      uint8_t* reason, int device);
 
+/* ---- the columns the next prover commits: 22 Plonk + 88 Poseidon ----------------------------------------------------
+ * generate_plonk_with_poseidon_circuit (constraint_system/src/plonk_with_poseidon.rs:522-629) turns the circuit into the
+ * two components of the next proof.  Every column is canonical M31 u32, [column][row], rows in the order the prover holds
+ * them (position i = the i-th value of the bit-reversed circle-domain evaluation), 2^log rows per column.
+ *
+ * Log sizes: log_plonk = ceil_log2(n_rows) (pad(): next_power_of_two, :283-331); log_poseidon =
+ * ceil_log2(6 * max(32, roundup16(n_flow))) with n_flow = the circuit's invocations (copies * flow_count).  The Poseidon
+ * rule is not written in the reference (the trace generator sits in the un-vendored stwo fork); it reproduces the header of
+ * the next fixture for all 14 consecutive pairs of the reference's fixture chain.  RSV_E_SIZE for zero rows or flow, or
+ * a log size beyond RSV_MAX_WITNESS_LOG. */
+int rsv_trace_log_sizes(size_t n_rows, size_t n_flow, uint32_t* log_plonk, uint32_t* log_poseidon);
+/* The PREPROCESSED columns (host arithmetic, no device), from the unpadded gate list [n_rows][6] and flow wires
+ * [n_flow][5] exactly as rsv_witness_program_gates / _export return them.
+ *   plonk_pre [10][2^log_plonk]: a_wire, b_wire, c_wire, op, mult_a, mult_b, mult_c, poseidon_wire, mult_poseidon,
+ *     enforce_c_m31 (the AIR's order, components/recursive/composition/src/plonk.rs:14-41).  Padding rows (0, 0, 0, op 1);
+ *     multiplicities as populate_logup_arguments (:345-466) with num_input = 3 (components/recursive allocates no public
+ *     input; the four constant rows the constraint system starts with are checked, RSV_E_RANGE otherwise); 1 - count is
+ *     taken mod P.  `op` is the template's: patch the witness_ops rows per proof (rsv_witness_trace_dev's d_ops).
+ *   poseidon_pre [40][2^log_poseidon]: is_first, is_last, is_full, round_id, rc0[16], rc1[16], wire of r1 / r3, wire of
+ *     r2 / r4, r1 / r3 wire != 0, r2 / r4 wire != 0 (composition/src/poseidon.rs:73-241).  Invocation k (of the flow padded
+ *     with wire-0, address-0 entries) sits at rows ((k / 16) * 6 + j) * 16 + k % 16, j < 6; round_id = 6 k + j; rc0[0] of
+ *     its first row carries the swap address; rows behind the padded flow have is_first = is_last = 1, all else 0.
+ * Log sizes smaller than rsv_trace_log_sizes' (larger is allowed), zero rows or flow: RSV_E_SIZE; NULL: RSV_E_NULL; a
+ * Poseidon output wire used more than once: RSV_E_RANGE.  Nothing is written unless RSV_OK. */
+int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
+                           uint32_t log_poseidon, uint32_t* plonk_pre, uint32_t* poseidon_pre);
+/* The TRACE columns of a batch, from what rsv_witness_eval_dev wrote (d_variables in the layout RSV_OPT_WITNESS_LAYOUT
+ * names, d_flow / d_flow_swap, d_accept).  Built programs only (RSV_E_SIZE otherwise); the program's padded wires and
+ * witness ops go to the device on the first call.  lp, lq = rsv_trace_log_sizes(gate rows, copies * flow_count).
+ *   d_plonk [n][12][2^lp]: a_val, b_val, c_val (4 words each) = variables[wire[row]] (:571-618).
+ *   d_poseidon [n][48][2^lq]: in[16], intermediate[16], out[16] of the six rows per invocation above: the state entering
+ *     the row's rounds; row 0: intermediate[0] = swap bit, out = external matrix of the (swapped) input; rows 1, 2, 4, 5:
+ *     intermediate = the first full round's S-box outputs, out = the state after two full rounds; row 3: intermediate[r] =
+ *     the r-th partial S-box output (r < 14).  Invocation k of copy c hashes flow record k - c * flow_count; the padding
+ *     invocations hash zeros.  Rows behind the padded flow are zero.
+ *   d_ops [n][n_witness_ops]: the `op` of witness-op row k for proof i = variables[bit].x ? constant : 0.
+ * Any of the three may be NULL (skipped); d_variables is needed for d_plonk / d_ops, d_flow + d_flow_swap for d_poseidon
+ * (RSV_E_NULL otherwise).  d_variables, d_flow, d_poseidon 16-byte aligned.  Every element is written; a proof with
+ * d_accept[i] == 0 gets zero columns and zero ops.  Enqueued on the context's stream. */
+int rsv_witness_trace_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                          const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
+                          uint32_t* d_ops);
+/* rsv_witness_eval + rsv_witness_trace_dev on host buffers (plonk, poseidon, ops may each be NULL). */
+int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                      const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,
+                      uint8_t* reason, int device);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

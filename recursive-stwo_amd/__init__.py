@@ -210,6 +210,11 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_eval_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, vp, vp, vp, vp]),
         "rsv_witness_eval": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u8p,
                                             _u8p, _u8p, ctypes.c_int]),
+        "rsv_trace_log_sizes": (ctypes.c_int, [sz, sz, _u32p, _u32p]),
+        "rsv_trace_preprocessed": (ctypes.c_int, [_u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p]),
+        "rsv_witness_trace_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "rsv_witness_trace": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u32p,
+                                             _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
         "rsv_host_free": (None, [vp]),
         "rsv_shard_range": (None, [sz, sz, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
@@ -251,7 +256,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_line_eval", "rsv_oods_eval", "rsv_last_layer_check",
            "rsv_transcript_batch", "rsv_poseidon_flow_count", "rsv_witness_program_create", "rsv_witness_program_destroy",
            "rsv_witness_program_build", "rsv_witness_program_info", "rsv_witness_program_export", "rsv_witness_program_gates",
-           "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval",
+           "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
+           "rsv_witness_trace_dev", "rsv_witness_trace",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -630,6 +636,24 @@ class WitnessProgram:
             rows[ops[:, 0], 3] = np.where(variables[ops[:, 1], 0] != 0, ops[:, 2], 0)
         return rows, ops
 
+    def trace_sizes(self):
+        """(log_plonk, log_poseidon) of the circuit's components (rsv_trace_log_sizes of its gate rows and flow)."""
+        rows, _ = self.gates()
+        return trace_log_sizes(len(rows), self.shape.copies * self.shape.flow_count)
+
+    def preprocessed(self, variables=None):
+        """The 10 Plonk and 40 Poseidon preprocessed columns (rsv_trace_preprocessed): uint32[10, 2^lp], uint32[40, 2^lq].
+        With `variables` (uint32[n_vars, 4] of one proof of the shape) `op` is that proof's, as gates(variables) sets it."""
+        rows, _ = self.gates(variables)
+        wires = np.ascontiguousarray(self.export().flow_wires, dtype=np.uint32)
+        rows = np.ascontiguousarray(rows)
+        lp, lq = trace_log_sizes(len(rows), len(wires))
+        plonk = np.zeros((10, 1 << lp), np.uint32)
+        poseidon = np.zeros((40, 1 << lq), np.uint32)
+        _check(lib.rsv_trace_preprocessed(rows.ctypes.data_as(_u32p), len(rows), wires.ctypes.data_as(_u32p), len(wires), lp, lq,
+                                          plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p)), "rsv_trace_preprocessed")
+        return plonk, poseidon
+
     def close(self):
         if getattr(self, "_h", None):
             lib.rsv_witness_program_destroy(self._h)
@@ -667,6 +691,33 @@ def witness(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_IN
                                 swap.ctypes.data_as(_u8p) if with_flow else None, accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device),
            "rsv_witness_eval")
     return (variables, accept, reason, flow, swap) if with_flow else (variables, accept, reason)
+
+
+def trace_log_sizes(n_rows: int, n_flow: int):
+    """(log_plonk, log_poseidon) of the next proof's two components for a circuit of n_rows gate rows and n_flow Poseidon
+    invocations (rsv_trace_log_sizes)."""
+    lp, lq = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    _check(lib.rsv_trace_log_sizes(n_rows, n_flow, ctypes.byref(lp), ctypes.byref(lq)), "rsv_trace_log_sizes")
+    return int(lp.value), int(lq.value)
+
+
+def witness_trace(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_INPUTS, device: int = 0):
+    """The trace columns of the recursion circuit for every proof of a batch (rsv_witness_trace): plonk uint32[n, 12, 2^lp],
+    poseidon uint32[n, 48, 2^lq], ops uint32[n, n_witness_ops], accept, reason."""
+    blob, offsets = pack(proofs)
+    n = len(proofs)
+    lp, lq = program.trace_sizes()
+    n_ops = len(program.gates()[1])
+    plonk = np.zeros((n, 12, 1 << lp), np.uint32)
+    poseidon = np.zeros((n, 48, 1 << lq), np.uint32)
+    ops = np.zeros((n, n_ops), np.uint32)
+    accept = np.zeros(n, np.uint8)
+    reason = np.zeros(n, np.uint8)
+    pi = make_inputs(inputs)
+    _check(lib.rsv_witness_trace(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), pi,
+                                 len(list(inputs)), plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p), ops.ctypes.data_as(_u32p),
+                                 accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_witness_trace")
+    return plonk, poseidon, ops, accept, reason
 
 
 def fri_paths(proofs: Sequence[bytes], cfg, n_queries: int, max_log: int, n_inner: int, inputs=STANDARD_INPUTS, device: int = 0):
@@ -891,6 +942,15 @@ class Context:
                                         d_flow_swap.data_ptr() if d_flow_swap is not None else None, d_accept.data_ptr(),
                                         d_reason.data_ptr() if d_reason is not None else None),
                "rsv_witness_eval_dev")
+
+    def witness_trace(self, program: WitnessProgram, d_variables, d_accept, n: int, d_plonk=None, d_poseidon=None, d_ops=None, d_flow=None,
+                      d_flow_swap=None):
+        """rsv_witness_trace_dev on what Context.witness wrote: d_plonk uint32[n, 12, 2^lp], d_poseidon uint32[n, 48, 2^lq],
+        d_ops uint32[n, n_witness_ops] (any may be None); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_trace_dev(self._h, program._h, ptr(d_variables), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(), n,
+                                         ptr(d_plonk), ptr(d_poseidon), ptr(d_ops)), "rsv_witness_trace_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

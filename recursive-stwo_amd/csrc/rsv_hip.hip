@@ -26,6 +26,8 @@
 #include "verify.hpp"
 #include "host_logic.hpp"
 #include "k_witness.hpp"
+#include "k_trace.hpp"
+#include "trace_host.hpp"
 
 using namespace rsv;
 
@@ -493,3 +495,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "circuit_program.hpp"
 #include "witness_api.inc"
 #include "circuit_builder.inc"
+#include "trace_api.inc"

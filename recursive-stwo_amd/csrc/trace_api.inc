@@ -1,0 +1,161 @@
+// trace_api.inc — rsv_trace_log_sizes / rsv_trace_preprocessed (host arithmetic, trace_host.hpp) and
+// rsv_witness_trace_dev / rsv_witness_trace (the trace columns on the device, k_trace.hpp): the 110 columns the next
+// prover commits for the recursion circuit of a batch (include/rsv.h).  Included at the end of rsv_hip.hip.
+
+namespace {
+
+// The program's padded wires and witness ops on the device, uploaded once (built programs only: RSV_E_SIZE otherwise).
+int trace_upload(rsv_witness_program* prog) {
+    std::lock_guard<std::mutex> lk(prog->trace_mu);
+    if (prog->d_trace_wires) return RSV_OK;
+    if (prog->gates.empty() || prog->flow_wires.empty()) return RSV_E_SIZE;
+    const size_t n_rows = prog->gates.size() / 6;
+    for (size_t i = 0; i < n_rows; i++)  // every index the kernels gather with
+        for (int k = 0; k < 3; k++)
+            if (prog->gates[i * 6 + k] >= prog->n_vars) return RSV_E_RANGE;
+    for (size_t i = 0; i < prog->witness_ops.size() / 3; i++)
+        if (prog->witness_ops[i * 3 + 1] >= prog->n_vars) return RSV_E_RANGE;
+    uint32_t lp = 0, lq = 0;
+    int rc = rsv::trace::log_sizes(n_rows, prog->flow_wires.size() / 5, lp, lq);
+    if (rc != RSV_OK) return rc;
+    const std::vector<uint32_t> wires = rsv::trace::padded_wires(prog->gates.data(), n_rows, lp);
+    uint32_t *dw = nullptr, *dops = nullptr;
+    const size_t ops_bytes = prog->witness_ops.size() * 4;
+    if (hipMalloc(reinterpret_cast<void**>(&dw), wires.size() * 4) != hipSuccess) return RSV_E_DEVICE;
+    if (hipMemcpy(dw, wires.data(), wires.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&dops), ops_bytes ? ops_bytes : 4) != hipSuccess ||
+        (ops_bytes && hipMemcpy(dops, prog->witness_ops.data(), ops_bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(dw);
+        if (dops) (void)hipFree(dops);
+        return RSV_E_DEVICE;
+    }
+    prog->d_trace_ops = dops;
+    prog->trace_lp = lp;
+    prog->trace_lq = lq;
+    prog->d_trace_wires = dw;  // last: the flag the check above reads
+    return RSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsv_trace_log_sizes(size_t n_rows, size_t n_flow, uint32_t* log_plonk, uint32_t* log_poseidon) {
+    if (!log_plonk || !log_poseidon) return RSV_E_NULL;
+    return rsv::trace::log_sizes(n_rows, n_flow, *log_plonk, *log_poseidon);
+}
+
+int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
+                           uint32_t log_poseidon, uint32_t* plonk_pre, uint32_t* poseidon_pre) {
+    try {
+        return rsv::trace::preprocessed(gates, n_rows, flow_wires, n_flow, log_plonk, log_poseidon, rsv::RC_FULL_K, rsv::RC_PARTIAL_K,
+                                        rsv::RC_FULL_K + 4, plonk_pre, poseidon_pre);
+    } catch (const std::bad_alloc&) {
+        return RSV_E_NOMEM;
+    }
+}
+
+int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* cprog, const uint32_t* d_variables, const uint32_t* d_flow,
+                          const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
+                          uint32_t* d_ops) {
+    if (!c || !cprog || !d_accept) return RSV_E_NULL;
+    if ((d_plonk || d_ops) && !d_variables) return RSV_E_NULL;
+    if (d_poseidon && (!d_flow || !d_flow_swap)) return RSV_E_NULL;
+    if (((uintptr_t)d_variables & 15) || ((uintptr_t)d_flow & 15) || ((uintptr_t)d_poseidon & 15) || ((uintptr_t)d_plonk & 3) ||
+        ((uintptr_t)d_ops & 3))
+        return RSV_E_SIZE;
+    if (cprog->device != c->device || n > (1u << 20)) return RSV_E_SIZE;
+    rsv_witness_program* prog = const_cast<rsv_witness_program*>(cprog);  // the lazily uploaded device copies only
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = trace_upload(prog);
+    if (rc != RSV_OK) return rc;
+    if (n == 0) return RSV_OK;
+    const rsv_witness_shape& s = prog->shape;
+    rsv::TraceArgs a{};
+    a.vars = reinterpret_cast<const uint4*>(d_variables);
+    a.n_vars = prog->n_vars;
+    a.n = (uint32_t)n;
+    a.by_variable = c->opt.witness_layout == 2;
+    a.accept = d_accept;
+    a.wires = prog->d_trace_wires;
+    a.log_plonk = prog->trace_lp;
+    a.plonk = d_plonk;
+    a.flow = reinterpret_cast<const uint4*>(d_flow);
+    a.swap = d_flow_swap;
+    a.flow_count = s.flow_count;
+    a.copies = s.copies;
+    a.n_pad = (uint32_t)rsv::trace::padded_flow((uint64_t)s.flow_count * s.copies);
+    a.log_poseidon = prog->trace_lq;
+    a.poseidon = d_poseidon;
+    const uint64_t plonk_blocks = (uint64_t)((((size_t)1 << a.log_plonk) + 255) / 256) * n;
+    const uint64_t poseidon_blocks = (uint64_t)((a.n_pad + rsv::TRACE_WAVE - 1) / rsv::TRACE_WAVE) * n;
+    const size_t Q = (size_t)1 << a.log_poseidon, tail_first = (size_t)6 * a.n_pad;
+    const uint64_t tail_threads = (uint64_t)(Q - tail_first) / 4 * rsv::POSEIDON_COLS_K * n;
+    const size_t n_ops = prog->witness_ops.size() / 3;
+    if (plonk_blocks >= (1u << 31) || poseidon_blocks >= (1u << 31) || tail_threads / 256 >= (1u << 31) || (uint64_t)n_ops * n / 256 >= (1u << 31))
+        return RSV_E_SIZE;
+    hipStream_t st = c->stream;
+    if (d_plonk) hipLaunchKernelGGL(rsv::k_trace_plonk, dim3((unsigned)plonk_blocks), dim3(256), 0, st, a);
+    if (d_ops && n_ops) hipLaunchKernelGGL(rsv::k_trace_ops, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, a, prog->d_trace_ops, (uint32_t)n_ops, d_ops);
+    if (d_poseidon) {
+        hipLaunchKernelGGL(rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
+        if (tail_threads)
+            hipLaunchKernelGGL(rsv::k_trace_zero_tail, dim3(grid_for(tail_threads, 256)), dim3(256), 0, st, d_poseidon, a.log_poseidon,
+                               (uint32_t)tail_first, (uint64_t)rsv::POSEIDON_COLS_K * n);
+    }
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                      const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,
+                      uint8_t* reason, int device) {
+    if (!prog || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
+    if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_trace_dev
+    if (n == 0) return RSV_OK;
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
+    int rc = select_device(device);
+    if (rc != RSV_OK) return rc;
+    rsv_ctx* c = nullptr;
+    rc = rsv_ctx_create(device, &c);
+    if (rc != RSV_OK) return rc;
+    struct Guard { rsv_ctx* c; ~Guard() { rsv_ctx_destroy(c); } } guard{c};
+    c->opt.witness_layout = 2;  // the trace kernels read either layout; this one needs no transpose and no second copy
+    rc = trace_upload(const_cast<rsv_witness_program*>(prog));
+    if (rc != RSV_OK) return rc;
+    const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq, n_ops = prog->witness_ops.size() / 3;
+    const uint64_t base = offsets[0], total = offsets[n] - base;
+    std::vector<uint64_t> rel(n + 1);
+    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
+    DevBuf dblob, doffs, dvars, dacc, dreason, dflow, dswap, dplonk, dposeidon, dops;
+    const size_t flow_records = n * (size_t)prog->shape.flow_count;
+    HIP_TRY(dflow.alloc(flow_records * 128));
+    HIP_TRY(dswap.alloc(flow_records));
+    HIP_TRY(dblob.alloc(total));
+    HIP_TRY(doffs.alloc(8 * (n + 1)));
+    HIP_TRY(dvars.alloc(n * (size_t)prog->n_vars * 16));
+    HIP_TRY(dacc.alloc(n));
+    HIP_TRY(dreason.alloc(n));
+    if (plonk) HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
+    if (poseidon) HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
+    if (ops) HIP_TRY(dops.alloc(n * n_ops * 4));
+    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
+    rc = rsv_witness_eval_dev(c, prog, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, cfg, pi, n_pi, dvars.as<uint32_t>(),
+                              dflow.as<uint32_t>(), dswap.as<uint8_t>(), dacc.as<uint8_t>(), dreason.as<uint8_t>());
+    if (rc != RSV_OK) return rc;
+    rc = rsv_witness_trace_dev(c, prog, dvars.as<const uint32_t>(), dflow.as<const uint32_t>(), dswap.as<const uint8_t>(),
+                               dacc.as<const uint8_t>(), n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), dops.as<uint32_t>());
+    if (rc != RSV_OK) return rc;
+    rc = rsv_ctx_synchronize(c);
+    if (rc != RSV_OK) return rc;
+    if (plonk) HIP_TRY(hipMemcpy(plonk, dplonk.p, n * rsv::PLONK_COLS_K * N * 4, hipMemcpyDeviceToHost));
+    if (poseidon) HIP_TRY(hipMemcpy(poseidon, dposeidon.p, n * rsv::POSEIDON_COLS_K * Q * 4, hipMemcpyDeviceToHost));
+    if (ops && n_ops) HIP_TRY(hipMemcpy(ops, dops.p, n * n_ops * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost));
+    if (reason) HIP_TRY(hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost));
+    return RSV_OK;
+}
+
+}  // extern "C"

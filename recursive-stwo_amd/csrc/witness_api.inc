@@ -15,6 +15,12 @@ struct rsv_witness_program {
     std::vector<uint32_t> flow_wires;   // [copies * flow_count][5]: PoseidonEntry::wire of r1..r4, SwapOption::addr
     std::vector<uint32_t> gates;        // [n_rows][6]: a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31 (the template's)
     std::vector<uint32_t> witness_ops;  // [n][3]: row, bit variable, constant — rows whose op follows the witness
+    // rsv_witness_trace_dev (trace_api.inc): the padded a / b / c wires [3][2^trace_lp] and witness_ops on the device,
+    // uploaded by the first call
+    std::mutex trace_mu;
+    uint32_t* d_trace_wires = nullptr;
+    uint32_t* d_trace_ops = nullptr;
+    uint32_t trace_lp = 0, trace_lq = 0;
 };
 
 namespace {
@@ -82,6 +88,8 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     (void)hipSetDevice(p->device);
     if (p->d_instr) (void)hipFree(p->d_instr);
     if (p->d_levels) (void)hipFree(p->d_levels);
+    if (p->d_trace_wires) (void)hipFree(p->d_trace_wires);
+    if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
     delete p;
 }
 
