@@ -622,6 +622,36 @@ int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, cons
                       const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,
                       uint8_t* reason, int device);
 
+/* ---- the interaction (logup) columns: tree 2 of the next proof, 8 Plonk + 8 Poseidon ---------------------------------
+ * The AIR's relations (components/recursive/composition/src/{data_structures,plonk,poseidon}.rs) add the entries
+ * multiplicity / (sum_i alpha^i values[i] - z), batched Plonk {a, b}, {c, poseidon} and Poseidon {in_left, in_right,
+ * out_left}, {out_right, swap}; f0, f1 = the two batches' fraction sums at a row.  Per component, two secure columns as
+ * 4 M31 coordinate columns each (combine_ef order), rows stored as the trace columns:
+ *   columns 0..3: f0 at the row;
+ *   columns 4..7: S[k] = sum_{j <= k} (f0[j] + f1[j] - shift) over the domain's COSET order k (the row at position i holds
+ *     circle-domain index bitrev(i); coset index 2 d for d < 2^(log-1), 2^(log+1) - 2 d - 1 otherwise), shift = total /
+ *     2^log, total = sum over all rows of f0 + f1 = the component's claimed sum (S[last] = 0).
+ * For an accepted proof the claimed sums balance the public inputs: plonk + poseidon + sum_(idx, v) 1 / (v + idx alpha - z)
+ * = 0, for any (z, alpha).
+ *
+ * From the trace columns rsv_witness_trace_dev wrote (d_plonk [n][12][2^lp], d_poseidon [n][48][2^lq]), d_accept and the
+ * lookup elements the next proof's transcript draws after trees 0 and 1, d_lookup [n][8]: z, then alpha (QM31 words; any
+ * u32 is taken mod P).  Built programs only (RSV_E_SIZE otherwise); the 8 + 8 preprocessed columns the relations read go
+ * to the device on the first call.  Outputs: d_int_plonk [n][8][2^lp], d_int_poseidon [n][8][2^lq], d_sums [n][2][4] (the
+ * Plonk then the Poseidon claimed sum), d_ok [n] (may be NULL): 1 iff the proof was accepted and no denominator of either
+ * component is zero.  A proof with d_ok[i] == 0 (rejected, or a zero denominator) gets zero columns and zero sums; the
+ * other proofs of the batch are unaffected.  Every element is written.  NULL pointers (but d_ok): RSV_E_NULL; d_plonk,
+ * d_poseidon, d_lookup, d_sums 4-byte and d_int_plonk, d_int_poseidon 8-byte aligned, RSV_E_SIZE otherwise.  Enqueued on
+ * the context's stream; the context's workspace grows (with a synchronisation) only when a batch needs more. */
+int rsv_witness_interaction_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                                const uint8_t* d_accept, const uint32_t* d_lookup, size_t n, uint32_t* d_int_plonk,
+                                uint32_t* d_int_poseidon, uint32_t* d_sums, uint8_t* d_ok);
+/* rsv_witness_eval + rsv_witness_trace_dev + rsv_witness_interaction_dev on host buffers (lookup [n][8]; ok and reason
+ * may be NULL). */
+int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                            const rsv_public_input* pi, size_t n_pi, const uint32_t* lookup, uint32_t* int_plonk, uint32_t* int_poseidon,
+                            uint32_t* sums, uint8_t* ok, uint8_t* accept, uint8_t* reason, int device);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -215,6 +215,9 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_trace_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rsv_witness_trace": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u32p,
                                              _u8p, _u8p, ctypes.c_int]),
+        "rsv_witness_interaction_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]),
+        "rsv_witness_interaction": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p,
+                                                   _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
         "rsv_host_free": (None, [vp]),
         "rsv_shard_range": (None, [sz, sz, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
@@ -257,7 +260,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_transcript_batch", "rsv_poseidon_flow_count", "rsv_witness_program_create", "rsv_witness_program_destroy",
            "rsv_witness_program_build", "rsv_witness_program_info", "rsv_witness_program_export", "rsv_witness_program_gates",
            "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
-           "rsv_witness_trace_dev", "rsv_witness_trace",
+           "rsv_witness_trace_dev", "rsv_witness_trace", "rsv_witness_interaction_dev", "rsv_witness_interaction",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -720,6 +723,38 @@ def witness_trace(proofs: Sequence[bytes], program: WitnessProgram, inputs=STAND
     return plonk, poseidon, ops, accept, reason
 
 
+def _lookup_array(lookup, n):
+    """(z, alpha) per proof -> uint32[n, 8]: one pair (two 4-tuples, or 8 words) for all proofs, or one per proof."""
+    arr = np.asarray(lookup, dtype=np.int64).reshape(-1, 8)
+    if arr.shape[0] == 1 and n != 1:
+        arr = np.repeat(arr, n, axis=0)
+    if arr.shape[0] != n:
+        raise RsvError(-2, "witness_interaction: lookup must be one (z, alpha) or one per proof")
+    return np.ascontiguousarray(arr % 0x7FFFFFFF, dtype=np.uint32)
+
+
+def witness_interaction(proofs: Sequence[bytes], program: WitnessProgram, lookup, inputs=STANDARD_INPUTS, device: int = 0):
+    """The interaction (logup) columns of the recursion circuit for every proof of a batch (rsv_witness_interaction), with the
+    next proof's lookup elements `lookup` = (z, alpha) for all proofs or [n] of them: int_plonk uint32[n, 8, 2^lp],
+    int_poseidon uint32[n, 8, 2^lq], sums uint32[n, 2, 4] (the Plonk and Poseidon claimed sums), ok, accept, reason."""
+    blob, offsets = pack(proofs)
+    n = len(proofs)
+    lk = _lookup_array(lookup, n)
+    lp, lq = program.trace_sizes()
+    int_plonk = np.zeros((n, 8, 1 << lp), np.uint32)
+    int_poseidon = np.zeros((n, 8, 1 << lq), np.uint32)
+    sums = np.zeros((n, 2, 4), np.uint32)
+    ok = np.zeros(n, np.uint8)
+    accept = np.zeros(n, np.uint8)
+    reason = np.zeros(n, np.uint8)
+    pi = make_inputs(inputs)
+    _check(lib.rsv_witness_interaction(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(),
+                                       pi, len(list(inputs)), lk.ctypes.data_as(_u32p), int_plonk.ctypes.data_as(_u32p),
+                                       int_poseidon.ctypes.data_as(_u32p), sums.ctypes.data_as(_u32p), ok.ctypes.data_as(_u8p),
+                                       accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_witness_interaction")
+    return int_plonk, int_poseidon, sums, ok, accept, reason
+
+
 def fri_paths(proofs: Sequence[bytes], cfg, n_queries: int, max_log: int, n_inner: int, inputs=STANDARD_INPUTS, device: int = 0):
     """per-query pair paths of the FRI trees.  Returns (sib uint32[n,1+n_inner,nq,max_log,8],
     cols uint32[n,1+n_inner,nq,3,8], accept, reason)."""
@@ -951,6 +986,16 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_witness_trace_dev(self._h, program._h, ptr(d_variables), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(), n,
                                          ptr(d_plonk), ptr(d_poseidon), ptr(d_ops)), "rsv_witness_trace_dev")
+
+    def witness_interaction(self, program: WitnessProgram, d_plonk, d_poseidon, d_accept, d_lookup, n: int, d_int_plonk, d_int_poseidon, d_sums,
+                            d_ok=None):
+        """rsv_witness_interaction_dev on what Context.witness_trace wrote and d_lookup uint32[n, 8] (z, alpha): d_int_plonk
+        uint32[n, 8, 2^lp], d_int_poseidon uint32[n, 8, 2^lq], d_sums uint32[n, 2, 4], d_ok uint8[n] (may be None); enqueued on
+        the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_interaction_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_accept), ptr(d_lookup), n,
+                                               ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_ok)), "rsv_witness_interaction_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

@@ -27,6 +27,7 @@
 #include "host_logic.hpp"
 #include "k_witness.hpp"
 #include "k_trace.hpp"
+#include "k_interaction.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -96,6 +97,8 @@ struct rsv_ctx {
     size_t ws_rows_bytes = 0;
     void* ws_witness = nullptr;  // rsv_witness_eval_dev: the hints it asks the verifying pass for, and variables[var][proof]
     size_t ws_witness_bytes = 0;
+    void* ws_interaction = nullptr;  // rsv_witness_interaction_dev: zero flags, shifts, chunk prefixes
+    size_t ws_interaction_bytes = 0;
     const struct rsv::ProofMeta* last_metas = nullptr;  // the parser's records of the last batch (inside ws_fixed)
     VerifyState* vs = nullptr;
     rsv_public_input* d_pi = nullptr;
@@ -218,6 +221,7 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ws_fixed) (void)hipFree(c->ws_fixed);
     if (c->ws_rows) (void)hipFree(c->ws_rows);
     if (c->ws_witness) (void)hipFree(c->ws_witness);
+    if (c->ws_interaction) (void)hipFree(c->ws_interaction);
     if (c->d_pi) (void)hipFree(c->d_pi);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -496,3 +500,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "witness_api.inc"
 #include "circuit_builder.inc"
 #include "trace_api.inc"
+#include "interaction_api.inc"

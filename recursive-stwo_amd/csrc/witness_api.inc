@@ -21,6 +21,9 @@ struct rsv_witness_program {
     uint32_t* d_trace_wires = nullptr;
     uint32_t* d_trace_ops = nullptr;
     uint32_t trace_lp = 0, trace_lq = 0;
+    // rsv_witness_interaction_dev (interaction_api.inc): the 8 + 8 preprocessed columns its relations read, uploaded by
+    // the first call
+    uint32_t* d_int_pre = nullptr;
 };
 
 namespace {
@@ -90,6 +93,7 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_levels) (void)hipFree(p->d_levels);
     if (p->d_trace_wires) (void)hipFree(p->d_trace_wires);
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
+    if (p->d_int_pre) (void)hipFree(p->d_int_pre);
     delete p;
 }
 
