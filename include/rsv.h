@@ -652,6 +652,61 @@ int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob
                             const rsv_public_input* pi, size_t n_pi, const uint32_t* lookup, uint32_t* int_plonk, uint32_t* int_poseidon,
                             uint32_t* sums, uint8_t* ok, uint8_t* accept, uint8_t* reason, int device);
 
+/* ---- commitment of a tree of the next proof: interpolation, low-degree extension, Merkle root ------------------------
+ * A tree is one or more groups of M31 columns; group g has n_cols columns of 2^log_size rows, stored as the trace columns
+ * are (evaluations on CanonicCoset(log_size).circle_domain(), bit-reversed).  Each column is interpolated (CirclePoly
+ * coefficients: coefficient i multiplies y^{i_0} x^{i_1} pi(x)^{i_2} pi^2(x)^{i_3} ..., i_k = bit k of i, pi(x) =
+ * 2 x^2 - 1), evaluated on CanonicCoset(log_size + log_blowup).circle_domain() (bit-reversed) and the tree is committed
+ * with stwo's mixed-size rule: the leaves sit at the largest log_size + log_blowup, leaf = hash_node(None, that layer's
+ * columns); a lower layer l is hash_node((L, R), the columns of size 2^l) or just (L, R) where no column has that size.
+ * Within a layer the columns go in group order.  hash_node is rsv_merkle_hash_node's.
+ *
+ * The LDE is streamed in blocks of 2^log_size positions and hashed as it is made: the workspace holds the coefficients, the
+ * blocks in flight and the node layers of one pass, within RSV_OPT_WS_BUDGET_MB (a larger batch or tree is cut into passes
+ * of fewer blocks, then fewer proofs).  log_size + log_blowup <= RSV_MAX_LOG_SIZE, 1 <= log_blowup <= RSV_MAX_LOG_BLOWUP,
+ * 1 <= n_groups <= RSV_MAX_COMMIT_GROUPS, n_cols >= 1, n <= 2^20; RSV_E_SIZE otherwise, and for a pointer that is not
+ * 4-byte aligned. */
+#define RSV_MAX_COMMIT_GROUPS 8
+typedef struct {
+    uint32_t log_size;
+    uint32_t n_cols;
+    const uint32_t* d_cols;  /* [n][n_cols][2^log_size] (device); proof i's columns at d_cols + i * proof_stride */
+    uint64_t proof_stride;   /* words between two proofs' column sets; 0: one set shared by every proof */
+    uint32_t* d_coeffs;      /* optional output (may be NULL): the coefficients, [n][n_cols][2^log_size] */
+    uint32_t* d_lde;         /* optional output (may be NULL): the LDE, [n][n_cols][2^(log_size + log_blowup)], bit-reversed */
+} rsv_commit_group;
+/* d_roots [n][8] (device).  d_mask [n] (device, may be NULL): a proof whose byte is 0 gets a zero root and zero d_coeffs /
+ * d_lde; its neighbours are unaffected.  groups: HOST memory, read during the call.  NULL groups, d_cols or d_roots:
+ * RSV_E_NULL.  Enqueued on the context's stream; twiddle tables (one per domain size, kept in the context) and the
+ * workspace are allocated, with a synchronisation, only when a call needs more. */
+int rsv_commit_tree_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup,
+                        const uint8_t* d_mask, uint32_t* d_roots);
+
+/* Trees 0, 1 and 2 of the recursion circuit's next proof and the transcript between them, from what rsv_witness_trace_dev
+ * wrote (d_plonk, d_poseidon, d_ops [n][n_witness_ops]; d_ops may be NULL for a program without witness ops) and d_accept:
+ *   tree 0: the program's 10 Plonk + 40 Poseidon preprocessed columns (rsv_trace_preprocessed, uploaded on the first call)
+ *           with the op column's witness rows from d_ops;
+ *   tree 1: the 12 + 48 trace columns;
+ *   then, per proof, the next transcript's prefix: mix root 0, log_size_plonk, log_size_poseidon, root 1, draw (z, alpha);
+ *   tree 2: the interaction columns under that (z, alpha) (rsv_witness_interaction_dev, written to d_int_plonk
+ *           [n][8][2^lp] and d_int_poseidon [n][8][2^lq], 8-byte aligned; claimed sums to d_sums [n][2][4]);
+ *   then mix the two claimed sums and root 2, draw random_coeff.
+ * Outputs: d_roots [n][3][8]; d_draws [n][12]: z, alpha, random_coeff (QM31 words); d_channel [n][16] (may be NULL): the
+ * channel after the last draw, digest[8] then n_sent then 7 zero words, from which tree 3's stage continues (mix root 3,
+ * draw the OODS point); d_ok [n] (may be NULL): 1 iff the proof was accepted and no logup denominator is zero.  A proof
+ * with d_ok[i] == 0 gets zeros in every output; the other proofs are unaffected.  1 <= log_blowup <= RSV_MAX_LOG_BLOWUP
+ * and max(lp, lq) + log_blowup <= RSV_MAX_LOG_SIZE, else RSV_E_SIZE; alignment as rsv_witness_interaction_dev (d_ops,
+ * d_roots, d_draws, d_channel 4 bytes).  Enqueued on the context's stream. */
+int rsv_witness_commit_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                           const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
+                           uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
+                           uint8_t* d_ok);
+/* rsv_witness_eval + rsv_witness_trace_dev + rsv_witness_commit_dev on host buffers: roots [n][3][8], draws [n][12], sums
+ * [n][2][4] (ok and reason may be NULL). */
+int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                       const rsv_public_input* pi, size_t n_pi, uint32_t log_blowup, uint32_t* roots, uint32_t* draws, uint32_t* sums,
+                       uint8_t* ok, uint8_t* accept, uint8_t* reason, int device);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -130,6 +130,11 @@ class WitnessShape(ctypes.Structure):  # rsv_witness_shape
                                                "n_inner", "flow_count", "copies")]
 
 
+class CommitGroup(ctypes.Structure):  # rsv_commit_group
+    _fields_ = [("log_size", ctypes.c_uint32), ("n_cols", ctypes.c_uint32), ("d_cols", ctypes.c_void_p), ("proof_stride", ctypes.c_uint64),
+                ("d_coeffs", ctypes.c_void_p), ("d_lde", ctypes.c_void_p)]
+
+
 class Shard(ctypes.Structure):  # rsv_shard
     _fields_ = [("d_blob", ctypes.c_void_p), ("d_offsets", ctypes.c_void_p), ("n", ctypes.c_size_t), ("d_cfg_of", ctypes.c_void_p),
                 ("d_accept", ctypes.c_void_p), ("d_reason", ctypes.c_void_p)]
@@ -218,6 +223,10 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_interaction_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp, vp]),
         "rsv_witness_interaction": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p,
                                                    _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
+        "rsv_commit_tree_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, ctypes.c_uint32, vp, vp]),
+        "rsv_witness_commit_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+        "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
+                                              _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
         "rsv_host_free": (None, [vp]),
         "rsv_shard_range": (None, [sz, sz, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
@@ -261,6 +270,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_witness_program_build", "rsv_witness_program_info", "rsv_witness_program_export", "rsv_witness_program_gates",
            "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
            "rsv_witness_trace_dev", "rsv_witness_trace", "rsv_witness_interaction_dev", "rsv_witness_interaction",
+           "rsv_commit_tree_dev", "rsv_witness_commit_dev", "rsv_witness_commit",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -755,6 +765,39 @@ def witness_interaction(proofs: Sequence[bytes], program: WitnessProgram, lookup
     return int_plonk, int_poseidon, sums, ok, accept, reason
 
 
+def witness_commit(proofs: Sequence[bytes], program: WitnessProgram, log_blowup: int, inputs=STANDARD_INPUTS, device: int = 0):
+    """Trees 0, 1 and 2 of the next proof for every proof of a batch and the transcript draws between them
+    (rsv_witness_commit): roots uint32[n, 3, 8], draws uint32[n, 12] (z, alpha, random_coeff), sums uint32[n, 2, 4], ok,
+    accept, reason."""
+    blob, offsets = pack(proofs)
+    n = len(proofs)
+    roots = np.zeros((n, 3, 8), np.uint32)
+    draws = np.zeros((n, 12), np.uint32)
+    sums = np.zeros((n, 2, 4), np.uint32)
+    ok = np.zeros(n, np.uint8)
+    accept = np.zeros(n, np.uint8)
+    reason = np.zeros(n, np.uint8)
+    pi = make_inputs(inputs)
+    _check(lib.rsv_witness_commit(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), pi,
+                                  len(list(inputs)), log_blowup, roots.ctypes.data_as(_u32p), draws.ctypes.data_as(_u32p),
+                                  sums.ctypes.data_as(_u32p), ok.ctypes.data_as(_u8p), accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p),
+                                  device), "rsv_witness_commit")
+    return roots, draws, sums, ok, accept, reason
+
+
+def commit_groups(groups):
+    """[{log_size, d_cols, n_cols (default: d_cols.shape[-2]), proof_stride (default: n_cols << log_size), d_coeffs, d_lde}]
+    (torch tensors or None) -> a ctypes rsv_commit_group array."""
+    arr = (CommitGroup * max(len(groups), 1))()
+    for k, g in enumerate(groups):
+        cols = g.get("d_cols")
+        n_cols = g.get("n_cols", cols.shape[-2] if cols is not None and cols.dim() >= 2 else 1)
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        arr[k] = CommitGroup(g["log_size"], n_cols, ptr(cols), g.get("proof_stride", n_cols << g["log_size"]), ptr(g.get("d_coeffs")),
+                             ptr(g.get("d_lde")))
+    return arr
+
+
 def fri_paths(proofs: Sequence[bytes], cfg, n_queries: int, max_log: int, n_inner: int, inputs=STANDARD_INPUTS, device: int = 0):
     """per-query pair paths of the FRI trees.  Returns (sib uint32[n,1+n_inner,nq,max_log,8],
     cols uint32[n,1+n_inner,nq,3,8], accept, reason)."""
@@ -996,6 +1039,25 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_witness_interaction_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_accept), ptr(d_lookup), n,
                                                ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_ok)), "rsv_witness_interaction_dev")
+
+    def commit_tree(self, groups, n: int, log_blowup: int, d_roots, d_mask=None):
+        """rsv_commit_tree_dev: groups as commit_groups() takes them (dicts of torch tensors), d_roots uint32[n, 8], d_mask
+        uint8[n] (may be None); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        arr = commit_groups(groups)
+        self.acquire_from_torch()
+        _check(lib.rsv_commit_tree_dev(self._h, arr, len(groups), n, log_blowup, ptr(d_mask), ptr(d_roots)), "rsv_commit_tree_dev")
+
+    def witness_commit(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_accept, n: int, log_blowup: int, d_roots, d_draws,
+                       d_int_plonk, d_int_poseidon, d_sums, d_channel=None, d_ok=None):
+        """rsv_witness_commit_dev on what Context.witness_trace wrote: d_roots uint32[n, 3, 8], d_draws uint32[n, 12],
+        d_int_plonk uint32[n, 8, 2^lp], d_int_poseidon uint32[n, 8, 2^lq], d_sums uint32[n, 2, 4], d_channel uint32[n, 16] and
+        d_ok uint8[n] (may be None); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_commit_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_accept), n, log_blowup,
+                                          ptr(d_roots), ptr(d_draws), ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_channel),
+                                          ptr(d_ok)), "rsv_witness_commit_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

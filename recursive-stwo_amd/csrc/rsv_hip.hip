@@ -28,6 +28,7 @@
 #include "k_witness.hpp"
 #include "k_trace.hpp"
 #include "k_interaction.hpp"
+#include "k_commit.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -99,6 +100,11 @@ struct rsv_ctx {
     size_t ws_witness_bytes = 0;
     void* ws_interaction = nullptr;  // rsv_witness_interaction_dev: zero flags, shifts, chunk prefixes
     size_t ws_interaction_bytes = 0;
+    void* ws_commit = nullptr;  // rsv_commit_tree_dev: coefficients, LDE blocks, node layers of one pass
+    size_t ws_commit_bytes = 0;
+    void* ws_chain = nullptr;   // rsv_witness_commit_dev: op columns, lookup elements, channels, ok flags
+    size_t ws_chain_bytes = 0;
+    uint32_t* cm_tw[2][RSV_MAX_LOG_SIZE + 1] = {};  // k_cm_twiddles tables by domain log size: [0] forward, [1] inverse
     const struct rsv::ProofMeta* last_metas = nullptr;  // the parser's records of the last batch (inside ws_fixed)
     VerifyState* vs = nullptr;
     rsv_public_input* d_pi = nullptr;
@@ -222,6 +228,11 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ws_rows) (void)hipFree(c->ws_rows);
     if (c->ws_witness) (void)hipFree(c->ws_witness);
     if (c->ws_interaction) (void)hipFree(c->ws_interaction);
+    if (c->ws_commit) (void)hipFree(c->ws_commit);
+    if (c->ws_chain) (void)hipFree(c->ws_chain);
+    for (auto& by_log : c->cm_tw)
+        for (uint32_t* t : by_log)
+            if (t) (void)hipFree(t);
     if (c->d_pi) (void)hipFree(c->d_pi);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -501,3 +512,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "circuit_builder.inc"
 #include "trace_api.inc"
 #include "interaction_api.inc"
+#include "commit_api.inc"

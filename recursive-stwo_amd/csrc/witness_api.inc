@@ -24,6 +24,8 @@ struct rsv_witness_program {
     // rsv_witness_interaction_dev (interaction_api.inc): the 8 + 8 preprocessed columns its relations read, uploaded by
     // the first call
     uint32_t* d_int_pre = nullptr;
+    // rsv_witness_commit_dev (commit_api.inc): the 10 + 40 preprocessed columns of tree 0, uploaded by the first call
+    uint32_t* d_commit_pre = nullptr;
 };
 
 namespace {
@@ -94,6 +96,7 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_trace_wires) (void)hipFree(p->d_trace_wires);
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
     if (p->d_int_pre) (void)hipFree(p->d_int_pre);
+    if (p->d_commit_pre) (void)hipFree(p->d_commit_pre);
     delete p;
 }
 

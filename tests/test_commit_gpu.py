@@ -1,0 +1,297 @@
+"""rsv_commit_tree_dev / rsv_witness_commit_dev / rsv_witness_commit (`-m gpu`): trees 0, 1 and 2 of the next proof, their
+Merkle roots and the transcript draws between them.  Against the REFERENCE for all 14 consecutive fixture pairs (with no
+value borrowed from fixture K+1: the roots are its commitments[0..2], the draws its (z, alpha) and random_coeff, the sums
+its stmt1, and the channel continued with its commitments[3] draws its OODS point), the coefficients and the LDE against
+K+1's sampled and decommitted values, and bit for bit against the numpy restatement (tests/commit_ref.py, pinned to the
+fixtures by tests/test_commit_host.py) on random trees."""
+import numpy as np
+import pytest
+
+from tests import commit_ref as C
+from tests import interaction_ref as R
+from tests import oracle_binding as ob
+from tests.conftest import fixture_cfg, read_proof
+from tests.test_trace_gpu import _inputs, _walks
+from tests.test_trace_host import _pins
+
+pytestmark = pytest.mark.gpu
+P = C.P
+DEV = "cuda:0"
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def _program(rsv, pin):
+    src = pin["src"]
+    return rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=pin["multiplier"], set_walks=_walks(pin))
+
+
+def _chain(rsv, ctx, wp, batch, inputs, b):
+    """Context.witness -> witness_trace -> witness_commit on tensors in HBM, every output prefilled with -1 -> dict of numpy."""
+    import torch
+    dev = torch.device(DEV)
+    n = len(batch)
+    lp, lq = wp.trace_sizes()
+    F = wp.shape.flow_count
+    n_ops = len(wp.gates()[1])
+    blob, offsets = rsv.pack(batch)
+    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    d_vars = torch.zeros((n, wp.n_vars, 4), dtype=torch.int32, device=dev)
+    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
+    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
+    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
+    ctx.witness(wp, d_blob, d_off, n, d_vars, d_acc, inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
+    d_plonk = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
+    d_pos = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
+    d_ops = torch.zeros((n, max(n_ops, 1)), dtype=torch.int32, device=dev)
+    ctx.witness_trace(wp, d_vars, d_acc, n, d_plonk=d_plonk, d_poseidon=d_pos, d_ops=d_ops, d_flow=d_flow, d_flow_swap=d_swap)
+    full = lambda shape: torch.full(shape, -1, dtype=torch.int32, device=dev)  # noqa: E731
+    out = {"roots": full((n, 3, 8)), "draws": full((n, 12)), "ip": full((n, 8, 1 << lp)), "iq": full((n, 8, 1 << lq)), "sums": full((n, 2, 4)),
+           "chan": full((n, 16))}
+    d_ok = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+    ctx.witness_commit(wp, d_plonk, d_pos, d_ops, d_acc, n, b, out["roots"], out["draws"], out["ip"], out["iq"], out["sums"],
+                       d_channel=out["chan"], d_ok=d_ok)
+    ctx.synchronize()
+    res = {k: _u32(v) for k, v in out.items()}
+    res.update(ok=d_ok.cpu().numpy(), accept=d_acc.cpu().numpy(), plonk=_u32(d_plonk), poseidon=_u32(d_pos), ops=_u32(d_ops)[:, :n_ops])
+    return res
+
+
+def _want(dst):
+    from oracle import recursion_circuit as rc
+    nxt = read_proof(dst)
+    d = rc.parse_proof(nxt)
+    tr = ob.transcript_raw(nxt)
+    return d, tr
+
+
+@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+def test_chain_is_what_the_next_fixture_commits(rsv, pin):
+    """The library alone, with K+1's log_blowup_factor and nothing else from K+1: roots = K+1's commitments[0..2], draws =
+    its (z, alpha) and random_coeff, sums = its stmt1; the channel continued with commitments[3] draws its OODS point."""
+    src, dst = pin["src"], pin["dst"]
+    wp = _program(rsv, pin)
+    b = fixture_cfg(dst).log_blowup_factor
+    ctx = rsv.Context(0)
+    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    ctx.close()
+    d, tr = _want(dst)
+    assert r["accept"][0] == 1 and r["ok"][0] == 1
+    for t in range(3):
+        assert r["roots"][0, t].tolist() == [int(x) for x in d.commitments[t]], t
+    assert r["draws"][0].tolist() == tr[4:16].tolist()
+    assert tuple(r["sums"][0, 0].tolist()) == tuple(d.plonk_total_sum) and tuple(r["sums"][0, 1].tolist()) == tuple(d.poseidon_total_sum)
+    ch = C.Channel(ob, r["chan"][0, :8], int(r["chan"][0, 8]))
+    assert not r["chan"][0, 9:].any()
+    ch.mix([int(x) for x in d.commitments[3]])
+    assert list(ch.draw()[0]) == tr[16:20].tolist()
+    wp.close()
+
+
+def test_host_form_equals_the_device_chain(rsv):
+    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
+    wp = _program(rsv, pin)
+    src, dst = pin["src"], pin["dst"]
+    b = fixture_cfg(dst).log_blowup_factor
+    roots, draws, sums, ok, accept, _ = rsv.witness_commit([read_proof(src)], wp, b, _inputs(src))
+    d, tr = _want(dst)
+    assert accept.tolist() == [1] and ok.tolist() == [1]
+    assert roots[0].tolist() == [[int(x) for x in d.commitments[t]] for t in range(3)]
+    assert draws[0].tolist() == tr[4:16].tolist()
+    wp.close()
+
+
+def _trees(wp, r, k):
+    """The three trees' groups of proof k of a chain result, as (log, int64 columns) in commitment order."""
+    lp, lq = wp.trace_sizes()
+    ppre, qpre = wp.preprocessed()
+    _, wops = wp.gates()
+    ppre = ppre.copy()
+    if len(wops):
+        ppre[3, wops[:, 0]] = r["ops"][k]
+    return [[(lp, ppre), (lq, qpre)], [(lp, r["plonk"][k]), (lq, r["poseidon"][k])], [(lp, r["ip"][k]), (lq, r["iq"][k])]]
+
+
+def _commit_dev(rsv, ctx, groups, b, n=1, coeffs=False, lde=False, mask=None, shared=()):
+    """Context.commit_tree of numpy groups [(log, uint32[n or 1, cols, 2^log])] -> (roots, [coeffs], [lde])."""
+    import torch
+    dev = torch.device(DEV)
+    gs, cf, ld = [], [], []
+    for i, (log, cols) in enumerate(groups):
+        cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) % P, dtype=np.uint32)
+        if cols.ndim == 2:
+            cols = cols[None]
+        t = torch.from_numpy(cols.view(np.int32)).to(dev)
+        nc = cols.shape[1]
+        g = {"log_size": log, "d_cols": t, "n_cols": nc, "proof_stride": 0 if i in shared else nc << log}
+        if coeffs:
+            g["d_coeffs"] = torch.full((n, nc, 1 << log), -1, dtype=torch.int32, device=dev)
+            cf.append(g["d_coeffs"])
+        if lde:
+            g["d_lde"] = torch.full((n, nc, 1 << (log + b)), -1, dtype=torch.int32, device=dev)
+            ld.append(g["d_lde"])
+        gs.append(g)
+    d_roots = torch.full((n, 8), -1, dtype=torch.int32, device=dev)
+    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    ctx.commit_tree(gs, n, b, d_roots, d_mask)
+    ctx.synchronize()
+    return _u32(d_roots), [_u32(x) for x in cf], [_u32(x) for x in ld]
+
+
+@pytest.mark.parametrize("src", ["level2-1.bin", "level6-1.bin", "level9-1.bin"])
+def test_coefficients_give_the_sampled_values(rsv, src):
+    """d_coeffs of the three trees evaluated at K+1's OODS point (and at the previous-row point where the mask asks for it)
+    = K+1's 134 sampled values of trees 0-2; the roots from rsv_commit_tree_dev = the chain's."""
+    pin = next(p for p in _pins() if p["src"] == src)
+    wp = _program(rsv, pin)
+    dst = pin["dst"]
+    b = fixture_cfg(dst).log_blowup_factor
+    ctx = rsv.Context(0)
+    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    d, tr = _want(dst)
+    oods = (tuple(int(x) for x in tr[20:24]), tuple(int(x) for x in tr[24:28]))
+    for t, groups in enumerate(_trees(wp, r, 0)):
+        roots, cf, _ = _commit_dev(rsv, ctx, groups, b, coeffs=True)
+        assert roots[0].tolist() == r["roots"][0, t].tolist(), t
+        got = []
+        for (log, _), co in zip(groups, cf):
+            for k in range(co.shape[1]):
+                if t == 2 and k >= 4:
+                    got.append([C.eval_at_point(co[0, k], log, R.prev_row_point(oods, log)), C.eval_at_point(co[0, k], log, oods)])
+                else:
+                    got.append([C.eval_at_point(co[0, k], log, oods)])
+        want = [[tuple(v) for v in col] for col in d.sampled_values[t]]
+        assert got == want, (t, [k for k in range(len(want)) if got[k] != want[k]])
+    ctx.close()
+    wp.close()
+
+
+@pytest.mark.parametrize("src", ["recursive_proof_16_15.bin", "level2-1.bin"])
+def test_lde_at_the_query_positions(rsv, src):
+    """d_lde of the three trees at K+1's query positions = the values K+1 decommits (SinglePathMerkleProof::columns)."""
+    pin = next(p for p in _pins() if p["src"] == src)
+    wp = _program(rsv, pin)
+    dst = pin["dst"]
+    b = fixture_cfg(dst).log_blowup_factor
+    ctx = rsv.Context(0)
+    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    nxt = read_proof(dst)
+    cols = ob.trace_cols(nxt, _inputs(dst))
+    qM, M = C.query_positions(nxt, ob)
+    for t, groups in enumerate(_trees(wp, r, 0)):
+        roots, _, ld = _commit_dev(rsv, ctx, groups, b, lde=True)
+        assert roots[0].tolist() == r["roots"][0, t].tolist(), t
+        layers = {}
+        for (log, _), e in zip(groups, ld):
+            layers[log + b] = e[0] if log + b not in layers else np.concatenate([layers[log + b], e[0]])
+        top = max(layers)
+        for j, q in enumerate(qM):
+            got = C.decommitted(layers, int(q) >> (M - top))
+            assert got == cols[t, j, :len(got)].tolist(), (t, j)
+    ctx.close()
+    wp.close()
+
+
+CASES = [  # (groups as (log, cols, shared), b, n, mask)
+    ([(5, 3, False)], 1, 1, None),
+    ([(4, 2, False), (6, 9, False)], 3, 3, None),
+    ([(6, 9, False), (4, 2, False)], 2, 2, None),
+    ([(5, 4, False), (5, 12, False), (3, 1, False)], 4, 2, None),
+    ([(0, 1, False), (1, 2, False), (2, 3, False), (3, 17, False)], 5, 2, None),
+    ([(7, 8, False)], 9, 1, None),
+    ([(6, 5, True), (5, 7, False)], 2, 4, [1, 0, 1, 1]),
+    ([(3, 10, False), (2, 8, True)], 6, 5, [1, 1, 0, 1, 1]),
+]
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_commit_tree_bit_for_bit(rsv, case):
+    """Random trees: roots, d_coeffs and d_lde = the restatement; a masked proof gets zeros."""
+    spec, b, n, mask = CASES[case]
+    rng = np.random.default_rng(100 + case)
+    groups = [(log, rng.integers(0, P, (1 if sh else n, nc, 1 << log))) for log, nc, sh in spec]
+    shared = {i for i, (_, _, sh) in enumerate(spec) if sh}
+    ctx = rsv.Context(0)
+    roots, cf, ld = _commit_dev(rsv, ctx, groups, b, n=n, coeffs=True, lde=True, mask=mask, shared=shared)
+    ctx.close()
+    for p in range(n):
+        if mask is not None and not mask[p]:
+            assert not roots[p].any() and all(not c[p].any() for c in cf) and all(not e[p].any() for e in ld), p
+            continue
+        mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
+        for (log, cols), co, e in zip(mine, cf, ld):
+            assert np.array_equal(co[p], C.interpolate(cols, log)), p
+            assert np.array_equal(e[p], C.evaluate(co[p], log, log + b)), p
+        assert roots[p].tolist() == C.commit(mine, b, ob).tolist(), p
+
+
+def test_workspace_groups_and_one_proof(rsv):
+    """A batch cut into passes (fewer blocks, then fewer proofs) under a 1 MB workspace budget equals the uncut batch and
+    the restatement; n = 1 equals proof 0 of the batch."""
+    rng = np.random.default_rng(9)
+    n, b = 40, 4
+    groups = [(9, rng.integers(0, P, (n, 6, 1 << 9))), (8, rng.integers(0, P, (n, 11, 1 << 8)))]
+    ctx = rsv.Context(0)
+    whole, _, _ = _commit_dev(rsv, ctx, groups, b, n=n)
+    ctx.set_option("ws_budget_mb", 1)
+    cut, _, _ = _commit_dev(rsv, ctx, groups, b, n=n)
+    one, _, _ = _commit_dev(rsv, ctx, [(log, c[:1]) for log, c in groups], b, n=1)
+    ctx.close()
+    assert np.array_equal(whole, cut)
+    assert np.array_equal(one[0], whole[0])
+    for p in (0, 17, 39):
+        assert whole[p].tolist() == C.commit([(log, c[p]) for log, c in groups], b, ob).tolist(), p
+
+
+def test_mixed_batch_with_a_rejected_proof(rsv):
+    """Five proofs of one shape, the third tampered (rejected): it gets zeros everywhere and d_ok = 0; every output element
+    of the others is written and equals its solo run."""
+    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
+    wp = _program(rsv, pin)
+    src = pin["src"]
+    b = fixture_cfg(pin["dst"]).log_blowup_factor
+    proof = read_proof(src)
+    batch = [proof, proof, ob.tamper(proof, 5), proof, proof]
+    ctx = rsv.Context(0)
+    r = _chain(rsv, ctx, wp, batch, _inputs(src), b)
+    solo = _chain(rsv, ctx, wp, [proof], _inputs(src), b)
+    ctx.close()
+    assert r["accept"].tolist() == [1, 1, 0, 1, 1] and r["ok"].tolist() == [1, 1, 0, 1, 1]
+    for key in ("roots", "draws", "ip", "iq", "sums", "chan"):
+        assert not r[key][2].any(), key
+        for k in (0, 1, 3, 4):
+            assert np.array_equal(r[key][k], solo[key][0]), (key, k)
+    wp.close()
+
+
+def test_device_refusals(rsv):
+    """RSV_E_SIZE with nothing written for a misaligned pointer, log_blowup 0 or above the limit, log + b above
+    RSV_MAX_LOG_SIZE, too many groups; RSV_E_NULL for missing columns."""
+    import torch
+    dev = torch.device(DEV)
+    ctx = rsv.Context(0)
+    cols = torch.zeros((1, 2, 16), dtype=torch.int32, device=dev)
+    raw = torch.zeros(4 * 32 + 8, dtype=torch.uint8, device=dev)
+    roots = torch.full((1, 8), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+
+    def refused(code, groups, b=2, d_roots=roots):
+        with pytest.raises(rsv.RsvError) as e:
+            ctx.commit_tree(groups, 1, b, d_roots)
+        assert e.value.code == code
+
+    g = {"log_size": 4, "d_cols": cols, "n_cols": 2}
+    refused(-2, [g], b=0)
+    refused(-2, [g], b=17)
+    refused(-2, [dict(g, log_size=29)], b=2)
+    refused(-2, [g] * 9)
+    refused(-2, [dict(g, n_cols=0)])
+    refused(-1, [dict(g, d_cols=None)])
+    refused(-2, [dict(g, d_cols=raw[1:])])
+    refused(-2, [g], d_roots=raw[2:34])
+    ctx.synchronize()
+    assert bool((roots == 0x5A5A5A5A).all())
+    ctx.commit_tree([g], 1, 2, roots)
+    ctx.synchronize()
+    ctx.close()
