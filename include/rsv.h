@@ -636,13 +636,14 @@ int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, cons
  *
  * From the trace columns rsv_witness_trace_dev wrote (d_plonk [n][12][2^lp], d_poseidon [n][48][2^lq]), d_accept and the
  * lookup elements the next proof's transcript draws after trees 0 and 1, d_lookup [n][8]: z, then alpha (QM31 words; any
- * u32 is taken mod P).  Built programs only (RSV_E_SIZE otherwise); the 8 + 8 preprocessed columns the relations read go
- * to the device on the first call.  Outputs: d_int_plonk [n][8][2^lp], d_int_poseidon [n][8][2^lq], d_sums [n][2][4] (the
- * Plonk then the Poseidon claimed sum), d_ok [n] (may be NULL): 1 iff the proof was accepted and no denominator of either
- * component is zero.  A proof with d_ok[i] == 0 (rejected, or a zero denominator) gets zero columns and zero sums; the
- * other proofs of the batch are unaffected.  Every element is written.  NULL pointers (but d_ok): RSV_E_NULL; d_plonk,
- * d_poseidon, d_lookup, d_sums 4-byte and d_int_plonk, d_int_poseidon 8-byte aligned, RSV_E_SIZE otherwise.  Enqueued on
- * the context's stream; the context's workspace grows (with a synchronisation) only when a batch needs more. */
+ * u32 is taken mod P).  Built programs only (RSV_E_SIZE otherwise); the program's 10 + 40 preprocessed columns, shared with
+ * rsv_witness_commit_dev, go to the device on the first call.  Outputs: d_int_plonk [n][8][2^lp], d_int_poseidon
+ * [n][8][2^lq], d_sums [n][2][4] (the Plonk then the Poseidon claimed sum), d_ok [n] (may be NULL): 1 iff the proof was
+ * accepted and no denominator of either component is zero.  A proof with d_ok[i] == 0 (rejected, or a zero denominator)
+ * gets zero columns and zero sums; the other proofs of the batch are unaffected.  Every element is written.  NULL pointers
+ * (but d_ok): RSV_E_NULL; d_plonk, d_poseidon, d_lookup, d_sums 4-byte and d_int_plonk, d_int_poseidon 8-byte aligned,
+ * RSV_E_SIZE otherwise.  Enqueued on the context's stream; the context's workspace grows (with a synchronisation) only
+ * when a batch needs more. */
 int rsv_witness_interaction_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                                 const uint8_t* d_accept, const uint32_t* d_lookup, size_t n, uint32_t* d_int_plonk,
                                 uint32_t* d_int_poseidon, uint32_t* d_sums, uint8_t* d_ok);

@@ -688,19 +688,25 @@ class WitnessProgram:
         return int(out.value)
 
 
+def _witness_batch(proofs: Sequence[bytes], program: WitnessProgram, inputs):
+    """What the rsv_witness_* host forms share: their leading arguments (program, blob, offsets, n, cfg, pi, n_pi), n, and
+    the accept and reason arrays they fill."""
+    blob, offsets = pack(proofs)
+    n = len(proofs)
+    items = list(inputs)
+    lead = (program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), make_inputs(items),
+            len(items))
+    return lead, n, np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+
 def witness(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_INPUTS, device: int = 0, with_flow: bool = False):
     """`variables` of the recursion circuit for every proof of a batch (rsv_witness_eval): uint32[n, n_vars, 4], accept, reason
     [, flow uint32[n, flow_count, 32], flow_swap uint8[n, flow_count] with with_flow]."""
-    blob, offsets = pack(proofs)
-    n = len(proofs)
+    lead, n, accept, reason = _witness_batch(proofs, program, inputs)
     variables = np.zeros((n, program.n_vars, 4), np.uint32)
-    accept = np.zeros(n, np.uint8)
-    reason = np.zeros(n, np.uint8)
     flow = np.zeros((n, program.shape.flow_count, 32), np.uint32) if with_flow else None
     swap = np.zeros((n, program.shape.flow_count), np.uint8) if with_flow else None
-    pi = make_inputs(inputs)
-    _check(lib.rsv_witness_eval(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), pi,
-                                len(list(inputs)), variables.ctypes.data_as(_u32p), flow.ctypes.data_as(_u32p) if with_flow else None,
+    _check(lib.rsv_witness_eval(*lead, variables.ctypes.data_as(_u32p), flow.ctypes.data_as(_u32p) if with_flow else None,
                                 swap.ctypes.data_as(_u8p) if with_flow else None, accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device),
            "rsv_witness_eval")
     return (variables, accept, reason, flow, swap) if with_flow else (variables, accept, reason)
@@ -717,18 +723,13 @@ def trace_log_sizes(n_rows: int, n_flow: int):
 def witness_trace(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_INPUTS, device: int = 0):
     """The trace columns of the recursion circuit for every proof of a batch (rsv_witness_trace): plonk uint32[n, 12, 2^lp],
     poseidon uint32[n, 48, 2^lq], ops uint32[n, n_witness_ops], accept, reason."""
-    blob, offsets = pack(proofs)
-    n = len(proofs)
+    lead, n, accept, reason = _witness_batch(proofs, program, inputs)
     lp, lq = program.trace_sizes()
     n_ops = len(program.gates()[1])
     plonk = np.zeros((n, 12, 1 << lp), np.uint32)
     poseidon = np.zeros((n, 48, 1 << lq), np.uint32)
     ops = np.zeros((n, n_ops), np.uint32)
-    accept = np.zeros(n, np.uint8)
-    reason = np.zeros(n, np.uint8)
-    pi = make_inputs(inputs)
-    _check(lib.rsv_witness_trace(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), pi,
-                                 len(list(inputs)), plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p), ops.ctypes.data_as(_u32p),
+    _check(lib.rsv_witness_trace(*lead, plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p), ops.ctypes.data_as(_u32p),
                                  accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_witness_trace")
     return plonk, poseidon, ops, accept, reason
 
@@ -747,21 +748,16 @@ def witness_interaction(proofs: Sequence[bytes], program: WitnessProgram, lookup
     """The interaction (logup) columns of the recursion circuit for every proof of a batch (rsv_witness_interaction), with the
     next proof's lookup elements `lookup` = (z, alpha) for all proofs or [n] of them: int_plonk uint32[n, 8, 2^lp],
     int_poseidon uint32[n, 8, 2^lq], sums uint32[n, 2, 4] (the Plonk and Poseidon claimed sums), ok, accept, reason."""
-    blob, offsets = pack(proofs)
-    n = len(proofs)
+    lead, n, accept, reason = _witness_batch(proofs, program, inputs)
     lk = _lookup_array(lookup, n)
     lp, lq = program.trace_sizes()
     int_plonk = np.zeros((n, 8, 1 << lp), np.uint32)
     int_poseidon = np.zeros((n, 8, 1 << lq), np.uint32)
     sums = np.zeros((n, 2, 4), np.uint32)
     ok = np.zeros(n, np.uint8)
-    accept = np.zeros(n, np.uint8)
-    reason = np.zeros(n, np.uint8)
-    pi = make_inputs(inputs)
-    _check(lib.rsv_witness_interaction(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(),
-                                       pi, len(list(inputs)), lk.ctypes.data_as(_u32p), int_plonk.ctypes.data_as(_u32p),
-                                       int_poseidon.ctypes.data_as(_u32p), sums.ctypes.data_as(_u32p), ok.ctypes.data_as(_u8p),
-                                       accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_witness_interaction")
+    _check(lib.rsv_witness_interaction(*lead, lk.ctypes.data_as(_u32p), int_plonk.ctypes.data_as(_u32p), int_poseidon.ctypes.data_as(_u32p),
+                                       sums.ctypes.data_as(_u32p), ok.ctypes.data_as(_u8p), accept.ctypes.data_as(_u8p),
+                                       reason.ctypes.data_as(_u8p), device), "rsv_witness_interaction")
     return int_plonk, int_poseidon, sums, ok, accept, reason
 
 
@@ -769,19 +765,14 @@ def witness_commit(proofs: Sequence[bytes], program: WitnessProgram, log_blowup:
     """Trees 0, 1 and 2 of the next proof for every proof of a batch and the transcript draws between them
     (rsv_witness_commit): roots uint32[n, 3, 8], draws uint32[n, 12] (z, alpha, random_coeff), sums uint32[n, 2, 4], ok,
     accept, reason."""
-    blob, offsets = pack(proofs)
-    n = len(proofs)
+    lead, n, accept, reason = _witness_batch(proofs, program, inputs)
     roots = np.zeros((n, 3, 8), np.uint32)
     draws = np.zeros((n, 12), np.uint32)
     sums = np.zeros((n, 2, 4), np.uint32)
     ok = np.zeros(n, np.uint8)
-    accept = np.zeros(n, np.uint8)
-    reason = np.zeros(n, np.uint8)
-    pi = make_inputs(inputs)
-    _check(lib.rsv_witness_commit(program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), pi,
-                                  len(list(inputs)), log_blowup, roots.ctypes.data_as(_u32p), draws.ctypes.data_as(_u32p),
-                                  sums.ctypes.data_as(_u32p), ok.ctypes.data_as(_u8p), accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p),
-                                  device), "rsv_witness_commit")
+    _check(lib.rsv_witness_commit(*lead, log_blowup, roots.ctypes.data_as(_u32p), draws.ctypes.data_as(_u32p), sums.ctypes.data_as(_u32p),
+                                  ok.ctypes.data_as(_u8p), accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device),
+           "rsv_witness_commit")
     return roots, draws, sums, ok, accept, reason
 
 

@@ -163,34 +163,6 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
     return RSV_OK;
 }
 
-// Tree 0's preprocessed columns of the program ([10][2^lp] then [40][2^lq]), uploaded once.
-int commit_upload(rsv_witness_program* prog) {
-    int rc = trace_upload(prog);
-    if (rc != RSV_OK) return rc;
-    std::lock_guard<std::mutex> lk(prog->trace_mu);
-    if (prog->d_commit_pre) return RSV_OK;
-    const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
-    const size_t N = (size_t)1 << lp, Q = (size_t)1 << lq;
-    std::vector<uint32_t> pre;
-    try {
-        pre.resize(rsv::trace::PLONK_PRE_COLS * N + rsv::trace::POSEIDON_PRE_COLS * Q);
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-    rc = rsv::trace::preprocessed(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5, lp, lq,
-                                  rsv::RC_FULL_K, rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, pre.data(),
-                                  pre.data() + rsv::trace::PLONK_PRE_COLS * N);
-    if (rc != RSV_OK) return rc;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), pre.size() * 4) != hipSuccess) return RSV_E_DEVICE;
-    if (hipMemcpy(d, pre.data(), pre.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return RSV_E_DEVICE;
-    }
-    prog->d_commit_pre = d;
-    return RSV_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -200,21 +172,18 @@ int rsv_commit_tree_dev(rsv_ctx* c, const rsv_commit_group* groups, size_t n_gro
     return commit_tree(c, groups, n_groups, n, log_blowup, d_mask, d_roots, 8);
 }
 
-int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* cprog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                            const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
                            uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
                            uint8_t* d_ok) {
-    if (!c || !cprog || !d_plonk || !d_poseidon || !d_accept || !d_roots || !d_draws || !d_int_plonk || !d_int_poseidon || !d_sums)
+    if (!c || !prog || !d_plonk || !d_poseidon || !d_accept || !d_roots || !d_draws || !d_int_plonk || !d_int_poseidon || !d_sums)
         return RSV_E_NULL;
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
     if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_roots & 3) ||
         ((uintptr_t)d_draws & 3) || ((uintptr_t)d_int_plonk & 7) || ((uintptr_t)d_int_poseidon & 7) || ((uintptr_t)d_sums & 3) ||
         ((uintptr_t)d_channel & 3))
         return RSV_E_SIZE;
-    if (cprog->device != c->device || n > (1u << 20)) return RSV_E_SIZE;
-    rsv_witness_program* prog = const_cast<rsv_witness_program*>(cprog);  // the lazily uploaded device copies only
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = commit_upload(prog);
+    int rc = chain_begin(c, prog, n, true);
     if (rc != RSV_OK) return rc;
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     if (std::max(lp, lq) + log_blowup > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
@@ -236,7 +205,7 @@ int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* cprog, const u
     uint32_t* chan = cv.take<uint32_t>(n * 16);
     uint8_t* ok = cv.take<uint8_t>(n);
     hipStream_t st = c->stream;
-    const uint32_t* pre = prog->d_commit_pre;
+    const uint32_t* pre = prog->d_trace_pre;
     const uint32_t* qpre = pre + rsv::trace::PLONK_PRE_COLS * N;
     // tree 0: the op column (column 3 of the Plonk preprocessed ones) follows the proof, the other 49 are the program's
     hipLaunchKernelGGL(rsv::k_cm_op_column, dim3(grid_for(n * N, 256)), dim3(256), 0, st, pre + 3 * N, lp, (uint32_t)n, ops_col);
@@ -275,32 +244,14 @@ int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, con
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
     if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_commit_dev
     if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    struct Guard { rsv_ctx* c; ~Guard() { rsv_ctx_destroy(c); } } guard{c};
-    c->opt.witness_layout = 2;  // as rsv_witness_trace: no transpose, no second copy
-    rc = commit_upload(const_cast<rsv_witness_program*>(prog));
+    WitnessStage st;
+    int rc = st.open(offsets, n, device, true);
+    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
     if (rc != RSV_OK) return rc;
     if (std::max(prog->trace_lp, prog->trace_lq) + log_blowup > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
     const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
     const size_t n_ops = prog->witness_ops.size() / 3;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dvars, dacc, dreason, dflow, dswap, dplonk, dposeidon, dops, dip, diq, droots, ddraws, dsums, dok;
-    const size_t flow_records = n * (size_t)prog->shape.flow_count;
-    HIP_TRY(dflow.alloc(flow_records * 128));
-    HIP_TRY(dswap.alloc(flow_records));
-    HIP_TRY(dblob.alloc(total));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dvars.alloc(n * (size_t)prog->n_vars * 16));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
+    DevBuf dplonk, dposeidon, dops, dip, diq, droots, ddraws, dsums, dok;
     HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
     HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
     HIP_TRY(dops.alloc(n * n_ops * 4));
@@ -310,26 +261,20 @@ int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, con
     HIP_TRY(ddraws.alloc(n * 48));
     HIP_TRY(dsums.alloc(n * 32));
     HIP_TRY(dok.alloc(n));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    rc = rsv_witness_eval_dev(c, prog, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, cfg, pi, n_pi, dvars.as<uint32_t>(),
-                              dflow.as<uint32_t>(), dswap.as<uint8_t>(), dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_witness_trace_dev(c, prog, dvars.as<const uint32_t>(), dflow.as<const uint32_t>(), dswap.as<const uint8_t>(),
-                               dacc.as<const uint8_t>(), n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), dops.as<uint32_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_witness_commit_dev(c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), dops.as<const uint32_t>(),
-                                dacc.as<const uint8_t>(), n, log_blowup, droots.as<uint32_t>(), ddraws.as<uint32_t>(), dip.as<uint32_t>(),
-                                diq.as<uint32_t>(), dsums.as<uint32_t>(), nullptr, dok.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_ctx_synchronize(c);
+    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+    if (rc == RSV_OK)
+        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(),
+                                   dops.as<uint32_t>());
+    if (rc == RSV_OK)
+        rc = rsv_witness_commit_dev(st.c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), dops.as<const uint32_t>(),
+                                    st.accept, n, log_blowup, droots.as<uint32_t>(), ddraws.as<uint32_t>(), dip.as<uint32_t>(),
+                                    diq.as<uint32_t>(), dsums.as<uint32_t>(), nullptr, dok.as<uint8_t>());
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
     HIP_TRY(hipMemcpy(roots, droots.p, n * 96, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(draws, ddraws.p, n * 48, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sums, dsums.p, n * 32, hipMemcpyDeviceToHost));
     if (ok) HIP_TRY(hipMemcpy(ok, dok.p, n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost));
-    if (reason) HIP_TRY(hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost));
     return RSV_OK;
 }
 

@@ -4,43 +4,6 @@
 
 namespace {
 
-// The preprocessed columns the relations read, [8][2^lp] then [8][2^lq] on the device, uploaded once (after
-// trace_upload, which checks the program and sets lp, lq).
-int interaction_upload(rsv_witness_program* prog) {
-    int rc = trace_upload(prog);
-    if (rc != RSV_OK) return rc;
-    std::lock_guard<std::mutex> lk(prog->trace_mu);
-    if (prog->d_int_pre) return RSV_OK;
-    const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
-    const size_t N = (size_t)1 << lp, Q = (size_t)1 << lq;
-    std::vector<uint32_t> plonk, poseidon, compact;
-    try {
-        plonk.resize(rsv::trace::PLONK_PRE_COLS * N);
-        poseidon.resize(rsv::trace::POSEIDON_PRE_COLS * Q);
-        compact.resize(rsv::INT_PRE_COLS * (N + Q));
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-    rc = rsv::trace::preprocessed(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5, lp, lq,
-                                  rsv::RC_FULL_K, rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, plonk.data(), poseidon.data());
-    if (rc != RSV_OK) return rc;
-    // Plonk: a_wire, b_wire, c_wire, mult_a, mult_b, mult_c, poseidon_wire, mult_poseidon (op and enforce_c_m31 are read
-    // by no relation); Poseidon: is_first, is_last, round_id, rc0[0], external_idx_1 / _2, their nonzero flags.
-    static const uint32_t PC[8] = {0, 1, 2, 4, 5, 6, 7, 8}, QC[8] = {0, 1, 3, 4, 36, 37, 38, 39};
-    for (int k = 0; k < 8; k++) {
-        std::memcpy(compact.data() + k * N, plonk.data() + PC[k] * N, N * 4);
-        std::memcpy(compact.data() + 8 * N + k * Q, poseidon.data() + QC[k] * Q, Q * 4);
-    }
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), compact.size() * 4) != hipSuccess) return RSV_E_DEVICE;
-    if (hipMemcpy(d, compact.data(), compact.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(d);
-        return RSV_E_DEVICE;
-    }
-    prog->d_int_pre = d;
-    return RSV_OK;
-}
-
 // Chunk bits of a component of 2^log rows for a batch of n: 2^(B-1) scan lanes per (proof, component), aiming at about
 // 2^17 in all (2 components x n proofs x 2^(B-1)) but at least 64 and at most 2^(INT_MAX_B - 1) = 2 048 per proof, so a
 // batch of fewer than 32 proofs has fewer (4 096 for one proof; the k_int_offsets scan of 2^B sums stays one workgroup);
@@ -57,17 +20,14 @@ uint32_t interaction_chunk_bits(uint32_t log, size_t n) {
 
 extern "C" {
 
-int rsv_witness_interaction_dev(rsv_ctx* c, const rsv_witness_program* cprog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+int rsv_witness_interaction_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                                 const uint8_t* d_accept, const uint32_t* d_lookup, size_t n, uint32_t* d_int_plonk,
                                 uint32_t* d_int_poseidon, uint32_t* d_sums, uint8_t* d_ok) {
-    if (!c || !cprog || !d_plonk || !d_poseidon || !d_accept || !d_lookup || !d_int_plonk || !d_int_poseidon || !d_sums) return RSV_E_NULL;
+    if (!c || !prog || !d_plonk || !d_poseidon || !d_accept || !d_lookup || !d_int_plonk || !d_int_poseidon || !d_sums) return RSV_E_NULL;
     if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_lookup & 3) || ((uintptr_t)d_int_plonk & 7) ||
         ((uintptr_t)d_int_poseidon & 7) || ((uintptr_t)d_sums & 3))
         return RSV_E_SIZE;
-    if (cprog->device != c->device || n > (1u << 20)) return RSV_E_SIZE;
-    rsv_witness_program* prog = const_cast<rsv_witness_program*>(cprog);  // the lazily uploaded device copies only
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = interaction_upload(prog);
+    int rc = chain_begin(c, prog, n, true);
     if (rc != RSV_OK) return rc;
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     if (lp < 2 || lq < 2) return RSV_E_SIZE;  // one chunk bit at least
@@ -97,7 +57,7 @@ int rsv_witness_interaction_dev(rsv_ctx* c, const rsv_witness_program* cprog, co
     a.ok = d_ok;
     uint4* shifts = cv.take<uint4>(2 * n);
     rsv::IntComp& cp = a.c[0];
-    cp.pre = prog->d_int_pre;
+    cp.pre = prog->d_trace_pre;
     cp.trace = d_plonk;
     cp.n_trace = rsv::PLONK_COLS_K;
     cp.log = lp;
@@ -108,7 +68,7 @@ int rsv_witness_interaction_dev(rsv_ctx* c, const rsv_witness_program* cprog, co
     cp.shift = shifts;
     cp.sums = d_sums;
     rsv::IntComp& cq = a.c[1];
-    cq.pre = prog->d_int_pre + rsv::INT_PRE_COLS * N;
+    cq.pre = prog->d_trace_pre + rsv::trace::PLONK_PRE_COLS * N;
     cq.trace = d_poseidon;
     cq.n_trace = rsv::POSEIDON_COLS_K;
     cq.log = lq;
@@ -135,30 +95,12 @@ int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob
     if (!prog || (n && (!blob || !offsets || !lookup || !int_plonk || !int_poseidon || !sums || !accept))) return RSV_E_NULL;
     if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_interaction_dev
     if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    struct Guard { rsv_ctx* c; ~Guard() { rsv_ctx_destroy(c); } } guard{c};
-    c->opt.witness_layout = 2;  // as rsv_witness_trace: no transpose, no second copy
-    rc = interaction_upload(const_cast<rsv_witness_program*>(prog));
+    WitnessStage st;
+    int rc = st.open(offsets, n, device, true);
+    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
     if (rc != RSV_OK) return rc;
     const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dvars, dacc, dreason, dflow, dswap, dplonk, dposeidon, dlookup, dip, diq, dsums, dok;
-    const size_t flow_records = n * (size_t)prog->shape.flow_count;
-    HIP_TRY(dflow.alloc(flow_records * 128));
-    HIP_TRY(dswap.alloc(flow_records));
-    HIP_TRY(dblob.alloc(total));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dvars.alloc(n * (size_t)prog->n_vars * 16));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
+    DevBuf dplonk, dposeidon, dlookup, dip, diq, dsums, dok;
     HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
     HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
     HIP_TRY(dlookup.alloc(n * 32));
@@ -166,27 +108,20 @@ int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob
     HIP_TRY(diq.alloc(n * rsv::INT_COLS * Q * 4));
     HIP_TRY(dsums.alloc(n * 32));
     HIP_TRY(dok.alloc(n));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(dlookup.p, lookup, n * 32, hipMemcpyHostToDevice));
-    rc = rsv_witness_eval_dev(c, prog, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, cfg, pi, n_pi, dvars.as<uint32_t>(),
-                              dflow.as<uint32_t>(), dswap.as<uint8_t>(), dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_witness_trace_dev(c, prog, dvars.as<const uint32_t>(), dflow.as<const uint32_t>(), dswap.as<const uint8_t>(),
-                               dacc.as<const uint8_t>(), n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), nullptr);
-    if (rc != RSV_OK) return rc;
-    rc = rsv_witness_interaction_dev(c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), dacc.as<const uint8_t>(),
-                                     dlookup.as<const uint32_t>(), n, dip.as<uint32_t>(), diq.as<uint32_t>(), dsums.as<uint32_t>(),
-                                     dok.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_ctx_synchronize(c);
+    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+    if (rc == RSV_OK)
+        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), nullptr);
+    if (rc == RSV_OK)
+        rc = rsv_witness_interaction_dev(st.c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), st.accept,
+                                         dlookup.as<const uint32_t>(), n, dip.as<uint32_t>(), diq.as<uint32_t>(), dsums.as<uint32_t>(),
+                                         dok.as<uint8_t>());
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
     HIP_TRY(hipMemcpy(int_plonk, dip.p, n * rsv::INT_COLS * N * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(int_poseidon, diq.p, n * rsv::INT_COLS * Q * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(sums, dsums.p, n * 32, hipMemcpyDeviceToHost));
     if (ok) HIP_TRY(hipMemcpy(ok, dok.p, n, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost));
-    if (reason) HIP_TRY(hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost));
     return RSV_OK;
 }
 

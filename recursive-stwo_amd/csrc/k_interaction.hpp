@@ -34,17 +34,17 @@
 // nothing else, since no inverse is shared across rows.
 #pragma once
 #include "field.hpp"
+#include "trace_host.hpp"
 
 namespace rsv {
 
 constexpr uint32_t INT_COLS = 8;       // M31 columns per component
-constexpr uint32_t INT_PRE_COLS = 8;   // preprocessed columns a component's relations read
 constexpr uint32_t INT_MAX_B = 12;     // at most 4 096 chunks per (proof, component): 4 per thread of k_int_offsets
 constexpr uint32_t INT_OFF_THREADS = 1024;
 
 // Per component.
 struct IntComp {
-    const uint32_t* pre;      // [8][2^log]: the relation's preprocessed columns (interaction_api.inc)
+    const uint32_t* pre;      // [10 | 40][2^log]: the component's preprocessed columns (rsv_trace_preprocessed)
     const uint32_t* trace;    // [n][n_trace][2^log]
     uint32_t n_trace, log, B;
     uint32_t* out;            // [n][8][2^log]
@@ -102,27 +102,30 @@ __global__ __launch_bounds__(256) void k_int_prep(IntArgs a) {
 }
 
 // ---------------------------------------------------------------- fractions
-// Plonk preprocessed (compact): a_wire, b_wire, c_wire, mult_a, mult_b, mult_c, poseidon_wire, mult_poseidon.
+// Plonk preprocessed: a_wire, b_wire, c_wire, mult_a, mult_b, mult_c, poseidon_wire, mult_poseidon.
 __device__ __forceinline__ void int_plonk_row(const IntComp& c, const uint32_t* t, const uint32_t* w, size_t N, QM31 z, QM31 alpha,
                                               QM31 alpha2, QM31& p0, QM31& q0, QM31& p1, QM31& q1) {
+    using namespace trace;
     const QM31 av = q_of4(t[0], t[N], t[2 * N], t[3 * N]), bv = q_of4(t[4 * N], t[5 * N], t[6 * N], t[7 * N]);
     const QM31 cv = q_of4(t[8 * N], t[9 * N], t[10 * N], t[11 * N]);
-    const QM31 qa = q_sub(q_add(av, q_mul_m(alpha, w[0])), z);
-    const QM31 qb = q_sub(q_add(bv, q_mul_m(alpha, w[N])), z);
-    const QM31 qc = q_sub(q_add(cv, q_mul_m(alpha, w[2 * N])), z);
-    const QM31 qp = den_mqq(w[6 * N], av, bv, alpha, alpha2, z);
-    p0 = q_add(q_mul_m(qb, w[3 * N]), q_mul_m(qa, w[4 * N]));
-    p1 = q_add(q_mul_m(qp, w[5 * N]), q_mul_m(qc, m_neg(w[7 * N])));
+    const QM31 qa = q_sub(q_add(av, q_mul_m(alpha, w[PLONK_A_WIRE * N])), z);
+    const QM31 qb = q_sub(q_add(bv, q_mul_m(alpha, w[PLONK_B_WIRE * N])), z);
+    const QM31 qc = q_sub(q_add(cv, q_mul_m(alpha, w[PLONK_C_WIRE * N])), z);
+    const QM31 qp = den_mqq(w[PLONK_POSEIDON_WIRE * N], av, bv, alpha, alpha2, z);
+    p0 = q_add(q_mul_m(qb, w[PLONK_MULT_A * N]), q_mul_m(qa, w[PLONK_MULT_B * N]));
+    p1 = q_add(q_mul_m(qp, w[PLONK_MULT_C * N]), q_mul_m(qc, m_neg(w[PLONK_MULT_POSEIDON * N])));
     q0 = q_mul(qa, qb);
     q1 = q_mul(qc, qp);
 }
 
-// Poseidon preprocessed (compact): is_first, is_last, round_id, rc0[0] (the swap address), external_idx_1, external_idx_2,
+// Poseidon preprocessed: is_first, is_last, round_id, rc0[0] (the swap address), external_idx_1, external_idx_2,
 // is_external_idx_1_nonzero, is_external_idx_2_nonzero.  Trace: in[16], intermediate[16], out[16].
 __device__ __forceinline__ void int_poseidon_row(const IntComp& c, const uint32_t* t, const uint32_t* w, size_t N, QM31 z, QM31 alpha,
                                                  QM31 alpha2, QM31& p0, QM31& q0, QM31& p1, QM31& q1) {
-    const uint32_t first = w[0], last = w[N], rid2 = m_dbl(w[2 * N]), addr = w[3 * N];
-    const uint32_t ext1 = w[4 * N], ext2 = w[5 * N], nz1 = w[6 * N], nz2 = w[7 * N];
+    using namespace trace;
+    const uint32_t first = w[POSEIDON_IS_FIRST * N], last = w[POSEIDON_IS_LAST * N], rid2 = m_dbl(w[POSEIDON_ROUND_ID * N]);
+    const uint32_t addr = w[POSEIDON_SWAP_ADDR * N], ext1 = w[POSEIDON_EXT_WIRE_1 * N], ext2 = w[POSEIDON_EXT_WIRE_2 * N];
+    const uint32_t nz1 = w[POSEIDON_EXT_NZ_1 * N], nz2 = w[POSEIDON_EXT_NZ_2 * N];
     const uint32_t nf = m_sub(1, first), nl = m_sub(1, last);
     auto st = [&](int k) { return q_of4(t[(size_t)k * N], t[(size_t)(k + 1) * N], t[(size_t)(k + 2) * N], t[(size_t)(k + 3) * N]); };
     // in_left, in_right: ids 2 round_id (+1) unless the first round (the external wire)

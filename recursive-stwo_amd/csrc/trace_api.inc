@@ -4,36 +4,67 @@
 
 namespace {
 
-// The program's padded wires and witness ops on the device, uploaded once (built programs only: RSV_E_SIZE otherwise).
-int trace_upload(rsv_witness_program* prog) {
+// The program's device copies, each uploaded once (built programs only: RSV_E_SIZE otherwise): the padded wires and the
+// witness ops, then, with `with_pre`, the 10 + 40 preprocessed columns that the interaction relations and tree 0 read.
+int program_upload(rsv_witness_program* prog, bool with_pre) {
     std::lock_guard<std::mutex> lk(prog->trace_mu);
-    if (prog->d_trace_wires) return RSV_OK;
-    if (prog->gates.empty() || prog->flow_wires.empty()) return RSV_E_SIZE;
-    const size_t n_rows = prog->gates.size() / 6;
-    for (size_t i = 0; i < n_rows; i++)  // every index the kernels gather with
-        for (int k = 0; k < 3; k++)
-            if (prog->gates[i * 6 + k] >= prog->n_vars) return RSV_E_RANGE;
-    for (size_t i = 0; i < prog->witness_ops.size() / 3; i++)
-        if (prog->witness_ops[i * 3 + 1] >= prog->n_vars) return RSV_E_RANGE;
-    uint32_t lp = 0, lq = 0;
-    int rc = rsv::trace::log_sizes(n_rows, prog->flow_wires.size() / 5, lp, lq);
+    if (!prog->d_trace_wires) {
+        if (prog->gates.empty() || prog->flow_wires.empty()) return RSV_E_SIZE;
+        const size_t n_rows = prog->gates.size() / 6;
+        for (size_t i = 0; i < n_rows; i++)  // every index the kernels gather with
+            for (int k = 0; k < 3; k++)
+                if (prog->gates[i * 6 + k] >= prog->n_vars) return RSV_E_RANGE;
+        for (size_t i = 0; i < prog->witness_ops.size() / 3; i++)
+            if (prog->witness_ops[i * 3 + 1] >= prog->n_vars) return RSV_E_RANGE;
+        uint32_t lp = 0, lq = 0;
+        int rc = rsv::trace::log_sizes(n_rows, prog->flow_wires.size() / 5, lp, lq);
+        if (rc != RSV_OK) return rc;
+        const std::vector<uint32_t> wires = rsv::trace::padded_wires(prog->gates.data(), n_rows, lp);
+        uint32_t *dw = nullptr, *dops = nullptr;
+        const size_t ops_bytes = prog->witness_ops.size() * 4;
+        if (hipMalloc(reinterpret_cast<void**>(&dw), wires.size() * 4) != hipSuccess) return RSV_E_DEVICE;
+        if (hipMemcpy(dw, wires.data(), wires.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+            hipMalloc(reinterpret_cast<void**>(&dops), ops_bytes ? ops_bytes : 4) != hipSuccess ||
+            (ops_bytes && hipMemcpy(dops, prog->witness_ops.data(), ops_bytes, hipMemcpyHostToDevice) != hipSuccess)) {
+            (void)hipFree(dw);
+            if (dops) (void)hipFree(dops);
+            return RSV_E_DEVICE;
+        }
+        prog->d_trace_ops = dops;
+        prog->trace_lp = lp;
+        prog->trace_lq = lq;
+        prog->d_trace_wires = dw;
+    }
+    if (!with_pre || prog->d_trace_pre) return RSV_OK;
+    const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
+    const size_t N = (size_t)1 << lp, Q = (size_t)1 << lq;
+    std::vector<uint32_t> pre;
+    int rc;
+    try {
+        pre.resize(rsv::trace::PLONK_PRE_COLS * N + rsv::trace::POSEIDON_PRE_COLS * Q);
+        rc = rsv::trace::preprocessed(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5, lp, lq,
+                                      rsv::RC_FULL_K, rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, pre.data(),
+                                      pre.data() + rsv::trace::PLONK_PRE_COLS * N);
+    } catch (const std::bad_alloc&) {
+        return RSV_E_NOMEM;
+    }
     if (rc != RSV_OK) return rc;
-    const std::vector<uint32_t> wires = rsv::trace::padded_wires(prog->gates.data(), n_rows, lp);
-    uint32_t *dw = nullptr, *dops = nullptr;
-    const size_t ops_bytes = prog->witness_ops.size() * 4;
-    if (hipMalloc(reinterpret_cast<void**>(&dw), wires.size() * 4) != hipSuccess) return RSV_E_DEVICE;
-    if (hipMemcpy(dw, wires.data(), wires.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&dops), ops_bytes ? ops_bytes : 4) != hipSuccess ||
-        (ops_bytes && hipMemcpy(dops, prog->witness_ops.data(), ops_bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-        (void)hipFree(dw);
-        if (dops) (void)hipFree(dops);
+    uint32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), pre.size() * 4) != hipSuccess) return RSV_E_DEVICE;
+    if (hipMemcpy(d, pre.data(), pre.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
         return RSV_E_DEVICE;
     }
-    prog->d_trace_ops = dops;
-    prog->trace_lp = lp;
-    prog->trace_lq = lq;
-    prog->d_trace_wires = dw;  // last: the flag the check above reads
+    prog->d_trace_pre = d;
     return RSV_OK;
+}
+
+// What the chain's _dev forms do after their argument checks: the program's device and the batch limit, the context's
+// device, the program's device copies (program_upload).
+int chain_begin(rsv_ctx* c, const rsv_witness_program* prog, size_t n, bool with_pre) {
+    if (prog->device != c->device || n > (1u << 20)) return RSV_E_SIZE;
+    HIP_TRY(hipSetDevice(c->device));
+    return program_upload(const_cast<rsv_witness_program*>(prog), with_pre);  // the lazily uploaded device copies only
 }
 
 }  // namespace
@@ -55,19 +86,16 @@ int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t*
     }
 }
 
-int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* cprog, const uint32_t* d_variables, const uint32_t* d_flow,
+int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
                           const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
                           uint32_t* d_ops) {
-    if (!c || !cprog || !d_accept) return RSV_E_NULL;
+    if (!c || !prog || !d_accept) return RSV_E_NULL;
     if ((d_plonk || d_ops) && !d_variables) return RSV_E_NULL;
     if (d_poseidon && (!d_flow || !d_flow_swap)) return RSV_E_NULL;
     if (((uintptr_t)d_variables & 15) || ((uintptr_t)d_flow & 15) || ((uintptr_t)d_poseidon & 15) || ((uintptr_t)d_plonk & 3) ||
         ((uintptr_t)d_ops & 3))
         return RSV_E_SIZE;
-    if (cprog->device != c->device || n > (1u << 20)) return RSV_E_SIZE;
-    rsv_witness_program* prog = const_cast<rsv_witness_program*>(cprog);  // the lazily uploaded device copies only
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = trace_upload(prog);
+    int rc = chain_begin(c, prog, n, false);
     if (rc != RSV_OK) return rc;
     if (n == 0) return RSV_OK;
     const rsv_witness_shape& s = prog->shape;
@@ -113,48 +141,24 @@ int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, cons
     if (!prog || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
     if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_trace_dev
     if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    struct Guard { rsv_ctx* c; ~Guard() { rsv_ctx_destroy(c); } } guard{c};
-    c->opt.witness_layout = 2;  // the trace kernels read either layout; this one needs no transpose and no second copy
-    rc = trace_upload(const_cast<rsv_witness_program*>(prog));
+    WitnessStage st;
+    int rc = st.open(offsets, n, device, true);
+    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), false);
     if (rc != RSV_OK) return rc;
     const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq, n_ops = prog->witness_ops.size() / 3;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dvars, dacc, dreason, dflow, dswap, dplonk, dposeidon, dops;
-    const size_t flow_records = n * (size_t)prog->shape.flow_count;
-    HIP_TRY(dflow.alloc(flow_records * 128));
-    HIP_TRY(dswap.alloc(flow_records));
-    HIP_TRY(dblob.alloc(total));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dvars.alloc(n * (size_t)prog->n_vars * 16));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
+    DevBuf dplonk, dposeidon, dops;
     if (plonk) HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
     if (poseidon) HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
     if (ops) HIP_TRY(dops.alloc(n * n_ops * 4));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    rc = rsv_witness_eval_dev(c, prog, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, cfg, pi, n_pi, dvars.as<uint32_t>(),
-                              dflow.as<uint32_t>(), dswap.as<uint8_t>(), dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_witness_trace_dev(c, prog, dvars.as<const uint32_t>(), dflow.as<const uint32_t>(), dswap.as<const uint8_t>(),
-                               dacc.as<const uint8_t>(), n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), dops.as<uint32_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_ctx_synchronize(c);
+    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+    if (rc == RSV_OK)
+        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(),
+                                   dops.as<uint32_t>());
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
     if (plonk) HIP_TRY(hipMemcpy(plonk, dplonk.p, n * rsv::PLONK_COLS_K * N * 4, hipMemcpyDeviceToHost));
     if (poseidon) HIP_TRY(hipMemcpy(poseidon, dposeidon.p, n * rsv::POSEIDON_COLS_K * Q * 4, hipMemcpyDeviceToHost));
     if (ops && n_ops) HIP_TRY(hipMemcpy(ops, dops.p, n * n_ops * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost));
-    if (reason) HIP_TRY(hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost));
     return RSV_OK;
 }
 

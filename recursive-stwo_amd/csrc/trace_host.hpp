@@ -19,6 +19,12 @@ namespace rsv::trace {
 
 constexpr uint32_t MP = 0x7fffffffu;
 constexpr uint32_t PLONK_PRE_COLS = 10, POSEIDON_PRE_COLS = 40, PLONK_TRACE_COLS = 12, POSEIDON_TRACE_COLS = 48;
+// The preprocessed columns the logup relations read (k_interaction.hpp), by their index in preprocessed()'s tables; op,
+// enforce_c_m31, is_full, rc0[1..15] and rc1 are read by no relation.
+constexpr uint32_t PLONK_A_WIRE = 0, PLONK_B_WIRE = 1, PLONK_C_WIRE = 2, PLONK_MULT_A = 4, PLONK_MULT_B = 5, PLONK_MULT_C = 6,
+                   PLONK_POSEIDON_WIRE = 7, PLONK_MULT_POSEIDON = 8;
+constexpr uint32_t POSEIDON_IS_FIRST = 0, POSEIDON_IS_LAST = 1, POSEIDON_ROUND_ID = 3, POSEIDON_SWAP_ADDR = 4 /* rc0[0] */,
+                   POSEIDON_EXT_WIRE_1 = 36, POSEIDON_EXT_WIRE_2 = 37, POSEIDON_EXT_NZ_1 = 38, POSEIDON_EXT_NZ_2 = 39;
 constexpr uint32_t ROWS_PER_INVOCATION = 6;
 // The constraint system starts with four constant variables (0, 1, i, j) and one row each (plonk_with_poseidon.rs:95-
 // 137); num_input counts the three non-zero ones.  components/recursive allocates no public input (only components/last

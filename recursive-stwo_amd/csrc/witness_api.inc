@@ -15,17 +15,15 @@ struct rsv_witness_program {
     std::vector<uint32_t> flow_wires;   // [copies * flow_count][5]: PoseidonEntry::wire of r1..r4, SwapOption::addr
     std::vector<uint32_t> gates;        // [n_rows][6]: a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31 (the template's)
     std::vector<uint32_t> witness_ops;  // [n][3]: row, bit variable, constant — rows whose op follows the witness
-    // rsv_witness_trace_dev (trace_api.inc): the padded a / b / c wires [3][2^trace_lp] and witness_ops on the device,
-    // uploaded by the first call
+    // The chain's device copies (program_upload, trace_api.inc), each uploaded by the first call that needs it, under
+    // trace_mu.  rsv_witness_trace_dev and after: the padded a / b / c wires [3][2^trace_lp] and witness_ops.
     std::mutex trace_mu;
     uint32_t* d_trace_wires = nullptr;
     uint32_t* d_trace_ops = nullptr;
     uint32_t trace_lp = 0, trace_lq = 0;
-    // rsv_witness_interaction_dev (interaction_api.inc): the 8 + 8 preprocessed columns its relations read, uploaded by
-    // the first call
-    uint32_t* d_int_pre = nullptr;
-    // rsv_witness_commit_dev (commit_api.inc): the 10 + 40 preprocessed columns of tree 0, uploaded by the first call
-    uint32_t* d_commit_pre = nullptr;
+    // rsv_witness_interaction_dev and rsv_witness_commit_dev: the 10 + 40 preprocessed columns, [10][2^trace_lp] then
+    // [40][2^trace_lq] (rsv_trace_preprocessed's order): the relations' columns and tree 0
+    uint32_t* d_trace_pre = nullptr;
 };
 
 namespace {
@@ -51,6 +49,72 @@ __global__ void k_witness_gate(const ProofMeta* __restrict__ metas, uint32_t n, 
                       m.blowup == s.log_blowup && m.log_last == s.log_last && m.nq == s.n_queries && m.n_inner == s.n_inner;
     if (!same) accept[p] = 0;
 }
+
+// The host-buffer forms of the witness chain (rsv_witness_eval, _trace, _interaction, _commit) on a context of their own:
+// open(), the form's program upload and output buffers, eval(), the form's _dev calls on vars / flow / swap / accept,
+// finish(), the form's own outputs copied back.
+struct WitnessStage {
+    rsv_ctx* c = nullptr;
+    const uint64_t* offsets = nullptr;  // the batch as open() took it (host)
+    size_t n = 0;
+    const uint32_t* vars = nullptr;     // eval()'s outputs on the device
+    const uint32_t* flow = nullptr;     // NULL unless eval() was asked to keep the flow records
+    const uint8_t* swap = nullptr;
+    const uint8_t* accept = nullptr;
+    DevBuf d_blob, d_offsets, d_vars, d_flow, d_swap, d_accept, d_reason;
+
+    ~WitnessStage() { rsv_ctx_destroy(c); }
+
+    // batch_offsets [batch_n + 1] have to be monotonic; by_variable: RSV_OPT_WITNESS_LAYOUT = 2, which the chain's kernels
+    // read as they are written (no transpose, no second copy of the variables), else the default
+    int open(const uint64_t* batch_offsets, size_t batch_n, int device, bool by_variable) {
+        for (size_t i = 0; i < batch_n; i++)
+            if (batch_offsets[i + 1] < batch_offsets[i]) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc == RSV_OK) rc = rsv_ctx_create(device, &c);
+        if (rc != RSV_OK) return rc;
+        if (by_variable) c->opt.witness_layout = 2;
+        offsets = batch_offsets;
+        n = batch_n;
+        return RSV_OK;
+    }
+
+    int eval(const rsv_witness_program* prog, const uint8_t* blob, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi,
+             bool keep_flow) {
+        const uint64_t base = offsets[0], total = offsets[n] - base;
+        std::vector<uint64_t> rel(n + 1);
+        for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
+        const size_t flow_records = n * (size_t)prog->shape.flow_count;
+        if (keep_flow) {
+            HIP_TRY(d_flow.alloc(flow_records * 128));
+            HIP_TRY(d_swap.alloc(flow_records));
+            HIP_TRY(hipMemset(d_flow.p, 0, flow_records * 128));
+            HIP_TRY(hipMemset(d_swap.p, 0, flow_records));
+        }
+        HIP_TRY(d_blob.alloc(total));
+        HIP_TRY(d_offsets.alloc(8 * (n + 1)));
+        HIP_TRY(d_vars.alloc(n * (size_t)prog->n_vars * 16));
+        HIP_TRY(d_accept.alloc(n));
+        HIP_TRY(d_reason.alloc(n));
+        HIP_TRY(hipMemcpy(d_blob.p, blob + base, total, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_offsets.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
+        vars = d_vars.as<uint32_t>();
+        flow = d_flow.as<uint32_t>();
+        swap = d_swap.as<uint8_t>();
+        accept = d_accept.as<uint8_t>();
+        return rsv_witness_eval_dev(c, prog, d_blob.as<const uint8_t>(), d_offsets.as<const uint64_t>(), n, cfg, pi, n_pi, d_vars.as<uint32_t>(),
+                                    d_flow.as<uint32_t>(), d_swap.as<uint8_t>(), d_accept.as<uint8_t>(), d_reason.as<uint8_t>());
+    }
+
+    // Waits for the context, then copies accept and reason (may be NULL) back.
+    int finish(uint8_t* h_accept, uint8_t* h_reason) {
+        int rc = rsv_ctx_synchronize(c);
+        if (rc != RSV_OK) return rc;
+        HIP_TRY(hipMemcpy(h_accept, d_accept.p, n, hipMemcpyDeviceToHost));
+        if (h_reason) HIP_TRY(hipMemcpy(h_reason, d_reason.p, n, hipMemcpyDeviceToHost));
+        return RSV_OK;
+    }
+};
 
 }  // namespace
 
@@ -95,8 +159,7 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_levels) (void)hipFree(p->d_levels);
     if (p->d_trace_wires) (void)hipFree(p->d_trace_wires);
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
-    if (p->d_int_pre) (void)hipFree(p->d_int_pre);
-    if (p->d_commit_pre) (void)hipFree(p->d_commit_pre);
+    if (p->d_trace_pre) (void)hipFree(p->d_trace_pre);
     delete p;
 }
 
@@ -227,43 +290,16 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
     if ((flow == nullptr) != (flow_swap == nullptr)) return RSV_E_NULL;
     if (n == 0) return RSV_OK;
     if (n > (1u << 20)) return RSV_E_SIZE;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    int rc = select_device(device);
+    WitnessStage st;
+    int rc = st.open(offsets, n, device, false);
+    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr);
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    struct Guard { rsv_ctx* c; ~Guard() { rsv_ctx_destroy(c); } } guard{c};
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dvars, dacc, dreason, dflow, dswap;
     const size_t flow_records = n * (size_t)prog->shape.flow_count;
+    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
     if (flow) {
-        HIP_TRY(dflow.alloc(flow_records * 128));
-        HIP_TRY(dswap.alloc(flow_records));
-        HIP_TRY(hipMemset(dflow.p, 0, flow_records * 128));
-        HIP_TRY(hipMemset(dswap.p, 0, flow_records));
-    }
-    HIP_TRY(dblob.alloc(total));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dvars.alloc(n * (size_t)prog->n_vars * 16));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    rc = rsv_witness_eval_dev(c, prog, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, cfg, pi, n_pi, dvars.as<uint32_t>(),
-                              dflow.as<uint32_t>(), dswap.as<uint8_t>(), dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc != RSV_OK) return rc;
-    rc = rsv_ctx_synchronize(c);
-    if (rc != RSV_OK) return rc;
-    HIP_TRY(hipMemcpy(variables, dvars.p, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost));
-    if (reason) HIP_TRY(hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost));
-    if (flow) {
-        HIP_TRY(hipMemcpy(flow, dflow.p, flow_records * 128, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(flow_swap, dswap.p, flow_records, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
     }
     return RSV_OK;
 }
