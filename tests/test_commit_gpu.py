@@ -206,25 +206,57 @@ CASES = [  # (groups as (log, cols, shared), b, n, mask)
 ]
 
 
+def _random_case(rsv, ctx, spec, b, n, mask, seed, label):
+    """One random tree of CASES / GLOBAL_CASES on ctx: roots, d_coeffs and d_lde = the restatement; a masked proof gets
+    zeros."""
+    rng = np.random.default_rng(seed)
+    groups = [(log, rng.integers(0, P, (1 if sh else n, nc, 1 << log))) for log, nc, sh in spec]
+    shared = {i for i, (_, _, sh) in enumerate(spec) if sh}
+    roots, cf, ld = _commit_dev(rsv, ctx, groups, b, n=n, coeffs=True, lde=True, mask=mask, shared=shared)
+    for p in range(n):
+        if mask is not None and not mask[p]:
+            assert not roots[p].any() and all(not c[p].any() for c in cf) and all(not e[p].any() for e in ld), (label, p)
+            continue
+        mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
+        for i, ((log, cols), co, e) in enumerate(zip(mine, cf, ld)):
+            assert np.array_equal(co[p], C.interpolate(cols, log)), (label, p, i)
+            assert np.array_equal(e[p], C.evaluate(co[p], log, log + b)), (label, p, i)
+        assert roots[p].tolist() == C.commit(mine, b, ob).tolist(), (label, p)
+
+
 @pytest.mark.parametrize("case", range(len(CASES)))
 def test_commit_tree_bit_for_bit(rsv, case):
     """Random trees: roots, d_coeffs and d_lde = the restatement; a masked proof gets zeros."""
     spec, b, n, mask = CASES[case]
-    rng = np.random.default_rng(100 + case)
-    groups = [(log, rng.integers(0, P, (1 if sh else n, nc, 1 << log))) for log, nc, sh in spec]
-    shared = {i for i, (_, _, sh) in enumerate(spec) if sh}
     ctx = rsv.Context(0)
-    roots, cf, ld = _commit_dev(rsv, ctx, groups, b, n=n, coeffs=True, lde=True, mask=mask, shared=shared)
+    _random_case(rsv, ctx, spec, b, n, mask, 100 + case, case)
     ctx.close()
-    for p in range(n):
-        if mask is not None and not mask[p]:
-            assert not roots[p].any() and all(not c[p].any() for c in cf) and all(not e[p].any() for e in ld), p
-            continue
-        mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
-        for (log, cols), co, e in zip(mine, cf, ld):
-            assert np.array_equal(co[p], C.interpolate(cols, log)), p
-            assert np.array_equal(e[p], C.evaluate(co[p], log, log + b)), p
-        assert roots[p].tolist() == C.commit(mine, b, ob).tolist(), p
+
+
+GLOBAL_CASES = [  # as CASES: around CM_LDS_LOG = 12 (layers m >= 12 run in k_cm_fft_layer) and at the driver's limits
+    ([(11, 2, False)], 3, 2, None),
+    ([(12, 2, False)], 2, 2, None),
+    ([(13, 2, False)], 3, 2, None),  # one global layer each way, the forward one reading the coefficients through CmSrc
+    ([(14, 1, False)], 2, 3, None),  # forward table of 2^16 again (cached by the case above)
+    ([(16, 1, False)], 1, 1, None),  # four global layers; the inverse table of 2^16
+    ([(13, 1, False), (15, 2, False)], 2, 2, None),  # two global depths feeding one hash layer each
+    ([(14, 2, True), (9, 3, False)], 2, 4, [1, 0, 1, 0]),  # a masked shared group (proof_stride 0) through the global layers
+    ([(2, 3, False)], 16, 2, None),  # RSV_MAX_LOG_BLOWUP: 2^16 block subtrees, 16 node layers above them
+    ([(0, 2, False)], 16, 2, [0, 1]),
+    ([(3, 3, False), (3, 6, False), (2, 7, False), (3, 1, False), (2, 2, False), (3, 4, False), (4, 9, False), (2, 5, False)], 3, 2,
+     None),  # RSV_MAX_COMMIT_GROUPS, interleaved sizes: 8-word chunks of k_cm_hash_layer across group boundaries
+    ([(5, 3, False), (4, 2, False), (5, 6, False)], 3, 3, [1, 1, 0]),  # equal logs apart: joined in group order
+]
+
+
+def test_commit_tree_global_passes_and_limits(rsv):
+    """GLOBAL_CASES in one Context (the twiddle tables cached by a case serve the later ones): logs 11 to 16 across the LDS /
+    global-pass boundary, two global depths in one tree, a masked shared log-14 group, log_blowup 16 at logs 2 and 0, 8
+    groups, equal logs out of order.  Roots, d_coeffs and d_lde = the restatement, element by element."""
+    ctx = rsv.Context(0)
+    for case, (spec, b, n, mask) in enumerate(GLOBAL_CASES):
+        _random_case(rsv, ctx, spec, b, n, mask, 300 + case, case)
+    ctx.close()
 
 
 def test_workspace_groups_and_one_proof(rsv):
@@ -245,6 +277,38 @@ def test_workspace_groups_and_one_proof(rsv):
         assert whole[p].tolist() == C.commit([(log, c[p]) for log, c in groups], b, ob).tolist(), p
 
 
+def test_workspace_cut_with_caller_owned_outputs(rsv):
+    """d_coeffs and d_lde given, a mask, 41 proofs at b = 3 of a log-13 group, a shared log-9 group and a log-10 group.  The
+    workspace is then the node layers alone, about P nb 384 KiB: a 5 MB budget cuts it to one block per pass (nb = 1 < 2^b)
+    and to P = 11 proofs per pass (41 -> 21 -> 11), so four passes of 11, 11, 11 and a short last one of 8, each reaching
+    its outputs at p0 and blk0 offsets.  Masked proofs sit in the first, a middle and the last pass.  Every element of the
+    roots, d_coeffs and d_lde equals the uncut run; sampled proofs equal the restatement; masked proofs are all zeros."""
+    rng = np.random.default_rng(41)
+    n, b = 41, 3
+    spec = [(13, 2, False), (9, 3, True), (10, 4, False)]
+    groups = [(log, rng.integers(0, P, (1 if sh else n, nc, 1 << log))) for log, nc, sh in spec]
+    shared = {1}
+    mask = [0 if p in (1, 20, 39) else 1 for p in range(n)]
+    ctx = rsv.Context(0)
+    whole = _commit_dev(rsv, ctx, groups, b, n=n, coeffs=True, lde=True, mask=mask, shared=shared)
+    ctx.set_option("ws_budget_mb", 5)
+    cut = _commit_dev(rsv, ctx, groups, b, n=n, coeffs=True, lde=True, mask=mask, shared=shared)
+    ctx.close()
+    roots, cf, ld = whole
+    assert np.array_equal(cut[0], roots)
+    for i in range(len(spec)):
+        assert np.array_equal(cut[1][i], cf[i]), i
+        assert np.array_equal(cut[2][i], ld[i]), i
+    for p in (1, 20, 39):
+        assert not roots[p].any() and all(not c[p].any() for c in cf) and all(not e[p].any() for e in ld), p
+    for p in (0, 10, 11, 33, 40):
+        mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
+        for i, ((log, cols), co, e) in enumerate(zip(mine, cf, ld)):
+            assert np.array_equal(co[p], C.interpolate(cols, log)), (p, i)
+            assert np.array_equal(e[p], C.evaluate(co[p], log, log + b)), (p, i)
+        assert roots[p].tolist() == C.commit(mine, b, ob).tolist(), p
+
+
 def test_mixed_batch_with_a_rejected_proof(rsv):
     """Five proofs of one shape, the third tampered (rejected): it gets zeros everywhere and d_ok = 0; every output element
     of the others is written and equals its solo run."""
@@ -263,6 +327,30 @@ def test_mixed_batch_with_a_rejected_proof(rsv):
         assert not r[key][2].any(), key
         for k in (0, 1, 3, 4):
             assert np.array_equal(r[key][k], solo[key][0]), (key, k)
+    wp.close()
+
+
+def test_chain_under_a_small_workspace_budget(rsv):
+    """The batch of test_mixed_batch_with_a_rejected_proof (the level10 shape, 2^16 / 2^15 rows at b = 8) under a 200 MB
+    budget: each of the three commit_tree calls keeps its five proofs but cuts its 256 blocks into passes of nb = 2 (trees 0
+    and 1) or nb = 4 (tree 2, about 16 MB of coefficients + 31 MB per block), with d_accept, then ok, as the mask.  Every
+    output, ok included, is bit-identical to the default-budget run."""
+    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
+    wp = _program(rsv, pin)
+    src = pin["src"]
+    b = fixture_cfg(pin["dst"]).log_blowup_factor
+    assert wp.trace_sizes() == (16, 15) and b == 8
+    proof = read_proof(src)
+    batch = [proof, proof, ob.tamper(proof, 5), proof, proof]
+    ctx = rsv.Context(0)
+    whole = _chain(rsv, ctx, wp, batch, _inputs(src), b)
+    ctx.set_option("ws_budget_mb", 200)
+    cut = _chain(rsv, ctx, wp, batch, _inputs(src), b)
+    ctx.close()
+    assert whole["ok"].tolist() == [1, 1, 0, 1, 1]
+    for key in ("roots", "draws", "ip", "iq", "sums", "chan", "ok"):
+        assert np.array_equal(cut[key], whole[key]), key
+    assert not whole["roots"][2].any() and whole["roots"][0].any()
     wp.close()
 
 

@@ -3,7 +3,9 @@ columns, and its two claimed sums.  Against the REFERENCE for all 14 consecutive
 lookup elements, the sums are K+1's stmt1 and the 16 columns give K+1's 24 tree-2 sampled values), and bit for bit
 against the numpy restatement (tests/interaction_ref.py, pinned to the fixtures by tests/test_interaction_host.py) fed
 with the GPU's own trace columns: a mixed batch with per-proof lookup elements and rejected proofs, both variable layouts,
-a five-copy program, one proof, and a crafted zero denominator."""
+a five-copy program, one proof, a crafted zero denominator, and batches of 32 to 1 100 proofs that reach every scan width."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -259,3 +261,98 @@ def test_alignment_and_batch_limit(rsv):
     ctx.synchronize()
     ctx.close()
     wp.close()
+
+
+# (n, B): B = clamp(17 - min(ceil(log2 n), 10), 7, 12), then B <= log - 1 (interaction_chunk_bits, interaction_api.inc), the
+# same for both components of the level10 shape (2^16 and 2^15 rows)
+SWEEP = [(32, 12), (33, 11), (65, 10), (129, 9), (257, 8), (513, 7), (1100, 7)]
+N_POOL = 6
+
+
+def _scan_bits(n, log):
+    return min(max(17 - min((n - 1).bit_length(), 10), 7), 12, log - 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_pool(rsv):
+    """The device trace columns of level10-1 and level11-1 under the level10 program, a pool of N_POOL random (z, alpha), a
+    lookup crafted for a zero denominator in a late Plonk row of level10-1, and the restatement of every (trace, lookup)
+    pair: (plonk [2, 12, 2^lp], poseidon [2, 48, 2^lq], lookup words [N_POOL + 1, 8], expected int_plonk / int_poseidon /
+    sums with an all-zero entry last)."""
+    wp = rsv.WitnessProgram.build(read_proof("level10-1.bin"), fixture_cfg("level10-1.bin"))
+    plonk, poseidon, _, acc, _ = rsv.witness_trace([read_proof("level10-1.bin"), read_proof("level11-1.bin")], wp)
+    assert acc.tolist() == [1, 1]
+    lp, lq = wp.trace_sizes()
+    rng = np.random.default_rng(1100)
+    pool = _random_lookup(rng, N_POOL + 1)
+    ppre, _ = wp.preprocessed()
+    row = (1 << lp) - 5
+    alpha = pool[N_POOL][1]
+    z = R.q_add(R.q(plonk[0][0:4, row]), R.q_mul_m(R.q(alpha), int(ppre[0][row])))
+    pool[N_POOL] = (tuple(int(x) for x in z[:, 0]), alpha)
+    ep = np.zeros((2 * N_POOL + 1, 8, 1 << lp), np.uint32)
+    eq = np.zeros((2 * N_POOL + 1, 8, 1 << lq), np.uint32)
+    es = np.zeros((2 * N_POOL + 1, 2, 4), np.uint32)
+    for s in range(2):
+        for j in range(N_POOL):
+            ep[N_POOL * s + j], eq[N_POOL * s + j], es[N_POOL * s + j], wok = _expected(rsv, wp, plonk[s], poseidon[s], *pool[j])
+            assert wok, (s, j)
+    assert not _expected(rsv, wp, plonk[0], poseidon[0], *pool[N_POOL])[3]
+    words = rsv._lookup_array(pool, N_POOL + 1)
+    wp.close()
+    return plonk, poseidon, words, ep, eq, es
+
+
+@pytest.mark.parametrize("n,B", SWEEP, ids=[f"n{n}-B{B}" for n, B in SWEEP])
+def test_every_scan_width(rsv, n, B):
+    """n proofs of the level10 shape in one rsv_witness_interaction_dev call, so that the scan width is B =
+    clamp(17 - min(ceil(log2 n), 10), 7, 12) (interaction_chunk_bits): 12, 11, 10, 9, 8, 7, 7 for n = 32, 33, 65, 129, 257,
+    513, 1100 — the chunk boundaries, the cc << (log - B) shift terms of k_int_offsets (at B = 7, 128 of its 4 096 slots,
+    all in wave 0) and the backward walk of k_int_scan.  Each proof takes level10-1's or level11-1's device trace columns and
+    one (z, alpha) of a pool; proofs 3 and n - 1 (and 70, 200, 700 where n allows) have accept = 0, proofs n / 2 + 1 and
+    n - 2 a zero denominator.  Every proof's columns equal the restatement, compared on the device; sums and ok too; the
+    rejected and zero-denominator proofs are all zeros with ok = 0."""
+    import torch
+    dev = torch.device("cuda:0")
+    assert _scan_bits(n, 16) == _scan_bits(n, 15) == B
+    plonk, poseidon, words, ep, eq, es = _sweep_pool(rsv)
+    wp = rsv.WitnessProgram.build(read_proof("level10-1.bin"), fixture_cfg("level10-1.bin"))
+    lp, lq = wp.trace_sizes()
+    rng = np.random.default_rng(n)
+    src = rng.integers(0, 2, n)
+    lk = rng.integers(0, N_POOL, n)
+    rejected = {3, n - 1} | {k for k in (70, 200, 700) if k < n - 1}
+    zero_den = {n // 2 + 1, n - 2}
+    assert not rejected & zero_den
+    for k in zero_den:
+        src[k], lk[k] = 0, N_POOL
+    accept = np.array([0 if k in rejected else 1 for k in range(n)], np.uint8)
+    want = np.where(accept == 1, N_POOL * src + lk, 2 * N_POOL)
+    want[sorted(zero_den)] = 2 * N_POOL
+    d_src = torch.from_numpy(src).to(dev)
+    d_plonk = torch.from_numpy(plonk.view(np.int32)).to(dev).index_select(0, d_src)
+    d_pos = torch.from_numpy(poseidon.view(np.int32)).to(dev).index_select(0, d_src)
+    d_acc = torch.from_numpy(accept).to(dev)
+    d_lookup = torch.from_numpy(words[lk].view(np.int32)).to(dev)
+    d_ip = torch.full((n, 8, 1 << lp), -1, dtype=torch.int32, device=dev)
+    d_iq = torch.full((n, 8, 1 << lq), -1, dtype=torch.int32, device=dev)
+    d_sums = torch.full((n, 2, 4), -1, dtype=torch.int32, device=dev)
+    d_ok = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+    ctx = rsv.Context(0)
+    ctx.witness_interaction(wp, d_plonk, d_pos, d_acc, d_lookup, n, d_ip, d_iq, d_sums, d_ok)
+    ctx.synchronize()
+    ctx.close()
+    wp.close()
+    e_p, e_q = torch.from_numpy(ep.view(np.int32)).to(dev), torch.from_numpy(eq.view(np.int32)).to(dev)
+    d_want = torch.from_numpy(want).to(dev)
+    wrong = []
+    for k0 in range(0, n, 64):
+        k1 = min(n, k0 + 64)
+        same = (d_ip[k0:k1] == e_p.index_select(0, d_want[k0:k1])).flatten(1).all(1)
+        same &= (d_iq[k0:k1] == e_q.index_select(0, d_want[k0:k1])).flatten(1).all(1)
+        wrong += [k0 + int(i) for i in torch.nonzero(~same).flatten().tolist()]
+    assert not wrong, wrong[:16]
+    assert np.array_equal(d_sums.cpu().numpy().view(np.uint32), es[want])
+    assert d_ok.cpu().numpy().tolist() == [0 if k in rejected | zero_den else 1 for k in range(n)]
+    del d_plonk, d_pos, d_ip, d_iq
+    torch.cuda.empty_cache()
