@@ -114,6 +114,7 @@ __device__ __forceinline__ void poseidon2_ref_inline(uint32_t* s) {
 //                 v_mad_u64_u32 (4.55; 5.05 with a live 64-bit addend)   -- the 32x32->64 multiply is
 //                 NOT quarter rate on gfx950, so the cost of a modular multiply is its reduction.
 //                 v_mad_i64_i32 without an addend 4.34, v_mad_u64_u32 with an SGPR-pair addend 4.48 (pow5)
+//                 v_mad_i64_i32 with an SGPR-pair addend 4.51, 4.30 as a square (pow5c)
 // Consequences used below:
 //   * linear layers accumulate UNREDUCED in 64 bits (one v_lshl_add_u64 / v_mad_u64_u32 per term,
 //     shifts by 1..4 and small multipliers are free), and are folded once per round;
@@ -133,8 +134,9 @@ __device__ __forceinline__ void poseidon2_ref_inline(uint32_t* s) {
 //     two wait states behind the multiplies: 36.17 (worse) | s_nop 3: 40.2
 // The wait states cost nothing at >= 4 waves per SIMD (other waves fill them); at one wave per SIMD (the lane-form
 // transcript of batches > 24 576) they lengthen the chain by ~25 % — that kernel runs underneath k_row_hash.
-// PACE: the wait states above (one behind every v_mad_u64_u32, one behind the v_min that ends a reduction).  They pay where
-// several waves share a SIMD and cost ~25 % where a wave is (nearly) alone on it, so the verify kernels pick the instance by
+// PACE: the wait states above (one behind every 64-bit multiply, one behind the v_min that ends a reduction and behind the
+// fold that ends pow5c's x^4).  They pay where several waves share a SIMD and cost ~25 % where a wave is (nearly) alone on
+// it, so the verify kernels pick the instance by
 // the size of the launch (poseidon2_half below): paced for launches that fill the machine, unpaced for a small batch's trees
 // and for the one-wave-per-SIMD lane-form transcript.
 template <bool PACE>
@@ -196,6 +198,19 @@ struct PermT {
         else asm("v_mad_i64_i32 %0, %1, %2, %2, 0" : "=v"(d), "=s"(carry) : "v"(a));
         return d;
     }
+    // signed a * b + c (v_mad_i64_i32), c a signed 64-bit constant in an SGPR pair; the square a * a + c reads one register
+    static __device__ __forceinline__ uint64_t mad64s(int32_t a, int32_t b, uint64_t c_uniform) {
+        uint64_t d, carry;
+        if constexpr (PACE) asm("v_mad_i64_i32 %0, %1, %2, %3, %4\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
+        else asm("v_mad_i64_i32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
+        return d;
+    }
+    static __device__ __forceinline__ uint64_t sqr64s(int32_t a, uint64_t c_uniform) {
+        uint64_t d, carry;
+        if constexpr (PACE) asm("v_mad_i64_i32 %0, %1, %2, %2, %3\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "s"(c_uniform));
+        else asm("v_mad_i64_i32 %0, %1, %2, %2, %3" : "=v"(d), "=s"(carry) : "v"(a), "s"(c_uniform));
+        return d;
+    }
     static __device__ __forceinline__ uint32_t dbl32(uint32_t x) {  // x + x as a fast-class add (not a shift)
         uint32_t d;
         asm("v_add_u32 %0, %1, %1" : "=v"(d) : "v"(x));
@@ -225,6 +240,41 @@ struct PermT {
         // (V2 >> 31) + (V2 & P) <= (P - 1) + P
         const uint32_t c4 = canon(__builtin_amdgcn_alignbit((uint32_t)(V2 >> 32), (uint32_t)V2, 31) + ((uint32_t)V2 & P));
         return fold2(mul64(xx, c4));                          // 2x*c4: hi <= P, lo>>1 <= P
+    }
+    // (pow5 above is the S-box of the previous form, x canonical; the permutation calls pow5c.  It stays beside it as the
+    // form tests/test_sbox_signed_square.py models.)
+
+    // The centred S-box's three 64-bit addends, multiples of P in SGPR pairs (opaque64()), read as signed 64-bit values:
+    // KP = -P * 2^32 (the first product's, as in pow5), KN = -P * 2^31 (the second), KQ = P * 2^31 (the last).
+    static constexpr uint64_t KN = 0 - ((uint64_t)P << 31), KQ = (uint64_t)P << 31;
+    struct SboxK {
+        uint64_t kp, kn, kq;
+    };
+    static __device__ __forceinline__ SboxK sbox_k() { return {opaque64(KP), opaque64(KN), opaque64(KQ)}; }
+    // The S-box input is reduced by canon_rc with the round constant moved by CENTRE: it yields m = (x + 2^30) mod P, and
+    // x = m - 2^30 is the CENTRED representative of x, in [-2^30, 2^30 - 2].
+    static constexpr uint32_t CENTRE = 1u << 30;
+    static constexpr uint32_t centred(uint32_t rc) { return (uint32_t)(((uint64_t)rc + CENTRE) % P); }
+
+    // m = (x + 2^30) mod P  ->  x^5 in L2, every intermediate a signed word (v_mad_i64_i32 with the addends above):
+    //     x  = m - 2^30                  [-2^30, 2^30 - 2]
+    //     xx = 2x                        [-2^31, 2^31 - 4]: even, and an int32 because x is centred
+    //     s1 = fold2(xx * x + KP)        2x^2 <= 2^61: fold2(2x^2) - P in [-P, 2^29], congruent to x^2
+    //     V2 = s1 * s1 + KN              [-P * 2^31, -P]
+    //     c4 = (V2 >> 31) + (V2 & P)     fold(s1^2) - P in [-P, P - 2], congruent to x^4, with no conditional subtract
+    //     y  = fold2(xx * c4 + KQ)       xx * c4 in [-2^31 P, 2^31 P], so V3 in [0, 2^32 P] and even: y in [0, 2P - 1]
+    // The last product is the one a signed S-box has to resolve: x * c4 over two full-width operands spans 2 P^2, one bit
+    // more than a 32-bit fold takes.  Centring x lets it be doubled inside an int32, so the product is even, spans 2^32 P <
+    // 2^63 and ends in the two-instruction fold2.  Against pow5: one v_min fewer (c4 stays centred), the centring subtract
+    // where the canonicalisation's subtract was; 12 instructions.  tests/test_sbox_centred.py proves the ranges.
+    static __device__ __forceinline__ uint32_t pow5c(uint32_t m, const SboxK& k) {
+        const int32_t x = (int32_t)(m - CENTRE);
+        const int32_t xx = (int32_t)dbl32((uint32_t)x);
+        const int32_t s1 = (int32_t)fold2(mad64s(xx, x, k.kp));
+        const uint64_t V2 = sqr64s(s1, k.kn);
+        uint32_t c4 = __builtin_amdgcn_alignbit((uint32_t)(V2 >> 32), (uint32_t)V2, 31) + ((uint32_t)V2 & P);
+        if constexpr (PACE) asm volatile("s_nop 0" : "+v"(c4));  // the reduction's end: the wait state of pow5's v_min
+        return fold2(mad64s(xx, (int32_t)c4, k.kq));
     }
 
     // Y = 2*M4*(x0..x3) for 32-bit inputs (any u32), exact in 64 bits.
@@ -279,21 +329,21 @@ struct PermT {
     }
 
     template <int R, int I>
-    static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, uint64_t kp) {
-        s[I] = pow5(canon_rc<RC_FULL_K[R][I], HI_FULL>(fold2(V[I])), kp);
-        if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, kp);
+    static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, const SboxK& k) {
+        s[I] = pow5c(canon_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
+        if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, k);
     }
     // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
-    static __device__ __forceinline__ void sbox_full4(uint32_t* s, uint64_t kp) {
-        s[I] = pow5(canon_rc<RC_FULL_K[4][I], HI_PARTIAL>(s[I]), kp);
-        if constexpr (I + 1 < 16) sbox_full4<I + 1>(s, kp);
+    static __device__ __forceinline__ void sbox_full4(uint32_t* s, const SboxK& k) {
+        s[I] = pow5c(canon_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k);
+        if constexpr (I + 1 < 16) sbox_full4<I + 1>(s, k);
     }
 
     // Inputs: any u32 words, s[0] <= P + HI_PARTIAL.
     template <int R>
-    static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd, uint64_t kp) {
-        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]), kp);
+    static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd, const SboxK& k) {
+        uint32_t u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
         // sum2 = 2 * (u0 + s[1] + ... + s[15]) < 2^37, two chains
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
@@ -315,15 +365,15 @@ struct PermT {
     // (its multiplier is 2^31); tests/test_partial_pairs.py proves the bounds over the schedule.
     template <int R>
     static __device__ __forceinline__ void partial_pair(uint32_t* s, uint32_t k2, uint32_t k6, uint32_t k30, const uint32_t* kd,
-                                                        const uint32_t* kq, uint64_t kp) {
-        uint32_t u0 = pow5(canon_rc<RC_PARTIAL_K[R], HI_PARTIAL>(s[0]), kp);
+                                                        const uint32_t* kq, const SboxK& k) {
+        uint32_t u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
         uint64_t sum2 = add64(a, b);                                          // 2S < 2^37
         const uint32_t s0 = fold2(mad64(u0, k6, sum2));                       // round R's word 0, <= P + 2^6
         const uint32_t sf = fold2(sum2);                                      // S, <= P + 2^5
-        u0 = pow5(canon_rc<RC_PARTIAL_K[R + 1], HI_PARTIAL>(s0), kp);
+        u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k);
         // sum2 = 2S' = 2 u0' + sum_i 2 d_i s_i + 30 S < 2^50 + 2^37, two chains
         a = mul64(u0, k2, 0); b = mul64(s[1], kd[1], 0);
     #pragma unroll
@@ -340,13 +390,13 @@ struct PermT {
     static __device__ __forceinline__ void poseidon2_rounds(uint32_t* s, uint32_t k2, uint32_t k4) {
         uint64_t V[16];
         const uint32_t k6 = opaque(6);
-        const uint64_t kp = opaque64(KP);
+        const SboxK k5 = sbox_k();
         // s: canonical input.  V never carries a round constant: the constants are literals of the fused reductions.
         mds16_2x(k2, k4, s, V);
-        sbox_full<0, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
-        sbox_full<1, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
-        sbox_full<2, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
-        sbox_full<3, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
+        sbox_full<0, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        sbox_full<1, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        sbox_full<2, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        sbox_full<3, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
         // partial rounds: every lane lazily folded (any u32 inside the pairs, <= P + 2^18 after a single round), lane 0 goes
         // through the S-box
     #pragma unroll
@@ -370,14 +420,14 @@ struct PermT {
         const uint32_t k30 = opaque(30);
         // 14 = 1 + 6 x 2 + 1.  The last round must be a single one: the pairs leave word 14 near 2^32 and word 13 above 2^31
         // (multipliers 2^31 and 2^29); a single round brings every word back to <= P + 2^18, within what sbox_full4 takes
-        partial_round<0>(s, k2, k6, kd, kp);
-        partial_pair<1>(s, k2, k6, k30, kd, kq, kp);  partial_pair<3>(s, k2, k6, k30, kd, kq, kp);  partial_pair<5>(s, k2, k6, k30, kd, kq, kp);
-        partial_pair<7>(s, k2, k6, k30, kd, kq, kp);  partial_pair<9>(s, k2, k6, k30, kd, kq, kp);  partial_pair<11>(s, k2, k6, k30, kd, kq, kp);
-        partial_round<13>(s, k2, k6, kd, kp);
-        sbox_full4<0>(s, kp);      mds16_2x(k2, k4, s, V);
-        sbox_full<5, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
-        sbox_full<6, 0>(V, s, kp); mds16_2x(k2, k4, s, V);
-        sbox_full<7, 0>(V, s, kp);
+        partial_round<0>(s, k2, k6, kd, k5);
+        partial_pair<1>(s, k2, k6, k30, kd, kq, k5);  partial_pair<3>(s, k2, k6, k30, kd, kq, k5);  partial_pair<5>(s, k2, k6, k30, kd, kq, k5);
+        partial_pair<7>(s, k2, k6, k30, kd, kq, k5);  partial_pair<9>(s, k2, k6, k30, kd, kq, k5);  partial_pair<11>(s, k2, k6, k30, kd, kq, k5);
+        partial_round<13>(s, k2, k6, kd, k5);
+        sbox_full4<0>(s, k5);      mds16_2x(k2, k4, s, V);
+        sbox_full<5, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        sbox_full<6, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        sbox_full<7, 0>(V, s, k5);
     }
 
     static __device__ __forceinline__ void poseidon2_inline(uint32_t* s) {

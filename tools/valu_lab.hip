@@ -97,6 +97,9 @@ DEF_KERNEL(k_lshl_or, asm volatile("v_lshl_or_b32 %0, %0, 1, %1" : "+v"(a[i]) : 
 // the signed S-box (PermT::pow5): the signed square without an addend, and the first product with a 64-bit SGPR-pair addend
 DEF_KERNEL(k_mad_i64, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %1, 0" : "=v"(w[i]) : "v"(a[i]) : "s10", "s11"))
 DEF_KERNEL(k_mad64_spair, asm volatile("v_mad_u64_u32 %0, s[10:11], %1, %2, s[20:21]" : "=v"(w[i]) : "v"(a[i]), "v"(b) : "s10", "s11", "s20", "s21"))
+// the centred S-box (PermT::pow5c): all three products are v_mad_i64_i32 with a signed 64-bit SGPR-pair addend
+DEF_KERNEL(k_mad_i64_spair, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %2, s[20:21]" : "=v"(w[i]) : "v"(a[i]), "v"(b) : "s10", "s11", "s20", "s21"))
+DEF_KERNEL(k_sqr_i64_spair, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %1, s[20:21]" : "=v"(w[i]) : "v"(a[i]) : "s10", "s11", "s20", "s21"))
 
 // MFMA rows: one MFMA per "instruction" of the generic harness (8 independent accumulators per wave).
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -218,6 +221,7 @@ int main(int argc, char** argv) {
                     {"v_add_u32_sdwa WORD_1", k_add_sdwa}, {"v_add_u32_dpp quad_perm", k_add_dpp}, {"v_sub_u32 clamp", k_sub_clamp},
                     {"v_cvt_f64_u32", k_cvt_f64_u32}, {"v_cvt_u32_f64", k_cvt_u32_f64}, {"v_min_f32", k_min_f32}, {"v_lshl_or_b32", k_lshl_or},
                     {"v_mad_i64_i32(0) square", k_mad_i64}, {"v_mad_u64_u32 sgpr-pair addend", k_mad64_spair},
+                    {"v_mad_i64_i32 sgpr-pair addend", k_mad_i64_spair}, {"v_mad_i64_i32 square sgpr-pair", k_sqr_i64_spair},
                     {"MFMA i32_16x16x32_i8", k_mfma_i8}, {"MFMA f64_16x16x4 (x1/4 iters)", k_mfma_f64},
                     {"MIX half waves v_add / half MFMA i8", k_mix_mfma_valu},
                     {"v_add_u32 + s_nop", k_add_nop}, {"v_mad_u64_u32(acc) + s_nop", k_mad64_acc_nop}, {"v_lshl_add_u64 + s_nop", k_lshl_add64_nop},
