@@ -683,6 +683,50 @@ typedef struct {
 int rsv_commit_tree_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup,
                         const uint8_t* d_mask, uint32_t* d_roots);
 
+/* rsv_commit_tree_dev that also leaves the tree's CAP: d_cap [n][2^(log_blowup + 1)][8] (device, may be NULL: then exactly
+ * rsv_commit_tree_dev), the nodes of layers 0 .. log_blowup in heap order: layer l at entries 2^l .. 2^(l+1) - 1 (entry 1 is
+ * the root, entries 2^log_blowup .. are the roots of the streamed blocks' subtrees), entry 0 zero; all zero for a masked
+ * proof.  64 B .. 4 MB per proof.  It is what rsv_decommit_tree_dev needs of the tree besides the columns, so a prover
+ * pays for the tree once.  The roots are those of rsv_commit_tree_dev, bit for bit.  d_cap 4-byte aligned. */
+int rsv_commit_tree_cap_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup,
+                            const uint8_t* d_mask, uint32_t* d_roots, uint32_t* d_cap);
+
+/* ---- decommitment of a tree of the next proof: queried values and Merkle witness --------------------------------------
+ * The opening of a tree rsv_commit_tree_dev committed, at a list of positions: what a proof carries for the tree besides
+ * its root and sampled values, queried_values[t] and decommitments[t].hash_witness, in stwo's batched order
+ * (MerkleProver::decommit; the order SinglePathMerkleProof::from_stwo_proof, components/hints/src/decommit.rs, consumes).
+ * The same groups, n, log_blowup and d_mask as the commitment (d_coeffs and d_lde are ignored), plus
+ *   d_queries [n][n_queries] (device): positions in the tree's largest layer, top = max(log_size) + log_blowup bits, in
+ *     the bit-reversed storage order d_lde is indexed by.  Any order, duplicates allowed; bits above `top` are ignored
+ *     (any u32 is taken mod 2^top).  1 <= n_queries <= RSV_MAX_QUERIES.
+ *   d_values [n][values_cap], d_n_values [n]: layer by layer from `top` down, for every distinct queried node of the
+ *     layer (queries >> (top - layer)) in ascending position, that layer's columns in commitment order (groups of one
+ *     size in group order).
+ *   d_witness [n][witness_cap][8], d_n_witness [n]: layer by layer from `top` down, for every distinct parent in
+ *     ascending order, the child that is not itself on a queried path (none where both are).
+ *   The capacities are rsv_decommit_sizes': n_queries * sum(n_cols) words and n_queries * top nodes.  Words past a proof's
+ *   count are zero; a masked proof gets zero counts and zero buffers, its neighbours are unaffected.  stwo's
+ *   column_witness is always empty for these trees (the smaller columns' queries are the larger ones shifted): there is
+ *   no output for it.
+ * The tree was streamed and never stored, so the opening recomputes what it opens: the LDE rows and the subtree of a
+ * block (position >> (top - log_blowup)) for the values and the witness nodes above layer log_blowup; the witness nodes
+ * at layers <= log_blowup come from the tree's cap (rsv_commit_tree_cap_dev).  cap_mode:
+ *   RSV_CAP_NONE   no d_cap: every block is recomputed (about one commitment), the cap lives in the workspace;
+ *   RSV_CAP_WRITE  the same, and the cap is left in d_cap [n][2^(log_blowup + 1)][8];
+ *   RSV_CAP_READ   d_cap is trusted as given and only the blocks the queries touch are recomputed.
+ * Refusals as rsv_commit_tree_dev, before any device work: NULL ctx, groups, d_cols, d_queries or an output (d_cap in
+ * the modes that use it): RSV_E_NULL; sizes, n_queries, an unknown cap_mode, a pointer not 4-byte aligned: RSV_E_SIZE.
+ * Enqueued on the context's stream with no host synchronisation but the workspace's and the twiddle tables' growth; the
+ * workspace (the plan, the coefficients, the blocks in flight, two node layers) stays within RSV_OPT_WS_BUDGET_MB by
+ * cutting the work into passes of fewer (proof, block) units, as the commitment does. */
+enum rsv_cap_mode { RSV_CAP_NONE = 0, RSV_CAP_WRITE = 1, RSV_CAP_READ = 2 };
+/* Host arithmetic: the output capacities of rsv_decommit_tree_dev per proof, values in words, witness in nodes. */
+int rsv_decommit_sizes(const rsv_commit_group* groups, size_t n_groups, uint32_t log_blowup, uint32_t n_queries, size_t* values_cap,
+                       size_t* witness_cap);
+int rsv_decommit_tree_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup,
+                          const uint8_t* d_mask, const uint32_t* d_queries, uint32_t n_queries, int cap_mode, uint32_t* d_cap,
+                          uint32_t* d_values, uint32_t* d_n_values, uint32_t* d_witness, uint32_t* d_n_witness);
+
 /* Trees 0, 1 and 2 of the recursion circuit's next proof and the transcript between them, from what rsv_witness_trace_dev
  * wrote (d_plonk, d_poseidon, d_ops [n][n_witness_ops]; d_ops may be NULL for a program without witness ops) and d_accept:
  *   tree 0: the program's 10 Plonk + 40 Poseidon preprocessed columns (rsv_trace_preprocessed, uploaded on the first call)
@@ -702,6 +746,26 @@ int rsv_witness_commit_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const 
                            const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
                            uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
                            uint8_t* d_ok);
+/* rsv_witness_commit_dev that also leaves the three trees' caps: d_caps [n][3][2^(log_blowup + 1)][8] (may be NULL: then
+ * exactly rsv_witness_commit_dev), each as rsv_commit_tree_cap_dev's; a proof with d_ok[i] == 0 keeps the caps of the
+ * trees committed before it was refused, and its roots are zero. */
+int rsv_witness_commit_caps_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                                const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
+                                uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums,
+                                uint32_t* d_channel, uint8_t* d_ok, uint32_t* d_caps);
+/* The decommitment of trees 0, 1 and 2 of the recursion circuit's next proof (rsv_decommit_tree_dev three times, on the
+ * trees rsv_witness_commit_dev commits) from the buffers the chain holds: d_plonk, d_poseidon, d_ops, the interaction
+ * columns d_int_plonk and d_int_poseidon, and the mask d_ok (rsv_witness_commit_dev's; NULL: d_accept is the mask).
+ * d_queries [n][n_queries] at the trees' own largest layer, max(lp, lq) + log_blowup bits.  d_caps [n][3][2^(log_blowup +
+ * 1)][8] from rsv_witness_commit_caps_dev (RSV_CAP_READ), or NULL (RSV_CAP_NONE).  Outputs, with tree t's capacities
+ * v_t, w from rsv_decommit_sizes (groups (lp, 10), (lq, 40); (lp, 12), (lq, 48); (lp, 8), (lq, 8)): d_values
+ * [n][v_0 + v_1 + v_2] (a proof's three trees one after the other), d_n_values [n][3], d_witness [n][3][w][8],
+ * d_n_witness [n][3].  Built programs only; refusals and alignment as rsv_witness_commit_dev and rsv_decommit_tree_dev. */
+int rsv_witness_decommit_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                             const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon,
+                             const uint8_t* d_accept, const uint8_t* d_ok, size_t n, uint32_t log_blowup, const uint32_t* d_queries,
+                             uint32_t n_queries, const uint32_t* d_caps, uint32_t* d_values, uint32_t* d_n_values,
+                             uint32_t* d_witness, uint32_t* d_n_witness);
 /* rsv_witness_eval + rsv_witness_trace_dev + rsv_witness_commit_dev on host buffers: roots [n][3][8], draws [n][12], sums
  * [n][2][4] (ok and reason may be NULL). */
 int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,

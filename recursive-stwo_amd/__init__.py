@@ -225,6 +225,14 @@ def _load() -> ctypes.CDLL:
                                                    _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_commit_tree_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, ctypes.c_uint32, vp, vp]),
         "rsv_witness_commit_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
+        "rsv_commit_tree_cap_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, ctypes.c_uint32, vp, vp, vp]),
+        "rsv_witness_commit_caps_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rsv_decommit_sizes": (ctypes.c_int, [ctypes.POINTER(CommitGroup), sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(sz),
+                                              ctypes.POINTER(sz)]),
+        "rsv_decommit_tree_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, ctypes.c_uint32, vp, vp, ctypes.c_uint32, ctypes.c_int,
+                                                 vp, vp, vp, vp, vp]),
+        "rsv_witness_decommit_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp,
+                                                    vp, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -271,6 +279,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
            "rsv_witness_trace_dev", "rsv_witness_trace", "rsv_witness_interaction_dev", "rsv_witness_interaction",
            "rsv_commit_tree_dev", "rsv_witness_commit_dev", "rsv_witness_commit",
+           "rsv_commit_tree_cap_dev", "rsv_witness_commit_caps_dev", "rsv_decommit_sizes", "rsv_decommit_tree_dev", "rsv_witness_decommit_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -789,6 +798,28 @@ def commit_groups(groups):
     return arr
 
 
+CAP_NONE, CAP_WRITE, CAP_READ = 0, 1, 2  # rsv_cap_mode
+
+
+def decommit_sizes(groups, log_blowup: int, n_queries: int):
+    """rsv_decommit_sizes: (values_cap in words, witness_cap in nodes) per proof of rsv_decommit_tree_dev's outputs; groups
+    as commit_groups() takes them, or (log_size, n_cols) pairs.  Host arithmetic."""
+    if groups and not isinstance(groups[0], dict):
+        arr = (CommitGroup * len(groups))(*[CommitGroup(log, nc, None, 0, None, None) for log, nc in groups])
+    else:
+        arr = commit_groups(groups)
+    v, w = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(lib.rsv_decommit_sizes(arr, len(groups), log_blowup, n_queries, ctypes.byref(v), ctypes.byref(w)), "rsv_decommit_sizes")
+    return v.value, w.value
+
+
+def witness_decommit_sizes(program, log_blowup: int, n_queries: int):
+    """The capacities of Context.witness_decommit's outputs: ([values_cap of tree 0, 1, 2], witness_cap)."""
+    lp, lq = program.trace_sizes()
+    sizes = [decommit_sizes([(lp, a), (lq, b)], log_blowup, n_queries) for a, b in ((10, 40), (12, 48), (8, 8))]
+    return [v for v, _ in sizes], sizes[0][1]
+
+
 def fri_paths(proofs: Sequence[bytes], cfg, n_queries: int, max_log: int, n_inner: int, inputs=STANDARD_INPUTS, device: int = 0):
     """per-query pair paths of the FRI trees.  Returns (sib uint32[n,1+n_inner,nq,max_log,8],
     cols uint32[n,1+n_inner,nq,3,8], accept, reason)."""
@@ -1031,24 +1062,59 @@ class Context:
         _check(lib.rsv_witness_interaction_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_accept), ptr(d_lookup), n,
                                                ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_ok)), "rsv_witness_interaction_dev")
 
-    def commit_tree(self, groups, n: int, log_blowup: int, d_roots, d_mask=None):
+    def commit_tree(self, groups, n: int, log_blowup: int, d_roots, d_mask=None, d_cap=None):
         """rsv_commit_tree_dev: groups as commit_groups() takes them (dicts of torch tensors), d_roots uint32[n, 8], d_mask
-        uint8[n] (may be None); enqueued on the context's stream."""
+        uint8[n] (may be None); with d_cap uint32[n, 2^(log_blowup + 1), 8], rsv_commit_tree_cap_dev; enqueued on the
+        context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         arr = commit_groups(groups)
         self.acquire_from_torch()
-        _check(lib.rsv_commit_tree_dev(self._h, arr, len(groups), n, log_blowup, ptr(d_mask), ptr(d_roots)), "rsv_commit_tree_dev")
+        if d_cap is None:
+            _check(lib.rsv_commit_tree_dev(self._h, arr, len(groups), n, log_blowup, ptr(d_mask), ptr(d_roots)), "rsv_commit_tree_dev")
+        else:
+            _check(lib.rsv_commit_tree_cap_dev(self._h, arr, len(groups), n, log_blowup, ptr(d_mask), ptr(d_roots), ptr(d_cap)),
+                   "rsv_commit_tree_cap_dev")
+
+    def decommit_tree(self, groups, n: int, log_blowup: int, d_queries, n_queries: int, d_values, d_n_values, d_witness, d_n_witness,
+                      d_mask=None, cap_mode: int = CAP_NONE, d_cap=None):
+        """rsv_decommit_tree_dev: the opening of the tree commit_tree commits at d_queries uint32[n, n_queries]: d_values
+        uint32[n, values_cap], d_n_values uint32[n], d_witness uint32[n, witness_cap, 8], d_n_witness uint32[n] (capacities:
+        decommit_sizes); cap_mode CAP_NONE / CAP_WRITE / CAP_READ with d_cap uint32[n, 2^(log_blowup + 1), 8]; enqueued on
+        the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        arr = commit_groups(groups)
+        self.acquire_from_torch()
+        _check(lib.rsv_decommit_tree_dev(self._h, arr, len(groups), n, log_blowup, ptr(d_mask), ptr(d_queries), n_queries, cap_mode,
+                                         ptr(d_cap), ptr(d_values), ptr(d_n_values), ptr(d_witness), ptr(d_n_witness)),
+               "rsv_decommit_tree_dev")
 
     def witness_commit(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_accept, n: int, log_blowup: int, d_roots, d_draws,
-                       d_int_plonk, d_int_poseidon, d_sums, d_channel=None, d_ok=None):
+                       d_int_plonk, d_int_poseidon, d_sums, d_channel=None, d_ok=None, d_caps=None):
         """rsv_witness_commit_dev on what Context.witness_trace wrote: d_roots uint32[n, 3, 8], d_draws uint32[n, 12],
         d_int_plonk uint32[n, 8, 2^lp], d_int_poseidon uint32[n, 8, 2^lq], d_sums uint32[n, 2, 4], d_channel uint32[n, 16] and
-        d_ok uint8[n] (may be None); enqueued on the context's stream."""
+        d_ok uint8[n] (may be None); with d_caps uint32[n, 3, 2^(log_blowup + 1), 8], rsv_witness_commit_caps_dev; enqueued on
+        the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         self.acquire_from_torch()
-        _check(lib.rsv_witness_commit_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_accept), n, log_blowup,
-                                          ptr(d_roots), ptr(d_draws), ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_channel),
-                                          ptr(d_ok)), "rsv_witness_commit_dev")
+        lead = (self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_accept), n, log_blowup, ptr(d_roots), ptr(d_draws),
+                ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_sums), ptr(d_channel), ptr(d_ok))
+        if d_caps is None:
+            _check(lib.rsv_witness_commit_dev(*lead), "rsv_witness_commit_dev")
+        else:
+            _check(lib.rsv_witness_commit_caps_dev(*lead, ptr(d_caps)), "rsv_witness_commit_caps_dev")
+
+    def witness_decommit(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int,
+                         log_blowup: int, d_queries, n_queries: int, d_values, d_n_values, d_witness, d_n_witness, d_ok=None, d_caps=None):
+        """rsv_witness_decommit_dev on what Context.witness_commit left: the openings of trees 0, 1 and 2 at d_queries
+        uint32[n, n_queries]: d_values uint32[n, v0 + v1 + v2], d_n_values uint32[n, 3], d_witness uint32[n, 3, w, 8],
+        d_n_witness uint32[n, 3] (capacities: witness_decommit_sizes); d_caps as Context.witness_commit wrote them, or None;
+        enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_decommit_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk),
+                                            ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, log_blowup, ptr(d_queries), n_queries,
+                                            ptr(d_caps), ptr(d_values), ptr(d_n_values), ptr(d_witness), ptr(d_n_witness)),
+               "rsv_witness_decommit_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

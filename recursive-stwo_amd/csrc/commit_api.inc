@@ -1,6 +1,7 @@
-// commit_api.inc — rsv_commit_tree_dev (a generic tree commitment: interpolation, LDE, mixed-size Merkle tree) and
-// rsv_witness_commit_dev / rsv_witness_commit (trees 0, 1, 2 of the recursion circuit's next proof and the transcript
-// draws between them): k_commit.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after interaction_api.inc.
+// commit_api.inc — rsv_commit_tree_dev / rsv_commit_tree_cap_dev (a generic tree commitment: interpolation, LDE, mixed-size
+// Merkle tree, optionally leaving the tree's cap) and rsv_witness_commit_dev / rsv_witness_commit_caps_dev /
+// rsv_witness_commit (trees 0, 1, 2 of the recursion circuit's next proof and the transcript draws between them):
+// k_commit.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after interaction_api.inc; decommit_api.inc follows.
 
 namespace {
 
@@ -57,11 +58,12 @@ size_t cm_ws_bytes(const rsv_commit_group* g, size_t ng, uint32_t b, uint32_t Lm
     return sz.off;
 }
 
+// d_cap (may be nullptr): the nodes of layers 0 .. b of proof i in heap order at d_cap + i * cap_stride (words).
 int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint32_t b, const uint8_t* d_mask, uint32_t* d_roots,
-                uint32_t roots_stride) {
+                uint32_t roots_stride, uint32_t* d_cap = nullptr, uint64_t cap_stride = 0) {
     if (!c || !g || !d_roots) return RSV_E_NULL;
     if (ng == 0 || ng > RSV_MAX_COMMIT_GROUPS || n > (1u << 20) || b < 1 || b > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if ((uintptr_t)d_roots & 3) return RSV_E_SIZE;
+    if (((uintptr_t)d_roots & 3) || ((uintptr_t)d_cap & 3)) return RSV_E_SIZE;
     uint32_t Lmax = 0;
     for (size_t i = 0; i < ng; i++) {
         if (!g[i].d_cols) return RSV_E_NULL;
@@ -150,12 +152,20 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
                 child = a.out;
             }
         }
-        // the plain node layers above the block roots
+        // the plain node layers above the block roots; each level also goes to the cap where one is asked for
+        auto to_cap = [&](const uint32_t* lvl, uint64_t stride, uint32_t l) {
+            if (d_cap)
+                hipLaunchKernelGGL(rsv::k_cm_cap_level, dim3(grid_for(Pc << l, 256)), dim3(256), 0, st, lvl, stride, d_cap, cap_stride, l,
+                                   (uint32_t)Pc, d_mask, (uint32_t)p0);
+        };
         const uint32_t* in = broots;
+        to_cap(broots, (uint64_t)8 << b, b);
         for (uint32_t l = b; l-- > 0;) {
             uint32_t* out = (b - 1 - l) & 1 ? tb : ta;
             hipLaunchKernelGGL(rsv::k_cm_top, dim3(grid_for(Pc << l, 256)), dim3(256), 0, st, in, out, l, (uint32_t)Pc, d_roots, roots_stride,
                                d_mask, (uint32_t)p0);
+            if (l) to_cap(out, (uint64_t)8 << l, l);
+            else to_cap(d_roots + p0 * roots_stride, roots_stride, 0);
             in = out;
         }
     }
@@ -163,26 +173,17 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
     return RSV_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rsv_commit_tree_dev(rsv_ctx* c, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup, const uint8_t* d_mask,
-                        uint32_t* d_roots) {
-    return commit_tree(c, groups, n_groups, n, log_blowup, d_mask, d_roots, 8);
-}
-
-int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
-                           const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
-                           uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
-                           uint8_t* d_ok) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_accept || !d_roots || !d_draws || !d_int_plonk || !d_int_poseidon || !d_sums)
-        return RSV_E_NULL;
-    if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_roots & 3) ||
-        ((uintptr_t)d_draws & 3) || ((uintptr_t)d_int_plonk & 7) || ((uintptr_t)d_int_poseidon & 7) || ((uintptr_t)d_sums & 3) ||
-        ((uintptr_t)d_channel & 3))
-        return RSV_E_SIZE;
+// The three trees of the recursion circuit's next proof as commit groups, and the chain's workspace: tree 0's op column
+// of every proof (column 3 of the Plonk preprocessed ones follows the proof, the other 49 are the program's), the lookup
+// elements, the channels and the ok flags between the trees.  Shared by rsv_witness_commit_caps_dev and
+// rsv_witness_decommit_dev.  Enqueues the op column on the context's stream.
+struct ChainTrees {
+    rsv_commit_group t0[4], t1[2], t2[2];
+    uint32_t *lookup, *chan;
+    uint8_t* ok;
+};
+int chain_trees(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
+                const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, size_t n, uint32_t log_blowup, ChainTrees* ct) {
     int rc = chain_begin(c, prog, n, true);
     if (rc != RSV_OK) return rc;
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
@@ -201,38 +202,78 @@ int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* prog, const ui
     if (rc != RSV_OK) return rc;
     rsv::host::Carve cv{static_cast<char*>(c->ws_chain)};
     uint32_t* ops_col = cv.take<uint32_t>(n * N);
-    uint32_t* lookup = cv.take<uint32_t>(n * 8);
-    uint32_t* chan = cv.take<uint32_t>(n * 16);
-    uint8_t* ok = cv.take<uint8_t>(n);
+    ct->lookup = cv.take<uint32_t>(n * 8);
+    ct->chan = cv.take<uint32_t>(n * 16);
+    ct->ok = cv.take<uint8_t>(n);
     hipStream_t st = c->stream;
     const uint32_t* pre = prog->d_trace_pre;
     const uint32_t* qpre = pre + rsv::trace::PLONK_PRE_COLS * N;
-    // tree 0: the op column (column 3 of the Plonk preprocessed ones) follows the proof, the other 49 are the program's
     hipLaunchKernelGGL(rsv::k_cm_op_column, dim3(grid_for(n * N, 256)), dim3(256), 0, st, pre + 3 * N, lp, (uint32_t)n, ops_col);
     if (n_ops)
         hipLaunchKernelGGL(rsv::k_cm_op_patch, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, prog->d_trace_ops, (uint32_t)n_ops, d_ops, lp,
                            (uint32_t)n, ops_col);
-    const rsv_commit_group t0[4] = {{lp, 3, pre, 0, nullptr, nullptr},
-                                    {lp, 1, ops_col, N, nullptr, nullptr},
-                                    {lp, 6, pre + 4 * N, 0, nullptr, nullptr},
-                                    {lq, rsv::trace::POSEIDON_PRE_COLS, qpre, 0, nullptr, nullptr}};
-    rc = commit_tree(c, t0, 4, n, log_blowup, d_accept, d_roots, 24);
+    ct->t0[0] = {lp, 3, pre, 0, nullptr, nullptr};
+    ct->t0[1] = {lp, 1, ops_col, N, nullptr, nullptr};
+    ct->t0[2] = {lp, 6, pre + 4 * N, 0, nullptr, nullptr};
+    ct->t0[3] = {lq, rsv::trace::POSEIDON_PRE_COLS, qpre, 0, nullptr, nullptr};
+    ct->t1[0] = {lp, rsv::PLONK_COLS_K, d_plonk, rsv::PLONK_COLS_K * N, nullptr, nullptr};  // the 12 + 48 trace columns
+    ct->t1[1] = {lq, rsv::POSEIDON_COLS_K, d_poseidon, rsv::POSEIDON_COLS_K * Q, nullptr, nullptr};
+    ct->t2[0] = {lp, rsv::INT_COLS, d_int_plonk, rsv::INT_COLS * N, nullptr, nullptr};
+    ct->t2[1] = {lq, rsv::INT_COLS, d_int_poseidon, rsv::INT_COLS * Q, nullptr, nullptr};
+    return RSV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsv_commit_tree_dev(rsv_ctx* c, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup, const uint8_t* d_mask,
+                        uint32_t* d_roots) {
+    return commit_tree(c, groups, n_groups, n, log_blowup, d_mask, d_roots, 8);
+}
+
+int rsv_commit_tree_cap_dev(rsv_ctx* c, const rsv_commit_group* groups, size_t n_groups, size_t n, uint32_t log_blowup,
+                            const uint8_t* d_mask, uint32_t* d_roots, uint32_t* d_cap) {
+    return commit_tree(c, groups, n_groups, n, log_blowup, d_mask, d_roots, 8, d_cap, (uint64_t)16 << log_blowup);
+}
+
+int rsv_witness_commit_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                           const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
+                           uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
+                           uint8_t* d_ok) {
+    return rsv_witness_commit_caps_dev(c, prog, d_plonk, d_poseidon, d_ops, d_accept, n, log_blowup, d_roots, d_draws, d_int_plonk,
+                                       d_int_poseidon, d_sums, d_channel, d_ok, nullptr);
+}
+
+int rsv_witness_commit_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                                const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
+                                uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
+                                uint8_t* d_ok, uint32_t* d_caps) {
+    if (!c || !prog || !d_plonk || !d_poseidon || !d_accept || !d_roots || !d_draws || !d_int_plonk || !d_int_poseidon || !d_sums)
+        return RSV_E_NULL;
+    if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
+    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_roots & 3) ||
+        ((uintptr_t)d_draws & 3) || ((uintptr_t)d_int_plonk & 7) || ((uintptr_t)d_int_poseidon & 7) || ((uintptr_t)d_sums & 3) ||
+        ((uintptr_t)d_channel & 3) || ((uintptr_t)d_caps & 3))
+        return RSV_E_SIZE;
+    ChainTrees ct;
+    int rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, log_blowup, &ct);
+    if (rc != RSV_OK || n == 0) return rc;
+    const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
+    hipStream_t st = c->stream;
+    const uint64_t cap1 = (uint64_t)16 << log_blowup, cap3 = 3 * cap1;  // words of one tree's cap, of a proof's three
+    rc = commit_tree(c, ct.t0, 4, n, log_blowup, d_accept, d_roots, 24, d_caps, cap3);
     if (rc != RSV_OK) return rc;
-    // tree 1: the 12 + 48 trace columns
-    const rsv_commit_group t1[2] = {{lp, rsv::PLONK_COLS_K, d_plonk, rsv::PLONK_COLS_K * N, nullptr, nullptr},
-                                    {lq, rsv::POSEIDON_COLS_K, d_poseidon, rsv::POSEIDON_COLS_K * Q, nullptr, nullptr}};
-    rc = commit_tree(c, t1, 2, n, log_blowup, d_accept, d_roots + 8, 24);
+    rc = commit_tree(c, ct.t1, 2, n, log_blowup, d_accept, d_roots + 8, 24, d_caps ? d_caps + cap1 : nullptr, cap3);
     if (rc != RSV_OK) return rc;
-    hipLaunchKernelGGL(rsv::k_cm_draw_lookup, dim3(grid_for(n, 64)), dim3(64), 0, st, d_roots, lp, lq, (uint32_t)n, lookup, chan);
+    hipLaunchKernelGGL(rsv::k_cm_draw_lookup, dim3(grid_for(n, 64)), dim3(64), 0, st, d_roots, lp, lq, (uint32_t)n, ct.lookup, ct.chan);
     // tree 2: the interaction columns under the drawn (z, alpha)
-    rc = rsv_witness_interaction_dev(c, prog, d_plonk, d_poseidon, d_accept, lookup, n, d_int_plonk, d_int_poseidon, d_sums, ok);
+    rc = rsv_witness_interaction_dev(c, prog, d_plonk, d_poseidon, d_accept, ct.lookup, n, d_int_plonk, d_int_poseidon, d_sums, ct.ok);
     if (rc != RSV_OK) return rc;
-    const rsv_commit_group t2[2] = {{lp, rsv::INT_COLS, d_int_plonk, rsv::INT_COLS * N, nullptr, nullptr},
-                                    {lq, rsv::INT_COLS, d_int_poseidon, rsv::INT_COLS * Q, nullptr, nullptr}};
-    rc = commit_tree(c, t2, 2, n, log_blowup, ok, d_roots + 16, 24);
+    rc = commit_tree(c, ct.t2, 2, n, log_blowup, ct.ok, d_roots + 16, 24, d_caps ? d_caps + 2 * cap1 : nullptr, cap3);
     if (rc != RSV_OK) return rc;
-    hipLaunchKernelGGL(rsv::k_cm_draw_coeff, dim3(grid_for(n, 64)), dim3(64), 0, st, d_roots, lookup, d_sums, ok, (uint32_t)n, chan, d_draws,
-                       d_channel, d_ok);
+    hipLaunchKernelGGL(rsv::k_cm_draw_coeff, dim3(grid_for(n, 64)), dim3(64), 0, st, d_roots, ct.lookup, d_sums, ct.ok, (uint32_t)n, ct.chan,
+                       d_draws, d_channel, d_ok);
     HIP_TRY(hipGetLastError());
     return RSV_OK;
 }

@@ -29,6 +29,7 @@
 #include "k_trace.hpp"
 #include "k_interaction.hpp"
 #include "k_commit.hpp"
+#include "k_decommit.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -513,3 +514,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "trace_api.inc"
 #include "interaction_api.inc"
 #include "commit_api.inc"
+#include "decommit_api.inc"

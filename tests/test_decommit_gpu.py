@@ -1,0 +1,358 @@
+"""rsv_decommit_tree_dev / rsv_commit_tree_cap_dev / rsv_witness_decommit_dev / rsv_witness_commit_caps_dev (`-m gpu`): the
+opening of trees 0, 1 and 2 of the next proof.  Against the REFERENCE for all 14 consecutive fixture pairs (the values and
+witness nodes are K+1's queried_values[t] and hash_witness[t], word for word and in count, with nothing taken from K+1 but
+log_blowup_factor, n_queries and the positions), bit for bit against the numpy restatement (tests/decommit_ref.py, pinned
+to the fixtures by tests/test_decommit_host.py) on random trees in the three cap modes, the cap being trusted, and the
+refusals."""
+import numpy as np
+import pytest
+
+from tests import commit_ref as C
+from tests import decommit_ref as D
+from tests import oracle_binding as ob
+from tests.conftest import fixture_cfg, read_proof
+from tests.test_commit_gpu import CASES, _program
+from tests.test_trace_gpu import _inputs
+from tests.test_trace_host import _pins
+
+pytestmark = pytest.mark.gpu
+P = C.P
+DEV = "cuda:0"
+FILL = -1  # every output is prefilled with 0xffffffff: what a call leaves undefined shows
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def _chain_dev(rsv, ctx, wp, batch, inputs, b, caps):
+    """Context.witness -> witness_trace -> witness_commit(d_caps=) -> the device tensors witness_decommit takes."""
+    import torch
+    dev = torch.device(DEV)
+    n = len(batch)
+    lp, lq = wp.trace_sizes()
+    F = wp.shape.flow_count
+    n_ops = len(wp.gates()[1])
+    blob, offsets = rsv.pack(batch)
+    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    d_vars = torch.zeros((n, wp.n_vars, 4), dtype=torch.int32, device=dev)
+    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
+    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
+    t = {"acc": torch.zeros(n, dtype=torch.uint8, device=dev)}
+    ctx.witness(wp, d_blob, d_off, n, d_vars, t["acc"], inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
+    t["plonk"] = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
+    t["pos"] = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
+    t["ops"] = torch.zeros((n, max(n_ops, 1)), dtype=torch.int32, device=dev)
+    ctx.witness_trace(wp, d_vars, t["acc"], n, d_plonk=t["plonk"], d_poseidon=t["pos"], d_ops=t["ops"], d_flow=d_flow, d_flow_swap=d_swap)
+    full = lambda shape: torch.full(shape, FILL, dtype=torch.int32, device=dev)  # noqa: E731
+    t.update(roots=full((n, 3, 8)), draws=full((n, 12)), ip=full((n, 8, 1 << lp)), iq=full((n, 8, 1 << lq)), sums=full((n, 2, 4)),
+             ok=torch.full((n,), 7, dtype=torch.uint8, device=dev), caps=full((n, 3, 2 << b, 8)) if caps else None)
+    ctx.witness_commit(wp, t["plonk"], t["pos"], t["ops"], t["acc"], n, b, t["roots"], t["draws"], t["ip"], t["iq"], t["sums"], d_ok=t["ok"],
+                       d_caps=t["caps"])
+    return t
+
+
+def _witness_decommit(rsv, ctx, wp, t, n, b, queries, caps):
+    """Context.witness_decommit -> per proof and tree (values, witness) cut at the counts; the words past them are zero."""
+    import torch
+    dev = torch.device(DEV)
+    nq = queries.shape[1]
+    vcaps, wcap = rsv.witness_decommit_sizes(wp, b, nq)
+    d_q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.uint32).view(np.int32)).to(dev)
+    d_v = torch.full((n, sum(vcaps)), FILL, dtype=torch.int32, device=dev)
+    d_w = torch.full((n, 3, wcap, 8), FILL, dtype=torch.int32, device=dev)
+    d_nv = torch.full((n, 3), FILL, dtype=torch.int32, device=dev)
+    d_nw = torch.full((n, 3), FILL, dtype=torch.int32, device=dev)
+    ctx.witness_decommit(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, b, d_q, nq, d_v, d_nv, d_w, d_nw, d_ok=t["ok"],
+                         d_caps=t["caps"] if caps else None)
+    ctx.synchronize()
+    v, w, nv, nw = _u32(d_v), _u32(d_w), _u32(d_nv), _u32(d_nw)
+    out = []
+    for p in range(n):
+        off, per = 0, []
+        for k in range(3):
+            vals, wit = v[p, off:off + vcaps[k]], w[p, k]
+            assert nv[p, k] <= vcaps[k] and nw[p, k] <= wcap
+            assert not vals[nv[p, k]:].any() and not wit[nw[p, k]:].any(), (p, k)
+            per.append((vals[:nv[p, k]].copy(), wit[:nw[p, k]].copy()))
+            off += vcaps[k]
+        out.append(per)
+    return out
+
+
+@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+def test_chain_opens_what_the_next_fixture_decommits(rsv, pin):
+    """The library alone, with K+1's log_blowup_factor, n_queries and query positions and nothing else from K+1: for t = 0,
+    1, 2 the values and witness nodes are K+1's queried_values[t] and hash_witness[t], in count and word for word, and zero
+    past the counts; the call without caps gives identical outputs."""
+    src, dst = pin["src"], pin["dst"]
+    wp = _program(rsv, pin)
+    cfg = fixture_cfg(dst)
+    b = cfg.log_blowup_factor
+    nxt = read_proof(dst)
+    qM, M = C.query_positions(nxt, ob)
+    assert len(qM) == cfg.n_queries
+    top = max(wp.trace_sizes()) + b
+    q = (qM >> (M - top)).astype(np.uint32)[None]
+    ctx = rsv.Context(0)
+    t = _chain_dev(rsv, ctx, wp, [read_proof(src)], _inputs(src), b, caps=True)
+    with_caps = _witness_decommit(rsv, ctx, wp, t, 1, b, q, caps=True)[0]
+    without = _witness_decommit(rsv, ctx, wp, t, 1, b, q, caps=False)[0]
+    ctx.close()
+    want = ob.split_variable_part(nxt)
+    for k in range(3):
+        wv = np.array([int(x) for x in want["queried_values"][k]], np.uint32)
+        ww = np.array(want["hash_witness"][k], np.uint32).reshape(-1, 8)
+        for label, (vals, wit) in (("caps", with_caps[k]), ("no caps", without[k])):
+            print(f"{src} tree {k} {label}: {len(vals)} values (fixture {len(wv)}), {len(wit)} witness nodes (fixture {len(ww)})")
+            assert len(vals) == len(wv) and np.array_equal(vals, wv), (k, label)
+            assert len(wit) == len(ww) and np.array_equal(wit, ww), (k, label)
+    wp.close()
+
+
+def test_chain_masked_proof_and_batch(rsv):
+    """Five proofs, the third tampered (rejected), per-proof different queries: the rejected proof gets zero counts and zero
+    buffers, the others what their solo run gives."""
+    pin = next(p for p in _pins() if p["src"] == "recursive_proof_16_15.bin")
+    wp = _program(rsv, pin)
+    src = pin["src"]
+    b = fixture_cfg(pin["dst"]).log_blowup_factor
+    proof = read_proof(src)
+    batch = [proof, proof, ob.tamper(proof, 5), proof, proof]
+    top = max(wp.trace_sizes()) + b
+    q = np.random.default_rng(5).integers(0, 1 << top, (5, 16)).astype(np.uint32)
+    ctx = rsv.Context(0)
+    t = _chain_dev(rsv, ctx, wp, batch, _inputs(src), b, caps=True)
+    got = _witness_decommit(rsv, ctx, wp, t, 5, b, q, caps=True)
+    assert t["ok"].cpu().tolist() == [1, 1, 0, 1, 1]
+    s = _chain_dev(rsv, ctx, wp, [proof], _inputs(src), b, caps=True)
+    for p in range(5):
+        if p == 2:
+            assert all(len(v) == 0 and len(w) == 0 for v, w in got[p])
+            continue
+        solo = _witness_decommit(rsv, ctx, wp, s, 1, b, q[p:p + 1], caps=(p & 1) == 0)[0]
+        for k in range(3):
+            assert np.array_equal(got[p][k][0], solo[k][0]) and np.array_equal(got[p][k][1], solo[k][1]), (p, k)
+    ctx.close()
+    wp.close()
+
+
+def _groups_dev(groups, shared):
+    import torch
+    dev = torch.device(DEV)
+    gs = []
+    for i, (log, cols) in enumerate(groups):
+        cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) % P, dtype=np.uint32)
+        nc = cols.shape[1]
+        gs.append({"log_size": log, "d_cols": torch.from_numpy(cols.view(np.int32)).to(dev), "n_cols": nc,
+                   "proof_stride": 0 if i in shared else nc << log})
+    return gs
+
+
+def _decommit_dev(rsv, ctx, gs, b, n, queries, mask=None, mode=0, cap=None):
+    """Context.decommit_tree -> (values [n][vcap], n_values, witness [n][wcap][8], n_witness, cap tensor or None)."""
+    import torch
+    dev = torch.device(DEV)
+    nq = queries.shape[1]
+    vcap, wcap = rsv.decommit_sizes(gs, b, nq)
+    d_q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.uint32).view(np.int32)).to(dev)
+    d_v = torch.full((n, vcap), FILL, dtype=torch.int32, device=dev)
+    d_w = torch.full((n, wcap, 8), FILL, dtype=torch.int32, device=dev)
+    d_nv = torch.full((n,), FILL, dtype=torch.int32, device=dev)
+    d_nw = torch.full((n,), FILL, dtype=torch.int32, device=dev)
+    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    if mode == rsv.CAP_WRITE:
+        cap = torch.full((n, 2 << b, 8), FILL, dtype=torch.int32, device=dev)
+    ctx.decommit_tree(gs, n, b, d_q, nq, d_v, d_nv, d_w, d_nw, d_mask=d_mask, cap_mode=mode, d_cap=cap)
+    ctx.synchronize()
+    return _u32(d_v), _u32(d_nv), _u32(d_w), _u32(d_nw), cap
+
+
+def _commit_cap(rsv, ctx, gs, b, n, mask, with_cap):
+    import torch
+    dev = torch.device(DEV)
+    d_roots = torch.full((n, 8), FILL, dtype=torch.int32, device=dev)
+    d_cap = torch.full((n, 2 << b, 8), FILL, dtype=torch.int32, device=dev) if with_cap else None
+    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    ctx.commit_tree(gs, n, b, d_roots, d_mask, d_cap=d_cap)
+    ctx.synchronize()
+    return _u32(d_roots), d_cap
+
+
+def _queries(rng, n, nq, top, b, kind):
+    q = rng.integers(0, 1 << 32, (n, nq)).astype(np.uint32)  # bits above top are ignored
+    if kind == "dup" and nq >= 4:
+        q[:, nq // 2:] = q[:, :nq - nq // 2]          # every position twice, unsorted
+        q[:, 1] = q[:, 0] ^ 1                         # a sibling pair: no witness node at the leaves for it
+    if kind == "one_block":
+        q = ((q[:, :1] >> (32 - b)).astype(np.uint64) << (top - b) | (q & ((1 << (top - b)) - 1))).astype(np.uint32)
+    return q
+
+
+def _check_case(rsv, ctx, spec, b, n, mask, nq, seed, kind="dup", budget_cut=None):
+    """One random tree: in the three cap modes the outputs equal the restatement's, element by element and in count, zero
+    past the counts; CAP_WRITE's cap = the restatement's = commit_tree(d_cap=)'s; the roots do not depend on d_cap."""
+    rng = np.random.default_rng(seed)
+    groups = [(log, rng.integers(0, P, (1 if sh else n, nc, 1 << log))) for log, nc, sh in spec]
+    shared = {i for i, (_, _, sh) in enumerate(spec) if sh}
+    top = max(log for log, _, _ in spec) + b
+    q = _queries(rng, n, nq, top, b, kind)
+    gs = _groups_dev(groups, shared)
+    none = _decommit_dev(rsv, ctx, gs, b, n, q, mask, rsv.CAP_NONE)
+    write = _decommit_dev(rsv, ctx, gs, b, n, q, mask, rsv.CAP_WRITE)
+    read = _decommit_dev(rsv, ctx, gs, b, n, q, mask, rsv.CAP_READ, cap=write[4])
+    roots, _ = _commit_cap(rsv, ctx, gs, b, n, mask, False)
+    roots_c, cap_c = _commit_cap(rsv, ctx, gs, b, n, mask, True)
+    assert np.array_equal(roots, roots_c)
+    cap_w, cap_c = _u32(write[4]), _u32(cap_c)
+    assert np.array_equal(cap_w, cap_c)
+    for label, other in (("write", write), ("read", read)):
+        for k in range(4):
+            assert np.array_equal(none[k], other[k]), (label, k)
+    if budget_cut is not None:
+        ctx.set_option("ws_budget_mb", budget_cut)
+        for mode, cap in ((rsv.CAP_NONE, None), (rsv.CAP_READ, write[4])):
+            cut = _decommit_dev(rsv, ctx, gs, b, n, q, mask, mode, cap=cap)
+            for k in range(4):
+                assert np.array_equal(none[k], cut[k]), ("cut", mode, k)
+        ctx.set_option("ws_budget_mb", 8192)
+    values, nv, wit, nw, _ = none
+    for p in range(n):
+        if mask is not None and not mask[p]:
+            assert nv[p] == 0 and nw[p] == 0 and not values[p].any() and not wit[p].any() and not cap_w[p].any(), p
+            continue
+        mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
+        layers = C.tree_layers(mine, b)
+        rv, rw, rcap = D.decommit(layers, q[p], ob, b)
+        assert nv[p] == len(rv) and nw[p] == len(rw), (p, nv[p], len(rv), nw[p], len(rw))
+        assert np.array_equal(values[p, :nv[p]], rv) and not values[p, nv[p]:].any(), p
+        assert np.array_equal(wit[p, :nw[p]], rw) and not wit[p, nw[p]:].any(), p
+        assert np.array_equal(cap_w[p], rcap) and roots[p].tolist() == rcap[1].tolist(), p
+    return groups, q, gs, write[4], none
+
+
+@pytest.mark.parametrize("case", range(len(CASES)))
+def test_decommit_tree_bit_for_bit(rsv, case):
+    """The shapes of test_commit_gpu.CASES, 7 queries with duplicates and a sibling pair, per-proof different."""
+    spec, b, n, mask = CASES[case]
+    ctx = rsv.Context(0)
+    _check_case(rsv, ctx, spec, b, n, mask, 7, 500 + case)
+    ctx.close()
+
+
+WIDE = [  # (groups, b, n, mask, nq, kind)
+    ([(4, 3, False), (6, 2, False)], 8, 2, None, 1, "any"),
+    ([(4, 3, False), (6, 2, False)], 8, 2, None, 16, "dup"),
+    ([(4, 3, False), (6, 2, False)], 8, 1, None, 128, "any"),
+    ([(5, 2, False)], 9, 1, None, 1, "any"),
+    ([(5, 2, False), (3, 4, False)], 9, 2, None, 16, "one_block"),
+    ([(3, 1, False)], 9, 1, None, 128, "dup"),
+    ([(11, 2, False), (7, 3, False)], 3, 2, None, 16, "dup"),   # below CM_LDS_LOG = 12: the LDS pass alone
+    ([(13, 1, False), (9, 2, True)], 3, 2, None, 16, "dup"),    # above: one global forward pass reading the coefficients
+    ([(6, 5, True), (5, 7, False)], 4, 5, [1, 1, 0, 1, 1], 9, "dup"),
+    ([(2, 3, False)], 2, 3, None, 128, "any"),                   # every leaf queried many times over: no witness at all
+    ([(0, 2, False), (3, 1, False)], 2, 2, [0, 1], 5, "dup"),    # a log-0 group: its values sit at layer b, the block roots'
+]
+
+
+def test_decommit_tree_wide_blowups_passes_and_masks(rsv):
+    """log_blowup 8 and 9 with 1, 16 and 128 queries (most blocks untouched), all queries in one block, logs 11 and 13 across
+    the LDS / global-pass boundary mixed with a smaller group, n = 5 with a masked proof, a tiny tree with every leaf queried,
+    a log-0 group."""
+    ctx = rsv.Context(0)
+    for case, (spec, b, n, mask, nq, kind) in enumerate(WIDE):
+        _check_case(rsv, ctx, spec, b, n, mask, nq, 700 + case, kind)
+    ctx.close()
+
+
+def test_decommit_under_a_small_workspace_budget(rsv):
+    """41 proofs at b = 4, a log-9 and a log-8 group, three masked, 7 queries: under a 1 MB budget the opening is cut into
+    passes of fewer list entries and fewer proofs with a short last one, in CAP_NONE (16 blocks a proof) and in CAP_READ
+    (at most 7); both equal the uncut run, and the uncut run the restatement."""
+    mask = [0 if p in (1, 20, 40) else 1 for p in range(41)]
+    ctx = rsv.Context(0)
+    _check_case(rsv, ctx, [(9, 6, False), (8, 11, False)], 4, 41, mask, 7, 900, budget_cut=1)
+    ctx.close()
+
+
+def test_the_cap_is_trusted(rsv):
+    """CAP_READ with one cap entry at a layer <= log_blowup overwritten: the overwritten node appears in d_witness where the
+    plan puts it and nothing else changes, so untouched blocks are not recomputed."""
+    spec, b, n, nq = [(5, 3, False), (4, 2, False)], 6, 2, 5
+    ctx = rsv.Context(0)
+    groups, q, gs, cap, base = _check_case(rsv, ctx, spec, b, n, None, nq, 1100, kind="any")
+    top = 5 + b
+    hits = 0
+    for p in range(n):
+        _, wit = D.plan(q[p], top)
+        slot = sum(len(wit[l]) for l in range(top, b, -1))
+        for l in range(b, 0, -1):
+            for x in wit[l]:
+                bad = cap.clone()
+                bad[p, (1 << l) + x, 3] = 0x1234567
+                got = _decommit_dev(rsv, ctx, gs, b, n, q, None, rsv.CAP_READ, cap=bad)
+                want_w = base[2].copy()
+                want_w[p, slot, 3] = 0x1234567
+                assert np.array_equal(got[2], want_w), (p, l, x)
+                assert np.array_equal(got[0], base[0]) and np.array_equal(got[1], base[1]) and np.array_equal(got[3], base[3])
+                slot += 1
+                hits += 1
+        assert slot == base[3][p]
+    assert hits >= n  # 5 queries cannot cover the 8 nodes of layer 3: every proof misses a sibling at a layer <= 3
+    ctx.close()
+
+
+def test_device_refusals(rsv):
+    """NULL pointers, n_queries 0 and 129, a bad mode, CAP_READ / CAP_WRITE without a buffer, misalignment, log_blowup out of
+    range: the commitment's codes, nothing written."""
+    import torch
+    dev = torch.device(DEV)
+    ctx = rsv.Context(0)
+    cols = torch.zeros((1, 2, 16), dtype=torch.int32, device=dev)
+    raw = torch.zeros(4096, dtype=torch.uint8, device=dev)
+    b, nq = 2, 4
+    g = {"log_size": 4, "d_cols": cols, "n_cols": 2}
+    vcap, wcap = rsv.decommit_sizes([g], b, nq)
+    mark = lambda shape: torch.full(shape, 0x5A5A5A5A, dtype=torch.int32, device=dev)  # noqa: E731
+    outs = {"d_values": mark((1, vcap)), "d_n_values": mark((1,)), "d_witness": mark((1, wcap, 8)), "d_n_witness": mark((1,))}
+    cap = mark((1, 2 << b, 8))
+    q = torch.zeros((1, nq), dtype=torch.int32, device=dev)
+
+    def refused(code, groups=(g,), b=b, d_queries=q, nq=nq, **kw):
+        args = dict(outs, **kw)
+        with pytest.raises(rsv.RsvError) as e:
+            ctx.decommit_tree(list(groups), 1, b, d_queries, nq, args["d_values"], args["d_n_values"], args["d_witness"], args["d_n_witness"],
+                              cap_mode=args.get("cap_mode", 0), d_cap=args.get("d_cap"))
+        assert e.value.code == code, (code, e.value.code)
+
+    refused(-1, d_queries=None)
+    for name in outs:
+        refused(-1, **{name: None})
+        refused(-2, **{name: raw[1:1025]})
+    refused(-1, groups=[dict(g, d_cols=None)])
+    refused(-1, cap_mode=rsv.CAP_READ)
+    refused(-1, cap_mode=rsv.CAP_WRITE)
+    refused(-2, cap_mode=3, d_cap=cap)
+    refused(-2, cap_mode=rsv.CAP_WRITE, d_cap=raw[2:2050])
+    refused(-2, nq=0)
+    refused(-2, nq=129)
+    refused(-2, b=0)
+    refused(-2, b=17)
+    refused(-2, groups=[g] * 9)
+    refused(-2, groups=[dict(g, n_cols=0)])
+    refused(-2, groups=[dict(g, log_size=29)])
+    refused(-2, groups=[dict(g, d_cols=raw[1:])])
+    refused(-2, d_queries=raw[1:17])
+    roots = mark((1, 8))
+    with pytest.raises(rsv.RsvError) as e:
+        ctx.commit_tree([g], 1, b, roots, d_cap=raw[2:2050])
+    assert e.value.code == -2
+    ctx.synchronize()
+    for t in list(outs.values()) + [cap, roots]:
+        assert bool((t == 0x5A5A5A5A).all())
+    ctx.decommit_tree([g], 1, b, q, nq, outs["d_values"], outs["d_n_values"], outs["d_witness"], outs["d_n_witness"], cap_mode=rsv.CAP_WRITE,
+                      d_cap=cap)
+    ctx.synchronize()
+    # four times position 0: one leaf of two columns, one witness node per layer below the top = 4 + b
+    assert int(outs["d_n_values"][0]) == 2 and int(outs["d_n_witness"][0]) == 4 + b and not bool((cap == 0x5A5A5A5A).any())
+    ctx.close()
