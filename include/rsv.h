@@ -772,6 +772,39 @@ int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, con
                        const rsv_public_input* pi, size_t n_pi, uint32_t log_blowup, uint32_t* roots, uint32_t* draws, uint32_t* sums,
                        uint8_t* ok, uint8_t* accept, uint8_t* reason, int device);
 
+/* ---- sampled values of a tree of the next proof: the columns at the OODS point ----------------------------------------
+ * What a proof carries for a tree besides its root and its opening: sampled_values[t], the value of every column's
+ * interpolant (CirclePoly::eval_at_point of the coefficients rsv_commit_group::d_coeffs documents) at QM31 points.  The
+ * same groups, n and d_mask as rsv_commit_tree_dev (d_coeffs and d_lde are ignored), plus
+ *   source    RSV_SAMPLE_COLUMNS: d_cols holds the evaluations, as for the commitment; they are interpolated in the
+ *             workspace by the commitment's own interpolation, in passes of fewer proofs under RSV_OPT_WS_BUDGET_MB.
+ *             RSV_SAMPLE_COEFFS: d_cols holds what a commitment wrote to d_coeffs; the workspace is the weight tables
+ *             and partial sums alone.  The words must be canonical (< P), as a commitment's are: unlike the point
+ *             words they are NOT reduced, and a word >= P is not refused either: the values of that column are then
+ *             unspecified (the unreduced 64-bit sums may wrap), those of the other columns unaffected.
+ *   d_points  [n][n_points][8] (device): per proof and point x then y, QM31 words; any u32 is taken mod P.  The point
+ *             need not lie on the circle.  1 <= n_points <= RSV_MAX_SAMPLE_POINTS.
+ *   d_samples [n][n_points][sum n_cols][4] (device): the columns in group order.  Every element is written; zeros for a
+ *             masked proof, its neighbours unaffected.
+ * log_size <= RSV_MAX_LOG_SIZE - 1 (log_size 0: the constant).  Refusals before any device work: NULL ctx, groups,
+ * d_cols, d_points or d_samples: RSV_E_NULL; group sizes, n, n_points, an unknown source, a pointer not 4-byte aligned:
+ * RSV_E_SIZE.  Enqueued on the context's stream with no host synchronisation but the workspace's and the twiddle
+ * tables' growth. */
+#define RSV_MAX_SAMPLE_POINTS 4
+enum rsv_sample_source { RSV_SAMPLE_COLUMNS = 0, RSV_SAMPLE_COEFFS = 1 };
+int rsv_sample_tree_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_groups, size_t n, const uint8_t* d_mask, int source,
+                        const uint32_t* d_points, uint32_t n_points, uint32_t* d_samples);
+/* sampled_values[0..2] of the recursion circuit's next proof from the buffers the chain holds (arguments as
+ * rsv_witness_decommit_dev's leading ones; the mask is d_ok, or d_accept when d_ok is NULL) and the OODS point d_oods
+ * [n][8] (x then y; any u32 is taken mod P).  d_samples [n][134][4] in the proof's own order, tree-major, column-major,
+ * sample-minor: tree 0 at values 0..49 and tree 1 at 50..109, one value per column at the OODS point; tree 2 at
+ * 110..133, per component columns 0..3 one value and the cumulative columns 4..7 two, first at the previous-row point
+ * (the OODS point minus the step of CanonicCoset(the component's log size), formed on the device), then at the OODS
+ * point.  Zeros for a masked proof.  Built programs only; refusals and alignment as rsv_witness_decommit_dev. */
+int rsv_witness_sample_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                           const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon,
+                           const uint8_t* d_accept, const uint8_t* d_ok, size_t n, const uint32_t* d_oods, uint32_t* d_samples);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -233,6 +233,8 @@ def _load() -> ctypes.CDLL:
                                                  vp, vp, vp, vp, vp]),
         "rsv_witness_decommit_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp,
                                                     vp, vp]),
+        "rsv_sample_tree_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, vp, ctypes.c_int, vp, ctypes.c_uint32, vp]),
+        "rsv_witness_sample_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -280,6 +282,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_witness_trace_dev", "rsv_witness_trace", "rsv_witness_interaction_dev", "rsv_witness_interaction",
            "rsv_commit_tree_dev", "rsv_witness_commit_dev", "rsv_witness_commit",
            "rsv_commit_tree_cap_dev", "rsv_witness_commit_caps_dev", "rsv_decommit_sizes", "rsv_decommit_tree_dev", "rsv_witness_decommit_dev",
+           "rsv_sample_tree_dev", "rsv_witness_sample_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -799,6 +802,8 @@ def commit_groups(groups):
 
 
 CAP_NONE, CAP_WRITE, CAP_READ = 0, 1, 2  # rsv_cap_mode
+SAMPLE_COLUMNS, SAMPLE_COEFFS = 0, 1  # rsv_sample_source
+MAX_SAMPLE_POINTS = 4  # RSV_MAX_SAMPLE_POINTS
 
 
 def decommit_sizes(groups, log_blowup: int, n_queries: int):
@@ -1115,6 +1120,26 @@ class Context:
                                             ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, log_blowup, ptr(d_queries), n_queries,
                                             ptr(d_caps), ptr(d_values), ptr(d_n_values), ptr(d_witness), ptr(d_n_witness)),
                "rsv_witness_decommit_dev")
+
+    def sample_tree(self, groups, n: int, d_points, n_points: int, d_samples, d_mask=None, source: int = SAMPLE_COLUMNS):
+        """rsv_sample_tree_dev: the columns of the tree commit_tree commits (source SAMPLE_COLUMNS: d_cols holds evaluations;
+        SAMPLE_COEFFS: what a commitment wrote to d_coeffs) at d_points uint32[n, n_points, 8] (x then y): d_samples
+        uint32[n, n_points, sum n_cols, 4]; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        arr = commit_groups(groups)
+        self.acquire_from_torch()
+        _check(lib.rsv_sample_tree_dev(self._h, arr, len(groups), n, ptr(d_mask), source, ptr(d_points), n_points, ptr(d_samples)),
+               "rsv_sample_tree_dev")
+
+    def witness_sample(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int, d_oods,
+                       d_samples, d_ok=None):
+        """rsv_witness_sample_dev on what Context.witness_commit left: sampled_values[0..2] of the next proof at d_oods
+        uint32[n, 8], d_samples uint32[n, 134, 4] in the proof's own order; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_sample_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk),
+                                          ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, ptr(d_oods), ptr(d_samples)),
+               "rsv_witness_sample_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

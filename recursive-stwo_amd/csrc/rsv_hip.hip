@@ -30,6 +30,7 @@
 #include "k_interaction.hpp"
 #include "k_commit.hpp"
 #include "k_decommit.hpp"
+#include "k_sample.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -515,3 +516,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "interaction_api.inc"
 #include "commit_api.inc"
 #include "decommit_api.inc"
+#include "sample_api.inc"
