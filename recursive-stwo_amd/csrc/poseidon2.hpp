@@ -276,6 +276,9 @@ struct PermT {
         if constexpr (PACE) asm volatile("s_nop 0" : "+v"(c4));  // the reduction's end: the wait state of pow5's v_min
         return fold2(mad64s(xx, (int32_t)c4, k.kq));
     }
+    // the same S-box entered with the centred x itself (centre_rc below): m = x + 2^30, and the compiler cancels the two
+    // literals against each other, so this form has no centring subtract of its own
+    static __device__ __forceinline__ uint32_t pow5c(int32_t x, const SboxK& k) { return pow5c((uint32_t)x + CENTRE, k); }
 
     // Y = 2*M4*(x0..x3) for 32-bit inputs (any u32), exact in 64 bits.
     static __device__ __forceinline__ void mds4_2x(uint32_t k2, uint32_t k4, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
@@ -327,23 +330,53 @@ struct PermT {
         if constexpr (PACE) asm volatile("s_nop 0" : "+v"(r));
         return r;
     }
+    // The same reduction straight to the centred representative, without the v_min.  canon_rc's minimum is a two-way select on
+    // the sign of a = t - c read as an int32: a lies in [-c, P + HI - c] and does not wrap (c > HI, asserted; the upper end is
+    // HI + RC < P).  With m = canon_rc(t) and x = m - 2^30:
+    //     a >= 0 :  x = a - 2^30           = a + 0xC0000000
+    //     a <  0 :  x = a + P - 2^30       = a + 0x3FFFFFFF
+    // and the two addends are bit-complements, so the sign mask picks one: x = a + ((a >> 31) ^ 0xC0000000), arithmetic shift.
+    // Written in C++ on purpose: hipcc folds the literal add into the fold2 that feeds it (v_add3_u32, the literal in an SGPR)
+    // and the xor into the last add (v_xad_u32; 0xC0000000 is the inline constant -2.0), so the entry is v_add3_u32,
+    // v_ashrrev_i32, v_xad_u32 where fold2's add, canon_rc's two literal adds and v_min and pow5c's centring subtract were
+    // five.  x is bit-identical for every t <= P + HI (tests/test_sbox_signmask.py); tools/perm_ceiling.py prints the static
+    // opcode counts that pin the form.  No wait state of its own: the v_min's went with it.
+    // -DRSV_SBOX_VMIN builds the permutation on the previous entry (canon_rc + pow5c(m)): the parent's code for an A/B
+    // from one tree.
+#ifndef RSV_SBOX_VMIN
+    static constexpr bool CENTRE_RC = true;
+#else
+    static constexpr bool CENTRE_RC = false;
+#endif
+    template <uint32_t RC, uint32_t HI>
+    static __device__ __forceinline__ int32_t centre_rc(uint32_t t) {
+        static_assert(HI < P - RC, "round constant too close to P for the fused reduction");
+        constexpr uint32_t c = P - RC;
+        static_assert((uint64_t)P + HI - c <= 0x7FFFFFFFull, "t - c leaves the int32 range");
+        const int32_t a = (int32_t)(t - c);
+        const uint32_t q = (uint32_t)(a >> 31) ^ 0xC0000000u;
+        return (int32_t)((uint32_t)a + q);
+    }
 
     template <int R, int I>
     static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, const SboxK& k) {
-        s[I] = pow5c(canon_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
+        s[I] = CENTRE_RC ? pow5c(centre_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k)
+                       : pow5c(canon_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
         if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, k);
     }
     // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
     static __device__ __forceinline__ void sbox_full4(uint32_t* s, const SboxK& k) {
-        s[I] = pow5c(canon_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k);
+        s[I] = CENTRE_RC ? pow5c(centre_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k)
+                       : pow5c(canon_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k);
         if constexpr (I + 1 < 16) sbox_full4<I + 1>(s, k);
     }
 
     // Inputs: any u32 words, s[0] <= P + HI_PARTIAL.
     template <int R>
     static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd, const SboxK& k) {
-        uint32_t u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
+        uint32_t u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k)
+                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
         // sum2 = 2 * (u0 + s[1] + ... + s[15]) < 2^37, two chains
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
@@ -366,14 +399,16 @@ struct PermT {
     template <int R>
     static __device__ __forceinline__ void partial_pair(uint32_t* s, uint32_t k2, uint32_t k6, uint32_t k30, const uint32_t* kd,
                                                         const uint32_t* kq, const SboxK& k) {
-        uint32_t u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
+        uint32_t u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k)
+                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
         uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
         uint64_t sum2 = add64(a, b);                                          // 2S < 2^37
         const uint32_t s0 = fold2(mad64(u0, k6, sum2));                       // round R's word 0, <= P + 2^6
         const uint32_t sf = fold2(sum2);                                      // S, <= P + 2^5
-        u0 = pow5c(canon_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k);
+        u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k)
+                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k);
         // sum2 = 2S' = 2 u0' + sum_i 2 d_i s_i + 30 S < 2^50 + 2^37, two chains
         a = mul64(u0, k2, 0); b = mul64(s[1], kd[1], 0);
     #pragma unroll

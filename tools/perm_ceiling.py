@@ -3,16 +3,18 @@
 Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 permutations), derived from the source
 (recursive-stwo_amd/csrc/poseidon2.hpp) and checked against the hardware count:
 
-  S-box with its pre-reduction, x -> x^5 (142 of them: 8 full rounds x 16 + 14 partial rounds x 1), in centred form
-      fold2 (lshr, add) + round constant (moved by 2^30) and canonicalisation in one (2 add-literal, min)
+  S-box with its pre-reduction, x -> x^5 (142 of them: 8 full rounds x 16 + 14 partial rounds x 1), in centred form,
+  entered through centre_rc (the sign-mask select, no v_min)
+      fold2 + round constant (moved by 2^30) + centred representative in one: lshr, v_add3_u32 (hi + lo/2 - c, the literal
+      in an SGPR), v_ashrrev_i32 (the sign of a = t - c), v_xad_u32 ((sign ^ 0xC0000000) + a, the mask an inline constant)
       + pow5c, every product v_mad_i64_i32 with a signed SGPR-pair addend (KP = -P * 2^32, KN = -P * 2^31, KQ = P * 2^31):
-             [add-literal (x = m - 2^30), add (2x)] + [mad(2x, x, KP), lshr, add] + [mad(s1, s1, KN), alignbit, and, add]
-             + [mad(2x, c4, KQ), lshr, add]
-      = 12 fast, 1 v_min_u32, 2 v_mad_i64_i32 a * b + SGPR pair, 1 v_mad_i64_i32 a * a + SGPR pair, 1 v_alignbit_b32
-                                                                        (the partial-round S-box has no fold2: 10 fast)
-      (before the centred form: pow5 = [add, mad (SGPR pair), lshr, add] + [v_mad_i64_i32, alignbit, and, add, add-literal,
-      min] + [mad, lshr, add]: the same 12 fast, 2 min, 42.0 cycles against 37.7 now; before the signed square: 14 fast, 3
-      min, 3 mads without addend per pow5, 47.2 cycles)
+             [add (2x)] + [mad(2x, x, KP), lshr, add] + [mad(s1, s1, KN), alignbit, and, add] + [mad(2x, c4, KQ), lshr, add]
+      = 9 fast, 1 v_add3_u32, 1 v_xad_u32, 2 v_mad_i64_i32 a * b + SGPR pair, 1 v_mad_i64_i32 a * a + SGPR pair,
+        1 v_alignbit_b32
+      (before the sign-mask entry: fold2's add, canon_rc's two literal adds and v_min, pow5c's centring subtract: 12 fast
+      and 1 v_min_u32, 3.0 cycles more than now; before the centred form: pow5 = [add, mad (SGPR pair), lshr, add] +
+      [v_mad_i64_i32, alignbit, and, add, add-literal, min] + [mad, lshr, add]: 12 fast, 2 min, 42.0 cycles; before the
+      signed square: 14 fast, 3 min, 3 mads without addend per pow5, 47.2 cycles)
   full-round linear layer mds16_2x (9 of them; none carries round constants: they are literals of the S-box reduction)
       per 4-word group 2 mad (no addend) + 4 mad (addend) + 2 lshl_add_u64 + 2 lshl_add_u64 (plain adds)        = 40
       column sums 12 + 16 lshl_add_u64                                                                          = 28
@@ -25,23 +27,30 @@ Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 perm
 
   class                      count   cycles/instr at 4 waves/SIMD, expressed at 2.4 GHz (tools/valu_lab.hip, measured r2;
                                      the rows of the signed S-boxes measured with it, 8 waves/SIMD in brackets)
-  fast  (add/sub/lshr/and)    2004   2.50     (a 32-bit literal operand does not change the class: 2.52)
-  v_min_u32                    158   4.27
+  fast  (add/sub/lshr/ashr/and) 1578 2.50     (a 32-bit literal operand does not change the class: 2.52; v_ashrrev_i32 2.44-2.47,
+                                              profiles/r3_valu_lab_*)
+  v_min_u32                     16   4.27     (the output canonicalisations)
+  v_add3_u32                   142   4.42     (4.54 / 4.29 at 4 / 6 waves per SIMD, profiles/r3_valu_lab_*; 4.22 at 8, r14)
+  v_xad_u32                    142   4.38     (4.44 / 4.32 at 4 / 6 waves per SIMD; 4.20 at 8)
   v_mad_u64_u32, no addend     100   4.54
   v_lshl_add_u64               410   4.48
   v_mad_u64_u32, with addend   570   5.10     (SGPR multiplier or live 64-bit addend: 5.05-5.15)
   v_mad_i64_i32, SGPR pair     284   4.51     (4.37; v_mad_u64_u32 with an SGPR-pair addend in the same run: 4.51 (4.37))
   v_mad_i64_i32 square, pair   142   4.30     (4.27; one VGPR operand read twice: the square without addend 4.33 (4.26))
   v_alignbit_b32               142   4.40     (4.20)
-  total                       3810            = the static count: the function is straight-line code since the constants
-                                              became literals (before: 4 428 with 736 addend-mads, 15 650 cycles, 10.05 G/s;
+  total                       3526            = the static count: the function is straight-line code since the constants
+                                              became literals; the 142 v_add3_u32 take their constant from an SGPR, so the
+                                              function also holds 142 + 32 s_mov_b32 (SALU, not in the mix)
+                                              (before: 4 428 with 736 addend-mads, 15 650 cycles, 10.05 G/s;
                                               before the paired partial rounds: 4 398, 2 456 fast and 564 addend-mads,
                                               15 129 cycles, 10.40 G/s; before the signed square: 4 236, 2 288 fast, 442
                                               v_min, 526 mads without addend, 14 739 cycles, 10.67 G/s; before the centred
                                               S-box: 3 952, 300 v_min, 242 mads without addend, 142 v_mad_i64_i32 without
-                                              addend, 142 v_mad_u64_u32 with an SGPR-pair addend, 14 011 cycles, 11.23 G/s)
+                                              addend, 142 v_mad_u64_u32 with an SGPR-pair addend, 14 011 cycles, 11.23 G/s;
+                                              before the sign-mask entry: 3 810, 2 004 fast, 158 v_min, no v_add3_u32 or
+                                              v_xad_u32, 13 399 cycles, 11.74 G/s)
 
-=> 13 399 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 13 399 x 64 = 11.74 G permutations/s.
+=> 12 977 cycles-at-2.4-GHz per 64 permutations per SIMD => 1024 SIMDs x 2.4e9 / 12 977 x 64 = 12.12 G permutations/s.
 (The lab's "cycles at 2.4 GHz" are wall time x 2.4 GHz.  Round 5 separated clock from issue cost (tools/valu_clock.sh,
 profiles/r5_valu_lab_*): under the lab's dense VALU load GRBM_GUI_ACTIVE holds 2.35-2.40 GHz — v_and_b32 at 4 waves per
 SIMD: 2.242 ms at 2.383 GHz for 2 097 152 wave-instructions per SIMD = 2.55 REAL cycles each — so the fast class's 2.5
@@ -55,7 +64,7 @@ import collections
 import re
 import sys
 
-MIX = [("fast", 2004, 2.50), ("v_min_u32", 158, 4.27), ("v_mad_u64_u32 (no addend)", 100, 4.54),
+MIX = [("fast", 1578, 2.50), ("v_min_u32", 16, 4.27), ("v_add3_u32", 142, 4.42), ("v_xad_u32", 142, 4.38), ("v_mad_u64_u32 (no addend)", 100, 4.54),
        ("v_lshl_add_u64", 410, 4.48), ("v_mad_u64_u32 (addend)", 570, 5.10), ("v_mad_i64_i32 (SGPR-pair addend)", 284, 4.51),
        ("v_mad_i64_i32 square (SGPR-pair addend)", 142, 4.30), ("v_alignbit_b32", 142, 4.40)]
 SIMDS, LAB_GHZ = 1024, 2.4

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #define ITERS 65536
@@ -100,6 +101,22 @@ DEF_KERNEL(k_mad64_spair, asm volatile("v_mad_u64_u32 %0, s[10:11], %1, %2, s[20
 // the centred S-box (PermT::pow5c): all three products are v_mad_i64_i32 with a signed 64-bit SGPR-pair addend
 DEF_KERNEL(k_mad_i64_spair, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %2, s[20:21]" : "=v"(w[i]) : "v"(a[i]), "v"(b) : "s10", "s11", "s20", "s21"))
 DEF_KERNEL(k_sqr_i64_spair, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %1, s[20:21]" : "=v"(w[i]) : "v"(a[i]) : "s10", "s11", "s20", "s21"))
+
+// ---- round 16 lab list: the S-box's entry select without v_min.  x = min_u32(t - c, t - c + P) - 2^30 today (sub, add, min,
+// sub: the reference rows) against the sign-mask form a = t - c, sg = a >> 31 (arithmetic), x = a + (sg ^ 0xC0000000): four
+// fast-class ops, each reading the one before it.  Costs of these rows are per SEQUENCE (the count is in the name).  The
+// plain rows run eight sequences back to back per wave, the DEP rows feed each sequence's x to the next one's t.
+DEF_KERNEL(k_xor_lit, asm volatile("v_xor_b32 %0, 0xc0000000, %0" : "+v"(a[i])))
+#define SEL_REF(NOP_MIN) "v_add_u32 %1, 0x8d74a52e, %0\n\tv_add_u32 %0, 0x0d74a52d, %0\n\tv_min_u32 %0, %1, %0\n\t" NOP_MIN "v_add_u32 %0, 0xc0000000, %0"
+#define SEL_SIGN(NOP_END) "v_add_u32 %1, 0x8d74a52e, %0\n\tv_ashrrev_i32 %0, 31, %1\n\tv_xor_b32 %0, 0xc0000000, %0\n\tv_add_u32 %0, %1, %0" NOP_END
+#define SEL_XAD(NOP_END) "v_add_u32 %1, 0x8d74a52e, %0\n\tv_ashrrev_i32 %0, 31, %1\n\tv_xad_u32 %0, %0, %2, %1" NOP_END
+DEF_KERNEL(k_sel_ref, uint32_t t_; asm volatile(SEL_REF("") : "+v"(a[i]), "=&v"(t_)))
+DEF_KERNEL(k_sel_ref_nop, uint32_t t_; asm volatile(SEL_REF("s_nop 0\n\t") : "+v"(a[i]), "=&v"(t_)))
+DEF_KERNEL(k_sel_sign, uint32_t t_; asm volatile(SEL_SIGN("") : "+v"(a[i]), "=&v"(t_)))
+DEF_KERNEL(k_sel_sign_nop, uint32_t t_; asm volatile(SEL_SIGN("\n\ts_nop 0") : "+v"(a[i]), "=&v"(t_)))
+// v_xad_u32 is VOP3: no literal on gfx950, the mask comes from an SGPR
+DEF_KERNEL(k_sel_xad, uint32_t t_; asm volatile(SEL_XAD("") : "+v"(a[i]), "=&v"(t_) : "s"(__builtin_amdgcn_readfirstlane(0xc0000000u ^ (seed >> 31)))))
+DEF_KERNEL(k_sel_xad_nop, uint32_t t_; asm volatile(SEL_XAD("\n\ts_nop 0") : "+v"(a[i]), "=&v"(t_) : "s"(__builtin_amdgcn_readfirstlane(0xc0000000u ^ (seed >> 31)))))
 
 // MFMA rows: one MFMA per "instruction" of the generic harness (8 independent accumulators per wave).
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -195,6 +212,14 @@ DEF_DEP(d_mix, asm volatile("v_add_u32 %1, %1, %2\n\tv_mad_u64_u32 %0, s[10:11],
 DEF_DEP(d_mix_n0, asm volatile("v_add_u32 %1, %1, %2\n\ts_nop 0\n\tv_mad_u64_u32 %0, s[10:11], %1, %1, %0\n\ts_nop 0\n\tv_lshl_add_u64 %0, %0, 1, %0\n\ts_nop 0" : "+v"(w), "+v"(a) : "v"(b) : "s10", "s11"))
 DEF_DEP(d_mix_n1, asm volatile("v_add_u32 %1, %1, %2\n\ts_nop 1\n\tv_mad_u64_u32 %0, s[10:11], %1, %1, %0\n\ts_nop 1\n\tv_lshl_add_u64 %0, %0, 1, %0\n\ts_nop 1" : "+v"(w), "+v"(a) : "v"(b) : "s10", "s11"))
 
+// the round 16 select as ONE chain per wave (the S-box entry of a partial round is such a chain)
+DEF_DEP(d_sel_ref, uint32_t t_; asm volatile(SEL_REF("") : "+v"(a), "=&v"(t_)))
+DEF_DEP(d_sel_ref_nop, uint32_t t_; asm volatile(SEL_REF("s_nop 0\n\t") : "+v"(a), "=&v"(t_)))
+DEF_DEP(d_sel_sign, uint32_t t_; asm volatile(SEL_SIGN("") : "+v"(a), "=&v"(t_)))
+DEF_DEP(d_sel_sign_nop, uint32_t t_; asm volatile(SEL_SIGN("\n\ts_nop 0") : "+v"(a), "=&v"(t_)))
+DEF_DEP(d_sel_xad, uint32_t t_; asm volatile(SEL_XAD("") : "+v"(a), "=&v"(t_) : "s"(__builtin_amdgcn_readfirstlane(0xc0000000u ^ (seed >> 31)))))
+DEF_DEP(d_sel_xad_nop, uint32_t t_; asm volatile(SEL_XAD("\n\ts_nop 0") : "+v"(a), "=&v"(t_) : "s"(__builtin_amdgcn_readfirstlane(0xc0000000u ^ (seed >> 31)))))
+
 typedef void (*kern_t)(uint32_t*, uint32_t);
 struct Case { const char* name; kern_t k; };
 
@@ -229,7 +254,14 @@ int main(int argc, char** argv) {
                     {"DEP v_add_u32", d_add}, {"DEP v_add_u32 + s_nop 0", d_add_n0}, {"DEP v_add_u32 + s_nop 1", d_add_n1}, {"DEP v_add_u32 + s_nop 3", d_add_n3},
                     {"DEP v_min_u32", d_min}, {"DEP v_min_u32 + s_nop 0", d_min_n0}, {"DEP v_min_u32 + s_nop 1", d_min_n1},
                     {"DEP v_mad_u64_u32", d_mad}, {"DEP v_mad_u64_u32 + s_nop 0", d_mad_n0}, {"DEP v_mad_u64_u32 + s_nop 1", d_mad_n1}, {"DEP v_mad_u64_u32 + s_nop 3", d_mad_n3},
-                    {"DEP add,mad,add64 (3)", d_mix}, {"DEP add,mad,add64 + s_nop 0 each (3)", d_mix_n0}, {"DEP add,mad,add64 + s_nop 1 each (3)", d_mix_n1}};
+                    {"DEP add,mad,add64 (3)", d_mix}, {"DEP add,mad,add64 + s_nop 0 each (3)", d_mix_n0}, {"DEP add,mad,add64 + s_nop 1 each (3)", d_mix_n1},
+                    {"v_xor_b32 literal", k_xor_lit},
+                    {"select sub,add,min,sub (4) [today]", k_sel_ref}, {"select sub,add,min+s_nop,sub (4) [today, paced]", k_sel_ref_nop},
+                    {"select sub,ashr,xor,add (4)", k_sel_sign}, {"select sub,ashr,xor,add + s_nop (4)", k_sel_sign_nop},
+                    {"select sub,ashr,xad (3)", k_sel_xad}, {"select sub,ashr,xad + s_nop (3)", k_sel_xad_nop},
+                    {"DEP select sub,add,min,sub (4)", d_sel_ref}, {"DEP select sub,add,min+s_nop,sub (4)", d_sel_ref_nop},
+                    {"DEP select sub,ashr,xor,add (4)", d_sel_sign}, {"DEP select sub,ashr,xor,add + s_nop (4)", d_sel_sign_nop},
+                    {"DEP select sub,ashr,xad (3)", d_sel_xad}, {"DEP select sub,ashr,xad + s_nop (3)", d_sel_xad_nop}};
     hipDeviceProp_t prop;
     hipGetDeviceProperties(&prop, 0);
     int cus = prop.multiProcessorCount;
@@ -239,6 +271,7 @@ int main(int argc, char** argv) {
     hipEventCreate(&e0); hipEventCreate(&e1);
     printf("%-38s %9s %12s %12s %10s\n", "instruction", "ms", "cyc@2.4(wall)", "cyc(shader)", "clock GHz");
     for (auto& c : cases) {
+        if (argc > 2 && !strstr(c.name, argv[2])) continue;                 // optional: only the rows whose name contains argv[2]
         hipLaunchKernelGGL(c.k, dim3(blocks), dim3(256), 0, 0, out, 1u);
         hipDeviceSynchronize();
         hipMemset(out, 0, out_bytes);
