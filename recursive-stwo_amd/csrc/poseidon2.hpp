@@ -9,7 +9,7 @@
 // MI355X mapping: ONE LANE PER PERMUTATION.  The 16-word state lives in 16
 // VGPRs of one lane, so a wave64 advances 64 independent permutations with no
 // cross-lane traffic.  The fast path (poseidon2_inline, below) is straight-line
-// code: round constants are 32-bit literals of a fused add + canonicalise, the
+// code: round constants are 32-bit literals of a fused add + reduce, the
 // linear layers accumulate unreduced in 64 bits, the partial-round diagonal is
 // a multiply-accumulate by a power of two.  One out-of-line instance
 // (poseidon2(), ~30 KB of code in 38 VGPRs) is shared by every call site.
@@ -50,7 +50,8 @@ constexpr uint32_t RC_FULL_K[8][16] = RSV_RC_FULL_INIT;  // the same values as c
 __constant__ __attribute__((aligned(64))) uint32_t RC_PARTIAL[16] = RSV_RC_PARTIAL_INIT;
 constexpr uint32_t RC_PARTIAL_K[16] = RSV_RC_PARTIAL_INIT;
 
-// ---- straightforward canonical implementation (readable restatement; baseline of tools/perm_lab.hip)
+// ---- canonical S-box and external matrix, one reduction per operation: what the trace and emulated-field kernels use
+// (k_trace.hpp, k_emulated.hpp).  tools/perm_lab.hip builds the whole permutation from them as its baseline.
 __device__ __forceinline__ uint32_t pow5_ref(uint32_t x) {
     uint32_t x2 = m_sqr(x);
     return m_mul(m_sqr(x2), x);
@@ -78,67 +79,42 @@ __device__ __forceinline__ void mds16_ref(uint32_t* s) {
     }
 }
 
-__device__ __forceinline__ void poseidon2_ref_inline(uint32_t* s) {
-    mds16_ref(s);
-#pragma unroll 1
-    for (int r = 0; r < 4; r++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = pow5_ref(m_add(s[i], RC_FULL[r][i]));
-        mds16_ref(s);
-    }
-#pragma unroll 1
-    for (int r = 0; r < 14; r++) {
-        s[0] = pow5_ref(m_add(s[0], RC_PARTIAL[r]));
-        // sum of all 16 words as a balanced tree
-        uint32_t a0 = m_add(s[0], s[1]), a1 = m_add(s[2], s[3]), a2 = m_add(s[4], s[5]), a3 = m_add(s[6], s[7]);
-        uint32_t a4 = m_add(s[8], s[9]), a5 = m_add(s[10], s[11]), a6 = m_add(s[12], s[13]),
-                 a7 = m_add(s[14], s[15]);
-        uint32_t sum = m_add(m_add(m_add(a0, a1), m_add(a2, a3)), m_add(m_add(a4, a5), m_add(a6, a7)));
-        s[0] = m_add(sum, m_add(m_dbl(s[0]), s[0]));  // diag 3
-#pragma unroll
-        for (int i = 1; i < 16; i++) s[i] = m_add(sum, m_shl(s[i], i + 1));  // diag 2^(i+1)
-    }
-#pragma unroll 1
-    for (int r = 4; r < 8; r++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = pow5_ref(m_add(s[i], RC_FULL[r][i]));
-        mds16_ref(s);
-    }
-}
-
-
 // ===========================================================================================
 // Fast path.  Instruction costs measured on MI355X (tools/valu_lab.hip, 4 waves/SIMD):
-//   ~2.5 cycles : v_add_u32 v_sub_u32 v_and_b32 v_or_b32 v_lshrrev_b32 v_mov_b32 (also with a literal)
-//   ~4.3-4.6    : v_min_u32 v_lshlrev_b32 v_alignbit_b32 v_and_or_b32 v_mul_lo/hi_u32 v_lshl_add_u64
+//   ~2.5 cycles : v_add_u32 v_sub_u32 v_and_b32 v_or_b32 v_lshrrev_b32 v_ashrrev_i32 v_mov_b32 (also with a literal)
+//   ~4.3-4.6    : v_min_u32 v_lshlrev_b32 v_alignbit_b32 v_and_or_b32 v_mul_lo/hi_u32 v_lshl_add_u64 v_add3_u32 v_xad_u32
 //                 v_mad_u64_u32 (4.55; 5.05 with a live 64-bit addend)   -- the 32x32->64 multiply is
 //                 NOT quarter rate on gfx950, so the cost of a modular multiply is its reduction.
-//                 v_mad_i64_i32 without an addend 4.34, v_mad_u64_u32 with an SGPR-pair addend 4.48 (pow5)
-//                 v_mad_i64_i32 with an SGPR-pair addend 4.51, 4.30 as a square (pow5c)
+//                 v_mad_i64_i32 with an SGPR-pair addend 4.51, 4.30 as a square (the S-box's products); without an
+//                 addend 4.34; v_mad_u64_u32 with an SGPR-pair addend 4.48
 // Consequences used below:
 //   * linear layers accumulate UNREDUCED in 64 bits (one v_lshl_add_u64 / v_mad_u64_u32 per term,
 //     shifts by 1..4 and small multipliers are free), and are folded once per round;
 //   * accumulators hold 2*v, so the Mersenne fold (v >> 31) + (v & P) is hi32 + (lo32 >> 1): two
 //     fast-class instructions instead of v_and + v_alignbit + v_add;
 //   * a product x*y is formed as (2x)*y for the same reason;
+//   * a conditional subtract is a slow-class v_min, so the S-box has none: its values are signed words, kept in range by
+//     addends that are multiples of P (pow5c), and its input is reduced by a sign-mask select (centre_rc);
 //   * values between steps are only "weakly" reduced; the ranges are tracked in the comments:
 //       C  = [0, P]           (canonical, or P itself which is congruent to 0)
 //       L2 = [0, 2P]          (one conditional subtract away from C)
-//     Bit-exactness with the canonical reference (poseidon2_ref_inline) is tested on the GPU.
+//     tests/perm_model.py restates this arithmetic on machine words: the tests built on it prove every range and compare
+//     the model with the reference permutation.  The kernels are compared with that reference on the GPU
+//     (tests/test_perm_signmask_gpu.py); tools/perm_lab.hip compares them with a canonical restatement.
 // ===========================================================================================
 // Issue pacing.  Measured on MI355X (whole pipeline, 65 536 proofs): when a wave presents an instruction that depends
-// on its own previous VALU result, the SIMD stalls on it instead of issuing another wave's instruction.  One extra
-// wait state behind every v_mad_u64_u32 (the compiler adds one of its own behind an asm statement whose result is
-// read next) and two behind the v_min that ends a reduction take the wave out of arbitration for those cycles:
-//     no pacing 37.75 ms | mad 36.40 | mad + canon 35.80 | also behind fold2 / the doublings: 35.75-35.85 (plateau)
+// on its own previous VALU result, the SIMD stalls on it instead of issuing another wave's instruction.  A wait state
+// behind such an instruction takes the wave out of arbitration for those cycles.  Measured when every reduction still
+// ended in a v_min: one extra wait state behind every v_mad_u64_u32 (the compiler adds one of its own behind an asm
+// statement whose result is read next) and two behind the v_min gave
+//     no pacing 37.75 ms | mad 36.40 | mad + v_min 35.80 | also behind fold2 / the doublings: 35.75-35.85 (plateau)
 //     two wait states behind the multiplies: 36.17 (worse) | s_nop 3: 40.2
 // The wait states cost nothing at >= 4 waves per SIMD (other waves fill them); at one wave per SIMD (the lane-form
 // transcript of batches > 24 576) they lengthen the chain by ~25 % — that kernel runs underneath k_row_hash.
-// PACE: the wait states above (one behind every 64-bit multiply, one behind the v_min that ends a reduction and behind the
-// fold that ends pow5c's x^4).  They pay where several waves share a SIMD and cost ~25 % where a wave is (nearly) alone on
-// it, so the verify kernels pick the instance by
-// the size of the launch (poseidon2_half below): paced for launches that fill the machine, unpaced for a small batch's trees
-// and for the one-wave-per-SIMD lane-form transcript.
+// PACE: one wait state behind every 64-bit multiply and one behind the fold that ends pow5c's x^4 (the end of the S-box's
+// only multi-instruction reduction).  They pay where several waves share a SIMD and cost ~25 % where a wave is (nearly)
+// alone on it, so the verify kernels pick the instance by the size of the launch (poseidon2_half below): paced for
+// launches that fill the machine, unpaced for a small batch's trees and for the one-wave-per-SIMD lane-form transcript.
 template <bool PACE>
 struct PermT {
     static __device__ __forceinline__ uint64_t add64(uint64_t a, uint64_t b) {
@@ -160,20 +136,13 @@ struct PermT {
         asm volatile("s_mov_b32 %0, %1" : "=s"(r) : "n"(k));
         return r;
     }
-    // the same for a 64-bit constant, in an SGPR pair (the S-box's addend: see pow5)
+    // the same for a 64-bit constant, in an SGPR pair (the S-box's addends: see pow5c)
     static __device__ __forceinline__ uint64_t opaque64(uint64_t k) {
         return (uint64_t)opaque((uint32_t)(k >> 32)) << 32 | opaque((uint32_t)k);
     }
-    static constexpr uint64_t KP = 0 - ((uint64_t)P << 32);  // 2^64 - P * 2^32
     // The asm form (instead of `(uint64_t)a * b + c`) also keeps hipcc from re-associating
     // x0*k + x1*k into (x0 + x1)*k, which costs a 64-bit add, a 64x32 multiply and zero-extension moves.
-    static __device__ __forceinline__ uint64_t mul64(uint32_t a, uint32_t b) {
-        uint64_t d, carry;
-        if constexpr (PACE) asm("v_mad_u64_u32 %0, %1, %2, %3, 0\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b));
-        else asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b));
-        return d;
-    }
-    static __device__ __forceinline__ uint64_t mul64(uint32_t a, uint32_t b_uniform, int) {  // b in an SGPR
+    static __device__ __forceinline__ uint64_t mul64(uint32_t a, uint32_t b_uniform) {  // a * b, b in an SGPR
         uint64_t d, carry;
         if constexpr (PACE) asm("v_mad_u64_u32 %0, %1, %2, %3, 0\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "s"(b_uniform));
         else asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(d), "=s"(carry) : "v"(a), "s"(b_uniform));
@@ -183,19 +152,6 @@ struct PermT {
         uint64_t d, carry;
         if constexpr (PACE) asm("v_mad_u64_u32 %0, %1, %2, %3, %4\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "s"(b_uniform), "v"(c));
         else asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "s"(b_uniform), "v"(c));
-        return d;
-    }
-    static __device__ __forceinline__ uint64_t mad64(uint32_t a, uint32_t b, uint64_t c_uniform, int) {  // a * b + c, c in an SGPR pair
-        uint64_t d, carry;
-        if constexpr (PACE) asm("v_mad_u64_u32 %0, %1, %2, %3, %4\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
-        else asm("v_mad_u64_u32 %0, %1, %2, %3, %4" : "=v"(d), "=s"(carry) : "v"(a), "v"(b), "s"(c_uniform));
-        return d;
-    }
-    // signed 32x32 -> 64 square (v_mad_i64_i32): |a| <= P gives a^2 <= P^2 < 2^62
-    static __device__ __forceinline__ uint64_t sqr64s(int32_t a) {
-        uint64_t d, carry;
-        if constexpr (PACE) asm("v_mad_i64_i32 %0, %1, %2, %2, 0\n\ts_nop 0" : "=v"(d), "=s"(carry) : "v"(a));
-        else asm("v_mad_i64_i32 %0, %1, %2, %2, 0" : "=v"(d), "=s"(carry) : "v"(a));
         return d;
     }
     // signed a * b + c (v_mad_i64_i32), c a signed 64-bit constant in an SGPR pair; the square a * a + c reads one register
@@ -221,43 +177,22 @@ struct PermT {
         uint32_t r = (uint32_t)(V >> 32) + ((uint32_t)V >> 1);
         return r;
     }
-    // t in [0, 2P] -> C
-    static __device__ __forceinline__ uint32_t canon(uint32_t t) {
-        uint32_t r = min(t, t - P);
-        if constexpr (PACE) asm volatile("s_nop 0" : "+v"(r));
-        return r;
-    }
 
-    // x in C  ->  x^5 in L2.  x^2 is squared in SIGNED form instead of being canonicalised and doubled: with the addend
-    // kp = 2^64 - P * 2^32 (an SGPR pair, see opaque64()) the first product is 2x^2 - P * 2^32 mod 2^64 (the carry-out is
-    // dropped), so its fold is t1 - P with t1 = fold2(2x^2) in [0, 2P - 1]: s1 in [-P, P - 1], congruent to x^2.  Then
-    // s1^2 <= P^2 < 2^62 is folded undoubled.  13 instructions instead of 15 (one v_min and one fast-class doubling fewer);
-    // tests/test_sbox_signed_square.py proves the ranges at their extremes.
-    static __device__ __forceinline__ uint32_t pow5(uint32_t x, uint64_t kp) {
-        const uint32_t xx = dbl32(x);                         // 2x <= 2P, used by the first and the last product
-        const int32_t s1 = (int32_t)fold2(mad64(xx, x, kp, 0));  // 2x^2 < 2^63; t1 - P in [-P, P - 1]
-        const uint64_t V2 = sqr64s(s1);                       // [0, P^2]
-        // (V2 >> 31) + (V2 & P) <= (P - 1) + P
-        const uint32_t c4 = canon(__builtin_amdgcn_alignbit((uint32_t)(V2 >> 32), (uint32_t)V2, 31) + ((uint32_t)V2 & P));
-        return fold2(mul64(xx, c4));                          // 2x*c4: hi <= P, lo>>1 <= P
-    }
-    // (pow5 above is the S-box of the previous form, x canonical; the permutation calls pow5c.  It stays beside it as the
-    // form tests/test_sbox_signed_square.py models.)
-
-    // The centred S-box's three 64-bit addends, multiples of P in SGPR pairs (opaque64()), read as signed 64-bit values:
-    // KP = -P * 2^32 (the first product's, as in pow5), KN = -P * 2^31 (the second), KQ = P * 2^31 (the last).
+    // ---- The S-box.  Its input is the CENTRED representative x of t + rc, in [-2^30, 2^30 - 2] (centre_rc below), and
+    // every intermediate is a signed word.  The three products are v_mad_i64_i32 with a signed 64-bit addend that is a
+    // multiple of P, held in an SGPR pair (opaque64()): KP = -P * 2^32, KN = -P * 2^31, KQ = P * 2^31.
+    static constexpr uint64_t KP = 0 - ((uint64_t)P << 32);
     static constexpr uint64_t KN = 0 - ((uint64_t)P << 31), KQ = (uint64_t)P << 31;
     struct SboxK {
         uint64_t kp, kn, kq;
     };
     static __device__ __forceinline__ SboxK sbox_k() { return {opaque64(KP), opaque64(KN), opaque64(KQ)}; }
-    // The S-box input is reduced by canon_rc with the round constant moved by CENTRE: it yields m = (x + 2^30) mod P, and
-    // x = m - 2^30 is the CENTRED representative of x, in [-2^30, 2^30 - 2].
+    // centre_rc reduces with the round constant moved by CENTRE: (t + rc + 2^30) mod P, less 2^30, is the centred x
     static constexpr uint32_t CENTRE = 1u << 30;
     static constexpr uint32_t centred(uint32_t rc) { return (uint32_t)(((uint64_t)rc + CENTRE) % P); }
 
-    // m = (x + 2^30) mod P  ->  x^5 in L2, every intermediate a signed word (v_mad_i64_i32 with the addends above):
-    //     x  = m - 2^30                  [-2^30, 2^30 - 2]
+    // x centred  ->  x^5 in L2:
+    //     x                              [-2^30, 2^30 - 2]
     //     xx = 2x                        [-2^31, 2^31 - 4]: even, and an int32 because x is centred
     //     s1 = fold2(xx * x + KP)        2x^2 <= 2^61: fold2(2x^2) - P in [-P, 2^29], congruent to x^2
     //     V2 = s1 * s1 + KN              [-P * 2^31, -P]
@@ -265,26 +200,22 @@ struct PermT {
     //     y  = fold2(xx * c4 + KQ)       xx * c4 in [-2^31 P, 2^31 P], so V3 in [0, 2^32 P] and even: y in [0, 2P - 1]
     // The last product is the one a signed S-box has to resolve: x * c4 over two full-width operands spans 2 P^2, one bit
     // more than a 32-bit fold takes.  Centring x lets it be doubled inside an int32, so the product is even, spans 2^32 P <
-    // 2^63 and ends in the two-instruction fold2.  Against pow5: one v_min fewer (c4 stays centred), the centring subtract
-    // where the canonicalisation's subtract was; 12 instructions.  tests/test_sbox_centred.py proves the ranges.
-    static __device__ __forceinline__ uint32_t pow5c(uint32_t m, const SboxK& k) {
-        const int32_t x = (int32_t)(m - CENTRE);
+    // 2^63 and ends in the two-instruction fold2.  11 instructions: a doubling, three multiplies, two fold2 and the
+    // three-instruction fold of V2 (alignbit, and, add).  tests/test_sbox_centred.py proves the ranges.
+    static __device__ __forceinline__ uint32_t pow5c(int32_t x, const SboxK& k) {
         const int32_t xx = (int32_t)dbl32((uint32_t)x);
         const int32_t s1 = (int32_t)fold2(mad64s(xx, x, k.kp));
         const uint64_t V2 = sqr64s(s1, k.kn);
         uint32_t c4 = __builtin_amdgcn_alignbit((uint32_t)(V2 >> 32), (uint32_t)V2, 31) + ((uint32_t)V2 & P);
-        if constexpr (PACE) asm volatile("s_nop 0" : "+v"(c4));  // the reduction's end: the wait state of pow5's v_min
+        if constexpr (PACE) asm volatile("s_nop 0" : "+v"(c4));  // the reduction's end
         return fold2(mad64s(xx, (int32_t)c4, k.kq));
     }
-    // the same S-box entered with the centred x itself (centre_rc below): m = x + 2^30, and the compiler cancels the two
-    // literals against each other, so this form has no centring subtract of its own
-    static __device__ __forceinline__ uint32_t pow5c(int32_t x, const SboxK& k) { return pow5c((uint32_t)x + CENTRE, k); }
 
     // Y = 2*M4*(x0..x3) for 32-bit inputs (any u32), exact in 64 bits.
     static __device__ __forceinline__ void mds4_2x(uint32_t k2, uint32_t k4, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
                                             uint64_t& y0, uint64_t& y1, uint64_t& y2, uint64_t& y3) {
-        uint64_t T0 = mad64(x0, k2, mul64(x1, k2, 0));           // 2(x0 + x1)
-        uint64_t T1 = mad64(x2, k2, mul64(x3, k2, 0));           // 2(x2 + x3)
+        uint64_t T0 = mad64(x0, k2, mul64(x1, k2));           // 2(x0 + x1)
+        uint64_t T1 = mad64(x2, k2, mul64(x3, k2));           // 2(x2 + x3)
         uint64_t T2 = mad64(x1, k4, T1);                      // 2(2x1 + t1)
         uint64_t T3 = mad64(x3, k4, T0);                      // 2(2x3 + t0)
         uint64_t T4 = shl_add64<2>(T1, T3);                   // 2(4t1 + t3)
@@ -309,45 +240,25 @@ struct PermT {
         }
     }
 
-    // Round constant + canonicalisation in one step.  t = fold2(V) with V the doubled accumulator of a linear layer
-    // WITHOUT its round constant: t <= P + HI where HI bounds the accumulator's high word at the call site (HI_FULL after a
-    // full-round layer, HI_PARTIAL after a partial round or pair).  With c = P - rc (a compile-time literal):
-    //     t >= c :  t - c in [0, P - 1]  (needs c > HI: asserted per call site below)
-    //               and t - c + P in [P, 2P - 1]: the minimum is t - c  = t + rc - P
-    //     t <  c :  t - c wraps to >= 2^32 - P > 2^31 and t - c + P = t + rc in [0, P - 1]: the minimum is t + rc
-    // so min(t - c, t - c + P) is the CANONICAL t + rc mod P in two literal adds (fast class, 2.5 cycles each) and a
-    // v_min — against v_mad_u64_u32 (2 * rc folded into V, 5.1) + a literal add + v_min for the unfused form.
-    // The high words that reach canon_rc (tests/test_partial_pairs.py proves both over the whole schedule):
+    // Round constant + reduction to the centred representative in one step: the S-box's entry.  t = fold2(V) with V the
+    // doubled accumulator of a linear layer WITHOUT its round constant: t <= P + HI where HI bounds the accumulator's high
+    // word at the call site.  RC is the round constant moved by 2^30 (centred()), c = P - RC a compile-time literal, and
+    // a = t - c read as an int32 lies in [-c, P + HI - c]: it does not wrap (c > HI, asserted; the upper end is HI + RC < P).
+    // t + RC mod P is a two-way select on the sign of a, and x is that less 2^30:
+    //     a >= 0 :  t + RC - P in [0, P - 1]      x = a - 2^30       = a + 0xC0000000
+    //     a <  0 :  t + RC     in [0, P - 1]      x = a + P - 2^30   = a + 0x3FFFFFFF
+    // The two addends are bit-complements, so the sign mask picks one: x = a + ((a >> 31) ^ 0xC0000000), arithmetic shift.
+    // Written in C++ on purpose: hipcc folds the literal add into the fold2 that feeds it (v_add3_u32, the literal in an SGPR)
+    // and the xor into the last add (v_xad_u32; 0xC0000000 is the inline constant -2.0), so fold2 and the entry together
+    // are v_lshrrev_b32, v_add3_u32, v_ashrrev_i32, v_xad_u32 — against v_mad_u64_u32 (2 * rc folded into V, 5.1) and a
+    // conditional subtract for a round constant carried by the accumulator.  No wait state of its own.
+    // tests/test_sbox_signmask.py proves x equal to min(t - c, t - c + P) - 2^30, the same select by v_min, at every call
+    // site; tools/perm_ceiling.py prints the static opcode counts that pin the form.
+    // The high words that reach centre_rc (tests/test_partial_pairs.py proves both over the whole schedule):
     //   HI_FULL    the fold of a full-round layer: the rows of circ(2M4, M4, M4, M4) sum to at most 80, so V < 160 * 2^32;
     //   HI_PARTIAL word 0 after a single partial round or a pair (at most 165 492), and every word after a single round (at
     //              most 65 561): V < 2^50 with a small addend.
     static constexpr uint32_t HI_FULL = 160, HI_PARTIAL = 1u << 18;
-    template <uint32_t RC, uint32_t HI>
-    static __device__ __forceinline__ uint32_t canon_rc(uint32_t t) {
-        static_assert(HI < P - RC, "round constant too close to P for the fused reduction");
-        constexpr uint32_t c = P - RC;
-        uint32_t r = min(t - c, t + (P - c));
-        if constexpr (PACE) asm volatile("s_nop 0" : "+v"(r));
-        return r;
-    }
-    // The same reduction straight to the centred representative, without the v_min.  canon_rc's minimum is a two-way select on
-    // the sign of a = t - c read as an int32: a lies in [-c, P + HI - c] and does not wrap (c > HI, asserted; the upper end is
-    // HI + RC < P).  With m = canon_rc(t) and x = m - 2^30:
-    //     a >= 0 :  x = a - 2^30           = a + 0xC0000000
-    //     a <  0 :  x = a + P - 2^30       = a + 0x3FFFFFFF
-    // and the two addends are bit-complements, so the sign mask picks one: x = a + ((a >> 31) ^ 0xC0000000), arithmetic shift.
-    // Written in C++ on purpose: hipcc folds the literal add into the fold2 that feeds it (v_add3_u32, the literal in an SGPR)
-    // and the xor into the last add (v_xad_u32; 0xC0000000 is the inline constant -2.0), so the entry is v_add3_u32,
-    // v_ashrrev_i32, v_xad_u32 where fold2's add, canon_rc's two literal adds and v_min and pow5c's centring subtract were
-    // five.  x is bit-identical for every t <= P + HI (tests/test_sbox_signmask.py); tools/perm_ceiling.py prints the static
-    // opcode counts that pin the form.  No wait state of its own: the v_min's went with it.
-    // -DRSV_SBOX_VMIN builds the permutation on the previous entry (canon_rc + pow5c(m)): the parent's code for an A/B
-    // from one tree.
-#ifndef RSV_SBOX_VMIN
-    static constexpr bool CENTRE_RC = true;
-#else
-    static constexpr bool CENTRE_RC = false;
-#endif
     template <uint32_t RC, uint32_t HI>
     static __device__ __forceinline__ int32_t centre_rc(uint32_t t) {
         static_assert(HI < P - RC, "round constant too close to P for the fused reduction");
@@ -360,25 +271,22 @@ struct PermT {
 
     template <int R, int I>
     static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, const SboxK& k) {
-        s[I] = CENTRE_RC ? pow5c(centre_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k)
-                       : pow5c(canon_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
+        s[I] = pow5c(centre_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
         if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, k);
     }
     // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
     static __device__ __forceinline__ void sbox_full4(uint32_t* s, const SboxK& k) {
-        s[I] = CENTRE_RC ? pow5c(centre_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k)
-                       : pow5c(canon_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k);
+        s[I] = pow5c(centre_rc<centred(RC_FULL_K[4][I]), HI_PARTIAL>(s[I]), k);
         if constexpr (I + 1 < 16) sbox_full4<I + 1>(s, k);
     }
 
     // Inputs: any u32 words, s[0] <= P + HI_PARTIAL.
     template <int R>
     static __device__ __forceinline__ void partial_round(uint32_t* s, uint32_t k2, uint32_t k6, const uint32_t* kd, const SboxK& k) {
-        uint32_t u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k)
-                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
+        uint32_t u0 = pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
         // sum2 = 2 * (u0 + s[1] + ... + s[15]) < 2^37, two chains
-        uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
+        uint64_t a = mul64(u0, k2), b = mul64(s[1], k2);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
         uint64_t sum2 = add64(a, b);
@@ -399,18 +307,16 @@ struct PermT {
     template <int R>
     static __device__ __forceinline__ void partial_pair(uint32_t* s, uint32_t k2, uint32_t k6, uint32_t k30, const uint32_t* kd,
                                                         const uint32_t* kq, const SboxK& k) {
-        uint32_t u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k)
-                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
-        uint64_t a = mul64(u0, k2, 0), b = mul64(s[1], k2, 0);
+        uint32_t u0 = pow5c(centre_rc<centred(RC_PARTIAL_K[R]), HI_PARTIAL>(s[0]), k);
+        uint64_t a = mul64(u0, k2), b = mul64(s[1], k2);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], k2, a); b = mad64(s[i + 1], k2, b); }
         uint64_t sum2 = add64(a, b);                                          // 2S < 2^37
         const uint32_t s0 = fold2(mad64(u0, k6, sum2));                       // round R's word 0, <= P + 2^6
         const uint32_t sf = fold2(sum2);                                      // S, <= P + 2^5
-        u0 = CENTRE_RC ? pow5c(centre_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k)
-                       : pow5c(canon_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k);
+        u0 = pow5c(centre_rc<centred(RC_PARTIAL_K[R + 1]), HI_PARTIAL>(s0), k);
         // sum2 = 2S' = 2 u0' + sum_i 2 d_i s_i + 30 S < 2^50 + 2^37, two chains
-        a = mul64(u0, k2, 0); b = mul64(s[1], kd[1], 0);
+        a = mul64(u0, k2); b = mul64(s[1], kd[1]);
     #pragma unroll
         for (int i = 2; i < 16; i += 2) { a = mad64(s[i], kd[i], a); b = mad64(s[i + 1], kd[i + 1], b); }
         a = mad64(sf, k30, a);
@@ -478,22 +384,21 @@ struct PermT {
         }
     }
 
-    // The last linear layer for ONE half of the state (hi = 0: words 0..7, the rate; 1: words 8..15, the capacity): the four
+    // The last linear layer for ONE half of the state (HI false: words 0..7, the rate; true: words 8..15, the capacity): the four
     // M4 blocks and the column sums are needed either way, the per-word additions, folds and canonicalisations only for
     // the eight words asked for — every hash of the verify pipeline keeps one half of the permutation's output
     // (Poseidon2HalfVar::permute's ignore_left_result / ignore_right_result, primitives/poseidon31/src/lib.rs:251-288).
-    template <bool HI_CONST = false, bool HI_VALUE = false>
-    static __device__ __forceinline__ void poseidon2_inline_half(uint32_t* s, uint32_t hi, uint32_t* out8) {
-        if (HI_CONST) hi = HI_VALUE ? 1u : 0u;
+    template <bool HI>
+    static __device__ __forceinline__ void poseidon2_inline_half(uint32_t* s, uint32_t* out8) {
         const uint32_t k2 = opaque(2), k4 = opaque(4);
         poseidon2_rounds(s, k2, k4);
         uint64_t V[16];
     #pragma unroll
         for (int g = 0; g < 4; g++)
             mds4_2x(k2, k4, s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3], V[4 * g], V[4 * g + 1], V[4 * g + 2], V[4 * g + 3]);
-        // one column at a time (the column sum lives in two registers), the branch outside the loop: the instance must fit
-        // the 40 caller-saved registers v0..v39 like poseidon2(), or the Merkle kernels spill around every call
-        if (hi) {  // wave-uniform at every call site
+        // one column at a time (the column sum lives in two registers): the instance must fit the 40 caller-saved registers
+        // v0..v39 like poseidon2(), or the Merkle kernels spill around every call
+        if constexpr (HI) {
     #pragma unroll
             for (int j = 0; j < 4; j++) {
                 const uint64_t sum = add64(add64(V[j], V[j + 4]), add64(V[j + 8], V[j + 12]));
@@ -520,21 +425,22 @@ __device__ __forceinline__ void poseidon2_inline(uint32_t* s) { PermT<true>::pos
 __device__ unsigned long long g_perm_counter[16];
 __shared__ unsigned s_perm_tag;
 #define RSV_TAG(k) do { if (threadIdx.x == 0) s_perm_tag = (k); __syncthreads(); } while (0)
+// one wave-level call of an out-of-line instance, counted by the wave's first active lane
+__device__ __forceinline__ void count_perm_call() {
+    const unsigned long long m = __ballot(1);
+    if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(m)) {
+        atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u)], (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u) + 1], 1ull);
+    }
+}
 #else
 #define RSV_TAG(k) do { } while (0)
+__device__ __forceinline__ void count_perm_call() {}
 #endif
 
 // Out-of-line instance with the whole output state: rsv_poseidon2_permute*, the PoseidonFlow kernels.
 __device__ __noinline__ State16 poseidon2(State16 st) {
-#ifdef RSV_COUNT_PERMS
-    {
-        const unsigned long long m = __ballot(1);
-        if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(m)) {
-            atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u)], (unsigned long long)__builtin_popcountll(m));
-            atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u) + 1], 1ull);
-        }
-    }
-#endif
+    count_perm_call();
     poseidon2_inline(st.s);
     return st;
 }
@@ -578,17 +484,9 @@ __device__ __forceinline__ Hash8 zero8() {
 // lose 4.7 % at 65 536 proofs: not taken; the choice is the call site's own template argument.
 template <bool HI, bool PACE>
 __device__ __noinline__ Hash8 poseidon2_half_t(State16 st) {
-#ifdef RSV_COUNT_PERMS
-    {
-        const unsigned long long m = __ballot(1);
-        if ((threadIdx.x & 63u) == (unsigned)__builtin_ctzll(m)) {
-            atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u)], (unsigned long long)__builtin_popcountll(m));
-            atomicAdd(&g_perm_counter[2 * (s_perm_tag & 7u) + 1], 1ull);
-        }
-    }
-#endif
+    count_perm_call();
     Hash8 h;
-    PermT<PACE>::template poseidon2_inline_half<true, HI>(st.s, 0u, h.w);
+    PermT<PACE>::template poseidon2_inline_half<HI>(st.s, h.w);
     return h;
 }
 // The row form of the same call (poseidon2_row.hpp): the 16 lanes of a DPP row hold the SAME state and the same result,

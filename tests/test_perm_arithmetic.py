@@ -20,8 +20,9 @@ def _constants():
 
 
 def test_fused_round_constant_reduction():
-    """canon_rc: for a lazily folded t <= P + HI (HI < 2^19) and c = P - rc, min(t - c, t - c + P) in 32-bit wrapping
-    arithmetic is the canonical (t + rc) mod P — provided every rc < P - 2^19, which the kernel static_asserts."""
+    """The fused round-constant reduction in its v_min reference form: for a lazily folded t <= P + HI (HI < 2^19) and
+    c = P - rc, min(t - c, t - c + P) in 32-bit wrapping arithmetic is the canonical (t + rc) mod P — provided every
+    rc < P - 2^19.  (The kernel's sign-mask form of it, with its own static_asserts: tests/test_sbox_signmask.py.)"""
     rcs = _constants()
     assert len(rcs) == 142 and max(rcs) < P - (1 << 19)
     hi = (1 << 19) - 1

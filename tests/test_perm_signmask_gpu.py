@@ -2,14 +2,13 @@
 
 rsv_poseidon2_permute_dev (the paced out-of-line instance) runs 2^16 random states plus states built to put the select's
 operand a = t - c on both sides of zero: first-round a equal to -2, -1, 0, 1 and -c in all 16 words at once (the external
-matrix is inverted mod P on the CPU model of tests/test_partial_pairs.py, which also confirms each a), and every word in turn
+matrix is inverted mod P on the CPU model of tests/perm_model.py, which also confirms each a), and every word in turn
 at 0 and P - 1.  The unpaced instances are reached through a small batch's verify (at most 1 024 proofs)."""
 import numpy as np
 import pytest
 
 from tests import oracle_binding as ob
-from tests import test_partial_pairs as tpp
-from tests import test_sbox_centred as tsc
+from tests import perm_model as pm
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -40,16 +39,16 @@ def _solve(M, y):
 
 
 def _first_round_a(model, st):
-    full, _ = tpp._constants()
+    full, _ = pm.constants()
     V = model.mds16_2x(st)
-    return [model.fold2(V[i]) - (P - tsc.centred(full[0][i])) for i in range(16)]
+    return [model.fold2(V[i]) - (P - pm.centred(full[0][i])) for i in range(16)]
 
 
 def _edge_states():
-    model = tpp._model(tpp.Exact)
-    full, _ = tpp._constants()
+    model = pm.model(pm.Exact)
+    full, _ = pm.constants()
     M = _matrix(model)
-    c = [P - tsc.centred(rc) for rc in full[0]]
+    c = [P - pm.centred(rc) for rc in full[0]]
     states = []
     for k in (-2, -1, 0, 1):
         st = _solve(M, [ci + k for ci in c])

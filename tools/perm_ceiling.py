@@ -11,10 +11,10 @@ Dynamic VALU instruction mix of ONE wave-level call of rsv::poseidon2() (64 perm
              [add (2x)] + [mad(2x, x, KP), lshr, add] + [mad(s1, s1, KN), alignbit, and, add] + [mad(2x, c4, KQ), lshr, add]
       = 9 fast, 1 v_add3_u32, 1 v_xad_u32, 2 v_mad_i64_i32 a * b + SGPR pair, 1 v_mad_i64_i32 a * a + SGPR pair,
         1 v_alignbit_b32
-      (before the sign-mask entry: fold2's add, canon_rc's two literal adds and v_min, pow5c's centring subtract: 12 fast
-      and 1 v_min_u32, 3.0 cycles more than now; before the centred form: pow5 = [add, mad (SGPR pair), lshr, add] +
+      (before the sign-mask entry: fold2's add, two literal adds and a v_min, pow5c's centring subtract: 12 fast
+      and 1 v_min_u32, 3.0 cycles more than now; before the centred form: [add, mad (SGPR pair), lshr, add] +
       [v_mad_i64_i32, alignbit, and, add, add-literal, min] + [mad, lshr, add]: 12 fast, 2 min, 42.0 cycles; before the
-      signed square: 14 fast, 3 min, 3 mads without addend per pow5, 47.2 cycles)
+      signed square: 14 fast, 3 min, 3 mads without addend per S-box, 47.2 cycles)
   full-round linear layer mds16_2x (9 of them; none carries round constants: they are literals of the S-box reduction)
       per 4-word group 2 mad (no addend) + 4 mad (addend) + 2 lshl_add_u64 + 2 lshl_add_u64 (plain adds)        = 40
       column sums 12 + 16 lshl_add_u64                                                                          = 28

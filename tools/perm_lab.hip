@@ -10,6 +10,35 @@
 
 using namespace rsv;
 
+// the baseline (variant 0): the permutation as the specification states it, one canonical reduction per operation
+__device__ __forceinline__ void poseidon2_ref_inline(uint32_t* s) {
+    mds16_ref(s);
+#pragma unroll 1
+    for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) s[i] = pow5_ref(m_add(s[i], RC_FULL[r][i]));
+        mds16_ref(s);
+    }
+#pragma unroll 1
+    for (int r = 0; r < 14; r++) {
+        s[0] = pow5_ref(m_add(s[0], RC_PARTIAL[r]));
+        // sum of all 16 words as a balanced tree
+        uint32_t a0 = m_add(s[0], s[1]), a1 = m_add(s[2], s[3]), a2 = m_add(s[4], s[5]), a3 = m_add(s[6], s[7]);
+        uint32_t a4 = m_add(s[8], s[9]), a5 = m_add(s[10], s[11]), a6 = m_add(s[12], s[13]),
+                 a7 = m_add(s[14], s[15]);
+        uint32_t sum = m_add(m_add(m_add(a0, a1), m_add(a2, a3)), m_add(m_add(a4, a5), m_add(a6, a7)));
+        s[0] = m_add(sum, m_add(m_dbl(s[0]), s[0]));  // diag 3
+#pragma unroll
+        for (int i = 1; i < 16; i++) s[i] = m_add(sum, m_shl(s[i], i + 1));  // diag 2^(i+1)
+    }
+#pragma unroll 1
+    for (int r = 4; r < 8; r++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) s[i] = pow5_ref(m_add(s[i], RC_FULL[r][i]));
+        mds16_ref(s);
+    }
+}
+
 template <int VARIANT>
 __global__ __launch_bounds__(256) void k_perm(const uint4* __restrict__ in, uint4* __restrict__ out, size_t n, int reps) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

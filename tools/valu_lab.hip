@@ -95,7 +95,7 @@ DEF_KERNEL(k_cvt_f64_u32, asm volatile("v_cvt_f64_u32 %0, %1" : "=v"(w[i]) : "v"
 DEF_KERNEL(k_cvt_u32_f64, asm volatile("v_cvt_u32_f64 %0, %1" : "=v"(a[i]) : "v"(w[i])))
 DEF_KERNEL(k_min_f32, asm volatile("v_min_f32 %0, %0, %1" : "+v"(a[i]) : "v"(b)))
 DEF_KERNEL(k_lshl_or, asm volatile("v_lshl_or_b32 %0, %0, 1, %1" : "+v"(a[i]) : "v"(b)))
-// the signed S-box (PermT::pow5): the signed square without an addend, and the first product with a 64-bit SGPR-pair addend
+// reference rows for the S-box's products: a signed square without an addend, and v_mad_u64_u32 with a 64-bit SGPR-pair addend
 DEF_KERNEL(k_mad_i64, asm volatile("v_mad_i64_i32 %0, s[10:11], %1, %1, 0" : "=v"(w[i]) : "v"(a[i]) : "s10", "s11"))
 DEF_KERNEL(k_mad64_spair, asm volatile("v_mad_u64_u32 %0, s[10:11], %1, %2, s[20:21]" : "=v"(w[i]) : "v"(a[i]), "v"(b) : "s10", "s11", "s20", "s21"))
 // the centred S-box (PermT::pow5c): all three products are v_mad_i64_i32 with a signed 64-bit SGPR-pair addend
