@@ -805,6 +805,53 @@ int rsv_witness_sample_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const 
                            const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon,
                            const uint8_t* d_accept, const uint8_t* d_ok, size_t n, const uint32_t* d_oods, uint32_t* d_samples);
 
+/* ---- tree 3 of the next proof: the composition polynomial -------------------------------------------------------------
+ * With clb = max(lp + 2, lq + 3) (the verifier's composition log degree bound) and L3 = clb - 1: for a point p of
+ * CanonicCoset(clb).circle_domain(), A(p) is the accumulator of CompositionCheck::compute over the 86 constraints (6 Plonk,
+ * then 80 Poseidon): acc = acc * random_coeff + constraint / Z_l(p), Z_l(p) = pi^(l-1)(p.x) for the component's log size l,
+ * the mask values being the 126 columns' interpolants at p (the cumulative interaction columns 4..7 of each component
+ * also at p minus the step of CanonicCoset(l)) and the claimed-sum shift sum / 2^l.  The four QM31 coordinates of A on the
+ * 2^clb positions (bit-reversed) are interpolated as columns are (rsv_commit_group::d_coeffs' convention) and the
+ * coefficients cut at the middle: C = left + pi^(clb-2)(x) * right.  Tree 3 has eight columns of 2^L3 rows, stored as the
+ * trace columns are: column k is coordinate k of left, column 4 + k coordinate k of right.  The definition is exact for
+ * arbitrary columns, not only satisfying ones.
+ * rsv_composition_log_size: host arithmetic, L3 for (lp, lq); RSV_E_SIZE for sizes rsv_composition_dev refuses. */
+int rsv_composition_log_size(uint32_t lp, uint32_t lq, uint32_t* log_size);
+/* The generic call on raw device columns: the Plonk component's preprocessed [10][2^lp], trace [n][12][2^lp] and
+ * interaction [n][8][2^lp] columns, the Poseidon component's [40], [48], [8] at 2^lq, each with its proof stride in words
+ * (0: one set shared by every proof, as rsv_commit_group::proof_stride); d_sums [n][2][4] and d_draws [n][12] (z, alpha,
+ * random_coeff) as rsv_witness_commit_dev leaves them (any u32 is taken mod P); d_mask [n] (may be NULL).  Outputs: d_comp
+ * [n][8][2^L3], the form rsv_commit_tree_dev takes, and d_comp_coeffs (may be NULL) of the same shape, the columns'
+ * coefficients (left and right themselves), the form RSV_SAMPLE_COEFFS takes.  Every element is written; a masked proof
+ * gets zeros, its neighbours are unaffected.  The columns are extended to 2^clb rows by the commitment's interpolation
+ * and forward FFT, in aligned blocks of rows within RSV_OPT_WS_BUDGET_MB (fewer blocks, then fewer proofs; the
+ * accumulator's 4 x 2^clb words per proof stay in the workspace).  Refusals before any device work: a NULL pointer (but
+ * d_mask, d_comp_coeffs): RSV_E_NULL; lp or lq below 2, clb above RSV_MAX_LOG_SIZE, n above 2^20, a pointer not 4-byte
+ * aligned: RSV_E_SIZE.  Enqueued on the context's stream with no host synchronisation but the workspace's and the
+ * twiddle tables' growth. */
+int rsv_composition_dev(rsv_ctx* ctx, uint32_t lp, uint32_t lq, const uint32_t* d_plonk_pre, uint64_t plonk_pre_stride,
+                        const uint32_t* d_plonk, uint64_t plonk_stride, const uint32_t* d_int_plonk, uint64_t int_plonk_stride,
+                        const uint32_t* d_poseidon_pre, uint64_t poseidon_pre_stride, const uint32_t* d_poseidon,
+                        uint64_t poseidon_stride, const uint32_t* d_int_poseidon, uint64_t int_poseidon_stride, const uint32_t* d_sums,
+                        const uint32_t* d_draws, const uint8_t* d_mask, size_t n, uint32_t* d_comp, uint32_t* d_comp_coeffs);
+/* Tree 3 of the recursion circuit's next proof from the buffers the chain holds (leading arguments as
+ * rsv_witness_sample_dev's; the mask is d_ok, or d_accept when d_ok is NULL) and what rsv_witness_commit_dev left in
+ * d_sums, d_draws and d_channel [n][16] (read and updated):
+ *   the composition columns d_comp [n][8][2^L3], which the caller keeps for a later rsv_decommit_tree_dev;
+ *   their commitment, one group (L3, 8), as rsv_commit_tree_cap_dev: d_root3 [n][8], d_cap3 [n][2^(log_blowup + 1)][8]
+ *   (may be NULL);
+ *   per proof, mix root 3 and draw t: the OODS point ((1 - t^2) / (1 + t^2), 2 t / (1 + t^2)) to d_oods [n][8], x then y,
+ *   the form rsv_witness_sample_dev takes, and the channel after the draw to d_channel;
+ *   d_samples3 [n][8][4]: the eight columns at that point (sampled_values[3]).
+ * A proof whose mask byte is 0 gets zeros in every output; its neighbours are unaffected.  Built programs only.  Refusals
+ * as rsv_witness_sample_dev and rsv_composition_dev; L3 + log_blowup above RSV_MAX_LOG_SIZE or log_blowup outside
+ * 1 .. RSV_MAX_LOG_BLOWUP: RSV_E_SIZE. */
+int rsv_witness_tree3_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                          const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                          const uint8_t* d_ok, size_t n, uint32_t log_blowup, const uint32_t* d_sums, const uint32_t* d_draws,
+                          uint32_t* d_channel, uint32_t* d_comp, uint32_t* d_root3, uint32_t* d_cap3, uint32_t* d_oods,
+                          uint32_t* d_samples3);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

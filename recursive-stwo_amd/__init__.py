@@ -235,6 +235,9 @@ def _load() -> ctypes.CDLL:
                                                     vp, vp]),
         "rsv_sample_tree_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), sz, sz, vp, ctypes.c_int, vp, ctypes.c_uint32, vp]),
         "rsv_witness_sample_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+        "rsv_composition_log_size": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+        "rsv_composition_dev": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32] + [vp, ctypes.c_uint64] * 6 + [vp, vp, vp, sz, vp, vp]),
+        "rsv_witness_tree3_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -283,6 +286,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_commit_tree_dev", "rsv_witness_commit_dev", "rsv_witness_commit",
            "rsv_commit_tree_cap_dev", "rsv_witness_commit_caps_dev", "rsv_decommit_sizes", "rsv_decommit_tree_dev", "rsv_witness_decommit_dev",
            "rsv_sample_tree_dev", "rsv_witness_sample_dev",
+           "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -818,6 +822,13 @@ def decommit_sizes(groups, log_blowup: int, n_queries: int):
     return v.value, w.value
 
 
+def composition_log_size(lp: int, lq: int) -> int:
+    """rsv_composition_log_size: L3 = max(lp + 2, lq + 3) - 1, the log size of tree 3's eight columns.  Host arithmetic."""
+    out = ctypes.c_uint32(0)
+    _check(lib.rsv_composition_log_size(lp, lq, ctypes.byref(out)), "rsv_composition_log_size")
+    return int(out.value)
+
+
 def witness_decommit_sizes(program, log_blowup: int, n_queries: int):
     """The capacities of Context.witness_decommit's outputs: ([values_cap of tree 0, 1, 2], witness_cap)."""
     lp, lq = program.trace_sizes()
@@ -1140,6 +1151,31 @@ class Context:
         _check(lib.rsv_witness_sample_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk),
                                           ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, ptr(d_oods), ptr(d_samples)),
                "rsv_witness_sample_dev")
+
+    def composition(self, lp: int, lq: int, plonk, poseidon, d_sums, d_draws, n: int, d_comp, d_comp_coeffs=None, d_mask=None):
+        """rsv_composition_dev: plonk and poseidon are (preprocessed, trace, interaction) triples of tensors, uint32[n, cols,
+        2^log] each, or [1, cols, 2^log] / [cols, 2^log] for a set every proof shares (proof stride 0); d_sums uint32[n, 2, 4],
+        d_draws uint32[n, 12]; d_comp and d_comp_coeffs (may be None) uint32[n, 8, 2^L3]; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        cols = []
+        for t in tuple(plonk) + tuple(poseidon):
+            shared = t is None or t.dim() != 3 or (t.shape[0] == 1 and n > 1)
+            cols += [ptr(t), 0 if shared else t.shape[1] * t.shape[2]]
+        self.acquire_from_torch()
+        _check(lib.rsv_composition_dev(self._h, lp, lq, *cols, ptr(d_sums), ptr(d_draws), ptr(d_mask), n, ptr(d_comp), ptr(d_comp_coeffs)),
+               "rsv_composition_dev")
+
+    def witness_tree3(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int,
+                      log_blowup: int, d_sums, d_draws, d_channel, d_comp, d_root3, d_oods, d_samples3, d_ok=None, d_cap3=None):
+        """rsv_witness_tree3_dev on what Context.witness_commit left (d_sums, d_draws, d_channel uint32[n, 16], updated): d_comp
+        uint32[n, 8, 2^L3], d_root3 uint32[n, 8], d_cap3 uint32[n, 2^(log_blowup + 1), 8] (may be None), d_oods uint32[n, 8] as
+        Context.witness_sample takes it, d_samples3 uint32[n, 8, 4]; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_tree3_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk),
+                                         ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, log_blowup, ptr(d_sums), ptr(d_draws),
+                                         ptr(d_channel), ptr(d_comp), ptr(d_root3), ptr(d_cap3), ptr(d_oods), ptr(d_samples3)),
+               "rsv_witness_tree3_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

@@ -31,6 +31,7 @@
 #include "k_commit.hpp"
 #include "k_decommit.hpp"
 #include "k_sample.hpp"
+#include "k_composition.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -517,3 +518,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "commit_api.inc"
 #include "decommit_api.inc"
 #include "sample_api.inc"
+#include "composition_api.inc"

@@ -1,0 +1,314 @@
+"""rsv_composition_dev / rsv_witness_tree3_dev (`-m gpu`): tree 3 of the next proof, the composition polynomial.  Against
+the REFERENCE for all 14 consecutive fixture pairs (the chain of fixture K gives K+1's commitments[3], the OODS point its
+transcript draws behind that root and its sampled_values[3]), bit for bit against the numpy restatement
+(tests/composition_ref.py, pinned to the reference by tests/test_composition_host.py) on random canonical columns at the
+smallest shapes where a path changes, the coefficients output, a workspace budget that cuts rows and proofs, the largest
+words, and the refusals.  Every comparison is exact on 32-bit words and covers every element; outputs are prefilled with
+0xffffffff."""
+import numpy as np
+import pytest
+
+from tests import commit_ref as C
+from tests import composition_ref as K
+from tests import oracle_binding as ob
+from tests.conftest import fixture_cfg, read_proof
+from tests.test_commit_gpu import _program
+from tests.test_decommit_gpu import _chain_dev
+from tests.test_sample_gpu import _next_samples, _witness_sample
+from tests.test_trace_gpu import _inputs
+from tests.test_trace_host import _pins
+
+pytestmark = pytest.mark.gpu
+P = C.P
+DEV = "cuda:0"
+FILL = -1
+
+
+def _u32(t):
+    return t.cpu().numpy().view(np.uint32)
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.int64) % (1 << 32), dtype=np.uint32).view(np.int32)).to(torch.device(DEV))
+
+
+def _full(shape):
+    import torch
+    return torch.full(shape, FILL, dtype=torch.int32, device=torch.device(DEV))
+
+
+class _WithChannel:
+    """The context _chain_dev drives, with witness_commit also leaving d_channel."""
+
+    def __init__(self, ctx, chan):
+        self._ctx, self._chan = ctx, chan
+
+    def __getattr__(self, name):
+        return getattr(self._ctx, name)
+
+    def witness_commit(self, *a, **kw):
+        return self._ctx.witness_commit(*a, d_channel=self._chan, **kw)
+
+
+def _tree3(rsv, ctx, wp, batch, inputs, b, cap=False):
+    """_chain_dev, then Context.witness_tree3 -> (the chain's tensors, dict of numpy outputs)."""
+    n = len(batch)
+    chan = _full((n, 16))
+    t = _chain_dev(rsv, _WithChannel(ctx, chan), wp, batch, inputs, b, caps=False)
+    lp, lq = wp.trace_sizes()
+    L3 = rsv.composition_log_size(lp, lq)
+    out = {"comp": _full((n, 8, 1 << L3)), "root": _full((n, 8)), "oods": _full((n, 8)), "samples": _full((n, 8, 4)),
+           "cap": _full((n, 2 << b, 8)) if cap else None}
+    ctx.witness_tree3(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, b, t["sums"], t["draws"], chan, out["comp"],
+                      out["root"], out["oods"], out["samples"], d_ok=t["ok"], d_cap3=out["cap"])
+    ctx.synchronize()
+    res = {k: _u32(v) for k, v in out.items() if v is not None}
+    res["chan"] = _u32(chan)
+    t["comp"] = out["comp"]
+    return t, res
+
+
+def _want3(dst):
+    from oracle import recursion_circuit as rc
+    nxt = read_proof(dst)
+    d = rc.parse_proof(nxt)
+    tr = ob.transcript_raw(nxt)
+    root = np.array([int(x) for x in d.commitments[3]], dtype=np.uint32)
+    samples = np.array([v for col in d.sampled_values[3] for v in col], dtype=np.uint32)
+    assert samples.shape == (8, 4)
+    return root, np.array(tr[20:28], dtype=np.uint32), samples
+
+
+ROUND_TRIP = "level2-1.bin"  # the one pair whose OODS point is fed back into witness_sample (test_sample_gpu.py pins the rest)
+
+
+@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+def test_chain_gives_what_the_next_fixture_carries(rsv, pin):
+    """witness_tree3 of fixture K: K+1's commitments[3], its OODS point (transcript_raw words 20..27) and its
+    sampled_values[3]; for one pair, witness_sample fed with the returned d_oods gives K+1's other 134 values."""
+    src, dst = pin["src"], pin["dst"]
+    wp = _program(rsv, pin)
+    b = fixture_cfg(dst).log_blowup_factor
+    root, oods, samples = _want3(dst)
+    ctx = rsv.Context(0)
+    t, got = _tree3(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    assert t["ok"].cpu().tolist() == [1]
+    assert np.array_equal(got["root"][0], root)
+    assert np.array_equal(got["oods"][0], oods)
+    assert np.array_equal(got["samples"][0], samples)
+    if src == ROUND_TRIP:
+        want, _ = _next_samples(dst)
+        assert np.array_equal(_witness_sample(ctx, wp, t, 1, got["oods"])[0], want)
+    ctx.close()
+    wp.close()
+
+
+def test_batch_with_a_rejected_proof(rsv):
+    """Three proofs, the middle one tampered: zeros everywhere for it, the solo values for the other two."""
+    pin = next(p for p in _pins() if p["src"] == ROUND_TRIP)
+    src, dst = pin["src"], pin["dst"]
+    wp = _program(rsv, pin)
+    b = fixture_cfg(dst).log_blowup_factor
+    root, oods, samples = _want3(dst)
+    proof = read_proof(src)
+    ctx = rsv.Context(0)
+    t, solo = _tree3(rsv, ctx, wp, [proof], _inputs(src), b, cap=True)
+    t, got = _tree3(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], _inputs(src), b, cap=True)
+    ctx.close()
+    wp.close()
+    assert t["ok"].cpu().tolist() == [1, 0, 1]
+    for k in ("comp", "root", "oods", "samples", "cap", "chan"):
+        assert np.array_equal(got[k][0], solo[k][0]) and np.array_equal(got[k][2], solo[k][0]), k
+        assert not got[k][1].any(), k
+    assert np.array_equal(solo["root"][0], root) and np.array_equal(solo["oods"][0], oods) and np.array_equal(solo["samples"][0], samples)
+    assert np.array_equal(solo["cap"][0, 1], root) and not solo["cap"][0, 0].any()
+
+
+# ---------------------------------------------------------------- rsv_composition_dev on random columns
+def _random_inputs(rng, lp, lq, n, shared, value=None):
+    """plonk, poseidon: (preprocessed, trace, interaction) int64[n or 1, cols, 2^log]; sums [n, 2, 4], draws [n, 12]."""
+    draw = (lambda shape: rng.integers(0, P, shape)) if value is None else (lambda shape: np.full(shape, value, np.int64))
+    plonk = [draw((1 if shared else n, 10, 1 << lp)), draw((n, 12, 1 << lp)), draw((n, 8, 1 << lp))]
+    poseidon = [draw((1 if shared else n, 40, 1 << lq)), draw((n, 48, 1 << lq)), draw((n, 8, 1 << lq))]
+    return plonk, poseidon, draw((n, 2, 4)), draw((n, 12))
+
+
+def _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask=None, coeffs=True, shared=False):
+    import torch
+    L3 = rsv.composition_log_size(lp, lq)
+    d_comp = _full((n, 8, 1 << L3))
+    d_co = _full((n, 8, 1 << L3)) if coeffs else None
+    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(torch.device(DEV))
+    dp, dq = [_dev(c) for c in plonk], [_dev(c) for c in poseidon]
+    if shared:
+        dp[0], dq[0] = dp[0][0], dq[0][0]  # [cols, 2^log]: proof stride 0
+    ctx.composition(lp, lq, dp, dq, _dev(sums), _dev(draws), n, d_comp, d_co, d_mask=d_mask)
+    ctx.synchronize()
+    return _u32(d_comp), (_u32(d_co) if coeffs else None), (d_comp, d_co)
+
+
+def _ref(plonk, poseidon, lp, lq, sums, draws, p):
+    mine = lambda cols: [c[0 if c.shape[0] == 1 else p] for c in cols]  # noqa: E731
+    return K.composition(mine(plonk), mine(poseidon), lp, lq, sums[p], draws[p])
+
+
+SHAPES = [  # (lp, lq, n, mask, shared preprocessed columns)
+    (4, 3, 2, None, False),       # clb = 6 from the Plonk term
+    (3, 5, 3, [1, 0, 1], False),  # clb = 8 from the Poseidon term, Plonk over-extended by 2^5; one proof masked
+    (6, 6, 2, None, True),        # preprocessed columns shared by every proof (stride 0)
+    (11, 10, 2, None, False),     # clb = 13: just past the 4 096-point switch between the LDS and the global FFT stages
+]
+
+
+@pytest.mark.parametrize("case", range(len(SHAPES)), ids=lambda k: "lp%d_lq%d" % SHAPES[k][:2])
+def test_composition_bit_for_bit(rsv, case):
+    """Random canonical columns, sums and draws: d_comp and d_comp_coeffs equal the restatement's, d_comp_coeffs is
+    C.interpolate of d_comp, the run without d_comp_coeffs gives the same columns, a masked proof is zero."""
+    lp, lq, n, mask, shared = SHAPES[case]
+    rng = np.random.default_rng(1700 + case)
+    plonk, poseidon, sums, draws = _random_inputs(rng, lp, lq, n, shared)
+    ctx = rsv.Context(0)
+    comp, co, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask, True, shared)
+    alone, _, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask, False, shared)
+    ctx.close()
+    assert np.array_equal(alone, comp)
+    L3 = rsv.composition_log_size(lp, lq)
+    assert np.array_equal(co, C.interpolate(comp.astype(np.int64), L3))
+    for p in range(n):
+        if mask is not None and not mask[p]:
+            assert not comp[p].any() and not co[p].any(), p
+            continue
+        want, want_co = _ref(plonk, poseidon, lp, lq, sums, draws, p)
+        assert np.array_equal(co[p], want_co), (case, p)
+        assert np.array_equal(comp[p], want), (case, p)
+
+
+def test_coefficients_sample_as_the_columns(rsv):
+    """sample_tree(source=COEFFS) on d_comp_coeffs equals sample_tree on d_comp, at two points per proof."""
+    lp, lq, n = 5, 4, 2
+    rng = np.random.default_rng(1710)
+    plonk, poseidon, sums, draws = _random_inputs(rng, lp, lq, n, False)
+    ctx = rsv.Context(0)
+    _, _, (d_comp, d_co) = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n)
+    L3 = rsv.composition_log_size(lp, lq)
+    pts = _dev(rng.integers(0, P, (n, 2, 8)))
+    a, c = _full((n, 2, 8, 4)), _full((n, 2, 8, 4))
+    ctx.sample_tree([{"log_size": L3, "d_cols": d_comp, "n_cols": 8}], n, pts, 2, a, source=rsv.SAMPLE_COLUMNS)
+    ctx.sample_tree([{"log_size": L3, "d_cols": d_co, "n_cols": 8}], n, pts, 2, c, source=rsv.SAMPLE_COEFFS)
+    ctx.synchronize()
+    ctx.close()
+    assert np.array_equal(_u32(a), _u32(c)) and _u32(a).any() and not (_u32(a) == 0xFFFFFFFF).any()
+
+
+def _pass_size(lp, lq, n, shared, budget, coeffs):
+    """The driver's pass restated (composition_api.inc: co_ws_bytes and the two halving loops) -> (proofs per pass, blocks
+    of 2^(max(lp, lq) + 1) rows per pass, bytes of the whole batch uncut).  Per group the coefficients and the extended rows
+    in flight (one set for a shared group), 92 x 4 parameter words per proof, the two 1/Z tables, the accumulator (4 x 2^clb
+    per proof) and, without d_comp_coeffs, the cut coefficients; every part on a 256-byte boundary."""
+    clb = K.clb_of(lp, lq)
+    groups = [(lp, 10, shared), (lp, 12, False), (lp, 8, False), (lq, 40, shared), (lq, 48, False), (lq, 8, False)]
+
+    def ws(m, nc):
+        rows = nc << (max(lp, lq) + 1)
+        parts = []
+        for log, cols, sh in groups:
+            parts += [((1 if sh else m) * cols) << log, (1 if sh else m) * cols * rows]
+        parts += [m * 92 * 4, 1 << (clb - lp), 1 << (clb - lq), (m * 4) << clb] + ([] if coeffs else [(m * 4) << clb])
+        off = 0
+        for words in parts:
+            off = ((off + 255) & ~255) + 4 * words
+        return off
+    m, nc = n, 1 << (clb - max(lp, lq) - 1)
+    whole = ws(m, nc)
+    while ws(m, nc) > budget and nc > 1:
+        nc >>= 1
+    while ws(m, nc) > budget and m > 1:
+        m = (m + 1) // 2
+    return m, nc, whole
+
+
+def test_composition_under_a_small_workspace_budget(rsv):
+    """19 proofs of (lp, lq) = (6, 6), shared preprocessed columns, three proofs masked.  The whole batch needs 3 626 496
+    bytes in one pass of all four blocks of 128 rows; under a 1 MB budget the driver first streams one block at a time
+    (1 331 712 bytes, still too many), then halves the proofs to 10 a pass (719 360 bytes; passes of 10 + 9): both cuts
+    happen, the previous-row neighbours cross from one 64-row half of a block to the other, and the caller's buffers are
+    read at p0 = 10.  _pass_size restates the driver's arithmetic and the test asserts the figures, so it cannot go vacuous
+    if the layout changes.  Every element of the cut run equals the uncut run, and the uncut run the restatement."""
+    lp, lq, n = 6, 6, 19
+    budget = 1 << 20
+    assert _pass_size(lp, lq, n, True, budget, True) == (10, 1, 3626496)
+    assert _pass_size(lp, lq, n, True, 1331712, True)[:2] == (n, 1) and _pass_size(lp, lq, 10, True, 719360, True)[:2] == (10, 1)
+    assert _pass_size(lp, lq, n, True, 8192 << 20, True)[:2] == (n, 4)
+    rng = np.random.default_rng(1720)
+    plonk, poseidon, sums, draws = _random_inputs(rng, lp, lq, n, True)
+    mask = [0 if p in (0, 9, 18) else 1 for p in range(n)]
+    ctx = rsv.Context(0)
+    whole, whole_co, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask, True, True)
+    ctx.set_option("ws_budget_mb", 1)
+    cut, cut_co, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask, True, True)
+    ctx.close()
+    assert np.array_equal(cut, whole) and np.array_equal(cut_co, whole_co)
+    for p in range(n):
+        if not mask[p]:
+            assert not whole[p].any() and not whole_co[p].any(), p
+            continue
+        want, want_co = _ref(plonk, poseidon, lp, lq, sums, draws, p)
+        assert np.array_equal(whole[p], want) and np.array_equal(whole_co[p], want_co), p
+
+
+def test_largest_words(rsv):
+    """Every input column, sum and draw word at P - 1, the largest canonical word, equals the restatement.  What this
+    reaches: the largest operands of every m_* and q_* step of the row kernels and the largest powers' words the draws
+    allow.  What it does not: the edge of the unreduced u64 sums.  Their operands are a constraint value and a word of a
+    power of random_coeff, both results of modular arithmetic on the inputs and not under the test's control, so the sums
+    stay far from 4 (2^31 - 2)^2 + 2^34; the bound next to CoAcc covers any canonical operands."""
+    lp, lq = 4, 3
+    plonk, poseidon, sums, draws = _random_inputs(None, lp, lq, 1, False, value=P - 1)
+    ctx = rsv.Context(0)
+    comp, co, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, 1)
+    ctx.close()
+    want, want_co = _ref(plonk, poseidon, lp, lq, sums, draws, 0)
+    assert np.array_equal(comp[0], want) and np.array_equal(co[0], want_co)
+
+
+def test_device_refusals(rsv):
+    """NULL pointers, sizes and misalignment with a live context: the neighbours' codes, nothing written."""
+    import torch
+    dev = torch.device(DEV)
+    lp, lq, n = 4, 3, 1
+    ctx = rsv.Context(0)
+    z = lambda *shape: torch.zeros(shape, dtype=torch.int32, device=dev)  # noqa: E731
+    plonk, poseidon = [z(1, 10, 16), z(1, 12, 16), z(1, 8, 16)], [z(1, 40, 8), z(1, 48, 8), z(1, 8, 8)]
+    sums, draws = z(1, 2, 4), z(1, 12)
+    raw = torch.zeros(8192, dtype=torch.uint8, device=dev)
+    out = torch.full((1, 8, 32), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    co = torch.full((1, 8, 32), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+
+    def refused(code, lp=lp, lq=lq, plonk=plonk, poseidon=poseidon, sums=sums, draws=draws, n=n, d_comp=out, d_co=co):
+        with pytest.raises(rsv.RsvError) as e:
+            ctx.composition(lp, lq, plonk, poseidon, sums, draws, n, d_comp, d_co)
+        assert e.value.code == code, (code, e.value.code)
+
+    for k in range(3):
+        refused(-1, plonk=[None if i == k else t for i, t in enumerate(plonk)])
+        refused(-1, poseidon=[None if i == k else t for i, t in enumerate(poseidon)])
+    refused(-1, sums=None)
+    refused(-1, draws=None)
+    refused(-1, d_comp=None)
+    refused(-2, lp=1)
+    refused(-2, lq=1)
+    refused(-2, lp=29)
+    refused(-2, lq=28)
+    refused(-2, n=(1 << 20) + 1)
+    refused(-2, sums=raw[1:33])
+    refused(-2, draws=raw[2:50])
+    refused(-2, d_comp=raw[1:1025])
+    refused(-2, d_co=raw[2:1026])
+    refused(-2, plonk=[plonk[0], raw[1:769], plonk[2]])
+    ctx.synchronize()
+    assert bool((out == 0x5A5A5A5A).all()) and bool((co == 0x5A5A5A5A).all())
+    ctx.composition(lp, lq, plonk, poseidon, sums, draws, n, out, co)
+    ctx.synchronize()
+    assert not bool(out.any()) and not bool(co.any())  # zero columns: every constraint is zero, every word written
+    ctx.close()
