@@ -211,35 +211,42 @@ struct PermT {
         return fold2(mad64s(xx, (int32_t)c4, k.kq));
     }
 
-    // Y = 2*M4*(x0..x3) for 32-bit inputs (any u32), exact in 64 bits.
-    static __device__ __forceinline__ void mds4_2x(uint32_t k2, uint32_t k4, uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3,
-                                            uint64_t& y0, uint64_t& y1, uint64_t& y2, uint64_t& y3) {
-        uint64_t T0 = mad64(x0, k2, mul64(x1, k2));           // 2(x0 + x1)
-        uint64_t T1 = mad64(x2, k2, mul64(x3, k2));           // 2(x2 + x3)
-        uint64_t T2 = mad64(x1, k4, T1);                      // 2(2x1 + t1)
-        uint64_t T3 = mad64(x3, k4, T0);                      // 2(2x3 + t0)
-        uint64_t T4 = shl_add64<2>(T1, T3);                   // 2(4t1 + t3)
-        uint64_t T5 = shl_add64<2>(T0, T2);                   // 2(4t0 + t2)
-        y0 = add64(T3, T5);
-        y1 = T5;
-        y2 = add64(T2, T4);
-        y3 = T4;
-    }
-
-    // V[i] = 2 * (circ(2M4, M4, M4, M4) * s)[i], inputs any u32 (< 2^32): the matrix rows sum to at most 16 * 5 = 80, so
-    // every V[i] < 2 * 80 * 2^32 < 2^40.  V never carries a round constant (they are literals of the fused reductions).
-    static __device__ __forceinline__ void mds16_2x(uint32_t k2, uint32_t k4, const uint32_t* s, uint64_t* V) {
+    // ---- The external linear layer, V[i] = 2 * (circ(2M4, M4, M4, M4) * s)[i], inputs any u32 (< 2^32).  With the column
+    // sums X_j = s_j + s_{4+j} + s_{8+j} + s_{12+j}, group g of the product is M4 s_g + M4 X = M4 (s_g + X): the sums are
+    // formed FIRST and one M4 per group does the rest, on 64-bit inputs with shifts and adds alone (16 + 16 multiplies and
+    // 4 x 8 v_lshl_add_u64 for the layer; M4 per group first and the sums of its outputs afterwards is 24 + 44).  Everything
+    // is doubled from the first multiply on, and exact in 64 bits:
+    //     X2_j = 2 X_j                  < 4 * 2^33 = 2^35
+    //     z_j  = 2 s_{4g+j} + X2_j      < 10 * 2^32 < 2^36
+    //     t0, t1 < 2^37;  t2, t3 < 40 * 2^32;  t4, t5 < 120 * 2^32;  y_j < 160 * 2^32 < 2^40
+    // The matrix rows sum to at most 16 * 5 = 80, which is the bound on y: V[i] < 160 * 2^32 (HI_FULL below).  V never carries
+    // a round constant (they are literals of the fused reductions).  tests/test_mds_colsum.py proves the bounds and V equal
+    // to the sum-after-M4 form on machine words.
+    static __device__ __forceinline__ void colsums_2x(uint32_t k2, const uint32_t* s, uint64_t* X2) {
     #pragma unroll
-        for (int g = 0; g < 4; g++)
-            mds4_2x(k2, k4, s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3], V[4 * g], V[4 * g + 1], V[4 * g + 2], V[4 * g + 3]);
+        for (int j = 0; j < 4; j++) X2[j] = mul64(s[j], k2);
     #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            uint64_t sum = add64(add64(V[j], V[j + 4]), add64(V[j + 8], V[j + 12]));
+        for (int g = 1; g < 4; g++) {
     #pragma unroll
-            for (int g = 0; g < 4; g++) V[4 * g + j] = add64(V[4 * g + j], sum);
+            for (int j = 0; j < 4; j++) X2[j] = mad64(s[4 * g + j], k2, X2[j]);
         }
     }
-
+    // Y = M4 * (z0..z3) for 64-bit inputs, eight v_lshl_add_u64 (the additions, doublings and x4 of mds4_ref).
+    static __device__ __forceinline__ void mds4(uint64_t z0, uint64_t z1, uint64_t z2, uint64_t z3,
+                                                uint64_t& y0, uint64_t& y1, uint64_t& y2, uint64_t& y3) {
+        uint64_t t0 = add64(z0, z1), t1 = add64(z2, z3);
+        uint64_t t2 = shl_add64<1>(z1, t1), t3 = shl_add64<1>(z3, t0);
+        uint64_t t4 = shl_add64<2>(t1, t3), t5 = shl_add64<2>(t0, t2);
+        y0 = add64(t3, t5);
+        y1 = t5;
+        y2 = add64(t2, t4);
+        y3 = t4;
+    }
+    // one group of the layer: V[0..3] = M4 (2 x + X2) for the group's four words x.  The callers take the layer a group at a
+    // time (mds_sbox, mds_fold, poseidon2_inline_half), so the sixteen accumulators never exist at once.
+    static __device__ __forceinline__ void mds_group_2x(uint32_t k2, const uint64_t* X2, const uint32_t* x, uint64_t* V) {
+        mds4(mad64(x[0], k2, X2[0]), mad64(x[1], k2, X2[1]), mad64(x[2], k2, X2[2]), mad64(x[3], k2, X2[3]), V[0], V[1], V[2], V[3]);
+    }
     // Round constant + reduction to the centred representative in one step: the S-box's entry.  t = fold2(V) with V the
     // doubled accumulator of a linear layer WITHOUT its round constant: t <= P + HI where HI bounds the accumulator's high
     // word at the call site.  RC is the round constant moved by 2^30 (centred()), c = P - RC a compile-time literal, and
@@ -269,10 +276,35 @@ struct PermT {
         return (int32_t)((uint32_t)a + q);
     }
 
-    template <int R, int I>
+    template <int R, int I, int END = 16>
     static __device__ __forceinline__ void sbox_full(const uint64_t* V, uint32_t* s, const SboxK& k) {
         s[I] = pow5c(centre_rc<centred(RC_FULL_K[R][I]), HI_FULL>(fold2(V[I])), k);
-        if constexpr (I + 1 < 16) sbox_full<R, I + 1>(V, s, k);
+        if constexpr (I + 1 < END) sbox_full<R, I + 1, END>(V, s, k);
+    }
+    // The linear layer and the S-box layer of round R behind it, ONE GROUP AT A TIME: the column sums (8 VGPRs) are live across
+    // the layer with all sixteen input words, a group's z and M4 temporaries are about 8 more, and each of its four outputs
+    // goes straight into its fold and S-box and replaces the group's input words — the whole V (32 VGPRs) never exists, and
+    // the out-of-line instances stay within the 40 caller-saved registers.
+    template <int R>
+    static __device__ __forceinline__ void mds_sbox(uint32_t k2, uint32_t* s, const SboxK& k) {
+        uint64_t X2[4], V[16];
+        colsums_2x(k2, s, X2);
+        mds_group_2x(k2, X2, s, V);           sbox_full<R, 0, 4>(V, s, k);
+        mds_group_2x(k2, X2, s + 4, V + 4);   sbox_full<R, 4, 8>(V, s, k);
+        mds_group_2x(k2, X2, s + 8, V + 8);   sbox_full<R, 8, 12>(V, s, k);
+        mds_group_2x(k2, X2, s + 12, V + 12); sbox_full<R, 12, 16>(V, s, k);
+    }
+    // the layer alone, folded (<= P + HI_FULL): what the partial rounds take
+    static __device__ __forceinline__ void mds_fold(uint32_t k2, uint32_t* s) {
+        uint64_t X2[4];
+        colsums_2x(k2, s, X2);
+    #pragma unroll
+        for (int g = 0; g < 4; g++) {
+            uint64_t V[4];
+            mds_group_2x(k2, X2, s + 4 * g, V);
+    #pragma unroll
+            for (int j = 0; j < 4; j++) s[4 * g + j] = fold2(V[j]);
+        }
     }
     // the first full round of the second half takes its inputs already folded (from the last partial round, a single one)
     template <int I>
@@ -329,19 +361,16 @@ struct PermT {
 
     // Everything up to and including the S-box layer of the last full round: s = that layer's outputs (range L2).
     static __device__ __forceinline__ void poseidon2_rounds(uint32_t* s, uint32_t k2, uint32_t k4) {
-        uint64_t V[16];
         const uint32_t k6 = opaque(6);
         const SboxK k5 = sbox_k();
-        // s: canonical input.  V never carries a round constant: the constants are literals of the fused reductions.
-        mds16_2x(k2, k4, s, V);
-        sbox_full<0, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
-        sbox_full<1, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
-        sbox_full<2, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
-        sbox_full<3, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
+        // s: canonical input.  No accumulator carries a round constant: the constants are literals of the fused reductions.
+        mds_sbox<0>(k2, s, k5);
+        mds_sbox<1>(k2, s, k5);
+        mds_sbox<2>(k2, s, k5);
+        mds_sbox<3>(k2, s, k5);
         // partial rounds: every lane lazily folded (any u32 inside the pairs, <= P + 2^18 after a single round), lane 0 goes
         // through the S-box
-    #pragma unroll
-        for (int i = 0; i < 16; i++) s[i] = fold2(V[i]);
+        mds_fold(k2, s);
         // 2 * diag: 2^(i+2) for lanes 1..15, as opaque wave-uniform multipliers
         uint32_t kd[16];
         kd[0] = k6;
@@ -365,54 +394,41 @@ struct PermT {
         partial_pair<1>(s, k2, k6, k30, kd, kq, k5);  partial_pair<3>(s, k2, k6, k30, kd, kq, k5);  partial_pair<5>(s, k2, k6, k30, kd, kq, k5);
         partial_pair<7>(s, k2, k6, k30, kd, kq, k5);  partial_pair<9>(s, k2, k6, k30, kd, kq, k5);  partial_pair<11>(s, k2, k6, k30, kd, kq, k5);
         partial_round<13>(s, k2, k6, kd, k5);
-        sbox_full4<0>(s, k5);      mds16_2x(k2, k4, s, V);
-        sbox_full<5, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
-        sbox_full<6, 0>(V, s, k5); mds16_2x(k2, k4, s, V);
-        sbox_full<7, 0>(V, s, k5);
+        sbox_full4<0>(s, k5);
+        mds_sbox<5>(k2, s, k5);
+        mds_sbox<6>(k2, s, k5);
+        mds_sbox<7>(k2, s, k5);
     }
 
     static __device__ __forceinline__ void poseidon2_inline(uint32_t* s) {
         const uint32_t k2 = opaque(2), k4 = opaque(4);
         poseidon2_rounds(s, k2, k4);
-        uint64_t V[16];
-        mds16_2x(k2, k4, s, V);
+        mds_fold(k2, s);
         // canonical output: fold <= P + 160, so one conditional subtract lands in [0, P); P itself maps to 0
     #pragma unroll
-        for (int i = 0; i < 16; i++) {
-            uint32_t t = fold2(V[i]);
-            s[i] = min(t, t - P);
-        }
+        for (int i = 0; i < 16; i++) s[i] = min(s[i], s[i] - P);
     }
 
-    // The last linear layer for ONE half of the state (HI false: words 0..7, the rate; true: words 8..15, the capacity): the four
-    // M4 blocks and the column sums are needed either way, the per-word additions, folds and canonicalisations only for
-    // the eight words asked for — every hash of the verify pipeline keeps one half of the permutation's output
+    // The last linear layer for ONE half of the state (HI false: words 0..7, the rate; true: words 8..15, the capacity): all
+    // four column sums are needed either way, the z, the M4, the folds and the canonicalisations only for the two groups
+    // asked for — every hash of the verify pipeline keeps one half of the permutation's output
     // (Poseidon2HalfVar::permute's ignore_left_result / ignore_right_result, primitives/poseidon31/src/lib.rs:251-288).
+    // 16 + 8 multiplies and 2 x 8 v_lshl_add_u64.  The instance must fit the 40 caller-saved registers v0..v39 like
+    // poseidon2(), or the Merkle kernels spill around every call.
     template <bool HI>
     static __device__ __forceinline__ void poseidon2_inline_half(uint32_t* s, uint32_t* out8) {
         const uint32_t k2 = opaque(2), k4 = opaque(4);
         poseidon2_rounds(s, k2, k4);
-        uint64_t V[16];
+        uint64_t X2[4];
+        colsums_2x(k2, s, X2);
     #pragma unroll
-        for (int g = 0; g < 4; g++)
-            mds4_2x(k2, k4, s[4 * g], s[4 * g + 1], s[4 * g + 2], s[4 * g + 3], V[4 * g], V[4 * g + 1], V[4 * g + 2], V[4 * g + 3]);
-        // one column at a time (the column sum lives in two registers): the instance must fit the 40 caller-saved registers
-        // v0..v39 like poseidon2(), or the Merkle kernels spill around every call
-        if constexpr (HI) {
-    #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const uint64_t sum = add64(add64(V[j], V[j + 4]), add64(V[j + 8], V[j + 12]));
-                const uint32_t t0 = fold2(add64(V[8 + j], sum)), t1 = fold2(add64(V[12 + j], sum));
-                out8[j] = min(t0, t0 - P);
-                out8[4 + j] = min(t1, t1 - P);
-            }
-        } else {
+        for (int g = 0; g < 2; g++) {
+            uint64_t V[4];
+            mds_group_2x(k2, X2, s + (HI ? 8 : 0) + 4 * g, V);
     #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const uint64_t sum = add64(add64(V[j], V[j + 4]), add64(V[j + 8], V[j + 12]));
-                const uint32_t t0 = fold2(add64(V[j], sum)), t1 = fold2(add64(V[4 + j], sum));
-                out8[j] = min(t0, t0 - P);
-                out8[4 + j] = min(t1, t1 - P);
+                const uint32_t t = fold2(V[j]);
+                out8[4 * g + j] = min(t, t - P);
             }
         }
     }
