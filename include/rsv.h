@@ -852,6 +852,85 @@ int rsv_witness_tree3_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const u
                           uint32_t* d_channel, uint32_t* d_comp, uint32_t* d_root3, uint32_t* d_cap3, uint32_t* d_oods,
                           uint32_t* d_samples3);
 
+/* ---- the commit phase of FRI of the next proof: DEEP quotients, layer trees, folds, the last polynomial -------------------
+ * The definition is the verifier's (rsv_verify_batch_dev forms the same quotients and folds per query), evaluated at every
+ * position.  Sizes below are LDE log sizes: a column group of log size l gives values on
+ * CanonicCoset(l + log_blowup).circle_domain(), bit-reversed.
+ * Quotients: the groups of one log size form one QM31 quotient column, their columns in group order.  Sample k of a column
+ * (value v at the point (px, py)) has the line coefficients a = w v.b, b = w (v.a py.b - v.b py.a), c = w py.b (v = (v.a,
+ * v.b) in CM31 halves), w the running power of `after`: -2u at the column's first sample, then times `after` per sample
+ * through batch 0 (the samples at point 0, in column order), batch 1, ...  At position q with domain point (x, y):
+ *   value = sum over batches of (sum_k c_k row[col_k] - (a_k y + b_k)) / ((px.a - x) py.b - (py.a - y) px.b).
+ * Folds: pair (2k, 2k + 1) of a column of size l gives (f0 + f1) + alpha[M - l] (f0 - f1) / y, y of the pair's first point
+ * (circle to line), of a line layer of size l (f0 + f1) + alpha (f0 - f1) / x, x of half_odds(l).at(bit_reverse(2k, l)).
+ * With M the largest size: the first tree commits every column (four M31 coordinate columns each) by rsv_commit_tree_dev's
+ * mixed-size rule; the running line evaluation starts as the size-M column's fold (log size M - 1); inner layer i is the
+ * evaluation at log size M - 1 - i, committed as a four-column tree, folded under alpha[i + 1] to log size M - 2 - i, after
+ * which a column of size M - 1 - i joins: evaluation * alpha[i + 1]^2 + the column's fold under alpha[i + 1].  n_inner =
+ * M - 1 - log_last - log_blowup layers leave 2^(log_last + log_blowup) values, whose line-polynomial coefficients in
+ * degree order are cut at 2^log_last: the first 2^log_last are the last layer's polynomial, stored in the bit-reversed
+ * order rsv_line_eval reads; the rest are zero exactly when the input was of low degree.
+ * Transcript: mix the first root, draw alpha[0]; per inner layer mix its root, draw alpha[i + 1]; mix the last
+ * polynomial's coefficients two per mix (a single one at the end of an odd count).
+ *
+ * rsv_fri_sizes: host arithmetic for the recursion circuit's shape (log sizes lp, lq): sizes[3] the distinct quotient
+ * sizes descending (lde of tree 3: max(lp + 1, lq + 2) + log_blowup, then lp + log_blowup and lq + log_blowup), their
+ * number, n_inner, and the words per proof of d_quot, d_layers and d_last_poly.  RSV_E_SIZE for what rsv_witness_fri_dev
+ * refuses. */
+int rsv_fri_sizes(uint32_t lp, uint32_t lq, uint32_t log_blowup, uint32_t log_last, uint32_t* sizes, uint32_t* n_sizes, uint32_t* n_inner,
+                  size_t* quot_words, size_t* layer_words, size_t* last_words);
+/* Which points apply to a group's columns: point k (< n_points) to the columns col_lo[k] .. col_hi[k] - 1 (col_hi[k] <=
+ * col_lo[k]: to none).  Host memory. */
+typedef struct rsv_fri_group_points {
+    uint32_t col_lo[4]; /* RSV_MAX_SAMPLE_POINTS */
+    uint32_t col_hi[4];
+} rsv_fri_group_points;
+/* The quotient columns of column groups (rsv_commit_group: log_size, n_cols, d_cols, proof_stride; d_coeffs and d_lde are
+ * not used), 1 <= log_size, log_size + log_blowup <= RSV_MAX_LOG_SIZE.
+ *   source        as rsv_sample_tree_dev: RSV_SAMPLE_COLUMNS (d_cols holds evaluations) or RSV_SAMPLE_COEFFS (canonical
+ *                 coefficients, as a commitment's d_coeffs).
+ *   d_points      [n][n_points][8]: x then y; any u32 is taken mod P.  Batches are taken in ascending point index.
+ *   d_samples     [n][n_points][sum n_cols][4], the layout rsv_sample_tree_dev writes for these groups and points; only
+ *                 the values group_points selects are read.
+ *   d_after       [n][4]: the random coefficient.
+ *   d_quot        per proof the columns in descending size, each [4][2^(log_size + log_blowup)] coordinate-major, the form
+ *                 a column group has.  Every element is written; zeros for a masked proof (d_mask [n], may be NULL).
+ * The extended rows never exist whole: each column's groups are interpolated and extended block by block within
+ * RSV_OPT_WS_BUDGET_MB (fewer blocks, then fewer proofs).  Refusals before any device work: a NULL pointer (but d_mask):
+ * RSV_E_NULL; n_groups, n_points, log_blowup, sizes, col_hi above n_cols, n above 2^20, an unknown source, a pointer not
+ * 4-byte aligned: RSV_E_SIZE.  Enqueued on the context's stream with no host synchronisation but the workspace's and the
+ * twiddle tables' growth. */
+int rsv_fri_quotients_dev(rsv_ctx* ctx, const rsv_commit_group* groups, const rsv_fri_group_points* group_points, size_t n_groups, size_t n,
+                          uint32_t log_blowup, const uint8_t* d_mask, int source, const uint32_t* d_points, uint32_t n_points,
+                          const uint32_t* d_samples, const uint32_t* d_after, uint32_t* d_quot);
+/* The layers of d_quot (sizes [n_sizes], HOST: the columns' LDE log sizes, strictly descending): d_channel [n][16] read
+ * and updated (the state after the last mix is what the proof-of-work stage continues from); d_roots [n][1 + n_inner][8];
+ * d_alphas [n][1 + n_inner][4]; d_layers per proof the inner layers' evaluations one after another, layer i
+ * [4][2^(M - 1 - i)] (may be NULL when n_inner is 0); d_last_poly [n][2^log_last][4]; d_low_degree [n] bytes: 1 iff every
+ * coefficient past 2^log_last is zero.  A masked proof gets zeros in every output and a zeroed channel.  Proofs in passes
+ * within RSV_OPT_WS_BUDGET_MB.  Refusals before any device work: a NULL pointer (but d_mask): RSV_E_NULL; n_sizes 0 or
+ * above RSV_MAX_COMMIT_GROUPS, sizes not descending or above RSV_MAX_LOG_SIZE, a column of log size (size - log_blowup)
+ * <= log_last, log_last > RSV_MAX_LOG_LAST_LAYER, n_inner > RSV_MAX_FRI_INNER, log_blowup outside 1 .. RSV_MAX_LOG_BLOWUP,
+ * n above 2^20, a pointer not 4-byte aligned: RSV_E_SIZE. */
+int rsv_fri_commit_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last,
+                       size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                       uint32_t* d_last_poly, uint8_t* d_low_degree);
+/* The commit phase of FRI of the recursion circuit's next proof from the buffers the chain holds (leading arguments as
+ * rsv_witness_tree3_dev's; the mask is d_ok, or d_accept when d_ok is NULL): d_comp, d_oods and d_samples3 [n][8][4] as
+ * rsv_witness_tree3_dev left them, d_samples [n][134][4] as rsv_witness_sample_dev, d_channel [n][16] (read and updated).
+ * Per proof: mix the 142 sampled values two per mix, draw `after` (to d_after [n][4]); the quotient columns d_quot (sizes
+ * and words: rsv_fri_sizes) from tree 3's columns at the OODS point, and per tree 0, 1, 2 the Plonk and the Poseidon
+ * columns at the OODS point and then the cumulative interaction columns 4..7 at the previous-row points (formed on the
+ * device); then rsv_fri_commit_dev's outputs.  d_quot and d_layers stay with the caller for the openings.  A masked proof
+ * gets zeros in every output and a zeroed channel.  Built programs only.  Refusals as rsv_witness_tree3_dev and
+ * rsv_fri_commit_dev. */
+int rsv_witness_fri_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                        const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                        const uint8_t* d_ok, size_t n, uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp,
+                        const uint32_t* d_oods, const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel,
+                        uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                        uint32_t* d_last_poly, uint8_t* d_low_degree);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

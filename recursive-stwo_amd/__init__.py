@@ -135,6 +135,10 @@ class CommitGroup(ctypes.Structure):  # rsv_commit_group
                 ("d_coeffs", ctypes.c_void_p), ("d_lde", ctypes.c_void_p)]
 
 
+class FriGroupPoints(ctypes.Structure):  # rsv_fri_group_points
+    _fields_ = [("col_lo", ctypes.c_uint32 * 4), ("col_hi", ctypes.c_uint32 * 4)]
+
+
 class Shard(ctypes.Structure):  # rsv_shard
     _fields_ = [("d_blob", ctypes.c_void_p), ("d_offsets", ctypes.c_void_p), ("n", ctypes.c_size_t), ("d_cfg_of", ctypes.c_void_p),
                 ("d_accept", ctypes.c_void_p), ("d_reason", ctypes.c_void_p)]
@@ -238,6 +242,11 @@ def _load() -> ctypes.CDLL:
         "rsv_composition_log_size": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
         "rsv_composition_dev": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint32] + [vp, ctypes.c_uint64] * 6 + [vp, vp, vp, sz, vp, vp]),
         "rsv_witness_tree3_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rsv_fri_sizes": (ctypes.c_int, [ctypes.c_uint32] * 4 + [_u32p, _u32p, _u32p, ctypes.POINTER(sz), ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "rsv_fri_quotients_dev": (ctypes.c_int, [vp, ctypes.POINTER(CommitGroup), ctypes.POINTER(FriGroupPoints), sz, sz, ctypes.c_uint32, vp,
+                                                 ctypes.c_int, vp, ctypes.c_uint32, vp, vp, vp]),
+        "rsv_fri_commit_dev": (ctypes.c_int, [vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp]),
+        "rsv_witness_fri_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -287,6 +296,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_commit_tree_cap_dev", "rsv_witness_commit_caps_dev", "rsv_decommit_sizes", "rsv_decommit_tree_dev", "rsv_witness_decommit_dev",
            "rsv_sample_tree_dev", "rsv_witness_sample_dev",
            "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
+           "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -829,6 +839,18 @@ def composition_log_size(lp: int, lq: int) -> int:
     return int(out.value)
 
 
+def fri_sizes(lp: int, lq: int, log_blowup: int, log_last: int) -> dict:
+    """rsv_fri_sizes: {"sizes": the quotient columns' LDE log sizes, descending, "n_inner", "quot_words", "layer_words",
+    "last_words": words per proof of d_quot, d_layers, d_last_poly} for the recursion circuit's shape.  Host arithmetic."""
+    sizes = np.zeros(3, np.uint32)
+    ns, ni = np.zeros(1, np.uint32), np.zeros(1, np.uint32)
+    q, lw, last = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    as_p = lambda a: a.ctypes.data_as(_u32p)  # noqa: E731
+    _check(lib.rsv_fri_sizes(lp, lq, log_blowup, log_last, as_p(sizes), as_p(ns), as_p(ni), ctypes.byref(q), ctypes.byref(lw), ctypes.byref(last)), "rsv_fri_sizes")
+    return {"sizes": [int(v) for v in sizes[:int(ns[0])]], "n_inner": int(ni[0]), "quot_words": q.value, "layer_words": lw.value,
+            "last_words": last.value}
+
+
 def witness_decommit_sizes(program, log_blowup: int, n_queries: int):
     """The capacities of Context.witness_decommit's outputs: ([values_cap of tree 0, 1, 2], witness_cap)."""
     lp, lq = program.trace_sizes()
@@ -1176,6 +1198,48 @@ class Context:
                                          ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n, log_blowup, ptr(d_sums), ptr(d_draws),
                                          ptr(d_channel), ptr(d_comp), ptr(d_root3), ptr(d_cap3), ptr(d_oods), ptr(d_samples3)),
                "rsv_witness_tree3_dev")
+
+    def fri_quotients(self, groups, group_points, n: int, log_blowup: int, d_points, n_points: int, d_samples, d_after, d_quot, d_mask=None,
+                      source: int = SAMPLE_COLUMNS):
+        """rsv_fri_quotients_dev: groups as commit_groups() takes them; group_points per group a list over the points of
+        (col_lo, col_hi) pairs, or None where a point applies to none of the group's columns; d_points uint32[n, n_points, 8],
+        d_samples uint32[n, n_points, sum n_cols, 4] as Context.sample_tree writes them, d_after uint32[n, 4]; d_quot per proof
+        the quotient columns in descending size, each uint32[4, 2^(log_size + log_blowup)]; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        arr = commit_groups(groups)
+        gp = (FriGroupPoints * max(len(groups), 1))()
+        for i, pts in enumerate(group_points):
+            for k, r in enumerate(pts):
+                if r is not None:
+                    gp[i].col_lo[k], gp[i].col_hi[k] = r
+        self.acquire_from_torch()
+        _check(lib.rsv_fri_quotients_dev(self._h, arr, gp, len(groups), n, log_blowup, ptr(d_mask), source, ptr(d_points), n_points,
+                                         ptr(d_samples), ptr(d_after), ptr(d_quot)), "rsv_fri_quotients_dev")
+
+    def fri_commit(self, d_quot, sizes, log_blowup: int, log_last: int, n: int, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                   d_low_degree, d_mask=None):
+        """rsv_fri_commit_dev: d_quot as Context.fri_quotients wrote it, sizes its columns' LDE log sizes (descending);
+        d_channel uint32[n, 16] (updated), d_roots uint32[n, 1 + n_inner, 8], d_alphas uint32[n, 1 + n_inner, 4], d_layers the
+        inner layers per proof (may be None when there is none), d_last_poly uint32[n, 2^log_last, 4], d_low_degree uint8[n];
+        enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        sz = _u32(list(sizes))
+        self.acquire_from_torch()
+        _check(lib.rsv_fri_commit_dev(self._h, ptr(d_quot), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask), ptr(d_channel), ptr(d_roots),
+                                      ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree)), "rsv_fri_commit_dev")
+
+    def witness_fri(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int,
+                    log_blowup: int, log_last: int, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas,
+                    d_layers, d_last_poly, d_low_degree, d_ok=None):
+        """rsv_witness_fri_dev on what Context.witness_tree3 and Context.witness_sample left (d_comp, d_oods, d_samples3,
+        d_samples uint32[n, 134, 4], d_channel uint32[n, 16], updated): d_after uint32[n, 4], d_quot uint32[n, quot_words],
+        d_layers uint32[n, layer_words] (fri_sizes), and the outputs of Context.fri_commit; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_fri_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk), ptr(d_int_poseidon),
+                                       ptr(d_accept), ptr(d_ok), n, log_blowup, log_last, ptr(d_comp), ptr(d_oods), ptr(d_samples),
+                                       ptr(d_samples3), ptr(d_channel), ptr(d_after), ptr(d_quot), ptr(d_roots), ptr(d_alphas), ptr(d_layers),
+                                       ptr(d_last_poly), ptr(d_low_degree)), "rsv_witness_fri_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

@@ -1,0 +1,458 @@
+// fri_api.inc — rsv_fri_sizes, rsv_fri_quotients_dev (the DEEP quotient columns over their whole domains),
+// rsv_fri_commit_dev (the FRI layers' trees, the transcript between them, the folds, the last layer's polynomial) and
+// rsv_witness_fri_dev (both from the chain's buffers): k_fri.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after
+// composition_api.inc.
+//
+// Quotients: one quotient column (one LDE log size) at a time; its groups are interpolated (from evaluations) and
+// extended block by block as commit_tree does, and k_fr_rows consumes each pass of blocks.  Commit: the per-layer form,
+// one launch per tree level, one channel launch and one or two fold launches per layer; there is no single-workgroup tail
+// kernel for the small layers.
+
+namespace {
+
+constexpr size_t FR_MAX_SIZES = RSV_MAX_COMMIT_GROUPS;
+
+// What the points and samples of one group are (rsv::FrGroup's host half).
+struct FrSpec {
+    const uint32_t* samples;
+    uint64_t sstride;
+    uint32_t lo[rsv::FR_MAX_POINTS], hi[rsv::FR_MAX_POINTS], entry[rsv::FR_MAX_POINTS], step[rsv::FR_MAX_POINTS];
+};
+
+// The distinct log sizes of the groups, descending -> their number.
+size_t fr_sizes_of(const rsv_commit_group* g, size_t ng, uint32_t* sizes) {
+    size_t ns = 0;
+    for (size_t i = 0; i < ng; i++) {
+        bool seen = false;
+        for (size_t k = 0; k < ns; k++) seen |= sizes[k] == g[i].log_size;
+        if (!seen) sizes[ns++] = g[i].log_size;
+    }
+    std::sort(sizes, sizes + ns, [](uint32_t a, uint32_t b) { return a > b; });
+    return ns;
+}
+
+struct FrWs {
+    uint32_t *coef[rsv::FR_MAX_GROUPS], *ext[rsv::FR_MAX_GROUPS], *par;
+};
+// Workspace of a pass of P proofs and nb blocks of one quotient column (the groups of log size ls): per group the
+// coefficients (from evaluations only) and the extended blocks in flight (one set for a shared group), then the
+// constants.
+size_t fr_ws_bytes(const rsv_commit_group* g, size_t ng, uint32_t ls, bool interpolate, size_t P, size_t nb, uint32_t par_words, char* base,
+                   FrWs* w) {
+    rsv::host::Carve sz{base};
+    FrWs t{};
+    for (size_t i = 0; i < ng; i++) {
+        if (g[i].log_size != ls) continue;
+        const size_t np = g[i].proof_stride ? P : 1;
+        t.coef[i] = interpolate ? sz.take<uint32_t>(np * g[i].n_cols << ls) : nullptr;
+        t.ext[i] = sz.take<uint32_t>((np * g[i].n_cols * nb) << ls);
+    }
+    t.par = sz.take<uint32_t>(P * par_words);
+    if (w) *w = t;
+    return sz.off;
+}
+
+// g / fs: ng <= FR_MAX_GROUPS groups; d_quot: per proof (stride the sum of 4 << (size + b)) the columns in descending size.
+int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_t ng, size_t n, uint32_t b, const uint8_t* d_mask, int source,
+                  const uint32_t* d_points, uint32_t n_points, const uint32_t* d_after, uint32_t* d_quot) {
+    uint32_t sizes[rsv::FR_MAX_GROUPS];
+    const size_t ns = fr_sizes_of(g, ng, sizes);
+    uint64_t qstride = 0;
+    for (size_t s = 0; s < ns; s++) qstride += (uint64_t)4 << (sizes[s] + b);
+    if (n == 0) return RSV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool interpolate = source == RSV_SAMPLE_COLUMNS;
+    const size_t budget = ws_budget(c);
+    const uint64_t lim = (uint64_t)1 << 31;
+    hipStream_t st = c->stream;
+    uint64_t col_off = 0;
+    for (size_t s = 0; s < ns; s++) {
+        const uint32_t ls = sizes[s], N = ls + b;
+        uint32_t terms = 0;
+        for (size_t i = 0; i < ng; i++)
+            if (g[i].log_size == ls)
+                for (uint32_t k = 0; k < n_points; k++) terms += fs[i].hi[k] > fs[i].lo[k] ? fs[i].hi[k] - fs[i].lo[k] : 0;
+        const uint32_t par_words = rsv::FR_TERMS_AT + 4 * terms;
+        // the largest pass within the budget: all blocks of all proofs, then fewer blocks, then fewer proofs
+        size_t P = n, nb = (size_t)1 << b;
+        while (fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr) > budget && nb > 1) nb >>= 1;
+        while (fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
+        // every launch's grid stays below 2^31 workgroups
+        for (size_t i = 0; i < ng; i++) {
+            if (g[i].log_size != ls) continue;
+            const uint64_t rows = (uint64_t)P * g[i].n_cols * nb;
+            if (rows >= lim || (rows << ls) / 256 >= lim) return RSV_E_SIZE;
+        }
+        const size_t R = nb << ls;
+        if ((uint64_t)P * std::max<size_t>(R / 256, 1) >= lim) return RSV_E_SIZE;
+        uint32_t rlog = 0;
+        while (((size_t)1 << rlog) < R) rlog++;
+        const uint32_t *tw_inv = nullptr, *tw_fwd;
+        int rc = cm_twiddles(c, N, false, &tw_fwd);
+        if (rc == RSV_OK && interpolate) rc = cm_twiddles(c, ls, true, &tw_inv);
+        if (rc == RSV_OK) rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr));
+        if (rc != RSV_OK) return rc;
+        FrWs w;
+        fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, static_cast<char*>(c->ws_commit), &w);
+        for (size_t p0 = 0; p0 < n; p0 += P) {
+            const size_t Pc = std::min(P, n - p0);
+            rsv::FrRows a{};
+            rsv::FrCol& col = a.col;
+            const uint32_t* cf[rsv::FR_MAX_GROUPS];
+            uint64_t cf_stride[rsv::FR_MAX_GROUPS];
+            size_t at[rsv::FR_MAX_GROUPS];
+            for (size_t i = 0; i < ng; i++) {
+                if (g[i].log_size != ls) continue;
+                const uint32_t cols = g[i].n_cols;
+                const size_t row = (size_t)1 << ls;
+                const bool shared = g[i].proof_stride == 0;
+                at[col.ng] = i;
+                rsv::FrGroup& k = col.g[col.ng++];
+                k.ext = w.ext[i];
+                k.pstride = shared ? 0 : (uint64_t)cols * R;
+                k.samples = fs[i].samples;
+                k.sstride = fs[i].sstride;
+                k.n_cols = cols;
+                for (uint32_t q = 0; q < rsv::FR_MAX_POINTS; q++) {
+                    const bool on = q < n_points && fs[i].hi[q] > fs[i].lo[q];
+                    k.lo[q] = on ? fs[i].lo[q] : 0;
+                    k.hi[q] = on ? fs[i].hi[q] : 0;
+                    k.entry[q] = fs[i].entry[q];
+                    k.step[q] = fs[i].step[q];
+                }
+                if (!interpolate) {
+                    cf[i] = g[i].d_cols + p0 * g[i].proof_stride;
+                    cf_stride[i] = g[i].proof_stride;
+                    continue;
+                }
+                cf[i] = w.coef[i];
+                cf_stride[i] = shared ? 0 : (uint64_t)cols * row;
+                if (shared && p0) continue;
+                // the commitment's interpolation: the columns -> the coefficients; a shared group once, masked proofs zero
+                rsv::CmRows r{w.coef[i], row, (uint64_t)(shared ? 1 : Pc) * cols, ls, ls, 1, 0};
+                rsv::CmSrc src{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, shared ? nullptr : d_mask, cols, (uint32_t)p0,
+                               1u << (31 - ls)};
+                cm_fft<true>(st, r, src, tw_inv);
+            }
+            col.np = n_points;
+            col.par_words = par_words;
+            col.p0 = (uint32_t)p0;
+            col.mask = d_mask;
+            col.par = w.par;
+            hipLaunchKernelGGL(rsv::k_fr_consts, dim3(grid_for(Pc, 64)), dim3(64), 0, st, col, d_points, d_after, (uint32_t)Pc);
+            a.rlog = rlog;
+            a.N = N;
+            a.tw = tw_fwd;
+            a.quot = d_quot + p0 * qstride + col_off;
+            a.qstride = qstride;
+            for (size_t blk0 = 0; blk0 < ((size_t)1 << b); blk0 += nb) {
+                // the LDE of blocks blk0 .. blk0 + nb - 1 of every group of this size
+                for (uint32_t k = 0; k < col.ng; k++) {
+                    const size_t i = at[k];
+                    const uint32_t cols = g[i].n_cols;
+                    const size_t np = g[i].proof_stride ? Pc : 1;
+                    rsv::CmRows r{w.ext[i], (uint64_t)nb << ls, (uint64_t)np * cols * nb, ls, N, (uint32_t)nb, (uint32_t)blk0};
+                    rsv::CmSrc src{cf[i], cf_stride[i], (uint64_t)1 << ls, nullptr, cols, 0, 1};
+                    cm_fft<false>(st, r, src, tw_fwd);
+                }
+                a.row0 = (uint64_t)blk0 << ls;
+                hipLaunchKernelGGL(rsv::k_fr_rows, dim3((unsigned)(Pc * std::max<size_t>(R / 256, 1))), dim3(256), 0, st, a);
+            }
+        }
+        col_off += (uint64_t)4 << N;
+    }
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+int fr_check_commit(const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n) {
+    if (ns == 0 || ns > FR_MAX_SIZES || b < 1 || b > RSV_MAX_LOG_BLOWUP || n > (1u << 20)) return RSV_E_SIZE;
+    if (log_last > RSV_MAX_LOG_LAST_LAYER) return RSV_E_SIZE;
+    for (size_t s = 0; s < ns; s++) {
+        if (sizes[s] > RSV_MAX_LOG_SIZE || sizes[s] < b + 1 || (s && sizes[s] >= sizes[s - 1])) return RSV_E_SIZE;
+        if (sizes[s] - b <= log_last) return RSV_E_SIZE;  // every column is larger than the last layer
+    }
+    if (sizes[0] - 1 - log_last - b > RSV_MAX_FRI_INNER) return RSV_E_SIZE;
+    return RSV_OK;
+}
+
+struct FrCommitWs {
+    uint32_t *na, *nb, *root, *last;
+};
+size_t fr_commit_ws_bytes(uint32_t M, uint32_t L, size_t P, char* base, FrCommitWs* w) {
+    rsv::host::Carve sz{base};
+    FrCommitWs t{};
+    t.na = sz.take<uint32_t>((P * 8) << M);
+    t.nb = sz.take<uint32_t>((P * 8) << (M - 1));
+    t.root = sz.take<uint32_t>(P * 8);
+    t.last = sz.take<uint32_t>((P * 4) << L);
+    if (w) *w = t;
+    return sz.off;
+}
+
+int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n,
+               const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly,
+               uint8_t* d_low_degree) {
+    if (n == 0) return RSV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L;
+    uint64_t qstride = 0, col_at[FR_MAX_SIZES], lstride = 0;
+    for (size_t s = 0; s < ns; s++) {
+        col_at[s] = qstride;
+        qstride += (uint64_t)4 << sizes[s];
+    }
+    for (uint32_t i = 0; i < n_inner; i++) lstride += (uint64_t)4 << (M - 1 - i);
+    const size_t budget = ws_budget(c);
+    size_t P = n;
+    while (fr_commit_ws_bytes(M, L, P, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
+    if (((uint64_t)P << M) / 256 >= ((uint64_t)1 << 31)) return RSV_E_SIZE;
+    // 1 / y of every column's pairs, 1 / x of every inner layer's and of the last layer's interpolation
+    const uint32_t *inv_y[FR_MAX_SIZES], *inv_x[RSV_MAX_LOG_SIZE + 2] = {};
+    int rc = RSV_OK;
+    for (size_t s = 0; s < ns && rc == RSV_OK; s++) rc = cm_twiddles(c, sizes[s], true, &inv_y[s]);
+    for (uint32_t l = L; l < M && rc == RSV_OK; l++) rc = cm_twiddles(c, l + 1, true, &inv_x[l]);  // the line domain 2^l
+    if (rc == RSV_OK) rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, fr_commit_ws_bytes(M, L, P, nullptr, nullptr));
+    if (rc != RSV_OK) return rc;
+    FrCommitWs w;
+    fr_commit_ws_bytes(M, L, P, static_cast<char*>(c->ws_commit), &w);
+    hipStream_t st = c->stream;
+    const uint64_t rstride = (uint64_t)(1 + n_inner) * 8, astride = (uint64_t)(1 + n_inner) * 4;
+    auto column_of = [&](uint32_t l) -> int {
+        for (size_t s = 0; s < ns; s++)
+            if (sizes[s] == l) return (int)s;
+        return -1;
+    };
+    for (size_t p0 = 0; p0 < n; p0 += P) {
+        const uint32_t Pc = (uint32_t)std::min(P, n - p0);
+        const uint8_t* mask = d_mask ? d_mask + p0 : nullptr;
+        const uint32_t* quot = d_quot + p0 * qstride;
+        uint32_t* chan = d_channel + p0 * 16;
+        uint32_t* roots = d_roots + p0 * rstride;
+        uint32_t* alphas = d_alphas + p0 * astride;
+        uint32_t* layers = d_layers ? d_layers + p0 * lstride : nullptr;
+        // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root
+        auto tree = [&](uint32_t top, auto data_at) {
+            const uint32_t* child = nullptr;
+            for (uint32_t l = top + 1; l-- > 0;) {
+                uint64_t dstride = 0;
+                const uint32_t* data = data_at(l, &dstride);
+                uint32_t* out = l == 0 ? w.root : ((top - l) & 1 ? w.nb : w.na);
+                hipLaunchKernelGGL(rsv::k_fr_hash_layer, dim3(grid_for((size_t)Pc << l, 256)), dim3(256), 0, st, data, dstride, l, Pc, child, out);
+                child = out;
+            }
+        };
+        auto draw = [&](uint32_t idx) {
+            hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
+                               alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
+        };
+        // where the running evaluation of log size l lives: inner layer M - 1 - l, or the last evaluation
+        auto eval_at = [&](uint32_t l) -> rsv::FrVec {
+            if (l == L) return {w.last, (uint64_t)4 << L};
+            uint64_t off = 0;
+            for (uint32_t i = 0; i < M - 1 - l; i++) off += (uint64_t)4 << (M - 1 - i);
+            return {layers + off, lstride};
+        };
+        // the first layer: every quotient column at its own level
+        tree(M, [&](uint32_t l, uint64_t* stride) -> const uint32_t* {
+            const int s = column_of(l);
+            *stride = qstride;
+            return s < 0 ? nullptr : quot + col_at[s];
+        });
+        draw(0);
+        {
+            const rsv::FrVec src{const_cast<uint32_t*>(quot), qstride};
+            hipLaunchKernelGGL(rsv::k_fr_fold<false>, dim3(grid_for((size_t)Pc << (M - 1), 256)), dim3(256), 0, st, src, eval_at(M - 1), M, Pc,
+                               inv_y[0] + rsv::cm_tw_off(M, 0), alphas, astride, mask);
+        }
+        for (uint32_t i = 0; i < n_inner; i++) {
+            const uint32_t l = M - 1 - i;
+            const rsv::FrVec cur = eval_at(l), next = eval_at(l - 1);
+            tree(l, [&](uint32_t lv, uint64_t* stride) -> const uint32_t* {
+                *stride = cur.stride;
+                return lv == l ? cur.base : nullptr;
+            });
+            draw(i + 1);
+            const dim3 grid(grid_for((size_t)Pc << (l - 1), 256));
+            hipLaunchKernelGGL(rsv::k_fr_fold<false>, grid, dim3(256), 0, st, cur, next, l, Pc, inv_x[l] + rsv::cm_tw_off(l + 1, 1), alphas + (i + 1) * 4,
+                               astride, mask);
+            const int s = column_of(l);
+            if (s >= 0) {
+                const rsv::FrVec src{const_cast<uint32_t*>(quot) + col_at[s], qstride};
+                hipLaunchKernelGGL(rsv::k_fr_fold<true>, grid, dim3(256), 0, st, src, next, l, Pc, inv_y[s] + rsv::cm_tw_off(l, 0), alphas + (i + 1) * 4,
+                                   astride, mask);
+            }
+        }
+        // the last layer: the evaluation's coefficients, the first 2^log_last out, the rest checked, the final mixes
+        for (uint32_t m = 0; m < L; m++)
+            hipLaunchKernelGGL(rsv::k_fr_line_layer, dim3(grid_for(((size_t)Pc * 4) << (L - 1), 256)), dim3(256), 0, st, w.last, L, m, Pc,
+                               inv_x[L] + rsv::cm_tw_off(L + 1, m + 1));
+        hipLaunchKernelGGL(rsv::k_fr_last, dim3(grid_for((size_t)Pc << L, 256)), dim3(256), 0, st, w.last, L, log_last, Pc, mask,
+                           d_last_poly + ((p0 * 4) << log_last), d_low_degree + p0);
+        hipLaunchKernelGGL(rsv::k_fr_mix_last, dim3(grid_for(Pc, 64)), dim3(64), 0, st, d_last_poly + ((p0 * 4) << log_last), log_last, mask, Pc,
+                           chan);
+    }
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+int fr_check_chain(uint32_t lp, uint32_t lq, uint32_t b, uint32_t log_last, size_t n, uint32_t* sizes, size_t* ns) {
+    int rc = co_check_sizes(lp, lq, n);
+    if (rc != RSV_OK) return rc;
+    if (b < 1 || b > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
+    const uint32_t M = co_clb(lp, lq) - 1 + b, A = lp + b, B = lq + b;
+    if (M > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
+    size_t k = 0;
+    sizes[k++] = M;
+    sizes[k++] = std::max(A, B);
+    if (A != B) sizes[k++] = std::min(A, B);
+    *ns = k;
+    return fr_check_commit(sizes, k, b, log_last, n);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsv_fri_sizes(uint32_t lp, uint32_t lq, uint32_t log_blowup, uint32_t log_last, uint32_t* sizes, uint32_t* n_sizes, uint32_t* n_inner,
+                  size_t* quot_words, size_t* layer_words, size_t* last_words) {
+    if (!sizes || !n_sizes || !n_inner || !quot_words || !layer_words || !last_words) return RSV_E_NULL;
+    uint32_t sz[3];
+    size_t ns = 0;
+    const int rc = fr_check_chain(lp, lq, log_blowup, log_last, 0, sz, &ns);
+    if (rc != RSV_OK) return rc;
+    size_t q = 0, lw = 0;
+    for (size_t s = 0; s < ns; s++) {
+        sizes[s] = sz[s];
+        q += (size_t)4 << sz[s];
+    }
+    const uint32_t ni = sz[0] - 1 - log_last - log_blowup;
+    for (uint32_t i = 0; i < ni; i++) lw += (size_t)4 << (sz[0] - 1 - i);
+    *n_sizes = (uint32_t)ns;
+    *n_inner = ni;
+    *quot_words = q;
+    *layer_words = lw;
+    *last_words = (size_t)4 << log_last;
+    return RSV_OK;
+}
+
+int rsv_fri_quotients_dev(rsv_ctx* c, const rsv_commit_group* groups, const rsv_fri_group_points* group_points, size_t n_groups, size_t n,
+                          uint32_t log_blowup, const uint8_t* d_mask, int source, const uint32_t* d_points, uint32_t n_points,
+                          const uint32_t* d_samples, const uint32_t* d_after, uint32_t* d_quot) {
+    if (!c || !groups || !group_points || !d_points || !d_samples || !d_after || !d_quot) return RSV_E_NULL;
+    if (n_points < 1 || n_points > RSV_MAX_SAMPLE_POINTS || n_groups == 0 || n_groups > RSV_MAX_COMMIT_GROUPS || n > (1u << 20)) return RSV_E_SIZE;
+    if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
+    if (source != RSV_SAMPLE_COLUMNS && source != RSV_SAMPLE_COEFFS) return RSV_E_SIZE;
+    if (((uintptr_t)d_points & 3) || ((uintptr_t)d_samples & 3) || ((uintptr_t)d_after & 3) || ((uintptr_t)d_quot & 3)) return RSV_E_SIZE;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_groups; i++) {
+        if (!groups[i].d_cols) return RSV_E_NULL;
+        if (groups[i].n_cols == 0 || groups[i].log_size < 1 || groups[i].log_size + log_blowup > RSV_MAX_LOG_SIZE || ((uintptr_t)groups[i].d_cols & 3))
+            return RSV_E_SIZE;
+        for (uint32_t k = 0; k < n_points; k++)
+            if (group_points[i].col_hi[k] > groups[i].n_cols) return RSV_E_SIZE;
+        total += groups[i].n_cols;
+    }
+    if (total * n_points > 0x3fffffffu) return RSV_E_SIZE;
+    FrSpec fs[RSV_MAX_COMMIT_GROUPS];
+    uint32_t col0 = 0;
+    for (size_t i = 0; i < n_groups; i++) {
+        fs[i].samples = d_samples;
+        fs[i].sstride = (uint64_t)n_points * total * 4;
+        for (uint32_t k = 0; k < rsv::FR_MAX_POINTS; k++) {
+            const bool on = k < n_points;
+            fs[i].lo[k] = on ? group_points[i].col_lo[k] : 0;
+            fs[i].hi[k] = on ? group_points[i].col_hi[k] : 0;
+            fs[i].entry[k] = (uint32_t)(k * total) + col0 + fs[i].lo[k];
+            fs[i].step[k] = 1;
+        }
+        col0 += groups[i].n_cols;
+    }
+    return fri_quotients(c, groups, fs, n_groups, n, log_blowup, d_mask, source, d_points, n_points, d_after, d_quot);
+}
+
+int rsv_fri_commit_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
+                       const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                       uint32_t* d_last_poly, uint8_t* d_low_degree) {
+    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
+    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    if (rc != RSV_OK) return rc;
+    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
+        ((uintptr_t)d_last_poly & 3))
+        return RSV_E_SIZE;
+    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
+}
+
+int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
+                        const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
+                        uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
+                        const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots,
+                        uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree) {
+    if (!c || !prog || !d_plonk || !d_poseidon || !d_int_plonk || !d_int_poseidon || !d_accept || !d_comp || !d_oods || !d_samples ||
+        !d_samples3 || !d_channel || !d_after || !d_quot || !d_roots || !d_alphas || !d_last_poly || !d_low_degree)
+        return RSV_E_NULL;
+    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_int_plonk & 3) ||
+        ((uintptr_t)d_int_poseidon & 3) || ((uintptr_t)d_comp & 3) || ((uintptr_t)d_oods & 3) || ((uintptr_t)d_samples & 3) ||
+        ((uintptr_t)d_samples3 & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_after & 3) || ((uintptr_t)d_quot & 3) ||
+        ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) || ((uintptr_t)d_last_poly & 3))
+        return RSV_E_SIZE;
+    if (prog->gates.empty()) return RSV_E_SIZE;  // built programs only
+    const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
+    uint32_t sizes[3];
+    size_t ns = 0;
+    int rc = fr_check_chain(lp, lq, log_blowup, log_last, n, sizes, &ns);
+    if (rc != RSV_OK) return rc;
+    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    ChainTrees ct;
+    rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, log_blowup, &ct);
+    if (rc != RSV_OK || n == 0) return rc;
+    const uint8_t* mask = d_ok ? d_ok : d_accept;
+    rc = ensure_buf(c, &c->ws_fri, &c->ws_fri_bytes, n * 24 * 4);
+    if (rc != RSV_OK) return rc;
+    uint32_t* pts = static_cast<uint32_t*>(c->ws_fri);
+    hipLaunchKernelGGL(rsv::k_fr_begin, dim3(grid_for(n, 64)), dim3(64), 0, c->stream, d_samples, d_samples3, d_oods, mask, lp, lq, (uint32_t)n,
+                       d_channel, d_after, pts);
+    // The quotient columns' groups: tree 3, then per tree the Plonk groups and the Poseidon groups (one column where the
+    // sizes are equal).  The interaction groups are cut into columns 0..3 (one sample) and the cumulative 4..7 (two: the
+    // proof's order has the previous-row value first).  Points: 0 the OODS point, 1 and 2 it minus the step of lp / lq.
+    const size_t Np = (size_t)1 << lp, Nq = (size_t)1 << lq;
+    rsv_commit_group g[rsv::FR_MAX_GROUPS];
+    FrSpec fs[rsv::FR_MAX_GROUPS] = {};
+    size_t ng = 0;
+    auto add = [&](const rsv_commit_group& grp, const uint32_t* samples, uint64_t sstride, uint32_t entry, uint32_t step, int prev_point) {
+        g[ng] = grp;
+        fs[ng].samples = samples;
+        fs[ng].sstride = sstride;
+        fs[ng].lo[0] = 0;
+        fs[ng].hi[0] = grp.n_cols;
+        fs[ng].entry[0] = entry;
+        fs[ng].step[0] = step;
+        if (prev_point) {
+            fs[ng].hi[prev_point] = grp.n_cols;
+            fs[ng].entry[prev_point] = entry - 1;
+            fs[ng].step[prev_point] = step;
+        }
+        ng++;
+    };
+    const uint32_t L3 = co_clb(lp, lq) - 1;
+    add({L3, 8, d_comp, (uint64_t)8 << L3, nullptr, nullptr}, d_samples3, 32, 0, 1, 0);
+    auto half = [](const rsv_commit_group& t, size_t rows, uint32_t first) {
+        return rsv_commit_group{t.log_size, 4, t.d_cols + first * rows, t.proof_stride, nullptr, nullptr};
+    };
+    // tree 0: the Plonk columns 0..9 (three groups), the Poseidon columns 10..49; tree 1: 50..61, 62..109; tree 2: 110.., 122..
+    add(ct.t0[0], d_samples, 134 * 4, 0, 1, 0);
+    add(ct.t0[1], d_samples, 134 * 4, 3, 1, 0);
+    add(ct.t0[2], d_samples, 134 * 4, 4, 1, 0);
+    add(ct.t0[3], d_samples, 134 * 4, 10, 1, 0);
+    add(ct.t1[0], d_samples, 134 * 4, 50, 1, 0);
+    add(ct.t1[1], d_samples, 134 * 4, 62, 1, 0);
+    add(half(ct.t2[0], Np, 0), d_samples, 134 * 4, 110, 1, 0);
+    add(half(ct.t2[0], Np, 4), d_samples, 134 * 4, 115, 2, 1);
+    add(half(ct.t2[1], Nq, 0), d_samples, 134 * 4, 122, 1, 0);
+    add(half(ct.t2[1], Nq, 4), d_samples, 134 * 4, 127, 2, 2);
+    rc = fri_quotients(c, g, fs, ng, n, log_blowup, mask, RSV_SAMPLE_COLUMNS, pts, 3, d_after, d_quot);
+    if (rc != RSV_OK) return rc;
+    return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
+}
+
+}  // extern "C"

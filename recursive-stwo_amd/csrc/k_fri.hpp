@@ -1,0 +1,366 @@
+// k_fri.hpp — the commit phase of FRI of the next proof: the DEEP quotient columns over their whole domains, the first
+// layer's and the inner layers' Merkle trees, the transcript between them, the two folds and the last layer's polynomial
+// (fri_api.inc drives the launches; include/rsv.h: rsv_fri_quotients_dev, rsv_fri_commit_dev, rsv_witness_fri_dev).
+//
+// The definition is the verifier's (k_query.hpp: the quotient constants, the row quotient and the folds per query),
+// evaluated at every position instead of the queried ones.
+//
+// Quotients.  One QM31 column per distinct LDE log size N.  Sample k of a column (value v at the point (px, py), both
+// QM31 = (CM31, CM31)) has the line coefficients a = w v.b, b = w (v.a py.b - v.b py.a), c = w py.b with w the running
+// power of `after`, starting at -2u for every column and advancing through the batches (one per point) in order.  At
+// position q, whose domain point is the M31 point (x, y),
+//   value = sum over batches of (sum_k c_k row[col_k] - (y sum_k a_k + sum_k b_k)) / den,
+//   den   = (px.a - x) py.b - (py.a - y) px.b = D0 - x py.b + y px.b          (CM31),
+// so a batch is a dot product of M31 row words with wave-uniform QM31 coefficients (four multiply-accumulates per
+// column into unreduced u64 sums, as k_sp_dot's), one affine term and one CM31 inverse.  k_fr_consts forms c_k, sum a,
+// sum b, D0 once per proof; the row words are the commitment's LDE, streamed in blocks (k_commit.hpp), never whole.
+// The domain point comes from the forward twiddle table of the domain 2^N the FFT uses anyway: y of position q is layer
+// 0's entry q >> 1, negated for odd q; x is layer 1's entry q >> 2, negated where bit 1 of q is set.
+//
+// Folds (bit-reversed storage, pair (2k, 2k + 1)).  Circle to line, column of log size l: (f0 + f1) + alpha (f0 - f1) / y,
+// 1 / y = entry k of layer 0 of the inverse table of 2^l.  Line, layer of log size l: (f0 + f1) + alpha (f0 - f1) / x,
+// 1 / x = entry k of layer 1 of the inverse table of 2^(l + 1).  No factor 1/2.
+#pragma once
+#include "k_commit.hpp"
+#include "k_sample.hpp"
+
+namespace rsv {
+
+constexpr uint32_t FR_MAX_GROUPS = 12;  // RSV_MAX_COMMIT_GROUPS for a caller; the chain has eleven (fri_api.inc)
+constexpr uint32_t FR_MAX_POINTS = 4;   // RSV_MAX_SAMPLE_POINTS
+constexpr uint32_t FR_HDR_WORDS = 16;   // per batch: sum a [4], sum b [4], D0 [2], py.b [2], px.b [2], 2 unused
+constexpr uint32_t FR_TERMS_AT = FR_MAX_POINTS * FR_HDR_WORDS;  // the terms' c follow the four headers, four words each
+
+// One column group of a quotient column.  Point k applies to its columns lo[k] .. hi[k] - 1 (hi <= lo: to none); the
+// sampled value of column c at point k is entry entry[k] + (c - lo[k]) * step[k] (four words each) of proof p's values at
+// samples + p * sstride.  ext: the extended rows of the pass, proof p (of the pass), column c, row r of the block at
+// ext + p * pstride + (c << rlog) + r (pstride 0: shared by every proof).
+struct FrGroup {
+    const uint32_t* ext;
+    uint64_t pstride;
+    const uint32_t* samples;
+    uint64_t sstride;
+    uint32_t n_cols;
+    uint32_t lo[FR_MAX_POINTS], hi[FR_MAX_POINTS], entry[FR_MAX_POINTS], step[FR_MAX_POINTS];
+};
+struct FrCol {
+    FrGroup g[FR_MAX_GROUPS];
+    uint32_t ng, np;        // groups of this size, points
+    uint32_t par_words;     // FR_TERMS_AT + 4 * terms
+    uint32_t p0;            // the pass's first proof (mask, points, after, samples are indexed p0 + p)
+    const uint8_t* mask;
+    uint32_t* par;          // [proofs of the pass][par_words]
+};
+
+// One lane per proof of the pass: points [n][np][8] (x then y), after [n][4]; any u32 is taken mod P.
+__global__ __launch_bounds__(64) void k_fr_consts(FrCol a, const uint32_t* __restrict__ points, const uint32_t* __restrict__ after,
+                                                  uint32_t n_pass) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n_pass || (a.mask && !a.mask[a.p0 + p])) return;
+    const uint64_t pp = a.p0 + p;
+    uint32_t* par = a.par + (uint64_t)p * a.par_words;
+    const QM31 step = sp_load_q(after + pp * 4);
+    QM31 w = q_mk(0, 0, P - 2, 0);
+    uint32_t t = 0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < a.np; k++) {
+        const uint32_t* pt = points + (pp * a.np + k) * 8;
+        const QM31 px = sp_load_q(pt), py = sp_load_q(pt + 4);
+        QM31 sa = q_zero(), sb = q_zero();
+#pragma unroll 1
+        for (uint32_t gi = 0; gi < a.ng; gi++) {
+            const FrGroup& g = a.g[gi];
+            const uint32_t* sv = g.samples + pp * g.sstride;
+#pragma unroll 1
+            for (uint32_t c = g.lo[k]; c < g.hi[k]; c++, t++) {
+                const QM31 v = sp_load_q(sv + ((uint64_t)g.entry[k] + (uint64_t)(c - g.lo[k]) * g.step[k]) * 4);
+                sa = q_add(sa, q_mul_c(w, v.b));
+                sb = q_add(sb, q_mul_c(w, c_sub(c_mul(v.a, py.b), c_mul(v.b, py.a))));
+                const QM31 cc = q_mul_c(w, py.b);
+                uint32_t* o = par + FR_TERMS_AT + t * 4;
+                o[0] = cc.a.a; o[1] = cc.a.b; o[2] = cc.b.a; o[3] = cc.b.b;
+                w = q_mul(w, step);
+            }
+        }
+        const CM31 d0 = c_sub(c_mul(px.a, py.b), c_mul(py.a, px.b));
+        uint32_t* h = par + k * FR_HDR_WORDS;
+        h[0] = sa.a.a; h[1] = sa.a.b; h[2] = sa.b.a; h[3] = sa.b.b;
+        h[4] = sb.a.a; h[5] = sb.a.b; h[6] = sb.b.a; h[7] = sb.b.b;
+        h[8] = d0.a; h[9] = d0.b; h[10] = py.b.a; h[11] = py.b.b; h[12] = px.b.a; h[13] = px.b.b; h[14] = 0u; h[15] = 0u;
+    }
+}
+
+// The rows of one pass of one quotient column: 2^rlog rows per proof from position row0 of the domain 2^N.
+struct FrRows {
+    FrCol col;
+    uint32_t rlog, N;
+    uint64_t row0;
+    const uint32_t* tw;  // forward twiddle table of the domain 2^N
+    uint32_t* quot;      // the column of proof p0: coordinate j of proof p0 + p at quot + p * qstride + (j << N)
+    uint64_t qstride;
+};
+
+// One lane per (proof, row): the quotient column's value at the row's position; zeros for a masked proof.  The sums are
+// CoAcc's: a folded remainder < 2^34 plus at most four products of canonical words (the LDE's m_* results, k_fr_consts'
+// q_mul results).
+__global__ __launch_bounds__(256) void k_fr_rows(FrRows a) {
+    const uint32_t bpp = a.rlog > 8 ? 1u << (a.rlog - 8) : 1u;  // workgroups per proof: a wave's rows belong to one proof
+    const uint32_t p = blockIdx.x / bpp, r = (blockIdx.x - p * bpp) * 256 + threadIdx.x;
+    if (r >= (1u << a.rlog)) return;
+    const uint64_t pos = a.row0 + r;
+    uint32_t* o = a.quot + (uint64_t)p * a.qstride + pos;
+    QM31 v = q_zero();
+    if (!(a.col.mask && !a.col.mask[a.col.p0 + p])) {
+        const uint32_t* par = a.col.par + (uint64_t)p * a.col.par_words;
+        uint32_t y = a.tw[cm_tw_off(a.N, 0) + (pos >> 1)], x = a.tw[cm_tw_off(a.N, 1) + (pos >> 2)];
+        if (pos & 1) y = m_neg(y);
+        if (pos & 2) x = m_neg(x);
+        const uint32_t* ct = par + FR_TERMS_AT;
+#pragma unroll 1
+        for (uint32_t k = 0; k < a.col.np; k++) {
+            uint64_t acc[4] = {0, 0, 0, 0};
+            uint32_t nt = 0;
+#pragma unroll 1
+            for (uint32_t gi = 0; gi < a.col.ng; gi++) {
+                const FrGroup& g = a.col.g[gi];
+                const uint32_t* e = g.ext + p * g.pstride + r;
+#pragma unroll 4
+                for (uint32_t c = g.lo[k]; c < g.hi[k]; c++, nt++, ct += 4) {
+                    const uint32_t w = e[(uint64_t)c << a.rlog];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        acc[j] += (uint64_t)w * ct[j];
+                        if ((nt & 3) == 3) acc[j] = sp_fold(acc[j]);
+                    }
+                }
+            }
+            if (!nt) continue;
+            const uint32_t* h = par + k * FR_HDR_WORDS;
+            const QM31 sum = q_mk(sp_canon(sp_fold(acc[0])), sp_canon(sp_fold(acc[1])), sp_canon(sp_fold(acc[2])), sp_canon(sp_fold(acc[3])));
+            const QM31 lin = q_add(q_mul_m(q_mk(h[0], h[1], h[2], h[3]), y), q_mk(h[4], h[5], h[6], h[7]));
+            const CM31 den = c_add(c_sub(c_mk(h[8], h[9]), c_mul_m(c_mk(h[10], h[11]), x)), c_mul_m(c_mk(h[12], h[13]), y));
+            v = q_add(v, q_mul_c(q_sub(sum, lin), c_inv(den)));
+        }
+    }
+    o[0] = v.a.a;
+    o[(uint64_t)1 << a.N] = v.a.b;
+    o[(uint64_t)2 << a.N] = v.b.a;
+    o[(uint64_t)3 << a.N] = v.b.b;
+}
+
+// ---------------------------------------------------------------- layer trees
+// hash_node of every node of one layer of P trees, one lane per node: out [P][2^l][8]; child [P][2^(l+1)][8], nullptr at
+// the leaves; data (may be nullptr): the one QM31 column this layer carries, coordinate j of proof p, node i at
+// data + p * dstride + (j << l) + i — four M31 columns to the hash, as k_cm_hash_layer takes a group of four.
+__global__ __launch_bounds__(256) void k_fr_hash_layer(const uint32_t* __restrict__ data, uint64_t dstride, uint32_t l, uint32_t P_,
+                                                       const uint32_t* __restrict__ child, uint32_t* __restrict__ out) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ << l)) return;
+    Hash8 d = zero8();
+    if (data) {
+        const uint64_t p = t >> l, i = t & (((uint64_t)1 << l) - 1);
+        const uint32_t* s = data + p * dstride + i;
+        d = sponge_capacity4<1>(s[0], s[(uint64_t)1 << l], s[(uint64_t)2 << l], s[(uint64_t)3 << l]);
+    }
+    Hash8 h;
+    if (!child) {
+        h = leaf_from_capacity<1>(d);
+    } else {
+        h = hash_tree<1>(load_hash(child + t * 16), load_hash(child + t * 16 + 8));
+        if (data) h = combine_with_column<1>(h, d);
+    }
+    store_hash(out + t * 8, h);
+}
+
+// The channel step of one layer, one lane per proof: mix the layer's root, draw alpha.  chan [P][16] (digest, n_sent),
+// read and updated; the root to roots + p * rstride, alpha to alphas + p * astride.  A masked proof: zeros in all three.
+// low (may be nullptr): the proof's low-degree flag, set to 1 here (0 for a masked proof) before k_fr_last clears it.
+__global__ __launch_bounds__(64) void k_fr_draw(const uint32_t* __restrict__ root, const uint8_t* __restrict__ mask, uint32_t P_,
+                                                uint32_t* __restrict__ chan, uint32_t* __restrict__ roots, uint64_t rstride,
+                                                uint32_t* __restrict__ alphas, uint64_t astride, uint8_t* __restrict__ low) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= P_) return;
+    uint32_t* co = chan + (size_t)p * 16;
+    uint32_t* ro = roots + p * rstride;
+    uint32_t* ao = alphas + p * astride;
+    const bool keep = !mask || mask[p];
+    if (low) low[p] = keep ? 1 : 0;
+    if (!keep) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) co[i] = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) ro[i] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) ao[i] = 0u;
+        return;
+    }
+    Channel<0> ch;
+    ch.init();
+    ch.digest = load_hash(co);
+    ch.n_sent = co[8];
+    const Hash8 r = load_hash(root + (size_t)p * 8);
+    ch.mix(r);
+    const Hash8 dr = ch.draw();
+    store_hash(co, ch.digest);
+    co[8] = ch.n_sent;
+    store_hash(ro, r);
+#pragma unroll
+    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
+}
+
+// ---------------------------------------------------------------- folds
+// A set of P QM31 vectors of 2^l values: coordinate j of proof p, value i at base + p * stride + (j << l) + i.
+struct FrVec {
+    uint32_t* base;
+    uint64_t stride;
+};
+__device__ __forceinline__ QM31 fr_ld(const uint32_t* s, uint32_t l) {
+    return q_mk(s[0], s[(uint64_t)1 << l], s[(uint64_t)2 << l], s[(uint64_t)3 << l]);
+}
+__device__ __forceinline__ void fr_st(uint32_t* d, uint32_t l, QM31 v) {
+    d[0] = v.a.a;
+    d[(uint64_t)1 << l] = v.a.b;
+    d[(uint64_t)2 << l] = v.b.a;
+    d[(uint64_t)3 << l] = v.b.b;
+}
+
+// src (log size l) -> dst (log size l - 1), one lane per (proof, k): (f0 + f1) + alpha (f0 - f1) winv[k], winv the layer
+// of the inverse twiddle table that holds 1 / y (circle to line) or 1 / x (line).  JOIN: dst = alpha^2 dst + that (a
+// quotient column joining the running evaluation).  alpha: alphas + p * astride.  A masked proof gets zeros.
+template <bool JOIN>
+__global__ __launch_bounds__(256) void k_fr_fold(FrVec src, FrVec dst, uint32_t l, uint32_t P_, const uint32_t* __restrict__ winv,
+                                                 const uint32_t* __restrict__ alphas, uint64_t astride, const uint8_t* __restrict__ mask) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ << (l - 1))) return;
+    const uint64_t p = t >> (l - 1), k = t & (((uint64_t)1 << (l - 1)) - 1);
+    uint32_t* d = dst.base + p * dst.stride + k;
+    QM31 v = q_zero();
+    if (!mask || mask[p]) {
+        const uint32_t* s = src.base + p * src.stride + 2 * k;
+        const QM31 f0 = fr_ld(s, l), f1 = fr_ld(s + 1, l);
+        const uint32_t* ap = alphas + p * astride;
+        const QM31 alpha = q_mk(ap[0], ap[1], ap[2], ap[3]);
+        v = q_add(q_add(f0, f1), q_mul(q_mul_m(q_sub(f0, f1), winv[k]), alpha));
+        if (JOIN) v = q_add(q_mul(q_mul(alpha, alpha), fr_ld(d, l - 1)), v);
+    }
+    fr_st(d, l - 1, v);
+}
+
+// ---------------------------------------------------------------- last layer
+// One inverse butterfly layer m of the line interpolation of P x 4 vectors of 2^L words (ev [P][4][2^L], in place), one
+// lane per pair.  The line domain of 2^L points is the x-projection of the circle domain 2^(L+1): its layer m is that
+// domain's layer m + 1, whose inverse twiddles winv holds (2^(L-1-m) entries).
+__global__ __launch_bounds__(256) void k_fr_line_layer(uint32_t* __restrict__ ev, uint32_t L, uint32_t m, uint32_t P_,
+                                                       const uint32_t* __restrict__ winv) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ * 4) << (L - 1)) return;
+    const uint64_t row = t >> (L - 1);
+    const uint32_t j = (uint32_t)(t & (((uint64_t)1 << (L - 1)) - 1));
+    const uint32_t a_at = ((j >> m) << (m + 1)) | (j & ((1u << m) - 1)), b_at = a_at + (1u << m);
+    uint32_t* d = ev + (row << L);
+    uint32_t a = d[a_at], b = d[b_at];
+    cm_butterfly<true>(a, b, winv[a_at >> (m + 1)]);
+    d[a_at] = a;
+    d[b_at] = b;
+}
+
+// After the layers, word j of a vector times 2^-L is the coefficient of prod_m pi^m(x)^(bit m of j): natural order.  The
+// first 2^log_last of them go to last [P][2^log_last][4] in the order rsv_line_eval reads (index bit-reversed over
+// log_last bits); a non-zero one past them clears the proof's low-degree flag (k_fr_draw set it).  One lane per (proof,
+// j); zeros for a masked proof.
+__global__ __launch_bounds__(256) void k_fr_last(const uint32_t* __restrict__ ev, uint32_t L, uint32_t log_last, uint32_t P_,
+                                                 const uint8_t* __restrict__ mask, uint32_t* __restrict__ last, uint8_t* __restrict__ low) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ << L)) return;
+    const uint64_t p = t >> L;
+    const uint32_t j = (uint32_t)(t & (((uint64_t)1 << L) - 1));
+    const bool keep = !mask || mask[p];
+    const uint32_t scale = L ? 1u << (31 - L) : 1u;  // 2^-L mod P
+    uint32_t w[4];
+#pragma unroll
+    for (int c = 0; c < 4; c++) w[c] = keep ? m_mul(ev[((p * 4 + c) << L) + j], scale) : 0u;
+    if (j < (1u << log_last)) {
+        const uint32_t i = log_last ? bit_reverse(j, log_last) : 0u;
+        uint32_t* o = last + ((p << log_last) + i) * 4;
+#pragma unroll
+        for (int c = 0; c < 4; c++) o[c] = w[c];
+    } else if (w[0] | w[1] | w[2] | w[3]) {
+        low[p] = 0;
+    }
+}
+
+// The transcript's last step of the stage, one lane per proof: mix the last polynomial's coefficients two per mix, a
+// single one at the end of an odd count.  chan as k_fr_draw's; a masked proof keeps its zeros.
+__global__ __launch_bounds__(64) void k_fr_mix_last(const uint32_t* __restrict__ last, uint32_t log_last, const uint8_t* __restrict__ mask,
+                                                    uint32_t P_, uint32_t* __restrict__ chan) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= P_ || (mask && !mask[p])) return;
+    uint32_t* co = chan + (size_t)p * 16;
+    Channel<0> ch;
+    ch.init();
+    ch.digest = load_hash(co);
+    ch.n_sent = co[8];
+    const uint32_t n = 1u << log_last;
+    const uint32_t* c = last + ((size_t)p << log_last) * 4;
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i += 2) {
+        const QM31 f = q_mk(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+        if (i + 1 < n) ch.mix_two(f, q_mk(c[4 * i + 4], c[4 * i + 5], c[4 * i + 6], c[4 * i + 7]));
+        else ch.mix_one(f);
+    }
+    store_hash(co, ch.digest);
+    co[8] = ch.n_sent;
+}
+
+// ---------------------------------------------------------------- the recursion circuit's chain (rsv_witness_fri_dev)
+// One lane per proof (run_transcript order): mix the 142 sampled values two per mix (the 134 of trees 0..2, then tree
+// 3's eight), draw `after`; the three points of the quotients: the OODS point, and it minus the step of CanonicCoset(lp)
+// and of CanonicCoset(lq) (k_sp_weights' form).  chan [n][16] read and updated, after [n][4], pts [n][3][8].  A masked
+// proof gets zeros in all three.
+__global__ __launch_bounds__(64) void k_fr_begin(const uint32_t* __restrict__ samples, const uint32_t* __restrict__ samples3,
+                                                 const uint32_t* __restrict__ oods, const uint8_t* __restrict__ mask, uint32_t lp, uint32_t lq,
+                                                 uint32_t n, uint32_t* __restrict__ chan, uint32_t* __restrict__ after, uint32_t* __restrict__ pts) {
+    const uint32_t p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= n) return;
+    uint32_t* co = chan + (size_t)p * 16;
+    uint32_t* ao = after + (size_t)p * 4;
+    uint32_t* po = pts + (size_t)p * 24;
+    if (mask && !mask[p]) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) co[i] = 0u;
+#pragma unroll
+        for (int i = 0; i < 4; i++) ao[i] = 0u;
+#pragma unroll
+        for (int i = 0; i < 24; i++) po[i] = 0u;
+        return;
+    }
+    Channel<0> ch;
+    ch.init();
+    ch.digest = load_hash(co);
+    ch.n_sent = co[8];
+#pragma unroll 1
+    for (uint32_t i = 0; i < 142; i += 2) {
+        const uint32_t* s = i < 134 ? samples + ((size_t)p * 134 + i) * 4 : samples3 + ((size_t)p * 8 + (i - 134)) * 4;
+        ch.mix(load_hash(s));
+    }
+    const Hash8 dr = ch.draw();
+    store_hash(co, ch.digest);
+    co[8] = ch.n_sent;
+#pragma unroll
+    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
+    const QM31 x = sp_load_q(oods + (size_t)p * 8), y = sp_load_q(oods + (size_t)p * 8 + 4);
+    auto put = [&](uint32_t k, QM31 px, QM31 py) {
+        uint32_t* o = po + k * 8;
+        o[0] = px.a.a; o[1] = px.a.b; o[2] = px.b.a; o[3] = px.b.b;
+        o[4] = py.a.a; o[5] = py.a.b; o[6] = py.b.a; o[7] = py.b.b;
+    };
+    put(0, x, y);
+#pragma unroll 1
+    for (uint32_t k = 1; k < 3; k++) {
+        const uint32_t log = k == 1 ? lp : lq;
+        const uint32_t sx = GEN_POW.x[31 - log], sy = GEN_POW.y[31 - log];  // the step's inverse is (sx, -sy)
+        put(k, q_add(q_mul_m(x, sx), q_mul_m(y, sy)), q_sub(q_mul_m(y, sx), q_mul_m(x, sy)));
+    }
+}
+
+}  // namespace rsv
