@@ -1400,3 +1400,4 @@ class Exchange:
 
 
 from . import witness_program  # noqa: E402,F401  (the witness program container)
+from .chain import Chain  # noqa: E402,F401  (the next-proof chain's buffers and stages as one object)

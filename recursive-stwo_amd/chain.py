@@ -1,0 +1,144 @@
+"""Chain: the buffers and stages of "the next proof on the GPU" as one object.
+
+Every stage of the chain (Context.witness, witness_trace, witness_commit, witness_decommit, witness_tree3, witness_sample,
+witness_fri) takes the same program, trace columns and flags, followed by its own tensors.  A Chain owns those tensors,
+allocates each when the stage that writes it first runs, and makes each Context call with the arguments drawn from itself.
+The Context methods stay the 1:1 layer over the C-ABI; nothing here reaches past them.
+"""
+import numpy as np
+
+from . import composition_log_size, fri_sizes, pack
+
+_FLAGS = ("acc", "ok", "low_degree")
+_WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
+            "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree")
+
+
+class Chain:
+    """Chain(ctx, program, n, log_blowup): n proofs through witness() -> trace() -> commit() -> decommit() / tree3() ->
+    sample() -> fri().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
+    ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
+    a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3)."""
+
+    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, device="cuda:0"):
+        self.ctx, self.program, self.n, self.log_blowup, self.log_last = ctx, program, n, log_blowup, log_last
+        self.fill, self.with_caps, self.device = fill, caps, device
+        self.lp, self.lq = program.trace_sizes()
+        self.n_ops = len(program.gates()[1])
+        self.done = set()
+        self._blob = self._vars = self._flow = self._swap = None
+        for name in _WRITTEN:
+            setattr(self, name, None)
+
+    def _new(self, *shape, flag=False, fill=None):
+        import torch
+        fill = self.fill if fill is None else fill
+        if flag:
+            return torch.full(shape, 7 if fill else 0, dtype=torch.uint8, device=self.device)
+        return torch.full(shape, fill - (1 << 32) if fill >> 31 else fill, dtype=torch.int32, device=self.device)
+
+    def _need(self, stage, *before):
+        for b in before:
+            if b not in self.done:
+                raise ValueError(f"Chain.{stage}() needs {b}() first")
+
+    def witness(self, proofs_or_blob, inputs, by_variable=False):
+        """Context.witness on proofs (a list of bytes) or a packed (blob, offsets); by_variable: the context's
+        witness_layout option is "by_variable"."""
+        import torch
+        blob, offsets = pack(proofs_or_blob) if isinstance(proofs_or_blob, list) else proofs_or_blob
+        n, wp = self.n, self.program
+        self._blob = (torch.from_numpy(blob.copy()).to(self.device), torch.from_numpy(offsets.astype(np.int64)).to(self.device))
+        F = wp.shape.flow_count
+        self._vars = self._new(*((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4)), fill=0)
+        self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
+        self.acc = self._new(n, flag=True, fill=0)
+        self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
+        self.done = {"witness"}
+
+    def trace(self, plonk=True, poseidon=True, ops=True):
+        """Context.witness_trace (an output may be skipped), then the blob, the variables and the flow are dropped: torch's
+        stream is first made to wait for the context, so that a reuse of their memory is ordered behind the kernels reading it."""
+        self._need("trace", "witness")
+        n = self.n
+        self.plonk = self._new(n, 12, 1 << self.lp) if plonk else None
+        self.poseidon = self._new(n, 48, 1 << self.lq) if poseidon else None
+        self.ops = self._new(n, max(self.n_ops, 1)) if ops else None
+        self.ctx.witness_trace(self.program, self._vars, self.acc, n, d_plonk=self.plonk, d_poseidon=self.poseidon, d_ops=self.ops,
+                               d_flow=self._flow, d_flow_swap=self._swap)
+        self.ctx.release_to_torch()
+        self._blob = self._vars = self._flow = self._swap = None
+        self.done = {"trace"}
+
+    def _lead(self):
+        return (self.program, self.plonk, self.poseidon, self.ops, self.int_plonk, self.int_poseidon, self.acc, self.n)
+
+    def commit(self):
+        """Context.witness_commit: trees 0-2, the draws, the interaction columns and sums, the channel, ok (and the caps)."""
+        self._need("commit", "trace")
+        n, b, lp, lq = self.n, self.log_blowup, self.lp, self.lq
+        if self.roots is None:
+            self.roots, self.draws, self.sums, self.channel = self._new(n, 3, 8), self._new(n, 12), self._new(n, 2, 4), self._new(n, 16)
+            self.int_plonk, self.int_poseidon = self._new(n, 8, 1 << lp), self._new(n, 8, 1 << lq)
+            self.ok = self._new(n, flag=True)
+            self.caps = self._new(n, 3, 2 << b, 8) if self.with_caps else None
+        self.ctx.witness_commit(self.program, self.plonk, self.poseidon, self.ops, self.acc, n, b, self.roots, self.draws, self.int_plonk,
+                                self.int_poseidon, self.sums, d_channel=self.channel, d_ok=self.ok, d_caps=self.caps)
+        self.done.add("commit")
+
+    def decommit(self, d_queries, d_values, d_n_values, d_witness, d_n_witness, caps=True):
+        """Context.witness_decommit at d_queries uint32[n, n_queries] into the caller's buffers (capacities:
+        witness_decommit_sizes); caps=False opens without the caps even where the chain keeps them."""
+        self._need("decommit", "commit")
+        self.ctx.witness_decommit(*self._lead(), self.log_blowup, d_queries, d_queries.shape[1], d_values, d_n_values, d_witness, d_n_witness,
+                                  d_ok=self.ok, d_caps=self.caps if caps else None)
+
+    def tree3(self):
+        """Context.witness_tree3: the composition polynomial, its root (and cap), the OODS point, its samples; the channel moves on."""
+        self._need("tree3", "commit")
+        n = self.n
+        if self.comp is None:
+            L3 = composition_log_size(self.lp, self.lq)
+            self.comp, self.root3, self.oods, self.samples3 = self._new(n, 8, 1 << L3), self._new(n, 8), self._new(n, 8), self._new(n, 8, 4)
+            self.cap3 = self._new(n, 2 << self.log_blowup, 8) if self.with_caps else None
+        self.ctx.witness_tree3(*self._lead(), self.log_blowup, self.sums, self.draws, self.channel, self.comp, self.root3, self.oods,
+                               self.samples3, d_ok=self.ok, d_cap3=self.cap3)
+        self.done.add("tree3")
+
+    def sample(self, d_oods=None):
+        """Context.witness_sample at d_oods uint32[n, 8], or at the point tree3() drew."""
+        self._need("sample", "commit", *(() if d_oods is not None else ("tree3",)))
+        if self.samples is None:
+            self.samples = self._new(self.n, 134, 4)
+        self.ctx.witness_sample(*self._lead(), self.oods if d_oods is None else d_oods, self.samples, d_ok=self.ok)
+        self.done.add("sample")
+
+    def fri(self):
+        """Context.witness_fri (log_last as given to the constructor): `after`, the quotient columns, the layers' roots and
+        alphas, the inner layers, the last polynomial, low_degree; the channel moves on."""
+        self._need("fri", "tree3", "sample")
+        if self.log_last is None:
+            raise ValueError("Chain.fri() needs log_last")
+        n, b, last = self.n, self.log_blowup, self.log_last
+        if self.quot is None:
+            sz = fri_sizes(self.lp, self.lq, b, last)
+            ni = sz["n_inner"]
+            self.after, self.quot, self.fri_roots, self.alphas = self._new(n, 4), self._new(n, sz["quot_words"]), self._new(n, 1 + ni, 8), self._new(n, 1 + ni, 4)
+            self.layers, self.last_poly = self._new(n, max(sz["layer_words"], 1)), self._new(n, 1 << last, 4)
+            self.low_degree = self._new(n, flag=True)
+        self.ctx.witness_fri(*self._lead(), b, last, self.comp, self.oods, self.samples, self.samples3, self.channel, self.after, self.quot,
+                             self.fri_roots, self.alphas, self.layers, self.last_poly, self.low_degree, d_ok=self.ok)
+        self.done.add("fri")
+
+    def numpy(self):
+        """Synchronises -> {name: array} of every tensor allocated so far: uint32 views, the flags uint8; ops cut to the
+        program's n_witness_ops."""
+        self.ctx.synchronize()
+        out = {}
+        for name in _WRITTEN:
+            t = getattr(self, name)
+            if t is not None:
+                out[name] = t.cpu().numpy() if name in _FLAGS else t.cpu().numpy().view(np.uint32)
+        if "ops" in out:
+            out["ops"] = out["ops"][:, :self.n_ops]
+        return out

@@ -173,17 +173,91 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
     return RSV_OK;
 }
 
-// The three trees of the recursion circuit's next proof as commit groups, and the chain's workspace: tree 0's op column
-// of every proof (column 3 of the Plonk preprocessed ones follows the proof, the other 49 are the program's), the lookup
-// elements, the channels and the ok flags between the trees.  Shared by rsv_witness_commit_caps_dev and
-// rsv_witness_decommit_dev.  Enqueues the op column on the context's stream.
+// Any of the pointers null; any of them off a 4-byte boundary (a null pointer is aligned).
+template <class... P>
+bool any_null(const P*... p) {
+    return (... || !p);
+}
+template <class... P>
+bool any_misaligned(const P*... p) {
+    return (... || ((uintptr_t)p & 3));
+}
+
+// What every stage of the chain takes first: the context, the program, the proofs' trace and interaction columns (d_ops may
+// be null), the flags and the batch.  A stage tests chain_null and chain_misaligned with its own pointers added, then its
+// own sizes, then calls chain_open.  The two tests are not inside chain_open because a null pointer of any kind, shared or
+// the stage's own, is RSV_E_NULL before any misalignment or size is RSV_E_SIZE, and each stage's size checks stand between
+// the tests and chain_open's body: one call could only keep that order by taking the stage's pointers and sizes as well.
+struct ChainArgs {
+    rsv_ctx* c;
+    const rsv_witness_program* prog;
+    const uint32_t *plonk, *poseidon, *ops, *int_plonk, *int_poseidon;
+    const uint8_t *accept, *ok;
+    size_t n;
+    uint32_t log_blowup;
+};
+template <class... P>
+bool chain_null(const ChainArgs& a, const P*... stage) {
+    return any_null(a.c, a.prog, a.plonk, a.poseidon, a.int_plonk, a.int_poseidon, a.accept, stage...);
+}
+template <class... P>
+bool chain_misaligned(const ChainArgs& a, const P*... stage) {
+    return any_misaligned(a.plonk, a.poseidon, a.ops, a.int_plonk, a.int_poseidon, stage...);
+}
+
+// The three trees of the recursion circuit's next proof as commit groups, the mask of the stages behind the commitment
+// (d_ok where given, else d_accept), and the chain's workspace: tree 0's op column of every proof (column 3 of the Plonk
+// preprocessed ones follows the proof, the other 49 are the program's), the lookup elements, the channels and the ok flags
+// between the trees.
 struct ChainTrees {
     rsv_commit_group t0[4], t1[2], t2[2];
+    const uint8_t* mask;
     uint32_t *lookup, *chan;
     uint8_t* ok;
+    const rsv_commit_group* tree(int t) const { return t == 0 ? t0 : t == 1 ? t1 : t2; }
 };
-int chain_trees(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
-                const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, size_t n, uint32_t log_blowup, ChainTrees* ct) {
+constexpr size_t CHAIN_TREE_GROUPS[3] = {4, 2, 2};
+
+// sampled_values[0..2] of the next proof, group by group in the proof's own order: the tree, the group within it
+// (ChainTrees) and which of its columns (the interaction groups are cut into columns 0..3, one value each, and the
+// cumulative 4..7, two each: the previous-row value, then the OODS value); the entry of the first column's OODS value, the
+// step from column to column, and which previous-row point the group has (0: none, 1: the Plonk step, 2: the Poseidon one).
+// A cut group has two rows, the cumulative half straight after the other: rsv_witness_sample_dev samples the group whole
+// from the first row, and its output form (SpOut, chain == 1, single == the first row's cols, two points) puts the
+// cumulative columns' OODS values at entry + cols + 1, step 2.  chain_samples_before holds the second row to that.
+struct ChainSamples {
+    uint32_t tree, group, col0, cols, entry, step, prev_point;
+};
+constexpr ChainSamples CHAIN_SAMPLES[10] = {
+    {0, 0, 0, 3, 0, 1, 0},   {0, 1, 0, 1, 3, 1, 0},   {0, 2, 0, 6, 4, 1, 0},   {0, 3, 0, 40, 10, 1, 0},  {1, 0, 0, 12, 50, 1, 0},
+    {1, 1, 0, 48, 62, 1, 0}, {2, 0, 0, 4, 110, 1, 0}, {2, 0, 4, 4, 115, 2, 1}, {2, 1, 0, 4, 122, 1, 0}, {2, 1, 4, 4, 127, 2, 2}};
+// The values of the table's first k groups; 0 unless each group starts where the one before ends, only a cumulative half
+// has a previous-row point and the step of 2 that goes with it, and such a half follows the first half of its own group.
+constexpr uint32_t chain_samples_before(size_t k) {
+    uint32_t at = 0;
+    for (size_t i = 0; i < k; i++) {
+        const ChainSamples& s = CHAIN_SAMPLES[i];
+        if (s.entry != at + (s.prev_point ? 1 : 0) || s.step != (s.prev_point ? 2u : 1u) || (s.col0 != 0) != (s.prev_point != 0)) return 0;
+        if (s.col0) {
+            if (i == 0) return 0;
+            const ChainSamples& h = CHAIN_SAMPLES[i - 1];
+            if (h.tree != s.tree || h.group != s.group || h.col0 != 0 || h.cols != s.col0) return 0;
+        }
+        at += s.cols * s.step;
+    }
+    return at;
+}
+constexpr uint32_t CHAIN_SAMPLE_VALUES = chain_samples_before(10);
+static_assert(CHAIN_SAMPLE_VALUES == 134, "trees 0, 1 and 2: 50 + 60 + 24 sampled values");
+
+// Enqueues the op column on the context's stream.
+int chain_open(const ChainArgs& a, ChainTrees* ct) {
+    rsv_ctx* c = a.c;
+    const rsv_witness_program* prog = a.prog;
+    const uint32_t *d_plonk = a.plonk, *d_poseidon = a.poseidon, *d_ops = a.ops, *d_int_plonk = a.int_plonk, *d_int_poseidon = a.int_poseidon;
+    const size_t n = a.n;
+    const uint32_t log_blowup = a.log_blowup;
+    ct->mask = a.ok ? a.ok : a.accept;
     int rc = chain_begin(c, prog, n, true);
     if (rc != RSV_OK) return rc;
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
@@ -249,15 +323,14 @@ int rsv_witness_commit_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, con
                                 const uint32_t* d_ops, const uint8_t* d_accept, size_t n, uint32_t log_blowup, uint32_t* d_roots,
                                 uint32_t* d_draws, uint32_t* d_int_plonk, uint32_t* d_int_poseidon, uint32_t* d_sums, uint32_t* d_channel,
                                 uint8_t* d_ok, uint32_t* d_caps) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_accept || !d_roots || !d_draws || !d_int_plonk || !d_int_poseidon || !d_sums)
-        return RSV_E_NULL;
+    // the commitment's own mask is d_accept (d_ok is its output)
+    const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, nullptr, n, log_blowup};
+    if (chain_null(a, d_roots, d_draws, d_sums)) return RSV_E_NULL;
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_roots & 3) ||
-        ((uintptr_t)d_draws & 3) || ((uintptr_t)d_int_plonk & 7) || ((uintptr_t)d_int_poseidon & 7) || ((uintptr_t)d_sums & 3) ||
-        ((uintptr_t)d_channel & 3) || ((uintptr_t)d_caps & 3))
+    if (chain_misaligned(a, d_roots, d_draws, d_sums, d_channel, d_caps) || ((uintptr_t)d_int_plonk & 7) || ((uintptr_t)d_int_poseidon & 7))
         return RSV_E_SIZE;
     ChainTrees ct;
-    int rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, log_blowup, &ct);
+    int rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     hipStream_t st = c->stream;

@@ -175,15 +175,10 @@ int rsv_witness_tree3_dev(rsv_ctx* c, const rsv_witness_program* prog, const uin
                           const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
                           const uint8_t* d_ok, size_t n, uint32_t log_blowup, const uint32_t* d_sums, const uint32_t* d_draws,
                           uint32_t* d_channel, uint32_t* d_comp, uint32_t* d_root3, uint32_t* d_cap3, uint32_t* d_oods, uint32_t* d_samples3) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_int_plonk || !d_int_poseidon || !d_accept || !d_sums || !d_draws || !d_channel ||
-        !d_comp || !d_root3 || !d_oods || !d_samples3)
-        return RSV_E_NULL;
+    const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, 0};
+    if (chain_null(a, d_sums, d_draws, d_channel, d_comp, d_root3, d_oods, d_samples3)) return RSV_E_NULL;
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_int_plonk & 3) ||
-        ((uintptr_t)d_int_poseidon & 3) || ((uintptr_t)d_sums & 3) || ((uintptr_t)d_draws & 3) || ((uintptr_t)d_channel & 3) ||
-        ((uintptr_t)d_comp & 3) || ((uintptr_t)d_root3 & 3) || ((uintptr_t)d_cap3 & 3) || ((uintptr_t)d_oods & 3) ||
-        ((uintptr_t)d_samples3 & 3))
-        return RSV_E_SIZE;
+    if (chain_misaligned(a, d_sums, d_draws, d_channel, d_comp, d_root3, d_cap3, d_oods, d_samples3)) return RSV_E_SIZE;
     if (prog->gates.empty()) return RSV_E_SIZE;  // built programs only
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     int rc = co_check_sizes(lp, lq, n);
@@ -191,9 +186,9 @@ int rsv_witness_tree3_dev(rsv_ctx* c, const rsv_witness_program* prog, const uin
     const uint32_t L3 = co_clb(lp, lq) - 1;
     if (L3 + log_blowup > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
     ChainTrees ct;
-    rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, 0, &ct);
+    rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
-    const uint8_t* mask = d_ok ? d_ok : d_accept;
+    const uint8_t* mask = ct.mask;
     // the components' columns in component order: preprocessed (the op column is the proof's own), trace, interaction
     const rsv_commit_group g[8] = {ct.t0[0], ct.t0[1], ct.t0[2], ct.t1[0], ct.t2[0], ct.t0[3], ct.t1[1], ct.t2[1]};
     rc = composition(c, g, 5, 8, lp, lq, n, d_sums, d_draws, mask, d_comp, nullptr);

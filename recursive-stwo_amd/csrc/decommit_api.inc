@@ -237,29 +237,23 @@ int rsv_witness_decommit_dev(rsv_ctx* c, const rsv_witness_program* prog, const 
                              const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
                              const uint8_t* d_ok, size_t n, uint32_t log_blowup, const uint32_t* d_queries, uint32_t n_queries,
                              const uint32_t* d_caps, uint32_t* d_values, uint32_t* d_n_values, uint32_t* d_witness, uint32_t* d_n_witness) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_int_plonk || !d_int_poseidon || !d_accept || !d_queries || !d_values || !d_n_values ||
-        !d_witness || !d_n_witness)
-        return RSV_E_NULL;
+    const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup};
+    if (chain_null(a, d_queries, d_values, d_n_values, d_witness, d_n_witness)) return RSV_E_NULL;
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP || n_queries < 1 || n_queries > RSV_MAX_QUERIES) return RSV_E_SIZE;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_int_plonk & 3) ||
-        ((uintptr_t)d_int_poseidon & 3) || ((uintptr_t)d_queries & 3) || ((uintptr_t)d_caps & 3) || ((uintptr_t)d_values & 3) ||
-        ((uintptr_t)d_n_values & 3) || ((uintptr_t)d_witness & 3) || ((uintptr_t)d_n_witness & 3))
-        return RSV_E_SIZE;
+    if (chain_misaligned(a, d_queries, d_caps, d_values, d_n_values, d_witness, d_n_witness)) return RSV_E_SIZE;
     ChainTrees ct;
-    int rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, log_blowup, &ct);
+    int rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
-    const rsv_commit_group* trees[3] = {ct.t0, ct.t1, ct.t2};
-    const size_t ngs[3] = {4, 2, 2};
     uint32_t top;
     size_t vcap[3], wcap, vall = 0;
     for (int t = 0; t < 3; t++) {
-        decommit_caps(trees[t], ngs[t], log_blowup, n_queries, &top, &vcap[t], &wcap);
+        decommit_caps(ct.tree(t), CHAIN_TREE_GROUPS[t], log_blowup, n_queries, &top, &vcap[t], &wcap);
         vall += vcap[t];
     }
     const uint64_t cap1 = (uint64_t)16 << log_blowup;
     size_t voff = 0;
     for (int t = 0; t < 3; t++) {
-        rc = decommit_tree(c, trees[t], ngs[t], n, log_blowup, d_ok ? d_ok : d_accept, d_queries, n_queries,
+        rc = decommit_tree(c, ct.tree(t), CHAIN_TREE_GROUPS[t], n, log_blowup, ct.mask, d_queries, n_queries,
                            d_caps ? RSV_CAP_READ : RSV_CAP_NONE, d_caps ? const_cast<uint32_t*>(d_caps) + t * cap1 : nullptr, 3 * cap1,
                            d_values + voff, vall, d_n_values + t, d_witness + t * wcap * 8, 3 * wcap * 8, d_n_witness + t, 3);
         if (rc != RSV_OK) return rc;

@@ -388,13 +388,10 @@ int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint3
                         uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
                         const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots,
                         uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_int_plonk || !d_int_poseidon || !d_accept || !d_comp || !d_oods || !d_samples ||
-        !d_samples3 || !d_channel || !d_after || !d_quot || !d_roots || !d_alphas || !d_last_poly || !d_low_degree)
+    const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup};
+    if (chain_null(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_last_poly, d_low_degree))
         return RSV_E_NULL;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_int_plonk & 3) ||
-        ((uintptr_t)d_int_poseidon & 3) || ((uintptr_t)d_comp & 3) || ((uintptr_t)d_oods & 3) || ((uintptr_t)d_samples & 3) ||
-        ((uintptr_t)d_samples3 & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_after & 3) || ((uintptr_t)d_quot & 3) ||
-        ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) || ((uintptr_t)d_last_poly & 3))
+    if (chain_misaligned(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly))
         return RSV_E_SIZE;
     if (prog->gates.empty()) return RSV_E_SIZE;  // built programs only
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
@@ -404,22 +401,20 @@ int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint3
     if (rc != RSV_OK) return rc;
     if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
     ChainTrees ct;
-    rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, log_blowup, &ct);
+    rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
-    const uint8_t* mask = d_ok ? d_ok : d_accept;
+    const uint8_t* mask = ct.mask;
     rc = ensure_buf(c, &c->ws_fri, &c->ws_fri_bytes, n * 24 * 4);
     if (rc != RSV_OK) return rc;
     uint32_t* pts = static_cast<uint32_t*>(c->ws_fri);
     hipLaunchKernelGGL(rsv::k_fr_begin, dim3(grid_for(n, 64)), dim3(64), 0, c->stream, d_samples, d_samples3, d_oods, mask, lp, lq, (uint32_t)n,
                        d_channel, d_after, pts);
-    // The quotient columns' groups: tree 3, then per tree the Plonk groups and the Poseidon groups (one column where the
-    // sizes are equal).  The interaction groups are cut into columns 0..3 (one sample) and the cumulative 4..7 (two: the
-    // proof's order has the previous-row value first).  Points: 0 the OODS point, 1 and 2 it minus the step of lp / lq.
-    const size_t Np = (size_t)1 << lp, Nq = (size_t)1 << lq;
+    // The quotient columns' groups: tree 3, then the groups of CHAIN_SAMPLES (per tree the Plonk groups and the Poseidon
+    // groups: one column where the sizes are equal).  Points: 0 the OODS point, 1 and 2 it minus the step of lp / lq.
     rsv_commit_group g[rsv::FR_MAX_GROUPS];
     FrSpec fs[rsv::FR_MAX_GROUPS] = {};
     size_t ng = 0;
-    auto add = [&](const rsv_commit_group& grp, const uint32_t* samples, uint64_t sstride, uint32_t entry, uint32_t step, int prev_point) {
+    auto add = [&](const rsv_commit_group& grp, const uint32_t* samples, uint64_t sstride, uint32_t entry, uint32_t step, uint32_t prev_point) {
         g[ng] = grp;
         fs[ng].samples = samples;
         fs[ng].sstride = sstride;
@@ -436,20 +431,11 @@ int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint3
     };
     const uint32_t L3 = co_clb(lp, lq) - 1;
     add({L3, 8, d_comp, (uint64_t)8 << L3, nullptr, nullptr}, d_samples3, 32, 0, 1, 0);
-    auto half = [](const rsv_commit_group& t, size_t rows, uint32_t first) {
-        return rsv_commit_group{t.log_size, 4, t.d_cols + first * rows, t.proof_stride, nullptr, nullptr};
-    };
-    // tree 0: the Plonk columns 0..9 (three groups), the Poseidon columns 10..49; tree 1: 50..61, 62..109; tree 2: 110.., 122..
-    add(ct.t0[0], d_samples, 134 * 4, 0, 1, 0);
-    add(ct.t0[1], d_samples, 134 * 4, 3, 1, 0);
-    add(ct.t0[2], d_samples, 134 * 4, 4, 1, 0);
-    add(ct.t0[3], d_samples, 134 * 4, 10, 1, 0);
-    add(ct.t1[0], d_samples, 134 * 4, 50, 1, 0);
-    add(ct.t1[1], d_samples, 134 * 4, 62, 1, 0);
-    add(half(ct.t2[0], Np, 0), d_samples, 134 * 4, 110, 1, 0);
-    add(half(ct.t2[0], Np, 4), d_samples, 134 * 4, 115, 2, 1);
-    add(half(ct.t2[1], Nq, 0), d_samples, 134 * 4, 122, 1, 0);
-    add(half(ct.t2[1], Nq, 4), d_samples, 134 * 4, 127, 2, 2);
+    for (const ChainSamples& s : CHAIN_SAMPLES) {
+        const rsv_commit_group& t = ct.tree(s.tree)[s.group];
+        add({t.log_size, s.cols, t.d_cols + ((size_t)s.col0 << t.log_size), t.proof_stride, nullptr, nullptr}, d_samples,
+            CHAIN_SAMPLE_VALUES * 4, s.entry, s.step, s.prev_point);
+    }
     rc = fri_quotients(c, g, fs, ng, n, log_blowup, mask, RSV_SAMPLE_COLUMNS, pts, 3, d_after, d_quot);
     if (rc != RSV_OK) return rc;
     return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);

@@ -137,32 +137,24 @@ int rsv_sample_tree_dev(rsv_ctx* c, const rsv_commit_group* groups, size_t n_gro
 int rsv_witness_sample_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                            const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
                            const uint8_t* d_ok, size_t n, const uint32_t* d_oods, uint32_t* d_samples) {
-    if (!c || !prog || !d_plonk || !d_poseidon || !d_int_plonk || !d_int_poseidon || !d_accept || !d_oods || !d_samples) return RSV_E_NULL;
-    if (((uintptr_t)d_plonk & 3) || ((uintptr_t)d_poseidon & 3) || ((uintptr_t)d_ops & 3) || ((uintptr_t)d_int_plonk & 3) ||
-        ((uintptr_t)d_int_poseidon & 3) || ((uintptr_t)d_oods & 3) || ((uintptr_t)d_samples & 3))
-        return RSV_E_SIZE;
+    const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, 0};
+    if (chain_null(a, d_oods, d_samples)) return RSV_E_NULL;
+    if (chain_misaligned(a, d_oods, d_samples)) return RSV_E_SIZE;
     ChainTrees ct;
-    int rc = chain_trees(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, n, 0, &ct);
+    int rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
-    const rsv_commit_group* trees[3] = {ct.t0, ct.t1, ct.t2};
-    const size_t ngs[3] = {4, 2, 2};
-    const uint8_t* mask = d_ok ? d_ok : d_accept;
-    const uint64_t stride = 134 * 4;  // the proof's sampled_values[0..2]: 50 + 60 + 24 values
-    uint32_t entry = 0;
+    // One call per tree.  A group that CHAIN_SAMPLES cuts is sampled whole at two points: its first columns take the OODS
+    // value alone, the cumulative ones the previous-row value and then the OODS value.  That is the table's row of the
+    // cumulative half (entry + cols + 1, step 2: the table's static_assert), so the row itself has nothing left to place.
+    SpGroup sg[3][4];
+    for (const ChainSamples& s : CHAIN_SAMPLES) {
+        if (s.col0) continue;
+        const rsv_commit_group& g = ct.tree(s.tree)[s.group];
+        const bool cut = s.cols < g.n_cols;
+        sg[s.tree][s.group] = {{d_oods, 1, cut ? g.log_size : 0}, cut ? 2u : 1u, {d_samples, CHAIN_SAMPLE_VALUES * 4, s.entry, 0, cut ? s.cols : 0, 1}};
+    }
     for (int t = 0; t < 3; t++) {
-        SpGroup sg[4];
-        for (size_t i = 0; i < ngs[t]; i++) {
-            const uint32_t cols = trees[t][i].n_cols;
-            if (t < 2) {
-                sg[i] = {{d_oods, 1, 0}, 1, {d_samples, stride, entry, 0, 0, 1}};
-                entry += cols;
-            } else {
-                // columns 0..3: the OODS point; the cumulative columns 4..7: the previous-row point, then the OODS point
-                sg[i] = {{d_oods, 1, trees[t][i].log_size}, 2, {d_samples, stride, entry, 0, 4, 1}};
-                entry += 4 + (cols - 4) * 2;
-            }
-        }
-        rc = sample_groups(c, trees[t], ngs[t], n, mask, RSV_SAMPLE_COLUMNS, sg);
+        rc = sample_groups(c, ct.tree(t), CHAIN_TREE_GROUPS[t], n, ct.mask, RSV_SAMPLE_COLUMNS, sg[t]);
         if (rc != RSV_OK) return rc;
     }
     return RSV_OK;

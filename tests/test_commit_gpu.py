@@ -10,53 +10,11 @@ import pytest
 from tests import commit_ref as C
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
+from tests.chain_harness import CASES, DEV, chain, inputs_of, mask_dev, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_trace_gpu import _inputs, _walks
-from tests.test_trace_host import _pins
 
 pytestmark = pytest.mark.gpu
 P = C.P
-DEV = "cuda:0"
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _program(rsv, pin):
-    src = pin["src"]
-    return rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=pin["multiplier"], set_walks=_walks(pin))
-
-
-def _chain(rsv, ctx, wp, batch, inputs, b):
-    """Context.witness -> witness_trace -> witness_commit on tensors in HBM, every output prefilled with -1 -> dict of numpy."""
-    import torch
-    dev = torch.device(DEV)
-    n = len(batch)
-    lp, lq = wp.trace_sizes()
-    F = wp.shape.flow_count
-    n_ops = len(wp.gates()[1])
-    blob, offsets = rsv.pack(batch)
-    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_vars = torch.zeros((n, wp.n_vars, 4), dtype=torch.int32, device=dev)
-    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
-    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
-    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ctx.witness(wp, d_blob, d_off, n, d_vars, d_acc, inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
-    d_plonk = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
-    d_pos = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
-    d_ops = torch.zeros((n, max(n_ops, 1)), dtype=torch.int32, device=dev)
-    ctx.witness_trace(wp, d_vars, d_acc, n, d_plonk=d_plonk, d_poseidon=d_pos, d_ops=d_ops, d_flow=d_flow, d_flow_swap=d_swap)
-    full = lambda shape: torch.full(shape, -1, dtype=torch.int32, device=dev)  # noqa: E731
-    out = {"roots": full((n, 3, 8)), "draws": full((n, 12)), "ip": full((n, 8, 1 << lp)), "iq": full((n, 8, 1 << lq)), "sums": full((n, 2, 4)),
-           "chan": full((n, 16))}
-    d_ok = torch.full((n,), 7, dtype=torch.uint8, device=dev)
-    ctx.witness_commit(wp, d_plonk, d_pos, d_ops, d_acc, n, b, out["roots"], out["draws"], out["ip"], out["iq"], out["sums"],
-                       d_channel=out["chan"], d_ok=d_ok)
-    ctx.synchronize()
-    res = {k: _u32(v) for k, v in out.items()}
-    res.update(ok=d_ok.cpu().numpy(), accept=d_acc.cpu().numpy(), plonk=_u32(d_plonk), poseidon=_u32(d_pos), ops=_u32(d_ops)[:, :n_ops])
-    return res
 
 
 def _want(dst):
@@ -67,35 +25,35 @@ def _want(dst):
     return d, tr
 
 
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_chain_is_what_the_next_fixture_commits(rsv, pin):
     """The library alone, with K+1's log_blowup_factor and nothing else from K+1: roots = K+1's commitments[0..2], draws =
     its (z, alpha) and random_coeff, sums = its stmt1; the channel continued with commitments[3] draws its OODS point."""
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     b = fixture_cfg(dst).log_blowup_factor
     ctx = rsv.Context(0)
-    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    r = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b).numpy()
     ctx.close()
     d, tr = _want(dst)
-    assert r["accept"][0] == 1 and r["ok"][0] == 1
+    assert r["acc"][0] == 1 and r["ok"][0] == 1
     for t in range(3):
         assert r["roots"][0, t].tolist() == [int(x) for x in d.commitments[t]], t
     assert r["draws"][0].tolist() == tr[4:16].tolist()
     assert tuple(r["sums"][0, 0].tolist()) == tuple(d.plonk_total_sum) and tuple(r["sums"][0, 1].tolist()) == tuple(d.poseidon_total_sum)
-    ch = C.Channel(ob, r["chan"][0, :8], int(r["chan"][0, 8]))
-    assert not r["chan"][0, 9:].any()
+    ch = C.Channel(ob, r["channel"][0, :8], int(r["channel"][0, 8]))
+    assert not r["channel"][0, 9:].any()
     ch.mix([int(x) for x in d.commitments[3]])
     assert list(ch.draw()[0]) == tr[16:20].tolist()
     wp.close()
 
 
 def test_host_form_equals_the_device_chain(rsv):
-    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == "level9-1.bin")
+    wp = program_of(rsv, pin)
     src, dst = pin["src"], pin["dst"]
     b = fixture_cfg(dst).log_blowup_factor
-    roots, draws, sums, ok, accept, _ = rsv.witness_commit([read_proof(src)], wp, b, _inputs(src))
+    roots, draws, sums, ok, accept, _ = rsv.witness_commit([read_proof(src)], wp, b, inputs_of(src))
     d, tr = _want(dst)
     assert accept.tolist() == [1] and ok.tolist() == [1]
     assert roots[0].tolist() == [[int(x) for x in d.commitments[t]] for t in range(3)]
@@ -111,7 +69,7 @@ def _trees(wp, r, k):
     ppre = ppre.copy()
     if len(wops):
         ppre[3, wops[:, 0]] = r["ops"][k]
-    return [[(lp, ppre), (lq, qpre)], [(lp, r["plonk"][k]), (lq, r["poseidon"][k])], [(lp, r["ip"][k]), (lq, r["iq"][k])]]
+    return [[(lp, ppre), (lq, qpre)], [(lp, r["plonk"][k]), (lq, r["poseidon"][k])], [(lp, r["int_plonk"][k]), (lq, r["int_poseidon"][k])]]
 
 
 def _commit_dev(rsv, ctx, groups, b, n=1, coeffs=False, lde=False, mask=None, shared=()):
@@ -134,22 +92,22 @@ def _commit_dev(rsv, ctx, groups, b, n=1, coeffs=False, lde=False, mask=None, sh
             ld.append(g["d_lde"])
         gs.append(g)
     d_roots = torch.full((n, 8), -1, dtype=torch.int32, device=dev)
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    d_mask = mask_dev(mask)
     ctx.commit_tree(gs, n, b, d_roots, d_mask)
     ctx.synchronize()
-    return _u32(d_roots), [_u32(x) for x in cf], [_u32(x) for x in ld]
+    return u32(d_roots), [u32(x) for x in cf], [u32(x) for x in ld]
 
 
 @pytest.mark.parametrize("src", ["level2-1.bin", "level6-1.bin", "level9-1.bin"])
 def test_coefficients_give_the_sampled_values(rsv, src):
     """d_coeffs of the three trees evaluated at K+1's OODS point (and at the previous-row point where the mask asks for it)
     = K+1's 134 sampled values of trees 0-2; the roots from rsv_commit_tree_dev = the chain's."""
-    pin = next(p for p in _pins() if p["src"] == src)
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == src)
+    wp = program_of(rsv, pin)
     dst = pin["dst"]
     b = fixture_cfg(dst).log_blowup_factor
     ctx = rsv.Context(0)
-    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    r = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b).numpy()
     d, tr = _want(dst)
     oods = (tuple(int(x) for x in tr[20:24]), tuple(int(x) for x in tr[24:28]))
     for t, groups in enumerate(_trees(wp, r, 0)):
@@ -171,14 +129,14 @@ def test_coefficients_give_the_sampled_values(rsv, src):
 @pytest.mark.parametrize("src", ["recursive_proof_16_15.bin", "level2-1.bin"])
 def test_lde_at_the_query_positions(rsv, src):
     """d_lde of the three trees at K+1's query positions = the values K+1 decommits (SinglePathMerkleProof::columns)."""
-    pin = next(p for p in _pins() if p["src"] == src)
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == src)
+    wp = program_of(rsv, pin)
     dst = pin["dst"]
     b = fixture_cfg(dst).log_blowup_factor
     ctx = rsv.Context(0)
-    r = _chain(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
+    r = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b).numpy()
     nxt = read_proof(dst)
-    cols = ob.trace_cols(nxt, _inputs(dst))
+    cols = ob.trace_cols(nxt, inputs_of(dst))
     qM, M = C.query_positions(nxt, ob)
     for t, groups in enumerate(_trees(wp, r, 0)):
         roots, _, ld = _commit_dev(rsv, ctx, groups, b, lde=True)
@@ -192,18 +150,6 @@ def test_lde_at_the_query_positions(rsv, src):
             assert got == cols[t, j, :len(got)].tolist(), (t, j)
     ctx.close()
     wp.close()
-
-
-CASES = [  # (groups as (log, cols, shared), b, n, mask)
-    ([(5, 3, False)], 1, 1, None),
-    ([(4, 2, False), (6, 9, False)], 3, 3, None),
-    ([(6, 9, False), (4, 2, False)], 2, 2, None),
-    ([(5, 4, False), (5, 12, False), (3, 1, False)], 4, 2, None),
-    ([(0, 1, False), (1, 2, False), (2, 3, False), (3, 17, False)], 5, 2, None),
-    ([(7, 8, False)], 9, 1, None),
-    ([(6, 5, True), (5, 7, False)], 2, 4, [1, 0, 1, 1]),
-    ([(3, 10, False), (2, 8, True)], 6, 5, [1, 1, 0, 1, 1]),
-]
 
 
 def _random_case(rsv, ctx, spec, b, n, mask, seed, label):
@@ -312,18 +258,18 @@ def test_workspace_cut_with_caller_owned_outputs(rsv):
 def test_mixed_batch_with_a_rejected_proof(rsv):
     """Five proofs of one shape, the third tampered (rejected): it gets zeros everywhere and d_ok = 0; every output element
     of the others is written and equals its solo run."""
-    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == "level9-1.bin")
+    wp = program_of(rsv, pin)
     src = pin["src"]
     b = fixture_cfg(pin["dst"]).log_blowup_factor
     proof = read_proof(src)
     batch = [proof, proof, ob.tamper(proof, 5), proof, proof]
     ctx = rsv.Context(0)
-    r = _chain(rsv, ctx, wp, batch, _inputs(src), b)
-    solo = _chain(rsv, ctx, wp, [proof], _inputs(src), b)
+    r = chain(rsv, ctx, wp, batch, inputs_of(src), b).numpy()
+    solo = chain(rsv, ctx, wp, [proof], inputs_of(src), b).numpy()
     ctx.close()
-    assert r["accept"].tolist() == [1, 1, 0, 1, 1] and r["ok"].tolist() == [1, 1, 0, 1, 1]
-    for key in ("roots", "draws", "ip", "iq", "sums", "chan"):
+    assert r["acc"].tolist() == [1, 1, 0, 1, 1] and r["ok"].tolist() == [1, 1, 0, 1, 1]
+    for key in ("roots", "draws", "int_plonk", "int_poseidon", "sums", "channel"):
         assert not r[key][2].any(), key
         for k in (0, 1, 3, 4):
             assert np.array_equal(r[key][k], solo[key][0]), (key, k)
@@ -335,20 +281,20 @@ def test_chain_under_a_small_workspace_budget(rsv):
     budget: each of the three commit_tree calls keeps its five proofs but cuts its 256 blocks into passes of nb = 2 (trees 0
     and 1) or nb = 4 (tree 2, about 16 MB of coefficients + 31 MB per block), with d_accept, then ok, as the mask.  Every
     output, ok included, is bit-identical to the default-budget run."""
-    pin = next(p for p in _pins() if p["src"] == "level9-1.bin")
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == "level9-1.bin")
+    wp = program_of(rsv, pin)
     src = pin["src"]
     b = fixture_cfg(pin["dst"]).log_blowup_factor
     assert wp.trace_sizes() == (16, 15) and b == 8
     proof = read_proof(src)
     batch = [proof, proof, ob.tamper(proof, 5), proof, proof]
     ctx = rsv.Context(0)
-    whole = _chain(rsv, ctx, wp, batch, _inputs(src), b)
+    whole = chain(rsv, ctx, wp, batch, inputs_of(src), b).numpy()
     ctx.set_option("ws_budget_mb", 200)
-    cut = _chain(rsv, ctx, wp, batch, _inputs(src), b)
+    cut = chain(rsv, ctx, wp, batch, inputs_of(src), b).numpy()
     ctx.close()
     assert whole["ok"].tolist() == [1, 1, 0, 1, 1]
-    for key in ("roots", "draws", "ip", "iq", "sums", "chan", "ok"):
+    for key in ("roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok"):
         assert np.array_equal(cut[key], whole[key]), key
     assert not whole["roots"][2].any() and whole["roots"][0].any()
     wp.close()

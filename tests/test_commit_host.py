@@ -12,15 +12,14 @@ from tests import commit_ref as C
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_interaction_host import _oracle_columns
-from tests.test_trace_gpu import _inputs
+from tests.chain_harness import inputs_of, oracle_columns
 
 P = C.P
 
 
 def test_restatement_reproduces_the_next_fixture():
     from oracle import recursion_circuit as rc
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns("recursive_proof_16_15.bin")
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns("recursive_proof_16_15.bin")
     nxt = read_proof(dst)
     b = fixture_cfg(dst).log_blowup_factor
     d = rc.parse_proof(nxt)
@@ -28,7 +27,7 @@ def test_restatement_reproduces_the_next_fixture():
     z, alpha = tuple(int(x) for x in tr[4:8]), tuple(int(x) for x in tr[8:12])
     # the draws come from the restated roots: tree 2 needs (z, alpha) only through them
     roots = []
-    cols = ob.trace_cols(nxt, _inputs(dst))
+    cols = ob.trace_cols(nxt, inputs_of(dst))
     qM, M = C.query_positions(nxt, ob)
     trees = [[(lp, ppre), (lq, qpre)], [(lp, ptr), (lq, qtr)], None]
     for t in range(3):

@@ -11,62 +11,11 @@ import pytest
 from tests import commit_ref as C
 from tests import composition_ref as K
 from tests import oracle_binding as ob
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, next_samples, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_commit_gpu import _program
-from tests.test_decommit_gpu import _chain_dev
-from tests.test_sample_gpu import _next_samples, _witness_sample
-from tests.test_trace_gpu import _inputs
-from tests.test_trace_host import _pins
 
 pytestmark = pytest.mark.gpu
 P = C.P
-DEV = "cuda:0"
-FILL = -1
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.int64) % (1 << 32), dtype=np.uint32).view(np.int32)).to(torch.device(DEV))
-
-
-def _full(shape):
-    import torch
-    return torch.full(shape, FILL, dtype=torch.int32, device=torch.device(DEV))
-
-
-class _WithChannel:
-    """The context _chain_dev drives, with witness_commit also leaving d_channel."""
-
-    def __init__(self, ctx, chan):
-        self._ctx, self._chan = ctx, chan
-
-    def __getattr__(self, name):
-        return getattr(self._ctx, name)
-
-    def witness_commit(self, *a, **kw):
-        return self._ctx.witness_commit(*a, d_channel=self._chan, **kw)
-
-
-def _tree3(rsv, ctx, wp, batch, inputs, b, cap=False):
-    """_chain_dev, then Context.witness_tree3 -> (the chain's tensors, dict of numpy outputs)."""
-    n = len(batch)
-    chan = _full((n, 16))
-    t = _chain_dev(rsv, _WithChannel(ctx, chan), wp, batch, inputs, b, caps=False)
-    lp, lq = wp.trace_sizes()
-    L3 = rsv.composition_log_size(lp, lq)
-    out = {"comp": _full((n, 8, 1 << L3)), "root": _full((n, 8)), "oods": _full((n, 8)), "samples": _full((n, 8, 4)),
-           "cap": _full((n, 2 << b, 8)) if cap else None}
-    ctx.witness_tree3(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, b, t["sums"], t["draws"], chan, out["comp"],
-                      out["root"], out["oods"], out["samples"], d_ok=t["ok"], d_cap3=out["cap"])
-    ctx.synchronize()
-    res = {k: _u32(v) for k, v in out.items() if v is not None}
-    res["chan"] = _u32(chan)
-    t["comp"] = out["comp"]
-    return t, res
 
 
 def _want3(dst):
@@ -83,46 +32,48 @@ def _want3(dst):
 ROUND_TRIP = "level2-1.bin"  # the one pair whose OODS point is fed back into witness_sample (test_sample_gpu.py pins the rest)
 
 
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_chain_gives_what_the_next_fixture_carries(rsv, pin):
     """witness_tree3 of fixture K: K+1's commitments[3], its OODS point (transcript_raw words 20..27) and its
     sampled_values[3]; for one pair, witness_sample fed with the returned d_oods gives K+1's other 134 values."""
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     b = fixture_cfg(dst).log_blowup_factor
     root, oods, samples = _want3(dst)
     ctx = rsv.Context(0)
-    t, got = _tree3(rsv, ctx, wp, [read_proof(src)], _inputs(src), b)
-    assert t["ok"].cpu().tolist() == [1]
-    assert np.array_equal(got["root"][0], root)
+    ch = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b, upto="tree3")
+    got = ch.numpy()
+    assert got["ok"].tolist() == [1]
+    assert np.array_equal(got["root3"][0], root)
     assert np.array_equal(got["oods"][0], oods)
-    assert np.array_equal(got["samples"][0], samples)
+    assert np.array_equal(got["samples3"][0], samples)
     if src == ROUND_TRIP:
-        want, _ = _next_samples(dst)
-        assert np.array_equal(_witness_sample(ctx, wp, t, 1, got["oods"])[0], want)
+        want, _ = next_samples(dst)
+        ch.sample()
+        assert np.array_equal(ch.numpy()["samples"][0], want)
     ctx.close()
     wp.close()
 
 
 def test_batch_with_a_rejected_proof(rsv):
     """Three proofs, the middle one tampered: zeros everywhere for it, the solo values for the other two."""
-    pin = next(p for p in _pins() if p["src"] == ROUND_TRIP)
+    pin = next(p for p in pins() if p["src"] == ROUND_TRIP)
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     b = fixture_cfg(dst).log_blowup_factor
     root, oods, samples = _want3(dst)
     proof = read_proof(src)
     ctx = rsv.Context(0)
-    t, solo = _tree3(rsv, ctx, wp, [proof], _inputs(src), b, cap=True)
-    t, got = _tree3(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], _inputs(src), b, cap=True)
+    solo = chain(rsv, ctx, wp, [proof], inputs_of(src), b, upto="tree3", caps=True).numpy()
+    got = chain(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], inputs_of(src), b, upto="tree3", caps=True).numpy()
     ctx.close()
     wp.close()
-    assert t["ok"].cpu().tolist() == [1, 0, 1]
-    for k in ("comp", "root", "oods", "samples", "cap", "chan"):
+    assert got["ok"].tolist() == [1, 0, 1]
+    for k in ("comp", "root3", "oods", "samples3", "cap3", "channel"):
         assert np.array_equal(got[k][0], solo[k][0]) and np.array_equal(got[k][2], solo[k][0]), k
         assert not got[k][1].any(), k
-    assert np.array_equal(solo["root"][0], root) and np.array_equal(solo["oods"][0], oods) and np.array_equal(solo["samples"][0], samples)
-    assert np.array_equal(solo["cap"][0, 1], root) and not solo["cap"][0, 0].any()
+    assert np.array_equal(solo["root3"][0], root) and np.array_equal(solo["oods"][0], oods) and np.array_equal(solo["samples3"][0], samples)
+    assert np.array_equal(solo["cap3"][0, 1], root) and not solo["cap3"][0, 0].any()
 
 
 # ---------------------------------------------------------------- rsv_composition_dev on random columns
@@ -135,17 +86,17 @@ def _random_inputs(rng, lp, lq, n, shared, value=None):
 
 
 def _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask=None, coeffs=True, shared=False):
-    import torch
     L3 = rsv.composition_log_size(lp, lq)
-    d_comp = _full((n, 8, 1 << L3))
-    d_co = _full((n, 8, 1 << L3)) if coeffs else None
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(torch.device(DEV))
-    dp, dq = [_dev(c) for c in plonk], [_dev(c) for c in poseidon]
+    d_comp = full((n, 8, 1 << L3))
+    d_co = full((n, 8, 1 << L3)) if coeffs else None
+    d_mask = mask_dev(mask)
+    dp, dq = [dev(c) for c in plonk], [dev(c) for c in poseidon]
     if shared:
         dp[0], dq[0] = dp[0][0], dq[0][0]  # [cols, 2^log]: proof stride 0
-    ctx.composition(lp, lq, dp, dq, _dev(sums), _dev(draws), n, d_comp, d_co, d_mask=d_mask)
+    d_sums, d_draws = dev(sums), dev(draws)
+    ctx.composition(lp, lq, dp, dq, d_sums, d_draws, n, d_comp, d_co, d_mask=d_mask)
     ctx.synchronize()
-    return _u32(d_comp), (_u32(d_co) if coeffs else None), (d_comp, d_co)
+    return u32(d_comp), (u32(d_co) if coeffs else None), (d_comp, d_co)
 
 
 def _ref(plonk, poseidon, lp, lq, sums, draws, p):
@@ -192,13 +143,13 @@ def test_coefficients_sample_as_the_columns(rsv):
     ctx = rsv.Context(0)
     _, _, (d_comp, d_co) = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n)
     L3 = rsv.composition_log_size(lp, lq)
-    pts = _dev(rng.integers(0, P, (n, 2, 8)))
-    a, c = _full((n, 2, 8, 4)), _full((n, 2, 8, 4))
+    pts = dev(rng.integers(0, P, (n, 2, 8)))
+    a, c = full((n, 2, 8, 4)), full((n, 2, 8, 4))
     ctx.sample_tree([{"log_size": L3, "d_cols": d_comp, "n_cols": 8}], n, pts, 2, a, source=rsv.SAMPLE_COLUMNS)
     ctx.sample_tree([{"log_size": L3, "d_cols": d_co, "n_cols": 8}], n, pts, 2, c, source=rsv.SAMPLE_COEFFS)
     ctx.synchronize()
     ctx.close()
-    assert np.array_equal(_u32(a), _u32(c)) and _u32(a).any() and not (_u32(a) == 0xFFFFFFFF).any()
+    assert np.array_equal(u32(a), u32(c)) and u32(a).any() and not (u32(a) == 0xFFFFFFFF).any()
 
 
 def _pass_size(lp, lq, n, shared, budget, coeffs):

@@ -21,8 +21,7 @@ from tests import composition_ref as K
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_interaction_host import _oracle_columns
-from tests.test_trace_gpu import _inputs
+from tests.chain_harness import inputs_of, oracle_columns
 
 P = C.P
 
@@ -36,7 +35,7 @@ def _point(N, pos, minus_step_of=None):
 
 
 def test_restatement_reproduces_the_next_fixture():
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns("recursive_proof_16_15.bin")
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns("recursive_proof_16_15.bin")
     nxt = read_proof(dst)
     b = fixture_cfg(dst).log_blowup_factor
     tr = ob.transcript_raw(nxt)
@@ -47,7 +46,7 @@ def test_restatement_reproduces_the_next_fixture():
     L3 = clb - 1
     qM, M = C.query_positions(nxt, ob)
     assert M == L3 + b  # tree 3 is the largest layer: a query position is its own
-    queried = ob.trace_cols(nxt, _inputs(dst))
+    queried = ob.trace_cols(nxt, inputs_of(dst))
     plonk = [C.interpolate(c, lp) for c in (ppre, ptr, cp)]
     poseidon = [C.interpolate(c, lq) for c in (qpre, qtr, cq)]
     for j in (0, 1, len(qM) - 1):

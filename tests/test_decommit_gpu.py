@@ -10,63 +10,22 @@ import pytest
 from tests import commit_ref as C
 from tests import decommit_ref as D
 from tests import oracle_binding as ob
+from tests.chain_harness import CASES, DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_commit_gpu import CASES, _program
-from tests.test_trace_gpu import _inputs
-from tests.test_trace_host import _pins
 
 pytestmark = pytest.mark.gpu
 P = C.P
-DEV = "cuda:0"
-FILL = -1  # every output is prefilled with 0xffffffff: what a call leaves undefined shows
 
 
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _chain_dev(rsv, ctx, wp, batch, inputs, b, caps):
-    """Context.witness -> witness_trace -> witness_commit(d_caps=) -> the device tensors witness_decommit takes."""
-    import torch
-    dev = torch.device(DEV)
-    n = len(batch)
-    lp, lq = wp.trace_sizes()
-    F = wp.shape.flow_count
-    n_ops = len(wp.gates()[1])
-    blob, offsets = rsv.pack(batch)
-    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_vars = torch.zeros((n, wp.n_vars, 4), dtype=torch.int32, device=dev)
-    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
-    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
-    t = {"acc": torch.zeros(n, dtype=torch.uint8, device=dev)}
-    ctx.witness(wp, d_blob, d_off, n, d_vars, t["acc"], inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
-    t["plonk"] = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
-    t["pos"] = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
-    t["ops"] = torch.zeros((n, max(n_ops, 1)), dtype=torch.int32, device=dev)
-    ctx.witness_trace(wp, d_vars, t["acc"], n, d_plonk=t["plonk"], d_poseidon=t["pos"], d_ops=t["ops"], d_flow=d_flow, d_flow_swap=d_swap)
-    full = lambda shape: torch.full(shape, FILL, dtype=torch.int32, device=dev)  # noqa: E731
-    t.update(roots=full((n, 3, 8)), draws=full((n, 12)), ip=full((n, 8, 1 << lp)), iq=full((n, 8, 1 << lq)), sums=full((n, 2, 4)),
-             ok=torch.full((n,), 7, dtype=torch.uint8, device=dev), caps=full((n, 3, 2 << b, 8)) if caps else None)
-    ctx.witness_commit(wp, t["plonk"], t["pos"], t["ops"], t["acc"], n, b, t["roots"], t["draws"], t["ip"], t["iq"], t["sums"], d_ok=t["ok"],
-                       d_caps=t["caps"])
-    return t
-
-
-def _witness_decommit(rsv, ctx, wp, t, n, b, queries, caps):
-    """Context.witness_decommit -> per proof and tree (values, witness) cut at the counts; the words past them are zero."""
-    import torch
-    dev = torch.device(DEV)
-    nq = queries.shape[1]
-    vcaps, wcap = rsv.witness_decommit_sizes(wp, b, nq)
-    d_q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.uint32).view(np.int32)).to(dev)
-    d_v = torch.full((n, sum(vcaps)), FILL, dtype=torch.int32, device=dev)
-    d_w = torch.full((n, 3, wcap, 8), FILL, dtype=torch.int32, device=dev)
-    d_nv = torch.full((n, 3), FILL, dtype=torch.int32, device=dev)
-    d_nw = torch.full((n, 3), FILL, dtype=torch.int32, device=dev)
-    ctx.witness_decommit(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, b, d_q, nq, d_v, d_nv, d_w, d_nw, d_ok=t["ok"],
-                         d_caps=t["caps"] if caps else None)
-    ctx.synchronize()
-    v, w, nv, nw = _u32(d_v), _u32(d_w), _u32(d_nv), _u32(d_nw)
+def _witness_decommit(rsv, ch, queries, caps):
+    """Chain.decommit -> per proof and tree (values, witness) cut at the counts; the words past them are zero."""
+    n = ch.n
+    vcaps, wcap = rsv.witness_decommit_sizes(ch.program, ch.log_blowup, queries.shape[1])
+    d_v, d_w, d_nv, d_nw = full((n, sum(vcaps))), full((n, 3, wcap, 8)), full((n, 3)), full((n, 3))
+    d_q = dev(queries)
+    ch.decommit(d_q, d_v, d_nv, d_w, d_nw, caps=caps)
+    ch.ctx.synchronize()
+    v, w, nv, nw = u32(d_v), u32(d_w), u32(d_nv), u32(d_nw)
     out = []
     for p in range(n):
         off, per = 0, []
@@ -80,13 +39,13 @@ def _witness_decommit(rsv, ctx, wp, t, n, b, queries, caps):
     return out
 
 
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_chain_opens_what_the_next_fixture_decommits(rsv, pin):
     """The library alone, with K+1's log_blowup_factor, n_queries and query positions and nothing else from K+1: for t = 0,
     1, 2 the values and witness nodes are K+1's queried_values[t] and hash_witness[t], in count and word for word, and zero
     past the counts; the call without caps gives identical outputs."""
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     cfg = fixture_cfg(dst)
     b = cfg.log_blowup_factor
     nxt = read_proof(dst)
@@ -95,9 +54,9 @@ def test_chain_opens_what_the_next_fixture_decommits(rsv, pin):
     top = max(wp.trace_sizes()) + b
     q = (qM >> (M - top)).astype(np.uint32)[None]
     ctx = rsv.Context(0)
-    t = _chain_dev(rsv, ctx, wp, [read_proof(src)], _inputs(src), b, caps=True)
-    with_caps = _witness_decommit(rsv, ctx, wp, t, 1, b, q, caps=True)[0]
-    without = _witness_decommit(rsv, ctx, wp, t, 1, b, q, caps=False)[0]
+    ch = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b, caps=True)
+    with_caps = _witness_decommit(rsv, ch, q, caps=True)[0]
+    without = _witness_decommit(rsv, ch, q, caps=False)[0]
     ctx.close()
     want = ob.split_variable_part(nxt)
     for k in range(3):
@@ -113,8 +72,8 @@ def test_chain_opens_what_the_next_fixture_decommits(rsv, pin):
 def test_chain_masked_proof_and_batch(rsv):
     """Five proofs, the third tampered (rejected), per-proof different queries: the rejected proof gets zero counts and zero
     buffers, the others what their solo run gives."""
-    pin = next(p for p in _pins() if p["src"] == "recursive_proof_16_15.bin")
-    wp = _program(rsv, pin)
+    pin = next(p for p in pins() if p["src"] == "recursive_proof_16_15.bin")
+    wp = program_of(rsv, pin)
     src = pin["src"]
     b = fixture_cfg(pin["dst"]).log_blowup_factor
     proof = read_proof(src)
@@ -122,15 +81,15 @@ def test_chain_masked_proof_and_batch(rsv):
     top = max(wp.trace_sizes()) + b
     q = np.random.default_rng(5).integers(0, 1 << top, (5, 16)).astype(np.uint32)
     ctx = rsv.Context(0)
-    t = _chain_dev(rsv, ctx, wp, batch, _inputs(src), b, caps=True)
-    got = _witness_decommit(rsv, ctx, wp, t, 5, b, q, caps=True)
-    assert t["ok"].cpu().tolist() == [1, 1, 0, 1, 1]
-    s = _chain_dev(rsv, ctx, wp, [proof], _inputs(src), b, caps=True)
+    ch = chain(rsv, ctx, wp, batch, inputs_of(src), b, caps=True)
+    got = _witness_decommit(rsv, ch, q, caps=True)
+    assert ch.ok.cpu().tolist() == [1, 1, 0, 1, 1]
+    solo_ch = chain(rsv, ctx, wp, [proof], inputs_of(src), b, caps=True)
     for p in range(5):
         if p == 2:
             assert all(len(v) == 0 and len(w) == 0 for v, w in got[p])
             continue
-        solo = _witness_decommit(rsv, ctx, wp, s, 1, b, q[p:p + 1], caps=(p & 1) == 0)[0]
+        solo = _witness_decommit(rsv, solo_ch, q[p:p + 1], caps=(p & 1) == 0)[0]
         for k in range(3):
             assert np.array_equal(got[p][k][0], solo[k][0]) and np.array_equal(got[p][k][1], solo[k][1]), (p, k)
     ctx.close()
@@ -138,45 +97,33 @@ def test_chain_masked_proof_and_batch(rsv):
 
 
 def _groups_dev(groups, shared):
-    import torch
-    dev = torch.device(DEV)
     gs = []
     for i, (log, cols) in enumerate(groups):
-        cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int64) % P, dtype=np.uint32)
         nc = cols.shape[1]
-        gs.append({"log_size": log, "d_cols": torch.from_numpy(cols.view(np.int32)).to(dev), "n_cols": nc,
-                   "proof_stride": 0 if i in shared else nc << log})
+        gs.append({"log_size": log, "d_cols": dev(np.asarray(cols, dtype=np.int64) % P), "n_cols": nc, "proof_stride": 0 if i in shared else nc << log})
     return gs
 
 
 def _decommit_dev(rsv, ctx, gs, b, n, queries, mask=None, mode=0, cap=None):
     """Context.decommit_tree -> (values [n][vcap], n_values, witness [n][wcap][8], n_witness, cap tensor or None)."""
-    import torch
-    dev = torch.device(DEV)
     nq = queries.shape[1]
     vcap, wcap = rsv.decommit_sizes(gs, b, nq)
-    d_q = torch.from_numpy(np.ascontiguousarray(queries, dtype=np.uint32).view(np.int32)).to(dev)
-    d_v = torch.full((n, vcap), FILL, dtype=torch.int32, device=dev)
-    d_w = torch.full((n, wcap, 8), FILL, dtype=torch.int32, device=dev)
-    d_nv = torch.full((n,), FILL, dtype=torch.int32, device=dev)
-    d_nw = torch.full((n,), FILL, dtype=torch.int32, device=dev)
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    d_v, d_w, d_nv, d_nw = full((n, vcap)), full((n, wcap, 8)), full((n,)), full((n,))
     if mode == rsv.CAP_WRITE:
-        cap = torch.full((n, 2 << b, 8), FILL, dtype=torch.int32, device=dev)
+        cap = full((n, 2 << b, 8))
+    d_q, d_mask = dev(queries), mask_dev(mask)
     ctx.decommit_tree(gs, n, b, d_q, nq, d_v, d_nv, d_w, d_nw, d_mask=d_mask, cap_mode=mode, d_cap=cap)
     ctx.synchronize()
-    return _u32(d_v), _u32(d_nv), _u32(d_w), _u32(d_nw), cap
+    return u32(d_v), u32(d_nv), u32(d_w), u32(d_nw), cap
 
 
 def _commit_cap(rsv, ctx, gs, b, n, mask, with_cap):
-    import torch
-    dev = torch.device(DEV)
-    d_roots = torch.full((n, 8), FILL, dtype=torch.int32, device=dev)
-    d_cap = torch.full((n, 2 << b, 8), FILL, dtype=torch.int32, device=dev) if with_cap else None
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    d_roots = full((n, 8))
+    d_cap = full((n, 2 << b, 8)) if with_cap else None
+    d_mask = mask_dev(mask)
     ctx.commit_tree(gs, n, b, d_roots, d_mask, d_cap=d_cap)
     ctx.synchronize()
-    return _u32(d_roots), d_cap
+    return u32(d_roots), d_cap
 
 
 def _queries(rng, n, nq, top, b, kind):
@@ -204,7 +151,7 @@ def _check_case(rsv, ctx, spec, b, n, mask, nq, seed, kind="dup", budget_cut=Non
     roots, _ = _commit_cap(rsv, ctx, gs, b, n, mask, False)
     roots_c, cap_c = _commit_cap(rsv, ctx, gs, b, n, mask, True)
     assert np.array_equal(roots, roots_c)
-    cap_w, cap_c = _u32(write[4]), _u32(cap_c)
+    cap_w, cap_c = u32(write[4]), u32(cap_c)
     assert np.array_equal(cap_w, cap_c)
     for label, other in (("write", write), ("read", read)):
         for k in range(4):

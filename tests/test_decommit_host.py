@@ -14,13 +14,13 @@ from tests import decommit_ref as D
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_interaction_host import _oracle_columns
+from tests.chain_harness import oracle_columns
 
 P = C.P
 
 
 def test_restatement_reproduces_the_next_fixture_decommitment():
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns("recursive_proof_16_15.bin")
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns("recursive_proof_16_15.bin")
     nxt = read_proof(dst)
     b = fixture_cfg(dst).log_blowup_factor
     tr = ob.transcript_raw(nxt)

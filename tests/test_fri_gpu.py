@@ -10,39 +10,17 @@ import pytest
 from tests import commit_ref as C
 from tests import fri_ref as F
 from tests import oracle_binding as ob
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, pow_words, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_commit_gpu import _program
-from tests.test_composition_gpu import _dev, _full, _tree3, _u32
-from tests.test_fri_host import pow_words
-from tests.test_sample_gpu import _witness_sample
-from tests.test_trace_gpu import _inputs
-from tests.test_trace_host import _pins
 
 pytestmark = pytest.mark.gpu
 P = C.P
-DEV = "cuda:0"
 
 
 def _fri(rsv, ctx, wp, batch, inputs, b, log_last):
     """The chain through witness_tree3, witness_sample and witness_fri -> (ok list, dict of numpy outputs)."""
-    import torch
-    n = len(batch)
-    t, got3 = _tree3(rsv, ctx, wp, batch, inputs, b)
-    samples = _dev(_witness_sample(ctx, wp, t, n, got3["oods"]))
-    lp, lq = wp.trace_sizes()
-    sz = rsv.fri_sizes(lp, lq, b, log_last)
-    ni = sz["n_inner"]
-    chan = _dev(got3["chan"])
-    out = {"after": _full((n, 4)), "quot": _full((n, sz["quot_words"])), "roots": _full((n, 1 + ni, 8)), "alphas": _full((n, 1 + ni, 4)),
-           "layers": _full((n, max(sz["layer_words"], 1))), "last": _full((n, 1 << log_last, 4)),
-           "low": torch.full((n,), 7, dtype=torch.uint8, device=torch.device(DEV))}
-    ctx.witness_fri(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, b, log_last, t["comp"], _dev(got3["oods"]), samples,
-                    _dev(got3["samples"]), chan, out["after"], out["quot"], out["roots"], out["alphas"], out["layers"], out["last"], out["low"],
-                    d_ok=t["ok"])
-    ctx.synchronize()
-    res = {k: (v.cpu().numpy() if k == "low" else _u32(v)) for k, v in out.items()}
-    res["chan"] = _u32(chan)
-    return t["ok"].cpu().tolist(), res
+    got = chain(rsv, ctx, wp, batch, inputs, b, upto="fri", log_last=log_last).numpy()
+    return got["ok"].tolist(), got
 
 
 def _want(dst):
@@ -56,27 +34,27 @@ def _want(dst):
 def _check_against(got, k, dst):
     nxt, lay, last, tr = _want(dst)
     ni = lay["n_inner"]
-    assert got["roots"].shape[1] == 1 + ni
-    assert np.array_equal(got["roots"][k], np.array(lay["fri_commitments"], dtype=np.uint32))
-    assert np.array_equal(got["last"][k], last)
+    assert got["fri_roots"].shape[1] == 1 + ni
+    assert np.array_equal(got["fri_roots"][k], np.array(lay["fri_commitments"], dtype=np.uint32))
+    assert np.array_equal(got["last_poly"][k], last)
     assert np.array_equal(got["after"][k], tr[28:32].astype(np.uint32))
     assert np.array_equal(got["alphas"][k].reshape(-1), tr[40:40 + 4 * (1 + ni)].astype(np.uint32))
-    assert got["low"][k] == 1
-    ch = C.Channel(ob, got["chan"][k, :8], int(got["chan"][k, 8]))
+    assert got["low_degree"][k] == 1
+    ch = C.Channel(ob, got["channel"][k, :8], int(got["channel"][k, 8]))
     ch.mix_one(pow_words(nxt))
     assert np.array_equal(ch.digest, tr[32:40].astype(np.uint32))
-    assert not got["chan"][k, 9:].any()
+    assert not got["channel"][k, 9:].any()
 
 
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_chain_gives_the_next_fixtures_fri_layers(rsv, pin):
     """witness_fri of fixture K: K+1's first_layer_commitment, inner_layer_commitments (and their count), last_poly,
     `after`, the alphas, low degree, and the channel its proof of work continues from."""
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     cfg = fixture_cfg(dst)
     ctx = rsv.Context(0)
-    ok, got = _fri(rsv, ctx, wp, [read_proof(src)], _inputs(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
+    ok, got = _fri(rsv, ctx, wp, [read_proof(src)], inputs_of(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
     ctx.close()
     wp.close()
     assert ok == [1]
@@ -86,18 +64,18 @@ def test_chain_gives_the_next_fixtures_fri_layers(rsv, pin):
 
 def test_batch_with_a_rejected_proof(rsv):
     """Three proofs, the middle one tampered: zeros everywhere for it, the solo values for the other two."""
-    pin = next(p for p in _pins() if p["src"] == "level2-1.bin")
+    pin = next(p for p in pins() if p["src"] == "level2-1.bin")
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     cfg = fixture_cfg(dst)
     proof = read_proof(src)
     ctx = rsv.Context(0)
-    _, solo = _fri(rsv, ctx, wp, [proof], _inputs(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
-    ok, got = _fri(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], _inputs(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
+    _, solo = _fri(rsv, ctx, wp, [proof], inputs_of(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
+    ok, got = _fri(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], inputs_of(src), cfg.log_blowup_factor, cfg.log_last_layer_degree_bound)
     ctx.close()
     wp.close()
     assert ok == [1, 0, 1]
-    for k in ("after", "quot", "roots", "alphas", "layers", "last", "low", "chan"):
+    for k in ("after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree", "channel"):
         assert np.array_equal(got[k][0], solo[k][0]) and np.array_equal(got[k][2], solo[k][0]), k
         assert not got[k][1].any(), k
     _check_against(solo, 0, dst)
@@ -129,13 +107,14 @@ def _run_quotients(ctx, groups, gpoints, b, n, points, samples, after, mask=None
     import torch
     gs = []
     for i, (log, cols) in enumerate(groups):
-        gs.append({"log_size": log, "d_cols": _dev(cols), "n_cols": cols.shape[-2], "proof_stride": 0 if i in shared else cols.shape[-2] << log})
+        gs.append({"log_size": log, "d_cols": dev(cols), "n_cols": cols.shape[-2], "proof_stride": 0 if i in shared else cols.shape[-2] << log})
     words = sum(4 << (log + b) for log in {log for log, _ in groups})
-    d_quot = _full((n, words))
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(torch.device(DEV))
-    ctx.fri_quotients(gs, gpoints, n, b, _dev(points), points.shape[1], _dev(samples), _dev(after), d_quot, d_mask=d_mask, source=source)
+    d_quot = full((n, words))
+    d_mask = mask_dev(mask)
+    d_points, d_samples, d_after = dev(points), dev(samples), dev(after)
+    ctx.fri_quotients(gs, gpoints, n, b, d_points, points.shape[1], d_samples, d_after, d_quot, d_mask=d_mask, source=source)
     ctx.synchronize()
-    return _u32(d_quot)
+    return u32(d_quot)
 
 
 ALL = lambda nc: (0, nc)  # noqa: E731
@@ -271,17 +250,18 @@ def test_commit_bit_for_bit(rsv, case):
     ni = F.n_inner_of(sizes[0], log_last, b)
     lw = sum(4 << (sizes[0] - 1 - i) for i in range(ni))
     quot = np.stack([np.concatenate([c[s].reshape(-1) for s in sizes]) for c in cols])
-    chan = _dev(chan0)
-    out = {"roots": _full((n, 1 + ni, 8)), "alphas": _full((n, 1 + ni, 4)), "layers": _full((n, max(lw, 1))), "last": _full((n, 1 << log_last, 4)),
+    chan = dev(chan0)
+    out = {"roots": full((n, 1 + ni, 8)), "alphas": full((n, 1 + ni, 4)), "layers": full((n, max(lw, 1))), "last": full((n, 1 << log_last, 4)),
            "low": torch.full((n,), 7, dtype=torch.uint8, device=torch.device(DEV))}
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(torch.device(DEV))
+    d_mask = mask_dev(mask)
     ctx = rsv.Context(0)
-    ctx.fri_commit(_dev(quot), sizes, b, log_last, n, chan, out["roots"], out["alphas"], out["layers"] if ni else None, out["last"], out["low"],
+    d_quot = dev(quot)
+    ctx.fri_commit(d_quot, sizes, b, log_last, n, chan, out["roots"], out["alphas"], out["layers"] if ni else None, out["last"], out["low"],
                    d_mask=d_mask)
     ctx.synchronize()
     ctx.close()
-    got = {k: (v.cpu().numpy() if k == "low" else _u32(v)) for k, v in out.items()}
-    got["chan"] = _u32(chan)
+    got = {k: (v.cpu().numpy() if k == "low" else u32(v)) for k, v in out.items()}
+    got["chan"] = u32(chan)
     for p in range(n):
         if mask is not None and not mask[p]:
             for k in ("roots", "alphas", "last", "chan") + (("layers",) if ni else ()):

@@ -9,6 +9,7 @@ from tests import commit_ref as C
 from tests import fri_ref as F
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
+from tests.chain_harness import pow_words
 from tests.conftest import read_proof
 
 FIXTURE = "level1-5.bin"
@@ -159,13 +160,6 @@ def test_channel_run(proof):
     F.mix_last(ch, d["last"])
     ch.mix_one(pow_words(d["proof"]))
     assert [int(v) for v in ch.digest] == [int(v) for v in d["tr"][32:40]]
-
-
-def pow_words(proof):
-    """The proof's nonce as the transcript mixes it: 22 / 21 / 21 bits."""
-    pos = 4 * ob.proof_layout(proof)["nonce_word"]
-    n = int.from_bytes(proof[pos:pos + 8], "little")
-    return [n & ((1 << 22) - 1), (n >> 22) & ((1 << 21) - 1), (n >> 43) & ((1 << 21) - 1), 0]
 
 
 def test_fri_sizes_and_refusals(rsv):

@@ -11,14 +11,11 @@ import pytest
 
 from tests import interaction_ref as R
 from tests import oracle_binding as ob
-from tests.conftest import fixture_cfg, load_manifest, read_proof
-from tests.test_interaction_host import lookup_of, oods_of
-from tests.test_trace_gpu import _eval, _inputs, _walks, _weights
-from tests.test_trace_host import _pins
+from tests.chain_harness import chain, eval_column, full, inputs_of, lookup_of, oods_of, pin_id, pins, u32, walks_of, weights
+from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
 P = R.P
-MAN = {e["file"]: e for e in load_manifest()}
 
 
 def _balance(sums, inputs, z, alpha):
@@ -26,15 +23,15 @@ def _balance(sums, inputs, z, alpha):
     return not t.any()
 
 
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_tree2_is_what_the_next_fixture_proves(rsv, pin):
     """The library alone: program -> witness_interaction with K+1's (z, alpha) -> K+1's claimed sums, its 24 tree-2 sampled
     values, and the balance identity with the circuit's public inputs."""
     from oracle import recursion_circuit as rc
     src, mult, dst = pin["src"], pin["multiplier"], pin["dst"]
-    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=mult, set_walks=_walks(pin))
+    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), inputs_of(src), copies=mult, set_walks=walks_of(pin))
     z, alpha = lookup_of(dst)
-    ip, iq, sums, ok, accept, _ = rsv.witness_interaction([read_proof(src)], wp, (z, alpha), _inputs(src))
+    ip, iq, sums, ok, accept, _ = rsv.witness_interaction([read_proof(src)], wp, (z, alpha), inputs_of(src))
     assert accept[0] == 1 and ok[0] == 1
     d = rc.parse_proof(read_proof(dst))
     assert tuple(sums[0, 0].tolist()) == tuple(d.plonk_total_sum)
@@ -43,12 +40,12 @@ def test_tree2_is_what_the_next_fixture_proves(rsv, pin):
     oods = oods_of(dst)
     got = []
     for log, cols in ((lp, ip[0]), (lq, iq[0])):
-        w, wprev = _weights(log, oods), _weights(log, R.prev_row_point(oods, log))
+        w, wprev = weights(log, oods), weights(log, R.prev_row_point(oods, log))
         for k in range(8):
-            got.append([_eval(w, cols[k])] if k < 4 else [_eval(wprev, cols[k]), _eval(w, cols[k])])
+            got.append([eval_column(w, cols[k])] if k < 4 else [eval_column(wprev, cols[k]), eval_column(w, cols[k])])
     want = [[tuple(v) for v in col] for col in d.sampled_values[2]]
     assert got == want, [k for k in range(16) if got[k] != want[k]]
-    assert _balance(sums[0].tolist(), _inputs(dst), z, alpha)
+    assert _balance(sums[0].tolist(), inputs_of(dst), z, alpha)
     wp.close()
 
 
@@ -62,35 +59,20 @@ def _expected(rsv, wp, plonk, poseidon, z, alpha):
 
 
 def _device(rsv, ctx, wp, batch, inputs, lookup, layout):
-    """Context.witness -> witness_trace -> witness_interaction on tensors in HBM (outputs filled with -1 first: every element
-    must be written) -> numpy int_plonk, int_poseidon, sums, ok, accept, plonk trace, poseidon trace."""
+    """The chain through Context.witness_trace, then Context.witness_interaction on tensors in HBM (outputs prefilled: every
+    element must be written) -> numpy int_plonk, int_poseidon, sums, ok, accept, plonk trace, poseidon trace."""
     import torch
-    dev = torch.device("cuda:0")
     n = len(batch)
-    lp, lq = wp.trace_sizes()
-    F = wp.shape.flow_count
-    blob, offsets = rsv.pack(batch)
-    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
     ctx.set_option("witness_layout", layout)
-    shape = (wp.n_vars, n, 4) if layout == "by_variable" else (n, wp.n_vars, 4)
-    d_vars = torch.zeros(shape, dtype=torch.int32, device=dev)
-    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
-    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
-    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ctx.witness(wp, d_blob, d_off, n, d_vars, d_acc, inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
-    d_plonk = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
-    d_pos = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
-    ctx.witness_trace(wp, d_vars, d_acc, n, d_plonk=d_plonk, d_poseidon=d_pos, d_flow=d_flow, d_flow_swap=d_swap)
-    d_lookup = torch.from_numpy(rsv._lookup_array(lookup, n).view(np.int32)).to(dev)
-    d_ip = torch.full((n, 8, 1 << lp), -1, dtype=torch.int32, device=dev)
-    d_iq = torch.full((n, 8, 1 << lq), -1, dtype=torch.int32, device=dev)
-    d_sums = torch.full((n, 2, 4), -1, dtype=torch.int32, device=dev)
-    d_ok = torch.full((n,), 7, dtype=torch.uint8, device=dev)
-    ctx.witness_interaction(wp, d_plonk, d_pos, d_acc, d_lookup, n, d_ip, d_iq, d_sums, d_ok)
-    ctx.synchronize()
-    get = lambda t: t.cpu().numpy().view(np.uint32)
+    ch = chain(rsv, ctx, wp, batch, inputs, 1, upto="trace", by_variable=layout == "by_variable")
+    lp, lq = wp.trace_sizes()
+    d_lookup = torch.from_numpy(rsv._lookup_array(lookup, n).view(np.int32)).to(ch.device)
+    d_ip, d_iq, d_sums = full((n, 8, 1 << lp)), full((n, 8, 1 << lq)), full((n, 2, 4))
+    d_ok = torch.full((n,), 7, dtype=torch.uint8, device=ch.device)
+    ctx.witness_interaction(wp, ch.plonk, ch.poseidon, ch.acc, d_lookup, n, d_ip, d_iq, d_sums, d_ok)
+    got = ch.numpy()
     ctx.set_option("witness_layout", "by_proof")
-    return get(d_ip), get(d_iq), get(d_sums), d_ok.cpu().numpy(), d_acc.cpu().numpy(), get(d_plonk), get(d_pos)
+    return u32(d_ip), u32(d_iq), u32(d_sums), d_ok.cpu().numpy(), got["acc"], got["plonk"], got["poseidon"]
 
 
 def _random_lookup(rng, n):
@@ -113,7 +95,7 @@ def test_mixed_batch_bit_for_bit(rsv):
     plonk, poseidon, _, acc2, _ = rsv.witness_trace([read_proof("level10-1.bin"), read_proof("level11-1.bin")], wp)
     assert acc2.tolist() == [1, 1]
     trace = {"level10-1.bin": (plonk[0], poseidon[0]), "level11-1.bin": (plonk[1], poseidon[1])}
-    inputs = _inputs("level11-1.bin")
+    inputs = inputs_of("level11-1.bin")
     for k, nm in enumerate(names):
         if k in rejected:
             assert not ip[k].any() and not iq[k].any() and not sums[k].any(), k
@@ -179,21 +161,21 @@ def _device_trace_poseidon(rsv, wp, proof):
 def test_five_copies_batch(rsv):
     """A copies = 5 program (2^19 Plonk, 2^18 Poseidon rows): a device batch with a rejected proof equals the restatement on
     its own trace columns for the accepted ones, and zero for the rejected one."""
-    pin = next(p for p in _pins() if p["multiplier"] == 5 and p["src"] == "recursive_proof_16_15.bin")
+    pin = next(p for p in pins() if p["multiplier"] == 5 and p["src"] == "recursive_proof_16_15.bin")
     src = pin["src"]
-    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=5, set_walks=_walks(pin))
+    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), inputs_of(src), copies=5, set_walks=walks_of(pin))
     assert wp.trace_sizes() == (19, 18)
     batch = [read_proof(src), ob.tamper(read_proof(src), 3), read_proof(src)]
     rng = np.random.default_rng(11)
     lookup = _random_lookup(rng, 3)
     ctx = rsv.Context(0)
-    dp, dq, ds, dok, da, plonk, poseidon = _device(rsv, ctx, wp, batch, _inputs(src), lookup, "by_proof")
+    dp, dq, ds, dok, da, plonk, poseidon = _device(rsv, ctx, wp, batch, inputs_of(src), lookup, "by_proof")
     assert da.tolist() == [1, 0, 1] and dok.tolist() == [1, 0, 1]
     assert not dp[1].any() and not dq[1].any() and not ds[1].any()
     for k in (0, 2):
         wpl, wpo, wsums, wok = _expected(rsv, wp, plonk[k], poseidon[k], *lookup[k])
         assert wok and np.array_equal(dp[k], wpl) and np.array_equal(dq[k], wpo) and np.array_equal(ds[k], wsums), k
-        assert _balance(ds[k].tolist(), _inputs(pin["dst"]), *lookup[k])
+        assert _balance(ds[k].tolist(), inputs_of(pin["dst"]), *lookup[k])
     ctx.close()
     wp.close()
 

@@ -9,23 +9,11 @@ import numpy as np
 import pytest
 
 from tests import interaction_ref as R
-from tests import oracle_binding as ob
 from tests.conftest import load_manifest, read_proof
-from tests.test_trace_host import _header_logs, _oracle_circuit, _pins, _round_constants
+from tests.chain_harness import lookup_of, oods_of, oracle_columns
 
 P = R.P
 MAN = {e["file"]: e for e in load_manifest()}
-
-
-def lookup_of(name):
-    """(z, alpha) the proof's transcript draws after trees 0 and 1."""
-    tr = ob.transcript_raw(read_proof(name))
-    return tuple(int(x) for x in tr[4:8]), tuple(int(x) for x in tr[8:12])
-
-
-def oods_of(name):
-    tr = ob.transcript_raw(read_proof(name))
-    return tuple(int(x) for x in tr[20:24]), tuple(int(x) for x in tr[24:28])
 
 
 def tree2_samples(cp, cq, lp, lq, oods):
@@ -40,29 +28,11 @@ def tree2_samples(cp, cq, lp, lq, oods):
     return out
 
 
-_CACHE = {}
-
-
-def _oracle_columns(src):
-    """(plonk pre [10, N], plonk trace [12, N], poseidon pre [40, Q], poseidon trace [48, Q], lp, lq, dst) of a pair."""
-    if src not in _CACHE:
-        from oracle.recursion_circuit import trace as T
-        pin = next(p for p in _pins() if p["src"] == src)
-        c, _, _ = _oracle_circuit(pin)
-        lp, lq = _header_logs(pin["dst"])
-        assert T.pad(c) == 1 << lp
-        pre, tr = T.plonk_columns(c)
-        ppre = np.stack([np.asarray(pre[k], dtype=np.int64) % P for k in T.PREPROCESSED])
-        qpre, qtr = T.poseidon_columns(c.flow, _round_constants(), lq, padding_hash=([0] * 8,))
-        _CACHE[src] = (ppre, np.asarray(tr, np.int64), qpre.astype(np.int64), qtr.astype(np.int64), lp, lq, pin["dst"])
-    return _CACHE[src]
-
-
 @pytest.mark.parametrize("src", ["small_proof.bin", "level10-1.bin"])
 def test_restatement_reproduces_the_next_fixture(src):
     """Claimed sums (stmt1) and all 24 tree-2 sampled values of fixture K+1, bit for bit, with K+1's (z, alpha)."""
     from oracle import recursion_circuit as rc
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns(src)
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns(src)
     z, alpha = lookup_of(dst)
     cp, cq, sums, ok = R.interaction(ppre, ptr, qpre, qtr, z, alpha, lp, lq)
     assert ok
@@ -79,7 +49,7 @@ def test_restatement_reproduces_the_next_fixture(src):
 
 def test_balance_identity_for_random_lookup_elements():
     """plonk + poseidon + sum over the public inputs of 1 / (v + idx alpha - z) = 0 for any (z, alpha)."""
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns("small_proof.bin")
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns("small_proof.bin")
     inputs = [(i, tuple(v)) for i, v in MAN[dst]["inputs"]]  # the circuit's: variables 1, 2, 3 = 1, i, j
     rng = np.random.default_rng(7)
     for _ in range(3):

@@ -12,25 +12,11 @@ import pytest
 from tests import commit_ref as C
 from tests import oracle_binding as ob
 from tests import sample_ref as S
+from tests.chain_harness import CASES, DEV, chain, dev, full, inputs_of, mask_dev, next_samples, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
-from tests.test_commit_gpu import CASES, _program
-from tests.test_decommit_gpu import _chain_dev
-from tests.test_trace_gpu import _inputs
-from tests.test_trace_host import _pins
 
 pytestmark = pytest.mark.gpu
 P = C.P
-DEV = "cuda:0"
-FILL = -1  # every output is prefilled with 0xffffffff: what a call leaves undefined shows
-
-
-def _u32(t):
-    return t.cpu().numpy().view(np.uint32)
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).to(torch.device(DEV))
 
 
 def _groups_dev(groups, shared=()):
@@ -40,29 +26,24 @@ def _groups_dev(groups, shared=()):
         if cols.ndim == 2:
             cols = cols[None]
         nc = cols.shape[1]
-        gs.append({"log_size": log, "d_cols": _dev(cols), "n_cols": nc, "proof_stride": 0 if i in shared else nc << log})
+        gs.append({"log_size": log, "d_cols": dev(cols), "n_cols": nc, "proof_stride": 0 if i in shared else nc << log})
     return gs
 
 
 def _sample_dev(ctx, gs, n, points, mask=None, source=0):
     """Context.sample_tree on device groups, points uint32[n, k, 8] -> uint32[n, k, sum n_cols, 4]."""
-    import torch
     k = points.shape[1]
-    total = sum(g["n_cols"] for g in gs)
-    d_out = torch.full((n, k, total, 4), FILL, dtype=torch.int32, device=torch.device(DEV))
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(torch.device(DEV))
-    ctx.sample_tree(gs, n, _dev(points), k, d_out, d_mask=d_mask, source=source)
+    d_out = full((n, k, sum(g["n_cols"] for g in gs), 4))
+    d_points, d_mask = dev(points), mask_dev(mask)
+    ctx.sample_tree(gs, n, d_points, k, d_out, d_mask=d_mask, source=source)
     ctx.synchronize()
-    return _u32(d_out)
+    return u32(d_out)
 
 
 def _coeffs_dev(ctx, gs, n, b, mask):
     """The groups with d_cols = the d_coeffs of a commit_tree of the same groups (proof_stride: every proof its own)."""
-    import torch
-    dev = torch.device(DEV)
-    with_cf = [dict(g, d_coeffs=torch.full((n, g["n_cols"], 1 << g["log_size"]), FILL, dtype=torch.int32, device=dev)) for g in gs]
-    d_roots = torch.full((n, 8), FILL, dtype=torch.int32, device=dev)
-    d_mask = None if mask is None else torch.from_numpy(np.asarray(mask, np.uint8)).to(dev)
+    with_cf = [dict(g, d_coeffs=full((n, g["n_cols"], 1 << g["log_size"]))) for g in gs]
+    d_roots, d_mask = full((n, 8)), mask_dev(mask)
     ctx.commit_tree(with_cf, n, b, d_roots, d_mask)
     ctx.synchronize()
     return [{"log_size": g["log_size"], "d_cols": g["d_coeffs"], "n_cols": g["n_cols"]} for g in with_cf]
@@ -98,33 +79,21 @@ def _check_random(ctx, spec, b, n, mask, seed, ks=(1, 2, 4)):
             assert np.array_equal(from_cols[p], want), (spec, k, p)
 
 
-def _witness_sample(ctx, wp, t, n, oods):
-    import torch
-    d_out = torch.full((n, 134, 4), FILL, dtype=torch.int32, device=torch.device(DEV))
-    ctx.witness_sample(wp, t["plonk"], t["pos"], t["ops"], t["ip"], t["iq"], t["acc"], n, _dev(oods), d_out, d_ok=t["ok"])
-    ctx.synchronize()
-    return _u32(d_out)
-
-
-def _next_samples(dst):
-    from oracle import recursion_circuit as rc
-    nxt = read_proof(dst)
-    tr = ob.transcript_raw(nxt)
-    return S.flatten_samples(rc.parse_proof(nxt).sampled_values), np.array(tr[20:28], dtype=np.uint32)
-
-
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_chain_samples_what_the_next_fixture_carries(rsv, pin):
     """The chain of fixture K at K+1's OODS point: K+1's sampled_values[0..2], all 134 values."""
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     b = fixture_cfg(dst).log_blowup_factor
-    want, oods = _next_samples(dst)
+    want, oods = next_samples(dst)
     ctx = rsv.Context(0)
-    t = _chain_dev(rsv, ctx, wp, [read_proof(src)], _inputs(src), b, caps=False)
-    got = _witness_sample(ctx, wp, t, 1, oods[None])
+    ch = chain(rsv, ctx, wp, [read_proof(src)], inputs_of(src), b)
+    d_oods = dev(oods[None])
+    ch.sample(d_oods)
+    r = ch.numpy()
+    got = r["samples"]
     ctx.close()
-    assert t["ok"].cpu().tolist() == [1]
+    assert r["ok"].tolist() == [1]
     assert np.array_equal(got[0], want), np.nonzero((got[0] != want).any(axis=1))[0].tolist()
     wp.close()
 
@@ -134,24 +103,27 @@ def test_sample_tree_per_tree_equals_the_chain(rsv):
     OODS point and the two previous-row points: every value the chain places is there, and a batch with a rejected proof
     gives zeros for it and the solo values for the others."""
     from tests import interaction_ref as R
-    pin = next(p for p in _pins() if p["src"] == "level2-1.bin")
+    pin = next(p for p in pins() if p["src"] == "level2-1.bin")
     src, dst = pin["src"], pin["dst"]
-    wp = _program(rsv, pin)
+    wp = program_of(rsv, pin)
     lp, lq = wp.trace_sizes()
     b = fixture_cfg(dst).log_blowup_factor
-    want, oods = _next_samples(dst)
+    want, oods = next_samples(dst)
     proof = read_proof(src)
     ctx = rsv.Context(0)
-    t = _chain_dev(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], _inputs(src), b, caps=False)
-    got = _witness_sample(ctx, wp, t, 3, np.stack([oods] * 3))
-    assert t["ok"].cpu().tolist() == [1, 0, 1]
+    ch = chain(rsv, ctx, wp, [proof, ob.tamper(proof, 5), proof], inputs_of(src), b)
+    d_oods = dev(np.stack([oods] * 3))
+    ch.sample(d_oods)
+    r = ch.numpy()
+    got = r["samples"]
+    assert r["ok"].tolist() == [1, 0, 1]
     assert np.array_equal(got[0], want) and np.array_equal(got[2], want) and not got[1].any()
     ppre, qpre = wp.preprocessed()
     _, wops = wp.gates()
     ppre = ppre.copy()
     if len(wops):
-        ppre[3, wops[:, 0]] = _u32(t["ops"])[0, :len(wops)]
-    trees = [[(lp, ppre), (lq, qpre)], [(lp, _u32(t["plonk"])[0]), (lq, _u32(t["pos"])[0])], [(lp, _u32(t["ip"])[0]), (lq, _u32(t["iq"])[0])]]
+        ppre[3, wops[:, 0]] = r["ops"][0]
+    trees = [[(lp, ppre), (lq, qpre)], [(lp, r["plonk"][0]), (lq, r["poseidon"][0])], [(lp, r["int_plonk"][0]), (lq, r["int_poseidon"][0])]]
     o = _pt(oods)
     pts = np.array([[list(q[0]) + list(q[1]) for q in (o, R.prev_row_point(o, lp), R.prev_row_point(o, lq))]], dtype=np.uint32)
     off = 0
@@ -287,7 +259,7 @@ def test_sample_at_a_domain_point_is_the_lde(rsv):
     groups = [(log, rng.integers(0, P, (n, nc, 1 << log))) for log, nc in spec]
     ctx = rsv.Context(0)
     gs = _groups_dev(groups)
-    with_lde = [dict(g, d_lde=torch.full((n, g["n_cols"], 1 << (g["log_size"] + b)), FILL, dtype=torch.int32, device=dev)) for g in gs]
+    with_lde = [dict(g, d_lde=full((n, g["n_cols"], 1 << (g["log_size"] + b)))) for g in gs]
     ctx.commit_tree(with_lde, n, b, torch.zeros((n, 8), dtype=torch.int32, device=dev))
     ctx.synchronize()
     for g in with_lde:
@@ -297,7 +269,7 @@ def test_sample_at_a_domain_point_is_the_lde(rsv):
         pts = np.zeros((n, 3, 8), np.uint32)
         pts[:, :, 0], pts[:, :, 4] = xy[:, :, 0], xy[:, :, 1]
         got = _sample_dev(ctx, [{k: v for k, v in g.items() if k != "d_lde"}], n, pts, None, 0)
-        lde = _u32(g["d_lde"])
+        lde = u32(g["d_lde"])
         for p in range(n):
             for j in range(3):
                 assert np.array_equal(got[p, j, :, 0], lde[p, :, pos[p, j]]) and not got[p, j, :, 1:].any(), (N, p, j)

@@ -14,7 +14,7 @@ from tests import commit_ref as C
 from tests import interaction_ref as R
 from tests import sample_ref as S
 from tests.conftest import read_proof
-from tests.test_interaction_host import _oracle_columns, lookup_of, oods_of
+from tests.chain_harness import lookup_of, oods_of, oracle_columns
 
 P = C.P
 
@@ -22,7 +22,7 @@ P = C.P
 @pytest.mark.parametrize("src", ["small_proof.bin", "recursive_proof_16_15.bin", "level10-1.bin"])
 def test_restatement_reproduces_the_next_fixture_samples(src):
     from oracle import recursion_circuit as rc
-    ppre, ptr, qpre, qtr, lp, lq, dst = _oracle_columns(src)
+    ppre, ptr, qpre, qtr, lp, lq, dst = oracle_columns(src)
     z, alpha = lookup_of(dst)
     cp, cq, _, ok = R.interaction(ppre, ptr, qpre, qtr, z, alpha, lp, lq)
     assert ok

@@ -7,41 +7,20 @@ import numpy as np
 import pytest
 
 from tests import oracle_binding as ob
-from tests.conftest import fixture_cfg, load_manifest, read_proof
-from tests.test_trace_host import _pins, _round_constants
+from tests.chain_harness import chain, eval_column, inputs_of, pin_id, pins, round_constants, walks_of, weights
+from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
-P = 0x7FFFFFFF
-MAN = {e["file"]: e for e in load_manifest()}
 
 
-def _inputs(name):
-    return [(i, tuple(v)) for i, v in MAN[name]["inputs"]]
-
-
-def _walks(pin):
-    orders = [tuple(tuple(x) for x in o) for o in pin["shift_orders"]]
-    return [(1 if o[0] == (-1, 0) else 0) | (2 if o[1] == (-1, 0) else 0) for o in orders]
-
-
-def _weights(log_size, point):
-    from oracle.recursion_circuit import trace as T
-    return [np.array(w, dtype=np.int64) for w in T.PointEvaluator(log_size, point).weights]
-
-
-def _eval(weights, column):
-    col = np.asarray(column, dtype=np.int64)
-    return tuple(int(((w * col) % P).sum() % P) for w in weights)
-
-
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_all_110_columns_are_what_the_next_fixture_proves(rsv, pin):
     """The library alone — program, preprocessed columns (op patched with the proof's d_ops), trace columns from the GPU —
     gives every one of the next fixture's 50 preprocessed and 60 trace sampled values."""
     from oracle import recursion_circuit as rc
     src, mult = pin["src"], pin["multiplier"]
-    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=mult, set_walks=_walks(pin))
-    plonk, poseidon, ops, accept, _ = rsv.witness_trace([read_proof(src)], wp, _inputs(src))
+    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), inputs_of(src), copies=mult, set_walks=walks_of(pin))
+    plonk, poseidon, ops, accept, _ = rsv.witness_trace([read_proof(src)], wp, inputs_of(src))
     assert accept[0] == 1
     ppre, qpre = wp.preprocessed()
     _, wops = wp.gates()
@@ -52,12 +31,12 @@ def test_all_110_columns_are_what_the_next_fixture_proves(rsv, pin):
     tr = ob.transcript_raw(nxt)
     oods = (tuple(int(x) for x in tr[20:24]), tuple(int(x) for x in tr[24:28]))
     want = rc.parse_proof(nxt).sampled_values
-    wp_, wq = _weights(lp, oods), _weights(lq, oods)
+    wp_, wq = weights(lp, oods), weights(lq, oods)
     pre_cols = [(wp_, c) for c in ppre] + [(wq, c) for c in qpre]
     tr_cols = [(wp_, c) for c in plonk[0]] + [(wq, c) for c in poseidon[0]]
     assert len(pre_cols) == 50 and len(tr_cols) == 60
-    bad = [k for k, (w, c) in enumerate(pre_cols) if _eval(w, c) != tuple(want[0][k][0])]
-    bad += [50 + k for k, (w, c) in enumerate(tr_cols) if _eval(w, c) != tuple(want[1][k][0])]
+    bad = [k for k, (w, c) in enumerate(pre_cols) if eval_column(w, c) != tuple(want[0][k][0])]
+    bad += [50 + k for k, (w, c) in enumerate(tr_cols) if eval_column(w, c) != tuple(want[1][k][0])]
     assert not bad, bad
     wp.close()
 
@@ -82,37 +61,19 @@ def _expected(rsv, wp, variables, flow, swap):
     n_pad = max(32, -(-len(recs) // 16) * 16)
     for _ in range(len(recs), n_pad):
         recs.append(((0, None), (0, None), (0, None), (0, None), 0, False))
-    _, poseidon = T.poseidon_columns(recs, _round_constants(), lq, padding_hash=([0] * 8,))
+    _, poseidon = T.poseidon_columns(recs, round_constants(), lq, padding_hash=([0] * 8,))
     ops = np.where(variables[wops[:, 1], 0] != 0, wops[:, 2], 0).astype(np.uint32)
     return plonk.astype(np.int64), poseidon.astype(np.int64), ops, n_pad
 
 
 def _device_trace(rsv, ctx, wp, batch, inputs, layout, plonk=True, poseidon=True, ops=True):
-    """Context.witness then Context.witness_trace on tensors in HBM (outputs filled with -1 first: every element must be
-    written) -> numpy plonk, poseidon, ops, accept (None for a skipped output)."""
-    import torch
-    dev = torch.device("cuda:0")
-    n = len(batch)
-    lp, lq = wp.trace_sizes()
-    n_ops = len(wp.gates()[1])
-    F = wp.shape.flow_count
-    blob, offsets = rsv.pack(batch)
-    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
+    """The chain through Context.witness_trace on tensors in HBM under a variable layout (outputs prefilled: every element
+    must be written) -> numpy plonk, poseidon, ops, accept (None for a skipped output)."""
     ctx.set_option("witness_layout", layout)
-    shape = (wp.n_vars, n, 4) if layout == "by_variable" else (n, wp.n_vars, 4)
-    d_vars = torch.zeros(shape, dtype=torch.int32, device=dev)
-    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
-    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
-    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ctx.witness(wp, d_blob, d_off, n, d_vars, d_acc, inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
-    d_plonk = torch.full((n, 12, 1 << lp), -1, dtype=torch.int32, device=dev) if plonk else None
-    d_pos = torch.full((n, 48, 1 << lq), -1, dtype=torch.int32, device=dev) if poseidon else None
-    d_ops = torch.full((n, n_ops), -1, dtype=torch.int32, device=dev) if ops else None
-    ctx.witness_trace(wp, d_vars, d_acc, n, d_plonk=d_plonk, d_poseidon=d_pos, d_ops=d_ops, d_flow=d_flow, d_flow_swap=d_swap)
-    ctx.synchronize()
-    get = lambda t: None if t is None else t.cpu().numpy().view(np.uint32)
+    got = chain(rsv, ctx, wp, batch, inputs, 1, upto="trace", by_variable=layout == "by_variable",
+                outputs={"plonk": plonk, "poseidon": poseidon, "ops": ops}).numpy()
     ctx.set_option("witness_layout", "by_proof")
-    return get(d_plonk), get(d_pos), get(d_ops), d_acc.cpu().numpy()
+    return got.get("plonk"), got.get("poseidon"), got.get("ops"), got["acc"]
 
 
 def test_mixed_batch_bit_for_bit(rsv):
@@ -174,14 +135,14 @@ def test_five_copies_batch(rsv):
     """A copies = 5 program (examples/multi-proofs' circuit: 2^19 Plonk, 2^18 Poseidon rows): a batch with a rejected proof
     on the device equals the single-proof host call row for row (that call is pinned to the next fixture above), and the
     five copies' Poseidon blocks hash the same records."""
-    pin = next(p for p in _pins() if p["multiplier"] == 5 and p["src"] == "recursive_proof_16_15.bin")
+    pin = next(p for p in pins() if p["multiplier"] == 5 and p["src"] == "recursive_proof_16_15.bin")
     src = pin["src"]
-    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), _inputs(src), copies=5, set_walks=_walks(pin))
-    plonk1, poseidon1, ops1, acc1, _ = rsv.witness_trace([read_proof(src)], wp, _inputs(src))
+    wp = rsv.WitnessProgram.build(read_proof(src), fixture_cfg(src), inputs_of(src), copies=5, set_walks=walks_of(pin))
+    plonk1, poseidon1, ops1, acc1, _ = rsv.witness_trace([read_proof(src)], wp, inputs_of(src))
     assert acc1[0] == 1 and wp.trace_sizes() == (19, 18)
     batch = [read_proof(src), ob.tamper(read_proof(src), 3), read_proof(src)]
     ctx = rsv.Context(0)
-    dp, dq, do, da = _device_trace(rsv, ctx, wp, batch, _inputs(src), "by_proof")
+    dp, dq, do, da = _device_trace(rsv, ctx, wp, batch, inputs_of(src), "by_proof")
     assert da.tolist() == [1, 0, 1]
     for k in (0, 2):
         assert np.array_equal(dp[k], plonk1[0]) and np.array_equal(dq[k], poseidon1[0]) and np.array_equal(do[k], ops1[0])

@@ -3,32 +3,16 @@
 (the header of fixture K+1 for every pair) and, column for column, to the oracle's restatement of pad() /
 populate_logup_arguments / the Poseidon AIR's rows (oracle/recursion_circuit/trace.py) on circuits the oracle builds on the CPU."""
 import ctypes
-import json
-import os
 
 import numpy as np
 import pytest
 
-from tests import oracle_binding as ob
-from tests.conftest import GOLDEN, load_manifest, read_proof
-
-P = 0x7FFFFFFF
-MAN = {e["file"]: e for e in load_manifest()}
+from tests.chain_harness import P, header_logs, oracle_circuit, pin_id, pins, round_constants
 
 
-def _pins():
-    with open(os.path.join(GOLDEN, "recursion_circuit_pins.json")) as f:
-        return json.load(f)["pairs"]
-
-
-def _header_logs(name):
-    w = np.frombuffer(read_proof(name)[:8], np.uint32)
-    return int(w[0]), int(w[1])
-
-
-@pytest.mark.parametrize("pin", _pins(), ids=lambda p: f"{p['src']}x{p['multiplier']}")
+@pytest.mark.parametrize("pin", pins(), ids=pin_id)
 def test_log_sizes_are_the_next_fixtures_header(rsv, pin):
-    assert rsv.trace_log_sizes(pin["plonk_rows"], pin["poseidon_invocations"]) == _header_logs(pin["dst"])
+    assert rsv.trace_log_sizes(pin["plonk_rows"], pin["poseidon_invocations"]) == header_logs(pin["dst"])
 
 
 def test_log_sizes_edges(rsv):
@@ -43,13 +27,6 @@ def test_log_sizes_edges(rsv):
         assert e.value.code == -2
 
 
-def _round_constants():
-    ob.lib.rsvo_round_constants.restype = ctypes.POINTER(ctypes.c_uint32)
-    r = [ob.lib.rsvo_round_constants(k) for k in range(3)]
-    return ([[int(r[0][16 * a + i]) for i in range(16)] for a in range(4)], [int(r[1][i]) for i in range(14)],
-            [[int(r[2][16 * a + i]) for i in range(16)] for a in range(4)])
-
-
 def _call(rsv, gates, wires, lp, lq, plonk=None, poseidon=None):
     plonk = np.zeros((10, 1 << lp), np.uint32) if plonk is None else plonk
     poseidon = np.zeros((40, 1 << lq), np.uint32) if poseidon is None else poseidon
@@ -60,25 +37,14 @@ def _call(rsv, gates, wires, lp, lq, plonk=None, poseidon=None):
     return rc, plonk, poseidon
 
 
-def _oracle_circuit(pin):
-    from oracle import recursion_circuit as rc
-    src = pin["src"]
-    orders = [tuple(tuple(x) for x in o) for o in pin["shift_orders"]]
-    c, _, _ = rc.build_circuit(read_proof(src), ob, [(i, tuple(v)) for i, v in MAN[src]["inputs"]], pin["multiplier"], orders)
-    gates = np.stack([np.array(x, dtype=np.int64) for x in (c.a_wire, c.b_wire, c.c_wire, c.op, c.poseidon_wire, c.enforce_c_m31)], axis=1)
-    gates = np.ascontiguousarray(gates % P, dtype=np.uint32)
-    wires = np.array([[e1[0], e2[0], e3[0], e4[0], addr] for (e1, e2, e3, e4, addr, _sw) in c.flow], dtype=np.uint32)
-    return c, gates, wires
-
-
 @pytest.mark.parametrize("src", ["small_proof.bin", "level10-1.bin"])
 def test_preprocessed_columns_are_the_oracles(rsv, src):
     """The library's 10 + 40 columns from the UNPADDED gate list and flow wires == the oracle's pad() + plonk_columns /
     poseidon_columns preprocessed halves, bit for bit, at the next fixture's log sizes."""
     from oracle.recursion_circuit import trace as T
-    pin = next(p for p in _pins() if p["src"] == src)
-    c, gates, wires = _oracle_circuit(pin)
-    lp, lq = _header_logs(pin["dst"])
+    pin = next(p for p in pins() if p["src"] == src)
+    c, gates, wires = oracle_circuit(pin)
+    lp, lq = header_logs(pin["dst"])
     assert rsv.trace_log_sizes(len(gates), len(wires)) == (lp, lq)
     rc_, plonk, poseidon = _call(rsv, gates, wires, lp, lq)
     assert rc_ == 0
@@ -86,7 +52,7 @@ def test_preprocessed_columns_are_the_oracles(rsv, src):
     pre, _ = T.plonk_columns(c)
     for k, name in enumerate(T.PREPROCESSED):
         assert np.array_equal(plonk[k], np.asarray(pre[name], dtype=np.int64) % P), name
-    qpre, _ = T.poseidon_columns(c.flow, _round_constants(), lq, padding_hash=([0] * 8,))
+    qpre, _ = T.poseidon_columns(c.flow, round_constants(), lq, padding_hash=([0] * 8,))
     assert np.array_equal(poseidon, qpre.astype(np.int64)), [k for k in range(40) if not np.array_equal(poseidon[k], qpre[k].astype(np.int64))]
     # larger log sizes than needed: the same columns, zero-extended (the Poseidon rows behind the flow first and last)
     rc_, plonk2, poseidon2 = _call(rsv, gates, wires, lp + 1, lq + 1)

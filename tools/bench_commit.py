@@ -16,13 +16,9 @@ layers written and read once (32 B each); against 8 TB/s.  `bound` is whichever 
 split run the tool under `rocprofv3 --kernel-trace --stats -- python tools/bench_commit.py ...`."""
 import argparse
 import json
-import os
-import sys
 
-import numpy as np
+from chain_bench import add_args, open_chain, time_interleaved
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 PEAK_GBS = 8000.0
 PERM_RATE = 9.5e9
 LDS_LOG = 12
@@ -56,63 +52,14 @@ def perms_per_proof(lp, lq, b):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--fixture", default="level9-1.bin")
-    ap.add_argument("--log-blowup", type=int, default=8)
-    ap.add_argument("--proofs", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--copies", type=int, default=1)
+    add_args(ap, "level9-1.bin", 8)
     args = ap.parse_args()
-    import rsvload
-    rsv = rsvload.load_package()
-    import torch
-    import bench
-    with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
-        man = {e["file"]: e for e in json.load(f)["proofs"]}
-    e = man[args.fixture]
-    inputs = [(i, tuple(v)) for i, v in e["inputs"]]
-    cfg = rsv.PcsConfig(e["pow_bits"], e["log_blowup_factor"], e["log_last_layer_degree_bound"], e["n_queries"])
-    proof = bench.read_fixture(args.fixture)
-    wp = rsv.WitnessProgram.build(proof, cfg, inputs, copies=args.copies)
-    lp, lq = wp.trace_sizes()
-    F = wp.shape.flow_count
-    n_ops = len(wp.gates()[1])
-    n, b = args.proofs, args.log_blowup
-    dev = torch.device("cuda:0")
-    blob, offsets = rsv.pack([proof] * n)
-    ctx = rsv.Context(0)
-    d_blob, d_off = torch.from_numpy(blob.copy()).to(dev), torch.from_numpy(offsets.astype(np.int64)).to(dev)
-    d_vars = torch.zeros((n, wp.n_vars, 4), dtype=torch.int32, device=dev)
-    d_flow = torch.zeros((n, F, 32), dtype=torch.int32, device=dev)
-    d_swap = torch.zeros((n, F), dtype=torch.uint8, device=dev)
-    d_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
-    ctx.witness(wp, d_blob, d_off, n, d_vars, d_acc, inputs=inputs, d_flow=d_flow, d_flow_swap=d_swap)
-    d_plonk = torch.zeros((n, 12, 1 << lp), dtype=torch.int32, device=dev)
-    d_pos = torch.zeros((n, 48, 1 << lq), dtype=torch.int32, device=dev)
-    d_ops = torch.zeros((n, max(n_ops, 1)), dtype=torch.int32, device=dev)
-    ctx.witness_trace(wp, d_vars, d_acc, n, d_plonk=d_plonk, d_poseidon=d_pos, d_ops=d_ops, d_flow=d_flow, d_flow_swap=d_swap)
-    del d_vars, d_flow, d_swap, d_blob
-    d_roots = torch.zeros((n, 3, 8), dtype=torch.int32, device=dev)
-    d_draws = torch.zeros((n, 12), dtype=torch.int32, device=dev)
-    d_ip = torch.zeros((n, 8, 1 << lp), dtype=torch.int32, device=dev)
-    d_iq = torch.zeros((n, 8, 1 << lq), dtype=torch.int32, device=dev)
-    d_sums = torch.zeros((n, 2, 4), dtype=torch.int32, device=dev)
-    d_ok = torch.zeros(n, dtype=torch.uint8, device=dev)
-    call = lambda: ctx.witness_commit(wp, d_plonk, d_pos, d_ops, d_acc, n, b, d_roots, d_draws, d_ip, d_iq, d_sums, d_ok=d_ok)  # noqa: E731
-    for _ in range(args.warmup):
-        call()
-    ctx.synchronize()
-    stream = torch.cuda.ExternalStream(ctx.stream) if ctx.stream else torch.cuda.current_stream()
-    times = []
-    for _ in range(args.steps):
-        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record(stream)
-        call()
-        t1.record(stream)
-        t1.synchronize()
-        times.append(t0.elapsed_time(t1))
-    ok = int(d_ok.sum().item())
-    ms = float(np.median(times))
+    rsv, ctx, wp, ch = open_chain(args, "trace")
+    lp, lq, n, b = ch.lp, ch.lq, ch.n, ch.log_blowup
+    # the chain allocates commit()'s tensors in its first call: with --warmup 0 that is the first timed one
+    times, med = time_interleaved(ctx, {"commit": ch.commit}, args.steps, args.warmup)
+    times, ms = times["commit"], med["commit"]
+    ok = int(ch.ok.sum().item())
     perms, byts = perms_per_proof(lp, lq, b)
     perm_frac = perms * n / (ms * 1e-3) / PERM_RATE
     hbm_frac = byts * n / (ms * 1e-3) / (PEAK_GBS * 1e9)

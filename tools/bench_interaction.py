@@ -19,13 +19,12 @@ file or an unprofiled shape leaves the bound null.  For a per-kernel split run t
 import argparse
 import json
 import os
-import sys
 import time
 
 import numpy as np
+from chain_bench import open_fixture
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 PEAK_GBS = 8000.0
 SIMDS, GHZ = 1024, 2.4
 VALU_FILE = os.path.join(ROOT, "profiles", "interaction_valu.json")
@@ -40,16 +39,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--copies", type=int, default=1)
     args = ap.parse_args()
-    import rsvload
-    rsv = rsvload.load_package()
+    rsv, proof, cfg, inputs = open_fixture(args)
     import torch
     import bench
-    with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
-        man = {e["file"]: e for e in json.load(f)["proofs"]}
-    e = man[args.fixture]
-    inputs = [(i, tuple(v)) for i, v in e["inputs"]]
-    cfg = rsv.PcsConfig(e["pow_bits"], e["log_blowup_factor"], e["log_last_layer_degree_bound"], e["n_queries"])
-    proof = bench.read_fixture(args.fixture)
     wp = rsv.WitnessProgram.build(proof, cfg, inputs, copies=args.copies)
     lp, lq = wp.trace_sizes()
     F = wp.shape.flow_count

@@ -11,14 +11,11 @@ and the eval and the trace together.  roofline: HBM-write bound — bytes writte
 from the profiler, run the tool under `rocprofv3 --kernel-trace --stats -- python tools/bench_trace.py ...`."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
+from chain_bench import open_fixture
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 PEAK_GBS = 8000.0
 
 
@@ -31,16 +28,9 @@ def main():
     ap.add_argument("--copies", type=int, default=1)
     ap.add_argument("--layout", choices=["by_proof", "by_variable"], default="by_proof", help="RSV_OPT_WITNESS_LAYOUT of d_variables")
     args = ap.parse_args()
-    import rsvload
-    rsv = rsvload.load_package()
+    rsv, proof, cfg, inputs = open_fixture(args)
     import torch
     import bench
-    with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
-        man = {e["file"]: e for e in json.load(f)["proofs"]}
-    e = man[args.fixture]
-    inputs = [(i, tuple(v)) for i, v in e["inputs"]]
-    cfg = rsv.PcsConfig(e["pow_bits"], e["log_blowup_factor"], e["log_last_layer_degree_bound"], e["n_queries"])
-    proof = bench.read_fixture(args.fixture)
     wp = rsv.WitnessProgram.build(proof, cfg, inputs, copies=args.copies)
     lp, lq = wp.trace_sizes()
     n_ops = len(wp.gates()[1])

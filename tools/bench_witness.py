@@ -11,14 +11,11 @@ roofline: the level kernels are HBM streaming — per instruction and proof 16 B
 the program; achieved = those bytes x proofs / (whole call - verifying pass)."""
 import argparse
 import json
-import os
-import sys
 import time
 
 import numpy as np
+from chain_bench import open_fixture
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 
 def main():
@@ -34,16 +31,9 @@ def main():
     ap.add_argument("--layout", choices=["by_proof", "by_variable"], default="by_proof",
                     help="by_variable: d_variables[variable][proof] as the level kernels write it (RSV_OPT_WITNESS_LAYOUT = 2): no transpose")
     args = ap.parse_args()
-    import rsvload
-    rsv = rsvload.load_package()
+    rsv, proof, cfg, inputs = open_fixture(args)
     import torch
     import bench
-    with open(os.path.join(ROOT, "tests", "golden", "manifest.json")) as f:
-        man = {e["file"]: e for e in json.load(f)["proofs"]}
-    e = man[args.fixture]
-    inputs = [(i, tuple(v)) for i, v in e["inputs"]]
-    cfg = rsv.PcsConfig(e["pow_bits"], e["log_blowup_factor"], e["log_last_layer_degree_bound"], e["n_queries"])
-    proof = bench.read_fixture(args.fixture)
     t0 = time.perf_counter()
     wp = rsv.WitnessProgram.build(proof, cfg, inputs, copies=args.copies)
     build_s = time.perf_counter() - t0
