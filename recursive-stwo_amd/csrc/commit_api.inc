@@ -2,6 +2,9 @@
 // Merkle tree, optionally leaving the tree's cap) and rsv_witness_commit_dev / rsv_witness_commit_caps_dev /
 // rsv_witness_commit (trees 0, 1, 2 of the recursion circuit's next proof and the transcript draws between them):
 // k_commit.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after interaction_api.inc; decommit_api.inc follows.
+//
+// Also the home of what every stage that takes groups of columns shares (decommit, sample, composition and fri_api.inc
+// after it): the twiddle tables, the FFT launches and the streaming helpers below them.  commit_tree is their first user.
 
 namespace {
 
@@ -36,25 +39,107 @@ void cm_fft(hipStream_t st, const rsv::CmRows& r, const rsv::CmSrc& s, const uin
     }
 }
 
-// Workspace of a pass of P proofs and nb blocks (bytes, with Carve's alignment); with cv, also where each part goes.
-size_t cm_ws_bytes(const rsv_commit_group* g, size_t ng, uint32_t b, uint32_t Lmax, size_t P, size_t nb, rsv::host::Carve* cv,
-                   uint32_t** coef, uint32_t** lde, uint32_t** nodes_a, uint32_t** nodes_b, uint32_t** broots, uint32_t** top_a,
-                   uint32_t** top_b) {
-    rsv::host::Carve sz{cv ? cv->base : nullptr};
+// ---- The streaming of column groups (rsv_commit_group) that commit_tree, decommit_tree, sample_groups, composition and
+// fri_quotients share.  A driver sizes a pass with rsv::host::plan_pass over its own *_ws_bytes, tests cm_rows_fit per
+// group and the limits of its own launches, looks the tables up, carves its workspace with cm_workspace, and per pass calls
+// cm_interpolate and then, per range of blocks, cm_extend (the block-list form: cm_extension and dc_fft).
+
+constexpr uint64_t CM_GRID_LIM = (uint64_t)1 << 31;  // every launch's grid stays below 2^31 workgroups
+
+// The FFT launches over `rows` rows of 2^log words stay below the limit (a row per workgroup, or 256 words).
+bool cm_rows_fit(uint64_t rows, uint32_t log) { return rows < CM_GRID_LIM && (rows << log) / 256 < CM_GRID_LIM; }
+
+// Per group the inverse table of its size (tw_inv; nullptr for a coefficient source) and the forward table of its LDE
+// domain 2^(log_size + b) (tw_fwd; nullptr where the driver extends to a domain of its own).
+int cm_group_twiddles(rsv_ctx* c, const rsv_commit_group* g, size_t ng, uint32_t b, const uint32_t** tw_inv, const uint32_t** tw_fwd) {
+    int rc = RSV_OK;
+    for (size_t i = 0; i < ng && rc == RSV_OK; i++) {
+        if (tw_inv) rc = cm_twiddles(c, g[i].log_size, true, &tw_inv[i]);
+        if (tw_fwd && rc == RSV_OK) rc = cm_twiddles(c, g[i].log_size + b, false, &tw_fwd[i]);
+    }
+    return rc;
+}
+
+// The context's pass workspace, large enough for layout(nullptr) bytes, then carved by layout(its base).
+template <class Layout>
+int cm_workspace(rsv_ctx* c, Layout layout) {
+    const int rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, layout(nullptr));
+    if (rc == RSV_OK) layout(static_cast<char*>(c->ws_commit));
+    return rc;
+}
+
+// Interpolation: the columns of proofs p0 .. p0 + Pc - 1 -> the coefficients at dst, masked proofs zero.  With `once`, a
+// group that every proof shares (proof_stride == 0) is held once, unmasked, and only the first pass makes it.
+void cm_interpolate(hipStream_t st, const rsv_commit_group& g, uint32_t* dst, size_t p0, size_t Pc, const uint8_t* d_mask, bool once,
+                    const uint32_t* tw) {
+    const bool shared = once && g.proof_stride == 0;
+    if (shared && p0) return;
+    const uint32_t log = g.log_size;
+    const size_t row = (size_t)1 << log;
+    const rsv::CmRows r{dst, row, (uint64_t)(shared ? 1 : Pc) * g.n_cols, log, log, 1, 0};
+    const rsv::CmSrc s{g.d_cols + p0 * g.proof_stride, g.proof_stride, row, shared ? nullptr : d_mask, g.n_cols, (uint32_t)p0,
+                       log ? 1u << (31 - log) : 1u};  // 2^-log = 2^(31-log) mod P
+    cm_fft<true>(st, r, s, tw);
+}
+
+// Where a group's blocks in flight are: those of (proof, column) row pc from base + pc * pc_stride on.
+struct CmBlocks {
+    uint32_t* base;
+    uint64_t pc_stride;
+};
+// The extension of `pcs` (proof, column) rows of a group, their coefficients at coef with pstride words between two
+// proofs, to blocks blk0 .. blk0 + nb - 1 (2^log_size rows each) of the domain 2^N.
+struct CmExt {
+    rsv::CmRows r;
+    rsv::CmSrc s;
+};
+CmExt cm_extension(const rsv_commit_group& g, const uint32_t* coef, uint64_t pstride, uint64_t pcs, uint32_t N, size_t nb, size_t blk0,
+                   CmBlocks to) {
+    const uint32_t log = g.log_size;
+    return {{to.base, to.pc_stride, pcs * nb, log, N, (uint32_t)nb, (uint32_t)blk0}, {coef, pstride, (uint64_t)1 << log, nullptr, g.n_cols, 0, 1}};
+}
+void cm_extend(hipStream_t st, const rsv_commit_group& g, const uint32_t* coef, uint64_t pstride, uint64_t pcs, uint32_t N, size_t nb,
+               size_t blk0, CmBlocks to, const uint32_t* tw) {
+    const CmExt e = cm_extension(g, coef, pstride, pcs, N, nb, blk0, to);
+    cm_fft<false>(st, e.r, e.s, tw);
+}
+
+// Level l of the block subtrees of a pass of Pc proofs and nb blocks: the groups whose LDE lives there, in commitment
+// order, their blocks at at[i].  The caller adds child, out and (commit_tree) blk0.
+rsv::CmHashArgs cm_layer_args(const rsv_commit_group* g, size_t ng, uint32_t b, uint32_t l, const CmBlocks* at, size_t Pc, size_t nb) {
+    rsv::CmHashArgs a{};
+    a.lw = l - b;
+    a.nb = (uint32_t)nb;
+    a.P = (uint32_t)Pc;
+    a.b = b;
+    for (size_t i = 0; i < ng; i++) {
+        if (g[i].log_size + b != l) continue;
+        a.g[a.ng++] = {at[i].base, at[i].pc_stride, g[i].n_cols};
+        a.n_cols += g[i].n_cols;
+    }
+    return a;
+}
+
+struct CmWs {
+    uint32_t *coef[RSV_MAX_COMMIT_GROUPS], *lde[RSV_MAX_COMMIT_GROUPS], *na, *nbuf, *broots, *ta, *tb;
+};
+
+// Workspace of a pass of P proofs and nb blocks (bytes, with Carve's alignment); with w, also where each part goes.
+size_t cm_ws_bytes(const rsv_commit_group* g, size_t ng, uint32_t b, uint32_t Lmax, size_t P, size_t nb, char* base, CmWs* w) {
+    rsv::host::Carve sz{base};
+    CmWs t{};
     for (size_t i = 0; i < ng; i++) {
         const size_t row = (size_t)1 << g[i].log_size;
-        uint32_t* p = g[i].d_coeffs ? nullptr : sz.take<uint32_t>(P * g[i].n_cols * row);
-        if (coef) coef[i] = p;
-        uint32_t* q = g[i].d_lde ? nullptr : sz.take<uint32_t>(P * g[i].n_cols * nb * row);
-        if (lde) lde[i] = q;
+        t.coef[i] = g[i].d_coeffs ? nullptr : sz.take<uint32_t>(P * g[i].n_cols * row);
+        t.lde[i] = g[i].d_lde ? nullptr : sz.take<uint32_t>(P * g[i].n_cols * nb * row);
     }
     const size_t leaves = P * nb << (Lmax - b);
-    uint32_t* a = sz.take<uint32_t>(leaves * 8);
-    uint32_t* bb = sz.take<uint32_t>(std::max<size_t>(leaves / 2, 1) * 8);
-    uint32_t* r = sz.take<uint32_t>((P << b) * 8);
-    uint32_t* ta = sz.take<uint32_t>((P << (b - 1)) * 8);
-    uint32_t* tb = sz.take<uint32_t>((P << (b - 1)) * 8);
-    if (nodes_a) { *nodes_a = a; *nodes_b = bb; *broots = r; *top_a = ta; *top_b = tb; }
+    t.na = sz.take<uint32_t>(leaves * 8);
+    t.nbuf = sz.take<uint32_t>(std::max<size_t>(leaves / 2, 1) * 8);
+    t.broots = sz.take<uint32_t>((P << b) * 8);
+    t.ta = sz.take<uint32_t>((P << (b - 1)) * 8);
+    t.tb = sz.take<uint32_t>((P << (b - 1)) * 8);
+    if (w) *w = t;
     return sz.off;
 }
 
@@ -73,81 +158,43 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
     }
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
-    // the largest pass within the budget: all blocks of all proofs, then fewer blocks, then fewer proofs
-    const size_t budget = ws_budget(c);
-    size_t P = n, nb = (size_t)1 << b;
-    while (cm_ws_bytes(g, ng, b, Lmax, P, nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) > budget && nb > 1) nb >>= 1;
-    while (cm_ws_bytes(g, ng, b, Lmax, P, nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-    // every launch's grid stays below 2^31 workgroups
-    const uint64_t lim = (uint64_t)1 << 31;
-    for (size_t i = 0; i < ng; i++) {
-        const uint64_t n_rows = (uint64_t)P * g[i].n_cols * nb;
-        if (n_rows >= lim || (n_rows << g[i].log_size) / 256 >= lim || ((uint64_t)P * g[i].n_cols << g[i].log_size) / 256 >= lim) return RSV_E_SIZE;
-    }
-    if (((uint64_t)P * nb << (Lmax - b)) / 256 >= lim) return RSV_E_SIZE;
-    const uint32_t* tw_inv[RSV_MAX_COMMIT_GROUPS];
-    const uint32_t* tw_fwd[RSV_MAX_COMMIT_GROUPS];
-    for (size_t i = 0; i < ng; i++) {
-        int rc = cm_twiddles(c, g[i].log_size, true, &tw_inv[i]);
-        if (rc == RSV_OK) rc = cm_twiddles(c, g[i].log_size + b, false, &tw_fwd[i]);
-        if (rc != RSV_OK) return rc;
-    }
-    const size_t need = cm_ws_bytes(g, ng, b, Lmax, P, nb, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-    int rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, need);
+    const auto ws = [&](size_t P, size_t nb, char* base = nullptr, CmWs* w = nullptr) { return cm_ws_bytes(g, ng, b, Lmax, P, nb, base, w); };
+    const rsv::host::Pass pass = rsv::host::plan_pass(ws_budget(c), n, (size_t)1 << b, ws);
+    const size_t P = pass.P, nb = pass.nb;
+    for (size_t i = 0; i < ng; i++)
+        if (!cm_rows_fit((uint64_t)P * g[i].n_cols * nb, g[i].log_size)) return RSV_E_SIZE;
+    if (((uint64_t)P * nb << (Lmax - b)) / 256 >= CM_GRID_LIM) return RSV_E_SIZE;
+    const uint32_t *tw_inv[RSV_MAX_COMMIT_GROUPS], *tw_fwd[RSV_MAX_COMMIT_GROUPS];
+    int rc = cm_group_twiddles(c, g, ng, b, tw_inv, tw_fwd);
+    CmWs w;
+    if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, nb, base, &w); });
     if (rc != RSV_OK) return rc;
-    rsv::host::Carve cv{static_cast<char*>(c->ws_commit)};
-    uint32_t *coef[RSV_MAX_COMMIT_GROUPS], *lde[RSV_MAX_COMMIT_GROUPS], *na, *nbuf, *broots, *ta, *tb;
-    cm_ws_bytes(g, ng, b, Lmax, P, nb, &cv, coef, lde, &na, &nbuf, &broots, &ta, &tb);
     hipStream_t st = c->stream;
     for (size_t p0 = 0; p0 < n; p0 += P) {
         const size_t Pc = std::min(P, n - p0);
-        // interpolation: the columns -> the coefficients (d_coeffs or the workspace), masked proofs zero
-        uint32_t* cf[RSV_MAX_COMMIT_GROUPS];
+        // the coefficients, in d_coeffs or the workspace
+        const uint32_t* cf[RSV_MAX_COMMIT_GROUPS];
         for (size_t i = 0; i < ng; i++) {
-            const uint32_t log = g[i].log_size, cols = g[i].n_cols;
-            const size_t row = (size_t)1 << log;
-            cf[i] = g[i].d_coeffs ? g[i].d_coeffs + p0 * cols * row : coef[i];
-            rsv::CmRows r{cf[i], row, (uint64_t)Pc * cols, log, log, 1, 0};
-            rsv::CmSrc s{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, d_mask, cols, (uint32_t)p0,
-                         log ? 1u << (31 - log) : 1u};  // 2^-log = 2^(31-log) mod P
-            cm_fft<true>(st, r, s, tw_inv[i]);
+            uint32_t* dst = g[i].d_coeffs ? g[i].d_coeffs + (p0 * g[i].n_cols << g[i].log_size) : w.coef[i];
+            cm_interpolate(st, g[i], dst, p0, Pc, d_mask, false, tw_inv[i]);
+            cf[i] = dst;
         }
         for (size_t blk0 = 0; blk0 < ((size_t)1 << b); blk0 += nb) {
-            // the LDE of blocks blk0 .. blk0 + nb - 1
+            // the LDE of blocks blk0 .. blk0 + nb - 1, in d_lde or the workspace
+            CmBlocks at[RSV_MAX_COMMIT_GROUPS];
             for (size_t i = 0; i < ng; i++) {
                 const uint32_t log = g[i].log_size, cols = g[i].n_cols, N = log + b;
-                const size_t row = (size_t)1 << log;
-                rsv::CmRows r{};
-                if (g[i].d_lde) r = {g[i].d_lde + p0 * cols * ((size_t)1 << N) + (blk0 << log), (uint64_t)1 << N, 0, log, N, (uint32_t)nb, (uint32_t)blk0};
-                else r = {lde[i], (uint64_t)nb << log, 0, log, N, (uint32_t)nb, (uint32_t)blk0};
-                r.rows = (uint64_t)Pc * cols * nb;
-                rsv::CmSrc s{cf[i], (uint64_t)cols * row, row, nullptr, cols, 0, 1};
-                cm_fft<false>(st, r, s, tw_fwd[i]);
+                if (g[i].d_lde) at[i] = {g[i].d_lde + p0 * cols * ((size_t)1 << N) + (blk0 << log), (uint64_t)1 << N};
+                else at[i] = {w.lde[i], (uint64_t)nb << log};
+                cm_extend(st, g[i], cf[i], (uint64_t)cols << log, (uint64_t)Pc * cols, N, nb, blk0, at[i], tw_fwd[i]);
             }
             // the block subtrees, leaves first
             const uint32_t* child = nullptr;
             for (uint32_t l = Lmax; l + 1 > b; l--) {
-                rsv::CmHashArgs a{};
-                a.lw = l - b;
-                a.nb = (uint32_t)nb;
-                a.P = (uint32_t)Pc;
+                rsv::CmHashArgs a = cm_layer_args(g, ng, b, l, at, Pc, nb);
                 a.child = child;
-                a.b = b;
                 a.blk0 = (uint32_t)blk0;
-                for (size_t i = 0; i < ng; i++) {
-                    if (g[i].log_size + b != l) continue;
-                    rsv::CmLayerCols& lc = a.g[a.ng++];
-                    lc.n_cols = g[i].n_cols;
-                    if (g[i].d_lde) {
-                        lc.base = g[i].d_lde + p0 * g[i].n_cols * ((size_t)1 << l) + (blk0 << g[i].log_size);
-                        lc.pc_stride = (uint64_t)1 << l;
-                    } else {
-                        lc.base = lde[i];
-                        lc.pc_stride = (uint64_t)nb << g[i].log_size;
-                    }
-                    a.n_cols += g[i].n_cols;
-                }
-                a.out = l == b ? broots : ((Lmax - l) & 1 ? nbuf : na);
+                a.out = l == b ? w.broots : ((Lmax - l) & 1 ? w.nbuf : w.na);
                 hipLaunchKernelGGL(rsv::k_cm_hash_layer, dim3(grid_for((size_t)Pc * nb << a.lw, 256)), dim3(256), 0, st, a);
                 child = a.out;
             }
@@ -158,10 +205,10 @@ int commit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, uint
                 hipLaunchKernelGGL(rsv::k_cm_cap_level, dim3(grid_for(Pc << l, 256)), dim3(256), 0, st, lvl, stride, d_cap, cap_stride, l,
                                    (uint32_t)Pc, d_mask, (uint32_t)p0);
         };
-        const uint32_t* in = broots;
-        to_cap(broots, (uint64_t)8 << b, b);
+        const uint32_t* in = w.broots;
+        to_cap(w.broots, (uint64_t)8 << b, b);
         for (uint32_t l = b; l-- > 0;) {
-            uint32_t* out = (b - 1 - l) & 1 ? tb : ta;
+            uint32_t* out = (b - 1 - l) & 1 ? w.tb : w.ta;
             hipLaunchKernelGGL(rsv::k_cm_top, dim3(grid_for(Pc << l, 256)), dim3(256), 0, st, in, out, l, (uint32_t)Pc, d_roots, roots_stride,
                                d_mask, (uint32_t)p0);
             if (l) to_cap(out, (uint64_t)8 << l, l);

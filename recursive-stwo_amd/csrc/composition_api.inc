@@ -6,7 +6,8 @@
 // The driver streams the extended domain of 2^clb rows in aligned blocks of 2^(max(lp, lq) + 1) rows, the smallest that
 // hold every row's previous-row neighbour of both components (k_composition.hpp); a pass holds nc of them for P proofs.
 // The accumulator's values of the whole domain stay in the workspace (4 x 2^clb words per proof), are interpolated in
-// place, cut, and evaluated on the domain 2^(clb - 1).
+// place, cut, and evaluated on the domain 2^(clb - 1).  The groups' passes, interpolation and extension are commit_api.inc's
+// streaming helpers (a block of theirs is 2^log rows of a group); the accumulator's and the output's FFTs are the driver's own.
 
 namespace {
 
@@ -46,31 +47,23 @@ int composition(rsv_ctx* c, const rsv_commit_group* g, size_t n_plonk, size_t ng
     const uint32_t clb = co_clb(lp, lq), L3 = clb - 1, Lb = std::max(lp, lq);
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
-    // the largest pass within the budget: all blocks of all proofs, then fewer blocks, then fewer proofs
-    const size_t budget = ws_budget(c);
     const bool cut = !d_comp_coeffs;
-    size_t P = n, nc = (size_t)1 << (clb - Lb - 1);
-    while (co_ws_bytes(g, ng, lp, lq, P, nc, cut, nullptr, nullptr) > budget && nc > 1) nc >>= 1;
-    while (co_ws_bytes(g, ng, lp, lq, P, nc, cut, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-    const size_t R = nc << (Lb + 1);
+    const auto ws = [&](size_t P, size_t nc, char* base = nullptr, CoWs* w = nullptr) { return co_ws_bytes(g, ng, lp, lq, P, nc, cut, base, w); };
+    const rsv::host::Pass pass = rsv::host::plan_pass(ws_budget(c), n, (size_t)1 << (clb - Lb - 1), ws);
+    const size_t P = pass.P, nc = pass.nb, R = nc << (Lb + 1);
     uint32_t rlog = 0;
     while (((size_t)1 << rlog) < R) rlog++;
-    // every launch's grid stays below 2^31 workgroups
-    const uint64_t lim = (uint64_t)1 << 31;
-    for (size_t i = 0; i < ng; i++) {
-        const uint64_t rows = (uint64_t)P * g[i].n_cols * (R >> g[i].log_size);
-        if (rows >= lim || (rows << g[i].log_size) / 256 >= lim) return RSV_E_SIZE;
-    }
-    if ((((uint64_t)P * 8) << L3) / 256 >= lim || (uint64_t)P * std::max<size_t>(R / 256, 1) >= lim) return RSV_E_SIZE;
+    for (size_t i = 0; i < ng; i++)
+        if (!cm_rows_fit((uint64_t)P * g[i].n_cols * (R >> g[i].log_size), g[i].log_size)) return RSV_E_SIZE;
+    if ((((uint64_t)P * 8) << L3) / 256 >= CM_GRID_LIM || (uint64_t)P * std::max<size_t>(R / 256, 1) >= CM_GRID_LIM) return RSV_E_SIZE;
     const uint32_t *tw_inv[RSV_MAX_COMMIT_GROUPS], *tw_ext, *tw_acc, *tw_out;
     int rc = cm_twiddles(c, clb, false, &tw_ext);
     if (rc == RSV_OK) rc = cm_twiddles(c, clb, true, &tw_acc);
     if (rc == RSV_OK) rc = cm_twiddles(c, L3, false, &tw_out);
-    for (size_t i = 0; i < ng && rc == RSV_OK; i++) rc = cm_twiddles(c, g[i].log_size, true, &tw_inv[i]);
-    if (rc == RSV_OK) rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, co_ws_bytes(g, ng, lp, lq, P, nc, cut, nullptr, nullptr));
-    if (rc != RSV_OK) return rc;
+    if (rc == RSV_OK) rc = cm_group_twiddles(c, g, ng, 0, tw_inv, nullptr);
     CoWs w;
-    co_ws_bytes(g, ng, lp, lq, P, nc, cut, static_cast<char*>(c->ws_commit), &w);
+    if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, nc, base, &w); });
+    if (rc != RSV_OK) return rc;
     hipStream_t st = c->stream;
     hipLaunchKernelGGL(rsv::k_co_zinv, dim3(grid_for((size_t)1 << (clb - lp), 256)), dim3(256), 0, st, clb, lp, w.zinv[0]);
     hipLaunchKernelGGL(rsv::k_co_zinv, dim3(grid_for((size_t)1 << (clb - lq), 256)), dim3(256), 0, st, clb, lq, w.zinv[1]);
@@ -78,26 +71,14 @@ int composition(rsv_ctx* c, const rsv_commit_group* g, size_t n_plonk, size_t ng
         const size_t Pc = std::min(P, n - p0);
         hipLaunchKernelGGL(rsv::k_co_params, dim3(grid_for(Pc, 64)), dim3(64), 0, st, d_draws, d_sums, d_mask, (uint32_t)p0, (uint32_t)Pc, lp, lq,
                            w.par);
-        // interpolation: the columns -> the coefficients; a shared group once, masked proofs zero
-        for (size_t i = 0; i < ng; i++) {
-            const uint32_t log = g[i].log_size, cols = g[i].n_cols;
-            const size_t row = (size_t)1 << log;
-            const bool shared = g[i].proof_stride == 0;
-            if (shared && p0) continue;
-            rsv::CmRows r{w.coef[i], row, (uint64_t)(shared ? 1 : Pc) * cols, log, log, 1, 0};
-            rsv::CmSrc s{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, shared ? nullptr : d_mask, cols, (uint32_t)p0,
-                         1u << (31 - log)};
-            cm_fft<true>(st, r, s, tw_inv[i]);
-        }
+        for (size_t i = 0; i < ng; i++) cm_interpolate(st, g[i], w.coef[i], p0, Pc, d_mask, true, tw_inv[i]);
         for (size_t row0 = 0; row0 < ((size_t)1 << clb); row0 += R) {
             // the extension of the rows row0 .. row0 + R - 1: R >> log blocks of every column
             rsv::CoRows a[2] = {};
             for (size_t i = 0; i < ng; i++) {
                 const uint32_t log = g[i].log_size, cols = g[i].n_cols;
                 const size_t np = g[i].proof_stride ? Pc : 1;
-                rsv::CmRows r{w.ext[i], R, np * cols * (R >> log), log, clb, (uint32_t)(R >> log), (uint32_t)(row0 >> log)};
-                rsv::CmSrc s{w.coef[i], (uint64_t)cols << log, (uint64_t)1 << log, nullptr, cols, 0, 1};
-                cm_fft<false>(st, r, s, tw_ext);
+                cm_extend(st, g[i], w.coef[i], (uint64_t)cols << log, np * cols, clb, R >> log, row0 >> log, {w.ext[i], R}, tw_ext);
                 rsv::CoRows& k = a[i < n_plonk ? 0 : 1];
                 const uint32_t col0 = k.n_parts ? k.part[k.n_parts - 1].col0 + g[i - 1].n_cols : 0;
                 k.part[k.n_parts++] = {w.ext[i], g[i].proof_stride ? (uint64_t)cols * R : 0, col0};

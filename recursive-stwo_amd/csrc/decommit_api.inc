@@ -1,6 +1,9 @@
 // decommit_api.inc — rsv_decommit_sizes, rsv_decommit_tree_dev (the opening of a streamed tree at a list of positions:
 // queried values and Merkle witness in stwo's batched order) and rsv_witness_decommit_dev (trees 0, 1, 2 of the recursion
 // circuit's next proof): k_decommit.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after commit_api.inc.
+//
+// decommit_tree streams the groups with commit_api.inc's helpers; its blocks are entries of the proofs' block lists, so
+// it takes the extension as a pair (cm_extension) and launches it on the block-list kernels (dc_fft, k_dc_hash_layer).
 
 namespace {
 
@@ -10,10 +13,10 @@ struct DcWs {
 };
 
 // Workspace of an opening: the plan of all n proofs, and of a pass of P proofs and nb list entries (blocks) the
-// coefficients, the blocks in flight, two node layers and (own_cap) the caps.  With cv, also where each part goes.
+// coefficients, the blocks in flight, two node layers and (own_cap) the caps.  With w, also where each part goes.
 size_t dc_ws_bytes(const rsv_commit_group* g, size_t ng, uint32_t b, uint32_t top, size_t n, uint32_t nq, size_t maxb, size_t P, size_t nb,
-                   bool own_cap, rsv::host::Carve* cv, DcWs* w) {
-    rsv::host::Carve sz{cv ? cv->base : nullptr};
+                   bool own_cap, char* base, DcWs* w) {
+    rsv::host::Carve sz{base};
     DcWs t{};
     const size_t wcap = (size_t)nq * top;
     t.pl.cnt = sz.take<uint32_t>(n);
@@ -109,32 +112,23 @@ int decommit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, ui
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
     const bool full = mode != RSV_CAP_READ, own_cap = mode == RSV_CAP_NONE;
-    // a pass is P proofs times nb entries of their block lists: all of both, then fewer entries, then fewer proofs
+    // a pass is P proofs times nb entries of their block lists
     const size_t maxb = full ? (size_t)1 << b : std::min<size_t>(nq, (size_t)1 << b);
-    const size_t budget = ws_budget(c);
-    size_t P = n, nb = maxb;
-    while (dc_ws_bytes(g, ng, b, top, n, nq, maxb, P, nb, own_cap, nullptr, nullptr) > budget && nb > 1) nb = (nb + 1) / 2;
-    while (dc_ws_bytes(g, ng, b, top, n, nq, maxb, P, nb, own_cap, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-    const uint64_t lim = (uint64_t)1 << 31;
-    for (size_t i = 0; i < ng; i++) {
-        const uint64_t n_rows = (uint64_t)P * g[i].n_cols * nb;
-        if (n_rows >= lim || (n_rows << g[i].log_size) / 256 >= lim || ((uint64_t)P * g[i].n_cols << g[i].log_size) / 256 >= lim) return RSV_E_SIZE;
-    }
-    if (((uint64_t)P * nb << (top - b)) / 256 >= lim || ((uint64_t)n * std::max(vcap, wcap * 8)) / 256 >= lim ||
-        (full && ((uint64_t)n << (b + 4)) / 256 >= lim))
+    const auto ws = [&](size_t P, size_t nb, char* base = nullptr, DcWs* w = nullptr) {
+        return dc_ws_bytes(g, ng, b, top, n, nq, maxb, P, nb, own_cap, base, w);
+    };
+    const rsv::host::Pass pass = rsv::host::plan_pass(ws_budget(c), n, maxb, ws);
+    const size_t P = pass.P, nb = pass.nb;
+    for (size_t i = 0; i < ng; i++)
+        if (!cm_rows_fit((uint64_t)P * g[i].n_cols * nb, g[i].log_size)) return RSV_E_SIZE;
+    if (((uint64_t)P * nb << (top - b)) / 256 >= CM_GRID_LIM || ((uint64_t)n * std::max(vcap, wcap * 8)) / 256 >= CM_GRID_LIM ||
+        (full && ((uint64_t)n << (b + 4)) / 256 >= CM_GRID_LIM))
         return RSV_E_SIZE;
-    const uint32_t* tw_inv[RSV_MAX_COMMIT_GROUPS];
-    const uint32_t* tw_fwd[RSV_MAX_COMMIT_GROUPS];
-    for (size_t i = 0; i < ng; i++) {
-        int rc = cm_twiddles(c, g[i].log_size, true, &tw_inv[i]);
-        if (rc == RSV_OK) rc = cm_twiddles(c, g[i].log_size + b, false, &tw_fwd[i]);
-        if (rc != RSV_OK) return rc;
-    }
-    int rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, dc_ws_bytes(g, ng, b, top, n, nq, maxb, P, nb, own_cap, nullptr, nullptr));
-    if (rc != RSV_OK) return rc;
-    rsv::host::Carve cv{static_cast<char*>(c->ws_commit)};
+    const uint32_t *tw_inv[RSV_MAX_COMMIT_GROUPS], *tw_fwd[RSV_MAX_COMMIT_GROUPS];
+    int rc = cm_group_twiddles(c, g, ng, b, tw_inv, tw_fwd);
     DcWs w;
-    dc_ws_bytes(g, ng, b, top, n, nq, maxb, P, nb, own_cap, &cv, &w);
+    if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, nb, base, &w); });
+    if (rc != RSV_OK) return rc;
     hipStream_t st = c->stream;
     // every element of the outputs is defined: zero, then the planned words
     hipLaunchKernelGGL(rsv::k_dc_zero, dim3(grid_for(n * vcap, 256)), dim3(256), 0, st, d_values, vstride, (uint64_t)vcap, (uint64_t)n);
@@ -149,43 +143,24 @@ int decommit_tree(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, ui
         const rsv::DcPlan pl = dc_plan_at(w.pl, p0);
         const rsv::DcOut out{d_values + p0 * vstride, d_witness + p0 * wstride, vstride, wstride};
         uint32_t* cap = own_cap ? w.cap : d_cap + p0 * cap_stride;
-        // interpolation: the columns -> the coefficients, masked proofs zero
-        for (size_t i = 0; i < ng; i++) {
-            const uint32_t log = g[i].log_size, cols = g[i].n_cols;
-            const size_t row = (size_t)1 << log;
-            rsv::CmRows r{w.coef[i], row, (uint64_t)Pc * cols, log, log, 1, 0};
-            rsv::CmSrc s{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, d_mask, cols, (uint32_t)p0, log ? 1u << (31 - log) : 1u};
-            cm_fft<true>(st, r, s, tw_inv[i]);
-        }
+        for (size_t i = 0; i < ng; i++) cm_interpolate(st, g[i], w.coef[i], p0, Pc, d_mask, false, tw_inv[i]);
         for (size_t k0 = 0; k0 < maxb; k0 += nb) {
             const size_t nbc = std::min(nb, maxb - k0);
             rsv::CmList L{pl.blocks, pl.cnt, (uint32_t)maxb, (uint32_t)k0, 0, cstride};
             // the LDE of the list's entries k0 .. k0 + nbc - 1
+            CmBlocks at[RSV_MAX_COMMIT_GROUPS];
             for (size_t i = 0; i < ng; i++) {
                 const uint32_t log = g[i].log_size, cols = g[i].n_cols;
-                const size_t row = (size_t)1 << log;
-                rsv::CmRows r{w.lde[i], (uint64_t)nbc << log, (uint64_t)Pc * cols * nbc, log, log + b, (uint32_t)nbc, 0};
-                rsv::CmSrc s{w.coef[i], (uint64_t)cols * row, row, nullptr, cols, 0, 1};
+                at[i] = {w.lde[i], (uint64_t)nbc << log};
                 L.cols = cols;
-                dc_fft(st, r, s, tw_fwd[i], L);
+                const CmExt e = cm_extension(g[i], w.coef[i], (uint64_t)cols << log, (uint64_t)Pc * cols, log + b, nbc, 0, at[i]);
+                dc_fft(st, e.r, e.s, tw_fwd[i], L);
             }
             // their subtrees, leaves first; after each layer, what the plan takes from it
             const uint32_t* child = nullptr;
             for (uint32_t l = top; l + 1 > b; l--) {
-                rsv::CmHashArgs a{};
-                a.lw = l - b;
-                a.nb = (uint32_t)nbc;
-                a.P = (uint32_t)Pc;
+                rsv::CmHashArgs a = cm_layer_args(g, ng, b, l, at, Pc, nbc);
                 a.child = child;
-                a.b = b;
-                for (size_t i = 0; i < ng; i++) {
-                    if (g[i].log_size + b != l) continue;
-                    rsv::CmLayerCols& lc = a.g[a.ng++];
-                    lc.n_cols = g[i].n_cols;
-                    lc.base = w.lde[i];
-                    lc.pc_stride = (uint64_t)nbc << g[i].log_size;
-                    a.n_cols += g[i].n_cols;
-                }
                 a.out = l == b ? cap : ((top - l) & 1 ? w.nbuf : w.na);
                 if (l > b || full)
                     hipLaunchKernelGGL(rsv::k_dc_hash_layer, dim3(grid_for((size_t)Pc * nbc << a.lw, 256)), dim3(256), 0, st, a, L);

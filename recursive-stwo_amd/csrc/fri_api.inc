@@ -4,7 +4,7 @@
 // composition_api.inc.
 //
 // Quotients: one quotient column (one LDE log size) at a time; its groups are interpolated (from evaluations) and
-// extended block by block as commit_tree does, and k_fr_rows consumes each pass of blocks.  Commit: the per-layer form,
+// extended block by block with commit_api.inc's streaming helpers, and k_fr_rows consumes each pass of blocks.  Commit: the per-layer form,
 // one launch per tree level, one channel launch and one or two fold launches per layer; there is no single-workgroup tail
 // kernel for the small layers.
 
@@ -62,8 +62,6 @@ int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
     const bool interpolate = source == RSV_SAMPLE_COLUMNS;
-    const size_t budget = ws_budget(c);
-    const uint64_t lim = (uint64_t)1 << 31;
     hipStream_t st = c->stream;
     uint64_t col_off = 0;
     for (size_t s = 0; s < ns; s++) {
@@ -73,27 +71,23 @@ int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_
             if (g[i].log_size == ls)
                 for (uint32_t k = 0; k < n_points; k++) terms += fs[i].hi[k] > fs[i].lo[k] ? fs[i].hi[k] - fs[i].lo[k] : 0;
         const uint32_t par_words = rsv::FR_TERMS_AT + 4 * terms;
-        // the largest pass within the budget: all blocks of all proofs, then fewer blocks, then fewer proofs
-        size_t P = n, nb = (size_t)1 << b;
-        while (fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr) > budget && nb > 1) nb >>= 1;
-        while (fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-        // every launch's grid stays below 2^31 workgroups
-        for (size_t i = 0; i < ng; i++) {
-            if (g[i].log_size != ls) continue;
-            const uint64_t rows = (uint64_t)P * g[i].n_cols * nb;
-            if (rows >= lim || (rows << ls) / 256 >= lim) return RSV_E_SIZE;
-        }
-        const size_t R = nb << ls;
-        if ((uint64_t)P * std::max<size_t>(R / 256, 1) >= lim) return RSV_E_SIZE;
+        const auto ws = [&](size_t P, size_t nb, char* base = nullptr, FrWs* w = nullptr) {
+            return fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, base, w);
+        };
+        const rsv::host::Pass pass = rsv::host::plan_pass(ws_budget(c), n, (size_t)1 << b, ws);
+        const size_t P = pass.P, nb = pass.nb, R = nb << ls;
+        for (size_t i = 0; i < ng; i++)
+            if (g[i].log_size == ls && !cm_rows_fit((uint64_t)P * g[i].n_cols * nb, ls)) return RSV_E_SIZE;
+        if ((uint64_t)P * std::max<size_t>(R / 256, 1) >= CM_GRID_LIM) return RSV_E_SIZE;
         uint32_t rlog = 0;
         while (((size_t)1 << rlog) < R) rlog++;
+        // one table per domain: every group of the pass has the size ls
         const uint32_t *tw_inv = nullptr, *tw_fwd;
         int rc = cm_twiddles(c, N, false, &tw_fwd);
         if (rc == RSV_OK && interpolate) rc = cm_twiddles(c, ls, true, &tw_inv);
-        if (rc == RSV_OK) rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, nullptr, nullptr));
-        if (rc != RSV_OK) return rc;
         FrWs w;
-        fr_ws_bytes(g, ng, ls, interpolate, P, nb, par_words, static_cast<char*>(c->ws_commit), &w);
+        if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, nb, base, &w); });
+        if (rc != RSV_OK) return rc;
         for (size_t p0 = 0; p0 < n; p0 += P) {
             const size_t Pc = std::min(P, n - p0);
             rsv::FrRows a{};
@@ -104,7 +98,6 @@ int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_
             for (size_t i = 0; i < ng; i++) {
                 if (g[i].log_size != ls) continue;
                 const uint32_t cols = g[i].n_cols;
-                const size_t row = (size_t)1 << ls;
                 const bool shared = g[i].proof_stride == 0;
                 at[col.ng] = i;
                 rsv::FrGroup& k = col.g[col.ng++];
@@ -126,13 +119,8 @@ int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_
                     continue;
                 }
                 cf[i] = w.coef[i];
-                cf_stride[i] = shared ? 0 : (uint64_t)cols * row;
-                if (shared && p0) continue;
-                // the commitment's interpolation: the columns -> the coefficients; a shared group once, masked proofs zero
-                rsv::CmRows r{w.coef[i], row, (uint64_t)(shared ? 1 : Pc) * cols, ls, ls, 1, 0};
-                rsv::CmSrc src{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, shared ? nullptr : d_mask, cols, (uint32_t)p0,
-                               1u << (31 - ls)};
-                cm_fft<true>(st, r, src, tw_inv);
+                cf_stride[i] = shared ? 0 : (uint64_t)cols << ls;
+                cm_interpolate(st, g[i], w.coef[i], p0, Pc, d_mask, true, tw_inv);
             }
             col.np = n_points;
             col.par_words = par_words;
@@ -149,11 +137,8 @@ int fri_quotients(rsv_ctx* c, const rsv_commit_group* g, const FrSpec* fs, size_
                 // the LDE of blocks blk0 .. blk0 + nb - 1 of every group of this size
                 for (uint32_t k = 0; k < col.ng; k++) {
                     const size_t i = at[k];
-                    const uint32_t cols = g[i].n_cols;
                     const size_t np = g[i].proof_stride ? Pc : 1;
-                    rsv::CmRows r{w.ext[i], (uint64_t)nb << ls, (uint64_t)np * cols * nb, ls, N, (uint32_t)nb, (uint32_t)blk0};
-                    rsv::CmSrc src{cf[i], cf_stride[i], (uint64_t)1 << ls, nullptr, cols, 0, 1};
-                    cm_fft<false>(st, r, src, tw_fwd);
+                    cm_extend(st, g[i], cf[i], cf_stride[i], np * g[i].n_cols, N, nb, blk0, {w.ext[i], (uint64_t)nb << ls}, tw_fwd);
                 }
                 a.row0 = (uint64_t)blk0 << ls;
                 hipLaunchKernelGGL(rsv::k_fr_rows, dim3((unsigned)(Pc * std::max<size_t>(R / 256, 1))), dim3(256), 0, st, a);
@@ -202,19 +187,17 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         qstride += (uint64_t)4 << sizes[s];
     }
     for (uint32_t i = 0; i < n_inner; i++) lstride += (uint64_t)4 << (M - 1 - i);
-    const size_t budget = ws_budget(c);
-    size_t P = n;
-    while (fr_commit_ws_bytes(M, L, P, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-    if (((uint64_t)P << M) / 256 >= ((uint64_t)1 << 31)) return RSV_E_SIZE;
+    const auto ws = [&](size_t P, size_t, char* base = nullptr, FrCommitWs* w = nullptr) { return fr_commit_ws_bytes(M, L, P, base, w); };
+    const size_t P = rsv::host::plan_pass(ws_budget(c), n, 1, ws).P;
+    if (((uint64_t)P << M) / 256 >= CM_GRID_LIM) return RSV_E_SIZE;
     // 1 / y of every column's pairs, 1 / x of every inner layer's and of the last layer's interpolation
     const uint32_t *inv_y[FR_MAX_SIZES], *inv_x[RSV_MAX_LOG_SIZE + 2] = {};
     int rc = RSV_OK;
     for (size_t s = 0; s < ns && rc == RSV_OK; s++) rc = cm_twiddles(c, sizes[s], true, &inv_y[s]);
     for (uint32_t l = L; l < M && rc == RSV_OK; l++) rc = cm_twiddles(c, l + 1, true, &inv_x[l]);  // the line domain 2^l
-    if (rc == RSV_OK) rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, fr_commit_ws_bytes(M, L, P, nullptr, nullptr));
-    if (rc != RSV_OK) return rc;
     FrCommitWs w;
-    fr_commit_ws_bytes(M, L, P, static_cast<char*>(c->ws_commit), &w);
+    if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, 1, base, &w); });
+    if (rc != RSV_OK) return rc;
     hipStream_t st = c->stream;
     const uint64_t rstride = (uint64_t)(1 + n_inner) * 8, astride = (uint64_t)(1 + n_inner) * 4;
     auto column_of = [&](uint32_t l) -> int {

@@ -1,5 +1,6 @@
 // host_logic.hpp — the HOST-side decisions of a verify call that touch no device: how a mixed batch is bucketed by
-// shape, and how the per-query stages are cut into groups that fit the workspace budget.  Plain C++ (no HIP): included by
+// shape, how the per-query stages are cut into groups that fit the workspace budget, and (plan_pass) how a stage of the
+// next proof sizes a pass of proofs and blocks to that budget.  Plain C++ (no HIP): included by
 // verify_api.inc, and compiled on its own by g++ with AddressSanitizer + UBSan for tests/host_logic_asan.cpp, which drives
 // it from recorded and adversarial shape arrays — the host code of the mixed-batch path had never seen a sanitizer
 // before round 4 (the r3a crash pointed at exactly this code or at the test's own threads).
@@ -188,6 +189,19 @@ inline size_t plan_groups(const std::vector<Bucket>& buckets, const GroupPolicy&
     }
     flush();
     return need;
+}
+
+// One pass of a stage that streams the next proof's column groups (commit_api.inc): P proofs times nb blocks.
+struct Pass { size_t P, nb; };
+
+// The largest pass whose workspace bytes(P, nb) fits the budget: all max_nb blocks of all n proofs, then fewer blocks
+// (halved, rounded up, down to one), then fewer proofs; {1, 1} where nothing fits.  A stage without blocks passes 1.
+template <class Bytes>
+Pass plan_pass(size_t budget, size_t n, size_t max_nb, Bytes bytes) {
+    Pass p{n, max_nb};
+    while (p.nb > 1 && bytes(p.P, p.nb) > budget) p.nb = (p.nb + 1) / 2;
+    while (p.P > 1 && bytes(p.P, p.nb) > budget) p.P = (p.P + 1) / 2;
+    return p;
 }
 
 // Which FRI tree each grid row (blockIdx.y) of a SMALL k_pair_merkle launch hashes.  A launch whose workgroups are all

@@ -4,7 +4,8 @@
 //
 // The driver has one path switch: a column of at most 2^SP_CHUNK_LOG = 2^13 rows is one workgroup of k_sp_dot, a larger
 // one 2^(log - 13) of them, whose sums k_sp_finish adds.  Inside the kernel a column below 2^8 rows leaves lanes idle and
-// one below 2^10 takes the loop without the four-way unrolling.
+// one below 2^10 takes the loop without the four-way unrolling.  Pass sizing, tables and the interpolation are
+// commit_api.inc's streaming helpers; there are no blocks, a pass is P proofs.
 
 namespace {
 
@@ -59,26 +60,17 @@ int sample_groups(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, co
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
     const bool interpolate = source == RSV_SAMPLE_COLUMNS;
-    const size_t budget = ws_budget(c);
-    size_t P = n;
-    while (sp_ws_bytes(g, sg, ng, interpolate, P, nullptr, nullptr) > budget && P > 1) P = (P + 1) / 2;
-    // every launch's grid stays below 2^31 workgroups
-    const uint64_t lim = (uint64_t)1 << 31;
+    const auto ws = [&](size_t P, size_t, char* base = nullptr, SpWs* w = nullptr) { return sp_ws_bytes(g, sg, ng, interpolate, P, base, w); };
+    const size_t P = rsv::host::plan_pass(ws_budget(c), n, 1, ws).P;
     for (size_t i = 0; i < ng; i++) {
         const uint32_t log = g[i].log_size;
-        const uint64_t rows = (uint64_t)P * g[i].n_cols;
-        if (rows >= lim || (rows << log) / 256 >= lim || (uint64_t)P * sg[i].np * rsv::sp_table_entries(log) / 256 >= lim) return RSV_E_SIZE;
+        if (!cm_rows_fit((uint64_t)P * g[i].n_cols, log) || (uint64_t)P * sg[i].np * rsv::sp_table_entries(log) / 256 >= CM_GRID_LIM) return RSV_E_SIZE;
     }
     const uint32_t* tw_inv[RSV_MAX_COMMIT_GROUPS] = {};
-    if (interpolate)
-        for (size_t i = 0; i < ng; i++) {
-            const int rc = cm_twiddles(c, g[i].log_size, true, &tw_inv[i]);
-            if (rc != RSV_OK) return rc;
-        }
-    int rc = ensure_buf(c, &c->ws_commit, &c->ws_commit_bytes, sp_ws_bytes(g, sg, ng, interpolate, P, nullptr, nullptr));
-    if (rc != RSV_OK) return rc;
+    int rc = cm_group_twiddles(c, g, ng, 0, interpolate ? tw_inv : nullptr, nullptr);
     SpWs w;
-    sp_ws_bytes(g, sg, ng, interpolate, P, static_cast<char*>(c->ws_commit), &w);
+    if (rc == RSV_OK) rc = cm_workspace(c, [&](char* base) { return ws(P, 1, base, &w); });
+    if (rc != RSV_OK) return rc;
     hipStream_t st = c->stream;
     for (size_t p0 = 0; p0 < n; p0 += P) {
         const size_t Pc = std::min(P, n - p0);
@@ -91,10 +83,7 @@ int sample_groups(rsv_ctx* c, const rsv_commit_group* g, size_t ng, size_t n, co
                                    (uint32_t)p0, (uint32_t)Pc, w.wt[i]);
             rsv::SpCols s{g[i].d_cols + p0 * g[i].proof_stride, g[i].proof_stride, row, d_mask, (uint32_t)p0, cols, log};
             if (interpolate) {
-                // the commitment's interpolation: the columns -> the coefficients in the workspace, masked proofs zero
-                rsv::CmRows r{w.coef[i], row, (uint64_t)Pc * cols, log, log, 1, 0};
-                rsv::CmSrc src{s.base, g[i].proof_stride, row, d_mask, cols, (uint32_t)p0, log ? 1u << (31 - log) : 1u};
-                cm_fft<true>(st, r, src, tw_inv[i]);
+                cm_interpolate(st, g[i], w.coef[i], p0, Pc, d_mask, false, tw_inv[i]);
                 s.base = w.coef[i];
                 s.pstride = (uint64_t)cols * row;
             }

@@ -8,6 +8,10 @@
 //   host_logic_asan buckets <seed> <rounds>           host_logic.hpp: bucket_by_shape + plan_groups on seeded shape arrays —
 //                                                     recorded fixture shapes, garbage, thousands of distinct shapes, rejected
 //                                                     proofs, 1 .. 128 queries — with the invariants the launcher relies on
+//   host_logic_asan passes <seed> <rounds>            host_logic.hpp: plan_pass on seeded workspace costs, monotone in the proofs
+//                                                     and the blocks of a pass — block counts that are powers of two and that
+//                                                     are not, budgets from below the smallest pass to above the largest —
+//                                                     against the two loops every streaming driver used to carry
 //
 // The hints file: 16 header words (magic, proof bytes, nq, M, n_inner, flow_count, n_pi, copies, 0...), then the proof
 // (padded to words), trace_sib, trace_pos, trace_cols, fri_sib, fri_cols, flow [flow_count][32], swap (bytes, padded),
@@ -247,9 +251,65 @@ static int run_buckets(uint32_t seed, int rounds) {
     return 0;
 }
 
+// A workspace as the streaming drivers carve it (Carve: every part rounded up to 256 bytes): a fixed part, parts per
+// proof, per block and per (proof, block), and one that never falls below a word.  Monotone in P and in nb.
+struct PassCost {
+    size_t fixed, per_proof, per_block, per_both, leaves;
+    size_t operator()(size_t P, size_t nb) const {
+        host::Carve sz{nullptr};
+        sz.take<uint32_t>(fixed);
+        sz.take<uint32_t>(P * per_proof);
+        sz.take<uint32_t>(nb * per_block);
+        sz.take<uint32_t>(P * nb * per_both);
+        sz.take<uint32_t>(std::max<size_t>(P * nb * leaves / 2, 1));
+        return sz.off;
+    }
+};
+
+static int run_passes(uint32_t seed, int rounds) {
+    std::mt19937 rng(seed);
+    const size_t block_counts[] = {1, 2, 4, 16, 256, 3, 27, 80};
+    size_t cut_blocks = 0, cut_proofs = 0, whole = 0, floor = 0;
+    for (int r = 0; r < rounds; r++) {
+        const size_t n = r % 7 == 0 ? 1 : 1 + rng() % (r % 3 ? 40 : 5000), max_nb = block_counts[r % 8];
+        const PassCost cost{rng() % 4096, rng() % 512, rng() % 2048, 1 + rng() % 65536, rng() % 64};
+        const size_t lo = cost(1, 1), hi = cost(n, max_nb);
+        CHECK(lo <= hi);
+        // below the smallest pass, each end exactly and one byte either side, above the largest pass, seeded points between
+        std::vector<size_t> budgets = {0, lo / 2, lo - 1, lo, lo + 1, hi - 1, hi, hi + 1, 2 * hi, cost(n, 1) - 1, cost(n, 1), cost(1, max_nb)};
+        for (int k = 0; k < 24; k++) budgets.push_back(lo + (size_t)(((uint64_t)rng() << 32 | rng()) % (hi - lo + 1)));
+        for (const size_t budget : budgets) {
+            size_t calls = 0;
+            const host::Pass got = host::plan_pass(budget, n, max_nb, [&](size_t P, size_t nb) {
+                CHECK(P >= 1 && P <= n && nb >= 1 && nb <= max_nb);
+                calls++;
+                return cost(P, nb);
+            });
+            // the two loops as the drivers wrote them
+            size_t P = n, nb = max_nb;
+            while (cost(P, nb) > budget && nb > 1) nb = (nb + 1) / 2;
+            while (cost(P, nb) > budget && P > 1) P = (P + 1) / 2;
+            CHECK(got.P == P && got.nb == nb);
+            CHECK(cost(got.P, got.nb) <= budget || (got.P == 1 && got.nb == 1));
+            if (hi <= budget) CHECK(got.P == n && got.nb == max_nb);
+            if (cost(n, 1) <= budget) CHECK(got.P == n);  // monotone: some nb fits at P == n exactly when nb == 1 does
+            CHECK(calls <= 2 + 8 + 13);                   // a probe per halving: log2 of 256 blocks, of 5000 proofs
+            whole += got.P == n && got.nb == max_nb;
+            cut_blocks += got.nb < max_nb;
+            cut_proofs += got.P < n;
+            floor += cost(got.P, got.nb) > budget;
+        }
+    }
+    CHECK(rounds < 16 || (whole && cut_blocks && cut_proofs && floor));  // every outcome was met
+    printf("passes: %d rounds, invariants hold (%zu whole, %zu fewer blocks, %zu fewer proofs, %zu over budget at (1, 1))\n", rounds, whole,
+           cut_blocks, cut_proofs, floor);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 4 && std::string(argv[1]) == "program") return run_program(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "buckets") return run_buckets((uint32_t)atoi(argv[2]), atoi(argv[3]));
-    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds>\n");
+    if (argc == 4 && std::string(argv[1]) == "passes") return run_passes((uint32_t)atoi(argv[2]), atoi(argv[3]));
+    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds> | passes <seed> <rounds>\n");
     return 2;
 }

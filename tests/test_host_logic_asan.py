@@ -11,7 +11,8 @@ the C++ mirror of the reference's gadgets) are plain C++ headers that g++ compil
     with every heap access instrumented;
   * with truncated / misaligned / absurd templates, hints that do not belong to the template, mutated programs;
   * with seeded shape arrays (the fixture chain's mix, one shape per proof, everything rejected, tiny query counts) against
-    the invariants the launcher relies on."""
+    the invariants the launcher relies on;
+  * with seeded workspace costs and budgets against the pass sizing of the next proof's streaming stages (plan_pass)."""
 import os
 import subprocess
 
@@ -36,6 +37,14 @@ def harness(tmp_path_factory):
 def test_bucketing_and_groups_under_sanitizers(harness):
     for seed, rounds in ((1, 25), (2, 40)):
         out = subprocess.run([harness, "buckets", str(seed), str(rounds)], capture_output=True, text=True, env=SAN_ENV, timeout=600)
+        assert out.returncode == 0 and "invariants hold" in out.stdout, out.stdout + out.stderr
+        assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
+def test_pass_sizing_under_sanitizers(harness):
+    """plan_pass (host_logic.hpp), which sizes the passes of every driver that streams the next proof's column groups."""
+    for seed, rounds in ((1, 64), (2, 200)):
+        out = subprocess.run([harness, "passes", str(seed), str(rounds)], capture_output=True, text=True, env=SAN_ENV, timeout=600)
         assert out.returncode == 0 and "invariants hold" in out.stdout, out.stdout + out.stderr
         assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
