@@ -931,6 +931,38 @@ int rsv_witness_fri_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uin
                         uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                         uint32_t* d_last_poly, uint8_t* d_low_degree);
 
+/* ---- proof of work and queries of the next proof -------------------------------------------------------------------------
+ * The definition is the verifier's (rsv_verify_batch_dev checks the same mix and draws the same positions).  A nonce is
+ * mixed as the QM31 (w0, w1, w2, 0): w0 = nonce & (2^22 - 1), w1 = (nonce >> 22) & (2^21 - 1), w2 = (nonce >> 43) &
+ * (2^21 - 1) — one permutation of (w0, w1, w2, 0, 0, 0, 0, 0 || digest), whose capacity half is the new digest; it
+ * qualifies when the canonical digest word 0 has pow_bits low zero bits.  The queries are the words of the draws that
+ * follow (n_sent restarts at 0 after the mix): ceil(n_queries / 8) draws of eight words each, in order, each word cut
+ * to its low log_size bits; the recursion circuit's surplus draws are not made.
+ *
+ * rsv_pow_grind_dev: the smallest nonce >= start whose mix leaves pow_bits low zero bits in digest word 0 (the
+ * reference's grinder starts at 0), among the max_tries candidates start .. start + max_tries - 1 (max_tries 0: 2^(pow_bits
+ * + 6), with which a search fails with probability about e^-64).
+ *   d_channel   [n][16] in the form rsv_witness_fri_dev leaves: digest, n_sent, seven zero words.  Read and updated: the
+ *               nonce is mixed in.
+ *   d_nonce     [n][2], low word first.
+ *   d_ok        [n] bytes, required: read as the mask, and cleared for a proof whose search is exhausted.
+ * A masked or exhausted proof gets a zero nonce and a zeroed channel; its neighbours are unaffected.  One lane per
+ * candidate; a lane that finds a qualifying nonce lowers the proof's minimum, every lane leaves at the first of its
+ * candidates that is not below that minimum.  Refusals before any device work: a NULL pointer: RSV_E_NULL; pow_bits >
+ * RSV_MAX_POW_BITS, n 0 or above 2^20, start + max_tries overflowing 64 bits, a pointer not 4-byte aligned: RSV_E_SIZE.
+ * Enqueued on the context's stream with no host synchronisation but the workspace's growth. */
+int rsv_pow_grind_dev(rsv_ctx* ctx, uint32_t pow_bits, uint64_t start, uint64_t max_tries, size_t n, uint8_t* d_ok, uint32_t* d_channel,
+                      uint32_t* d_nonce);
+/* The query positions: d_channel [n][16] as rsv_pow_grind_dev left it (read and updated: n_sent moves on by the draws);
+ * d_queries [n][n_queries], positions of log_size bits in draw order, unsorted and with duplicates kept — what
+ * rsv_decommit_tree_dev takes; d_queries_low (may be NULL) [n][n_queries]: the same positions >> (log_size - log_size_low),
+ * for the trees whose largest layer is smaller.  1 <= n_queries <= RSV_MAX_QUERIES, 1 <= log_size_low <= log_size <=
+ * RSV_MAX_LOG_SIZE.  A masked proof (d_mask [n], may be NULL) gets zero positions and a zeroed channel.  Refusals before any
+ * device work: a NULL pointer (but d_mask, d_queries_low): RSV_E_NULL; n 0 or above 2^20, the limits above, a pointer not
+ * 4-byte aligned: RSV_E_SIZE.  Enqueued on the context's stream with no host synchronisation. */
+int rsv_draw_queries_dev(rsv_ctx* ctx, size_t n, const uint8_t* d_mask, uint32_t n_queries, uint32_t log_size, uint32_t log_size_low,
+                         uint32_t* d_channel, uint32_t* d_queries, uint32_t* d_queries_low);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -247,6 +247,8 @@ def _load() -> ctypes.CDLL:
                                                  ctypes.c_int, vp, ctypes.c_uint32, vp, vp, vp]),
         "rsv_fri_commit_dev": (ctypes.c_int, [vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp]),
         "rsv_witness_fri_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12),
+        "rsv_pow_grind_dev": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
+        "rsv_draw_queries_dev": (ctypes.c_int, [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -297,6 +299,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_sample_tree_dev", "rsv_witness_sample_dev",
            "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
            "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
+           "rsv_pow_grind_dev", "rsv_draw_queries_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -1240,6 +1243,24 @@ class Context:
                                        ptr(d_accept), ptr(d_ok), n, log_blowup, log_last, ptr(d_comp), ptr(d_oods), ptr(d_samples),
                                        ptr(d_samples3), ptr(d_channel), ptr(d_after), ptr(d_quot), ptr(d_roots), ptr(d_alphas), ptr(d_layers),
                                        ptr(d_last_poly), ptr(d_low_degree)), "rsv_witness_fri_dev")
+
+    def pow_grind(self, pow_bits: int, n: int, d_ok, d_channel, d_nonce, start: int = 0, max_tries: int = 0):
+        """rsv_pow_grind_dev: the smallest nonce >= start (of max_tries candidates; 0: 2^(pow_bits + 6)) whose mix into
+        d_channel uint32[n, 16] leaves pow_bits low zero bits in digest word 0: d_nonce uint32[n, 2] (low word first), the
+        channel updated; d_ok uint8[n] is the mask and is cleared where the search is exhausted; enqueued on the context's
+        stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_pow_grind_dev(self._h, pow_bits, start, max_tries, n, ptr(d_ok), ptr(d_channel), ptr(d_nonce)), "rsv_pow_grind_dev")
+
+    def draw_queries(self, n: int, n_queries: int, log_size: int, log_size_low: int, d_channel, d_queries, d_queries_low=None, d_mask=None):
+        """rsv_draw_queries_dev: ceil(n_queries / 8) draws from d_channel uint32[n, 16] (updated): d_queries uint32[n,
+        n_queries] the positions of log_size bits in draw order, d_queries_low (may be None) the same >> (log_size -
+        log_size_low); d_mask uint8[n] (may be None); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_draw_queries_dev(self._h, n, ptr(d_mask), n_queries, log_size, log_size_low, ptr(d_channel), ptr(d_queries),
+                                        ptr(d_queries_low)), "rsv_draw_queries_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

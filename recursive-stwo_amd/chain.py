@@ -1,22 +1,23 @@
 """Chain: the buffers and stages of "the next proof on the GPU" as one object.
 
-Every stage of the chain (Context.witness, witness_trace, witness_commit, witness_decommit, witness_tree3, witness_sample,
-witness_fri) takes the same program, trace columns and flags, followed by its own tensors.  A Chain owns those tensors,
+Every stage of the chain up to FRI (Context.witness, witness_trace, witness_commit, witness_decommit, witness_tree3,
+witness_sample, witness_fri) takes the same program, trace columns and flags, followed by its own tensors.  A Chain owns those tensors,
 allocates each when the stage that writes it first runs, and makes each Context call with the arguments drawn from itself.
 The Context methods stay the 1:1 layer over the C-ABI; nothing here reaches past them.
 """
 import numpy as np
 
-from . import composition_log_size, fri_sizes, pack
+from . import CAP_NONE, CAP_READ, composition_log_size, decommit_sizes, fri_sizes, pack, witness_decommit_sizes
 
 _FLAGS = ("acc", "ok", "low_degree")
 _WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
-            "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree")
+            "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree",
+            "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3")
 
 
 class Chain:
     """Chain(ctx, program, n, log_blowup): n proofs through witness() -> trace() -> commit() -> decommit() / tree3() ->
-    sample() -> fri().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
+    sample() -> fri() -> pow() -> open().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
     ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
     a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3)."""
 
@@ -129,6 +130,40 @@ class Chain:
         self.ctx.witness_fri(*self._lead(), b, last, self.comp, self.oods, self.samples, self.samples3, self.channel, self.after, self.quot,
                              self.fri_roots, self.alphas, self.layers, self.last_poly, self.low_degree, d_ok=self.ok)
         self.done.add("fri")
+
+    def pow(self, pow_bits, n_queries, start=0, max_tries=0):
+        """Context.pow_grind, then Context.draw_queries: the nonce [n, 2], the queries [n, n_queries] at the largest column's
+        log size (fri_sizes' sizes[0]) and queries_low, the same at max(lp, lq) + log_blowup, where trees 0-2 are opened; the
+        channel moves on, ok is cleared where the search is exhausted."""
+        self._need("pow", "fri")
+        n = self.n
+        if self.nonce is None or self.queries.shape[1] != n_queries:
+            self.nonce, self.queries, self.queries_low = self._new(n, 2), self._new(n, n_queries), self._new(n, n_queries)
+        M = fri_sizes(self.lp, self.lq, self.log_blowup, self.log_last)["sizes"][0]
+        self.ctx.pow_grind(pow_bits, n, self.ok, self.channel, self.nonce, start=start, max_tries=max_tries)
+        self.ctx.draw_queries(n, n_queries, M, max(self.lp, self.lq) + self.log_blowup, self.channel, self.queries, self.queries_low, d_mask=self.ok)
+        self.done.discard("open")
+        self.done.add("pow")
+
+    def open(self, caps=True):
+        """The openings of trees 0-3 at the queries pow() drew: Context.witness_decommit at queries_low into values [n, v0 +
+        v1 + v2], n_values [n, 3], witness_nodes [n, 3, w, 8], n_witness [n, 3] (witness_decommit_sizes), and
+        Context.decommit_tree of tree 3 (the composition's eight columns) at queries into values3, n_values3 [n], witness3,
+        n_witness3 [n] (decommit_sizes); caps=False opens without the caps even where the chain keeps them."""
+        self._need("open", "pow")
+        n, b, nq = self.n, self.log_blowup, self.queries.shape[1]
+        L3 = composition_log_size(self.lp, self.lq)
+        if self.values is None or "open" not in self.done:
+            vcaps, wcap = witness_decommit_sizes(self.program, b, nq)
+            v3, w3 = decommit_sizes([(L3, 8)], b, nq)
+            self.values, self.n_values = self._new(n, sum(vcaps)), self._new(n, 3)
+            self.witness_nodes, self.n_witness = self._new(n, 3, wcap, 8), self._new(n, 3)
+            self.values3, self.n_values3, self.witness3, self.n_witness3 = self._new(n, v3), self._new(n), self._new(n, w3, 8), self._new(n)
+        self.decommit(self.queries_low, self.values, self.n_values, self.witness_nodes, self.n_witness, caps=caps)
+        cap3 = self.cap3 if caps else None
+        self.ctx.decommit_tree([{"log_size": L3, "d_cols": self.comp, "n_cols": 8}], n, b, self.queries, nq, self.values3, self.n_values3,
+                               self.witness3, self.n_witness3, d_mask=self.ok, cap_mode=CAP_NONE if cap3 is None else CAP_READ, d_cap=cap3)
+        self.done.add("open")
 
     def numpy(self):
         """Synchronises -> {name: array} of every tensor allocated so far: uint32 views, the flags uint8; ops cut to the

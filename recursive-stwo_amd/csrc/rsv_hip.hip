@@ -33,6 +33,7 @@
 #include "k_sample.hpp"
 #include "k_composition.hpp"
 #include "k_fri.hpp"
+#include "k_pow.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -110,6 +111,8 @@ struct rsv_ctx {
     size_t ws_chain_bytes = 0;
     void* ws_fri = nullptr;     // rsv_witness_fri_dev: the three points of the quotients
     size_t ws_fri_bytes = 0;
+    void* ws_pow = nullptr;     // rsv_pow_grind_dev: the smallest nonce found so far, per proof
+    size_t ws_pow_bytes = 0;
     uint32_t* cm_tw[2][RSV_MAX_LOG_SIZE + 1] = {};  // k_cm_twiddles tables by domain log size: [0] forward, [1] inverse
     const struct rsv::ProofMeta* last_metas = nullptr;  // the parser's records of the last batch (inside ws_fixed)
     VerifyState* vs = nullptr;
@@ -237,6 +240,7 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ws_commit) (void)hipFree(c->ws_commit);
     if (c->ws_chain) (void)hipFree(c->ws_chain);
     if (c->ws_fri) (void)hipFree(c->ws_fri);
+    if (c->ws_pow) (void)hipFree(c->ws_pow);
     for (auto& by_log : c->cm_tw)
         for (uint32_t* t : by_log)
             if (t) (void)hipFree(t);
@@ -524,3 +528,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "sample_api.inc"
 #include "composition_api.inc"
 #include "fri_api.inc"
+#include "pow_api.inc"
