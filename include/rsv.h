@@ -963,6 +963,38 @@ int rsv_pow_grind_dev(rsv_ctx* ctx, uint32_t pow_bits, uint64_t start, uint64_t 
 int rsv_draw_queries_dev(rsv_ctx* ctx, size_t n, const uint8_t* d_mask, uint32_t n_queries, uint32_t log_size, uint32_t log_size_low,
                          uint32_t* d_channel, uint32_t* d_queries, uint32_t* d_queries_low);
 
+/* ---- the openings of the FRI layer trees of the next proof ------------------------------------------------------------------
+ * stwo's pair-tree decommitment, as SinglePairMerkleProof::from_stwo_proof consumes it.  Tree 0 is the first layer (leaves
+ * at M = sizes[0], a QM31 value per node at every layer in sizes), tree 1 + i inner layer i (leaves at M - 1 - i, values
+ * there only); T = 1 + n_inner trees per proof.  For a tree with leaves at `top` and values at the layers D, Q_l the distinct
+ * (query >> (top - l)) ascending, S_l = Q_l and their siblings (x ^ 1) for l in D and Q_l elsewhere:
+ *   fri_witness   for l in D descending, the value (four words) at every x in S_l ascending that is not in Q_l;
+ *   hash_witness  for l = top - 1 .. 0 and x in S_l ascending, the nodes 2x and then 2x + 1 of layer l + 1 that are not in
+ *                 S_(l+1): a sibling nobody queries at a lower data layer gives both its children.
+ *
+ * rsv_fri_open_sizes: the capacities per (proof, tree), host arithmetic: values_cap = n_sizes * n_queries values,
+ * witness_cap = n_queries * (M + 2 * (n_sizes - 1)) nodes.  Both are bounds (a level without values gives at most n_queries
+ * nodes, a level with values below the top at most 3 n_queries), not tight.  Refusals as rsv_fri_open_dev's. */
+int rsv_fri_open_sizes(const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, uint32_t n_queries, size_t* values_cap,
+                       size_t* witness_cap);
+/* d_quot, sizes [n_sizes] (HOST) and d_layers exactly as rsv_fri_commit_dev takes and leaves them (d_layers may be NULL only
+ * when n_inner is 0); d_queries [n][n_queries] positions of M bits as rsv_draw_queries_dev writes them: any order,
+ * duplicates allowed, bits above M ignored (rsv_decommit_tree_dev's contract; inner layer i is opened at query >> (1 + i)).
+ *   d_fri_witness    [n][T][values_cap][4],  d_n_fri_witness  [n][T] values;
+ *   d_hash_witness   [n][T][witness_cap][8], d_n_hash_witness [n][T] nodes.
+ * Every word is written, zero past a count; a masked proof (d_mask [n], may be NULL) gets zero counts and zero buffers.
+ * The recompute form: rsv_fri_commit_dev keeps the roots only, so every tree is hashed again by the commitment's own
+ * kernel, level by level through two node buffers, and the planned nodes are copied out while their level is there — an
+ * opening costs about the layer trees of a commitment.  Proofs in passes within RSV_OPT_WS_BUDGET_MB.  Refusals before any
+ * device work: a NULL pointer (but d_mask and d_layers): RSV_E_NULL; what rsv_fri_commit_dev refuses of sizes, log_blowup,
+ * log_last and n: RSV_E_SIZE; then, n_inner being known only from sound sizes, a NULL d_layers with n_inner > 0: RSV_E_NULL;
+ * n_queries outside 1 .. RSV_MAX_QUERIES, a pointer not 4-byte aligned: RSV_E_SIZE.
+ * Enqueued on the context's stream with no host synchronisation but the workspace's growth. */
+int rsv_fri_open_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* d_layers, const uint32_t* sizes, size_t n_sizes,
+                     uint32_t log_blowup, uint32_t log_last, size_t n, const uint8_t* d_mask, const uint32_t* d_queries,
+                     uint32_t n_queries, uint32_t* d_fri_witness, uint32_t* d_n_fri_witness, uint32_t* d_hash_witness,
+                     uint32_t* d_n_hash_witness);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -249,6 +249,8 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_fri_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12),
         "rsv_pow_grind_dev": (ctypes.c_int, [vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, sz, vp, vp, vp]),
         "rsv_draw_queries_dev": (ctypes.c_int, [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]),
+        "rsv_fri_open_sizes": (ctypes.c_int, [_u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "rsv_fri_open_dev": (ctypes.c_int, [vp, vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, ctypes.c_uint32, vp, vp, vp, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -299,7 +301,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_sample_tree_dev", "rsv_witness_sample_dev",
            "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
            "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
-           "rsv_pow_grind_dev", "rsv_draw_queries_dev",
+           "rsv_pow_grind_dev", "rsv_draw_queries_dev", "rsv_fri_open_sizes", "rsv_fri_open_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -854,6 +856,16 @@ def fri_sizes(lp: int, lq: int, log_blowup: int, log_last: int) -> dict:
             "last_words": last.value}
 
 
+def fri_open_sizes(sizes, log_blowup: int, log_last: int, n_queries: int):
+    """rsv_fri_open_sizes: (values_cap in QM31 values, witness_cap in nodes) per (proof, tree) of rsv_fri_open_dev's outputs;
+    sizes the quotient columns' LDE log sizes, descending.  Host arithmetic."""
+    sz = _u32(list(sizes))
+    v, w = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(lib.rsv_fri_open_sizes(sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n_queries, ctypes.byref(v), ctypes.byref(w)),
+           "rsv_fri_open_sizes")
+    return v.value, w.value
+
+
 def witness_decommit_sizes(program, log_blowup: int, n_queries: int):
     """The capacities of Context.witness_decommit's outputs: ([values_cap of tree 0, 1, 2], witness_cap)."""
     lp, lq = program.trace_sizes()
@@ -1261,6 +1273,19 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_draw_queries_dev(self._h, n, ptr(d_mask), n_queries, log_size, log_size_low, ptr(d_channel), ptr(d_queries),
                                         ptr(d_queries_low)), "rsv_draw_queries_dev")
+
+    def fri_open(self, d_quot, d_layers, sizes, log_blowup: int, log_last: int, n: int, d_queries, n_queries: int, d_fri_witness,
+                 d_n_fri_witness, d_hash_witness, d_n_hash_witness, d_mask=None):
+        """rsv_fri_open_dev on what Context.fri_commit took and left (d_quot, sizes, d_layers; d_layers may be None when there
+        is no inner layer) at d_queries uint32[n, n_queries] (positions of sizes[0] bits): d_fri_witness uint32[n, T,
+        values_cap, 4], d_n_fri_witness uint32[n, T], d_hash_witness uint32[n, T, witness_cap, 8], d_n_hash_witness uint32[n,
+        T] (T = 1 + n_inner; capacities: fri_open_sizes); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        sz = _u32(list(sizes))
+        self.acquire_from_torch()
+        _check(lib.rsv_fri_open_dev(self._h, ptr(d_quot), ptr(d_layers), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask),
+                                    ptr(d_queries), n_queries, ptr(d_fri_witness), ptr(d_n_fri_witness), ptr(d_hash_witness),
+                                    ptr(d_n_hash_witness)), "rsv_fri_open_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

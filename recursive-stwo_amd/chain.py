@@ -3,21 +3,70 @@
 Every stage of the chain up to FRI (Context.witness, witness_trace, witness_commit, witness_decommit, witness_tree3,
 witness_sample, witness_fri) takes the same program, trace columns and flags, followed by its own tensors.  A Chain owns those tensors,
 allocates each when the stage that writes it first runs, and makes each Context call with the arguments drawn from itself.
-The Context methods stay the 1:1 layer over the C-ABI; nothing here reaches past them.
+The Context methods stay the 1:1 layer over the C-ABI; nothing here reaches past them.  Chain.proofs() puts what the stages
+left into the bytes of a PlonkWithPoseidonProof (proof_bytes: plain numpy on the host).
 """
 import numpy as np
 
-from . import CAP_NONE, CAP_READ, composition_log_size, decommit_sizes, fri_sizes, pack, witness_decommit_sizes
+from . import CAP_NONE, CAP_READ, composition_log_size, decommit_sizes, fri_open_sizes, fri_sizes, pack, witness_decommit_sizes
 
 _FLAGS = ("acc", "ok", "low_degree")
 _WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
             "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree",
-            "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3")
+            "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3",
+            "fri_witness", "n_fri_witness", "fri_hash_witness", "n_fri_hash_witness")
+SAMPLES_PER_COLUMN = ([1] * 50, [1] * 60, [1, 1, 1, 1, 2, 2, 2, 2] * 2, [1] * 8)  # sampled_values of trees 0-3 (SURVEY App. A)
+
+
+def _u64(v):
+    return np.array([int(v) & 0xFFFFFFFF, int(v) >> 32], np.uint32)
+
+
+def _vec(items):
+    """A bincode Vec of fixed-size items: the u64 count, then the words of items uint32[count, width]."""
+    items = np.asarray(items, np.uint32)
+    return [_u64(len(items)), items.reshape(-1)]
+
+
+def proof_bytes(lp, lq, sums, config, commitments, samples, openings, nonce, layers, last_poly, log_last):
+    """The serialised PlonkWithPoseidonProof (bincode: little-endian words, u64 length prefixes).
+    sums uint32[2, 4]; config (pow_bits, log_blowup, log_last, n_queries); commitments uint32[4, 8]; samples uint32[142, 4],
+    tree-major, column-major, sample-minor; openings: per tree 0-3 (queried values uint32[nv], hash witness uint32[nw, 8]);
+    nonce uint32[2], low word first; layers: the first layer, then the inner ones, each (fri_witness uint32[nf, 4],
+    hash_witness uint32[nh, 8], commitment uint32[8]); last_poly uint32[2^log_last, 4].  Every column_witness is empty."""
+    pow_bits, log_blowup, cfg_last, n_queries = config
+    out = [np.array([lp, lq], np.uint32), np.asarray(sums, np.uint32).reshape(8), np.array([pow_bits, log_blowup, cfg_last], np.uint32),
+           _u64(n_queries)]
+    out += _vec(np.asarray(commitments, np.uint32).reshape(4, 8))
+    samples, at = np.asarray(samples, np.uint32).reshape(-1, 4), 0
+    out.append(_u64(len(SAMPLES_PER_COLUMN)))
+    for tree in SAMPLES_PER_COLUMN:
+        out.append(_u64(len(tree)))
+        for k in tree:
+            out += _vec(samples[at:at + k])
+            at += k
+    assert at == len(samples) and sum(len(x) for x in out) == 895
+    out.append(_u64(len(openings)))
+    for _, witness in openings:
+        out += _vec(np.asarray(witness, np.uint32).reshape(-1, 8)) + [_u64(0)]
+    out.append(_u64(len(openings)))
+    for values, _ in openings:
+        out += _vec(np.asarray(values, np.uint32).reshape(-1, 1))
+    out.append(np.asarray(nonce, np.uint32).reshape(2))
+    for i, (fri_witness, hash_witness, commitment) in enumerate(layers):
+        if i == 1:
+            out.append(_u64(len(layers) - 1))
+        out += _vec(np.asarray(fri_witness, np.uint32).reshape(-1, 4)) + _vec(np.asarray(hash_witness, np.uint32).reshape(-1, 8))
+        out += [_u64(0), np.asarray(commitment, np.uint32).reshape(8)]
+    if len(layers) == 1:
+        out.append(_u64(0))
+    out += _vec(np.asarray(last_poly, np.uint32).reshape(-1, 4)) + [np.array([log_last], np.uint32)]
+    return np.concatenate(out).astype("<u4").tobytes()
 
 
 class Chain:
     """Chain(ctx, program, n, log_blowup): n proofs through witness() -> trace() -> commit() -> decommit() / tree3() ->
-    sample() -> fri() -> pow() -> open().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
+    sample() -> fri() -> pow() -> open() / fri_open() -> proofs().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
     ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
     a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3)."""
 
@@ -27,6 +76,7 @@ class Chain:
         self.lp, self.lq = program.trace_sizes()
         self.n_ops = len(program.gates()[1])
         self.done = set()
+        self.pow_bits = None
         self._blob = self._vars = self._flow = self._swap = None
         for name in _WRITTEN:
             setattr(self, name, None)
@@ -134,15 +184,17 @@ class Chain:
     def pow(self, pow_bits, n_queries, start=0, max_tries=0):
         """Context.pow_grind, then Context.draw_queries: the nonce [n, 2], the queries [n, n_queries] at the largest column's
         log size (fri_sizes' sizes[0]) and queries_low, the same at max(lp, lq) + log_blowup, where trees 0-2 are opened; the
-        channel moves on, ok is cleared where the search is exhausted."""
+        channel moves on, ok is cleared where the search is exhausted.  pow_bits is remembered for the proof's header."""
         self._need("pow", "fri")
         n = self.n
+        self.pow_bits = pow_bits
         if self.nonce is None or self.queries.shape[1] != n_queries:
             self.nonce, self.queries, self.queries_low = self._new(n, 2), self._new(n, n_queries), self._new(n, n_queries)
         M = fri_sizes(self.lp, self.lq, self.log_blowup, self.log_last)["sizes"][0]
         self.ctx.pow_grind(pow_bits, n, self.ok, self.channel, self.nonce, start=start, max_tries=max_tries)
         self.ctx.draw_queries(n, n_queries, M, max(self.lp, self.lq) + self.log_blowup, self.channel, self.queries, self.queries_low, d_mask=self.ok)
         self.done.discard("open")
+        self.done.discard("fri_open")
         self.done.add("pow")
 
     def open(self, caps=True):
@@ -164,6 +216,42 @@ class Chain:
         self.ctx.decommit_tree([{"log_size": L3, "d_cols": self.comp, "n_cols": 8}], n, b, self.queries, nq, self.values3, self.n_values3,
                                self.witness3, self.n_witness3, d_mask=self.ok, cap_mode=CAP_NONE if cap3 is None else CAP_READ, d_cap=cap3)
         self.done.add("open")
+
+    def fri_open(self):
+        """The openings of the FRI layer trees at the queries pow() drew: Context.fri_open on quot and layers into fri_witness
+        [n, T, v, 4], n_fri_witness [n, T], fri_hash_witness [n, T, w, 8], n_fri_hash_witness [n, T] (T = 1 + n_inner;
+        fri_open_sizes); every tree is hashed again."""
+        self._need("fri_open", "pow")
+        n, b, last, nq = self.n, self.log_blowup, self.log_last, self.queries.shape[1]
+        sz = fri_sizes(self.lp, self.lq, b, last)
+        T = 1 + sz["n_inner"]
+        if self.fri_witness is None or "fri_open" not in self.done:
+            vcap, wcap = fri_open_sizes(sz["sizes"], b, last, nq)
+            self.fri_witness, self.n_fri_witness = self._new(n, T, vcap, 4), self._new(n, T)
+            self.fri_hash_witness, self.n_fri_hash_witness = self._new(n, T, wcap, 8), self._new(n, T)
+        self.ctx.fri_open(self.quot, self.layers, sz["sizes"], b, last, n, self.queries, nq, self.fri_witness, self.n_fri_witness,
+                          self.fri_hash_witness, self.n_fri_hash_witness, d_mask=self.ok)
+        self.done.add("fri_open")
+
+    def proofs(self):
+        """-> per proof the serialised PlonkWithPoseidonProof (proof_bytes), None where ok is 0.  Assembled on the host from
+        numpy(): synchronises."""
+        self._need("proofs", "open", "fri_open")
+        a = self.numpy()
+        b, last, nq = self.log_blowup, self.log_last, self.queries.shape[1]
+        vat = np.cumsum([0] + witness_decommit_sizes(self.program, b, nq)[0])
+        out = []
+        for k in range(self.n):
+            if not a["ok"][k]:
+                out.append(None)
+                continue
+            openings = [(a["values"][k, vat[t]:vat[t] + a["n_values"][k, t]], a["witness_nodes"][k, t, :a["n_witness"][k, t]]) for t in range(3)]
+            openings.append((a["values3"][k, :a["n_values3"][k]], a["witness3"][k, :a["n_witness3"][k]]))
+            layers = [(a["fri_witness"][k, t, :a["n_fri_witness"][k, t]], a["fri_hash_witness"][k, t, :a["n_fri_hash_witness"][k, t]],
+                       a["fri_roots"][k, t]) for t in range(a["fri_roots"].shape[1])]
+            out.append(proof_bytes(self.lp, self.lq, a["sums"][k], (self.pow_bits, b, last, nq), np.concatenate([a["roots"][k], a["root3"][k][None]]),
+                                   np.concatenate([a["samples"][k], a["samples3"][k]]), openings, a["nonce"][k], layers, a["last_poly"][k], last))
+        return out
 
     def numpy(self):
         """Synchronises -> {name: array} of every tensor allocated so far: uint32 views, the flags uint8; ops cut to the

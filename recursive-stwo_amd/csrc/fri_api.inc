@@ -175,6 +175,22 @@ size_t fr_commit_ws_bytes(uint32_t M, uint32_t L, size_t P, char* base, FrCommit
     return sz.off;
 }
 
+// One layer tree of a pass of Pc proofs, a launch of k_fr_hash_layer per level top .. last: level l goes to na when top - l
+// is even and to nb when it is odd (level 0 to root), and is the next level's children.  data_at(l, &stride): the level's
+// column, or nullptr; after(l, nodes) runs behind each level's launch.  fri_commit (last = 0) and fri_open (last = 1) share it.
+template <class DataAt, class After>
+void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t* na, uint32_t* nb, uint32_t* root, DataAt data_at, After after) {
+    const uint32_t* child = nullptr;
+    for (uint32_t l = top + 1; l-- > last;) {
+        uint64_t dstride = 0;
+        const uint32_t* data = data_at(l, &dstride);
+        uint32_t* out = l == 0 ? root : ((top - l) & 1 ? nb : na);
+        hipLaunchKernelGGL(rsv::k_fr_hash_layer, dim3(grid_for((size_t)Pc << l, 256)), dim3(256), 0, st, data, dstride, l, Pc, child, out);
+        after(l, out);
+        child = out;
+    }
+}
+
 int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n,
                const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly,
                uint8_t* d_low_degree) {
@@ -214,16 +230,7 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         uint32_t* alphas = d_alphas + p0 * astride;
         uint32_t* layers = d_layers ? d_layers + p0 * lstride : nullptr;
         // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root
-        auto tree = [&](uint32_t top, auto data_at) {
-            const uint32_t* child = nullptr;
-            for (uint32_t l = top + 1; l-- > 0;) {
-                uint64_t dstride = 0;
-                const uint32_t* data = data_at(l, &dstride);
-                uint32_t* out = l == 0 ? w.root : ((top - l) & 1 ? w.nb : w.na);
-                hipLaunchKernelGGL(rsv::k_fr_hash_layer, dim3(grid_for((size_t)Pc << l, 256)), dim3(256), 0, st, data, dstride, l, Pc, child, out);
-                child = out;
-            }
-        };
+        auto tree = [&](uint32_t top, auto data_at) { fr_tree(st, Pc, top, 0, w.na, w.nb, w.root, data_at, [](uint32_t, const uint32_t*) {}); };
         auto draw = [&](uint32_t idx) {
             hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
                                alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
@@ -231,9 +238,7 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         // where the running evaluation of log size l lives: inner layer M - 1 - l, or the last evaluation
         auto eval_at = [&](uint32_t l) -> rsv::FrVec {
             if (l == L) return {w.last, (uint64_t)4 << L};
-            uint64_t off = 0;
-            for (uint32_t i = 0; i < M - 1 - l; i++) off += (uint64_t)4 << (M - 1 - i);
-            return {layers + off, lstride};
+            return {layers + rsv::fr_layer_off(M, l), lstride};
         };
         // the first layer: every quotient column at its own level
         tree(M, [&](uint32_t l, uint64_t* stride) -> const uint32_t* {

@@ -208,6 +208,10 @@ __global__ __launch_bounds__(64) void k_fr_draw(const uint32_t* __restrict__ roo
     for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
 }
 
+// Where inner layer M - 1 - l (log size l < M) begins in a proof's d_layers, the layers M - 1, M - 2, ... one after
+// another, each [4][2^size]: 4 (2^M - 2^(l+1)) words.
+__host__ __device__ inline uint64_t fr_layer_off(uint32_t M, uint32_t l) { return ((uint64_t)4 << M) - ((uint64_t)8 << l); }
+
 // ---------------------------------------------------------------- folds
 // A set of P QM31 vectors of 2^l values: coordinate j of proof p, value i at base + p * stride + (j << l) + i.
 struct FrVec {

@@ -34,6 +34,7 @@
 #include "k_composition.hpp"
 #include "k_fri.hpp"
 #include "k_pow.hpp"
+#include "k_fri_open.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -529,3 +530,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "composition_api.inc"
 #include "fri_api.inc"
 #include "pow_api.inc"
+#include "fri_open_api.inc"
