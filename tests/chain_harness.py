@@ -162,3 +162,24 @@ def chain(rsv, ctx, wp, batch, inputs, b, upto="commit", caps=False, log_last=No
     for stage in STAGES[1:STAGES.index(upto) + 1]:
         getattr(ch, stage)(**(outputs or {}) if stage == "trace" else {})
     return ch
+
+
+def whole_chain(rsv, ctx, wp, batch, inputs, cfg, caps=True):
+    """The whole chain of a batch under the configuration cfg -> (Chain.numpy(), Chain.proofs())."""
+    ch = chain(rsv, ctx, wp, batch, inputs, cfg.log_blowup_factor, upto="fri", caps=caps, log_last=cfg.log_last_layer_degree_bound)
+    ch.pow(cfg.pow_bits, cfg.n_queries)
+    ch.open()
+    ch.fri_open()
+    return ch.numpy(), ch.proofs()
+
+
+def slots_differ(got, k, want, j):
+    """The tensors of two Chain.numpy() results in which slot k of `got` is not word for word slot j of `want`."""
+    assert set(got) == set(want)
+    return [key for key in got if not np.array_equal(got[key][k], want[key][j])]
+
+
+def masked_past_64(n=70):
+    """The mask of a batch past one 64-lane workgroup of proofs: the last lane of the first workgroup and the first of the
+    second are cleared."""
+    return [0 if p in (63, 64) else 1 for p in range(n)]

@@ -11,7 +11,7 @@ import pytest
 from tests import commit_ref as C
 from tests import composition_ref as K
 from tests import oracle_binding as ob
-from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, next_samples, pin_id, pins, program_of, u32
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, masked_past_64, next_samples, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -112,12 +112,10 @@ SHAPES = [  # (lp, lq, n, mask, shared preprocessed columns)
 ]
 
 
-@pytest.mark.parametrize("case", range(len(SHAPES)), ids=lambda k: "lp%d_lq%d" % SHAPES[k][:2])
-def test_composition_bit_for_bit(rsv, case):
+def _check_shape(rsv, lp, lq, n, mask, shared, seed):
     """Random canonical columns, sums and draws: d_comp and d_comp_coeffs equal the restatement's, d_comp_coeffs is
     C.interpolate of d_comp, the run without d_comp_coeffs gives the same columns, a masked proof is zero."""
-    lp, lq, n, mask, shared = SHAPES[case]
-    rng = np.random.default_rng(1700 + case)
+    rng = np.random.default_rng(seed)
     plonk, poseidon, sums, draws = _random_inputs(rng, lp, lq, n, shared)
     ctx = rsv.Context(0)
     comp, co, _ = _run(rsv, ctx, lp, lq, plonk, poseidon, sums, draws, n, mask, True, shared)
@@ -131,8 +129,21 @@ def test_composition_bit_for_bit(rsv, case):
             assert not comp[p].any() and not co[p].any(), p
             continue
         want, want_co = _ref(plonk, poseidon, lp, lq, sums, draws, p)
-        assert np.array_equal(co[p], want_co), (case, p)
-        assert np.array_equal(comp[p], want), (case, p)
+        assert np.array_equal(co[p], want_co), (seed, p)
+        assert np.array_equal(comp[p], want), (seed, p)
+
+
+@pytest.mark.parametrize("case", range(len(SHAPES)), ids=lambda k: "lp%d_lq%d" % SHAPES[k][:2])
+def test_composition_bit_for_bit(rsv, case):
+    """SHAPES through _check_shape: d_comp and d_comp_coeffs equal the restatement's, a masked proof is zero."""
+    lp, lq, n, mask, shared = SHAPES[case]
+    _check_shape(rsv, lp, lq, n, mask, shared, 1700 + case)
+
+
+def test_composition_past_one_workgroup_of_proofs(rsv):
+    """(lp, lq) = (4, 3), 70 proofs, 63 and 64 masked: k_co_params' second workgroup of proofs, every proof against the
+    restatement."""
+    _check_shape(rsv, 4, 3, 70, masked_past_64(), False, 1730)
 
 
 def test_coefficients_sample_as_the_columns(rsv):

@@ -10,7 +10,7 @@ import pytest
 from tests import commit_ref as C
 from tests import decommit_ref as D
 from tests import oracle_binding as ob
-from tests.chain_harness import CASES, DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, program_of, u32
+from tests.chain_harness import CASES, DEV, chain, dev, full, inputs_of, mask_dev, masked_past_64, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -184,6 +184,15 @@ def test_decommit_tree_bit_for_bit(rsv, case):
     spec, b, n, mask = CASES[case]
     ctx = rsv.Context(0)
     _check_case(rsv, ctx, spec, b, n, mask, 7, 500 + case)
+    ctx.close()
+
+
+def test_decommit_tree_past_one_workgroup_of_proofs(rsv):
+    """The first of CASES with 70 proofs, four queries that differ per proof, 63 and 64 masked: the second workgroup of the
+    planner's per-proof rows, every proof against the restatement."""
+    spec, b, _, _ = CASES[0]
+    ctx = rsv.Context(0)
+    _check_case(rsv, ctx, spec, b, 70, masked_past_64(), 4, 950, kind="any")
     ctx.close()
 
 

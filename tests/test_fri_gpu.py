@@ -10,7 +10,7 @@ import pytest
 from tests import commit_ref as C
 from tests import fri_ref as F
 from tests import oracle_binding as ob
-from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, pow_words, program_of, u32
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, masked_past_64, pin_id, pins, pow_words, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -127,6 +127,7 @@ QCASES = {  # name: (b, n, mask, [(log, n_cols, shared, [per point (lo, hi) or N
                                        (4, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), (0, 4)])]),
     "shared_group": (1, 3, None, [(5, 6, True, [ALL(6)]), (5, 2, False, [ALL(2), (1, 2)])]),
     "past_the_lds_fft": (1, 1, None, [(11, 2, False, [ALL(2), (0, 1)])]),
+    "past_one_workgroup_of_proofs": (1, 70, None, [(4, 3, False, [ALL(3), (1, 3)]), (3, 2, False, [ALL(2)])]),  # k_fr_consts
 }
 
 
@@ -229,6 +230,7 @@ CCASES = {  # name: (sizes, log_last, b, n, mask, low degree input)
     "no_inner_layer": ([4], 2, 1, 1, None, False),
     "levels_past_one_workgroup": ([11, 9], 1, 1, 1, None, False),
     "low_degree": ([8, 7, 5], 2, 2, 2, None, True),
+    "past_one_workgroup_of_proofs": ([5, 3], 0, 1, 70, masked_past_64(), False),  # k_fr_draw, k_fr_mix_last
 }
 
 

@@ -11,7 +11,7 @@ from tests import commit_ref as C
 from tests import fri_open_ref as FO
 from tests import fri_ref as F
 from tests import oracle_binding as ob
-from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, program_of, u32
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, masked_past_64, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +115,24 @@ def test_batch_with_a_masked_proof(rsv):
         assert not got[k][1].any(), k
     for p in (0, 2):
         _check_proof(got, p, sizes, log_last, b, cols[p], queries[p])
+
+
+def test_past_one_workgroup_of_proofs(rsv):
+    """70 proofs of the no_inner_layer shape with their own columns and four queries each, 63 and 64 masked: the second
+    workgroup of the planner's per-proof rows, every live proof against the restatement."""
+    sizes, log_last, b = SHAPES["no_inner_layer"]
+    n, mask = 70, masked_past_64()
+    rng = np.random.default_rng(2250)
+    cols = [{s: rng.integers(0, P, (4, 1 << s)) for s in sizes} for _ in range(n)]
+    queries = [rng.integers(0, 1 << sizes[0], 4).tolist() for _ in range(n)]
+    ctx = rsv.Context(0)
+    got = _commit_and_open(rsv, ctx, sizes, log_last, b, cols, queries, mask=mask)
+    ctx.close()
+    for p in range(n):
+        if not mask[p]:
+            assert all(not got[k][p].any() for k in ("fw", "nf", "hw", "nh")), p
+        else:
+            _check_proof(got, p, sizes, log_last, b, cols[p], queries[p])
 
 
 def test_under_a_small_workspace_budget(rsv):

@@ -11,7 +11,7 @@ import pytest
 from tests import commit_ref as C
 from tests import oracle_binding as ob
 from tests import pow_ref as W
-from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, pin_id, pins, program_of, u32
+from tests.chain_harness import DEV, chain, dev, full, inputs_of, mask_dev, masked_past_64, pin_id, pins, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -139,6 +139,14 @@ def test_batch_of_five_with_a_masked_proof(rsv):
     ctx.close()
 
 
+def test_grind_past_one_workgroup_of_proofs(rsv):
+    """70 channels at pow_bits 4, proofs 63 and 64 masked: k_pow_finish's second workgroup of proofs, every proof against the
+    restatement."""
+    ctx = rsv.Context(0)
+    _check_grind(ctx, _channels(range(100, 170)), 4, mask=masked_past_64())
+    ctx.close()
+
+
 def test_the_cap_on_the_candidates(rsv):
     """max_tries = k + 1 finds the nonce k, max_tries = k exhausts: ok cleared, zero nonce, zeroed channel; the neighbour,
     whose nonce is smaller, is found either way."""
@@ -158,19 +166,15 @@ def test_the_cap_on_the_candidates(rsv):
 
 
 # ---------------------------------------------------------------- the draw
-@pytest.mark.parametrize("nq,log_size,log_low", [(1, 1, 1), (8, 20, 20), (9, 20, 13), (128, 30, 30), (128, 30, 7), (9, 30, 1)])
-def test_draw_bit_for_bit(rsv, nq, log_size, log_low):
-    """Three proofs, the second masked, with and without the low positions: the queries, the low queries, n_sent."""
-    chans = _channels((31, 32, 33))
-    chans[:, 8] = (0, 0, 2)
-    mask = [1, 0, 1]
-    ctx = rsv.Context(0)
+def _check_draw(ctx, chans, mask, nq, log_size, log_low):
+    """With and without the low positions: the queries, the low queries, n_sent; zeros for a masked proof."""
+    n = len(chans)
     for with_low in (True, False):
-        d_chan, d_q, d_low = dev(chans), full((3, nq)), full((3, nq))
-        ctx.draw_queries(3, nq, log_size, log_low, d_chan, d_q, d_low if with_low else None, d_mask=mask_dev(mask))
+        d_chan, d_q, d_low = dev(chans), full((n, nq)), full((n, nq))
+        ctx.draw_queries(n, nq, log_size, log_low, d_chan, d_q, d_low if with_low else None, d_mask=mask_dev(mask))
         ctx.synchronize()
         after, q, low = u32(d_chan), u32(d_q), u32(d_low)
-        for p in range(3):
+        for p in range(n):
             if not mask[p]:
                 assert not after[p].any() and not q[p].any()
                 assert not low[p].any() if with_low else (low[p] == 0xFFFFFFFF).all()
@@ -179,6 +183,22 @@ def test_draw_bit_for_bit(rsv, nq, log_size, log_low):
             assert np.array_equal(q[p], wq) and np.array_equal(after[p], wafter), p
             assert wafter[8] == chans[p, 8] + (nq + 7) // 8
             assert np.array_equal(low[p], wlow) if with_low else (low[p] == 0xFFFFFFFF).all(), p
+
+
+@pytest.mark.parametrize("nq,log_size,log_low", [(1, 1, 1), (8, 20, 20), (9, 20, 13), (128, 30, 30), (128, 30, 7), (9, 30, 1)])
+def test_draw_bit_for_bit(rsv, nq, log_size, log_low):
+    """Three proofs, the second masked, with and without the low positions: the queries, the low queries, n_sent."""
+    chans = _channels((31, 32, 33))
+    chans[:, 8] = (0, 0, 2)
+    ctx = rsv.Context(0)
+    _check_draw(ctx, chans, [1, 0, 1], nq, log_size, log_low)
+    ctx.close()
+
+
+def test_draw_past_one_workgroup_of_proofs(rsv):
+    """70 proofs, 63 and 64 masked: k_pow_queries' second workgroup of proofs, every proof against the restatement."""
+    ctx = rsv.Context(0)
+    _check_draw(ctx, _channels(range(200, 270)), masked_past_64(), 9, 20, 13)
     ctx.close()
 
 
