@@ -995,6 +995,71 @@ int rsv_fri_open_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* d_lay
                      uint32_t n_queries, uint32_t* d_fri_witness, uint32_t* d_n_fri_witness, uint32_t* d_hash_witness,
                      uint32_t* d_n_hash_witness);
 
+/* ---- the next proof serialised: the chain's buffers into the verifier's blob layout ------------------------------------------
+ * What the stages above leave, put into the bytes of a PlonkWithPoseidonProof on the device: n proofs as (d_blob,
+ * d_offsets), the pair every _dev entry point that takes a blob consumes (rsv_verify_batch_dev, rsv_witness_eval_dev of the
+ * next recursion level).  The bytes (bincode: little-endian 32-bit words, every length prefix a u64 = two
+ * words, low first; every column_witness empty), T = n_layers = 1 + n_inner:
+ *   head, 895 words     log_size_plonk, log_size_poseidon; the eight words of d_sums; pow_bits, log_blowup, log_last;
+ *                       u64(n_queries); u64(4) and the four commitments (d_roots' three, d_root3); u64(4) and per tree
+ *                       u64(columns) (50, 60, 16, 8), per column u64(samples) and its samples of four words: one per column,
+ *                       in tree 2 two for columns 4 .. 7 and 12 .. 15 — d_samples' 134 in order, then d_samples3's eight;
+ *   decommitments       u64(4); per tree 0 .. 3: u64(count), the hash_witness nodes of eight words, u64(0) (column_witness);
+ *   queried_values      u64(4); per tree 0 .. 3: u64(count), the values of one word;
+ *   proof of work       d_nonce's two words;
+ *   first layer         u64(count), the fri_witness values of four words; u64(count), the hash_witness nodes; u64(0)
+ *                       (column_witness); the eight words of d_fri_roots[0];
+ *   inner layers        u64(T - 1) (u64(0) when T is 1), then T - 1 layers in the first layer's form, trees 1 .. T - 1;
+ *   last layer          u64(2^log_last), d_last_poly's values of four words; the word log_last.
+ *
+ * A ragged list per proof: item e of proof p is d_items[p * stride + e * width] (words; width 1 for values, 8 for witness
+ * nodes), its count d_count[p * count_stride], at most cap.  fri_witness (width 4) and fri_hash_witness (width 8) hold T
+ * lists per proof: tree t of proof p at d_items[p * stride + t * cap * width], its count d_count[p * count_stride + t].
+ * The lists point into the buffers as rsv_witness_decommit_dev, rsv_decommit_tree_dev and rsv_fri_open_dev leave them: no
+ * staging copy (values of trees 0 .. 2 are three lists into one buffer, each at its tree's offset). */
+typedef struct rsv_proof_list {
+    const uint32_t* d_items;
+    size_t stride;
+    const uint32_t* d_count;
+    size_t count_stride;
+    uint32_t cap;
+} rsv_proof_list;
+typedef struct rsv_proof_parts {
+    uint32_t log_size_plonk, log_size_poseidon, pow_bits, log_blowup, log_last, n_queries, n_layers;
+    const uint32_t* d_sums;       /* [n][2][4] */
+    const uint32_t* d_roots;      /* [n][3][8] */
+    const uint32_t* d_root3;      /* [n][8] */
+    const uint32_t* d_samples;    /* [n][134][4] */
+    const uint32_t* d_samples3;   /* [n][8][4] */
+    const uint32_t* d_nonce;      /* [n][2] */
+    const uint32_t* d_fri_roots;  /* [n][T][8] */
+    const uint32_t* d_last_poly;  /* [n][2^log_last][4] */
+    rsv_proof_list values[4], witness[4];
+    rsv_proof_list fri_witness, fri_hash_witness;
+} rsv_proof_parts;
+/* The length in bytes of a proof with the given counts (HOST, 8 + 2 n_layers of them: values of trees 0 .. 3, witness
+ * nodes of trees 0 .. 3, then per layer tree its fri_witness values and its hash_witness nodes).  Host arithmetic: with
+ * the capacities it is the bound a caller sizes d_blob with (n times it), with a proof's stored counts the proof's length.
+ * NULL counts or bytes: RSV_E_NULL; log_last above RSV_MAX_LOG_LAST_LAYER, n_layers 0 or above 29: RSV_E_SIZE. */
+int rsv_proof_bytes(uint32_t log_last, uint32_t n_layers, const uint32_t* counts, size_t* bytes);
+/* d_offsets [n + 1] u64: d_offsets[0] = 0, d_offsets[p + 1] - d_offsets[p] the length of proof p — always exact, all
+ * multiples of 4: the form rsv_verify_batch_dev requires.  A proof gets a zero-length slot, its neighbours unaffected, when
+ * it is masked (d_mask [n] bytes, may be NULL: d_mask[p] == 0) or one of its counts exceeds its cap (nothing is read past
+ * a cap).  d_blob NULL: offsets only; the caller may read d_offsets[n] and allocate exactly.  With a d_blob, the bytes of
+ * proof p are written iff d_offsets[p + 1] <= blob_cap (bytes): nothing of a proof that does not fit is written, and the
+ * caller sees it from d_offsets[n] > blob_cap.  Bytes of d_blob outside the written proofs are left as they were.
+ * Three launches: one wave per proof (counts, length, the table of the proof's runs), one workgroup scanning the
+ * lengths, one lane per output word (the run found in the proof's table in LDS; dword loads and stores).  The map of the
+ * literal words is built on the host for the configuration words and kept in the context: a call under another
+ * configuration than the context's last uploads it again.  Refusals before any device work: NULL ctx, parts, d_offsets or
+ * any pointer of parts: RSV_E_NULL; n 0 or above 2^20, what rsv_cfg_check refuses of (pow_bits, log_blowup, log_last,
+ * n_queries), n_layers 0 or above 29, a pointer (d_blob included) not 4-byte aligned or d_offsets not 8-byte aligned, a
+ * stride below cap * width (T * cap * width for the two layer lists, whose count_stride must be at least T), capacities
+ * with which one proof exceeds 2^30 words: RSV_E_SIZE.
+ * Enqueued on the context's stream with no host synchronisation but the workspace's growth and the map's replacement. */
+int rsv_proof_pack_dev(rsv_ctx* ctx, const rsv_proof_parts* parts, size_t n, const uint8_t* d_mask, uint8_t* d_blob, size_t blob_cap,
+                       uint64_t* d_offsets);
+
 /* Pack n accept bytes (device) into a little-endian bitmap of ceil(n/32) u32
  * words (device) and return the popcount through *d_count (device u64, may be NULL).
  * This is the buffer the multi-GPU host exchanges with one RCCL all-gather (rsv_exchange_run, below). */

@@ -144,6 +144,18 @@ class Shard(ctypes.Structure):  # rsv_shard
                 ("d_accept", ctypes.c_void_p), ("d_reason", ctypes.c_void_p)]
 
 
+class ProofList(ctypes.Structure):  # rsv_proof_list
+    _fields_ = [("d_items", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("d_count", ctypes.c_void_p), ("count_stride", ctypes.c_size_t),
+                ("cap", ctypes.c_uint32)]
+
+
+class ProofParts(ctypes.Structure):  # rsv_proof_parts
+    _fields_ = [(k, ctypes.c_uint32) for k in ("log_size_plonk", "log_size_poseidon", "pow_bits", "log_blowup", "log_last", "n_queries",
+                                               "n_layers")] + \
+               [(k, ctypes.c_void_p) for k in ("d_sums", "d_roots", "d_root3", "d_samples", "d_samples3", "d_nonce", "d_fri_roots", "d_last_poly")] + \
+               [("values", ProofList * 4), ("witness", ProofList * 4), ("fri_witness", ProofList), ("fri_hash_witness", ProofList)]
+
+
 TRANSCRIPT_WORDS = 284  # RSV_TRANSCRIPT_WORDS
 EXCHANGE_ID_BYTES = 128  # RSV_EXCHANGE_ID_BYTES
 
@@ -251,6 +263,8 @@ def _load() -> ctypes.CDLL:
         "rsv_draw_queries_dev": (ctypes.c_int, [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]),
         "rsv_fri_open_sizes": (ctypes.c_int, [_u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "rsv_fri_open_dev": (ctypes.c_int, [vp, vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, ctypes.c_uint32, vp, vp, vp, vp]),
+        "rsv_proof_bytes": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(sz)]),
+        "rsv_proof_pack_dev": (ctypes.c_int, [vp, ctypes.POINTER(ProofParts), sz, vp, vp, sz, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                               _u32p, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
         "rsv_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
@@ -302,6 +316,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
            "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
            "rsv_pow_grind_dev", "rsv_draw_queries_dev", "rsv_fri_open_sizes", "rsv_fri_open_dev",
+           "rsv_proof_bytes", "rsv_proof_pack_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -866,6 +881,24 @@ def fri_open_sizes(sizes, log_blowup: int, log_last: int, n_queries: int):
     return v.value, w.value
 
 
+def proof_bytes_bound(log_last: int, n_layers: int, counts) -> int:
+    """rsv_proof_bytes: the length in bytes of a serialised proof with the given counts, 8 + 2 n_layers of them: values of
+    trees 0-3, witness nodes of trees 0-3, then per layer tree its fri_witness values and hash_witness nodes.  With the
+    capacities of the buffers it is the bound a d_blob is sized with, with a proof's own counts its length.  Host arithmetic."""
+    c = _u32(list(counts))
+    if len(c) != 8 + 2 * n_layers:
+        raise ValueError(f"proof_bytes_bound: {len(c)} counts for {n_layers} layer trees")
+    out = ctypes.c_size_t()
+    _check(lib.rsv_proof_bytes(log_last, n_layers, c.ctypes.data_as(_u32p), ctypes.byref(out)), "rsv_proof_bytes")
+    return out.value
+
+
+def proof_list(d_items, stride: int, d_count, count_stride: int, cap: int, items_at: int = 0, count_at: int = 0) -> ProofList:
+    """An rsv_proof_list over tensors of 32-bit words: the items from word items_at of d_items with `stride` words per proof,
+    the counts from word count_at of d_count with count_stride words per proof."""
+    return ProofList(d_items.data_ptr() + 4 * items_at, stride, d_count.data_ptr() + 4 * count_at, count_stride, cap)
+
+
 def witness_decommit_sizes(program, log_blowup: int, n_queries: int):
     """The capacities of Context.witness_decommit's outputs: ([values_cap of tree 0, 1, 2], witness_cap)."""
     lp, lq = program.trace_sizes()
@@ -1286,6 +1319,16 @@ class Context:
         _check(lib.rsv_fri_open_dev(self._h, ptr(d_quot), ptr(d_layers), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask),
                                     ptr(d_queries), n_queries, ptr(d_fri_witness), ptr(d_n_fri_witness), ptr(d_hash_witness),
                                     ptr(d_n_hash_witness)), "rsv_fri_open_dev")
+
+    def proof_pack(self, parts: ProofParts, n: int, d_blob, d_offsets, d_mask=None, blob_cap=None):
+        """rsv_proof_pack_dev: the n proofs `parts` (a ProofParts; its lists from proof_list) points at, serialised into d_blob
+        uint8 (None: offsets only) with d_offsets int64[n + 1]; a proof whose end lies beyond blob_cap bytes (default: all of
+        d_blob) is not written; d_mask uint8[n] (may be None); enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        if blob_cap is None:
+            blob_cap = d_blob.numel() * d_blob.element_size() if d_blob is not None else 0
+        self.acquire_from_torch()
+        _check(lib.rsv_proof_pack_dev(self._h, ctypes.byref(parts), n, ptr(d_mask), ptr(d_blob), blob_cap, ptr(d_offsets)), "rsv_proof_pack_dev")
 
     def accept_bitmap(self, d_accept, n: int, d_bitmap, d_count=None):
         self.acquire_from_torch()

@@ -4,11 +4,14 @@ Every stage of the chain up to FRI (Context.witness, witness_trace, witness_comm
 witness_sample, witness_fri) takes the same program, trace columns and flags, followed by its own tensors.  A Chain owns those tensors,
 allocates each when the stage that writes it first runs, and makes each Context call with the arguments drawn from itself.
 The Context methods stay the 1:1 layer over the C-ABI; nothing here reaches past them.  Chain.proofs() puts what the stages
-left into the bytes of a PlonkWithPoseidonProof (proof_bytes: plain numpy on the host).
+left into the bytes of a PlonkWithPoseidonProof (proof_bytes: plain numpy on the host, the definition of the bytes);
+Chain.pack() puts the same bytes into a (blob, offsets) pair on the device (Context.proof_pack), which Chain.witness of the
+next level takes as it is.
 """
 import numpy as np
 
-from . import CAP_NONE, CAP_READ, composition_log_size, decommit_sizes, fri_open_sizes, fri_sizes, pack, witness_decommit_sizes
+from . import (CAP_NONE, CAP_READ, ProofParts, composition_log_size, decommit_sizes, fri_open_sizes, fri_sizes, pack, proof_bytes_bound,
+               proof_list, witness_decommit_sizes)
 
 _FLAGS = ("acc", "ok", "low_degree")
 _WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
@@ -66,7 +69,7 @@ def proof_bytes(lp, lq, sums, config, commitments, samples, openings, nonce, lay
 
 class Chain:
     """Chain(ctx, program, n, log_blowup): n proofs through witness() -> trace() -> commit() -> decommit() / tree3() ->
-    sample() -> fri() -> pow() -> open() / fri_open() -> proofs().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
+    sample() -> fri() -> pow() -> open() / fri_open() -> proofs() or pack().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
     ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
     a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3)."""
 
@@ -94,12 +97,16 @@ class Chain:
                 raise ValueError(f"Chain.{stage}() needs {b}() first")
 
     def witness(self, proofs_or_blob, inputs, by_variable=False):
-        """Context.witness on proofs (a list of bytes) or a packed (blob, offsets); by_variable: the context's
-        witness_layout option is "by_variable"."""
+        """Context.witness on proofs (a list of bytes) or a packed (blob, offsets): numpy arrays, or device tensors (uint8
+        and int64[n + 1], what pack() returns), which are used as they are; by_variable: the context's witness_layout
+        option is "by_variable"."""
         import torch
         blob, offsets = pack(proofs_or_blob) if isinstance(proofs_or_blob, list) else proofs_or_blob
         n, wp = self.n, self.program
-        self._blob = (torch.from_numpy(blob.copy()).to(self.device), torch.from_numpy(offsets.astype(np.int64)).to(self.device))
+        if torch.is_tensor(blob):
+            self._blob = (blob, offsets)
+        else:
+            self._blob = (torch.from_numpy(blob.copy()).to(self.device), torch.from_numpy(offsets.astype(np.int64)).to(self.device))
         F = wp.shape.flow_count
         self._vars = self._new(*((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4)), fill=0)
         self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
@@ -252,6 +259,41 @@ class Chain:
             out.append(proof_bytes(self.lp, self.lq, a["sums"][k], (self.pow_bits, b, last, nq), np.concatenate([a["roots"][k], a["root3"][k][None]]),
                                    np.concatenate([a["samples"][k], a["samples3"][k]]), openings, a["nonce"][k], layers, a["last_poly"][k], last))
         return out
+
+    def pack(self, exact=False):
+        """-> (d_blob uint8, d_offsets int64[n + 1]) on the device: the serialised proofs in the verifier's blob layout
+        (Context.proof_pack pointed into the chain's own tensors), proof k at d_blob[d_offsets[k]:d_offsets[k + 1]], an empty
+        slot where ok is 0.  exact=False: the blob is sized by the capacities (proof_bytes_bound) and nothing synchronises;
+        exact=True: an offsets-only call, d_offsets[n] is read (synchronises), the blob holds exactly the proofs.  torch's
+        stream is made to wait for the context, so the pair may be read with torch as well as handed to a Context call."""
+        import torch
+        self._need("pack", "open", "fri_open")
+        n, b, last, nq = self.n, self.log_blowup, self.log_last, self.queries.shape[1]
+        T = self.fri_roots.shape[1]
+        vcaps = witness_decommit_sizes(self.program, b, nq)[0]
+        vat = np.cumsum([0] + vcaps)
+        wcap, v3, w3 = self.witness_nodes.shape[2], self.values3.shape[1], self.witness3.shape[1]
+        fv, fw = self.fri_witness.shape[2], self.fri_hash_witness.shape[2]
+        parts = ProofParts(self.lp, self.lq, self.pow_bits, b, last, nq, T, *(t.data_ptr() for t in (
+            self.sums, self.roots, self.root3, self.samples, self.samples3, self.nonce, self.fri_roots, self.last_poly)))
+        for t in range(3):
+            parts.values[t] = proof_list(self.values, int(vat[3]), self.n_values, 3, vcaps[t], items_at=int(vat[t]), count_at=t)
+            parts.witness[t] = proof_list(self.witness_nodes, 3 * wcap * 8, self.n_witness, 3, wcap, items_at=t * wcap * 8, count_at=t)
+        parts.values[3] = proof_list(self.values3, v3, self.n_values3, 1, v3)
+        parts.witness[3] = proof_list(self.witness3, w3 * 8, self.n_witness3, 1, w3)
+        parts.fri_witness = proof_list(self.fri_witness, T * fv * 4, self.n_fri_witness, T, fv)
+        parts.fri_hash_witness = proof_list(self.fri_hash_witness, T * fw * 8, self.n_fri_hash_witness, T, fw)
+        d_offsets = torch.full((n + 1,), -1 if self.fill else 0, dtype=torch.int64, device=self.device)
+        if exact:
+            self.ctx.proof_pack(parts, n, None, d_offsets, d_mask=self.ok)
+            self.ctx.release_to_torch()
+            size = int(d_offsets[n].item())
+        else:
+            size = n * proof_bytes_bound(last, T, vcaps + [v3] + [wcap] * 3 + [w3] + [fv, fw] * T)
+        d_blob = torch.full((max(size, 4),), self.fill & 0xFF, dtype=torch.uint8, device=self.device)[:size]
+        self.ctx.proof_pack(parts, n, d_blob, d_offsets, d_mask=self.ok)
+        self.ctx.release_to_torch()
+        return d_blob, d_offsets
 
     def numpy(self):
         """Synchronises -> {name: array} of every tensor allocated so far: uint32 views, the flags uint8; ops cut to the

@@ -35,6 +35,7 @@
 #include "k_fri.hpp"
 #include "k_pow.hpp"
 #include "k_fri_open.hpp"
+#include "k_pack.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -85,6 +86,8 @@ struct VerifyState;                       // stage clock of the last verify call
 void destroy_verify_state(VerifyState*);
 struct HostPipe;                          // pinned staging ring of rsv_verify_batch_host (host_stream.inc)
 void destroy_host_pipe(HostPipe*);
+struct PackState;                         // map and workspace of rsv_proof_pack_dev (pack_api.inc)
+void destroy_pack_state(PackState*);
 }  // namespace
 
 struct rsv_ctx {
@@ -120,6 +123,7 @@ struct rsv_ctx {
     rsv_public_input* d_pi = nullptr;
     size_t d_pi_cap = 0;
     HostPipe* host_pipe = nullptr;
+    PackState* pack = nullptr;
     Options opt;
 };
 
@@ -233,6 +237,7 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ev_front) (void)hipEventDestroy(c->ev_front);
     if (c->vs) destroy_verify_state(c->vs);
     if (c->host_pipe) destroy_host_pipe(c->host_pipe);
+    if (c->pack) destroy_pack_state(c->pack);
     if (c->ws) (void)hipFree(c->ws);
     if (c->ws_fixed) (void)hipFree(c->ws_fixed);
     if (c->ws_rows) (void)hipFree(c->ws_rows);
@@ -531,3 +536,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "fri_api.inc"
 #include "pow_api.inc"
 #include "fri_open_api.inc"
+#include "pack_api.inc"
