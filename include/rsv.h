@@ -995,6 +995,49 @@ int rsv_fri_open_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* d_lay
                      uint32_t n_queries, uint32_t* d_fri_witness, uint32_t* d_n_fri_witness, uint32_t* d_hash_witness,
                      uint32_t* d_n_hash_witness);
 
+/* ---- the caps of the FRI layer trees --------------------------------------------------------------------------------------
+ * The commitment keeps the top of every layer tree; the opening then hashes only the subtrees that hold a witness node.
+ * sub_log = h, 1 <= h <= RSV_MAX_FRI_SUB_LOG.  A tree with leaves at `top` keeps its layers 1 .. c, c = max(top - h, 0) (the
+ * root, layer 0, is in d_roots and nobody's witness; a tree with top <= h keeps nothing); below layer c it is 2^c subtrees of
+ * 2^(top - c) leaves.  d_caps is level-major and proof-minor: tree after tree (t = 0 .. n_inner), within a tree layer 1 .. c_t
+ * one after another, a layer [n][2^l][8] — the form the commitment's level kernel writes and reads, so the kept levels are
+ * written where they stay and the commitment gains no launch.  Tree t begins tree_words[t] words into d_caps, its layer l
+ * n * 8 * (2^l - 2) words after that, proof p's nodes of it p * 8 * 2^l words further.
+ *
+ * rsv_fri_cap_sizes: host arithmetic: cap_words = n * sum over the trees of 8 * (2^(c_t + 1) - 2), the words of d_caps for n
+ * proofs, and tree_words [1 + n_inner] (may be NULL).  Refusals as rsv_fri_open_sizes' (n above 2^20 with them); sub_log
+ * outside 1 .. RSV_MAX_FRI_SUB_LOG: RSV_E_SIZE. */
+#define RSV_MAX_FRI_SUB_LOG 8
+int rsv_fri_cap_sizes(const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, uint32_t sub_log, size_t n,
+                      size_t* cap_words, size_t* tree_words);
+/* rsv_fri_commit_dev that also leaves d_caps [cap_words]; with d_caps NULL it is exactly rsv_fri_commit_dev (sub_log is not
+ * read).  Every other output is bit for bit rsv_fri_commit_dev's, through the same launches.  Every word of d_caps is
+ * written, pass by pass where the proofs are cut into passes; a masked proof's entries are defined but meaningless.
+ * Refusals before any device work: rsv_fri_commit_dev's, in its order; sub_log outside 1 .. RSV_MAX_FRI_SUB_LOG, d_caps not
+ * 4-byte aligned: RSV_E_SIZE. */
+int rsv_fri_commit_cap_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup,
+                           uint32_t log_last, size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas,
+                           uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps);
+/* rsv_witness_fri_dev with the same two trailing arguments (sizes for rsv_fri_cap_sizes: rsv_fri_sizes'); d_caps NULL:
+ * exactly rsv_witness_fri_dev. */
+int rsv_witness_fri_caps_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                             const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                             const uint8_t* d_ok, size_t n, uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp,
+                             const uint32_t* d_oods, const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel,
+                             uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                             uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps);
+/* rsv_fri_open_dev from the caps: outputs and capacities are rsv_fri_open_dev's, word for word; every word is written, zero
+ * past a count, zeros for a masked proof (whose entries of d_caps are never read).  d_caps is trusted as given (as a cap
+ * under RSV_CAP_READ), with the sub_log and n it was written with.  A witness node at a layer <= c is read from d_caps; one
+ * above layer c comes from the subtree under its layer-c ancestor, which one workgroup hashes again in LDS from d_quot /
+ * d_layers: at most 2 n_queries subtrees per (proof, tree), six launches whatever M is, no node buffers in the workspace.
+ * Refusals before any device work: rsv_fri_open_dev's, in its order, d_caps NULL among the pointers (RSV_E_NULL), sub_log
+ * outside 1 .. RSV_MAX_FRI_SUB_LOG with n_queries and d_caps not 4-byte aligned with the pointers (RSV_E_SIZE). */
+int rsv_fri_open_cap_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* d_layers, const uint32_t* sizes, size_t n_sizes,
+                         uint32_t log_blowup, uint32_t log_last, size_t n, const uint8_t* d_mask, const uint32_t* d_queries,
+                         uint32_t n_queries, uint32_t* d_fri_witness, uint32_t* d_n_fri_witness, uint32_t* d_hash_witness,
+                         uint32_t* d_n_hash_witness, uint32_t sub_log, const uint32_t* d_caps);
+
 /* ---- the next proof serialised: the chain's buffers into the verifier's blob layout ------------------------------------------
  * What the stages above leave, put into the bytes of a PlonkWithPoseidonProof on the device: n proofs as (d_blob,
  * d_offsets), the pair every _dev entry point that takes a blob consumes (rsv_verify_batch_dev, rsv_witness_eval_dev of the

@@ -263,6 +263,11 @@ def _load() -> ctypes.CDLL:
         "rsv_draw_queries_dev": (ctypes.c_int, [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]),
         "rsv_fri_open_sizes": (ctypes.c_int, [_u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "rsv_fri_open_dev": (ctypes.c_int, [vp, vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, ctypes.c_uint32, vp, vp, vp, vp]),
+        "rsv_fri_cap_sizes": (ctypes.c_int, [_u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
+        "rsv_fri_commit_cap_dev": (ctypes.c_int, [vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]),
+        "rsv_witness_fri_caps_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12 + [ctypes.c_uint32, vp]),
+        "rsv_fri_open_cap_dev": (ctypes.c_int, [vp, vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, ctypes.c_uint32, vp, vp, vp, vp,
+                                                ctypes.c_uint32, vp]),
         "rsv_proof_bytes": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(sz)]),
         "rsv_proof_pack_dev": (ctypes.c_int, [vp, ctypes.POINTER(ProofParts), sz, vp, vp, sz, vp]),
         "rsv_witness_commit": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
@@ -316,6 +321,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_composition_log_size", "rsv_composition_dev", "rsv_witness_tree3_dev",
            "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
            "rsv_pow_grind_dev", "rsv_draw_queries_dev", "rsv_fri_open_sizes", "rsv_fri_open_dev",
+           "rsv_fri_cap_sizes", "rsv_fri_commit_cap_dev", "rsv_witness_fri_caps_dev", "rsv_fri_open_cap_dev",
            "rsv_proof_bytes", "rsv_proof_pack_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
@@ -881,6 +887,16 @@ def fri_open_sizes(sizes, log_blowup: int, log_last: int, n_queries: int):
     return v.value, w.value
 
 
+def fri_cap_sizes(sizes, log_blowup: int, log_last: int, sub_log: int, n: int = 1):
+    """rsv_fri_cap_sizes: (cap_words, tree_words): the words of d_caps for n proofs and per layer tree the words before it; layer
+    l (1 .. max(top - sub_log, 0)) of tree t is uint32[n, 2^l, 8] at tree_words[t] + n * 8 * (2^l - 2).  Host arithmetic."""
+    sz = _u32(list(sizes))
+    words = ctypes.c_size_t()
+    trees = (ctypes.c_size_t * 32)()
+    _check(lib.rsv_fri_cap_sizes(sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, sub_log, n, ctypes.byref(words), trees), "rsv_fri_cap_sizes")
+    return words.value, [int(trees[t]) for t in range(int(sz[0]) - log_last - log_blowup)]
+
+
 def proof_bytes_bound(log_last: int, n_layers: int, counts) -> int:
     """rsv_proof_bytes: the length in bytes of a serialised proof with the given counts, 8 + 2 n_layers of them: values of
     trees 0-3, witness nodes of trees 0-3, then per layer tree its fri_witness values and hash_witness nodes.  With the
@@ -1265,29 +1281,37 @@ class Context:
                                          ptr(d_samples), ptr(d_after), ptr(d_quot)), "rsv_fri_quotients_dev")
 
     def fri_commit(self, d_quot, sizes, log_blowup: int, log_last: int, n: int, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                   d_low_degree, d_mask=None):
+                   d_low_degree, d_mask=None, sub_log: int = 0, d_caps=None):
         """rsv_fri_commit_dev: d_quot as Context.fri_quotients wrote it, sizes its columns' LDE log sizes (descending);
         d_channel uint32[n, 16] (updated), d_roots uint32[n, 1 + n_inner, 8], d_alphas uint32[n, 1 + n_inner, 4], d_layers the
         inner layers per proof (may be None when there is none), d_last_poly uint32[n, 2^log_last, 4], d_low_degree uint8[n];
-        enqueued on the context's stream."""
+        with sub_log or d_caps uint32[cap_words] (fri_cap_sizes), rsv_fri_commit_cap_dev; enqueued on the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         sz = _u32(list(sizes))
         self.acquire_from_torch()
-        _check(lib.rsv_fri_commit_dev(self._h, ptr(d_quot), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask), ptr(d_channel), ptr(d_roots),
-                                      ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree)), "rsv_fri_commit_dev")
+        lead = (self._h, ptr(d_quot), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask), ptr(d_channel), ptr(d_roots),
+                ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree))
+        if d_caps is None and not sub_log:
+            _check(lib.rsv_fri_commit_dev(*lead), "rsv_fri_commit_dev")
+        else:
+            _check(lib.rsv_fri_commit_cap_dev(*lead, sub_log, ptr(d_caps)), "rsv_fri_commit_cap_dev")
 
     def witness_fri(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int,
                     log_blowup: int, log_last: int, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas,
-                    d_layers, d_last_poly, d_low_degree, d_ok=None):
+                    d_layers, d_last_poly, d_low_degree, d_ok=None, sub_log: int = 0, d_caps=None):
         """rsv_witness_fri_dev on what Context.witness_tree3 and Context.witness_sample left (d_comp, d_oods, d_samples3,
         d_samples uint32[n, 134, 4], d_channel uint32[n, 16], updated): d_after uint32[n, 4], d_quot uint32[n, quot_words],
-        d_layers uint32[n, layer_words] (fri_sizes), and the outputs of Context.fri_commit; enqueued on the context's stream."""
+        d_layers uint32[n, layer_words] (fri_sizes), and the outputs of Context.fri_commit; with sub_log or d_caps,
+        rsv_witness_fri_caps_dev; enqueued on the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         self.acquire_from_torch()
-        _check(lib.rsv_witness_fri_dev(self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk), ptr(d_int_poseidon),
-                                       ptr(d_accept), ptr(d_ok), n, log_blowup, log_last, ptr(d_comp), ptr(d_oods), ptr(d_samples),
-                                       ptr(d_samples3), ptr(d_channel), ptr(d_after), ptr(d_quot), ptr(d_roots), ptr(d_alphas), ptr(d_layers),
-                                       ptr(d_last_poly), ptr(d_low_degree)), "rsv_witness_fri_dev")
+        lead = (self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n,
+                log_blowup, log_last, ptr(d_comp), ptr(d_oods), ptr(d_samples), ptr(d_samples3), ptr(d_channel), ptr(d_after), ptr(d_quot),
+                ptr(d_roots), ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree))
+        if d_caps is None and not sub_log:
+            _check(lib.rsv_witness_fri_dev(*lead), "rsv_witness_fri_dev")
+        else:
+            _check(lib.rsv_witness_fri_caps_dev(*lead, sub_log, ptr(d_caps)), "rsv_witness_fri_caps_dev")
 
     def pow_grind(self, pow_bits: int, n: int, d_ok, d_channel, d_nonce, start: int = 0, max_tries: int = 0):
         """rsv_pow_grind_dev: the smallest nonce >= start (of max_tries candidates; 0: 2^(pow_bits + 6)) whose mix into
@@ -1308,17 +1332,21 @@ class Context:
                                         ptr(d_queries_low)), "rsv_draw_queries_dev")
 
     def fri_open(self, d_quot, d_layers, sizes, log_blowup: int, log_last: int, n: int, d_queries, n_queries: int, d_fri_witness,
-                 d_n_fri_witness, d_hash_witness, d_n_hash_witness, d_mask=None):
+                 d_n_fri_witness, d_hash_witness, d_n_hash_witness, d_mask=None, sub_log: int = 0, d_caps=None):
         """rsv_fri_open_dev on what Context.fri_commit took and left (d_quot, sizes, d_layers; d_layers may be None when there
         is no inner layer) at d_queries uint32[n, n_queries] (positions of sizes[0] bits): d_fri_witness uint32[n, T,
         values_cap, 4], d_n_fri_witness uint32[n, T], d_hash_witness uint32[n, T, witness_cap, 8], d_n_hash_witness uint32[n,
-        T] (T = 1 + n_inner; capacities: fri_open_sizes); enqueued on the context's stream."""
+        T] (T = 1 + n_inner; capacities: fri_open_sizes); with sub_log or d_caps (what Context.fri_commit left under the same
+        sub_log), rsv_fri_open_cap_dev; enqueued on the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         sz = _u32(list(sizes))
         self.acquire_from_torch()
-        _check(lib.rsv_fri_open_dev(self._h, ptr(d_quot), ptr(d_layers), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask),
-                                    ptr(d_queries), n_queries, ptr(d_fri_witness), ptr(d_n_fri_witness), ptr(d_hash_witness),
-                                    ptr(d_n_hash_witness)), "rsv_fri_open_dev")
+        lead = (self._h, ptr(d_quot), ptr(d_layers), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask), ptr(d_queries),
+                n_queries, ptr(d_fri_witness), ptr(d_n_fri_witness), ptr(d_hash_witness), ptr(d_n_hash_witness))
+        if d_caps is None and not sub_log:
+            _check(lib.rsv_fri_open_dev(*lead), "rsv_fri_open_dev")
+        else:
+            _check(lib.rsv_fri_open_cap_dev(*lead, sub_log, ptr(d_caps)), "rsv_fri_open_cap_dev")
 
     def proof_pack(self, parts: ProofParts, n: int, d_blob, d_offsets, d_mask=None, blob_cap=None):
         """rsv_proof_pack_dev: the n proofs `parts` (a ProofParts; its lists from proof_list) points at, serialised into d_blob

@@ -10,12 +10,12 @@ next level takes as it is.
 """
 import numpy as np
 
-from . import (CAP_NONE, CAP_READ, ProofParts, composition_log_size, decommit_sizes, fri_open_sizes, fri_sizes, pack, proof_bytes_bound,
-               proof_list, witness_decommit_sizes)
+from . import (CAP_NONE, CAP_READ, ProofParts, composition_log_size, decommit_sizes, fri_cap_sizes, fri_open_sizes, fri_sizes, pack,
+               proof_bytes_bound, proof_list, witness_decommit_sizes)
 
 _FLAGS = ("acc", "ok", "low_degree")
 _WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
-            "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree",
+            "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree", "fri_caps",
             "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3",
             "fri_witness", "n_fri_witness", "fri_hash_witness", "n_fri_hash_witness")
 SAMPLES_PER_COLUMN = ([1] * 50, [1] * 60, [1, 1, 1, 1, 2, 2, 2, 2] * 2, [1] * 8)  # sampled_values of trees 0-3
@@ -71,11 +71,13 @@ class Chain:
     """Chain(ctx, program, n, log_blowup): n proofs through witness() -> trace() -> commit() -> decommit() / tree3() ->
     sample() -> fri() -> pow() -> open() / fri_open() -> proofs() or pack().  The tensors are attributes (None until their stage has run): uint32 words as int32, the flags acc,
     ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
-    a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3)."""
+    a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3);
+    fri_sub_log = h (1 .. 8) also keeps the caps of the FRI layer trees (fri), from which fri_open() then rebuilds subtrees
+    of at most 2^h leaves only."""
 
-    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, device="cuda:0"):
+    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, device="cuda:0"):
         self.ctx, self.program, self.n, self.log_blowup, self.log_last = ctx, program, n, log_blowup, log_last
-        self.fill, self.with_caps, self.device = fill, caps, device
+        self.fill, self.with_caps, self.fri_sub_log, self.device = fill, caps, fri_sub_log, device
         self.lp, self.lq = program.trace_sizes()
         self.n_ops = len(program.gates()[1])
         self.done = set()
@@ -173,7 +175,7 @@ class Chain:
 
     def fri(self):
         """Context.witness_fri (log_last as given to the constructor): `after`, the quotient columns, the layers' roots and
-        alphas, the inner layers, the last polynomial, low_degree; the channel moves on."""
+        alphas, the inner layers, the last polynomial, low_degree (and fri_caps, with fri_sub_log); the channel moves on."""
         self._need("fri", "tree3", "sample")
         if self.log_last is None:
             raise ValueError("Chain.fri() needs log_last")
@@ -184,8 +186,11 @@ class Chain:
             self.after, self.quot, self.fri_roots, self.alphas = self._new(n, 4), self._new(n, sz["quot_words"]), self._new(n, 1 + ni, 8), self._new(n, 1 + ni, 4)
             self.layers, self.last_poly = self._new(n, max(sz["layer_words"], 1)), self._new(n, 1 << last, 4)
             self.low_degree = self._new(n, flag=True)
+            if self.fri_sub_log:
+                self.fri_caps = self._new(max(fri_cap_sizes(sz["sizes"], b, last, self.fri_sub_log, n)[0], 1))
         self.ctx.witness_fri(*self._lead(), b, last, self.comp, self.oods, self.samples, self.samples3, self.channel, self.after, self.quot,
-                             self.fri_roots, self.alphas, self.layers, self.last_poly, self.low_degree, d_ok=self.ok)
+                             self.fri_roots, self.alphas, self.layers, self.last_poly, self.low_degree, d_ok=self.ok,
+                             sub_log=self.fri_sub_log, d_caps=self.fri_caps)
         self.done.add("fri")
 
     def pow(self, pow_bits, n_queries, start=0, max_tries=0):
@@ -224,10 +229,11 @@ class Chain:
                                self.witness3, self.n_witness3, d_mask=self.ok, cap_mode=CAP_NONE if cap3 is None else CAP_READ, d_cap=cap3)
         self.done.add("open")
 
-    def fri_open(self):
+    def fri_open(self, caps=True):
         """The openings of the FRI layer trees at the queries pow() drew: Context.fri_open on quot and layers into fri_witness
         [n, T, v, 4], n_fri_witness [n, T], fri_hash_witness [n, T, w, 8], n_fri_hash_witness [n, T] (T = 1 + n_inner;
-        fri_open_sizes); every tree is hashed again."""
+        fri_open_sizes).  From fri_caps where the chain keeps them (fri_sub_log); otherwise, and with caps=False, every tree
+        is hashed again."""
         self._need("fri_open", "pow")
         n, b, last, nq = self.n, self.log_blowup, self.log_last, self.queries.shape[1]
         sz = fri_sizes(self.lp, self.lq, b, last)
@@ -236,8 +242,10 @@ class Chain:
             vcap, wcap = fri_open_sizes(sz["sizes"], b, last, nq)
             self.fri_witness, self.n_fri_witness = self._new(n, T, vcap, 4), self._new(n, T)
             self.fri_hash_witness, self.n_fri_hash_witness = self._new(n, T, wcap, 8), self._new(n, T)
+        d_caps = self.fri_caps if caps else None
         self.ctx.fri_open(self.quot, self.layers, sz["sizes"], b, last, n, self.queries, nq, self.fri_witness, self.n_fri_witness,
-                          self.fri_hash_witness, self.n_fri_hash_witness, d_mask=self.ok)
+                          self.fri_hash_witness, self.n_fri_hash_witness, d_mask=self.ok, sub_log=self.fri_sub_log if d_caps is not None else 0,
+                          d_caps=d_caps)
         self.done.add("fri_open")
 
     def proofs(self):

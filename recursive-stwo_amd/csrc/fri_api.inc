@@ -1,6 +1,7 @@
 // fri_api.inc — rsv_fri_sizes, rsv_fri_quotients_dev (the DEEP quotient columns over their whole domains),
 // rsv_fri_commit_dev (the FRI layers' trees, the transcript between them, the folds, the last layer's polynomial) and
-// rsv_witness_fri_dev (both from the chain's buffers): k_fri.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after
+// rsv_witness_fri_dev (both from the chain's buffers), rsv_fri_cap_sizes and the two forms that also leave the caps of the layer
+// trees (rsv_fri_commit_cap_dev, rsv_witness_fri_caps_dev): k_fri.hpp, include/rsv.h.  Included at the end of rsv_hip.hip, after
 // composition_api.inc.
 //
 // Quotients: one quotient column (one LDE log size) at a time; its groups are interpolated (from evaluations) and
@@ -175,16 +176,34 @@ size_t fr_commit_ws_bytes(uint32_t M, uint32_t L, size_t P, char* base, FrCommit
     return sz.off;
 }
 
+// No level of a tree is kept: fr_tree's levels go through the two node buffers.
+inline uint32_t* fr_keep_none(uint32_t) { return nullptr; }
+
+// The caps of the layer trees (include/rsv.h: rsv_fri_cap_sizes): tree t, leaves at M - t, keeps its layers 1 .. max(M - t -
+// h, 0), each [n][2^l][8], the trees and layers one after another.  -> the words of all; tree_at [1 + n_inner] (may be
+// nullptr): the words before tree t.
+uint64_t fr_cap_words(uint32_t M, uint32_t n_inner, uint32_t h, uint64_t n, uint64_t* tree_at) {
+    uint64_t at = 0;
+    for (uint32_t t = 0; t <= n_inner; t++) {
+        if (tree_at) tree_at[t] = at;
+        at += n * (((uint64_t)16 << rsv::fo_cap_layers(M - t, h)) - 16);
+    }
+    return at;
+}
+
 // One layer tree of a pass of Pc proofs, a launch of k_fr_hash_layer per level top .. last: level l goes to na when top - l
 // is even and to nb when it is odd (level 0 to root), and is the next level's children.  data_at(l, &stride): the level's
-// column, or nullptr; after(l, nodes) runs behind each level's launch.  fri_commit (last = 0) and fri_open (last = 1) share it.
-template <class DataAt, class After>
-void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t* na, uint32_t* nb, uint32_t* root, DataAt data_at, After after) {
+// column, or nullptr; kept(l): where a level the caller keeps goes instead ([Pc][2^l][8]), or nullptr; after(l, nodes) runs
+// behind each level's launch.  fri_commit (last = 0) and fri_open (last = 1) share it.
+template <class DataAt, class Kept, class After>
+void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t* na, uint32_t* nb, uint32_t* root, DataAt data_at, Kept kept,
+             After after) {
     const uint32_t* child = nullptr;
     for (uint32_t l = top + 1; l-- > last;) {
         uint64_t dstride = 0;
         const uint32_t* data = data_at(l, &dstride);
         uint32_t* out = l == 0 ? root : ((top - l) & 1 ? nb : na);
+        if (uint32_t* k = kept(l)) out = k;
         hipLaunchKernelGGL(rsv::k_fr_hash_layer, dim3(grid_for((size_t)Pc << l, 256)), dim3(256), 0, st, data, dstride, l, Pc, child, out);
         after(l, out);
         child = out;
@@ -193,7 +212,7 @@ void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t*
 
 int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n,
                const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly,
-               uint8_t* d_low_degree) {
+               uint8_t* d_low_degree, uint32_t sub_log = 0, uint32_t* d_caps = nullptr) {
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
     const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L;
@@ -216,6 +235,8 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
     if (rc != RSV_OK) return rc;
     hipStream_t st = c->stream;
     const uint64_t rstride = (uint64_t)(1 + n_inner) * 8, astride = (uint64_t)(1 + n_inner) * 4;
+    rsv::FoCaps caps{d_caps, {}, n, sub_log};
+    if (d_caps) fr_cap_words(M, n_inner, sub_log, n, caps.tree_at);
     auto column_of = [&](uint32_t l) -> int {
         for (size_t s = 0; s < ns; s++)
             if (sizes[s] == l) return (int)s;
@@ -229,8 +250,17 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         uint32_t* roots = d_roots + p0 * rstride;
         uint32_t* alphas = d_alphas + p0 * astride;
         uint32_t* layers = d_layers ? d_layers + p0 * lstride : nullptr;
-        // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root
-        auto tree = [&](uint32_t top, auto data_at) { fr_tree(st, Pc, top, 0, w.na, w.nb, w.root, data_at, [](uint32_t, const uint32_t*) {}); };
+        // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root.  With d_caps the
+        // levels 1 .. c go to the pass's proofs of the cap instead of a node buffer, and are read from there as children.
+        auto tree = [&](uint32_t top, auto data_at) {
+            const auto none = [](uint32_t, const uint32_t*) {};
+            if (!d_caps) return fr_tree(st, Pc, top, 0, w.na, w.nb, w.root, data_at, fr_keep_none, none);
+            const uint32_t t = M - top;
+            fr_tree(
+                st, Pc, top, 0, w.na, w.nb, w.root, data_at,
+                [&](uint32_t l) -> uint32_t* { return l >= 1 && l <= rsv::fo_cap_layers(top, sub_log) ? d_caps + rsv::fo_cap_at(caps, t, l, p0) : nullptr; },
+                none);
+        };
         auto draw = [&](uint32_t idx) {
             hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
                                alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
@@ -371,16 +401,53 @@ int rsv_fri_commit_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes
     return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
 }
 
-int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
-                        const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
-                        uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
-                        const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots,
-                        uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree) {
+int rsv_fri_cap_sizes(const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, uint32_t sub_log, size_t n, size_t* cap_words,
+                      size_t* tree_words) {
+    if (!sizes || !cap_words) return RSV_E_NULL;
+    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    if (rc != RSV_OK) return rc;
+    if (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG) return RSV_E_SIZE;
+    const uint32_t n_inner = sizes[0] - 1 - log_last - log_blowup;
+    uint64_t at[rsv::FO_MAX_TREES];
+    *cap_words = (size_t)fr_cap_words(sizes[0], n_inner, sub_log, n, at);
+    for (uint32_t t = 0; tree_words && t <= n_inner; t++) tree_words[t] = (size_t)at[t];
+    return RSV_OK;
+}
+
+int rsv_fri_commit_cap_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last,
+                           size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                           uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps) {
+    if (!d_caps)
+        return rsv_fri_commit_dev(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                                  d_low_degree);
+    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
+    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    if (rc != RSV_OK) return rc;
+    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG) return RSV_E_SIZE;
+    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
+        ((uintptr_t)d_last_poly & 3) || ((uintptr_t)d_caps & 3))
+        return RSV_E_SIZE;
+    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree,
+                      sub_log, d_caps);
+}
+
+}  // extern "C"
+
+namespace {
+
+// rsv_witness_fri_dev; with d_caps, rsv_witness_fri_caps_dev.
+int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
+                const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
+                uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
+                const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas,
+                uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps) {
     const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup};
     if (chain_null(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_last_poly, d_low_degree))
         return RSV_E_NULL;
     if (chain_misaligned(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly))
         return RSV_E_SIZE;
+    if (d_caps && (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG || ((uintptr_t)d_caps & 3))) return RSV_E_SIZE;
     if (prog->gates.empty()) return RSV_E_SIZE;  // built programs only
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     uint32_t sizes[3];
@@ -426,7 +493,31 @@ int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint3
     }
     rc = fri_quotients(c, g, fs, ng, n, log_blowup, mask, RSV_SAMPLE_COLUMNS, pts, 3, d_after, d_quot);
     if (rc != RSV_OK) return rc;
-    return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
+    return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log,
+                      d_caps);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
+                        const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
+                        uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
+                        const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots,
+                        uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree) {
+    return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
+                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, 0, nullptr);
+}
+
+int rsv_witness_fri_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                             const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                             const uint8_t* d_ok, size_t n, uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods,
+                             const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot,
+                             uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
+                             uint32_t sub_log, uint32_t* d_caps) {
+    return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
+                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // k_fri_open.hpp — the opening of the FRI layer trees (fri_open_api.inc drives the launches; include/rsv.h:
 // rsv_fri_open_dev): the plan of a (proof, tree)'s queries, the gather of the planned witness nodes after each rebuilt
-// level, the gather of the planned values.
+// level, the gather of the planned values; and for rsv_fri_open_cap_dev the list of the subtrees that hold a planned node,
+// their rebuilding in LDS and the gather from the caps (at the end of the file).
 //
 // stwo's pair-tree decommitment (consumed by SinglePairMerkleProof::from_stwo_proof).  A tree has leaves at layer `top`
 // and a QM31 value per node at its data layers D: tree 0 (the first layer) top = M and D = the quotient columns' sizes,
@@ -241,6 +242,151 @@ __global__ __launch_bounds__(256) void k_fo_values(FoData d, FoPlan pl, const ui
         v = s[((uint64_t)j << l) + x];
     }
     out[g] = v;
+}
+
+// ---------------------------------------------------------------- the cap form (rsv_fri_open_cap_dev)
+// rsv_fri_commit_cap_dev keeps layers 1 .. c of every tree, c = max(top - h, 0), in d_caps; below layer c a tree is 2^c
+// subtrees of 2^(top - c) leaves.  A planned node above layer c comes from the rebuilt subtree under its layer-c ancestor
+// (k_fo_sublist names those, k_fo_subtree hashes them in LDS), a planned node at a layer <= c from the cap (k_fo_cap_gather).
+constexpr uint32_t FO_MAX_TREES = 29;   // 1 + RSV_MAX_FRI_INNER
+constexpr uint32_t FO_MAX_SUB_LOG = 8;  // RSV_MAX_FRI_SUB_LOG
+
+__host__ __device__ inline uint32_t fo_cap_layers(uint32_t top, uint32_t h) { return top > h ? top - h : 0; }
+
+// d_caps, level-major and proof-minor: tree after tree, in a tree layer 1 .. c one after another, a layer [n][2^l][8] — what
+// k_fr_hash_layer writes as `out` and reads as `child`.
+struct FoCaps {
+    const uint32_t* caps;
+    uint64_t tree_at[FO_MAX_TREES];  // words before tree t
+    uint64_t n;
+    uint32_t h;
+};
+// Where proof p's nodes of layer l (1 <= l <= c) of tree t begin.
+__host__ __device__ inline uint64_t fo_cap_at(const FoCaps& k, uint32_t t, uint32_t l, uint64_t p) {
+    return k.tree_at[t] + k.n * (((uint64_t)8 << l) - 16) + ((p << l) << 3);
+}
+
+// The subtrees of every (proof, tree) (workspace): at most 2 nq, S_c holding every one of them.
+struct FoSubs {
+    uint32_t* cnt;  // [pt]
+    uint32_t* ids;  // [pt][2 nq] ascending: positions in layer c
+};
+
+// One workgroup of 128 lanes per (proof, tree): the distinct layer-c ancestors of the planned nodes above layer c (the
+// slots below woff[c]).  A layer's nodes are ascending, so is what lies above them in layer c: a slot opens a subtree when
+// its neighbour to the left lies under another one and a search of every layer before it finds none under the same.
+__global__ __launch_bounds__(128) void k_fo_sublist(FoPlan pl, uint32_t h, FoSubs sb) {
+    __shared__ uint32_t ids[2 * 128];
+    __shared__ uint32_t cnt;
+    const uint32_t p = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+    const size_t pt = (size_t)p * pl.T + t;
+    const uint32_t top = pl.M - t, c = fo_cap_layers(top, h), cap = 2 * pl.nq;
+    const uint32_t* woff = pl.woff + pt * DC_LAYERS;
+    const uint32_t* wnode = pl.wnode + pt * pl.wcap;
+    const uint32_t end = min(woff[c], pl.wcap);
+    if (tid == 0) cnt = 0;
+    __syncthreads();
+    for (uint32_t s = tid; s < end; s += 128) {
+        uint32_t l = top;  // layer l's nodes are the slots woff[l] .. woff[l - 1] - 1
+        while (l > c + 1 && s >= woff[l - 1]) l--;
+        const uint32_t a = wnode[s] >> (l - c);
+        bool opens = s == woff[l] || (wnode[s - 1] >> (l - c)) != a;
+        for (uint32_t u = top; opens && u > l; u--) {
+            const uint32_t stop = min(woff[u - 1], end);
+            uint32_t lo = woff[u], hi = stop;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if ((wnode[mid] >> (u - c)) < a) lo = mid + 1;
+                else hi = mid;
+            }
+            opens = !(lo < stop && (wnode[lo] >> (u - c)) == a);
+        }
+        if (opens) {
+            const uint32_t k = atomicAdd(&cnt, 1u);
+            if (k < cap) ids[k] = a;
+        }
+    }
+    __syncthreads();
+    const uint32_t m = min(cnt, cap);
+    for (uint32_t i = tid; i < m; i += 128) {
+        const uint32_t v = ids[i];
+        uint32_t r = 0;
+        for (uint32_t j = 0; j < m; j++) r += ids[j] < v ? 1u : 0u;
+        sb.ids[pt * cap + r] = v;
+    }
+    if (tid == 0) sb.cnt[pt] = m;
+}
+
+// One workgroup of 256 lanes per (proof, tree, listed subtree): k_fr_hash_layer's levels top .. c + 1 of the subtree under
+// node `id` of layer c, a lane per node, every level kept in LDS (word-major, level c + e at entries 2^e + j; the subtree's
+// own root is a node of the cap, or the tree's root, and is not hashed); then the planned nodes that lie in this subtree
+// to their slots of d_hash_witness, a lane per word.  out: d_hash_witness of proof 0.
+__global__ __launch_bounds__(256) void k_fo_subtree(FoData d, FoPlan pl, uint32_t h, FoSubs sb, uint32_t* __restrict__ out) {
+    __shared__ uint32_t node[8][2u << FO_MAX_SUB_LOG];
+    const uint32_t cap = 2 * pl.nq, tid = threadIdx.x;
+    const uint64_t pt = blockIdx.x / cap;
+    const uint32_t k = blockIdx.x - (uint32_t)pt * cap;
+    if (k >= sb.cnt[pt]) return;  // the whole workgroup
+    const uint64_t p = pt / pl.T;
+    const uint32_t t = (uint32_t)(pt - p * pl.T);
+    const uint32_t top = pl.M - t, c = fo_cap_layers(top, h), sl = top - c;
+    const uint32_t id = sb.ids[pt * cap + k];
+    if (id >> c) return;  // not a node of layer c: nothing is read past a column's end
+    for (uint32_t e = sl; e >= 1; e--) {
+        const uint32_t l = c + e;
+        if (tid < (1u << e)) {
+            const uint32_t* s = nullptr;
+            if (t == 0 ? pl.dmask >> l & 1u : l == top)
+                s = (t ? d.layers + p * d.lstride + fr_layer_off(pl.M, l) : d.quot + p * d.qstride + d.col_at[l]) + (((uint64_t)id << e) + tid);
+            Hash8 dc = zero8();
+            if (s) dc = sponge_capacity4<1>(s[0], s[(uint64_t)1 << l], s[(uint64_t)2 << l], s[(uint64_t)3 << l]);
+            Hash8 v;
+            if (e == sl) {
+                v = leaf_from_capacity<1>(dc);
+            } else {
+                const uint32_t at = (2u << e) + 2 * tid;
+                Hash8 a, b;
+#pragma unroll
+                for (int w = 0; w < 8; w++) {
+                    a.w[w] = node[w][at];
+                    b.w[w] = node[w][at + 1];
+                }
+                v = hash_tree<1>(a, b);
+                if (s) v = combine_with_column<1>(v, dc);
+            }
+#pragma unroll
+            for (int w = 0; w < 8; w++) node[w][(1u << e) + tid] = v.w[w];
+        }
+        __syncthreads();
+    }
+    const uint32_t* woff = pl.woff + pt * DC_LAYERS;
+    const uint32_t* wnode = pl.wnode + pt * pl.wcap;
+    const uint32_t end = min(woff[c], pl.wcap);
+    for (uint32_t g = tid; g < end * 8; g += 256) {
+        const uint32_t slot = g >> 3, w = g & 7;
+        uint32_t l = top;
+        while (l > c + 1 && slot >= woff[l - 1]) l--;
+        const uint32_t e = l - c, x = wnode[slot];
+        if ((x >> e) == id) out[(pt * pl.wcap + slot) * 8 + w] = node[w][(1u << e) + (x & ((1u << e) - 1))];
+    }
+}
+
+// The planned nodes of the layers <= c from the caps, one lane per word of d_hash_witness [n][T][wcap][8].
+__global__ __launch_bounds__(256) void k_fo_cap_gather(FoCaps kc, FoPlan pl, uint32_t n, uint32_t* __restrict__ out) {
+    const uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= (uint64_t)n * pl.T * pl.wcap * 8) return;
+    const uint32_t w = (uint32_t)(g & 7);
+    const uint32_t slot = (uint32_t)((g >> 3) % pl.wcap);
+    const uint64_t pt = (g >> 3) / pl.wcap;
+    const uint64_t p = pt / pl.T;
+    const uint32_t t = (uint32_t)(pt - p * pl.T);
+    const uint32_t c = fo_cap_layers(pl.M - t, kc.h);
+    const uint32_t* woff = pl.woff + pt * DC_LAYERS;
+    if (c == 0 || slot < woff[c] || slot >= woff[0]) return;
+    uint32_t l = c;
+    while (l > 1 && slot >= woff[l - 1]) l--;
+    const uint32_t x = pl.wnode[pt * pl.wcap + slot];
+    out[g] = kc.caps[fo_cap_at(kc, t, l, p) + (uint64_t)x * 8 + w];
 }
 
 }  // namespace rsv

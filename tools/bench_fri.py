@@ -9,7 +9,9 @@ Timed interleaved, `--steps` rounds, HIP events on the context's stream, medians
                the quotient call does again);
   fri          rsv_witness_fri_dev on what tree 3 and the sampling left (the channel is restored before every call):
                the sample mixes, the quotient columns and the layers;
-  fri_commit   rsv_fri_commit_dev alone on the quotient columns that call left.
+  fri_commit   rsv_fri_commit_dev alone on the quotient columns that call left;
+  fri_commit_cap  with `--sub-log h` (1 .. 8): rsv_fri_commit_cap_dev on the same columns in the same rounds, leaving the caps
+               of the layer trees (the same launches: the kept levels are written where they stay).
 `quotients` is fri - fri_commit.  The shares of the row kernel (k_fr_rows), the extension (k_cm_fft_*), the layer trees
 (k_fr_hash_layer), the folds (k_fr_fold) and the channel steps (k_fr_draw) are the rows of
 `rocprofv3 --kernel-trace --stats -- python tools/bench_fri.py ...`."""
@@ -23,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     add_args(ap, "level10-1.bin", 1)
     ap.add_argument("--log-last", type=int, default=0)
+    ap.add_argument("--sub-log", type=int, default=0)
     args = ap.parse_args()
     rsv, ctx, wp, ch = open_chain(args, "sample", log_last=args.log_last)
     import torch
@@ -41,14 +44,23 @@ def main():
         "fri_commit": lambda: ctx.fri_commit(ch.quot, sz["sizes"], b, args.log_last, n, ch.channel, ch.fri_roots, ch.alphas, ch.layers,
                                              ch.last_poly, ch.low_degree, d_mask=ch.ok),
     }
+    extra = {}
+    if args.sub_log:
+        cap_words = rsv.fri_cap_sizes(sz["sizes"], b, args.log_last, args.sub_log, n)[0]
+        caps = torch.zeros(max(cap_words, 1), dtype=torch.int32, device=ch.device)
+        calls["fri_commit_cap"] = lambda: ctx.fri_commit(ch.quot, sz["sizes"], b, args.log_last, n, ch.channel, ch.fri_roots, ch.alphas, ch.layers,
+                                                         ch.last_poly, ch.low_degree, d_mask=ch.ok, sub_log=args.sub_log, d_caps=caps)
+        extra = {"sub_log": args.sub_log, "cap_words": cap_words}
     times, med = time_interleaved(ctx, calls, args.steps, max(args.warmup, 1))
+    if args.sub_log:
+        extra["commit_cap_over_fri_commit"] = round(med["fri_commit_cap"] / med["fri_commit"], 5)
     ok = int(ch.ok.sum().item())
     positions = sum(1 << s for s in sz["sizes"])
     print(json.dumps({"tool": "bench_fri", "fixture": args.fixture, "log_plonk": lp, "log_poseidon": lq, "sizes": sz["sizes"], "n_inner": ni,
                       "log_blowup": b, "log_last": args.log_last, "proofs": n, "ok": ok, "low_degree": int(ch.low_degree.sum().item()),
                       "ms": {k: round(v, 4) for k, v in med.items()}, "ms_all": {k: [round(t, 4) for t in v] for k, v in times.items()},
                       "quotients_ms": round(med["fri"] - med["fri_commit"], 4), "fri_over_commit": round(med["fri"] / med["commit"], 5),
-                      "quotient_positions_per_proof": positions}))
+                      "quotient_positions_per_proof": positions, **extra}))
     ctx.close()
     wp.close()
 
