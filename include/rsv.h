@@ -1026,6 +1026,31 @@ int rsv_witness_fri_caps_dev(rsv_ctx* ctx, const rsv_witness_program* prog, cons
                              const uint32_t* d_oods, const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel,
                              uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                              uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps);
+/* ---- the tail form of the commit phase --------------------------------------------------------------------------------------
+ * rsv_fri_commit_cap_dev with one more argument, tail_log = t, 0 <= t <= RSV_MAX_FRI_TAIL_LOG.  t = 0 is exactly
+ * rsv_fri_commit_cap_dev (d_caps NULL: rsv_fri_commit_dev, sub_log is not read): one launch per tree level, one channel launch
+ * and one or two fold launches per layer.  With t > 0 every output, d_caps included, is bit for bit the same, through fewer
+ * launches: the levels t .. 0 of every layer tree and the channel step on its root are one launch, a workgroup per proof that
+ * hashes them in LDS (a tree with leaves at or below level t entirely); and, when log_last + log_blowup <= t, every inner
+ * layer of log size <= t (its tree, its channel step, its fold and the column that joins it) and the last layer (the
+ * interpolation, d_last_poly, d_low_degree, the final mixes) are one launch more, a workgroup per proof with the evaluation
+ * kept in LDS (64 KiB at t = 10).  It pays for one proof, and at t up to about 8: a level of more than 256 nodes takes the one
+ * workgroup several rounds of dependent permutations where the per-layer form spreads it over as many compute units, and
+ * those rounds, not the launch boundaries, are what the commit phase costs (profiles/HISTORY.md, "FRI tail").
+ * Refusals before any device work: rsv_fri_commit_cap_dev's, in its order; then tail_log > RSV_MAX_FRI_TAIL_LOG: RSV_E_SIZE. */
+#define RSV_MAX_FRI_TAIL_LOG 10
+int rsv_fri_commit_tail_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup,
+                            uint32_t log_last, size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas,
+                            uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps,
+                            uint32_t tail_log);
+/* rsv_witness_fri_caps_dev with the same trailing argument; tail_log 0: exactly rsv_witness_fri_caps_dev.  Refusals: its own,
+ * in its order; then tail_log > RSV_MAX_FRI_TAIL_LOG: RSV_E_SIZE. */
+int rsv_witness_fri_tail_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                             const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                             const uint8_t* d_ok, size_t n, uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp,
+                             const uint32_t* d_oods, const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel,
+                             uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                             uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log);
 /* rsv_fri_open_dev from the caps: outputs and capacities are rsv_fri_open_dev's, word for word; every word is written, zero
  * past a count, zeros for a masked proof (whose entries of d_caps are never read).  d_caps is trusted as given (as a cap
  * under RSV_CAP_READ), with the sub_log and n it was written with.  A witness node at a layer <= c is read from d_caps; one

@@ -266,6 +266,9 @@ def _load() -> ctypes.CDLL:
         "rsv_fri_cap_sizes": (ctypes.c_int, [_u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]),
         "rsv_fri_commit_cap_dev": (ctypes.c_int, [vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp]),
         "rsv_witness_fri_caps_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12 + [ctypes.c_uint32, vp]),
+        "rsv_fri_commit_tail_dev": (ctypes.c_int, [vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, vp, vp, vp, vp, vp, ctypes.c_uint32, vp,
+                                                   ctypes.c_uint32]),
+        "rsv_witness_fri_tail_dev": (ctypes.c_int, [vp] * 9 + [sz, ctypes.c_uint32, ctypes.c_uint32] + [vp] * 12 + [ctypes.c_uint32, vp, ctypes.c_uint32]),
         "rsv_fri_open_cap_dev": (ctypes.c_int, [vp, vp, vp, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, sz, vp, vp, ctypes.c_uint32, vp, vp, vp, vp,
                                                 ctypes.c_uint32, vp]),
         "rsv_proof_bytes": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _u32p, ctypes.POINTER(sz)]),
@@ -322,6 +325,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_fri_sizes", "rsv_fri_quotients_dev", "rsv_fri_commit_dev", "rsv_witness_fri_dev",
            "rsv_pow_grind_dev", "rsv_draw_queries_dev", "rsv_fri_open_sizes", "rsv_fri_open_dev",
            "rsv_fri_cap_sizes", "rsv_fri_commit_cap_dev", "rsv_witness_fri_caps_dev", "rsv_fri_open_cap_dev",
+           "rsv_fri_commit_tail_dev", "rsv_witness_fri_tail_dev",
            "rsv_proof_bytes", "rsv_proof_pack_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
@@ -1281,34 +1285,39 @@ class Context:
                                          ptr(d_samples), ptr(d_after), ptr(d_quot)), "rsv_fri_quotients_dev")
 
     def fri_commit(self, d_quot, sizes, log_blowup: int, log_last: int, n: int, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                   d_low_degree, d_mask=None, sub_log: int = 0, d_caps=None):
+                   d_low_degree, d_mask=None, sub_log: int = 0, d_caps=None, tail_log: int = 0):
         """rsv_fri_commit_dev: d_quot as Context.fri_quotients wrote it, sizes its columns' LDE log sizes (descending);
         d_channel uint32[n, 16] (updated), d_roots uint32[n, 1 + n_inner, 8], d_alphas uint32[n, 1 + n_inner, 4], d_layers the
         inner layers per proof (may be None when there is none), d_last_poly uint32[n, 2^log_last, 4], d_low_degree uint8[n];
-        with sub_log or d_caps uint32[cap_words] (fri_cap_sizes), rsv_fri_commit_cap_dev; enqueued on the context's stream."""
+        with sub_log or d_caps uint32[cap_words] (fri_cap_sizes), rsv_fri_commit_cap_dev; with tail_log (1 .. 10),
+        rsv_fri_commit_tail_dev: the same outputs through fewer launches; enqueued on the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         sz = _u32(list(sizes))
         self.acquire_from_torch()
         lead = (self._h, ptr(d_quot), sz.ctypes.data_as(_u32p), len(sz), log_blowup, log_last, n, ptr(d_mask), ptr(d_channel), ptr(d_roots),
                 ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree))
-        if d_caps is None and not sub_log:
+        if tail_log:
+            _check(lib.rsv_fri_commit_tail_dev(*lead, sub_log, ptr(d_caps), tail_log), "rsv_fri_commit_tail_dev")
+        elif d_caps is None and not sub_log:
             _check(lib.rsv_fri_commit_dev(*lead), "rsv_fri_commit_dev")
         else:
             _check(lib.rsv_fri_commit_cap_dev(*lead, sub_log, ptr(d_caps)), "rsv_fri_commit_cap_dev")
 
     def witness_fri(self, program: WitnessProgram, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, n: int,
                     log_blowup: int, log_last: int, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas,
-                    d_layers, d_last_poly, d_low_degree, d_ok=None, sub_log: int = 0, d_caps=None):
+                    d_layers, d_last_poly, d_low_degree, d_ok=None, sub_log: int = 0, d_caps=None, tail_log: int = 0):
         """rsv_witness_fri_dev on what Context.witness_tree3 and Context.witness_sample left (d_comp, d_oods, d_samples3,
         d_samples uint32[n, 134, 4], d_channel uint32[n, 16], updated): d_after uint32[n, 4], d_quot uint32[n, quot_words],
         d_layers uint32[n, layer_words] (fri_sizes), and the outputs of Context.fri_commit; with sub_log or d_caps,
-        rsv_witness_fri_caps_dev; enqueued on the context's stream."""
+        rsv_witness_fri_caps_dev; with tail_log, rsv_witness_fri_tail_dev; enqueued on the context's stream."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         self.acquire_from_torch()
         lead = (self._h, program._h, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops), ptr(d_int_plonk), ptr(d_int_poseidon), ptr(d_accept), ptr(d_ok), n,
                 log_blowup, log_last, ptr(d_comp), ptr(d_oods), ptr(d_samples), ptr(d_samples3), ptr(d_channel), ptr(d_after), ptr(d_quot),
                 ptr(d_roots), ptr(d_alphas), ptr(d_layers), ptr(d_last_poly), ptr(d_low_degree))
-        if d_caps is None and not sub_log:
+        if tail_log:
+            _check(lib.rsv_witness_fri_tail_dev(*lead, sub_log, ptr(d_caps), tail_log), "rsv_witness_fri_tail_dev")
+        elif d_caps is None and not sub_log:
             _check(lib.rsv_witness_fri_dev(*lead), "rsv_witness_fri_dev")
         else:
             _check(lib.rsv_witness_fri_caps_dev(*lead, sub_log, ptr(d_caps)), "rsv_witness_fri_caps_dev")

@@ -73,11 +73,12 @@ class Chain:
     ok and low_degree uint8.  Outputs are prefilled with `fill` (the flags ok and low_degree with 7 where fill is not 0), so
     a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3);
     fri_sub_log = h (1 .. 8) also keeps the caps of the FRI layer trees (fri), from which fri_open() then rebuilds subtrees
-    of at most 2^h leaves only."""
+    of at most 2^h leaves only; fri_tail_log = t (1 .. 10) runs fri()'s commit phase in the tail form (the same outputs through
+    fewer launches)."""
 
-    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, device="cuda:0"):
+    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, fri_tail_log=0, device="cuda:0"):
         self.ctx, self.program, self.n, self.log_blowup, self.log_last = ctx, program, n, log_blowup, log_last
-        self.fill, self.with_caps, self.fri_sub_log, self.device = fill, caps, fri_sub_log, device
+        self.fill, self.with_caps, self.fri_sub_log, self.fri_tail_log, self.device = fill, caps, fri_sub_log, fri_tail_log, device
         self.lp, self.lq = program.trace_sizes()
         self.n_ops = len(program.gates()[1])
         self.done = set()
@@ -190,7 +191,7 @@ class Chain:
                 self.fri_caps = self._new(max(fri_cap_sizes(sz["sizes"], b, last, self.fri_sub_log, n)[0], 1))
         self.ctx.witness_fri(*self._lead(), b, last, self.comp, self.oods, self.samples, self.samples3, self.channel, self.after, self.quot,
                              self.fri_roots, self.alphas, self.layers, self.last_poly, self.low_degree, d_ok=self.ok,
-                             sub_log=self.fri_sub_log, d_caps=self.fri_caps)
+                             sub_log=self.fri_sub_log, d_caps=self.fri_caps, tail_log=self.fri_tail_log)
         self.done.add("fri")
 
     def pow(self, pow_bits, n_queries, start=0, max_tries=0):

@@ -6,8 +6,10 @@
 //
 // Quotients: one quotient column (one LDE log size) at a time; its groups are interpolated (from evaluations) and
 // extended block by block with commit_api.inc's streaming helpers, and k_fr_rows consumes each pass of blocks.  Commit: the per-layer form,
-// one launch per tree level, one channel launch and one or two fold launches per layer; there is no single-workgroup tail
-// kernel for the small layers.
+// one launch per tree level, one channel launch and one or two fold launches per layer.  With tail_log = t > 0
+// (rsv_fri_commit_tail_dev, rsv_witness_fri_tail_dev) the tail form: a tree's levels t .. 0 and its channel step are one launch
+// of k_fr_tree_top, and, when the last layer is no larger than 2^t, every inner layer of log size <= t and the last layer are
+// one launch of k_fr_tail, a workgroup per proof each.  Same outputs, bit for bit.
 
 namespace {
 
@@ -194,9 +196,10 @@ uint64_t fr_cap_words(uint32_t M, uint32_t n_inner, uint32_t h, uint64_t n, uint
 // One layer tree of a pass of Pc proofs, a launch of k_fr_hash_layer per level top .. last: level l goes to na when top - l
 // is even and to nb when it is odd (level 0 to root), and is the next level's children.  data_at(l, &stride): the level's
 // column, or nullptr; kept(l): where a level the caller keeps goes instead ([Pc][2^l][8]), or nullptr; after(l, nodes) runs
-// behind each level's launch.  fri_commit (last = 0) and fri_open (last = 1) share it.
+// behind each level's launch.  fri_commit (last = 0, or tail_log + 1) and fri_open (last = 1) share it.  -> where level `last`
+// was left (nullptr when top < last).
 template <class DataAt, class Kept, class After>
-void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t* na, uint32_t* nb, uint32_t* root, DataAt data_at, Kept kept,
+const uint32_t* fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t* na, uint32_t* nb, uint32_t* root, DataAt data_at, Kept kept,
              After after) {
     const uint32_t* child = nullptr;
     for (uint32_t l = top + 1; l-- > last;) {
@@ -208,14 +211,16 @@ void fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last, uint32_t*
         after(l, out);
         child = out;
     }
+    return child;
 }
 
 int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n,
                const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly,
-               uint8_t* d_low_degree, uint32_t sub_log = 0, uint32_t* d_caps = nullptr) {
+               uint8_t* d_low_degree, uint32_t sub_log = 0, uint32_t* d_caps = nullptr, uint32_t tail_log = 0) {
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L;
+    const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L, T = tail_log;
+    const bool tail = T && L <= T;  // k_fr_tail takes the inner layers of log size <= T and the last layer
     uint64_t qstride = 0, col_at[FR_MAX_SIZES], lstride = 0;
     for (size_t s = 0; s < ns; s++) {
         col_at[s] = qstride;
@@ -242,28 +247,52 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
             if (sizes[s] == l) return (int)s;
         return -1;
     };
+    rsv::FrSmallCols small{};  // the columns k_fr_tree_top and k_fr_tail read themselves
+    const uint32_t* tail_inv_y[rsv::FR_TAIL_LOG + 1] = {};
+    for (size_t s = 0; s < ns && T; s++) {
+        if (sizes[s] > T) continue;
+        small.dmask |= 1u << sizes[s];
+        small.at[sizes[s]] = col_at[s];
+        tail_inv_y[sizes[s]] = inv_y[s] + rsv::cm_tw_off(sizes[s], 0);
+    }
+    small.qstride = qstride;
     for (size_t p0 = 0; p0 < n; p0 += P) {
         const uint32_t Pc = (uint32_t)std::min(P, n - p0);
         const uint8_t* mask = d_mask ? d_mask + p0 : nullptr;
         const uint32_t* quot = d_quot + p0 * qstride;
+        small.quot = quot;
         uint32_t* chan = d_channel + p0 * 16;
         uint32_t* roots = d_roots + p0 * rstride;
         uint32_t* alphas = d_alphas + p0 * astride;
         uint32_t* layers = d_layers ? d_layers + p0 * lstride : nullptr;
         // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root.  With d_caps the
         // levels 1 .. c go to the pass's proofs of the cap instead of a node buffer, and are read from there as children.
-        auto tree = [&](uint32_t top, auto data_at) {
+        // The tail form stops the launches at level T + 1.
+        auto tree = [&](uint32_t top, uint32_t stop, auto data_at) -> const uint32_t* {
             const auto none = [](uint32_t, const uint32_t*) {};
-            if (!d_caps) return fr_tree(st, Pc, top, 0, w.na, w.nb, w.root, data_at, fr_keep_none, none);
+            if (!d_caps) return fr_tree(st, Pc, top, stop, w.na, w.nb, w.root, data_at, fr_keep_none, none);
             const uint32_t t = M - top;
-            fr_tree(
-                st, Pc, top, 0, w.na, w.nb, w.root, data_at,
+            return fr_tree(
+                st, Pc, top, stop, w.na, w.nb, w.root, data_at,
                 [&](uint32_t l) -> uint32_t* { return l >= 1 && l <= rsv::fo_cap_layers(top, sub_log) ? d_caps + rsv::fo_cap_at(caps, t, l, p0) : nullptr; },
                 none);
         };
-        auto draw = [&](uint32_t idx) {
-            hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
-                               alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
+        const rsv::FrDraw step{mask, chan, roots, rstride, alphas, astride, d_low_degree + p0};
+        rsv::FrCapOut cap_out{d_caps, caps, 0, 0, p0};
+        // tree idx (leaves at top) and the channel step behind it: the per-layer form's launches, or the levels above T and k_fr_tree_top
+        auto layer_tree = [&](uint32_t idx, uint32_t top, auto data_at) {
+            if (!T) {
+                tree(top, 0, data_at);
+                hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
+                                   alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
+                return;
+            }
+            const uint32_t* child = top > T ? tree(top, T + 1, data_at) : nullptr;
+            cap_out.tree = idx;
+            cap_out.c = d_caps ? rsv::fo_cap_layers(top, sub_log) : 0;
+            rsv::FrSmallCols cols = small;
+            if (idx) cols.dmask = 0;  // an inner tree carries its evaluation at the leaves only, and those are above T
+            hipLaunchKernelGGL(rsv::k_fr_tree_top, dim3(Pc), dim3(256), 0, st, top, std::min(top, T), child, cols, cap_out, step, idx);
         };
         // where the running evaluation of log size l lives: inner layer M - 1 - l, or the last evaluation
         auto eval_at = [&](uint32_t l) -> rsv::FrVec {
@@ -271,12 +300,11 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
             return {layers + rsv::fr_layer_off(M, l), lstride};
         };
         // the first layer: every quotient column at its own level
-        tree(M, [&](uint32_t l, uint64_t* stride) -> const uint32_t* {
+        layer_tree(0, M, [&](uint32_t l, uint64_t* stride) -> const uint32_t* {
             const int s = column_of(l);
             *stride = qstride;
             return s < 0 ? nullptr : quot + col_at[s];
         });
-        draw(0);
         {
             const rsv::FrVec src{const_cast<uint32_t*>(quot), qstride};
             hipLaunchKernelGGL(rsv::k_fr_fold<false>, dim3(grid_for((size_t)Pc << (M - 1), 256)), dim3(256), 0, st, src, eval_at(M - 1), M, Pc,
@@ -284,12 +312,12 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         }
         for (uint32_t i = 0; i < n_inner; i++) {
             const uint32_t l = M - 1 - i;
+            if (tail && l <= T) break;
             const rsv::FrVec cur = eval_at(l), next = eval_at(l - 1);
-            tree(l, [&](uint32_t lv, uint64_t* stride) -> const uint32_t* {
+            layer_tree(i + 1, l, [&](uint32_t lv, uint64_t* stride) -> const uint32_t* {
                 *stride = cur.stride;
                 return lv == l ? cur.base : nullptr;
             });
-            draw(i + 1);
             const dim3 grid(grid_for((size_t)Pc << (l - 1), 256));
             hipLaunchKernelGGL(rsv::k_fr_fold<false>, grid, dim3(256), 0, st, cur, next, l, Pc, inv_x[l] + rsv::cm_tw_off(l + 1, 1), alphas + (i + 1) * 4,
                                astride, mask);
@@ -299,6 +327,22 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
                 hipLaunchKernelGGL(rsv::k_fr_fold<true>, grid, dim3(256), 0, st, src, next, l, Pc, inv_y[s] + rsv::cm_tw_off(l, 0), alphas + (i + 1) * 4,
                                    astride, mask);
             }
+        }
+        if (tail) {
+            // the evaluation the folds above left, of log size min(T, M - 1), through its layers and the last layer
+            rsv::FrTail a{};
+            a.M = M, a.L = L, a.log_last = log_last, a.l0 = std::min(T, M - 1);
+            const rsv::FrVec in = eval_at(a.l0);
+            a.in = in.base, a.istride = in.stride, a.layers = layers, a.lstride = lstride;
+            a.cols = small;
+            a.cols.dmask &= (2u << a.l0) - 1;
+            for (uint32_t l = L; l <= a.l0; l++) {
+                a.inv_x[l] = l == L ? inv_x[l] : inv_x[l] + rsv::cm_tw_off(l + 1, 1);
+                a.inv_y[l] = tail_inv_y[l];
+            }
+            a.last_poly = d_last_poly + ((p0 * 4) << log_last);
+            hipLaunchKernelGGL(rsv::k_fr_tail, dim3(Pc), dim3(256), 0, st, a, cap_out, step);
+            continue;
         }
         // the last layer: the evaluation's coefficients, the first 2^log_last out, the rest checked, the final mixes
         for (uint32_t m = 0; m < L; m++)
@@ -325,6 +369,21 @@ int fr_check_chain(uint32_t lp, uint32_t lq, uint32_t b, uint32_t log_last, size
     if (A != B) sizes[k++] = std::min(A, B);
     *ns = k;
     return fr_check_commit(sizes, k, b, log_last, n);
+}
+
+// What rsv_fri_commit_dev refuses, and with d_caps what rsv_fri_commit_cap_dev adds, in their order.
+int fr_commit_refusal(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
+                      uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
+                      uint32_t sub_log, uint32_t* d_caps) {
+    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
+    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    if (rc != RSV_OK) return rc;
+    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (d_caps && (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG)) return RSV_E_SIZE;
+    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
+        ((uintptr_t)d_last_poly & 3) || ((uintptr_t)d_caps & 3))
+        return RSV_E_SIZE;
+    return RSV_OK;
 }
 
 }  // namespace
@@ -391,13 +450,9 @@ int rsv_fri_quotients_dev(rsv_ctx* c, const rsv_commit_group* groups, const rsv_
 int rsv_fri_commit_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
                        const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                        uint32_t* d_last_poly, uint8_t* d_low_degree) {
-    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
-    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                                     d_low_degree, 0, nullptr);
     if (rc != RSV_OK) return rc;
-    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
-    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
-        ((uintptr_t)d_last_poly & 3))
-        return RSV_E_SIZE;
     return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
 }
 
@@ -420,28 +475,37 @@ int rsv_fri_commit_cap_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* s
     if (!d_caps)
         return rsv_fri_commit_dev(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
                                   d_low_degree);
-    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
-    const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
+    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                                     d_low_degree, sub_log, d_caps);
     if (rc != RSV_OK) return rc;
-    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
-    if (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG) return RSV_E_SIZE;
-    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
-        ((uintptr_t)d_last_poly & 3) || ((uintptr_t)d_caps & 3))
-        return RSV_E_SIZE;
     return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree,
                       sub_log, d_caps);
+}
+
+int rsv_fri_commit_tail_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last,
+                            size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
+                            uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log) {
+    if (tail_log == 0)
+        return rsv_fri_commit_cap_dev(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                                      d_low_degree, sub_log, d_caps);
+    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
+                                     d_low_degree, sub_log, d_caps);
+    if (rc != RSV_OK) return rc;
+    if (tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
+    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree,
+                      sub_log, d_caps, tail_log);
 }
 
 }  // extern "C"
 
 namespace {
 
-// rsv_witness_fri_dev; with d_caps, rsv_witness_fri_caps_dev.
+// rsv_witness_fri_dev; with d_caps, rsv_witness_fri_caps_dev; with tail_log, rsv_witness_fri_tail_dev.
 int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
                 const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
                 uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
                 const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas,
-                uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps) {
+                uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log = 0) {
     const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup};
     if (chain_null(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_last_poly, d_low_degree))
         return RSV_E_NULL;
@@ -455,6 +519,7 @@ int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_p
     int rc = fr_check_chain(lp, lq, log_blowup, log_last, n, sizes, &ns);
     if (rc != RSV_OK) return rc;
     if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
     ChainTrees ct;
     rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
@@ -494,7 +559,7 @@ int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_p
     rc = fri_quotients(c, g, fs, ng, n, log_blowup, mask, RSV_SAMPLE_COLUMNS, pts, 3, d_after, d_quot);
     if (rc != RSV_OK) return rc;
     return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log,
-                      d_caps);
+                      d_caps, tail_log);
 }
 
 }  // namespace
@@ -518,6 +583,17 @@ int rsv_witness_fri_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, const 
                              uint32_t sub_log, uint32_t* d_caps) {
     return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
                        d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps);
+}
+
+int rsv_witness_fri_tail_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
+                             const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,
+                             const uint8_t* d_ok, size_t n, uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods,
+                             const uint32_t* d_samples, const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot,
+                             uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
+                             uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log) {
+    return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
+                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps,
+                       tail_log);
 }
 
 }  // extern "C"

@@ -212,6 +212,25 @@ __global__ __launch_bounds__(64) void k_fr_draw(const uint32_t* __restrict__ roo
 // another, each [4][2^size]: 4 (2^M - 2^(l+1)) words.
 __host__ __device__ inline uint64_t fr_layer_off(uint32_t M, uint32_t l) { return ((uint64_t)4 << M) - ((uint64_t)8 << l); }
 
+// ---------------------------------------------------------------- the caps of the layer trees
+// rsv_fri_commit_cap_dev keeps layers 1 .. c of every tree, c = max(top - h, 0), in d_caps (k_fri_open.hpp reads them).
+constexpr uint32_t FO_MAX_TREES = 29;   // 1 + RSV_MAX_FRI_INNER
+
+__host__ __device__ inline uint32_t fo_cap_layers(uint32_t top, uint32_t h) { return top > h ? top - h : 0; }
+
+// d_caps, level-major and proof-minor: tree after tree, in a tree layer 1 .. c one after another, a layer [n][2^l][8] — what
+// k_fr_hash_layer writes as `out` and reads as `child`.
+struct FoCaps {
+    const uint32_t* caps;
+    uint64_t tree_at[FO_MAX_TREES];  // words before tree t
+    uint64_t n;
+    uint32_t h;
+};
+// Where proof p's nodes of layer l (1 <= l <= c) of tree t begin.
+__host__ __device__ inline uint64_t fo_cap_at(const FoCaps& k, uint32_t t, uint32_t l, uint64_t p) {
+    return k.tree_at[t] + k.n * (((uint64_t)8 << l) - 16) + ((p << l) << 3);
+}
+
 // ---------------------------------------------------------------- folds
 // A set of P QM31 vectors of 2^l values: coordinate j of proof p, value i at base + p * stride + (j << l) + i.
 struct FrVec {
@@ -314,6 +333,273 @@ __global__ __launch_bounds__(64) void k_fr_mix_last(const uint32_t* __restrict__
     }
     store_hash(co, ch.digest);
     co[8] = ch.n_sent;
+}
+
+// ---------------------------------------------------------------- the tail form (rsv_fri_commit_tail_dev, tail_log = t)
+// One workgroup of 256 lanes per proof finishes what the per-layer form spends a launch per level on: k_fr_tree_top the
+// levels t .. 0 of a layer tree and the channel step on its root, k_fr_tail every inner layer of log size <= t and the last
+// layer.  The node function is k_fr_hash_layer's, the channel step k_fr_draw's, the folds k_fr_fold's, the last layer
+// k_fr_line_layer's, k_fr_last's and k_fr_mix_last's: every output is the per-layer form's bit for bit.
+//
+// LDS, word-major as k_fo_subtree's: two node levels ping-ponged, level l in the first 2^T entries when first - l is even
+// and in the 2^(T-1) after them when it is odd (48 << T bytes); k_fr_tail also keeps the running evaluation, 4 x 2^T words
+// (16 << T bytes).  A level of more than 256 nodes is strided.  Every barrier is reached by the whole workgroup: a masked
+// proof is a value (`keep`), not a path.
+constexpr uint32_t FR_TAIL_LOG = 10;  // RSV_MAX_FRI_TAIL_LOG
+constexpr uint32_t FR_TAIL_NODES = 3u << (FR_TAIL_LOG - 1);
+
+// Where the kept levels of one tree of the pass go (caps == nullptr: nowhere): levels 1 .. c of tree `tree`, proof p0 + p.
+struct FrCapOut {
+    uint32_t* caps;
+    FoCaps at;
+    uint32_t tree, c;
+    uint64_t p0;
+};
+// What k_fr_draw takes, for the proofs of the pass.
+struct FrDraw {
+    const uint8_t* mask;
+    uint32_t* chan;
+    uint32_t* roots;
+    uint64_t rstride;
+    uint32_t* alphas;
+    uint64_t astride;
+    uint8_t* low;  // tree 0 only
+};
+// The quotient columns of log size <= FR_TAIL_LOG: bit l of dmask: one of log size l, coordinate j of proof p, value i at
+// quot + p * qstride + at[l] + (j << l) + i.
+struct FrSmallCols {
+    const uint32_t* quot;
+    uint64_t qstride;
+    uint64_t at[FR_TAIL_LOG + 1];
+    uint32_t dmask;
+};
+
+// Levels first .. 0 of one tree of leaves at `top` >= first, a lane per node.  Level first's children are child [2^(first +
+// 1)][8] (top > first) or none (the leaves); data(l, i, v): whether level l carries a column, and node i's four words of it.
+// cap(l): where level l is kept, or nullptr.  -> the root, in every lane.  Ends behind a barrier.
+template <class Data, class Cap>
+__device__ Hash8 fr_lds_tree(uint32_t (*node)[FR_TAIL_NODES], uint32_t top, uint32_t first, const uint32_t* __restrict__ child, Data data, Cap cap) {
+    const uint32_t tid = threadIdx.x;
+#pragma unroll 1
+    for (uint32_t l = first + 1; l-- > 0;) {
+        const uint32_t out = (first - l) & 1 ? 1u << FR_TAIL_LOG : 0u, in = out ? 0u : 1u << FR_TAIL_LOG;
+        uint32_t* kept = cap(l);
+#pragma unroll 1
+        for (uint32_t i = tid; i < (1u << l); i += 256) {
+            uint32_t v[4];
+            const bool has = data(l, i, v);
+            Hash8 d = zero8();
+            if (has) d = sponge_capacity4<1>(v[0], v[1], v[2], v[3]);
+            Hash8 h;
+            if (l == top) {
+                h = leaf_from_capacity<1>(d);
+            } else {
+                Hash8 a, b;
+                if (l == first) {
+                    a = load_hash(child + (uint64_t)i * 16);
+                    b = load_hash(child + (uint64_t)i * 16 + 8);
+                } else {
+#pragma unroll
+                    for (int w = 0; w < 8; w++) {
+                        a.w[w] = node[w][in + 2 * i];
+                        b.w[w] = node[w][in + 2 * i + 1];
+                    }
+                }
+                h = hash_tree<1>(a, b);
+                if (has) h = combine_with_column<1>(h, d);
+            }
+#pragma unroll
+            for (int w = 0; w < 8; w++) node[w][out + i] = h.w[w];
+            if (kept) store_hash(kept + (uint64_t)i * 8, h);
+        }
+        __syncthreads();
+    }
+    Hash8 r;
+    const uint32_t at = first & 1 ? 1u << FR_TAIL_LOG : 0u;
+#pragma unroll
+    for (int w = 0; w < 8; w++) r.w[w] = node[w][at];
+    return r;
+}
+
+// k_fr_draw's step for proof p of the pass and layer idx, by the one lane that calls it -> alpha (zero for a masked proof).
+__device__ inline QM31 fr_draw_one(const FrDraw& d, uint32_t p, uint32_t idx, bool keep, const Hash8& r) {
+    uint32_t* co = d.chan + (size_t)p * 16;
+    uint32_t* ro = d.roots + p * d.rstride + idx * 8;
+    uint32_t* ao = d.alphas + p * d.astride + idx * 4;
+    if (d.low && idx == 0) d.low[p] = keep ? 1 : 0;
+    if (!keep) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) co[i] = 0u;
+        store_hash(ro, zero8());
+#pragma unroll
+        for (int i = 0; i < 4; i++) ao[i] = 0u;
+        return q_zero();
+    }
+    Channel<0> ch;
+    ch.init();
+    ch.digest = load_hash(co);
+    ch.n_sent = co[8];
+    ch.mix(r);
+    const Hash8 dr = ch.draw();
+    store_hash(co, ch.digest);
+    co[8] = ch.n_sent;
+    store_hash(ro, r);
+#pragma unroll
+    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
+    return q_lo(dr);
+}
+
+__device__ __forceinline__ uint32_t* fr_cap_level(const FrCapOut& k, uint32_t tree, uint32_t c, uint32_t l, uint32_t p) {
+    return k.caps && l >= 1 && l <= c ? k.caps + fo_cap_at(k.at, tree, l, k.p0 + p) : nullptr;
+}
+
+// The top of layer tree idx of every proof of the pass: levels first = min(top, t) .. 0, then the channel step.  child: level
+// first + 1 of the pass, [P][2^(first + 1)][8] (not read when first == top); cols: the columns the levels carry (tree 0).
+__global__ __launch_bounds__(256) void k_fr_tree_top(uint32_t top, uint32_t first, const uint32_t* __restrict__ child, FrSmallCols cols,
+                                                     FrCapOut cap, FrDraw draw, uint32_t idx) {
+    __shared__ uint32_t node[8][FR_TAIL_NODES];
+    const uint32_t p = blockIdx.x;
+    const uint32_t* q = cols.dmask ? cols.quot + p * cols.qstride : nullptr;
+    const Hash8 r = fr_lds_tree(
+        node, top, first, first < top ? child + ((uint64_t)p << (first + 1)) * 8 : nullptr,
+        [&](uint32_t l, uint32_t i, uint32_t* v) {
+            if (!(cols.dmask >> l & 1u)) return false;
+            const uint32_t* s = q + cols.at[l] + i;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = s[(uint64_t)j << l];
+            return true;
+        },
+        [&](uint32_t l) { return fr_cap_level(cap, cap.tree, cap.c, l, p); });
+    if (threadIdx.x == 0) fr_draw_one(draw, p, idx, !draw.mask || draw.mask[p], r);
+}
+
+// The tail of every proof of the pass: the inner layers of log size l0 .. L + 1 (idx M - l each) and the last layer.
+struct FrTail {
+    uint32_t M, L, log_last, l0;
+    const uint32_t* in;   // the evaluation of log size l0: coordinate j of proof p, value i at in + p * istride + (j << l0) + i
+    uint64_t istride;
+    uint32_t* layers;     // of the pass's first proof (not read or written when l0 == L)
+    uint64_t lstride;
+    FrSmallCols cols;     // the columns that join: log sizes l0 .. L + 1
+    const uint32_t* inv_x[FR_TAIL_LOG + 1];  // [l], L < l <= l0: 1 / x of the line layer's pairs; [L]: the table of the interpolation
+    const uint32_t* inv_y[FR_TAIL_LOG + 1];  // [l], bit l of cols.dmask: 1 / y of the column's pairs
+    uint32_t* last_poly;  // of the pass's first proof
+};
+
+__global__ __launch_bounds__(256) void k_fr_tail(FrTail a, FrCapOut cap, FrDraw draw) {
+    static_assert((1u << (FR_TAIL_LOG - 1)) <= 2 * 256, "a fold keeps two results per lane");
+    __shared__ uint32_t node[8][FR_TAIL_NODES];
+    __shared__ uint32_t ev[4][1u << FR_TAIL_LOG];
+    __shared__ uint32_t s_alpha[4];
+    const uint32_t p = blockIdx.x, tid = threadIdx.x;
+    const bool keep = !draw.mask || draw.mask[p];
+    {
+        const uint32_t* s = a.in + p * a.istride;
+        for (uint32_t g = tid; g < (4u << a.l0); g += 256) ev[g >> a.l0][g & ((1u << a.l0) - 1)] = s[g];
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t l = a.l0; l > a.L; l--) {
+        const uint32_t idx = a.M - l;
+        const Hash8 r = fr_lds_tree(
+            node, l, l, nullptr,
+            [&](uint32_t lv, uint32_t i, uint32_t* v) {
+                if (lv != l) return false;
+#pragma unroll
+                for (int j = 0; j < 4; j++) v[j] = ev[j][i];
+                return true;
+            },
+            [&](uint32_t lv) { return fr_cap_level(cap, idx, fo_cap_layers(l, cap.at.h), lv, p); });
+        if (tid == 0) {
+            const QM31 al = fr_draw_one(draw, p, idx, keep, r);
+            s_alpha[0] = al.a.a; s_alpha[1] = al.a.b; s_alpha[2] = al.b.a; s_alpha[3] = al.b.b;
+        }
+        __syncthreads();
+        const QM31 alpha = q_mk(s_alpha[0], s_alpha[1], s_alpha[2], s_alpha[3]);
+        const bool join = a.cols.dmask >> l & 1u;
+        const uint32_t half = 1u << (l - 1);
+        QM31 v[2];
+#pragma unroll
+        for (int rr = 0; rr < 2; rr++) {
+            const uint32_t k = tid + rr * 256;
+            v[rr] = q_zero();
+            if (k < half && keep) {
+                const QM31 f0 = q_mk(ev[0][2 * k], ev[1][2 * k], ev[2][2 * k], ev[3][2 * k]);
+                const QM31 f1 = q_mk(ev[0][2 * k + 1], ev[1][2 * k + 1], ev[2][2 * k + 1], ev[3][2 * k + 1]);
+                v[rr] = q_add(q_add(f0, f1), q_mul(q_mul_m(q_sub(f0, f1), a.inv_x[l][k]), alpha));
+                if (join) {
+                    const uint32_t* s = a.cols.quot + p * a.cols.qstride + a.cols.at[l] + 2 * k;
+                    const QM31 g0 = fr_ld(s, l), g1 = fr_ld(s + 1, l);
+                    const QM31 c = q_add(q_add(g0, g1), q_mul(q_mul_m(q_sub(g0, g1), a.inv_y[l][k]), alpha));
+                    v[rr] = q_add(q_mul(q_mul(alpha, alpha), v[rr]), c);
+                }
+            }
+        }
+        __syncthreads();
+        // the next layer: where fri_open reads it, unless it is the last evaluation, which no one reads
+        uint32_t* d = l - 1 > a.L ? a.layers + p * a.lstride + fr_layer_off(a.M, l - 1) : nullptr;
+#pragma unroll
+        for (int rr = 0; rr < 2; rr++) {
+            const uint32_t k = tid + rr * 256;
+            if (k < half) {
+                ev[0][k] = v[rr].a.a; ev[1][k] = v[rr].a.b; ev[2][k] = v[rr].b.a; ev[3][k] = v[rr].b.b;
+                if (d) fr_st(d + k, l - 1, v[rr]);
+            }
+        }
+        __syncthreads();
+    }
+    // the last layer: k_fr_line_layer's butterflies, k_fr_last, k_fr_mix_last
+    const uint32_t L = a.L;
+#pragma unroll 1
+    for (uint32_t m = 0; m < L; m++) {
+        const uint32_t* winv = a.inv_x[L] + cm_tw_off(L + 1, m + 1);
+        for (uint32_t g = tid; g < (4u << (L - 1)); g += 256) {
+            const uint32_t row = g >> (L - 1), j = g & ((1u << (L - 1)) - 1);
+            const uint32_t a_at = ((j >> m) << (m + 1)) | (j & ((1u << m) - 1)), b_at = a_at + (1u << m);
+            uint32_t x = ev[row][a_at], y = ev[row][b_at];
+            cm_butterfly<true>(x, y, winv[a_at >> (m + 1)]);
+            ev[row][a_at] = x;
+            ev[row][b_at] = y;
+        }
+        __syncthreads();
+    }
+    const uint32_t scale = L ? 1u << (31 - L) : 1u;  // 2^-L mod P
+    uint32_t* last = a.last_poly + (((uint64_t)p << a.log_last) * 4);
+    for (uint32_t j = tid; j < (1u << L); j += 256) {
+        uint32_t w[4];
+#pragma unroll
+        for (int c = 0; c < 4; c++) w[c] = keep ? m_mul(ev[c][j], scale) : 0u;
+        if (j < (1u << a.log_last)) {
+            const uint32_t i = a.log_last ? bit_reverse(j, a.log_last) : 0u;
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                last[i * 4 + c] = w[c];
+                ev[c][j] = w[c];
+            }
+        } else if (w[0] | w[1] | w[2] | w[3]) {
+            draw.low[p] = 0;
+        }
+    }
+    __syncthreads();
+    if (tid == 0 && keep) {
+        uint32_t* co = draw.chan + (size_t)p * 16;
+        Channel<0> ch;
+        ch.init();
+        ch.digest = load_hash(co);
+        ch.n_sent = co[8];
+        const uint32_t n = 1u << a.log_last;
+        auto coef = [&](uint32_t i) {
+            const uint32_t j = a.log_last ? bit_reverse(i, a.log_last) : 0u;
+            return q_mk(ev[0][j], ev[1][j], ev[2][j], ev[3][j]);
+        };
+#pragma unroll 1
+        for (uint32_t i = 0; i < n; i += 2) {
+            if (i + 1 < n) ch.mix_two(coef(i), coef(i + 1));
+            else ch.mix_one(coef(i));
+        }
+        store_hash(co, ch.digest);
+        co[8] = ch.n_sent;
+    }
 }
 
 // ---------------------------------------------------------------- the recursion circuit's chain (rsv_witness_fri_dev)

@@ -248,23 +248,8 @@ __global__ __launch_bounds__(256) void k_fo_values(FoData d, FoPlan pl, const ui
 // rsv_fri_commit_cap_dev keeps layers 1 .. c of every tree, c = max(top - h, 0), in d_caps; below layer c a tree is 2^c
 // subtrees of 2^(top - c) leaves.  A planned node above layer c comes from the rebuilt subtree under its layer-c ancestor
 // (k_fo_sublist names those, k_fo_subtree hashes them in LDS), a planned node at a layer <= c from the cap (k_fo_cap_gather).
-constexpr uint32_t FO_MAX_TREES = 29;   // 1 + RSV_MAX_FRI_INNER
+// FoCaps, fo_cap_layers and fo_cap_at, the layout of d_caps, are k_fri.hpp's: the commitment's kernels write it.
 constexpr uint32_t FO_MAX_SUB_LOG = 8;  // RSV_MAX_FRI_SUB_LOG
-
-__host__ __device__ inline uint32_t fo_cap_layers(uint32_t top, uint32_t h) { return top > h ? top - h : 0; }
-
-// d_caps, level-major and proof-minor: tree after tree, in a tree layer 1 .. c one after another, a layer [n][2^l][8] — what
-// k_fr_hash_layer writes as `out` and reads as `child`.
-struct FoCaps {
-    const uint32_t* caps;
-    uint64_t tree_at[FO_MAX_TREES];  // words before tree t
-    uint64_t n;
-    uint32_t h;
-};
-// Where proof p's nodes of layer l (1 <= l <= c) of tree t begin.
-__host__ __device__ inline uint64_t fo_cap_at(const FoCaps& k, uint32_t t, uint32_t l, uint64_t p) {
-    return k.tree_at[t] + k.n * (((uint64_t)8 << l) - 16) + ((p << l) << 3);
-}
 
 // The subtrees of every (proof, tree) (workspace): at most 2 nq, S_c holding every one of them.
 struct FoSubs {
