@@ -9,7 +9,9 @@
 // one launch per tree level, one channel launch and one or two fold launches per layer.  With tail_log = t > 0
 // (rsv_fri_commit_tail_dev, rsv_witness_fri_tail_dev) the tail form: a tree's levels t .. 0 and its channel step are one launch
 // of k_fr_tree_top, and, when the last layer is no larger than 2^t, every inner layer of log size <= t and the last layer are
-// one launch of k_fr_tail, a workgroup per proof each.  Same outputs, bit for bit.
+// one launch of k_fr_tail, a workgroup per proof each.  Same outputs, bit for bit: the kernels of both forms call the same step
+// definitions (k_fri.hpp), and the three rsv_fri_commit*_dev entries are one checked path (fri_commit_checked) with zeros for what
+// an entry lacks.
 
 namespace {
 
@@ -214,12 +216,22 @@ const uint32_t* fr_tree(hipStream_t st, uint32_t Pc, uint32_t top, uint32_t last
     return child;
 }
 
+// What the commit phase leaves and which form it takes: the arguments of rsv_fri_commit_tail_dev behind d_mask.  sub_log counts
+// with d_caps only; tail_log 0: the per-layer form.
+struct FrOut {
+    uint32_t *d_channel, *d_roots, *d_alphas, *d_layers, *d_last_poly;
+    uint8_t* d_low_degree;
+    uint32_t sub_log;
+    uint32_t* d_caps;
+    uint32_t tail_log;
+};
+
 int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t ns, uint32_t b, uint32_t log_last, size_t n,
-               const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly,
-               uint8_t* d_low_degree, uint32_t sub_log = 0, uint32_t* d_caps = nullptr, uint32_t tail_log = 0) {
+               const uint8_t* d_mask, const FrOut& o) {
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L, T = tail_log;
+    const uint32_t M = sizes[0], L = log_last + b, n_inner = M - 1 - L, T = o.tail_log, sub_log = o.d_caps ? o.sub_log : 0;
+    uint32_t *const d_caps = o.d_caps, *const d_last_poly = o.d_last_poly;
     const bool tail = T && L <= T;  // k_fr_tail takes the inner layers of log size <= T and the last layer
     uint64_t qstride = 0, col_at[FR_MAX_SIZES], lstride = 0;
     for (size_t s = 0; s < ns; s++) {
@@ -261,10 +273,9 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
         const uint8_t* mask = d_mask ? d_mask + p0 : nullptr;
         const uint32_t* quot = d_quot + p0 * qstride;
         small.quot = quot;
-        uint32_t* chan = d_channel + p0 * 16;
-        uint32_t* roots = d_roots + p0 * rstride;
-        uint32_t* alphas = d_alphas + p0 * astride;
-        uint32_t* layers = d_layers ? d_layers + p0 * lstride : nullptr;
+        uint32_t* chan = o.d_channel + p0 * 16;
+        uint32_t* alphas = o.d_alphas + p0 * astride;
+        uint32_t* layers = o.d_layers ? o.d_layers + p0 * lstride : nullptr;
         // one tree: the levels top .. 0, `data_at` giving the level's column (or nullptr); the root to w.root.  With d_caps the
         // levels 1 .. c go to the pass's proofs of the cap instead of a node buffer, and are read from there as children.
         // The tail form stops the launches at level T + 1.
@@ -277,14 +288,15 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
                 [&](uint32_t l) -> uint32_t* { return l >= 1 && l <= rsv::fo_cap_layers(top, sub_log) ? d_caps + rsv::fo_cap_at(caps, t, l, p0) : nullptr; },
                 none);
         };
-        const rsv::FrDraw step{mask, chan, roots, rstride, alphas, astride, d_low_degree + p0};
+        const rsv::FrDraw step{mask, chan, o.d_roots + p0 * rstride, rstride, alphas, astride, o.d_low_degree + p0};
         rsv::FrCapOut cap_out{d_caps, caps, 0, 0, p0};
         // tree idx (leaves at top) and the channel step behind it: the per-layer form's launches, or the levels above T and k_fr_tree_top
         auto layer_tree = [&](uint32_t idx, uint32_t top, auto data_at) {
             if (!T) {
                 tree(top, 0, data_at);
-                hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, mask, Pc, chan, roots + idx * 8, rstride,
-                                   alphas + idx * 4, astride, idx == 0 ? d_low_degree + p0 : nullptr);
+                const rsv::FrDraw d = step.layer(idx);
+                hipLaunchKernelGGL(rsv::k_fr_draw, dim3(grid_for(Pc, 64)), dim3(64), 0, st, w.root, d.mask, Pc, d.chan, d.roots, d.rstride, d.alphas,
+                                   d.astride, d.low);
                 return;
             }
             const uint32_t* child = top > T ? tree(top, T + 1, data_at) : nullptr;
@@ -349,7 +361,7 @@ int fri_commit(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t
             hipLaunchKernelGGL(rsv::k_fr_line_layer, dim3(grid_for(((size_t)Pc * 4) << (L - 1), 256)), dim3(256), 0, st, w.last, L, m, Pc,
                                inv_x[L] + rsv::cm_tw_off(L + 1, m + 1));
         hipLaunchKernelGGL(rsv::k_fr_last, dim3(grid_for((size_t)Pc << L, 256)), dim3(256), 0, st, w.last, L, log_last, Pc, mask,
-                           d_last_poly + ((p0 * 4) << log_last), d_low_degree + p0);
+                           d_last_poly + ((p0 * 4) << log_last), o.d_low_degree + p0);
         hipLaunchKernelGGL(rsv::k_fr_mix_last, dim3(grid_for(Pc, 64)), dim3(64), 0, st, d_last_poly + ((p0 * 4) << log_last), log_last, mask, Pc,
                            chan);
     }
@@ -371,19 +383,20 @@ int fr_check_chain(uint32_t lp, uint32_t lq, uint32_t b, uint32_t log_last, size
     return fr_check_commit(sizes, k, b, log_last, n);
 }
 
-// What rsv_fri_commit_dev refuses, and with d_caps what rsv_fri_commit_cap_dev adds, in their order.
-int fr_commit_refusal(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
-                      uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
-                      uint32_t sub_log, uint32_t* d_caps) {
-    if (!c || !d_quot || !sizes || !d_channel || !d_roots || !d_alphas || !d_last_poly || !d_low_degree) return RSV_E_NULL;
+// The one checked path of rsv_fri_commit_dev, rsv_fri_commit_cap_dev and rsv_fri_commit_tail_dev: what the first refuses, with
+// d_caps what the second adds, then the third's bound, in that order.
+int fri_commit_checked(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
+                       const uint8_t* d_mask, const FrOut& o) {
+    if (!c || !d_quot || !sizes || !o.d_channel || !o.d_roots || !o.d_alphas || !o.d_last_poly || !o.d_low_degree) return RSV_E_NULL;
     const int rc = fr_check_commit(sizes, n_sizes, log_blowup, log_last, n);
     if (rc != RSV_OK) return rc;
-    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
-    if (d_caps && (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG)) return RSV_E_SIZE;
-    if (((uintptr_t)d_quot & 3) || ((uintptr_t)d_channel & 3) || ((uintptr_t)d_roots & 3) || ((uintptr_t)d_alphas & 3) || ((uintptr_t)d_layers & 3) ||
-        ((uintptr_t)d_last_poly & 3) || ((uintptr_t)d_caps & 3))
+    if (!o.d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (o.d_caps && (o.sub_log < 1 || o.sub_log > RSV_MAX_FRI_SUB_LOG)) return RSV_E_SIZE;
+    if (((uintptr_t)d_quot & 3) || ((uintptr_t)o.d_channel & 3) || ((uintptr_t)o.d_roots & 3) || ((uintptr_t)o.d_alphas & 3) ||
+        ((uintptr_t)o.d_layers & 3) || ((uintptr_t)o.d_last_poly & 3) || ((uintptr_t)o.d_caps & 3))
         return RSV_E_SIZE;
-    return RSV_OK;
+    if (o.tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
+    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, o);
 }
 
 }  // namespace
@@ -450,10 +463,8 @@ int rsv_fri_quotients_dev(rsv_ctx* c, const rsv_commit_group* groups, const rsv_
 int rsv_fri_commit_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, size_t n,
                        const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                        uint32_t* d_last_poly, uint8_t* d_low_degree) {
-    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                                     d_low_degree, 0, nullptr);
-    if (rc != RSV_OK) return rc;
-    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree);
+    return fri_commit_checked(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask,
+                              {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, 0, nullptr, 0});
 }
 
 int rsv_fri_cap_sizes(const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last, uint32_t sub_log, size_t n, size_t* cap_words,
@@ -472,28 +483,15 @@ int rsv_fri_cap_sizes(const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup
 int rsv_fri_commit_cap_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last,
                            size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                            uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps) {
-    if (!d_caps)
-        return rsv_fri_commit_dev(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                                  d_low_degree);
-    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                                     d_low_degree, sub_log, d_caps);
-    if (rc != RSV_OK) return rc;
-    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree,
-                      sub_log, d_caps);
+    return fri_commit_checked(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask,
+                              {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps, 0});
 }
 
 int rsv_fri_commit_tail_dev(rsv_ctx* c, const uint32_t* d_quot, const uint32_t* sizes, size_t n_sizes, uint32_t log_blowup, uint32_t log_last,
                             size_t n, const uint8_t* d_mask, uint32_t* d_channel, uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers,
                             uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log) {
-    if (tail_log == 0)
-        return rsv_fri_commit_cap_dev(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                                      d_low_degree, sub_log, d_caps);
-    const int rc = fr_commit_refusal(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_channel, d_roots, d_alphas, d_layers, d_last_poly,
-                                     d_low_degree, sub_log, d_caps);
-    if (rc != RSV_OK) return rc;
-    if (tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
-    return fri_commit(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree,
-                      sub_log, d_caps, tail_log);
+    return fri_commit_checked(c, d_quot, sizes, n_sizes, log_blowup, log_last, n, d_mask,
+                              {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps, tail_log});
 }
 
 }  // extern "C"
@@ -504,22 +502,22 @@ namespace {
 int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon, const uint32_t* d_ops,
                 const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept, const uint8_t* d_ok, size_t n,
                 uint32_t log_blowup, uint32_t log_last, const uint32_t* d_comp, const uint32_t* d_oods, const uint32_t* d_samples,
-                const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots, uint32_t* d_alphas,
-                uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree, uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log = 0) {
+                const uint32_t* d_samples3, uint32_t* d_after, uint32_t* d_quot, const FrOut& o) {
     const ChainArgs a{c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup};
-    if (chain_null(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_last_poly, d_low_degree))
+    uint32_t* const d_channel = o.d_channel;
+    if (chain_null(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, o.d_roots, o.d_alphas, o.d_last_poly, o.d_low_degree))
         return RSV_E_NULL;
-    if (chain_misaligned(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly))
+    if (chain_misaligned(a, d_comp, d_oods, d_samples, d_samples3, d_channel, d_after, d_quot, o.d_roots, o.d_alphas, o.d_layers, o.d_last_poly))
         return RSV_E_SIZE;
-    if (d_caps && (sub_log < 1 || sub_log > RSV_MAX_FRI_SUB_LOG || ((uintptr_t)d_caps & 3))) return RSV_E_SIZE;
+    if (o.d_caps && (o.sub_log < 1 || o.sub_log > RSV_MAX_FRI_SUB_LOG || ((uintptr_t)o.d_caps & 3))) return RSV_E_SIZE;
     if (prog->gates.empty()) return RSV_E_SIZE;  // built programs only
     const uint32_t lp = prog->trace_lp, lq = prog->trace_lq;
     uint32_t sizes[3];
     size_t ns = 0;
     int rc = fr_check_chain(lp, lq, log_blowup, log_last, n, sizes, &ns);
     if (rc != RSV_OK) return rc;
-    if (!d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
-    if (tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
+    if (!o.d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
+    if (o.tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
     ChainTrees ct;
     rc = chain_open(a, &ct);
     if (rc != RSV_OK || n == 0) return rc;
@@ -558,8 +556,7 @@ int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_p
     }
     rc = fri_quotients(c, g, fs, ng, n, log_blowup, mask, RSV_SAMPLE_COLUMNS, pts, 3, d_after, d_quot);
     if (rc != RSV_OK) return rc;
-    return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log,
-                      d_caps, tail_log);
+    return fri_commit(c, d_quot, sizes, ns, log_blowup, log_last, n, mask, o);
 }
 
 }  // namespace
@@ -572,7 +569,7 @@ int rsv_witness_fri_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint3
                         const uint32_t* d_samples3, uint32_t* d_channel, uint32_t* d_after, uint32_t* d_quot, uint32_t* d_roots,
                         uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree) {
     return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
-                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, 0, nullptr);
+                       d_samples, d_samples3, d_after, d_quot, {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, 0, nullptr, 0});
 }
 
 int rsv_witness_fri_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
@@ -582,7 +579,7 @@ int rsv_witness_fri_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, const 
                              uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
                              uint32_t sub_log, uint32_t* d_caps) {
     return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
-                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps);
+                       d_samples, d_samples3, d_after, d_quot, {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps, 0});
 }
 
 int rsv_witness_fri_tail_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
@@ -592,8 +589,7 @@ int rsv_witness_fri_tail_dev(rsv_ctx* c, const rsv_witness_program* prog, const 
                              uint32_t* d_roots, uint32_t* d_alphas, uint32_t* d_layers, uint32_t* d_last_poly, uint8_t* d_low_degree,
                              uint32_t sub_log, uint32_t* d_caps, uint32_t tail_log) {
     return witness_fri(c, prog, d_plonk, d_poseidon, d_ops, d_int_plonk, d_int_poseidon, d_accept, d_ok, n, log_blowup, log_last, d_comp, d_oods,
-                       d_samples, d_samples3, d_channel, d_after, d_quot, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps,
-                       tail_log);
+                       d_samples, d_samples3, d_after, d_quot, {d_channel, d_roots, d_alphas, d_layers, d_last_poly, d_low_degree, sub_log, d_caps, tail_log});
 }
 
 }  // extern "C"

@@ -246,10 +246,7 @@ __global__ __launch_bounds__(64) void k_cm_draw_coeff(uint32_t* __restrict__ roo
                                                       uint32_t* __restrict__ chan_out, uint8_t* __restrict__ ok_out) {
     const uint32_t p = blockIdx.x * 64 + threadIdx.x;
     if (p >= n) return;
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(chan + (size_t)p * 16);
-    ch.n_sent = chan[(size_t)p * 16 + 8];
+    Channel<0> ch = channel_load(chan + (size_t)p * 16);
     Hash8 s = load_hash(sums + (size_t)p * 8);
     ch.mix(s);
     ch.mix(load_hash(roots + (size_t)p * 24 + 16));

@@ -303,16 +303,12 @@ __global__ __launch_bounds__(64) void k_co_draw_oods(const uint32_t* __restrict_
         for (int i = 0; i < 8; i++) o[i] = 0u;
         return;
     }
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
+    Channel<0> ch = channel_load(co);
     ch.mix(load_hash(root3 + (size_t)p * 8));
     const QM31 t = q_lo(ch.draw());
     const QM31 t2 = q_mul(t, t), inv = q_inv(q_add(t2, q_one()));
     const QM31 x = q_mul(q_sub(q_one(), t2), inv), y = q_mul(q_dbl(t), inv);
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
+    channel_store(co, ch);
     o[0] = x.a.a; o[1] = x.a.b; o[2] = x.b.a; o[3] = x.b.b;
     o[4] = y.a.a; o[5] = y.a.b; o[6] = y.b.a; o[7] = y.b.b;
 }

@@ -20,6 +20,12 @@
 // Folds (bit-reversed storage, pair (2k, 2k + 1)).  Circle to line, column of log size l: (f0 + f1) + alpha (f0 - f1) / y,
 // 1 / y = entry k of layer 0 of the inverse table of 2^l.  Line, layer of log size l: (f0 + f1) + alpha (f0 - f1) / x,
 // 1 / x = entry k of layer 1 of the inverse table of 2^(l + 1).  No factor 1/2.
+//
+// Three forms of the commit phase (per layer; the same keeping the caps; the tail form) and the opening (k_fri_open.hpp) must
+// agree bit for bit, so every step has one __device__ definition here and a per-layer kernel that is index arithmetic around
+// it: fr_node (k_fr_hash_layer; fr_lds_tree, k_fo_subtree), fr_draw_one (k_fr_draw), fr_fold_pair and fr_fold_join
+// (k_fr_fold), fr_line_pair (k_fr_line_layer), fr_last_word (k_fr_last), fr_mix_last (k_fr_mix_last); k_fr_tree_top and
+// k_fr_tail are loops around the same calls.
 #pragma once
 #include "k_commit.hpp"
 #include "k_sample.hpp"
@@ -149,63 +155,100 @@ __global__ __launch_bounds__(256) void k_fr_rows(FrRows a) {
 }
 
 // ---------------------------------------------------------------- layer trees
-// hash_node of every node of one layer of P trees, one lane per node: out [P][2^l][8]; child [P][2^(l+1)][8], nullptr at
+// hash_node of one node of a layer tree, the one definition every form of the commit phase and the opening hash with.
+// col(v): whether the node's level carries a column, and then the node's QM31 of it in v — four M31 columns to the hash, as
+// k_cm_hash_layer takes a group of four.  kids(a, b): the node's children, asked for above the leaves only.  Callbacks, not
+// values: each caller's loads stay inside the branch that needs them.
+template <class Col, class Kids>
+__device__ __forceinline__ Hash8 fr_node(bool leaf, Col col, Kids kids) {
+    uint32_t v[4];
+    const bool has = col(v);
+    Hash8 d = zero8();
+    if (has) d = sponge_capacity4<1>(v[0], v[1], v[2], v[3]);
+    Hash8 h;
+    if (leaf) {
+        h = leaf_from_capacity<1>(d);
+    } else {
+        Hash8 a, b;
+        kids(a, b);
+        h = hash_tree<1>(a, b);
+        if (has) h = combine_with_column<1>(h, d);
+    }
+    return h;
+}
+
+// fr_node of every node of one layer of P trees, one lane per node: out [P][2^l][8]; child [P][2^(l+1)][8], nullptr at
 // the leaves; data (may be nullptr): the one QM31 column this layer carries, coordinate j of proof p, node i at
-// data + p * dstride + (j << l) + i — four M31 columns to the hash, as k_cm_hash_layer takes a group of four.
+// data + p * dstride + (j << l) + i.
 __global__ __launch_bounds__(256) void k_fr_hash_layer(const uint32_t* __restrict__ data, uint64_t dstride, uint32_t l, uint32_t P_,
                                                        const uint32_t* __restrict__ child, uint32_t* __restrict__ out) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= ((uint64_t)P_ << l)) return;
-    Hash8 d = zero8();
-    if (data) {
-        const uint64_t p = t >> l, i = t & (((uint64_t)1 << l) - 1);
-        const uint32_t* s = data + p * dstride + i;
-        d = sponge_capacity4<1>(s[0], s[(uint64_t)1 << l], s[(uint64_t)2 << l], s[(uint64_t)3 << l]);
-    }
-    Hash8 h;
-    if (!child) {
-        h = leaf_from_capacity<1>(d);
-    } else {
-        h = hash_tree<1>(load_hash(child + t * 16), load_hash(child + t * 16 + 8));
-        if (data) h = combine_with_column<1>(h, d);
-    }
+    const Hash8 h = fr_node(
+        !child,
+        [&](uint32_t* v) {
+            if (!data) return false;
+            const uint64_t p = t >> l, i = t & (((uint64_t)1 << l) - 1);
+            const uint32_t* s = data + p * dstride + i;
+#pragma unroll
+            for (int j = 0; j < 4; j++) v[j] = s[(uint64_t)j << l];
+            return true;
+        },
+        [&](Hash8& a, Hash8& b) {
+            a = load_hash(child + t * 16);
+            b = load_hash(child + t * 16 + 8);
+        });
     store_hash(out + t * 8, h);
 }
 
-// The channel step of one layer, one lane per proof: mix the layer's root, draw alpha.  chan [P][16] (digest, n_sent),
-// read and updated; the root to roots + p * rstride, alpha to alphas + p * astride.  A masked proof: zeros in all three.
-// low (may be nullptr): the proof's low-degree flag, set to 1 here (0 for a masked proof) before k_fr_last clears it.
+// Where the channel steps of the layers read and write, for the proofs of a pass: chan [P][16] (merkle.hpp: channel_load), read
+// and updated; a layer's root to roots + p * rstride, its alpha to alphas + p * astride.
+struct FrDraw {
+    const uint8_t* mask;
+    uint32_t* chan;
+    uint32_t* roots;  // of layer 0
+    uint64_t rstride;
+    uint32_t* alphas;
+    uint64_t astride;
+    uint8_t* low;  // the proofs' low-degree flags; layer 0's step sets them
+    // the same, with layer idx where layer 0 was
+    __host__ __device__ FrDraw layer(uint32_t idx) const { return {mask, chan, roots + idx * 8, rstride, alphas + idx * 4, astride, idx ? nullptr : low}; }
+};
+// The channel step of one layer (d: FrDraw::layer's) of proof p of the pass, by one lane: mix the layer's root (root(), asked
+// for when the proof is kept), draw alpha -> alpha.  A masked proof: zeros in the channel, the root and alpha.  Layer 0 also
+// sets the proof's low-degree flag to 1 (0 for a masked proof) before fr_last_word clears it.
+template <class Root>
+__device__ __forceinline__ QM31 fr_draw_one(const FrDraw& d, uint32_t p, bool keep, Root root) {
+    uint32_t* co = d.chan + (size_t)p * 16;
+    uint32_t* ro = d.roots + p * d.rstride;
+    uint32_t* ao = d.alphas + p * d.astride;
+    if (d.low) d.low[p] = keep ? 1 : 0;
+    if (!keep) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) co[i] = 0u;
+        store_hash(ro, zero8());
+#pragma unroll
+        for (int i = 0; i < 4; i++) ao[i] = 0u;
+        return q_zero();
+    }
+    Channel<0> ch = channel_load(co);
+    const Hash8 r = root();
+    ch.mix(r);
+    const Hash8 dr = ch.draw();
+    channel_store(co, ch);
+    store_hash(ro, r);
+#pragma unroll
+    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
+    return q_lo(dr);
+}
+
+// fr_draw_one of one layer, one lane per proof of the pass; root [P][8].
 __global__ __launch_bounds__(64) void k_fr_draw(const uint32_t* __restrict__ root, const uint8_t* __restrict__ mask, uint32_t P_,
                                                 uint32_t* __restrict__ chan, uint32_t* __restrict__ roots, uint64_t rstride,
                                                 uint32_t* __restrict__ alphas, uint64_t astride, uint8_t* __restrict__ low) {
     const uint32_t p = blockIdx.x * 64 + threadIdx.x;
     if (p >= P_) return;
-    uint32_t* co = chan + (size_t)p * 16;
-    uint32_t* ro = roots + p * rstride;
-    uint32_t* ao = alphas + p * astride;
-    const bool keep = !mask || mask[p];
-    if (low) low[p] = keep ? 1 : 0;
-    if (!keep) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) co[i] = 0u;
-#pragma unroll
-        for (int i = 0; i < 8; i++) ro[i] = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; i++) ao[i] = 0u;
-        return;
-    }
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
-    const Hash8 r = load_hash(root + (size_t)p * 8);
-    ch.mix(r);
-    const Hash8 dr = ch.draw();
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
-    store_hash(ro, r);
-#pragma unroll
-    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
+    fr_draw_one(FrDraw{mask, chan, roots, rstride, alphas, astride, low}, p, !mask || mask[p], [&] { return load_hash(root + (size_t)p * 8); });
 }
 
 // Where inner layer M - 1 - l (log size l < M) begins in a proof's d_layers, the layers M - 1, M - 2, ... one after
@@ -247,9 +290,16 @@ __device__ __forceinline__ void fr_st(uint32_t* d, uint32_t l, QM31 v) {
     d[(uint64_t)3 << l] = v.b.b;
 }
 
-// src (log size l) -> dst (log size l - 1), one lane per (proof, k): (f0 + f1) + alpha (f0 - f1) winv[k], winv the layer
-// of the inverse twiddle table that holds 1 / y (circle to line) or 1 / x (line).  JOIN: dst = alpha^2 dst + that (a
-// quotient column joining the running evaluation).  alpha: alphas + p * astride.  A masked proof gets zeros.
+// One pair of a fold: (f0 + f1) + alpha (f0 - f1) winv, winv = 1 / y of the pair (circle to line) or 1 / x (line).
+__device__ __forceinline__ QM31 fr_fold_pair(QM31 f0, QM31 f1, uint32_t winv, QM31 alpha) {
+    return q_add(q_add(f0, f1), q_mul(q_mul_m(q_sub(f0, f1), winv), alpha));
+}
+// A folded quotient column joining the running evaluation: alpha^2 run + col.
+__device__ __forceinline__ QM31 fr_fold_join(QM31 run, QM31 col, QM31 alpha) { return q_add(q_mul(q_mul(alpha, alpha), run), col); }
+
+// src (log size l) -> dst (log size l - 1), one lane per (proof, k): fr_fold_pair with winv[k], winv the layer of the inverse
+// twiddle table that holds 1 / y or 1 / x.  JOIN: dst = fr_fold_join of dst and that.  alpha: alphas + p * astride.  A masked
+// proof gets zeros.
 template <bool JOIN>
 __global__ __launch_bounds__(256) void k_fr_fold(FrVec src, FrVec dst, uint32_t l, uint32_t P_, const uint32_t* __restrict__ winv,
                                                  const uint32_t* __restrict__ alphas, uint64_t astride, const uint8_t* __restrict__ mask) {
@@ -263,46 +313,36 @@ __global__ __launch_bounds__(256) void k_fr_fold(FrVec src, FrVec dst, uint32_t 
         const QM31 f0 = fr_ld(s, l), f1 = fr_ld(s + 1, l);
         const uint32_t* ap = alphas + p * astride;
         const QM31 alpha = q_mk(ap[0], ap[1], ap[2], ap[3]);
-        v = q_add(q_add(f0, f1), q_mul(q_mul_m(q_sub(f0, f1), winv[k]), alpha));
-        if (JOIN) v = q_add(q_mul(q_mul(alpha, alpha), fr_ld(d, l - 1)), v);
+        v = fr_fold_pair(f0, f1, winv[k], alpha);
+        if (JOIN) v = fr_fold_join(fr_ld(d, l - 1), v, alpha);
     }
     fr_st(d, l - 1, v);
 }
 
 // ---------------------------------------------------------------- last layer
-// One inverse butterfly layer m of the line interpolation of P x 4 vectors of 2^L words (ev [P][4][2^L], in place), one
-// lane per pair.  The line domain of 2^L points is the x-projection of the circle domain 2^(L+1): its layer m is that
-// domain's layer m + 1, whose inverse twiddles winv holds (2^(L-1-m) entries).
-__global__ __launch_bounds__(256) void k_fr_line_layer(uint32_t* __restrict__ ev, uint32_t L, uint32_t m, uint32_t P_,
-                                                       const uint32_t* __restrict__ winv) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= ((uint64_t)P_ * 4) << (L - 1)) return;
-    const uint64_t row = t >> (L - 1);
-    const uint32_t j = (uint32_t)(t & (((uint64_t)1 << (L - 1)) - 1));
+// Pair j of inverse butterfly layer m of the line interpolation of a vector v of 2^L words, in place.  The line domain of 2^L
+// points is the x-projection of the circle domain 2^(L+1): its layer m is that domain's layer m + 1, whose inverse twiddles
+// winv holds (2^(L-1-m) entries).
+__device__ __forceinline__ void fr_line_pair(uint32_t* v, uint32_t m, uint32_t j, const uint32_t* __restrict__ winv) {
     const uint32_t a_at = ((j >> m) << (m + 1)) | (j & ((1u << m) - 1)), b_at = a_at + (1u << m);
-    uint32_t* d = ev + (row << L);
-    uint32_t a = d[a_at], b = d[b_at];
+    uint32_t a = v[a_at], b = v[b_at];
     cm_butterfly<true>(a, b, winv[a_at >> (m + 1)]);
-    d[a_at] = a;
-    d[b_at] = b;
+    v[a_at] = a;
+    v[b_at] = b;
 }
 
-// After the layers, word j of a vector times 2^-L is the coefficient of prod_m pi^m(x)^(bit m of j): natural order.  The
-// first 2^log_last of them go to last [P][2^log_last][4] in the order rsv_line_eval reads (index bit-reversed over
-// log_last bits); a non-zero one past them clears the proof's low-degree flag (k_fr_draw set it).  One lane per (proof,
-// j); zeros for a masked proof.
-__global__ __launch_bounds__(256) void k_fr_last(const uint32_t* __restrict__ ev, uint32_t L, uint32_t log_last, uint32_t P_,
-                                                 const uint8_t* __restrict__ mask, uint32_t* __restrict__ last, uint8_t* __restrict__ low) {
-    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= ((uint64_t)P_ << L)) return;
-    const uint64_t p = t >> L;
-    const uint32_t j = (uint32_t)(t & (((uint64_t)1 << L) - 1));
-    const bool keep = !mask || mask[p];
+// After the layers, word j of a vector times 2^-L is the coefficient of prod_m pi^m(x)^(bit m of j): natural order.  Word j of
+// proof p's four vectors (ev(c): vector c's), scaled, to w; zeros for a masked proof.  The first 2^log_last go to last
+// [P][2^log_last][4] in the order rsv_line_eval reads (index bit-reversed over log_last bits); a non-zero one past them
+// clears the proof's low-degree flag (fr_draw_one set it).  -> whether j is one of the first.
+template <class Ev>
+__device__ __forceinline__ bool fr_last_word(Ev ev, uint32_t L, uint32_t log_last, uint64_t p, uint32_t j, bool keep, uint32_t* __restrict__ last,
+                                             uint8_t* __restrict__ low, uint32_t* w) {
     const uint32_t scale = L ? 1u << (31 - L) : 1u;  // 2^-L mod P
-    uint32_t w[4];
 #pragma unroll
-    for (int c = 0; c < 4; c++) w[c] = keep ? m_mul(ev[((p * 4 + c) << L) + j], scale) : 0u;
-    if (j < (1u << log_last)) {
+    for (int c = 0; c < 4; c++) w[c] = keep ? m_mul(ev(c), scale) : 0u;
+    const bool first = j < (1u << log_last);
+    if (first) {
         const uint32_t i = log_last ? bit_reverse(j, log_last) : 0u;
         uint32_t* o = last + ((p << log_last) + i) * 4;
 #pragma unroll
@@ -310,36 +350,62 @@ __global__ __launch_bounds__(256) void k_fr_last(const uint32_t* __restrict__ ev
     } else if (w[0] | w[1] | w[2] | w[3]) {
         low[p] = 0;
     }
+    return first;
 }
 
-// The transcript's last step of the stage, one lane per proof: mix the last polynomial's coefficients two per mix, a
-// single one at the end of an odd count.  chan as k_fr_draw's; a masked proof keeps its zeros.
+// The transcript's last step of the stage, by one lane: mix the last polynomial's 2^log_last coefficients (coef(i, k): the
+// (i + k)-th of `last`, i even, k 0 or 1) two per mix, a single one at the end of an odd count.  co: the proof's channel.
+template <class Coef>
+__device__ __forceinline__ void fr_mix_last(uint32_t* co, uint32_t log_last, Coef coef) {
+    Channel<0> ch = channel_load(co);
+    const uint32_t n = 1u << log_last;
+#pragma unroll 1
+    for (uint32_t i = 0; i < n; i += 2) {
+        const QM31 f = coef(i, 0u);
+        if (i + 1 < n) ch.mix_two(f, coef(i, 1u));
+        else ch.mix_one(f);
+    }
+    channel_store(co, ch);
+}
+
+// fr_line_pair of layer m of P x 4 vectors of 2^L words (ev [P][4][2^L]), one lane per pair.
+__global__ __launch_bounds__(256) void k_fr_line_layer(uint32_t* __restrict__ ev, uint32_t L, uint32_t m, uint32_t P_,
+                                                       const uint32_t* __restrict__ winv) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ * 4) << (L - 1)) return;
+    const uint64_t row = t >> (L - 1);
+    fr_line_pair(ev + (row << L), m, (uint32_t)(t & (((uint64_t)1 << (L - 1)) - 1)), winv);
+}
+
+// fr_last_word, one lane per (proof, j): last [P][2^log_last][4], low [P].
+__global__ __launch_bounds__(256) void k_fr_last(const uint32_t* __restrict__ ev, uint32_t L, uint32_t log_last, uint32_t P_,
+                                                 const uint8_t* __restrict__ mask, uint32_t* __restrict__ last, uint8_t* __restrict__ low) {
+    const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= ((uint64_t)P_ << L)) return;
+    const uint64_t p = t >> L;
+    const uint32_t j = (uint32_t)(t & (((uint64_t)1 << L) - 1));
+    uint32_t w[4];
+    fr_last_word([=](int c) { return ev[((p * 4 + c) << L) + j]; }, L, log_last, p, j, !mask || mask[p], last, low, w);
+}
+
+// fr_mix_last, one lane per proof: chan [P][16]; a masked proof keeps its zeros.
 __global__ __launch_bounds__(64) void k_fr_mix_last(const uint32_t* __restrict__ last, uint32_t log_last, const uint8_t* __restrict__ mask,
                                                     uint32_t P_, uint32_t* __restrict__ chan) {
     const uint32_t p = blockIdx.x * 64 + threadIdx.x;
     if (p >= P_ || (mask && !mask[p])) return;
     uint32_t* co = chan + (size_t)p * 16;
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
-    const uint32_t n = 1u << log_last;
     const uint32_t* c = last + ((size_t)p << log_last) * 4;
-#pragma unroll 1
-    for (uint32_t i = 0; i < n; i += 2) {
-        const QM31 f = q_mk(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
-        if (i + 1 < n) ch.mix_two(f, q_mk(c[4 * i + 4], c[4 * i + 5], c[4 * i + 6], c[4 * i + 7]));
-        else ch.mix_one(f);
-    }
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
+    fr_mix_last(co, log_last, [=](uint32_t i, uint32_t k) {
+        const uint32_t at = 4 * i + 4 * k;
+        return q_mk(c[at], c[at + 1], c[at + 2], c[at + 3]);
+    });
 }
 
 // ---------------------------------------------------------------- the tail form (rsv_fri_commit_tail_dev, tail_log = t)
 // One workgroup of 256 lanes per proof finishes what the per-layer form spends a launch per level on: k_fr_tree_top the
 // levels t .. 0 of a layer tree and the channel step on its root, k_fr_tail every inner layer of log size <= t and the last
-// layer.  The node function is k_fr_hash_layer's, the channel step k_fr_draw's, the folds k_fr_fold's, the last layer
-// k_fr_line_layer's, k_fr_last's and k_fr_mix_last's: every output is the per-layer form's bit for bit.
+// layer.  Both are loops around the per-layer kernels' own steps — fr_node, fr_draw_one, fr_fold_pair and fr_fold_join,
+// fr_line_pair, fr_last_word, fr_mix_last — so every output is the per-layer form's bit for bit.
 //
 // LDS, word-major as k_fo_subtree's: two node levels ping-ponged, level l in the first 2^T entries when first - l is even
 // and in the 2^(T-1) after them when it is odd (48 << T bytes); k_fr_tail also keeps the running evaluation, 4 x 2^T words
@@ -355,16 +421,6 @@ struct FrCapOut {
     uint32_t tree, c;
     uint64_t p0;
 };
-// What k_fr_draw takes, for the proofs of the pass.
-struct FrDraw {
-    const uint8_t* mask;
-    uint32_t* chan;
-    uint32_t* roots;
-    uint64_t rstride;
-    uint32_t* alphas;
-    uint64_t astride;
-    uint8_t* low;  // tree 0 only
-};
 // The quotient columns of log size <= FR_TAIL_LOG: bit l of dmask: one of log size l, coordinate j of proof p, value i at
 // quot + p * qstride + at[l] + (j << l) + i.
 struct FrSmallCols {
@@ -374,43 +430,42 @@ struct FrSmallCols {
     uint32_t dmask;
 };
 
+// Level l of fr_lds_tree to node[][out ..] and to `kept`, a lane per node; kids(i, a, b): the children of node i.
+template <class Data, class Kids>
+__device__ __forceinline__ void fr_lds_level(uint32_t (*node)[FR_TAIL_NODES], uint32_t l, bool leaf, uint32_t out, uint32_t* kept, const Data& data,
+                                             Kids kids) {
+#pragma unroll 1
+    for (uint32_t i = threadIdx.x; i < (1u << l); i += 256) {
+        const Hash8 h = fr_node(leaf, [&](uint32_t* v) { return data(l, i, v); }, [&](Hash8& a, Hash8& b) { kids(i, a, b); });
+#pragma unroll
+        for (int w = 0; w < 8; w++) node[w][out + i] = h.w[w];
+        if (kept) store_hash(kept + (uint64_t)i * 8, h);
+    }
+}
+
 // Levels first .. 0 of one tree of leaves at `top` >= first, a lane per node.  Level first's children are child [2^(first +
 // 1)][8] (top > first) or none (the leaves); data(l, i, v): whether level l carries a column, and node i's four words of it.
 // cap(l): where level l is kept, or nullptr.  -> the root, in every lane.  Ends behind a barrier.
 template <class Data, class Cap>
 __device__ Hash8 fr_lds_tree(uint32_t (*node)[FR_TAIL_NODES], uint32_t top, uint32_t first, const uint32_t* __restrict__ child, Data data, Cap cap) {
-    const uint32_t tid = threadIdx.x;
 #pragma unroll 1
     for (uint32_t l = first + 1; l-- > 0;) {
         const uint32_t out = (first - l) & 1 ? 1u << FR_TAIL_LOG : 0u, in = out ? 0u : 1u << FR_TAIL_LOG;
-        uint32_t* kept = cap(l);
-#pragma unroll 1
-        for (uint32_t i = tid; i < (1u << l); i += 256) {
-            uint32_t v[4];
-            const bool has = data(l, i, v);
-            Hash8 d = zero8();
-            if (has) d = sponge_capacity4<1>(v[0], v[1], v[2], v[3]);
-            Hash8 h;
-            if (l == top) {
-                h = leaf_from_capacity<1>(d);
-            } else {
-                Hash8 a, b;
-                if (l == first) {
-                    a = load_hash(child + (uint64_t)i * 16);
-                    b = load_hash(child + (uint64_t)i * 16 + 8);
-                } else {
+        // one level loop per source of the children: one callback that branches between the global and the LDS loads compiles
+        // to flat loads as a struct and takes the compiler down (a segmentation fault in simplifycfg) as a lambda nested here
+        if (l == first && l < top) {
+            fr_lds_level(node, l, false, out, cap(l), data, [&](uint32_t i, Hash8& a, Hash8& b) {
+                a = load_hash(child + (uint64_t)i * 16);
+                b = load_hash(child + (uint64_t)i * 16 + 8);
+            });
+        } else {
+            fr_lds_level(node, l, l == top, out, cap(l), data, [&](uint32_t i, Hash8& a, Hash8& b) {
 #pragma unroll
-                    for (int w = 0; w < 8; w++) {
-                        a.w[w] = node[w][in + 2 * i];
-                        b.w[w] = node[w][in + 2 * i + 1];
-                    }
+                for (int w = 0; w < 8; w++) {
+                    a.w[w] = node[w][in + 2 * i];
+                    b.w[w] = node[w][in + 2 * i + 1];
                 }
-                h = hash_tree<1>(a, b);
-                if (has) h = combine_with_column<1>(h, d);
-            }
-#pragma unroll
-            for (int w = 0; w < 8; w++) node[w][out + i] = h.w[w];
-            if (kept) store_hash(kept + (uint64_t)i * 8, h);
+            });
         }
         __syncthreads();
     }
@@ -419,34 +474,6 @@ __device__ Hash8 fr_lds_tree(uint32_t (*node)[FR_TAIL_NODES], uint32_t top, uint
 #pragma unroll
     for (int w = 0; w < 8; w++) r.w[w] = node[w][at];
     return r;
-}
-
-// k_fr_draw's step for proof p of the pass and layer idx, by the one lane that calls it -> alpha (zero for a masked proof).
-__device__ inline QM31 fr_draw_one(const FrDraw& d, uint32_t p, uint32_t idx, bool keep, const Hash8& r) {
-    uint32_t* co = d.chan + (size_t)p * 16;
-    uint32_t* ro = d.roots + p * d.rstride + idx * 8;
-    uint32_t* ao = d.alphas + p * d.astride + idx * 4;
-    if (d.low && idx == 0) d.low[p] = keep ? 1 : 0;
-    if (!keep) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) co[i] = 0u;
-        store_hash(ro, zero8());
-#pragma unroll
-        for (int i = 0; i < 4; i++) ao[i] = 0u;
-        return q_zero();
-    }
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
-    ch.mix(r);
-    const Hash8 dr = ch.draw();
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
-    store_hash(ro, r);
-#pragma unroll
-    for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
-    return q_lo(dr);
 }
 
 __device__ __forceinline__ uint32_t* fr_cap_level(const FrCapOut& k, uint32_t tree, uint32_t c, uint32_t l, uint32_t p) {
@@ -470,7 +497,7 @@ __global__ __launch_bounds__(256) void k_fr_tree_top(uint32_t top, uint32_t firs
             return true;
         },
         [&](uint32_t l) { return fr_cap_level(cap, cap.tree, cap.c, l, p); });
-    if (threadIdx.x == 0) fr_draw_one(draw, p, idx, !draw.mask || draw.mask[p], r);
+    if (threadIdx.x == 0) fr_draw_one(draw.layer(idx), p, !draw.mask || draw.mask[p], [&] { return r; });
 }
 
 // The tail of every proof of the pass: the inner layers of log size l0 .. L + 1 (idx M - l each) and the last layer.
@@ -493,6 +520,7 @@ __global__ __launch_bounds__(256) void k_fr_tail(FrTail a, FrCapOut cap, FrDraw 
     __shared__ uint32_t s_alpha[4];
     const uint32_t p = blockIdx.x, tid = threadIdx.x;
     const bool keep = !draw.mask || draw.mask[p];
+    const auto ev_at = [&](uint32_t i) { return q_mk(ev[0][i], ev[1][i], ev[2][i], ev[3][i]); };
     {
         const uint32_t* s = a.in + p * a.istride;
         for (uint32_t g = tid; g < (4u << a.l0); g += 256) ev[g >> a.l0][g & ((1u << a.l0) - 1)] = s[g];
@@ -511,7 +539,7 @@ __global__ __launch_bounds__(256) void k_fr_tail(FrTail a, FrCapOut cap, FrDraw 
             },
             [&](uint32_t lv) { return fr_cap_level(cap, idx, fo_cap_layers(l, cap.at.h), lv, p); });
         if (tid == 0) {
-            const QM31 al = fr_draw_one(draw, p, idx, keep, r);
+            const QM31 al = fr_draw_one(draw.layer(idx), p, keep, [&] { return r; });
             s_alpha[0] = al.a.a; s_alpha[1] = al.a.b; s_alpha[2] = al.b.a; s_alpha[3] = al.b.b;
         }
         __syncthreads();
@@ -524,14 +552,10 @@ __global__ __launch_bounds__(256) void k_fr_tail(FrTail a, FrCapOut cap, FrDraw 
             const uint32_t k = tid + rr * 256;
             v[rr] = q_zero();
             if (k < half && keep) {
-                const QM31 f0 = q_mk(ev[0][2 * k], ev[1][2 * k], ev[2][2 * k], ev[3][2 * k]);
-                const QM31 f1 = q_mk(ev[0][2 * k + 1], ev[1][2 * k + 1], ev[2][2 * k + 1], ev[3][2 * k + 1]);
-                v[rr] = q_add(q_add(f0, f1), q_mul(q_mul_m(q_sub(f0, f1), a.inv_x[l][k]), alpha));
+                v[rr] = fr_fold_pair(ev_at(2 * k), ev_at(2 * k + 1), a.inv_x[l][k], alpha);
                 if (join) {
                     const uint32_t* s = a.cols.quot + p * a.cols.qstride + a.cols.at[l] + 2 * k;
-                    const QM31 g0 = fr_ld(s, l), g1 = fr_ld(s + 1, l);
-                    const QM31 c = q_add(q_add(g0, g1), q_mul(q_mul_m(q_sub(g0, g1), a.inv_y[l][k]), alpha));
-                    v[rr] = q_add(q_mul(q_mul(alpha, alpha), v[rr]), c);
+                    v[rr] = fr_fold_join(v[rr], fr_fold_pair(fr_ld(s, l), fr_ld(s + 1, l), a.inv_y[l][k], alpha), alpha);
                 }
             }
         }
@@ -548,58 +572,24 @@ __global__ __launch_bounds__(256) void k_fr_tail(FrTail a, FrCapOut cap, FrDraw 
         }
         __syncthreads();
     }
-    // the last layer: k_fr_line_layer's butterflies, k_fr_last, k_fr_mix_last
+    // the last layer; the coefficients stay in ev, in natural order, for the mixes
     const uint32_t L = a.L;
 #pragma unroll 1
     for (uint32_t m = 0; m < L; m++) {
         const uint32_t* winv = a.inv_x[L] + cm_tw_off(L + 1, m + 1);
-        for (uint32_t g = tid; g < (4u << (L - 1)); g += 256) {
-            const uint32_t row = g >> (L - 1), j = g & ((1u << (L - 1)) - 1);
-            const uint32_t a_at = ((j >> m) << (m + 1)) | (j & ((1u << m) - 1)), b_at = a_at + (1u << m);
-            uint32_t x = ev[row][a_at], y = ev[row][b_at];
-            cm_butterfly<true>(x, y, winv[a_at >> (m + 1)]);
-            ev[row][a_at] = x;
-            ev[row][b_at] = y;
-        }
+        for (uint32_t g = tid; g < (4u << (L - 1)); g += 256) fr_line_pair(ev[g >> (L - 1)], m, g & ((1u << (L - 1)) - 1), winv);
         __syncthreads();
     }
-    const uint32_t scale = L ? 1u << (31 - L) : 1u;  // 2^-L mod P
-    uint32_t* last = a.last_poly + (((uint64_t)p << a.log_last) * 4);
     for (uint32_t j = tid; j < (1u << L); j += 256) {
         uint32_t w[4];
+        if (fr_last_word([&](int c) { return ev[c][j]; }, L, a.log_last, p, j, keep, a.last_poly, draw.low, w)) {
 #pragma unroll
-        for (int c = 0; c < 4; c++) w[c] = keep ? m_mul(ev[c][j], scale) : 0u;
-        if (j < (1u << a.log_last)) {
-            const uint32_t i = a.log_last ? bit_reverse(j, a.log_last) : 0u;
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                last[i * 4 + c] = w[c];
-                ev[c][j] = w[c];
-            }
-        } else if (w[0] | w[1] | w[2] | w[3]) {
-            draw.low[p] = 0;
+            for (int c = 0; c < 4; c++) ev[c][j] = w[c];
         }
     }
     __syncthreads();
-    if (tid == 0 && keep) {
-        uint32_t* co = draw.chan + (size_t)p * 16;
-        Channel<0> ch;
-        ch.init();
-        ch.digest = load_hash(co);
-        ch.n_sent = co[8];
-        const uint32_t n = 1u << a.log_last;
-        auto coef = [&](uint32_t i) {
-            const uint32_t j = a.log_last ? bit_reverse(i, a.log_last) : 0u;
-            return q_mk(ev[0][j], ev[1][j], ev[2][j], ev[3][j]);
-        };
-#pragma unroll 1
-        for (uint32_t i = 0; i < n; i += 2) {
-            if (i + 1 < n) ch.mix_two(coef(i), coef(i + 1));
-            else ch.mix_one(coef(i));
-        }
-        store_hash(co, ch.digest);
-        co[8] = ch.n_sent;
-    }
+    if (tid == 0 && keep)
+        fr_mix_last(draw.chan + (size_t)p * 16, a.log_last, [&](uint32_t i, uint32_t k) { return ev_at(a.log_last ? bit_reverse(i + k, a.log_last) : 0u); });
 }
 
 // ---------------------------------------------------------------- the recursion circuit's chain (rsv_witness_fri_dev)
@@ -624,18 +614,14 @@ __global__ __launch_bounds__(64) void k_fr_begin(const uint32_t* __restrict__ sa
         for (int i = 0; i < 24; i++) po[i] = 0u;
         return;
     }
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
+    Channel<0> ch = channel_load(co);
 #pragma unroll 1
     for (uint32_t i = 0; i < 142; i += 2) {
         const uint32_t* s = i < 134 ? samples + ((size_t)p * 134 + i) * 4 : samples3 + ((size_t)p * 8 + (i - 134)) * 4;
         ch.mix(load_hash(s));
     }
     const Hash8 dr = ch.draw();
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
+    channel_store(co, ch);
 #pragma unroll
     for (int i = 0; i < 4; i++) ao[i] = dr.w[i];
     const QM31 x = sp_load_q(oods + (size_t)p * 8), y = sp_load_q(oods + (size_t)p * 8 + 4);

@@ -302,8 +302,8 @@ __global__ __launch_bounds__(128) void k_fo_sublist(FoPlan pl, uint32_t h, FoSub
     if (tid == 0) sb.cnt[pt] = m;
 }
 
-// One workgroup of 256 lanes per (proof, tree, listed subtree): k_fr_hash_layer's levels top .. c + 1 of the subtree under
-// node `id` of layer c, a lane per node, every level kept in LDS (word-major, level c + e at entries 2^e + j; the subtree's
+// One workgroup of 256 lanes per (proof, tree, listed subtree): fr_node (k_fri.hpp) of the levels top .. c + 1 of the subtree
+// under node `id` of layer c, a lane per node, every level kept in LDS (word-major, level c + e at entries 2^e + j; the subtree's
 // own root is a node of the cap, or the tree's root, and is not hashed); then the planned nodes that lie in this subtree
 // to their slots of d_hash_witness, a lane per word.  out: d_hash_witness of proof 0.
 __global__ __launch_bounds__(256) void k_fo_subtree(FoData d, FoPlan pl, uint32_t h, FoSubs sb, uint32_t* __restrict__ out) {
@@ -320,25 +320,23 @@ __global__ __launch_bounds__(256) void k_fo_subtree(FoData d, FoPlan pl, uint32_
     for (uint32_t e = sl; e >= 1; e--) {
         const uint32_t l = c + e;
         if (tid < (1u << e)) {
-            const uint32_t* s = nullptr;
-            if (t == 0 ? pl.dmask >> l & 1u : l == top)
-                s = (t ? d.layers + p * d.lstride + fr_layer_off(pl.M, l) : d.quot + p * d.qstride + d.col_at[l]) + (((uint64_t)id << e) + tid);
-            Hash8 dc = zero8();
-            if (s) dc = sponge_capacity4<1>(s[0], s[(uint64_t)1 << l], s[(uint64_t)2 << l], s[(uint64_t)3 << l]);
-            Hash8 v;
-            if (e == sl) {
-                v = leaf_from_capacity<1>(dc);
-            } else {
-                const uint32_t at = (2u << e) + 2 * tid;
-                Hash8 a, b;
+            const Hash8 v = fr_node(
+                e == sl,
+                [&](uint32_t* x) {
+                    if (!(t == 0 ? pl.dmask >> l & 1u : l == top)) return false;
+                    const uint32_t* s = (t ? d.layers + p * d.lstride + fr_layer_off(pl.M, l) : d.quot + p * d.qstride + d.col_at[l]) + (((uint64_t)id << e) + tid);
 #pragma unroll
-                for (int w = 0; w < 8; w++) {
-                    a.w[w] = node[w][at];
-                    b.w[w] = node[w][at + 1];
-                }
-                v = hash_tree<1>(a, b);
-                if (s) v = combine_with_column<1>(v, dc);
-            }
+                    for (int j = 0; j < 4; j++) x[j] = s[(uint64_t)j << l];
+                    return true;
+                },
+                [&](Hash8& a, Hash8& b) {
+                    const uint32_t at = (2u << e) + 2 * tid;
+#pragma unroll
+                    for (int w = 0; w < 8; w++) {
+                        a.w[w] = node[w][at];
+                        b.w[w] = node[w][at + 1];
+                    }
+                });
 #pragma unroll
             for (int w = 0; w < 8; w++) node[w][(1u << e) + tid] = v.w[w];
         }

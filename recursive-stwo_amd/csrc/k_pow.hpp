@@ -84,8 +84,7 @@ __global__ __launch_bounds__(64) void k_pow_finish(const unsigned long long* __r
     ch.init();
     ch.digest = load_hash(co);
     ch.mix(pow_rate(found));
-    store_hash(co, ch.digest);
-    co[8] = ch.n_sent;
+    channel_store(co, ch);
     nonce[2 * (size_t)p] = (uint32_t)found;
     nonce[2 * (size_t)p + 1] = (uint32_t)(found >> 32);
 }
@@ -111,10 +110,7 @@ __global__ __launch_bounds__(64) void k_pow_queries(const uint8_t* __restrict__ 
         }
         return;
     }
-    Channel<0> ch;
-    ch.init();
-    ch.digest = load_hash(co);
-    ch.n_sent = co[8];
+    Channel<0> ch = channel_load(co);
     const uint32_t cut = (1u << log_size) - 1u, down = log_size - log_low;
 #pragma unroll 1
     for (uint32_t got = 0; got < nq; got += 8) {

@@ -202,4 +202,17 @@ __device__ __forceinline__ void store_hash(uint32_t* p, const Hash8& h) {
     for (int i = 0; i < 8; i++) p[i] = h.w[i];
 }
 
+// A channel between two kernels of the chain is a record of 16 words: digest [8], n_sent, 7 zero words.  Flow records off.
+__device__ __forceinline__ Channel<0> channel_load(const uint32_t* rec) {
+    Channel<0> ch;
+    ch.init();
+    ch.digest = load_hash(rec);
+    ch.n_sent = rec[8];
+    return ch;
+}
+__device__ __forceinline__ void channel_store(uint32_t* rec, const Channel<0>& ch) {
+    store_hash(rec, ch.digest);
+    rec[8] = ch.n_sent;
+}
+
 }  // namespace rsv
