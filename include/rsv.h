@@ -510,7 +510,9 @@ int rsv_transcript_batch(const uint8_t* blob, const uint64_t* offsets, size_t n,
  * that writes down what it did) and the resulting PROGRAM — one instruction per variable, sorted by dependency depth — is evaluated
  * on the GPU for a whole batch, from the hints of the verifying pass (proof words, PoseidonFlow records, per-query
  * column values).  The circuit is `copies` copies of the verifier in one constraint system, as
- * examples/multi-proofs/src/main.rs:66-139 builds it (`multipliers`); every copy verifies the same proof.
+ * examples/multi-proofs/src/main.rs:66-139 builds it (`multipliers`).  Under rsv_witness_eval_dev every copy verifies the
+ * same proof, as in that example; under rsv_witness_eval_groups_dev copy c verifies the c-th proof of a group of `copies`
+ * proofs of one shape (aggregation).
  *
  * Instruction = 8 u32: op, dst, a, b, imm0..imm3 (ops: recursive-stwo_amd/csrc/k_witness.hpp WitnessOp; the table with
  * their meaning heads recursive-stwo_amd/witness_program.py).  rsv_witness_program_create checks every index the device
@@ -539,7 +541,10 @@ void rsv_witness_program_destroy(rsv_witness_program* prog);
  * columns) passes the walks that list was made with.  A PROVER INTEGRATION MUST DO SO: the library cannot observe which of
  * the four orders a given run of the reference took (the tests recover them per fixture pair by trying the four against the
  * next fixture's sampled values, tests/pin_recursion_circuit.py); with the wrong walks every value is still right but two
- * pairs of blocks of `variables` sit in the other order than the prover's wires expect. */
+ * pairs of blocks of `variables` sit in the other order than the prover's wires expect.
+ * The builder also records which copy allocated every variable (one byte each, kept with the program for
+ * rsv_witness_eval_groups_dev) and checks that every hint lies in the contiguous range of its own copy: RSV_E_RANGE
+ * otherwise (a fault of the library's mirror of the gadgets, never of the template). */
 int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
                               uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out);
 /* Sizes, then the arrays (any pointer may be NULL): instr [n_vars][8], level_offsets [n_levels + 1], flow_wires
@@ -565,8 +570,8 @@ int rsv_witness_scratch_bytes(const rsv_witness_program* prog, size_t n, size_t*
  * unspecified).  d_variables 16-byte aligned.
  * d_flow [n][flow_count][32] + d_flow_swap [n][flow_count] (optional, both or neither; as rsv_hints_out::d_flow with
  * flow_stride = the shape's flow_count): the PoseidonFlow of ONE copy of the verifier — the other thing the next prover
- * needs; every copy invokes the same permutations, the wire indices of invocation k of copy c are the host's
- * (rsv_witness_program_export, flow_wires).  Without them the records live in the context's scratch only. */
+ * needs; every copy verifies the same proof here and so invokes the same permutations, the wire indices of invocation k
+ * of copy c are the host's (rsv_witness_program_export, flow_wires).  Without them the records live in the context's scratch only. */
 int rsv_witness_eval_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
                          uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason);
@@ -574,6 +579,22 @@ int rsv_witness_eval_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const ui
 int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                      const rsv_public_input* pi, size_t n_pi, uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept,
                      uint8_t* reason, int device);
+/* AGGREGATION: the batch holds n_groups * copies proofs, group g = proofs [g * copies, (g + 1) * copies) of the blob, and
+ * copy c of group g's circuit verifies proof g * copies + c.  As rsv_witness_eval_dev (the same configuration check, the
+ * same alignment) with one `variables` vector per GROUP:
+ *   d_variables [n_groups][n_vars][4] ([n_vars][n_groups][4] under RSV_OPT_WITNESS_LAYOUT = 2);
+ *   d_flow [n_groups][copies][flow_count][32] + d_flow_swap [n_groups][copies][flow_count] (optional, both or neither): the
+ *     PoseidonFlow of every member, one proof after the other;
+ *   d_accept [n_groups]: 1 iff every member verified and is of the program's shape; only those rows are defined;
+ *   d_member_accept, d_member_reason [n_groups * copies]: the members' own verdicts (the reason may be NULL).
+ * Built programs only (RSV_E_SIZE otherwise: only the builder knows which copy a hint belongs to); n_groups * copies <= 2^20.
+ * With copies == 1 this writes exactly what rsv_witness_eval_dev writes.  rsv_witness_group_scratch_bytes: the HBM the
+ * context will hold for n_groups groups (the hints of n_groups * copies proofs + variables[var][group]). */
+int rsv_witness_eval_groups_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets,
+                                size_t n_groups, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables,
+                                uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept,
+                                uint8_t* d_member_reason);
+int rsv_witness_group_scratch_bytes(const rsv_witness_program* prog, size_t n_groups, size_t* bytes);
 
 /* ---- the columns the next prover commits: 22 Plonk + 88 Poseidon ----------------------------------------------------
  * generate_plonk_with_poseidon_circuit (constraint_system/src/plonk_with_poseidon.rs:522-629) turns the circuit into the
@@ -617,6 +638,13 @@ int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t*
 int rsv_witness_trace_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
                           const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
                           uint32_t* d_ops);
+/* The same from what rsv_witness_eval_groups_dev wrote, one set of columns per GROUP: d_variables and d_accept of n_groups
+ * groups, d_flow [n_groups][copies][flow_count][32] and d_flow_swap [n_groups][copies][flow_count].  Invocation k of copy c
+ * hashes flow record k - c * flow_count of the group's proof c.  Outputs, refusals and alignment as rsv_witness_trace_dev
+ * with n = n_groups; n_groups * copies <= 2^20.  Every later stage of the chain takes these columns as they are. */
+int rsv_witness_trace_groups_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                                 const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n_groups, uint32_t* d_plonk,
+                                 uint32_t* d_poseidon, uint32_t* d_ops);
 /* rsv_witness_eval + rsv_witness_trace_dev on host buffers (plonk, poseidon, ops may each be NULL). */
 int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                       const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,

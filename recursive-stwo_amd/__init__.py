@@ -231,6 +231,10 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_eval_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, vp, vp, vp, vp]),
         "rsv_witness_eval": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u8p,
                                             _u8p, _u8p, ctypes.c_int]),
+        "rsv_witness_eval_groups_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, vp, vp, vp, vp,
+                                                       vp]),
+        "rsv_witness_group_scratch_bytes": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+        "rsv_witness_trace_groups_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rsv_trace_log_sizes": (ctypes.c_int, [sz, sz, _u32p, _u32p]),
         "rsv_trace_preprocessed": (ctypes.c_int, [_u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p]),
         "rsv_witness_trace_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
@@ -316,7 +320,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_line_eval", "rsv_oods_eval", "rsv_last_layer_check",
            "rsv_transcript_batch", "rsv_poseidon_flow_count", "rsv_witness_program_create", "rsv_witness_program_destroy",
            "rsv_witness_program_build", "rsv_witness_program_info", "rsv_witness_program_export", "rsv_witness_program_gates",
-           "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
+           "rsv_witness_scratch_bytes", "rsv_witness_eval_dev", "rsv_witness_eval", "rsv_witness_eval_groups_dev",
+           "rsv_witness_group_scratch_bytes", "rsv_witness_trace_groups_dev", "rsv_trace_log_sizes", "rsv_trace_preprocessed",
            "rsv_witness_trace_dev", "rsv_witness_trace", "rsv_witness_interaction_dev", "rsv_witness_interaction",
            "rsv_commit_tree_dev", "rsv_witness_commit_dev", "rsv_witness_commit",
            "rsv_commit_tree_cap_dev", "rsv_witness_commit_caps_dev", "rsv_decommit_sizes", "rsv_decommit_tree_dev", "rsv_witness_decommit_dev",
@@ -743,6 +748,11 @@ class WitnessProgram:
         _check(lib.rsv_witness_scratch_bytes(self._h, n, ctypes.byref(out)), "rsv_witness_scratch_bytes")
         return int(out.value)
 
+    def group_scratch_bytes(self, n_groups: int) -> int:
+        out = ctypes.c_size_t(0)
+        _check(lib.rsv_witness_group_scratch_bytes(self._h, n_groups, ctypes.byref(out)), "rsv_witness_group_scratch_bytes")
+        return int(out.value)
+
 
 def _witness_batch(proofs: Sequence[bytes], program: WitnessProgram, inputs):
     """What the rsv_witness_* host forms share: their leading arguments (program, blob, offsets, n, cfg, pi, n_pi), n, and
@@ -1157,6 +1167,30 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_witness_trace_dev(self._h, program._h, ptr(d_variables), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(), n,
                                          ptr(d_plonk), ptr(d_poseidon), ptr(d_ops)), "rsv_witness_trace_dev")
+
+    def witness_groups(self, program: WitnessProgram, d_blob, d_offsets, n_groups: int, d_variables, d_accept, d_member_accept,
+                       d_member_reason=None, inputs=STANDARD_INPUTS, d_flow=None, d_flow_swap=None):
+        """rsv_witness_eval_groups_dev: the batch holds n_groups * copies proofs, copy c of group g's circuit verifies proof
+        g * copies + c.  d_variables uint32[n_groups, n_vars, 4], d_accept uint8[n_groups], d_member_accept (and
+        d_member_reason) uint8[n_groups * copies]; optionally d_flow uint32[n_groups, copies, flow_count, 32] and d_flow_swap
+        uint8[n_groups, copies, flow_count]; enqueued on the context's streams."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        pi = make_inputs(inputs)
+        pc = self.prepare_cfg(program.cfg(), n_groups * program.shape.copies)
+        self.acquire_from_torch()
+        self._keep(pc, None)
+        _check(lib.rsv_witness_eval_groups_dev(self._h, program._h, d_blob.data_ptr(), d_offsets.data_ptr(), n_groups, pc.ref(), pi,
+                                               len(list(inputs)), d_variables.data_ptr(), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(),
+                                               ptr(d_member_accept), ptr(d_member_reason)), "rsv_witness_eval_groups_dev")
+
+    def witness_trace_groups(self, program: WitnessProgram, d_variables, d_accept, n_groups: int, d_plonk=None, d_poseidon=None, d_ops=None,
+                             d_flow=None, d_flow_swap=None):
+        """rsv_witness_trace_groups_dev on what Context.witness_groups wrote: one set of columns per group, shapes as
+        witness_trace's with n = n_groups; enqueued on the context's stream."""
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self.acquire_from_torch()
+        _check(lib.rsv_witness_trace_groups_dev(self._h, program._h, ptr(d_variables), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(),
+                                                n_groups, ptr(d_plonk), ptr(d_poseidon), ptr(d_ops)), "rsv_witness_trace_groups_dev")
 
     def witness_interaction(self, program: WitnessProgram, d_plonk, d_poseidon, d_accept, d_lookup, n: int, d_int_plonk, d_int_poseidon, d_sums,
                             d_ok=None):

@@ -13,8 +13,8 @@ import numpy as np
 from . import (CAP_NONE, CAP_READ, ProofParts, composition_log_size, decommit_sizes, fri_cap_sizes, fri_open_sizes, fri_sizes, pack,
                proof_bytes_bound, proof_list, witness_decommit_sizes)
 
-_FLAGS = ("acc", "ok", "low_degree")
-_WRITTEN = ("acc", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
+_FLAGS = ("acc", "ok", "low_degree", "member_accept", "member_reason")
+_WRITTEN = ("acc", "member_accept", "member_reason", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
             "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree", "fri_caps",
             "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3",
             "fri_witness", "n_fri_witness", "fri_hash_witness", "n_fri_hash_witness")
@@ -74,10 +74,14 @@ class Chain:
     a word a stage leaves unwritten shows.  caps=True also keeps the caps of trees 0-2 (commit) and of tree 3 (tree3);
     fri_sub_log = h (1 .. 8) also keeps the caps of the FRI layer trees (fri), from which fri_open() then rebuilds subtrees
     of at most 2^h leaves only; fri_tail_log = t (1 .. 10) runs fri()'s commit phase in the tail form (the same outputs through
-    fewer launches)."""
+    fewer launches).  aggregate=True: n is the number of GROUPS of program.shape.copies proofs; copy c of group g's circuit
+    verifies proof g * copies + c of the batch witness() takes, every tensor and the next proof are per group, and
+    member_accept, member_reason [n, copies] hold the members' own verdicts."""
 
-    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, fri_tail_log=0, device="cuda:0"):
+    def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, fri_tail_log=0, device="cuda:0",
+                 aggregate=False):
         self.ctx, self.program, self.n, self.log_blowup, self.log_last = ctx, program, n, log_blowup, log_last
+        self.aggregate = aggregate
         self.fill, self.with_caps, self.fri_sub_log, self.fri_tail_log, self.device = fill, caps, fri_sub_log, fri_tail_log, device
         self.lp, self.lq = program.trace_sizes()
         self.n_ops = len(program.gates()[1])
@@ -102,7 +106,7 @@ class Chain:
     def witness(self, proofs_or_blob, inputs, by_variable=False):
         """Context.witness on proofs (a list of bytes) or a packed (blob, offsets): numpy arrays, or device tensors (uint8
         and int64[n + 1], what pack() returns), which are used as they are; by_variable: the context's witness_layout
-        option is "by_variable"."""
+        option is "by_variable".  With aggregate: n * copies proofs, group after group."""
         import torch
         blob, offsets = pack(proofs_or_blob) if isinstance(proofs_or_blob, list) else proofs_or_blob
         n, wp = self.n, self.program
@@ -112,9 +116,16 @@ class Chain:
             self._blob = (torch.from_numpy(blob.copy()).to(self.device), torch.from_numpy(offsets.astype(np.int64)).to(self.device))
         F = wp.shape.flow_count
         self._vars = self._new(*((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4)), fill=0)
-        self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
         self.acc = self._new(n, flag=True, fill=0)
-        self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
+        if self.aggregate:
+            m = wp.shape.copies
+            self._flow, self._swap = self._new(n, m, F, 32, fill=0), self._new(n, m, F, flag=True, fill=0)
+            self.member_accept, self.member_reason = self._new(n, m, flag=True, fill=0), self._new(n, m, flag=True, fill=0)
+            self.ctx.witness_groups(wp, *self._blob, n, self._vars, self.acc, self.member_accept, self.member_reason, inputs=inputs,
+                                    d_flow=self._flow, d_flow_swap=self._swap)
+        else:
+            self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
+            self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
         self.done = {"witness"}
 
     def trace(self, plonk=True, poseidon=True, ops=True):
@@ -125,8 +136,9 @@ class Chain:
         self.plonk = self._new(n, 12, 1 << self.lp) if plonk else None
         self.poseidon = self._new(n, 48, 1 << self.lq) if poseidon else None
         self.ops = self._new(n, max(self.n_ops, 1)) if ops else None
-        self.ctx.witness_trace(self.program, self._vars, self.acc, n, d_plonk=self.plonk, d_poseidon=self.poseidon, d_ops=self.ops,
-                               d_flow=self._flow, d_flow_swap=self._swap)
+        trace = self.ctx.witness_trace_groups if self.aggregate else self.ctx.witness_trace
+        trace(self.program, self._vars, self.acc, n, d_plonk=self.plonk, d_poseidon=self.poseidon, d_ops=self.ops, d_flow=self._flow,
+              d_flow_swap=self._swap)
         self.ctx.release_to_torch()
         self._blob = self._vars = self._flow = self._swap = None
         self.done = {"trace"}

@@ -52,6 +52,7 @@ int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_co
     prog->flow_wires = std::move(bp.flow_wires);
     prog->gates = std::move(bp.gates);
     prog->witness_ops = std::move(bp.witness_ops);
+    prog->copy_of = std::move(bp.copy_of);
     *out = prog;
     return RSV_OK;
 }

@@ -74,6 +74,8 @@ struct WitnessOp3 { uint32_t row, bit, constant; };  // a row whose `op` follows
 struct ConstraintSystem {
     std::vector<Q4> variables;
     std::vector<Instr> origin;
+    std::vector<uint8_t> copy_of;      // per variable: the copy of the verifier whose gadgets allocated it (begin_copy)
+    std::vector<uint32_t> copy_marks;  // variables.size() at the start of every copy: copy c allocates [marks[c], marks[c + 1])
     std::vector<FlowRecord> flow;
     std::vector<GateRow> rows;
     std::vector<WitnessOp3> witness_ops;
@@ -87,14 +89,18 @@ struct ConstraintSystem {
             Instr in = mk_instr(W_CONST, 0, 0, variables[k][0], variables[k][1], variables[k][2], variables[k][3]);
             in.dst = k;
             origin.push_back(in);
+            copy_of.push_back(0);
             rows.push_back(GateRow{k, 0, k, 1, 0, 0});
         }
     }
+    // the gadgets of the next copy of the verifier start here (at most 256 copies: copy_of is a byte)
+    void begin_copy() { copy_marks.push_back((uint32_t)variables.size()); }
     void row(uint32_t a, uint32_t b, uint32_t c, uint32_t op, uint32_t pw = 0, uint32_t m31 = 0) { rows.push_back(GateRow{a, b, c, op, pw, m31}); }
     uint32_t push(const Q4& v, Instr in) {
         in.dst = (uint32_t)variables.size();
         variables.push_back(v);
         origin.push_back(in);
+        copy_of.push_back(copy_marks.empty() ? 0 : (uint8_t)(copy_marks.size() - 1));
         return in.dst;
     }
     void insert_gate(uint32_t a, uint32_t b, uint32_t c, uint32_t op) { row(a, b, c, op); }

@@ -144,6 +144,8 @@ inline int check_program(const uint32_t* instr, size_t n_instr, const uint32_t* 
 struct BuiltProgram {
     size_t n_vars = 0;
     std::vector<uint32_t> instr, level_offsets, flow_wires, gates, witness_ops;
+    std::vector<uint8_t> copy_of;  // [n_vars]: the copy of the verifier that allocated the variable (the grouped witness kernels
+                                   // read it for hint instructions: copy c's hints are those of the group's proof c)
 };
 
 // d: the parsed template with its hint pointers set; flow / swap: the PoseidonFlow of ONE copy of the verifier.
@@ -154,7 +156,10 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
     FlowSource fsrc{flow, swap, flow_count, 0};
     Gadgets g{&cs, &fsrc};
     try {
-        for (uint32_t c = 0; c < copies; c++) verify_in_circuit(g, d, inputs, set_walks ? (set_walks[c] & 3u) : 0u);
+        for (uint32_t c = 0; c < copies; c++) {
+            cs.begin_copy();
+            verify_in_circuit(g, d, inputs, set_walks ? (set_walks[c] & 3u) : 0u);
+        }
     } catch (const std::exception& e) {
         if (log) fprintf(stderr, "[rsv] witness program build: %s\n", e.what());
         return RSV_E_RANGE;
@@ -163,6 +168,18 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
 
     // one instruction per variable, sorted by dependency depth
     const size_t n_vars = cs.variables.size();
+    // The gadgets run copy after copy, so a copy's variables are one contiguous range, and every hint (an instruction that
+    // reads the proof, its flow or its queried columns) lies in the range of the copy it was recorded for.  What copy 1 ..
+    // reuses of copy 0 are the cached constants: W_CONST, never a hint.
+    cs.copy_marks.push_back((uint32_t)n_vars);
+    if (cs.copy_marks.size() != (size_t)copies + 1 || cs.copy_of.size() != n_vars) return RSV_E_RANGE;
+    for (size_t k = 0; k < n_vars; k++) {
+        const uint32_t c = cs.copy_of[k];
+        if (cs.origin[k].op >= W_FLOW && (c >= copies || k < cs.copy_marks[c] || k >= cs.copy_marks[c + 1])) {
+            if (log) fprintf(stderr, "[rsv] witness program build: hint variable %zu lies outside copy %u\n", k, c);
+            return RSV_E_RANGE;
+        }
+    }
     std::vector<uint32_t> depth(n_vars, 0);
     uint32_t max_depth = 0;
     for (size_t k = 0; k < n_vars; k++) {
@@ -188,6 +205,7 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
     out.n_vars = n_vars;
     out.instr = std::move(instr);
     out.level_offsets = std::move(level_offsets);
+    out.copy_of = std::move(cs.copy_of);
     out.flow_wires.reserve(cs.flow.size() * 5);
     for (const FlowRecord& f : cs.flow) {
         for (int j = 0; j < 4; j++) out.flow_wires.push_back(f.wire[j]);

@@ -119,9 +119,10 @@ __device__ __forceinline__ void trace_flush(uint32_t* lds, const uint32_t* r0, c
 
 // Grid: proof-major, ceil(n_pad / 64) waves of 64 invocations per proof.  Invocation k < copies * flow_count hashes flow
 // record k % flow_count (every copy of the verifier invokes the same permutations); the padding invocations hash zeros
-// with wires and swap address 0.
-__global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
+// with wires and swap address 0.  GROUPED (rsv_witness_trace_groups_dev): p is a group of `copies` proofs whose records lie
+// one proof after the other, [n][copies][flow_count], and copy c hashes those of the group's proof c: record k of the group.
+template <bool GROUPED>
+__device__ __forceinline__ void trace_poseidon(const TraceArgs& a, uint32_t* lds) {
     const uint32_t per = (a.n_pad + TRACE_WAVE - 1) / TRACE_WAVE;
     const uint32_t p = blockIdx.x / per, k0 = (blockIdx.x % per) * TRACE_WAVE, k = k0 + threadIdx.x;
     const size_t Q = (size_t)1 << a.log_poseidon;
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; i++) in[i] = 0;
     if (k < a.flow_count * a.copies) {
-        const size_t rec = (size_t)p * a.flow_count + k % a.flow_count;
+        const size_t rec = GROUPED ? (size_t)p * a.flow_count * a.copies + k : (size_t)p * a.flow_count + k % a.flow_count;
         const uint4* f = a.flow + rec * 8;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -195,6 +196,14 @@ __global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
     trace_flush(lds, s, s1, out, Q, 0, 4, row_base, n_blocks);
     trace_flush(lds, mid0, mid1, out, Q, 16, 4, row_base, n_blocks);
     trace_flush(lds, s1, s2, out, Q, 32, 4, row_base, n_blocks);
+}
+__global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
+    trace_poseidon<false>(a, lds);
+}
+__global__ __launch_bounds__(64) void k_trace_poseidon_g(TraceArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
+    trace_poseidon<true>(a, lds);
 }
 
 // The rows behind the padded flow, [6 * n_pad, 2^lq) of all 48 columns of every proof: zero.  The start is a multiple of

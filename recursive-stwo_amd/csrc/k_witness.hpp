@@ -29,17 +29,30 @@ struct WitnessArgs {
     const uint32_t* fri_cols;    // [n][n_trees][nq][3][8]
     uint32_t nq, n_trees;
 };
+// The grouped form (rsv_witness_eval_groups_dev): n GROUPS of `copies` proofs, one `variables` vector per group.  Copy c of
+// group p's circuit verifies proof p * copies + c: vars, dst, accept and the arithmetic ops index the group, blob, offsets,
+// metas, flow, trace_cols and fri_cols the proof.
+struct WitnessGroupArgs : WitnessArgs {
+    const uint8_t* copy_of;  // [n_vars]: the copy that allocated a variable (circuit_program.hpp), read for hints only
+    uint32_t copies;
+};
+template <class A> struct witness_grouped { static constexpr bool value = false; };
+template <> struct witness_grouped<WitnessGroupArgs> { static constexpr bool value = true; };
 
 __device__ __forceinline__ QM31 q_of(uint4 v) { return q_mk(v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ uint4 u4_of(QM31 q) { return make_uint4(q.a.a, q.a.b, q.b.a, q.b.b); }
 __device__ __forceinline__ uint4 u4_words(const uint32_t* w) { return make_uint4(w[0], w[1], w[2], w[3]); }
 
 // one instruction (its eight words: w0 = op, dst, a, b; w1 = imm0..3) for one proof
-__device__ __forceinline__ void witness_exec(const WitnessArgs& a, const uint4 w0, const uint4 w1, uint32_t p) {
+template <class A>
+__device__ __forceinline__ void witness_exec(const A& a, const uint4 w0, const uint4 w1, uint32_t p) {
     const uint32_t op = w0.x, dst = w0.y, x = w0.z, y = w0.w, i0 = w1.x, i1 = w1.y, i2 = w1.z;
     const size_t n = a.n;
     uint4 r = make_uint4(0, 0, 0, 0);
     const bool ok = a.accept[p] != 0;  // a rejected proof's sections may not be where the program expects them
+    size_t q = p;                      // the proof a hint is read from: grouped, the group's member dst's copy verifies
+    if constexpr (witness_grouped<A>::value)
+        if (op >= W_FLOW && ok) q = (size_t)p * a.copies + a.copy_of[dst];
     switch (op) {
     case W_CONST: r = w1; break;
     case W_ADD: r = u4_of(q_add(q_of(a.vars[x * n + p]), q_of(a.vars[y * n + p]))); break;
@@ -68,12 +81,12 @@ __device__ __forceinline__ void witness_exec(const WitnessArgs& a, const uint4 w
     }
     case W_BIT: r.x = (a.vars[x * n + p].x >> i0) & 1u; break;
     case W_FLOW:
-        if (ok) r = a.flow[((size_t)p * a.flow_stride + i0) * 8 + (i1 >> 2)];
+        if (ok) r = a.flow[(q * a.flow_stride + i0) * 8 + (i1 >> 2)];
         break;
     default: {
         if (!ok) break;
-        const ProofMeta& m = a.metas[p];
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(a.blob + a.offsets[p]);
+        const ProofMeta& m = a.metas[q];
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(a.blob + a.offsets[q]);
         switch (op) {
         case W_WORD: r.x = w[i0]; break;
         case W_WORD4: r = u4_words(w + i0); break;
@@ -84,40 +97,48 @@ __device__ __forceinline__ void witness_exec(const WitnessArgs& a, const uint4 w
             r.x = i0 == 0 ? (uint32_t)(nonce & ((1u << 22) - 1)) : (uint32_t)((nonce >> (i0 == 1 ? 22 : 43)) & ((1u << 21) - 1));
             break;
         }
-        case W_TRACE_COL: r.x = a.trace_cols[(((size_t)p * 4 + i0) * a.nq + i1) * 64 + i2]; break;
-        case W_FRI_COL: r = u4_words(a.fri_cols + (((size_t)p * a.n_trees + i0) * a.nq + i1) * 24 + i2); break;
+        case W_TRACE_COL: r.x = a.trace_cols[((q * 4 + i0) * a.nq + i1) * 64 + i2]; break;
+        case W_FRI_COL: r = u4_words(a.fri_cols + ((q * a.n_trees + i0) * a.nq + i1) * 24 + i2); break;
         default: break;
         }
     }
     }
     a.vars[dst * n + p] = r;
 }
-__device__ __forceinline__ void witness_exec(const WitnessArgs& a, uint32_t i, uint32_t p) {
+template <class A>
+__device__ __forceinline__ void witness_exec(const A& a, uint32_t i, uint32_t p) {
     const uint4* in = reinterpret_cast<const uint4*>(a.instr) + (size_t)i * 2;
     witness_exec(a, in[0], in[1], p);
 }
 
 // one level, grid = (instructions of the level) x (proofs)
-__global__ __launch_bounds__(256) void k_witness_level(WitnessArgs a) {
+template <class A>
+__device__ __forceinline__ void witness_level(const A& a) {
     const uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     const uint32_t i = a.begin + (uint32_t)(t / a.n), p = (uint32_t)(t % a.n);
     if (i >= a.end) return;
     witness_exec(a, i, p);
 }
+__global__ __launch_bounds__(256) void k_witness_level(WitnessArgs a) { witness_level(a); }
+__global__ __launch_bounds__(256) void k_witness_level_g(WitnessGroupArgs a) { witness_level(a); }
 
 // the same for batches of at least a wave of proofs: blockIdx.y = the instruction, so that the instruction words are scalar
 // loads and the switch a scalar branch (in the 1-D form a wave may straddle two instructions, and every lane divides)
-__global__ __launch_bounds__(256) void k_witness_level_wide(WitnessArgs a) {
+template <class A>
+__device__ __forceinline__ void witness_level_wide(const A& a) {
     const uint32_t i = a.begin + blockIdx.y, p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= a.n) return;
     witness_exec(a, i, p);
 }
+__global__ __launch_bounds__(256) void k_witness_level_wide(WitnessArgs a) { witness_level_wide(a); }
+__global__ __launch_bounds__(256) void k_witness_level_wide_g(WitnessGroupArgs a) { witness_level_wide(a); }
 
 // Levels l0 .. l1 walked by ONE workgroup for its own proofs (dependencies never cross proofs): instruction slot `slot` of
 // `n_slots` takes instructions begin + slot, + n_slots, ... of every level, a workgroup barrier ends a level (the waves of
 // a workgroup share the CU's L1, so what one wave stored is what the next level's loads see).  A level costs about one
 // memory round trip (the operands): reading the bounds and instruction words a level ahead was measured and gains nothing.
-__device__ __forceinline__ void witness_walk(const WitnessArgs& a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1,
+template <class A>
+__device__ __forceinline__ void witness_walk(const A& a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1,
                                              uint32_t p, uint32_t slot, uint32_t n_slots) {
     for (uint32_t l = l0; l < l1; l++) {
         const uint32_t begin = level_offsets[l], end = level_offsets[l + 1];
@@ -136,6 +157,10 @@ __global__ __launch_bounds__(256) void k_witness_strip(WitnessArgs a, const uint
     const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
     witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
 }
+__global__ __launch_bounds__(256) void k_witness_strip_g(WitnessGroupArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
+    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
+}
 
 // Small and medium batches: the WHOLE program in one launch.  A workgroup of 1 024 lanes owns P2 = 2^log_p2 proofs (n <= 4:
 // one workgroup, P2 = n rounded up — the reference's own use is ONE proof per recursion step; larger batches: P2 proofs per
@@ -145,6 +170,11 @@ __global__ __launch_bounds__(256) void k_witness_strip(WitnessArgs a, const uint
 // instead of 1 KB), which is why the level-per-launch form takes over for large batches (witness_api.inc).
 __global__ __launch_bounds__(1024) void k_witness_small(WitnessArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
                                                         uint32_t log_p2) {
+    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
+    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
+}
+__global__ __launch_bounds__(1024) void k_witness_small_g(WitnessGroupArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
+                                                          uint32_t log_p2) {
     const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
     witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
 }

@@ -86,9 +86,10 @@ int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t*
     }
 }
 
-int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
-                          const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
-                          uint32_t* d_ops) {
+// rsv_witness_trace_dev (n proofs) and rsv_witness_trace_groups_dev (n groups, `grouped`): only the flow records differ
+static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                         const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
+                         uint32_t* d_ops, bool grouped) {
     if (!c || !prog || !d_accept) return RSV_E_NULL;
     if ((d_plonk || d_ops) && !d_variables) return RSV_E_NULL;
     if (d_poseidon && (!d_flow || !d_flow_swap)) return RSV_E_NULL;
@@ -97,6 +98,7 @@ int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* prog, const uin
         return RSV_E_SIZE;
     int rc = chain_begin(c, prog, n, false);
     if (rc != RSV_OK) return rc;
+    if (grouped && n > (1u << 20) / prog->shape.copies) return RSV_E_SIZE;  // (a built program has at least one copy)
     if (n == 0) return RSV_OK;
     const rsv_witness_shape& s = prog->shape;
     rsv::TraceArgs a{};
@@ -126,13 +128,25 @@ int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* prog, const uin
     if (d_plonk) hipLaunchKernelGGL(rsv::k_trace_plonk, dim3((unsigned)plonk_blocks), dim3(256), 0, st, a);
     if (d_ops && n_ops) hipLaunchKernelGGL(rsv::k_trace_ops, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, a, prog->d_trace_ops, (uint32_t)n_ops, d_ops);
     if (d_poseidon) {
-        hipLaunchKernelGGL(rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
+        hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_g : rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
         if (tail_threads)
             hipLaunchKernelGGL(rsv::k_trace_zero_tail, dim3(grid_for(tail_threads, 256)), dim3(256), 0, st, d_poseidon, a.log_poseidon,
                                (uint32_t)tail_first, (uint64_t)rsv::POSEIDON_COLS_K * n);
     }
     HIP_TRY(hipGetLastError());
     return RSV_OK;
+}
+
+int rsv_witness_trace_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                          const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n, uint32_t* d_plonk, uint32_t* d_poseidon,
+                          uint32_t* d_ops) {
+    return witness_trace(c, prog, d_variables, d_flow, d_flow_swap, d_accept, n, d_plonk, d_poseidon, d_ops, false);
+}
+
+int rsv_witness_trace_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                                 const uint8_t* d_flow_swap, const uint8_t* d_accept, size_t n_groups, uint32_t* d_plonk,
+                                 uint32_t* d_poseidon, uint32_t* d_ops) {
+    return witness_trace(c, prog, d_variables, d_flow, d_flow_swap, d_accept, n_groups, d_plonk, d_poseidon, d_ops, true);
 }
 
 int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,

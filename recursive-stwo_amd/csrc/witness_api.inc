@@ -24,6 +24,9 @@ struct rsv_witness_program {
     // rsv_witness_interaction_dev and rsv_witness_commit_dev: the 10 + 40 preprocessed columns, [10][2^trace_lp] then
     // [40][2^trace_lq] (rsv_trace_preprocessed's order): the relations' columns and tree 0
     uint32_t* d_trace_pre = nullptr;
+    // rsv_witness_eval_groups_dev: the copy that allocated each variable [n_vars] (built programs only; circuit_program.hpp)
+    std::vector<uint8_t> copy_of;
+    uint8_t* d_copy_of = nullptr;
 };
 
 namespace {
@@ -48,6 +51,78 @@ __global__ void k_witness_gate(const ProofMeta* __restrict__ metas, uint32_t n, 
     const bool same = m.reason == R_OK && m.lp == s.log_size_plonk && m.lq == s.log_size_poseidon && m.pow_bits == s.pow_bits &&
                       m.blowup == s.log_blowup && m.log_last == s.log_last && m.nq == s.n_queries && m.n_inner == s.n_inner;
     if (!same) accept[p] = 0;
+}
+
+// accept[g] = every member of group g verified and has the program's shape (members: k_witness_gate's verdicts, [n_groups][copies])
+__global__ void k_witness_group_accept(const uint8_t* __restrict__ members, uint32_t n_groups, uint32_t copies, uint8_t* __restrict__ accept) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    uint8_t all = 1;
+    for (uint32_t c = 0; c < copies; c++) all &= members[(size_t)g * copies + c] != 0;
+    accept[g] = all;
+}
+
+// The kernels of the two forms of the evaluation (k_witness.hpp): a batch of proofs, and groups of `copies` proofs.
+struct WitnessKernels {
+    static constexpr auto level = k_witness_level, level_wide = k_witness_level_wide;
+    static constexpr auto strip = k_witness_strip;
+    static constexpr auto small = k_witness_small;
+};
+struct WitnessGroupKernels {
+    static constexpr auto level = k_witness_level_g, level_wide = k_witness_level_wide_g;
+    static constexpr auto strip = k_witness_strip_g;
+    static constexpr auto small = k_witness_small_g;
+};
+
+// The program over n proofs (or n groups: a.n = n), in the launch form the batch size and the context's options choose.
+template <class K, class A>
+void witness_launch(rsv_ctx* c, const rsv_witness_program* prog, A a, size_t n) {
+    hipStream_t st = c->stream;
+    const size_t n_levels = prog->level_offsets.size() - 1;
+    // One launch for the whole program (k_witness_small) while a workgroup's share stays short: 2^log_p2 proofs per
+    // workgroup = n_instr * 2^log_p2 / 1024 rounds of its 1 024 lanes + a barrier per level, about a microsecond each,
+    // against ~140 launches with a drain between them (~0.75 ms) for the level form.
+    uint32_t log_p2 = 0;
+    if (n <= SMALL_BATCH) while ((1u << log_p2) < n) log_p2++;
+    else log_p2 = c->opt.witness_small_log ? (uint32_t)c->opt.witness_small_log - 1 : 2u;
+    const bool small = c->opt.witness_small_max ? n <= (size_t)c->opt.witness_small_max - 1
+                                                : n <= SMALL_MAX && (((uint64_t)prog->n_instr << log_p2) >> 10) <= SMALL_ROUNDS;
+    if (small) {
+        hipLaunchKernelGGL(K::small, dim3(grid_for(n, 1u << log_p2)), dim3(1024), 0, st, a, prog->d_levels, (uint32_t)n_levels, log_p2);
+    } else {
+    // Mid-size batches: the wide head of the program level by level, then EVERYTHING behind it in one launch, a 1 024-lane
+    // workgroup per 2^walk_log proofs walking the remaining levels (most of them ~100 instructions wide: a launch each
+    // would be half launch gap).  RSV_OPT_WITNESS_WALK_LOG: 0 auto, 1 off, else 1 + log2(proofs per workgroup).
+    uint32_t walk_log = 0;
+    bool walk = false;
+    if (c->opt.witness_walk_log >= 2) { walk = true; walk_log = (uint32_t)c->opt.witness_walk_log - 1; }
+    else if (c->opt.witness_walk_log == 0) {  // measured (tools/witness_small_sweep.py, level10 shape, whole call): 2 048 proofs 4.55 -> 4.29 ms
+        walk = true;                            // with 8 per workgroup, 4 096: 6.90 -> 6.66 and 8 192: 12.57 -> 12.17 with 16, 16 384: 24.18 -> 23.50 with 32
+        walk_log = n <= 2048 ? 3u : n <= 8192 ? 4u : 5u;
+    }
+    const size_t head_end = walk ? prog->walk_from : prog->strip_from;
+    for (size_t l = 0; l < head_end; l++) {
+        a.begin = prog->level_offsets[l];
+        a.end = prog->level_offsets[l + 1];
+        if (a.end == a.begin) continue;
+        if (n >= 64) {  // an instruction per blockIdx.y (65 535 at most per launch), proofs along x in blocks of 64 .. 256 lanes
+            const uint32_t block = n >= 256 ? 256u : (uint32_t)((n + 63) / 64 * 64), end = a.end;
+            for (uint32_t b = a.begin; b < end; b += 65535u) {
+                a.begin = b;
+                a.end = end - b > 65535u ? b + 65535u : end;
+                hipLaunchKernelGGL(K::level_wide, dim3(grid_for(n, block), a.end - a.begin), dim3(block), 0, st, a);
+            }
+            continue;
+        }
+        const size_t threads = (size_t)(a.end - a.begin) * n;
+        hipLaunchKernelGGL(K::level, dim3(grid_for(threads, 256)), dim3(256), 0, st, a);
+    }
+    if (walk && prog->walk_from < n_levels)
+        hipLaunchKernelGGL(K::small, dim3(grid_for(n, 1u << walk_log)), dim3(1024), 0, st, a, prog->d_levels + prog->walk_from,
+                           (uint32_t)(n_levels - prog->walk_from), walk_log);
+    else if (prog->strip_from < n_levels)
+        hipLaunchKernelGGL(K::strip, dim3(grid_for(n, 64)), dim3(256), 0, st, a, prog->d_levels, prog->strip_from, (uint32_t)n_levels);
+    }
 }
 
 // The host-buffer forms of the witness chain (rsv_witness_eval, _trace, _interaction, _commit) on a context of their own:
@@ -160,24 +235,98 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_trace_wires) (void)hipFree(p->d_trace_wires);
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
     if (p->d_trace_pre) (void)hipFree(p->d_trace_pre);
+    if (p->d_copy_of) (void)hipFree(p->d_copy_of);
     delete p;
 }
 
-static size_t witness_scratch(const rsv_witness_program* prog, size_t n, bool with_vars) {
+// The context's scratch of one evaluation: the hints of `members` proofs and, with `with_vars`, vars[variable][row] of `rows`
+// vectors (rows = members for a batch of proofs, the number of groups for groups).  base NULL: the size only.
+struct WitnessScratch {
+    uint32_t *trace_cols, *fri_cols;
+    uint4* flow;
+    uint8_t* flow_swap;
+    uint4* vars;
+    size_t bytes;
+};
+static WitnessScratch witness_carve(const rsv_witness_program* prog, char* base, size_t members, size_t rows, bool with_vars) {
     const rsv_witness_shape& s = prog->shape;
     const size_t nq = s.n_queries, nt = 1 + (size_t)s.n_inner;
-    Carve cv{nullptr};
-    cv.take<uint32_t>(n * 4 * nq * 64);
-    cv.take<uint32_t>(n * nt * nq * 24);
-    cv.take<uint4>(n * (size_t)s.flow_count * 8);
-    cv.take<uint8_t>(n * (size_t)s.flow_count);
-    if (with_vars) cv.take<uint4>(n * (size_t)prog->n_vars);
-    return cv.off + 4096;
+    Carve cv{base};
+    WitnessScratch w{};
+    w.trace_cols = cv.take<uint32_t>(members * 4 * nq * 64);
+    w.fri_cols = cv.take<uint32_t>(members * nt * nq * 24);
+    w.flow = cv.take<uint4>(members * (size_t)s.flow_count * 8);
+    w.flow_swap = cv.take<uint8_t>(members * (size_t)s.flow_count);
+    if (with_vars) w.vars = cv.take<uint4>(rows * (size_t)prog->n_vars);
+    w.bytes = cv.off + 4096;
+    return w;
 }
 
 int rsv_witness_scratch_bytes(const rsv_witness_program* prog, size_t n, size_t* bytes) {
     if (!prog || !bytes) return RSV_E_NULL;
-    *bytes = witness_scratch(prog, n, true);  // under RSV_OPT_WITNESS_LAYOUT = 2 the variables are not held twice: n * n_vars * 16 less
+    *bytes = witness_carve(prog, nullptr, n, n, true).bytes;  // under RSV_OPT_WITNESS_LAYOUT = 2 the variables are not held twice: n * n_vars * 16 less
+    return RSV_OK;
+}
+
+int rsv_witness_group_scratch_bytes(const rsv_witness_program* prog, size_t n_groups, size_t* bytes) {
+    if (!prog || !bytes) return RSV_E_NULL;
+    if (prog->copy_of.empty()) return RSV_E_SIZE;  // built programs only
+    *bytes = witness_carve(prog, nullptr, n_groups * (size_t)prog->shape.copies, n_groups, true).bytes;
+    return RSV_OK;
+}
+
+// What both forms of the evaluation do before the program runs: the configuration check, the scratch, the verifying pass
+// over `members` proofs with the hint outputs the program reads, and the members' verdicts (d_verdict, d_reason: the pass's,
+// then k_witness_gate).  Fills `a` for `rows` vectors, all but a.accept.
+static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
+                         size_t rows, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables,
+                         uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_verdict, uint8_t* d_reason, WitnessArgs& a) {
+    const rsv_witness_shape& s = prog->shape;
+    // the program belongs to one configuration: the batch has to be verified under exactly that one
+    if (!cfg || !cfg->cfgs || cfg->n_cfgs != 1 || cfg->cfg_of) return RSV_E_SIZE;
+    const rsv_pcs_config& pc = cfg->cfgs[0];
+    if (pc.pow_bits != s.pow_bits || pc.log_blowup_factor != s.log_blowup || pc.log_last_layer_degree_bound != s.log_last ||
+        pc.n_queries != s.n_queries)
+        return RSV_E_SIZE;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool by_variable = c->opt.witness_layout == 2;  // the caller takes vars[variable][row] as the kernels write it
+    int rc = ensure_buf(c, &c->ws_witness, &c->ws_witness_bytes, witness_carve(prog, nullptr, members, rows, !by_variable).bytes);
+    if (rc != RSV_OK) return rc;
+    const size_t nq = s.n_queries, nt = 1 + (size_t)s.n_inner;
+    const uint32_t M = (s.log_size_plonk + 1 > s.log_size_poseidon + 2 ? s.log_size_plonk + 1 : s.log_size_poseidon + 2) + s.log_blowup;
+    WitnessScratch w = witness_carve(prog, static_cast<char*>(c->ws_witness), members, rows, !by_variable);
+    if (d_flow) {  // the caller keeps the PoseidonFlow (the next prover needs it beside the variables): written there directly
+        w.flow = reinterpret_cast<uint4*>(d_flow);
+        w.flow_swap = d_flow_swap;
+    }
+    if (by_variable) w.vars = reinterpret_cast<uint4*>(d_variables);
+    rsv_hints_out ho{};
+    ho.n_queries = s.n_queries; ho.max_log = M; ho.n_inner = s.n_inner;
+    // the column values only: the sibling hashes of the paths are single-use halves of the circuit (no variables; their
+    // values are in the flow records), so the per-query sibling paths are not asked for
+    ho.d_trace_cols = w.trace_cols;
+    ho.d_fri_cols = w.fri_cols;
+    ho.d_flow = reinterpret_cast<uint32_t*>(w.flow);
+    ho.d_flow_swap = w.flow_swap;
+    ho.flow_stride = s.flow_count;
+    // a proof of another shape may be shorter than the program's columns: nothing of an earlier batch may be read for it
+    HIP_TRY(hipMemsetAsync(w.trace_cols, 0, members * 4 * nq * 64 * 4, c->stream));
+    HIP_TRY(hipMemsetAsync(w.fri_cols, 0, members * nt * nq * 24 * 4, c->stream));
+    rc = rsv_verify_hints_dev(c, d_blob, d_offsets, members, cfg, pi, n_pi, &ho, d_verdict, d_reason);
+    if (rc != RSV_OK) return rc;
+    hipLaunchKernelGGL(k_witness_gate, dim3(grid_for(members, 256)), dim3(256), 0, c->stream, c->last_metas, (uint32_t)members, s, d_verdict);
+    a.instr = prog->d_instr; a.n = (uint32_t)rows; a.vars = w.vars; a.blob = d_blob; a.offsets = d_offsets; a.metas = c->last_metas;
+    a.flow = w.flow; a.flow_stride = s.flow_count; a.trace_cols = w.trace_cols; a.fri_cols = w.fri_cols;
+    a.nq = s.n_queries; a.n_trees = (uint32_t)nt;
+    return RSV_OK;
+}
+
+// vars[variable][row] -> d_variables[row][variable], unless the caller takes the kernels' layout (then vars IS d_variables)
+static int witness_finish(rsv_ctx* c, const rsv_witness_program* prog, const uint4* vars, uint32_t* d_variables, size_t rows) {
+    if (c->opt.witness_layout != 2)
+        hipLaunchKernelGGL(k_witness_transpose, dim3(grid_for(prog->n_vars, 32), grid_for(rows, 32)), dim3(256), 0, c->stream, vars,
+                           reinterpret_cast<uint4*>(d_variables), prog->n_vars, (uint32_t)rows);
+    HIP_TRY(hipGetLastError());
     return RSV_OK;
 }
 
@@ -190,97 +339,46 @@ int rsv_witness_eval_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint
     if (n == 0) return RSV_OK;
     if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
     if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
-    const rsv_witness_shape& s = prog->shape;
-    // the program belongs to one configuration: the batch has to be verified under exactly that one
-    if (!cfg || !cfg->cfgs || cfg->n_cfgs != 1 || cfg->cfg_of) return RSV_E_SIZE;
-    const rsv_pcs_config& pc = cfg->cfgs[0];
-    if (pc.pow_bits != s.pow_bits || pc.log_blowup_factor != s.log_blowup || pc.log_last_layer_degree_bound != s.log_last ||
-        pc.n_queries != s.n_queries)
-        return RSV_E_SIZE;
-    HIP_TRY(hipSetDevice(c->device));
-    const bool by_variable = c->opt.witness_layout == 2;  // the caller takes vars[variable][proof] as the kernels write it
-    int rc = ensure_buf(c, &c->ws_witness, &c->ws_witness_bytes, witness_scratch(prog, n, !by_variable));
-    if (rc != RSV_OK) return rc;
-    const size_t nq = s.n_queries, nt = 1 + (size_t)s.n_inner;
-    const uint32_t M = (s.log_size_plonk + 1 > s.log_size_poseidon + 2 ? s.log_size_plonk + 1 : s.log_size_poseidon + 2) + s.log_blowup;
-    Carve cv{static_cast<char*>(c->ws_witness)};
-    rsv_hints_out ho{};
-    ho.n_queries = s.n_queries; ho.max_log = M; ho.n_inner = s.n_inner;
-    // the column values only: the sibling hashes of the paths are single-use halves of the circuit (no variables; their
-    // values are in the flow records), so the per-query sibling paths are not asked for
-    ho.d_trace_cols = cv.take<uint32_t>(n * 4 * nq * 64);
-    ho.d_fri_cols = cv.take<uint32_t>(n * nt * nq * 24);
-    uint4* flow = cv.take<uint4>(n * (size_t)s.flow_count * 8);
-    uint8_t* flow_swap = cv.take<uint8_t>(n * (size_t)s.flow_count);
-    if (d_flow) {  // the caller keeps the PoseidonFlow (the next prover needs it beside the variables): written there directly
-        flow = reinterpret_cast<uint4*>(d_flow);
-        flow_swap = d_flow_swap;
-    }
-    ho.d_flow = reinterpret_cast<uint32_t*>(flow);
-    ho.d_flow_swap = flow_swap;
-    ho.flow_stride = s.flow_count;
-    uint4* vars = by_variable ? reinterpret_cast<uint4*>(d_variables) : cv.take<uint4>(n * (size_t)prog->n_vars);
-    // a proof of another shape may be shorter than the program's columns: nothing of an earlier batch may be read for it
-    HIP_TRY(hipMemsetAsync(ho.d_trace_cols, 0, n * 4 * nq * 64 * 4, c->stream));
-    HIP_TRY(hipMemsetAsync(ho.d_fri_cols, 0, n * nt * nq * 24 * 4, c->stream));
-    rc = rsv_verify_hints_dev(c, d_blob, d_offsets, n, cfg, pi, n_pi, &ho, d_accept, d_reason);
-    if (rc != RSV_OK) return rc;
-    hipStream_t st = c->stream;
-    hipLaunchKernelGGL(k_witness_gate, dim3(grid_for(n, 256)), dim3(256), 0, st, c->last_metas, (uint32_t)n, s, d_accept);
     WitnessArgs a{};
-    a.instr = prog->d_instr; a.n = (uint32_t)n; a.vars = vars; a.blob = d_blob; a.offsets = d_offsets; a.metas = c->last_metas;
-    a.accept = d_accept; a.flow = flow; a.flow_stride = s.flow_count; a.trace_cols = ho.d_trace_cols; a.fri_cols = ho.d_fri_cols;
-    a.nq = s.n_queries; a.n_trees = (uint32_t)nt;
-    const size_t n_levels = prog->level_offsets.size() - 1;
-    // One launch for the whole program (k_witness_small) while a workgroup's share stays short: 2^log_p2 proofs per
-    // workgroup = n_instr * 2^log_p2 / 1024 rounds of its 1 024 lanes + a barrier per level, about a microsecond each,
-    // against ~140 launches with a drain between them (~0.75 ms) for the level form.
-    uint32_t log_p2 = 0;
-    if (n <= SMALL_BATCH) while ((1u << log_p2) < n) log_p2++;
-    else log_p2 = c->opt.witness_small_log ? (uint32_t)c->opt.witness_small_log - 1 : 2u;
-    const bool small = c->opt.witness_small_max ? n <= (size_t)c->opt.witness_small_max - 1
-                                                : n <= SMALL_MAX && (((uint64_t)prog->n_instr << log_p2) >> 10) <= SMALL_ROUNDS;
-    if (small) {
-        hipLaunchKernelGGL(k_witness_small, dim3(grid_for(n, 1u << log_p2)), dim3(1024), 0, st, a, prog->d_levels, (uint32_t)n_levels, log_p2);
-    } else {
-    // Mid-size batches: the wide head of the program level by level, then EVERYTHING behind it in one launch, a 1 024-lane
-    // workgroup per 2^walk_log proofs walking the remaining levels (most of them ~100 instructions wide: a launch each
-    // would be half launch gap).  RSV_OPT_WITNESS_WALK_LOG: 0 auto, 1 off, else 1 + log2(proofs per workgroup).
-    uint32_t walk_log = 0;
-    bool walk = false;
-    if (c->opt.witness_walk_log >= 2) { walk = true; walk_log = (uint32_t)c->opt.witness_walk_log - 1; }
-    else if (c->opt.witness_walk_log == 0) {  // measured (tools/witness_small_sweep.py, level10 shape, whole call): 2 048 proofs 4.55 -> 4.29 ms
-        walk = true;                            // with 8 per workgroup, 4 096: 6.90 -> 6.66 and 8 192: 12.57 -> 12.17 with 16, 16 384: 24.18 -> 23.50 with 32
-        walk_log = n <= 2048 ? 3u : n <= 8192 ? 4u : 5u;
-    }
-    const size_t head_end = walk ? prog->walk_from : prog->strip_from;
-    for (size_t l = 0; l < head_end; l++) {
-        a.begin = prog->level_offsets[l];
-        a.end = prog->level_offsets[l + 1];
-        if (a.end == a.begin) continue;
-        if (n >= 64) {  // an instruction per blockIdx.y (65 535 at most per launch), proofs along x in blocks of 64 .. 256 lanes
-            const uint32_t block = n >= 256 ? 256u : (uint32_t)((n + 63) / 64 * 64), end = a.end;
-            for (uint32_t b = a.begin; b < end; b += 65535u) {
-                a.begin = b;
-                a.end = end - b > 65535u ? b + 65535u : end;
-                hipLaunchKernelGGL(k_witness_level_wide, dim3(grid_for(n, block), a.end - a.begin), dim3(block), 0, st, a);
+    int rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a);
+    if (rc != RSV_OK) return rc;
+    a.accept = d_accept;
+    witness_launch<WitnessKernels>(c, prog, a, n);
+    return witness_finish(c, prog, a.vars, d_variables, n);
+}
+
+int rsv_witness_eval_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n_groups,
+                                const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
+                                uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
+    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
+    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
+    if (prog->copy_of.empty()) return RSV_E_SIZE;  // only a built program knows which copy a hint belongs to
+    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (n_groups == 0) return RSV_OK;
+    const size_t copies = prog->shape.copies;
+    if (n_groups > (1u << 20) / copies || prog->device != c->device) return RSV_E_SIZE;
+    WitnessGroupArgs a{};  // d_flow is [n_groups][copies][flow_count]: the members' records, one proof after the other
+    int rc = witness_hints(c, prog, d_blob, d_offsets, n_groups * copies, n_groups, cfg, pi, n_pi, d_variables, d_flow, d_flow_swap,
+                           d_member_accept, d_member_reason, a);
+    if (rc != RSV_OK) return rc;
+    {   // the table of copies goes to the device on the first call
+        rsv_witness_program* wp = const_cast<rsv_witness_program*>(prog);
+        std::lock_guard<std::mutex> lk(wp->trace_mu);
+        if (!wp->d_copy_of) {
+            uint8_t* d = nullptr;
+            if (hipMalloc(reinterpret_cast<void**>(&d), wp->copy_of.size()) != hipSuccess) return RSV_E_DEVICE;
+            if (hipMemcpy(d, wp->copy_of.data(), wp->copy_of.size(), hipMemcpyHostToDevice) != hipSuccess) {
+                (void)hipFree(d);
+                return RSV_E_DEVICE;
             }
-            continue;
+            wp->d_copy_of = d;
         }
-        const size_t threads = (size_t)(a.end - a.begin) * n;
-        hipLaunchKernelGGL(k_witness_level, dim3(grid_for(threads, 256)), dim3(256), 0, st, a);
     }
-    if (walk && prog->walk_from < n_levels)
-        hipLaunchKernelGGL(k_witness_small, dim3(grid_for(n, 1u << walk_log)), dim3(1024), 0, st, a, prog->d_levels + prog->walk_from,
-                           (uint32_t)(n_levels - prog->walk_from), walk_log);
-    else if (prog->strip_from < n_levels)
-        hipLaunchKernelGGL(k_witness_strip, dim3(grid_for(n, 64)), dim3(256), 0, st, a, prog->d_levels, prog->strip_from, (uint32_t)n_levels);
-    }
-    if (!by_variable)
-        hipLaunchKernelGGL(k_witness_transpose, dim3(grid_for(prog->n_vars, 32), grid_for(n, 32)), dim3(256), 0, st, vars,
-                           reinterpret_cast<uint4*>(d_variables), prog->n_vars, (uint32_t)n);
-    HIP_TRY(hipGetLastError());
-    return RSV_OK;
+    hipLaunchKernelGGL(k_witness_group_accept, dim3(grid_for(n_groups, 256)), dim3(256), 0, c->stream, d_member_accept, (uint32_t)n_groups,
+                       (uint32_t)copies, d_accept);
+    a.accept = d_accept; a.copy_of = prog->d_copy_of; a.copies = (uint32_t)copies;
+    witness_launch<WitnessGroupKernels>(c, prog, a, n_groups);
+    return witness_finish(c, prog, a.vars, d_variables, n_groups);
 }
 
 int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
