@@ -549,10 +549,12 @@ int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_co
                               uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out);
 /* Sizes, then the arrays (any pointer may be NULL): instr [n_vars][8], level_offsets [n_levels + 1], flow_wires
  * [copies * flow_count][5] = PoseidonEntry::wire of r1..r4 and SwapOption::addr of every invocation (constants of the
- * shape; known to built programs only, RSV_E_SIZE otherwise) — what rsv_witness_program_create takes back. */
+ * shape; known to built programs and to those made from a circuit, RSV_E_SIZE otherwise) — what
+ * rsv_witness_program_create takes back. */
 int rsv_witness_program_info(const rsv_witness_program* prog, uint32_t* n_vars, uint32_t* n_levels, rsv_witness_shape* shape);
 int rsv_witness_program_export(const rsv_witness_program* prog, uint32_t* instr, uint32_t* level_offsets, uint32_t* flow_wires);
-/* The circuit's gate list as the gadgets left it (built programs only, RSV_E_SIZE otherwise): gates [n_rows][6] =
+/* The circuit's gate list as the gadgets left it, or as rsv_circuit_program_create took it (RSV_E_SIZE for a program made
+ * from instructions alone): gates [n_rows][6] =
  * a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31 per Plonk row (plonk_with_poseidon.rs:23-36, before pad()) —
  * with `variables` and the flow everything generate_plonk_with_poseidon_circuit (:522-629) and populate_logup_arguments
  * (:345-466) read.  The rows are constants of the shape EXCEPT `op` at the rows listed in witness_ops [n][3] = (row, bit
@@ -596,6 +598,50 @@ int rsv_witness_eval_groups_dev(rsv_ctx* ctx, const rsv_witness_program* prog, c
                                 uint8_t* d_member_reason);
 int rsv_witness_group_scratch_bytes(const rsv_witness_program* prog, size_t n_groups, size_t* bytes);
 
+/* ---- a caller's own Plonk-with-Poseidon circuit through the chain -----------------------------------------------------
+ * The reference's prove_plonk_with_poseidon proves whatever circuit the constraint system holds; so does the chain from
+ * rsv_witness_trace_dev on, which reads of a program only its gate list, flow wires, witness ops and n_vars.
+ * rsv_circuit_program_create makes such a program from the circuit itself, in the arrays rsv_witness_program_gates and
+ * rsv_witness_program_export return: gates [n_rows][6] (unpadded), flow_wires [n_flow][5], witness_ops [n][3] (may be
+ * NULL with a count of 0).  num_input is the reference's: 3 for the constants 1, i, j plus one per new_*(PublicInput); the
+ * public inputs are variables 1 .. num_input.  The program has no instructions: shape.copies = 1, shape.flow_count =
+ * n_flow, the verifier fields of the shape are zero; _info, _export (instr: nothing is written), _gates and _destroy work
+ * on it and every stage of the chain accepts it; what evaluates a witness (rsv_witness_eval*, rsv_witness_scratch_bytes,
+ * the host forms rsv_witness_trace / _interaction / _commit, the _groups calls) refuses it with RSV_E_SIZE before any device
+ * work.  The witness is the caller's: `variables` [n][n_vars][4], and the flow, which rsv_circuit_flow_dev makes.
+ * Host work only (the device copies are uploaded by the first stage that needs them); everything is checked before
+ * anything is kept:
+ *   RSV_E_NULL   a NULL array with a non-zero count, out NULL;
+ *   RSV_E_SIZE   zero rows or flow, a log size beyond RSV_MAX_WITNESS_LOG, n_vars above 2^26;
+ *   RSV_E_RANGE  a wire, bit variable or swap address >= n_vars, a witness-op row >= n_rows; the four constant rows
+ *                (k, 0, k, op 1) absent; num_input < 3 or >= n_vars; a non-zero flow wire that is not the poseidon_wire of
+ *                exactly one row; a Poseidon wire used more than once (the reference's assert in populate_logup_arguments). */
+int rsv_circuit_program_create(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow,
+                               const uint32_t* witness_ops, size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, int device,
+                               rsv_witness_program** out);
+/* The reference's two checks before it proves, for n witnesses of one circuit in HBM (d_variables in the layout
+ * RSV_OPT_WITNESS_LAYOUT names, 16-byte aligned), for any program with a gate list, built or made from a circuit
+ * (RSV_E_SIZE otherwise; RSV_E_RANGE if the program's arrays fail rsv_circuit_program_create's checks).  Enqueued on the
+ * context's stream with no host synchronisation; the program's tables go to the device on the first call.
+ * d_ok [n] is only ever cleared: the caller sets it to 1, and the same array then serves as the chain's d_accept.  A proof
+ * with d_ok[i] == 0 on entry is skipped.  d_bad_row / d_bad_flow [n] are always written: the smallest failing row or
+ * invocation, 0xffffffff where there is none or the proof was skipped.
+ *   rsv_circuit_check_dev: cs.check_arithmetics() (plonk_with_poseidon.rs:337-381).  Row r fails unless
+ *     c == op (a + b) + (1 - op) a b in QM31 (at a witness-op row op = variables[bit].x ? constant : 0), words 1..3 of c are
+ *     zero where enforce_c_m31 is set, every word read is below P, and, for r < 4, variable r is 0, 1, i, j.
+ *   rsv_circuit_flow_dev: cs.check_poseidon_invocations() (:468-519), and the PoseidonFlow itself.  d_flow
+ *     [n][n_flow][32] (16-byte aligned) + d_flow_swap [n][n_flow], in the layout of rsv_hints_out::d_flow, are IN/OUT: an
+ *     input half r1 / r2 whose wire is 0 (a previous permutation's ignored output used once) is read from its place in
+ *     the record; one with a wire is the pair (variables[a_wire], variables[b_wire]) of the row carrying that
+ *     poseidon_wire.  The swap bit is variables[swap address] (address 0: no swap).  The state is r1 || r2, or r2 || r1
+ *     under swap; the permutation's output is r3 || r4.  All 32 words and the swap byte of every record are written
+ *     (zeros for a skipped proof).  Invocation k fails if a word of its input is not below P, the swap bit is not the
+ *     QM31 0 or 1, or an output with a wire differs from its pair in variables. */
+int rsv_circuit_check_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, uint8_t* d_ok,
+                          uint32_t* d_bad_row);
+int rsv_circuit_flow_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, uint32_t* d_flow,
+                         uint8_t* d_flow_swap, uint8_t* d_ok, uint32_t* d_bad_flow);
+
 /* ---- the columns the next prover commits: 22 Plonk + 88 Poseidon ----------------------------------------------------
  * generate_plonk_with_poseidon_circuit (constraint_system/src/plonk_with_poseidon.rs:522-629) turns the circuit into the
  * two components of the next proof.  Every column is canonical M31 u32, [column][row], rows in the order the prover holds
@@ -622,8 +668,14 @@ int rsv_trace_log_sizes(size_t n_rows, size_t n_flow, uint32_t* log_plonk, uint3
  * Poseidon output wire used more than once: RSV_E_RANGE.  Nothing is written unless RSV_OK. */
 int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
                            uint32_t log_poseidon, uint32_t* plonk_pre, uint32_t* poseidon_pre);
+/* The same for a circuit with public inputs: num_input is the reference's, 3 for the constants 1, i, j plus one per
+ * new_*(PublicInput); the public inputs are variables 1 .. num_input, each counted once more in the multiplicities.
+ * num_input < 3: RSV_E_RANGE.  rsv_trace_preprocessed is this with num_input = 3. */
+int rsv_trace_preprocessed_inputs(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
+                                  uint32_t log_poseidon, uint32_t num_input, uint32_t* plonk_pre, uint32_t* poseidon_pre);
 /* The TRACE columns of a batch, from what rsv_witness_eval_dev wrote (d_variables in the layout RSV_OPT_WITNESS_LAYOUT
- * names, d_flow / d_flow_swap, d_accept).  Built programs only (RSV_E_SIZE otherwise); the program's padded wires and
+ * names, d_flow / d_flow_swap, d_accept), or from a caller's own (rsv_circuit_program_create).  Programs with a gate list
+ * only: built or made from a circuit (RSV_E_SIZE otherwise), as for every later stage; the program's padded wires and
  * witness ops go to the device on the first call.  lp, lq = rsv_trace_log_sizes(gate rows, copies * flow_count).
  *   d_plonk [n][12][2^lp]: a_val, b_val, c_val (4 words each) = variables[wire[row]] (:571-618).
  *   d_poseidon [n][48][2^lq]: in[16], intermediate[16], out[16] of the six rows per invocation above: the state entering
@@ -664,7 +716,7 @@ int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, cons
  *
  * From the trace columns rsv_witness_trace_dev wrote (d_plonk [n][12][2^lp], d_poseidon [n][48][2^lq]), d_accept and the
  * lookup elements the next proof's transcript draws after trees 0 and 1, d_lookup [n][8]: z, then alpha (QM31 words; any
- * u32 is taken mod P).  Built programs only (RSV_E_SIZE otherwise); the program's 10 + 40 preprocessed columns, shared with
+ * u32 is taken mod P).  Programs with a gate list only (built, or made from a circuit: RSV_E_SIZE otherwise); the program's 10 + 40 preprocessed columns, shared with
  * rsv_witness_commit_dev, go to the device on the first call.  Outputs: d_int_plonk [n][8][2^lp], d_int_poseidon
  * [n][8][2^lq], d_sums [n][2][4] (the Plonk then the Poseidon claimed sum), d_ok [n] (may be NULL): 1 iff the proof was
  * accepted and no denominator of either component is zero.  A proof with d_ok[i] == 0 (rejected, or a zero denominator)
@@ -788,7 +840,7 @@ int rsv_witness_commit_caps_dev(rsv_ctx* ctx, const rsv_witness_program* prog, c
  * 1)][8] from rsv_witness_commit_caps_dev (RSV_CAP_READ), or NULL (RSV_CAP_NONE).  Outputs, with tree t's capacities
  * v_t, w from rsv_decommit_sizes (groups (lp, 10), (lq, 40); (lp, 12), (lq, 48); (lp, 8), (lq, 8)): d_values
  * [n][v_0 + v_1 + v_2] (a proof's three trees one after the other), d_n_values [n][3], d_witness [n][3][w][8],
- * d_n_witness [n][3].  Built programs only; refusals and alignment as rsv_witness_commit_dev and rsv_decommit_tree_dev. */
+ * d_n_witness [n][3].  Programs with a gate list only (built, or made from a circuit); refusals and alignment as rsv_witness_commit_dev and rsv_decommit_tree_dev. */
 int rsv_witness_decommit_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                              const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon,
                              const uint8_t* d_accept, const uint8_t* d_ok, size_t n, uint32_t log_blowup, const uint32_t* d_queries,
@@ -828,7 +880,7 @@ int rsv_sample_tree_dev(rsv_ctx* ctx, const rsv_commit_group* groups, size_t n_g
  * sample-minor: tree 0 at values 0..49 and tree 1 at 50..109, one value per column at the OODS point; tree 2 at
  * 110..133, per component columns 0..3 one value and the cumulative columns 4..7 two, first at the previous-row point
  * (the OODS point minus the step of CanonicCoset(the component's log size), formed on the device), then at the OODS
- * point.  Zeros for a masked proof.  Built programs only; refusals and alignment as rsv_witness_decommit_dev. */
+ * point.  Zeros for a masked proof.  Programs with a gate list only (built, or made from a circuit); refusals and alignment as rsv_witness_decommit_dev. */
 int rsv_witness_sample_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                            const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon,
                            const uint8_t* d_accept, const uint8_t* d_ok, size_t n, const uint32_t* d_oods, uint32_t* d_samples);
@@ -871,7 +923,7 @@ int rsv_composition_dev(rsv_ctx* ctx, uint32_t lp, uint32_t lq, const uint32_t* 
  *   per proof, mix root 3 and draw t: the OODS point ((1 - t^2) / (1 + t^2), 2 t / (1 + t^2)) to d_oods [n][8], x then y,
  *   the form rsv_witness_sample_dev takes, and the channel after the draw to d_channel;
  *   d_samples3 [n][8][4]: the eight columns at that point (sampled_values[3]).
- * A proof whose mask byte is 0 gets zeros in every output; its neighbours are unaffected.  Built programs only.  Refusals
+ * A proof whose mask byte is 0 gets zeros in every output; its neighbours are unaffected.  Programs with a gate list only (built, or made from a circuit).  Refusals
  * as rsv_witness_sample_dev and rsv_composition_dev; L3 + log_blowup above RSV_MAX_LOG_SIZE or log_blowup outside
  * 1 .. RSV_MAX_LOG_BLOWUP: RSV_E_SIZE. */
 int rsv_witness_tree3_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
@@ -950,7 +1002,7 @@ int rsv_fri_commit_dev(rsv_ctx* ctx, const uint32_t* d_quot, const uint32_t* siz
  * and words: rsv_fri_sizes) from tree 3's columns at the OODS point, and per tree 0, 1, 2 the Plonk and the Poseidon
  * columns at the OODS point and then the cumulative interaction columns 4..7 at the previous-row points (formed on the
  * device); then rsv_fri_commit_dev's outputs.  d_quot and d_layers stay with the caller for the openings.  A masked proof
- * gets zeros in every output and a zeroed channel.  Built programs only.  Refusals as rsv_witness_tree3_dev and
+ * gets zeros in every output and a zeroed channel.  Programs with a gate list only (built, or made from a circuit).  Refusals as rsv_witness_tree3_dev and
  * rsv_fri_commit_dev. */
 int rsv_witness_fri_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_plonk, const uint32_t* d_poseidon,
                         const uint32_t* d_ops, const uint32_t* d_int_plonk, const uint32_t* d_int_poseidon, const uint8_t* d_accept,

@@ -237,6 +237,11 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_trace_groups_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rsv_trace_log_sizes": (ctypes.c_int, [sz, sz, _u32p, _u32p]),
         "rsv_trace_preprocessed": (ctypes.c_int, [_u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p]),
+        "rsv_trace_preprocessed_inputs": (ctypes.c_int, [_u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, _u32p, _u32p]),
+        "rsv_circuit_program_create": (ctypes.c_int, [_u32p, sz, _u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                                      ctypes.POINTER(ctypes.c_void_p)]),
+        "rsv_circuit_check_dev": (ctypes.c_int, [vp, vp, vp, sz, vp, vp]),
+        "rsv_circuit_flow_dev": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp]),
         "rsv_witness_trace_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rsv_witness_trace": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u32p,
                                              _u8p, _u8p, ctypes.c_int]),
@@ -332,6 +337,7 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_fri_cap_sizes", "rsv_fri_commit_cap_dev", "rsv_witness_fri_caps_dev", "rsv_fri_open_cap_dev",
            "rsv_fri_commit_tail_dev", "rsv_witness_fri_tail_dev",
            "rsv_proof_bytes", "rsv_proof_pack_dev",
+           "rsv_trace_preprocessed_inputs", "rsv_circuit_program_create", "rsv_circuit_check_dev", "rsv_circuit_flow_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -644,6 +650,8 @@ class WitnessProgram:
     library's mirror of the reference's circuit gadgets over a template proof (rsv_witness_program_build);
     WitnessProgram(program) loads arrays made earlier (witness_program.Program, e.g. from a file)."""
 
+    num_input = 3  # the recursion circuit allocates no public input
+
     def __init__(self, program=None, device: int = 0, _handle=None):
         self._h = None
         if _handle is not None:
@@ -719,14 +727,7 @@ class WitnessProgram:
         """The 10 Plonk and 40 Poseidon preprocessed columns (rsv_trace_preprocessed): uint32[10, 2^lp], uint32[40, 2^lq].
         With `variables` (uint32[n_vars, 4] of one proof of the shape) `op` is that proof's, as gates(variables) sets it."""
         rows, _ = self.gates(variables)
-        wires = np.ascontiguousarray(self.export().flow_wires, dtype=np.uint32)
-        rows = np.ascontiguousarray(rows)
-        lp, lq = trace_log_sizes(len(rows), len(wires))
-        plonk = np.zeros((10, 1 << lp), np.uint32)
-        poseidon = np.zeros((40, 1 << lq), np.uint32)
-        _check(lib.rsv_trace_preprocessed(rows.ctypes.data_as(_u32p), len(rows), wires.ctypes.data_as(_u32p), len(wires), lp, lq,
-                                          plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p)), "rsv_trace_preprocessed")
-        return plonk, poseidon
+        return trace_preprocessed(rows, self.export().flow_wires, num_input=self.num_input)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -752,6 +753,37 @@ class WitnessProgram:
         out = ctypes.c_size_t(0)
         _check(lib.rsv_witness_group_scratch_bytes(self._h, n_groups, ctypes.byref(out)), "rsv_witness_group_scratch_bytes")
         return int(out.value)
+
+
+class Circuit(WitnessProgram):
+    """A caller's own Plonk-with-Poseidon circuit as the chain's program (rsv_circuit_program_create): gates uint32[n_rows, 6]
+    = a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31 (unpadded), flow_wires uint32[n_flow, 5] = the wires of
+    r1..r4 and the swap address, witness_ops uint32[n, 3] = (row, bit variable, constant) or None — the arrays
+    WitnessProgram.gates() and export() return.  num_input is the reference's: 3 for the constants 1, i, j plus one per
+    public input; the public inputs are variables 1 .. num_input.  It has no instructions: the witness is the caller's
+    (Chain.load), and what evaluates one refuses it."""
+
+    def __init__(self, gates, flow_wires, n_vars: int, num_input: int = 3, witness_ops=None, device: int = 0):
+        self._h = None
+        g, w = _u32(gates, (-1, 6)), _u32(flow_wires, (-1, 5))
+        ops = _u32(witness_ops if witness_ops is not None else [], (-1, 3))
+        h = ctypes.c_void_p()
+        _check(lib.rsv_circuit_program_create(g.ctypes.data_as(_u32p), len(g), w.ctypes.data_as(_u32p), len(w),
+                                              ops.ctypes.data_as(_u32p) if len(ops) else None, len(ops), n_vars, num_input, device,
+                                              ctypes.byref(h)), "rsv_circuit_program_create")
+        self.num_input = num_input
+        super().__init__(_handle=h)
+
+    def export(self):
+        """-> witness_program.Program with no instructions: the shape and the flow wires."""
+        s = self.shape
+        wires = np.zeros((s.flow_count, 5), np.uint32)
+        levels = np.zeros(1, np.uint32)
+        _check(lib.rsv_witness_program_export(self._h, None, levels.ctypes.data_as(_u32p), wires.ctypes.data_as(_u32p)),
+               "rsv_witness_program_export")
+        shape = dict(zip(witness_program.SHAPE_KEYS, (s.log_size_plonk, s.log_size_poseidon, s.pow_bits, s.log_blowup, s.log_last, s.n_queries,
+                                              s.n_inner, s.flow_count, s.copies)))
+        return witness_program.Program(np.zeros((0, 8), np.uint32), levels, self.n_vars, shape, wires)
 
 
 def _witness_batch(proofs: Sequence[bytes], program: WitnessProgram, inputs):
@@ -784,6 +816,19 @@ def trace_log_sizes(n_rows: int, n_flow: int):
     lp, lq = ctypes.c_uint32(0), ctypes.c_uint32(0)
     _check(lib.rsv_trace_log_sizes(n_rows, n_flow, ctypes.byref(lp), ctypes.byref(lq)), "rsv_trace_log_sizes")
     return int(lp.value), int(lq.value)
+
+
+def trace_preprocessed(gates, flow_wires, log_plonk=None, log_poseidon=None, num_input: int = 3):
+    """The 10 Plonk and 40 Poseidon preprocessed columns of a circuit (rsv_trace_preprocessed_inputs): uint32[10, 2^lp],
+    uint32[40, 2^lq], at trace_log_sizes' log sizes unless larger ones are given.  num_input: 3 plus the public inputs."""
+    rows, wires = _u32(gates, (-1, 6)), _u32(flow_wires, (-1, 5))
+    lp, lq = trace_log_sizes(len(rows), len(wires))
+    lp, lq = lp if log_plonk is None else log_plonk, lq if log_poseidon is None else log_poseidon
+    plonk = np.zeros((10, 1 << lp), np.uint32)
+    poseidon = np.zeros((40, 1 << lq), np.uint32)
+    _check(lib.rsv_trace_preprocessed_inputs(rows.ctypes.data_as(_u32p), len(rows), wires.ctypes.data_as(_u32p), len(wires), lp, lq, num_input,
+                                             plonk.ctypes.data_as(_u32p), poseidon.ctypes.data_as(_u32p)), "rsv_trace_preprocessed_inputs")
+    return plonk, poseidon
 
 
 def witness_trace(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_INPUTS, device: int = 0):
@@ -1167,6 +1212,22 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_witness_trace_dev(self._h, program._h, ptr(d_variables), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(), n,
                                          ptr(d_plonk), ptr(d_poseidon), ptr(d_ops)), "rsv_witness_trace_dev")
+
+    def circuit_check(self, program: WitnessProgram, d_variables, n: int, d_ok, d_bad_row):
+        """rsv_circuit_check_dev: the reference's check_arithmetics over n witnesses (d_variables in the context's
+        witness_layout); d_ok uint8[n] is cleared where a row fails (a proof with 0 on entry is skipped), d_bad_row
+        uint32[n] = the smallest failing row or 0xffffffff; enqueued on the context's stream."""
+        self.acquire_from_torch()
+        _check(lib.rsv_circuit_check_dev(self._h, program._h, d_variables.data_ptr(), n, d_ok.data_ptr(), d_bad_row.data_ptr()),
+               "rsv_circuit_check_dev")
+
+    def circuit_flow(self, program: WitnessProgram, d_variables, n: int, d_flow, d_flow_swap, d_ok, d_bad_flow):
+        """rsv_circuit_flow_dev: the reference's check_poseidon_invocations, and the flow: d_flow uint32[n, n_flow, 32]
+        (in: the halves without a wire; out: every word) and d_flow_swap uint8[n, n_flow]; d_ok and d_bad_flow as
+        circuit_check's; enqueued on the context's stream."""
+        self.acquire_from_torch()
+        _check(lib.rsv_circuit_flow_dev(self._h, program._h, d_variables.data_ptr(), n, d_flow.data_ptr(), d_flow_swap.data_ptr(),
+                                        d_ok.data_ptr(), d_bad_flow.data_ptr()), "rsv_circuit_flow_dev")
 
     def witness_groups(self, program: WitnessProgram, d_blob, d_offsets, n_groups: int, d_variables, d_accept, d_member_accept,
                        d_member_reason=None, inputs=STANDARD_INPUTS, d_flow=None, d_flow_swap=None):

@@ -10,11 +10,11 @@ next level takes as it is.
 """
 import numpy as np
 
-from . import (CAP_NONE, CAP_READ, ProofParts, composition_log_size, decommit_sizes, fri_cap_sizes, fri_open_sizes, fri_sizes, pack,
+from . import (CAP_NONE, CAP_READ, Circuit, ProofParts, composition_log_size, decommit_sizes, fri_cap_sizes, fri_open_sizes, fri_sizes, pack,
                proof_bytes_bound, proof_list, witness_decommit_sizes)
 
 _FLAGS = ("acc", "ok", "low_degree", "member_accept", "member_reason")
-_WRITTEN = ("acc", "member_accept", "member_reason", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
+_WRITTEN = ("acc", "bad_row", "bad_flow", "member_accept", "member_reason", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
             "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree", "fri_caps",
             "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3",
             "fri_witness", "n_fri_witness", "fri_hash_witness", "n_fri_hash_witness")
@@ -76,12 +76,15 @@ class Chain:
     of at most 2^h leaves only; fri_tail_log = t (1 .. 10) runs fri()'s commit phase in the tail form (the same outputs through
     fewer launches).  aggregate=True: n is the number of GROUPS of program.shape.copies proofs; copy c of group g's circuit
     verifies proof g * copies + c of the batch witness() takes, every tensor and the next proof are per group, and
-    member_accept, member_reason [n, copies] hold the members' own verdicts."""
+    member_accept, member_reason [n, copies] hold the members' own verdicts.  With a Circuit as the program the chain
+    starts at load() instead of witness(), and there is no aggregation."""
 
     def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, fri_tail_log=0, device="cuda:0",
                  aggregate=False):
         self.ctx, self.program, self.n, self.log_blowup, self.log_last = ctx, program, n, log_blowup, log_last
         self.aggregate = aggregate
+        if aggregate and isinstance(program, Circuit):
+            raise ValueError("Chain: aggregate=True needs a built program, not a Circuit")
         self.fill, self.with_caps, self.fri_sub_log, self.fri_tail_log, self.device = fill, caps, fri_sub_log, fri_tail_log, device
         self.lp, self.lq = program.trace_sizes()
         self.n_ops = len(program.gates()[1])
@@ -108,6 +111,8 @@ class Chain:
         and int64[n + 1], what pack() returns), which are used as they are; by_variable: the context's witness_layout
         option is "by_variable".  With aggregate: n * copies proofs, group after group."""
         import torch
+        if isinstance(self.program, Circuit):
+            raise ValueError("Chain.witness() evaluates the recursion circuit: a Circuit's witness comes through load()")
         blob, offsets = pack(proofs_or_blob) if isinstance(proofs_or_blob, list) else proofs_or_blob
         n, wp = self.n, self.program
         if torch.is_tensor(blob):
@@ -126,6 +131,38 @@ class Chain:
         else:
             self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
             self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
+        self.done = {"witness"}
+
+    def load(self, variables, flow=None, swap=None, check=True, by_variable=False):
+        """The caller's witnesses in the place of witness(): variables uint32[n, n_vars, 4] ([n_vars, n, 4] with
+        by_variable: the context's witness_layout option is "by_variable"), flow uint32[n, n_flow, 32] and swap
+        uint8[n, n_flow] (None: zeros); numpy arrays, or device tensors, which are used as they are (the flow is written).
+        check=True: Context.circuit_check and circuit_flow — acc is 1 where both of the reference's checks pass, bad_row
+        and bad_flow [n] hold the first failing row and invocation (all ones: none), and the flow is the one
+        circuit_flow made from `variables` and the halves without a wire.  check=False: everything is taken as given
+        and acc is ones.  Not with aggregate."""
+        import torch
+        if self.aggregate:
+            raise ValueError("Chain.load() is not for aggregate=True")
+        n, wp = self.n, self.program
+        F = wp.shape.copies * wp.shape.flow_count
+
+        def dev(x, shape, dtype):
+            if x is None:
+                return torch.zeros(shape, dtype=dtype, device=self.device)
+            if not torch.is_tensor(x):
+                x = np.ascontiguousarray(x, np.uint8 if dtype == torch.uint8 else np.uint32)
+                x = torch.from_numpy(x if dtype == torch.uint8 else x.view(np.int32)).to(self.device)
+            if tuple(x.shape) != shape or x.dtype != dtype or not x.is_contiguous():
+                raise ValueError(f"Chain.load(): a contiguous {dtype} tensor of shape {shape} is needed, not {x.dtype} {tuple(x.shape)}")
+            return x
+        self._vars = dev(variables, (wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4), torch.int32)
+        self._flow, self._swap = dev(flow, (n, F, 32), torch.int32), dev(swap, (n, F), torch.uint8)
+        self.acc = torch.ones(n, dtype=torch.uint8, device=self.device)
+        if check:
+            self.bad_row, self.bad_flow = self._new(n), self._new(n)
+            self.ctx.circuit_check(wp, self._vars, n, self.acc, self.bad_row)
+            self.ctx.circuit_flow(wp, self._vars, n, self._flow, self._swap, self.acc, self.bad_flow)
         self.done = {"witness"}
 
     def trace(self, plonk=True, poseidon=True, ops=True):

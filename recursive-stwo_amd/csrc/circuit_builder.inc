@@ -77,7 +77,7 @@ int rsv_witness_program_info(const rsv_witness_program* prog, uint32_t* n_vars, 
 
 int rsv_witness_program_export(const rsv_witness_program* prog, uint32_t* instr, uint32_t* level_offsets, uint32_t* flow_wires) {
     if (!prog) return RSV_E_NULL;
-    if (instr) {
+    if (instr && prog->n_instr) {
         if (prog->h_instr.empty()) {  // created from the caller's arrays: the copy lives on the device
             if (select_device(prog->device) != RSV_OK) return RSV_E_DEVICE;
             HIP_TRY(hipMemcpy(instr, prog->d_instr, (size_t)prog->n_instr * 32, hipMemcpyDeviceToHost));

@@ -403,7 +403,7 @@ int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, con
                        uint8_t* ok, uint8_t* accept, uint8_t* reason, int device) {
     if (!prog || (n && (!blob || !offsets || !roots || !draws || !sums || !accept))) return RSV_E_NULL;
     if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_commit_dev
+    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
     if (n == 0) return RSV_OK;
     WitnessStage st;
     int rc = st.open(offsets, n, device, true);

@@ -93,7 +93,7 @@ int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob
                             const rsv_public_input* pi, size_t n_pi, const uint32_t* lookup, uint32_t* int_plonk, uint32_t* int_poseidon,
                             uint32_t* sums, uint8_t* ok, uint8_t* accept, uint8_t* reason, int device) {
     if (!prog || (n && (!blob || !offsets || !lookup || !int_plonk || !int_poseidon || !sums || !accept))) return RSV_E_NULL;
-    if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_interaction_dev
+    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
     if (n == 0) return RSV_OK;
     WitnessStage st;
     int rc = st.open(offsets, n, device, true);

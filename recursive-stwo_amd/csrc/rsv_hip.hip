@@ -36,6 +36,7 @@
 #include "k_pow.hpp"
 #include "k_fri_open.hpp"
 #include "k_pack.hpp"
+#include "k_user_circuit.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -537,3 +538,4 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "pow_api.inc"
 #include "fri_open_api.inc"
 #include "pack_api.inc"
+#include "user_circuit_api.inc"

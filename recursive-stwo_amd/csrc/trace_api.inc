@@ -4,7 +4,7 @@
 
 namespace {
 
-// The program's device copies, each uploaded once (built programs only: RSV_E_SIZE otherwise): the padded wires and the
+// The program's device copies, each uploaded once (programs with a gate list only: RSV_E_SIZE otherwise): the padded wires and the
 // witness ops, then, with `with_pre`, the 10 + 40 preprocessed columns that the interaction relations and tree 0 read.
 int program_upload(rsv_witness_program* prog, bool with_pre) {
     std::lock_guard<std::mutex> lk(prog->trace_mu);
@@ -43,7 +43,7 @@ int program_upload(rsv_witness_program* prog, bool with_pre) {
     try {
         pre.resize(rsv::trace::PLONK_PRE_COLS * N + rsv::trace::POSEIDON_PRE_COLS * Q);
         rc = rsv::trace::preprocessed(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5, lp, lq,
-                                      rsv::RC_FULL_K, rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, pre.data(),
+                                      prog->num_input, rsv::RC_FULL_K, rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, pre.data(),
                                       pre.data() + rsv::trace::PLONK_PRE_COLS * N);
     } catch (const std::bad_alloc&) {
         return RSV_E_NOMEM;
@@ -78,9 +78,15 @@ int rsv_trace_log_sizes(size_t n_rows, size_t n_flow, uint32_t* log_plonk, uint3
 
 int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
                            uint32_t log_poseidon, uint32_t* plonk_pre, uint32_t* poseidon_pre) {
+    return rsv_trace_preprocessed_inputs(gates, n_rows, flow_wires, n_flow, log_plonk, log_poseidon, rsv::trace::NUM_INPUT, plonk_pre,
+                                         poseidon_pre);
+}
+
+int rsv_trace_preprocessed_inputs(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
+                                  uint32_t log_poseidon, uint32_t num_input, uint32_t* plonk_pre, uint32_t* poseidon_pre) {
     try {
-        return rsv::trace::preprocessed(gates, n_rows, flow_wires, n_flow, log_plonk, log_poseidon, rsv::RC_FULL_K, rsv::RC_PARTIAL_K,
-                                        rsv::RC_FULL_K + 4, plonk_pre, poseidon_pre);
+        return rsv::trace::preprocessed(gates, n_rows, flow_wires, n_flow, log_plonk, log_poseidon, num_input, rsv::RC_FULL_K,
+                                        rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, plonk_pre, poseidon_pre);
     } catch (const std::bad_alloc&) {
         return RSV_E_NOMEM;
     }
@@ -98,7 +104,7 @@ static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint
         return RSV_E_SIZE;
     int rc = chain_begin(c, prog, n, false);
     if (rc != RSV_OK) return rc;
-    if (grouped && n > (1u << 20) / prog->shape.copies) return RSV_E_SIZE;  // (a built program has at least one copy)
+    if (grouped && (prog->copy_of.empty() || n > (1u << 20) / prog->shape.copies)) return RSV_E_SIZE;  // built programs only (they have at least one copy)
     if (n == 0) return RSV_OK;
     const rsv_witness_shape& s = prog->shape;
     rsv::TraceArgs a{};
@@ -153,7 +159,7 @@ int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, cons
                       const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,
                       uint8_t* reason, int device) {
     if (!prog || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
-    if (prog->gates.empty() || n > (1u << 20)) return RSV_E_SIZE;  // built programs only, as rsv_witness_trace_dev
+    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
     if (n == 0) return RSV_OK;
     WitnessStage st;
     int rc = st.open(offsets, n, device, true);

@@ -27,8 +27,9 @@ constexpr uint32_t POSEIDON_IS_FIRST = 0, POSEIDON_IS_LAST = 1, POSEIDON_ROUND_I
                    POSEIDON_EXT_WIRE_1 = 36, POSEIDON_EXT_WIRE_2 = 37, POSEIDON_EXT_NZ_1 = 38, POSEIDON_EXT_NZ_2 = 39;
 constexpr uint32_t ROWS_PER_INVOCATION = 6;
 // The constraint system starts with four constant variables (0, 1, i, j) and one row each (plonk_with_poseidon.rs:95-
-// 137); num_input counts the three non-zero ones.  components/recursive allocates no public input (only components/last
-// calls new_public_input), so num_input stays 3: rsv_trace_preprocessed checks the four rows rather than assume them.
+// 137); num_input counts the three non-zero ones and every new_*(PublicInput) after them: the public inputs are
+// variables 1 .. num_input.  components/recursive allocates no public input (only components/last calls
+// new_public_input), so the recursion circuit's num_input is 3, which rsv_trace_preprocessed passes.
 constexpr uint32_t NUM_INPUT = 3;
 constexpr uint32_t MAX_WIRE = 1u << 26;  // rsv_witness_program_create's bound on n_vars
 
@@ -66,10 +67,11 @@ inline std::vector<uint32_t> padded_wires(const uint32_t* gates, size_t n_rows, 
 }
 
 // gates [n_rows][6] = a, b, c, op, poseidon_wire, enforce_c_m31; flow_wires [n_flow][5] = wires of r1..r4, swap address;
-// round constants: first [4][16], partial [14], last [4][16].  plonk_pre [10][2^log_plonk], poseidon_pre [40][2^log_poseidon].
+// num_input: see NUM_INPUT (RSV_E_RANGE below 3 or beyond the variables the arrays name); round constants: first [4][16],
+// partial [14], last [4][16].  plonk_pre [10][2^log_plonk], poseidon_pre [40][2^log_poseidon].
 // Everything is checked before anything is written: on an error status the outputs are untouched.
 inline int preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
-                        uint32_t log_poseidon, const uint32_t (*rc_first)[16], const uint32_t* rc_partial, const uint32_t (*rc_last)[16],
+                        uint32_t log_poseidon, uint32_t num_input, const uint32_t (*rc_first)[16], const uint32_t* rc_partial, const uint32_t (*rc_last)[16],
                         uint32_t* plonk_pre, uint32_t* poseidon_pre) {
     if (!gates || !flow_wires || !plonk_pre || !poseidon_pre || !rc_first || !rc_partial || !rc_last) return RSV_E_NULL;
     uint32_t need_lp = 0, need_lq = 0;
@@ -78,11 +80,12 @@ inline int preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* fl
     if (log_plonk < need_lp || log_poseidon < need_lq || log_plonk > RSV_MAX_WITNESS_LOG || log_poseidon > RSV_MAX_WITNESS_LOG)
         return RSV_E_SIZE;
     if (n_rows < 4) return RSV_E_RANGE;
-    for (uint32_t k = 0; k < 4; k++) {  // the four constant rows (k, 0, k, op 1): num_input = 3
+    if (num_input < NUM_INPUT || num_input >= MAX_WIRE) return RSV_E_RANGE;
+    for (uint32_t k = 0; k < 4; k++) {  // the four constant rows (k, 0, k, op 1)
         const uint32_t* g = gates + (size_t)k * 6;
         if (g[0] != k || g[1] != 0 || g[2] != k || g[3] != 1 || g[4] != 0 || g[5] != 0) return RSV_E_RANGE;
     }
-    uint32_t n_vars = 4;
+    uint32_t n_vars = num_input + 1;
     for (size_t i = 0; i < n_rows; i++)
         for (int k : {0, 1, 2, 4}) {
             const uint32_t w = gates[i * 6 + k];
@@ -101,7 +104,7 @@ inline int preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t* fl
     for (size_t i = 0; i < n_rows; i++)
         for (int k = 0; k < 3; k++) counts[gates[i * 6 + k]]++;
     counts[0] += 3 * (int64_t)(N - n_rows);
-    for (uint32_t k = 1; k <= NUM_INPUT; k++) counts[k]++;
+    for (uint32_t k = 1; k <= num_input; k++) counts[k]++;
     for (size_t f = 0; f < n_flow; f++) counts[flow_wires[f * 5 + 4]]++;
     counts[0] += (int64_t)(n_pad - n_flow);
     std::vector<uint32_t> mult(3 * N, 1);  // mult_a, mult_b, mult_c: 1, except 1 - count at a variable's first use

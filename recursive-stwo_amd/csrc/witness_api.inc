@@ -27,6 +27,12 @@ struct rsv_witness_program {
     // rsv_witness_eval_groups_dev: the copy that allocated each variable [n_vars] (built programs only; circuit_program.hpp)
     std::vector<uint8_t> copy_of;
     uint8_t* d_copy_of = nullptr;
+    // rsv_circuit_program_create (user_circuit_api.inc): a caller's circuit has no instructions (n_instr = 0), and the
+    // witness entry points refuse it; num_input is the reference's (3 for a built program: the recursion circuit has no
+    // public input).  rsv_circuit_check_dev / rsv_circuit_flow_dev: the row and flow source tables (user_circuit_host.hpp).
+    uint32_t num_input = 3;
+    uint32_t* d_uc_rows = nullptr;
+    uint32_t* d_uc_flow = nullptr;
 };
 
 namespace {
@@ -236,6 +242,8 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
     if (p->d_trace_pre) (void)hipFree(p->d_trace_pre);
     if (p->d_copy_of) (void)hipFree(p->d_copy_of);
+    if (p->d_uc_rows) (void)hipFree(p->d_uc_rows);
+    if (p->d_uc_flow) (void)hipFree(p->d_uc_flow);
     delete p;
 }
 
@@ -264,6 +272,7 @@ static WitnessScratch witness_carve(const rsv_witness_program* prog, char* base,
 
 int rsv_witness_scratch_bytes(const rsv_witness_program* prog, size_t n, size_t* bytes) {
     if (!prog || !bytes) return RSV_E_NULL;
+    if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit: nothing evaluates its witness
     *bytes = witness_carve(prog, nullptr, n, n, true).bytes;  // under RSV_OPT_WITNESS_LAYOUT = 2 the variables are not held twice: n * n_vars * 16 less
     return RSV_OK;
 }
@@ -335,7 +344,7 @@ int rsv_witness_eval_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint
                          uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason) {
     if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
     if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if ((uintptr_t)d_flow & 15) return RSV_E_SIZE;
+    if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;  // (a caller's circuit has no instructions)
     if (n == 0) return RSV_OK;
     if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
     if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
@@ -386,6 +395,7 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
                      uint8_t* reason, int device) {
     if (!prog || (n && (!blob || !offsets || !variables || !accept))) return RSV_E_NULL;
     if ((flow == nullptr) != (flow_swap == nullptr)) return RSV_E_NULL;
+    if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit
     if (n == 0) return RSV_OK;
     if (n > (1u << 20)) return RSV_E_SIZE;
     WitnessStage st;
