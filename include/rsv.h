@@ -206,6 +206,8 @@ typedef enum rsv_option {
     RSV_OPT_CAP_MID = 26,         /* with the cap's top in kernels of its own (RSV_OPT_CAP_TOP): 0 auto — a bucket of proofs whose dense cap levels
                                      fill the tree kernels' waves badly (80, 27, 11, 10 queries) hands its nodes over at the cap level, a
                                      lane per subtree walks the middle levels (k_cap_mid), k_cap_top the rest; 1 every bucket does, 2 none */
+    RSV_OPT_CIRCUIT_EVAL_FORM = 30, /* rsv_circuit_eval_dev: 0 auto (by batch size), 1 one launch per level of the evaluation program, 2 one
+                                     launch in which a workgroup per witness walks the levels */
     /* 15, 27, 28, 29: retired; rsv_ctx_set_option answers RSV_E_SIZE */
     RSV_OPT_CAP_TOP = 19          /* 0 auto (batches of >= 1 024 proofs), 1 the last two or three levels of every Merkle tree in a
                                      kernel of their own (one lane per tree), 2 inside the tree kernels (dense top-of-tree cap) */
@@ -641,6 +643,66 @@ int rsv_circuit_check_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const u
                           uint32_t* d_bad_row);
 int rsv_circuit_flow_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, uint32_t* d_flow,
                          uint8_t* d_flow_swap, uint8_t* d_ok, uint32_t* d_bad_flow);
+
+/* ---- a caller's circuit evaluated on the GPU: `variables` and the flow from the free inputs ---------------------------
+ * rsv_circuit_program_create_eval is rsv_circuit_program_create — the same checks first, with the same statuses, the same
+ * program (no verifier instructions: what evaluates the recursion circuit's witness still refuses it) — which beside
+ * that compiles the circuit into an EVALUATION program: one definition per variable, and the levels in which
+ * rsv_circuit_eval_dev runs them.  The caller then gives, per witness, only n_inputs free QM31 inputs.
+ *   hints [n_hints][4] = (dst variable, kind, src variable, imm): what the gate list cannot say.  RSV_HINT_INPUT: dst =
+ *     slot `imm` (< n_inputs) of the witness's input buffer; public inputs are ordinary inputs.  The other kinds are the
+ *     hints of the reference's gadgets, computed from variable src: COPY dst = src; INV and INV0 dst = (1 / src.x, 0, 0, 0)
+ *     with 1 / 0 = 0; QINV dst = 1 / src in QM31 (0 for 0); CINV dst = (coordinate imm (0, 1) of 1 / (src.x + src.y i),
+ *     0, 0, 0) (0 for 0); COORD dst = (word imm (0..3) of src, 0, 0, 0); BIT dst = (bit imm (0..31) of src.x, 0, 0, 0).
+ *   flow_links [n_flow][2], or NULL for none: the source of an input half r1 / r2 that has no wire.  0: the 8 words the
+ *     caller left in d_flow (rsv_circuit_flow_dev's convention); 1 + 2 k' + h': output half h' (0: r3, 1: r4) of invocation
+ *     k' — the reference's "ignored output fed to the next permutation", which never becomes a variable.
+ * Every variable gets exactly ONE definition, by the first of these rules that applies:
+ *   1. variables 0..3 are the constants 0, 1, i, j;
+ *   2. a variable that is the dst of a hint is defined by that hint;
+ *   3. take the row that carries the poseidon_wire named as r3 or r4 of an invocation: its a_wire is words 0..3 and its
+ *      b_wire words 4..7 of that output half (in the reference these are fresh witnesses filled from the permutation);
+ *   4. the first row in row order with c_wire == v, a_wire != v and b_wire != v defines v = op (a + b) + (1 - op) a b, where
+ *      at a witness-op row op is the row's constant if variables[bit].x != 0 and 0 otherwise.
+ * An input half with a wire is (variables[a_wire], variables[b_wire]) of its row, as in rsv_circuit_flow_dev.
+ * Instructions and invocations are the nodes of one dependency graph: an instruction depends on the definitions of its
+ * operands (at a witness-op row: and of the bit), an invocation on those of its bound input variables, of its swap
+ * variable and on its linked invocations, a rule-3 variable on its invocation.  A node's level is the longest path to it;
+ * a rule-3 variable is written by its invocation and so is ready with that invocation's level.  No invocation is
+ * renumbered: flow record k stays invocation k.
+ * Refusals beyond rsv_circuit_program_create's (out is untouched): hints NULL with a count: RSV_E_NULL; n_inputs above
+ * 2^26: RSV_E_SIZE; RSV_E_RANGE for a hint's dst or src >= n_vars, an unknown kind, an imm or slot out of range, a hint on
+ * a variable 0..3, two hints for one dst, a variable that rule 3 matches twice, a variable without a definition, a link
+ * on a half that has a wire, with k' >= n_flow or k' == k, a dependency cycle. */
+enum { RSV_HINT_INPUT, RSV_HINT_COPY, RSV_HINT_INV, RSV_HINT_INV0, RSV_HINT_QINV, RSV_HINT_CINV, RSV_HINT_COORD, RSV_HINT_BIT };
+int rsv_circuit_program_create_eval(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow,
+                                    const uint32_t* witness_ops, size_t n_witness_ops, uint32_t n_vars, uint32_t num_input,
+                                    const uint32_t* hints, size_t n_hints, const uint32_t* flow_links, uint32_t n_inputs, int device,
+                                    rsv_witness_program** out);
+/* The compiled evaluation program (RSV_E_SIZE for a program without one; any pointer may be NULL).  n_instr = n_vars less
+ * the rule-3 variables.  _export: instr [n_instr][8] = op, dst, a, b, imm0..3 in rsv_witness_program_create's layout, level
+ * after level (ops 0..10 as there; 32: dst = inputs[imm0]; 33: the general gate, op = imm0, or with imm2 = 1 imm0 where
+ * variables[imm1].x != 0 and 0 otherwise); level_offsets [n_levels + 1] into instr; flow_order [n_flow], the invocations
+ * level after level; flow_level_offsets [n_levels + 1] into flow_order. */
+int rsv_circuit_eval_info(const rsv_witness_program* prog, uint32_t* n_inputs, uint32_t* n_levels, uint32_t* n_instr);
+int rsv_circuit_eval_export(const rsv_witness_program* prog, uint32_t* instr, uint32_t* level_offsets, uint32_t* flow_order,
+                            uint32_t* flow_level_offsets);
+/* Evaluates n witnesses of a program made by rsv_circuit_program_create_eval (RSV_E_SIZE otherwise) from d_inputs
+ * [n][n_inputs][4] (16-byte aligned): d_variables in the layout RSV_OPT_WITNESS_LAYOUT names, d_flow [n][n_flow][32]
+ * (IN/OUT: the input halves with neither a wire nor a link are read from their place) and d_flow_swap [n][n_flow].  For a
+ * witness with d_ok[i] != 0 on entry every word of the three is written; a witness skipped on entry is left untouched.
+ * An input word >= P clears d_ok[i] and leaves the smallest offending slot in d_bad_input[i] (0xffffffff otherwise; the
+ * word counts as 0 in what is written).  The swap bit is variables[swap address].x & 1 (0 for address 0).  The call does
+ * not judge satisfiability: rsv_circuit_check_dev and rsv_circuit_flow_dev do, on what this call wrote.  Refusals before
+ * any device work: a NULL pointer (d_inputs may be NULL with n_inputs = 0): RSV_E_NULL; a program without an evaluation
+ * program or of another device, n above 2^20, a level too wide for one launch at this n, a pointer not 16-byte (d_bad_input:
+ * 4-byte) aligned: RSV_E_SIZE.  Enqueued on the context's stream with no host synchronisation; the program's tables go to
+ * the device on the first call.  RSV_OPT_CIRCUIT_EVAL_FORM selects between one launch per level and one launch in which a
+ * workgroup per witness walks the levels; both write the same words.  The call needs no scratch of the context:
+ * rsv_circuit_eval_scratch_bytes answers 0 (RSV_E_SIZE for a program without an evaluation program). */
+int rsv_circuit_eval_scratch_bytes(const rsv_witness_program* prog, size_t n, size_t* bytes);
+int rsv_circuit_eval_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_inputs, size_t n, uint32_t* d_variables,
+                         uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_ok, uint32_t* d_bad_input);
 
 /* ---- the columns the next prover commits: 22 Plonk + 88 Poseidon ----------------------------------------------------
  * generate_plonk_with_poseidon_circuit (constraint_system/src/plonk_with_poseidon.rs:522-629) turns the circuit into the

@@ -242,6 +242,12 @@ def _load() -> ctypes.CDLL:
                                                       ctypes.POINTER(ctypes.c_void_p)]),
         "rsv_circuit_check_dev": (ctypes.c_int, [vp, vp, vp, sz, vp, vp]),
         "rsv_circuit_flow_dev": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp]),
+        "rsv_circuit_program_create_eval": (ctypes.c_int, [_u32p, sz, _u32p, sz, _u32p, sz, ctypes.c_uint32, ctypes.c_uint32, _u32p, sz, _u32p,
+                                                           ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+        "rsv_circuit_eval_info": (ctypes.c_int, [vp, _u32p, _u32p, _u32p]),
+        "rsv_circuit_eval_export": (ctypes.c_int, [vp, _u32p, _u32p, _u32p, _u32p]),
+        "rsv_circuit_eval_scratch_bytes": (ctypes.c_int, [vp, sz, ctypes.POINTER(sz)]),
+        "rsv_circuit_eval_dev": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp]),
         "rsv_witness_trace_dev": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "rsv_witness_trace": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u32p,
                                              _u8p, _u8p, ctypes.c_int]),
@@ -338,6 +344,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_fri_commit_tail_dev", "rsv_witness_fri_tail_dev",
            "rsv_proof_bytes", "rsv_proof_pack_dev",
            "rsv_trace_preprocessed_inputs", "rsv_circuit_program_create", "rsv_circuit_check_dev", "rsv_circuit_flow_dev",
+           "rsv_circuit_program_create_eval", "rsv_circuit_eval_info", "rsv_circuit_eval_export", "rsv_circuit_eval_scratch_bytes",
+           "rsv_circuit_eval_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -364,8 +372,11 @@ def device_count() -> int:
 OPTIONS = {"transcript_form": 1, "transcript_split": 2, "oods_form": 3, "qconst_form": 4, "plan_form": 5, "tree_cap": 6,
            "overlap_trees": 7, "ws_budget_mb": 8, "perm_wg_per_cu": 9, "host_chunk_mb": 10, "host_threads": 11, "debug_log": 12,
            "critical_chain": 13, "device_order": 14,
-           "witness_layout": 16, "witness_small_max": 17, "witness_small_log": 18, "cap_top": 19, "witness_walk_log": 20, "flow_cap": 21, "pair_order": 22, "tree_pace": 23, "stage_times": 24, "query_form": 25, "cap_mid": 26}
-OPTION_VALUES = {"auto": 0, "row": 1, "lane": 2, "paced": 1, "unpaced": 2, "row16": 3, "whole": 1, "split": 2, "parallel": 1, "serial": 2, "on": 1, "off": 2, "device": 1, "host": 2,
+           "witness_layout": 16, "witness_small_max": 17, "witness_small_log": 18, "cap_top": 19, "witness_walk_log": 20, "flow_cap": 21, "pair_order": 22, "tree_pace": 23, "stage_times": 24, "query_form": 25, "cap_mid": 26,
+           "circuit_eval_form": 30}
+#: the hint kinds of rsv_circuit_program_create_eval (RSV_HINT_*)
+HINT_KINDS = {"input": 0, "copy": 1, "inv": 2, "inv_or_zero": 3, "qinv": 4, "cinv": 5, "coord": 6, "bit": 7}
+OPTION_VALUES = {"auto": 0, "per_level": 1, "walk": 2, "row": 1, "lane": 2, "paced": 1, "unpaced": 2, "row16": 3, "whole": 1, "split": 2, "parallel": 1, "serial": 2, "on": 1, "off": 2, "device": 1, "host": 2,
                  "by_proof": 1, "by_variable": 2}
 
 
@@ -761,18 +772,54 @@ class Circuit(WitnessProgram):
     r1..r4 and the swap address, witness_ops uint32[n, 3] = (row, bit variable, constant) or None — the arrays
     WitnessProgram.gates() and export() return.  num_input is the reference's: 3 for the constants 1, i, j plus one per
     public input; the public inputs are variables 1 .. num_input.  It has no instructions: the witness is the caller's
-    (Chain.load), and what evaluates one refuses it."""
+    (Chain.load), and what evaluates the recursion circuit's refuses it.  With hints uint32[n_hints, 4] = (dst, kind, src,
+    imm) — HINT_KINDS names the kinds —, flow_links uint32[n_flow, 2] or None and n_inputs it is made by
+    rsv_circuit_program_create_eval and also holds an evaluation program: Chain.evaluate computes the witnesses on the
+    device from their n_inputs free inputs (rsv.h has the rule by which every variable gets its definition)."""
 
-    def __init__(self, gates, flow_wires, n_vars: int, num_input: int = 3, witness_ops=None, device: int = 0):
+    def __init__(self, gates, flow_wires, n_vars: int, num_input: int = 3, witness_ops=None, device: int = 0, hints=None, flow_links=None,
+                 n_inputs: int = 0):
         self._h = None
         g, w = _u32(gates, (-1, 6)), _u32(flow_wires, (-1, 5))
         ops = _u32(witness_ops if witness_ops is not None else [], (-1, 3))
         h = ctypes.c_void_p()
-        _check(lib.rsv_circuit_program_create(g.ctypes.data_as(_u32p), len(g), w.ctypes.data_as(_u32p), len(w),
-                                              ops.ctypes.data_as(_u32p) if len(ops) else None, len(ops), n_vars, num_input, device,
-                                              ctypes.byref(h)), "rsv_circuit_program_create")
+        lead = (g.ctypes.data_as(_u32p), len(g), w.ctypes.data_as(_u32p), len(w), ops.ctypes.data_as(_u32p) if len(ops) else None, len(ops),
+                n_vars, num_input)
+        if hints is None:
+            _check(lib.rsv_circuit_program_create(*lead, device, ctypes.byref(h)), "rsv_circuit_program_create")
+        else:
+            hi = _u32(hints, (-1, 4))
+            links = None if flow_links is None else _u32(flow_links, (-1, 2))
+            if links is not None and len(links) != len(w):
+                raise ValueError("Circuit: flow_links needs one pair per invocation")
+            _check(lib.rsv_circuit_program_create_eval(*lead, hi.ctypes.data_as(_u32p) if len(hi) else None, len(hi),
+                                                       links.ctypes.data_as(_u32p) if links is not None else None, n_inputs, device,
+                                                       ctypes.byref(h)), "rsv_circuit_program_create_eval")
+            #: bool[n_flow, 2]: the input halves r1, r2 with neither a wire nor a link, which rsv_circuit_eval_dev reads from d_flow
+            self.flow_free = (w[:, :2] == 0) & ((links if links is not None else np.zeros((len(w), 2), np.uint32)) == 0)
         self.num_input = num_input
         super().__init__(_handle=h)
+
+    def eval_info(self):
+        """(n_inputs, n_levels, n_instr) of the evaluation program (rsv_circuit_eval_info); RsvError where there is none."""
+        out = [ctypes.c_uint32(0) for _ in range(3)]
+        _check(lib.rsv_circuit_eval_info(self._h, *(ctypes.byref(x) for x in out)), "rsv_circuit_eval_info")
+        return tuple(int(x.value) for x in out)
+
+    def eval_export(self):
+        """-> (instr uint32[n_instr, 8], level_offsets uint32[n_levels + 1], flow_order uint32[n_flow], flow_level_offsets
+        uint32[n_levels + 1]): the evaluation program as compiled (rsv_circuit_eval_export)."""
+        _, n_levels, n_instr = self.eval_info()
+        instr, levels = np.zeros((n_instr, 8), np.uint32), np.zeros(n_levels + 1, np.uint32)
+        order, flevels = np.zeros(self.shape.flow_count, np.uint32), np.zeros(n_levels + 1, np.uint32)
+        _check(lib.rsv_circuit_eval_export(self._h, instr.ctypes.data_as(_u32p), levels.ctypes.data_as(_u32p), order.ctypes.data_as(_u32p),
+                                           flevels.ctypes.data_as(_u32p)), "rsv_circuit_eval_export")
+        return instr, levels, order, flevels
+
+    def eval_scratch_bytes(self, n: int) -> int:
+        out = ctypes.c_size_t(0)
+        _check(lib.rsv_circuit_eval_scratch_bytes(self._h, n, ctypes.byref(out)), "rsv_circuit_eval_scratch_bytes")
+        return int(out.value)
 
     def export(self):
         """-> witness_program.Program with no instructions: the shape and the flow wires."""
@@ -1228,6 +1275,17 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_circuit_flow_dev(self._h, program._h, d_variables.data_ptr(), n, d_flow.data_ptr(), d_flow_swap.data_ptr(),
                                         d_ok.data_ptr(), d_bad_flow.data_ptr()), "rsv_circuit_flow_dev")
+
+    def circuit_eval(self, program: WitnessProgram, d_inputs, n: int, d_variables, d_flow, d_flow_swap, d_ok, d_bad_input):
+        """rsv_circuit_eval_dev: n witnesses of a Circuit made with hints from d_inputs uint32[n, n_inputs, 4] (None with
+        no inputs): d_variables (in the context's witness_layout), d_flow uint32[n, n_flow, 32] (in: the halves with neither
+        a wire nor a link) and d_flow_swap uint8[n, n_flow] are written for every witness with d_ok != 0; d_ok is cleared
+        where an input word is not below P, d_bad_input uint32[n] = the smallest such slot or 0xffffffff; enqueued on the
+        context's stream (the option circuit_eval_form: "auto", "per_level", "walk")."""
+        self.acquire_from_torch()
+        _check(lib.rsv_circuit_eval_dev(self._h, program._h, d_inputs.data_ptr() if d_inputs is not None else None, n, d_variables.data_ptr(),
+                                        d_flow.data_ptr(), d_flow_swap.data_ptr(), d_ok.data_ptr(), d_bad_input.data_ptr()),
+               "rsv_circuit_eval_dev")
 
     def witness_groups(self, program: WitnessProgram, d_blob, d_offsets, n_groups: int, d_variables, d_accept, d_member_accept,
                        d_member_reason=None, inputs=STANDARD_INPUTS, d_flow=None, d_flow_swap=None):

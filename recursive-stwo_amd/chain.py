@@ -14,7 +14,7 @@ from . import (CAP_NONE, CAP_READ, Circuit, ProofParts, composition_log_size, de
                proof_bytes_bound, proof_list, witness_decommit_sizes)
 
 _FLAGS = ("acc", "ok", "low_degree", "member_accept", "member_reason")
-_WRITTEN = ("acc", "bad_row", "bad_flow", "member_accept", "member_reason", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
+_WRITTEN = ("acc", "bad_row", "bad_flow", "bad_input","member_accept", "member_reason", "plonk", "poseidon", "ops", "roots", "draws", "int_plonk", "int_poseidon", "sums", "channel", "ok", "caps", "comp", "root3",
             "oods", "samples3", "cap3", "samples", "after", "quot", "fri_roots", "alphas", "layers", "last_poly", "low_degree", "fri_caps",
             "nonce", "queries", "queries_low", "values", "n_values", "witness_nodes", "n_witness", "values3", "n_values3", "witness3", "n_witness3",
             "fri_witness", "n_fri_witness", "fri_hash_witness", "n_fri_hash_witness")
@@ -77,7 +77,8 @@ class Chain:
     fewer launches).  aggregate=True: n is the number of GROUPS of program.shape.copies proofs; copy c of group g's circuit
     verifies proof g * copies + c of the batch witness() takes, every tensor and the next proof are per group, and
     member_accept, member_reason [n, copies] hold the members' own verdicts.  With a Circuit as the program the chain
-    starts at load() instead of witness(), and there is no aggregation."""
+    starts at load() (the caller's witnesses) or evaluate() (the witnesses computed on the device from their free
+    inputs) instead of witness(), and there is no aggregation."""
 
     def __init__(self, ctx, program, n, log_blowup, *, log_last=None, fill=0, caps=False, fri_sub_log=0, fri_tail_log=0, device="cuda:0",
                  aggregate=False):
@@ -159,6 +160,44 @@ class Chain:
         self._vars = dev(variables, (wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4), torch.int32)
         self._flow, self._swap = dev(flow, (n, F, 32), torch.int32), dev(swap, (n, F), torch.uint8)
         self.acc = torch.ones(n, dtype=torch.uint8, device=self.device)
+        if check:
+            self.bad_row, self.bad_flow = self._new(n), self._new(n)
+            self.ctx.circuit_check(wp, self._vars, n, self.acc, self.bad_row)
+            self.ctx.circuit_flow(wp, self._vars, n, self._flow, self._swap, self.acc, self.bad_flow)
+        self.done = {"witness"}
+
+    def evaluate(self, inputs, flow_in=None, check=True, by_variable=False, mask=None):
+        """The witnesses computed on the device in the place of load(), for a Circuit made with hints
+        (Context.circuit_eval): inputs uint32[n, n_inputs, 4], the free inputs of every witness; flow_in uint32[n, n_flow,
+        32] or None: the input halves with neither a wire nor a link (the other words are not read); mask uint8[n] or None:
+        0 skips a witness.  numpy arrays, or device tensors.  The variables ([n_vars, n, 4] with by_variable: the context's
+        witness_layout option is "by_variable"), the flow and the swap bytes are the chain's own, prefilled with `fill`
+        where flow_in gives no word: a skipped witness keeps the prefill.  acc is cleared, and bad_input [n] names the
+        smallest slot, where an input word is not below P (all ones: none).  check=True: then Context.circuit_check and
+        circuit_flow as in load(): acc, bad_row, bad_flow.  Not with aggregate."""
+        import torch
+        if self.aggregate:
+            raise ValueError("Chain.evaluate() is not for aggregate=True")
+        n, wp = self.n, self.program
+        n_inputs = wp.eval_info()[0]
+        F = wp.shape.flow_count
+
+        def dev(x, shape, dtype):
+            if not torch.is_tensor(x):
+                x = np.ascontiguousarray(x, np.uint8 if dtype == torch.uint8 else np.uint32)
+                x = torch.from_numpy(x if dtype == torch.uint8 else x.view(np.int32)).to(self.device)
+            if tuple(x.shape) != shape or x.dtype != dtype or not x.is_contiguous():
+                raise ValueError(f"Chain.evaluate(): a contiguous {dtype} tensor of shape {shape} is needed, not {x.dtype} {tuple(x.shape)}")
+            return x
+        d_inputs = dev(inputs, (n, n_inputs, 4), torch.int32) if n_inputs else None
+        self._vars = self._new(*((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4)))
+        self._flow, self._swap = self._new(n, F, 32), self._new(n, F, flag=True)
+        if flow_in is not None:
+            free = torch.from_numpy(np.repeat(wp.flow_free, 8, axis=1)).to(self.device)     # [F, 16]: the words that are read
+            self._flow[:, :, :16] = torch.where(free[None], dev(flow_in, (n, F, 32), torch.int32)[:, :, :16], self._flow[:, :, :16])
+        self.acc = torch.ones(n, dtype=torch.uint8, device=self.device) if mask is None else dev(mask, (n,), torch.uint8).clone()
+        self.bad_input = self._new(n)
+        self.ctx.circuit_eval(wp, d_inputs, n, self._vars, self._flow, self._swap, self.acc, self.bad_input)
         if check:
             self.bad_row, self.bad_flow = self._new(n), self._new(n)
             self.ctx.circuit_check(wp, self._vars, n, self.acc, self.bad_row)

@@ -37,6 +37,7 @@
 #include "k_fri_open.hpp"
 #include "k_pack.hpp"
 #include "k_user_circuit.hpp"
+#include "circuit_eval_host.hpp"
 #include "trace_host.hpp"
 
 using namespace rsv;
@@ -67,6 +68,7 @@ struct Options {
     long long witness_small_max = 0;  // 0 default, else 1 + the largest batch that runs the program in one launch
     int witness_small_log = 0;        // 0 default, else 1 + log2(proofs per workgroup) of that form
     int witness_walk_log = 0;         // level form: 0 auto, 1 off, else 1 + log2(proofs per workgroup) of the one-launch tail
+    int circuit_eval_form = 0;        // rsv_circuit_eval_dev: 0 auto (by batch size), 1 a launch per level, 2 a workgroup per witness walks the levels
 };
 static Options g_default_options;
 static std::mutex g_options_mu;
@@ -290,6 +292,7 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_STAGE_TIMES: return tri(&o.stage_times);
         case RSV_OPT_QUERY_FORM: return tri(&o.query_form);
         case RSV_OPT_CAP_MID: return tri(&o.cap_mid);
+        case RSV_OPT_CIRCUIT_EVAL_FORM: return tri(&o.circuit_eval_form);
         case RSV_OPT_WITNESS_WALK_LOG:
             if (value < 0 || value > 7) return RSV_E_RANGE;
             o.witness_walk_log = (int)value; return RSV_OK;
@@ -539,3 +542,5 @@ int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint
 #include "fri_open_api.inc"
 #include "pack_api.inc"
 #include "user_circuit_api.inc"
+#include "k_circuit_eval.hpp"  // behind everything else, so that its kernels follow every earlier one in the library
+#include "circuit_eval_api.inc"

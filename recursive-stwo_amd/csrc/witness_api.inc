@@ -33,6 +33,13 @@ struct rsv_witness_program {
     uint32_t num_input = 3;
     uint32_t* d_uc_rows = nullptr;
     uint32_t* d_uc_flow = nullptr;
+    // rsv_circuit_program_create_eval (circuit_eval_api.inc): the evaluation program (circuit_eval_host.hpp; none where
+    // level_offsets is empty) and its device copies, uploaded by the first rsv_circuit_eval_dev: the instructions, then
+    // level_offsets | flow_level_offsets | flow_order in one array, then the flow table.
+    rsv::ceval::Program ce;
+    uint32_t* d_ce_instr = nullptr;
+    uint32_t* d_ce_index = nullptr;
+    uint32_t* d_ce_flow = nullptr;
 };
 
 namespace {
@@ -244,6 +251,9 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_copy_of) (void)hipFree(p->d_copy_of);
     if (p->d_uc_rows) (void)hipFree(p->d_uc_rows);
     if (p->d_uc_flow) (void)hipFree(p->d_uc_flow);
+    if (p->d_ce_instr) (void)hipFree(p->d_ce_instr);
+    if (p->d_ce_index) (void)hipFree(p->d_ce_index);
+    if (p->d_ce_flow) (void)hipFree(p->d_ce_flow);
     delete p;
 }
 
