@@ -15,7 +15,8 @@ namespace {
 // fewer instructions per level than this one only moves the crossover up.
 constexpr size_t CE_WALK_MAX = 1024;
 
-// The evaluation program's tables, uploaded by the first call (under trace_mu).
+// The evaluation program's instructions and index, uploaded by the first call (under trace_mu); the flow table is
+// uc_upload's.
 int ce_upload(rsv_witness_program* prog) {
     std::lock_guard<std::mutex> lk(prog->trace_mu);
     if (prog->d_ce_instr) return RSV_OK;
@@ -28,20 +29,16 @@ int ce_upload(rsv_witness_program* prog) {
     } catch (const std::bad_alloc&) {
         return RSV_E_NOMEM;
     }
-    uint32_t *di = nullptr, *dx = nullptr, *df = nullptr;
+    uint32_t *di = nullptr, *dx = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&di), e.instr.size() * 4) != hipSuccess ||
         hipMemcpy(di, e.instr.data(), e.instr.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
         hipMalloc(reinterpret_cast<void**>(&dx), index.size() * 4) != hipSuccess ||
-        hipMemcpy(dx, index.data(), index.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&df), e.flow.size() * 4) != hipSuccess ||
-        hipMemcpy(df, e.flow.data(), e.flow.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(dx, index.data(), index.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         if (di) (void)hipFree(di);
         if (dx) (void)hipFree(dx);
-        if (df) (void)hipFree(df);
         return RSV_E_DEVICE;
     }
     prog->d_ce_index = dx;
-    prog->d_ce_flow = df;
     prog->d_ce_instr = di;
     return RSV_OK;
 }
@@ -54,18 +51,17 @@ int rsv_circuit_program_create_eval(const uint32_t* gates, size_t n_rows, const 
                                     size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, const uint32_t* hints, size_t n_hints,
                                     const uint32_t* flow_links, uint32_t n_inputs, int device, rsv_witness_program** out) {
     if (!out) return RSV_E_NULL;
-    rsv_witness_program* p = nullptr;
     try {
         rsv::ceval::Program e;
-        int rc = rsv::ceval::compile(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, hints, n_hints,
-                                     flow_links, n_inputs, &e);
-        if (rc == RSV_OK) rc = rsv_circuit_program_create(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, device, &p);
+        const int rc = rsv::ceval::compile(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, hints, n_hints,
+                                           flow_links, n_inputs, &e);
         if (rc != RSV_OK) return rc;
+        rsv_witness_program* p = uc_new_program(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, device, std::move(e.tables));
         p->ce = std::move(e);
+        *out = p;
     } catch (const std::bad_alloc&) {
         return RSV_E_NOMEM;
     }
-    *out = p;
     return RSV_OK;
 }
 
@@ -117,14 +113,15 @@ int rsv_circuit_eval_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint
     if (input_blocks >= (1u << 31)) return RSV_E_SIZE;
     if (n == 0) return RSV_OK;
     HIP_TRY(hipSetDevice(c->device));
-    const int rc = ce_upload(const_cast<rsv_witness_program*>(prog));
+    int rc = uc_upload(const_cast<rsv_witness_program*>(prog));
+    if (rc == RSV_OK) rc = ce_upload(const_cast<rsv_witness_program*>(prog));
     if (rc != RSV_OK) return rc;
     rsv::CeArgs a{};
     a.instr = reinterpret_cast<const uint4*>(prog->d_ce_instr);
     a.levels = prog->d_ce_index;
     a.flevels = prog->d_ce_index + (n_levels + 1);
     a.forder = prog->d_ce_index + 2 * (n_levels + 1);
-    a.src = reinterpret_cast<const uint4*>(prog->d_ce_flow);
+    a.src = reinterpret_cast<const uint4*>(prog->d_uc_flow);
     a.n_levels = (uint32_t)n_levels;
     a.n_flow = (uint32_t)e.flow_order.size();
     a.n_vars = prog->n_vars;

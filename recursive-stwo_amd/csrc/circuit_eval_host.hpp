@@ -1,7 +1,8 @@
 // circuit_eval_host.hpp — HOST code, plain C++ (no HIP): a caller's circuit compiled into an EVALUATION program
 // (rsv_circuit_program_create_eval, include/rsv.h): from the gate list, the hints and the links between invocations, one
 // definition per variable, and the levels in which rsv_circuit_eval_dev (k_circuit_eval.hpp) runs the instructions and
-// the Poseidon invocations.  Included by k_circuit_eval.hpp; compiles on its own with g++ beside user_circuit_host.hpp, so
+// the Poseidon invocations.  The flow table is user_circuit_host.hpp's: compile() adds the define bits and the links to the
+// Tables check() resolved, and the program keeps them.  Included by k_circuit_eval.hpp; compiles on its own with g++ beside user_circuit_host.hpp, so
 // a sanitizer build can drive it without a device.
 //
 // The definition rule (rsv.h has it in full) follows how the reference's constraint system allocates variables
@@ -14,21 +15,18 @@
 #include <utility>
 #include <vector>
 
+#include "layout.hpp"
 #include "user_circuit_host.hpp"
 
 namespace rsv::ceval {
 
-// Instruction: 8 u32 = op, dst, a, b, imm0..3 (k_witness.hpp's layout).  Ops 0..10 are layout.hpp's W_CONST .. W_BIT by
-// number (k_circuit_eval.hpp asserts it); the two below are this program's own.
+// Instruction: 8 u32 = op, dst, a, b, imm0..3 (k_witness.hpp's layout).  The ops are layout.hpp's W_CONST .. W_BIT, which
+// every circuit kernel runs through one function (k_circuit_ops.hpp), and the two below, this program's own.
 //   E_INPUT  dst = inputs[imm0]
 //   E_GATE   dst = op (a + b) + (1 - op) a b; op = imm0, or with imm2 = 1 (a witness-op row): imm0 where variables[imm1].x != 0, else 0
-constexpr uint32_t E_CONST = 0, E_ADD = 1, E_MUL = 2, E_MULC = 3, E_COPY = 4, E_INV = 5, E_INV0 = 6, E_QINV = 7, E_CINV = 8, E_COORD = 9,
-                   E_BIT = 10, E_INPUT = 32, E_GATE = 33;
+constexpr uint32_t E_INPUT = 32, E_GATE = 33;
+static_assert(E_INPUT >= W_N_OPS, "E_INPUT and E_GATE lie above layout.hpp's ops");
 constexpr uint32_t INSTR_WORDS = 8;
-// Flow table, [n_flow][12] (three 16-byte loads per lane): (a_wire, b_wire) of the rows that carry r1 and r2; the variables
-// the output defines — words 0..3 and 4..7 of r3, then of r4, 0: none —; a mask with bit h set where input half h has a
-// wire; the swap address; the links of the input halves r1, r2 (0: none, else 1 + 2 k' + h').
-constexpr uint32_t FLOW_WORDS = 12, FLOW_OUT = 4, FLOW_MASK = 8, FLOW_SWAP_ADDR = 9, FLOW_LINK = 10;
 
 struct Program {
     uint32_t n_inputs = 0;
@@ -36,7 +34,7 @@ struct Program {
     std::vector<uint32_t> level_offsets;       // [n_levels + 1] into instr
     std::vector<uint32_t> flow_order;          // [n_flow]: the invocations, level after level
     std::vector<uint32_t> flow_level_offsets;  // [n_levels + 1] into flow_order
-    std::vector<uint32_t> flow;                // [n_flow][12]
+    ucircuit::Tables tables;                   // check()'s, the flow table with the define bits and the links filled in
     size_t n_levels() const { return level_offsets.empty() ? 0 : level_offsets.size() - 1; }
 };
 
@@ -71,23 +69,19 @@ inline int compile(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wi
         def[dst] = D_HINT;
         def_at[dst] = (uint32_t)i;
     }
+    using ucircuit::FLOW_WORDS, ucircuit::FLOW_MASK, ucircuit::FLOW_SWAP_ADDR, ucircuit::FLOW_LINK, ucircuit::FLOW_DEFINES;
     Program p;
     p.n_inputs = n_inputs;
-    p.flow.assign(n_flow * FLOW_WORDS, 0);
     for (size_t k = 0; k < n_flow; k++) {
-        const uint32_t* s = t.flow.data() + k * ucircuit::FLOW_WORDS;
-        uint32_t* r = p.flow.data() + k * FLOW_WORDS;
-        for (int q = 0; q < 4; q++) r[q] = s[q];
-        r[FLOW_MASK] = s[ucircuit::FLOW_MASK] & 3u;
-        r[FLOW_SWAP_ADDR] = s[ucircuit::FLOW_SWAP_ADDR];
+        uint32_t* r = t.flow.data() + k * FLOW_WORDS;
         for (uint32_t q = 0; q < 4; q++) {  // output quarter q: half 2 + q / 2, its row's a (q even) or b wire
-            if (!((s[ucircuit::FLOW_MASK] >> (2 + q / 2)) & 1u)) continue;
-            const uint32_t v = s[4 + q];
+            if (!((r[FLOW_MASK] >> (2 + q / 2)) & 1u)) continue;
+            const uint32_t v = r[4 + q];
             if (def[v] == D_FLOW) return RSV_E_RANGE;  // the output of two rows, or both wires of one
             if (def[v] != D_NONE) continue;            // a constant or a hinted variable stays what it is
             def[v] = D_FLOW;
             def_at[v] = (uint32_t)k * 4 + q;
-            r[FLOW_OUT + q] = v;
+            r[FLOW_MASK] |= 1u << (FLOW_DEFINES + q);
         }
         for (uint32_t h = 0; h < 2; h++) {
             const uint32_t link = flow_links ? flow_links[k * 2 + h] : 0;
@@ -111,7 +105,7 @@ inline int compile(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wi
     auto deps = [&](size_t node, size_t* d) -> int {
         int n = 0;
         if (node >= n_vars) {
-            const uint32_t* r = p.flow.data() + (node - n_vars) * FLOW_WORDS;
+            const uint32_t* r = t.flow.data() + (node - n_vars) * FLOW_WORDS;
             for (uint32_t h = 0; h < 2; h++) {
                 if ((r[FLOW_MASK] >> h) & 1u) { d[n++] = r[2 * h]; d[n++] = r[2 * h + 1]; }
                 else if (r[FLOW_LINK + h]) d[n++] = (size_t)n_vars + (r[FLOW_LINK + h] - 1) / 2;
@@ -183,11 +177,11 @@ inline int compile(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wi
         uint32_t* w = p.instr.data() + (size_t)at[level[v]]++ * INSTR_WORDS;
         w[1] = v;
         if (def[v] == D_CONST) {
-            w[0] = E_CONST;
+            w[0] = W_CONST;
             if (v) w[3 + v] = 1;  // 1, i, j
         } else if (def[v] == D_HINT) {
             const uint32_t* h = hints + (size_t)def_at[v] * 4;
-            constexpr uint32_t op_of[8] = {E_INPUT, E_COPY, E_INV, E_INV0, E_QINV, E_CINV, E_COORD, E_BIT};
+            constexpr uint32_t op_of[8] = {E_INPUT, W_COPY, W_INV, W_INV0, W_QINV, W_CINV, W_COORD, W_BIT};
             w[0] = op_of[h[1]];
             if (h[1] != RSV_HINT_INPUT) w[2] = h[2];
             if (h[1] == RSV_HINT_INPUT || h[1] >= RSV_HINT_CINV) w[4] = h[3];
@@ -198,12 +192,13 @@ inline int compile(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wi
             w[3] = b;
             if (t.rows[row * ucircuit::ROW_WORDS + 2] & ucircuit::ROW_WITNESS_OP) {
                 w[0] = E_GATE; w[4] = op; w[5] = t.rows[row * ucircuit::ROW_WORDS + 1]; w[6] = 1;
-            } else if (op == 1) w[0] = E_ADD;
-            else if (op == 0) w[0] = E_MUL;
-            else if (b == 0) { w[0] = E_MULC; w[3] = 0; w[4] = op; }
+            } else if (op == 1) w[0] = W_ADD;
+            else if (op == 0) w[0] = W_MUL;
+            else if (b == 0) { w[0] = W_MULC; w[3] = 0; w[4] = op; }
             else { w[0] = E_GATE; w[4] = op; }
         }
     }
+    p.tables = std::move(t);
     if (out) *out = std::move(p);
     return RSV_OK;
 }

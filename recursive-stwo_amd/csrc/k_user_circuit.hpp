@@ -16,7 +16,11 @@
 // vector per lane, ~40 multiplies, no store but the rare atomic.  Padding rows are not visited.  k_uc_flow: one lane per
 // (invocation, proof), a wave's 64 invocations belong to one proof; 48 B of source table, up to eight 16-byte gathers,
 // one out-of-line permutation (poseidon2(), the lane form: the state in registers), one 128-byte record.
+// The gate formula (gate_value) and the invocation (poseidon_invoke) are k_circuit_ops.hpp's, shared with k_circuit_eval.hpp,
+// and so is the flow table (user_circuit_host.hpp; k_uc_flow reads neither its define bits nor its links).  k_uc_flow's own:
+// the swap variable has to be the QM31 0 or 1, a bound output is compared with its pair, the failing invocation is reported.
 #pragma once
+#include "k_circuit_ops.hpp"
 #include "k_trace.hpp"
 #include "user_circuit_host.hpp"
 
@@ -38,12 +42,6 @@ struct UcArgs {
     uint8_t* swap;              // [n][n_flow] (out)
 };
 
-__device__ __forceinline__ uint4 uc_var(const UcArgs& a, uint32_t p, uint32_t w) {
-    return a.by_variable ? a.vars[(size_t)w * a.n + p] : a.vars[(size_t)p * a.n_vars + w];
-}
-__device__ __forceinline__ bool uc_canonical(uint4 v) { return v.x < P && v.y < P && v.z < P && v.w < P; }
-__device__ __forceinline__ QM31 uc_q(uint4 v) { return q_mk(v.x, v.y, v.z, v.w); }
-
 // Block b: proof b / per, rows (b % per) * 256 ..., per = ceil(n_rows / 256).
 __global__ __launch_bounds__(256) void k_uc_gates(UcArgs a) {
     const uint32_t per = (a.n_rows + 255) / 256;
@@ -51,14 +49,12 @@ __global__ __launch_bounds__(256) void k_uc_gates(UcArgs a) {
     if (p >= a.n || row >= a.n_rows || !a.ok[p]) return;
     const size_t N = (size_t)1 << a.log_plonk;
     const uint4 t = a.rows[row];
-    const uint4 va = uc_var(a, p, a.wires[row]), vb = uc_var(a, p, a.wires[N + row]), vc = uc_var(a, p, a.wires[2 * N + row]);
+    const auto var = [&](uint32_t w) { return var_at(a.vars, a.by_variable, a.n, a.n_vars, p, w); };
+    const uint4 va = var(a.wires[row]), vb = var(a.wires[N + row]), vc = var(a.wires[2 * N + row]);
     bool good = uc_canonical(va) && uc_canonical(vb) && uc_canonical(vc);
-    uint32_t op = t.x;
-    if (t.z & ucircuit::ROW_WITNESS_OP) op = uc_var(a, p, t.y).x ? t.x : 0u;
-    // op (a + b) + (1 - op) a b; words at or above P have failed already, what they give here is dropped
-    const QM31 qa = uc_q(va), qb = uc_q(vb);
-    const QM31 want = q_add(q_mul_m(q_add(qa, qb), op), q_mul_m(q_mul(qa, qb), m_sub(1u, op)));
-    good = good && q_eq(want, uc_q(vc));
+    // words at or above P have failed already, what they give here is dropped (computed whatever `good` is: no load waits for a verdict)
+    const QM31 want = gate_value(va, vb, t.x, t.z & ucircuit::ROW_WITNESS_OP, t.y, var);
+    good = good && q_eq(want, q_of(vc));
     if (t.z & ucircuit::ROW_M31) good = good && (vc.y | vc.z | vc.w) == 0;
     if (row < 4) good = good && va.x == (row == 1) && va.y == (row == 2) && va.z == (row == 3) && va.w == 0;  // variables 0..3 = 0, 1, i, j
     if (!good) atomicMin(a.bad + p, row);
@@ -79,39 +75,24 @@ __global__ __launch_bounds__(64) void k_uc_flow(UcArgs a) {
     }
     const uint4 s0 = a.src[(size_t)k * 3], s1 = a.src[(size_t)k * 3 + 1], s2 = a.src[(size_t)k * 3 + 2];
     const uint32_t wire[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w}, mask = s2.x, addr = s2.y;
-    bool good = true;
+    const auto var = [&](uint32_t w) { return var_at(a.vars, a.by_variable, a.n, a.n_vars, p, w); };
     uint4 in[4];  // r1, r2 as given: from `variables` where the half has a wire, else from the record
 #pragma unroll
-    for (int q = 0; q < 4; q++) {
-        in[q] = (mask >> (q >> 1)) & 1u ? uc_var(a, p, wire[q]) : f[q];
-        good = good && uc_canonical(in[q]);
-    }
+    for (int q = 0; q < 4; q++) in[q] = (mask >> (q >> 1)) & 1u ? var(wire[q]) : f[q];
+    bool good = true;
     uint32_t sw = 0;
     if (addr) {  // the swap bit has to be the QM31 0 or 1
-        const uint4 b = uc_var(a, p, addr);
-        good = good && b.x <= 1u && (b.y | b.z | b.w) == 0;
+        const uint4 b = var(addr);
+        good = b.x <= 1u && (b.y | b.z | b.w) == 0;
         sw = b.x & 1u;
     }
-    State16 st;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint4 v = sw ? in[(q + 2) & 3] : in[q];
-        if (!good) v = make_uint4(0, 0, 0, 0);  // the permutation takes canonical words only
-        st.s[4 * q] = v.x; st.s[4 * q + 1] = v.y; st.s[4 * q + 2] = v.z; st.s[4 * q + 3] = v.w;
-    }
-    st = poseidon2(st);
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint4 o = make_uint4(st.s[4 * q], st.s[4 * q + 1], st.s[4 * q + 2], st.s[4 * q + 3]);
-        if ((mask >> (2 + (q >> 1))) & 1u) {  // a bound output is its pair in `variables`
-            const uint4 v = uc_var(a, p, wire[4 + q]);
-            good = good && v.x == o.x && v.y == o.y && v.z == o.z && v.w == o.w;
-        }
-        f[q] = in[q];
-        f[4 + q] = o;
-    }
-    a.swap[rec] = (uint8_t)sw;
-    if (!good) atomicMin(a.bad + p, k);
+    bool bound = true;  // a bound output is its pair in `variables`
+    good = poseidon_invoke(in, sw, good, f, a.swap + rec, [&](int q, uint4 o) {
+        if (!((mask >> (2 + (q >> 1))) & 1u)) return;
+        const uint4 v = var(wire[4 + q]);
+        bound = bound && v.x == o.x && v.y == o.y && v.z == o.z && v.w == o.w;
+    });
+    if (!(good && bound)) atomicMin(a.bad + p, k);
 }
 
 __global__ __launch_bounds__(256) void k_uc_verdict(const uint32_t* __restrict__ bad, uint32_t n, uint8_t* __restrict__ ok) {

@@ -7,8 +7,10 @@
 // and writes 1 KB rows; the work is HBM streaming (3 x 16 B per instruction and proof), not arithmetic.
 // Hint instructions read what rsv_verify_hints_dev left behind: the proof words (through the parser's offsets), the
 // PoseidonFlow records (the permutation outputs are hints of the circuit), the per-query column values of the four
-// commitment trees and of the FRI trees.
+// commitment trees and of the FRI trees.  The ops W_CONST .. W_BIT are k_circuit_ops.hpp's circuit_op, which the evaluation
+// of a caller's circuit (k_circuit_eval.hpp) runs too; the ops from W_FLOW on, accept and the grouped indexing are this file's.
 #pragma once
+#include "k_circuit_ops.hpp"
 #include "verify_common.hpp"
 
 namespace rsv {
@@ -39,71 +41,44 @@ struct WitnessGroupArgs : WitnessArgs {
 template <class A> struct witness_grouped { static constexpr bool value = false; };
 template <> struct witness_grouped<WitnessGroupArgs> { static constexpr bool value = true; };
 
-__device__ __forceinline__ QM31 q_of(uint4 v) { return q_mk(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ uint4 u4_of(QM31 q) { return make_uint4(q.a.a, q.a.b, q.b.a, q.b.b); }
-__device__ __forceinline__ uint4 u4_words(const uint32_t* w) { return make_uint4(w[0], w[1], w[2], w[3]); }
-
 // one instruction (its eight words: w0 = op, dst, a, b; w1 = imm0..3) for one proof
 template <class A>
 __device__ __forceinline__ void witness_exec(const A& a, const uint4 w0, const uint4 w1, uint32_t p) {
-    const uint32_t op = w0.x, dst = w0.y, x = w0.z, y = w0.w, i0 = w1.x, i1 = w1.y, i2 = w1.z;
-    const size_t n = a.n;
-    uint4 r = make_uint4(0, 0, 0, 0);
+    const uint32_t op = w0.x, dst = w0.y, i0 = w1.x, i1 = w1.y, i2 = w1.z;
     const bool ok = a.accept[p] != 0;  // a rejected proof's sections may not be where the program expects them
     size_t q = p;                      // the proof a hint is read from: grouped, the group's member dst's copy verifies
     if constexpr (witness_grouped<A>::value)
         if (op >= W_FLOW && ok) q = (size_t)p * a.copies + a.copy_of[dst];
-    switch (op) {
-    case W_CONST: r = w1; break;
-    case W_ADD: r = u4_of(q_add(q_of(a.vars[x * n + p]), q_of(a.vars[y * n + p]))); break;
-    case W_MUL: r = u4_of(q_mul(q_of(a.vars[x * n + p]), q_of(a.vars[y * n + p]))); break;
-    case W_MULC: r = u4_of(q_mul_m(q_of(a.vars[x * n + p]), i0)); break;
-    case W_COPY: r = a.vars[x * n + p]; break;
-    case W_INV: r.x = m_inv(a.vars[x * n + p].x); break;  // 0 -> 0
-    case W_INV0: r.x = m_inv(a.vars[x * n + p].x); break;
-    case W_QINV: {
-        const uint4 v = a.vars[x * n + p];
-        if (v.x | v.y | v.z | v.w) r = u4_of(q_inv(q_of(v)));
-        break;
-    }
-    case W_CINV: {
-        const uint4 v = a.vars[x * n + p];
-        if (v.x | v.y) {
-            const CM31 c = c_inv(c_mk(v.x, v.y));
-            r.x = i0 ? c.b : c.a;
-        }
-        break;
-    }
-    case W_COORD: {
-        const uint4 v = a.vars[x * n + p];
-        r.x = i0 == 0 ? v.x : i0 == 1 ? v.y : i0 == 2 ? v.z : v.w;
-        break;
-    }
-    case W_BIT: r.x = (a.vars[x * n + p].x >> i0) & 1u; break;
-    case W_FLOW:
-        if (ok) r = a.flow[(q * a.flow_stride + i0) * 8 + (i1 >> 2)];
-        break;
-    default: {
-        if (!ok) break;
-        const ProofMeta& m = a.metas[q];
-        const uint32_t* w = reinterpret_cast<const uint32_t*>(a.blob + a.offsets[q]);
+    const auto hint = [&]() {  // the ops that read what the verifying pass left
+        uint4 r = make_uint4(0, 0, 0, 0);
         switch (op) {
-        case W_WORD: r.x = w[i0]; break;
-        case W_WORD4: r = u4_words(w + i0); break;
-        case W_FRI_COMMIT: r = u4_words(w + (i0 == 0 ? m.first.commit_off : m.inner[i0 - 1].commit_off) + 4 * i1); break;
-        case W_LAST_POLY: r = u4_words(w + m.last_off + 4 * i0); break;
-        case W_NONCE: {  // the 22 / 21 / 21-bit split of data_structures/src/lib.rs:197-213
-            const uint64_t nonce = (uint64_t)w[m.nonce_off] | ((uint64_t)w[m.nonce_off + 1] << 32);
-            r.x = i0 == 0 ? (uint32_t)(nonce & ((1u << 22) - 1)) : (uint32_t)((nonce >> (i0 == 1 ? 22 : 43)) & ((1u << 21) - 1));
+        case W_FLOW:
+            if (ok) r = a.flow[(q * a.flow_stride + i0) * 8 + (i1 >> 2)];
             break;
+        default: {
+            if (!ok) break;
+            const ProofMeta& m = a.metas[q];
+            const uint32_t* w = reinterpret_cast<const uint32_t*>(a.blob + a.offsets[q]);
+            switch (op) {
+            case W_WORD: r.x = w[i0]; break;
+            case W_WORD4: r = u4_words(w + i0); break;
+            case W_FRI_COMMIT: r = u4_words(w + (i0 == 0 ? m.first.commit_off : m.inner[i0 - 1].commit_off) + 4 * i1); break;
+            case W_LAST_POLY: r = u4_words(w + m.last_off + 4 * i0); break;
+            case W_NONCE: {  // the 22 / 21 / 21-bit split of data_structures/src/lib.rs:197-213
+                const uint64_t nonce = (uint64_t)w[m.nonce_off] | ((uint64_t)w[m.nonce_off + 1] << 32);
+                r.x = i0 == 0 ? (uint32_t)(nonce & ((1u << 22) - 1)) : (uint32_t)((nonce >> (i0 == 1 ? 22 : 43)) & ((1u << 21) - 1));
+                break;
+            }
+            case W_TRACE_COL: r.x = a.trace_cols[((q * 4 + i0) * a.nq + i1) * 64 + i2]; break;
+            case W_FRI_COL: r = u4_words(a.fri_cols + ((q * a.n_trees + i0) * a.nq + i1) * 24 + i2); break;
+            default: break;
+            }
         }
-        case W_TRACE_COL: r.x = a.trace_cols[((q * 4 + i0) * a.nq + i1) * 64 + i2]; break;
-        case W_FRI_COL: r = u4_words(a.fri_cols + ((q * a.n_trees + i0) * a.nq + i1) * 24 + i2); break;
-        default: break;
         }
-    }
-    }
-    a.vars[dst * n + p] = r;
+        return r;
+    };
+    const size_t n = a.n;
+    var_at(a.vars, true, n, 0, p, dst) = circuit_op(w0, w1, [&](uint32_t v) { return var_at(a.vars, true, n, 0, p, v); }, hint);
 }
 template <class A>
 __device__ __forceinline__ void witness_exec(const A& a, uint32_t i, uint32_t p) {

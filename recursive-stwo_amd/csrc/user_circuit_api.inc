@@ -5,19 +5,21 @@
 
 namespace {
 
-// The row and flow source tables, uploaded by the first of the two calls (behind program_upload's wires, under trace_mu).
+// The row and flow tables, uploaded by the first call that reads them (under trace_mu): a built program has none yet.
 int uc_upload(rsv_witness_program* prog) {
     std::lock_guard<std::mutex> lk(prog->trace_mu);
     if (prog->d_uc_rows) return RSV_OK;
-    rsv::ucircuit::Tables t;
-    int rc;
-    try {
-        rc = rsv::ucircuit::check(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5,
-                                  prog->witness_ops.data(), prog->witness_ops.size() / 3, prog->n_vars, prog->num_input, &t);
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
+    rsv::ucircuit::Tables& t = prog->uc;
+    if (t.rows.empty()) {
+        int rc;
+        try {
+            rc = rsv::ucircuit::check(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5,
+                                      prog->witness_ops.data(), prog->witness_ops.size() / 3, prog->n_vars, prog->num_input, &t);
+        } catch (const std::bad_alloc&) {
+            return RSV_E_NOMEM;
+        }
+        if (rc != RSV_OK) return rc;
     }
-    if (rc != RSV_OK) return rc;
     uint32_t *dr = nullptr, *df = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&dr), t.rows.size() * 4) != hipSuccess) return RSV_E_DEVICE;
     if (hipMemcpy(dr, t.rows.data(), t.rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
@@ -56,6 +58,23 @@ int uc_begin(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_vari
     return RSV_OK;
 }
 
+// The program of arrays that check() has passed, with the tables it resolved.  Throws std::bad_alloc.
+rsv_witness_program* uc_new_program(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, const uint32_t* witness_ops,
+                                    size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, int device, rsv::ucircuit::Tables&& tables) {
+    std::unique_ptr<rsv_witness_program> p(new rsv_witness_program());
+    p->device = device;
+    p->n_vars = n_vars;
+    p->num_input = num_input;
+    p->shape.flow_count = (uint32_t)n_flow;
+    p->shape.copies = 1;
+    p->level_offsets.assign(1, 0);  // no instructions, no levels
+    p->gates.assign(gates, gates + n_rows * 6);
+    p->flow_wires.assign(flow_wires, flow_wires + n_flow * 5);
+    if (n_witness_ops) p->witness_ops.assign(witness_ops, witness_ops + n_witness_ops * 3);
+    p->uc = std::move(tables);
+    return p.release();
+}
+
 }  // namespace
 
 extern "C" {
@@ -63,25 +82,14 @@ extern "C" {
 int rsv_circuit_program_create(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, const uint32_t* witness_ops,
                                size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, int device, rsv_witness_program** out) {
     if (!out) return RSV_E_NULL;
-    rsv_witness_program* p = nullptr;
     try {
-        int rc = rsv::ucircuit::check(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, nullptr);
+        rsv::ucircuit::Tables t;
+        const int rc = rsv::ucircuit::check(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, &t);
         if (rc != RSV_OK) return rc;
-        p = new rsv_witness_program();
-        p->device = device;
-        p->n_vars = n_vars;
-        p->num_input = num_input;
-        p->shape.flow_count = (uint32_t)n_flow;
-        p->shape.copies = 1;
-        p->level_offsets.assign(1, 0);  // no instructions, no levels
-        p->gates.assign(gates, gates + n_rows * 6);
-        p->flow_wires.assign(flow_wires, flow_wires + n_flow * 5);
-        if (n_witness_ops) p->witness_ops.assign(witness_ops, witness_ops + n_witness_ops * 3);
+        *out = uc_new_program(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, device, std::move(t));
     } catch (const std::bad_alloc&) {
-        delete p;
         return RSV_E_NOMEM;
     }
-    *out = p;
     return RSV_OK;
 }
 

@@ -1,7 +1,7 @@
 // user_circuit_host.hpp — HOST code, plain C++ (no HIP): a caller's own Plonk-with-Poseidon circuit as the chain's program
 // (rsv_circuit_program_create, include/rsv.h).  check() is everything the library asks of the arrays before it keeps
 // them, and, given `out`, resolves them into the two device tables rsv_circuit_check_dev / rsv_circuit_flow_dev read
-// (k_user_circuit.hpp).  Included by user_circuit_api.inc; compiles on its own with g++ beside trace_host.hpp, so a
+// (k_user_circuit.hpp) and, with what circuit_eval_host.hpp adds to the flow table, rsv_circuit_eval_dev (k_circuit_eval.hpp).  Included by user_circuit_api.inc; compiles on its own with g++ beside trace_host.hpp, so a
 // sanitizer build can drive it without a device.  The circuit_*.hpp files are something else: the library's mirror of the
 // reference's verifier gadgets.
 //
@@ -20,9 +20,12 @@ namespace rsv::ucircuit {
 // Row table, [n_rows][4] (one 16-byte load per lane): the row's op mod P — at a witness-op row the constant the op takes
 // when the bit is set —, the bit's variable, ROW_* flags, 0.
 constexpr uint32_t ROW_WORDS = 4, ROW_M31 = 1u, ROW_WITNESS_OP = 2u;
-// Flow source table, [n_flow][12] (three 16-byte loads per lane): (a_wire, b_wire) of the row that carries the
-// poseidon_wire of r1, r2, r3, r4 (zeros for wire 0), a mask with bit h set where half h has a wire, the swap address, 0, 0.
-constexpr uint32_t FLOW_WORDS = 12, FLOW_MASK = 8, FLOW_SWAP_ADDR = 9;
+// Flow table, [n_flow][12] (three 16-byte loads per lane), the one table of k_uc_flow and of the evaluation kernels:
+// (a_wire, b_wire) of the row that carries the poseidon_wire of r1, r2, r3, r4 (zeros for wire 0), a mask with bit h set
+// where half h has a wire, the swap address, then what only an evaluation program has (check() leaves zeros,
+// ceval::compile fills them in, k_uc_flow reads neither): mask bit FLOW_DEFINES + q set where the invocation defines the
+// variable in word 4 + q, and the links of the input halves r1, r2 (0: none, else 1 + 2 k' + h').
+constexpr uint32_t FLOW_WORDS = 12, FLOW_MASK = 8, FLOW_SWAP_ADDR = 9, FLOW_LINK = 10, FLOW_DEFINES = 4;
 
 struct Tables {
     std::vector<uint32_t> rows, flow;

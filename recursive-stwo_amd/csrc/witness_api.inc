@@ -29,17 +29,19 @@ struct rsv_witness_program {
     uint8_t* d_copy_of = nullptr;
     // rsv_circuit_program_create (user_circuit_api.inc): a caller's circuit has no instructions (n_instr = 0), and the
     // witness entry points refuse it; num_input is the reference's (3 for a built program: the recursion circuit has no
-    // public input).  rsv_circuit_check_dev / rsv_circuit_flow_dev: the row and flow source tables (user_circuit_host.hpp).
+    // public input).  rsv_circuit_check_dev / rsv_circuit_flow_dev / rsv_circuit_eval_dev: the row and flow tables
+    // (user_circuit_host.hpp) — uc: as check() resolved them when the program was created, with the evaluation program's
+    // bits and links where it has one; empty for a built program, whose tables uc_upload resolves.
     uint32_t num_input = 3;
+    rsv::ucircuit::Tables uc;
     uint32_t* d_uc_rows = nullptr;
     uint32_t* d_uc_flow = nullptr;
     // rsv_circuit_program_create_eval (circuit_eval_api.inc): the evaluation program (circuit_eval_host.hpp; none where
     // level_offsets is empty) and its device copies, uploaded by the first rsv_circuit_eval_dev: the instructions, then
-    // level_offsets | flow_level_offsets | flow_order in one array, then the flow table.
+    // level_offsets | flow_level_offsets | flow_order in one array.
     rsv::ceval::Program ce;
     uint32_t* d_ce_instr = nullptr;
     uint32_t* d_ce_index = nullptr;
-    uint32_t* d_ce_flow = nullptr;
 };
 
 namespace {
@@ -253,7 +255,6 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_uc_flow) (void)hipFree(p->d_uc_flow);
     if (p->d_ce_instr) (void)hipFree(p->d_ce_instr);
     if (p->d_ce_index) (void)hipFree(p->d_ce_index);
-    if (p->d_ce_flow) (void)hipFree(p->d_ce_flow);
     delete p;
 }
 

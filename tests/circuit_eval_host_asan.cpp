@@ -16,6 +16,8 @@
 #include "../recursive-stwo_amd/csrc/circuit_eval_host.hpp"
 
 using namespace rsv::ceval;
+using namespace rsv::ucircuit;  // the flow table is user_circuit_host.hpp's; the ops below E_INPUT are layout.hpp's
+using rsv::W_ADD, rsv::W_MUL, rsv::W_MULC, rsv::W_CINV, rsv::W_COORD, rsv::W_BIT;
 
 #define REQUIRE(x)                                                          \
     do {                                                                    \
@@ -37,7 +39,9 @@ struct Circuit {
 // every index inside its array, every variable defined once, every read at a strictly lower level
 static void program_is_sound(const Circuit& c, const Program& p) {
     const size_t n_flow = c.flow.size() / 5, n_levels = p.n_levels(), n_instr = p.instr.size() / INSTR_WORDS;
-    REQUIRE(n_levels >= 1 && p.flow_level_offsets.size() == n_levels + 1 && p.flow_order.size() == n_flow && p.flow.size() == n_flow * FLOW_WORDS);
+    REQUIRE(n_levels >= 1 && p.flow_level_offsets.size() == n_levels + 1 && p.flow_order.size() == n_flow);
+    const std::vector<uint32_t>& flow = p.tables.flow;
+    REQUIRE(flow.size() == n_flow * FLOW_WORDS && p.tables.rows.size() == c.gates.size() / 6 * ROW_WORDS);
     REQUIRE(p.level_offsets[0] == 0 && p.level_offsets[n_levels] == n_instr && p.flow_level_offsets[0] == 0 && p.flow_level_offsets[n_levels] == n_flow);
     std::vector<int64_t> var_level(c.n_vars, -1), flow_level(n_flow, -1);
     for (size_t l = 0; l < n_levels; l++) {
@@ -51,10 +55,10 @@ static void program_is_sound(const Circuit& c, const Program& p) {
             const uint32_t k = p.flow_order[j];
             REQUIRE(k < n_flow && flow_level[k] < 0);
             flow_level[k] = (int64_t)l;
-            for (int q = 0; q < 4; q++) {
-                const uint32_t v = p.flow[k * FLOW_WORDS + FLOW_OUT + q];
-                if (!v) continue;
-                REQUIRE(v < c.n_vars && var_level[v] < 0);
+            for (int q = 0; q < 4; q++) {  // the variable output quarter q defines: word 4 + q where its define bit is set
+                if (!((flow[k * FLOW_WORDS + FLOW_MASK] >> (FLOW_DEFINES + q)) & 1u)) continue;
+                const uint32_t v = flow[k * FLOW_WORDS + 4 + q];
+                REQUIRE(v >= 4 && v < c.n_vars && var_level[v] < 0);
                 var_level[v] = (int64_t)l;
             }
         }
@@ -64,26 +68,28 @@ static void program_is_sound(const Circuit& c, const Program& p) {
         for (size_t i = p.level_offsets[l]; i < p.level_offsets[l + 1]; i++) {
             const uint32_t* w = p.instr.data() + i * INSTR_WORDS;
             const uint32_t op = w[0];
-            REQUIRE(op <= E_BIT || op == E_INPUT || op == E_GATE);
-            const bool two = op == E_ADD || op == E_MUL || op == E_GATE, one = two || (op >= E_MULC && op <= E_BIT);
+            REQUIRE(op <= W_BIT || op == E_INPUT || op == E_GATE);
+            const bool two = op == W_ADD || op == W_MUL || op == E_GATE, one = two || (op >= W_MULC && op <= W_BIT);
             if (one) REQUIRE(w[2] < c.n_vars && var_level[w[2]] < (int64_t)l);
             if (two) REQUIRE(w[3] < c.n_vars && var_level[w[3]] < (int64_t)l);
             if (op == E_GATE && w[6]) REQUIRE(w[5] < c.n_vars && var_level[w[5]] < (int64_t)l);
             if (op == E_INPUT) REQUIRE(w[4] < c.n_inputs);
-            if (op == E_CINV) REQUIRE(w[4] <= 1);
-            if (op == E_COORD) REQUIRE(w[4] <= 3);
-            if (op == E_BIT) REQUIRE(w[4] <= 31);
+            if (op == W_CINV) REQUIRE(w[4] <= 1);
+            if (op == W_COORD) REQUIRE(w[4] <= 3);
+            if (op == W_BIT) REQUIRE(w[4] <= 31);
         }
     }
     for (size_t k = 0; k < n_flow; k++) {
-        const uint32_t* r = p.flow.data() + k * FLOW_WORDS;
-        REQUIRE(r[FLOW_MASK] < 4 && r[FLOW_SWAP_ADDR] < c.n_vars);
+        const uint32_t* r = flow.data() + k * FLOW_WORDS;
+        REQUIRE(r[FLOW_MASK] < (16u << FLOW_DEFINES) && r[FLOW_SWAP_ADDR] < c.n_vars);
+        for (int q = 0; q < 4; q++)  // a define bit only on an output half that has a wire
+            if ((r[FLOW_MASK] >> (FLOW_DEFINES + q)) & 1u) REQUIRE((r[FLOW_MASK] >> (2 + q / 2)) & 1u);
         if (r[FLOW_SWAP_ADDR]) REQUIRE(var_level[r[FLOW_SWAP_ADDR]] < flow_level[k]);
         for (int h = 0; h < 2; h++) {
             if ((r[FLOW_MASK] >> h) & 1u) {
                 REQUIRE(r[2 * h] < c.n_vars && r[2 * h + 1] < c.n_vars && r[FLOW_LINK + h] == 0);
                 REQUIRE(var_level[r[2 * h]] < flow_level[k] && var_level[r[2 * h + 1]] < flow_level[k]);
-            } else if (r[FLOW_LINK + h]) {
+            } else if (r[FLOW_LINK + h]) {  // a link sits only on a half without a wire
                 const uint32_t from = (r[FLOW_LINK + h] - 1) / 2;
                 REQUIRE(from < n_flow && flow_level[from] < flow_level[k]);
             }
@@ -116,10 +122,15 @@ static int adversarial() {
     REQUIRE(c.run(&p) == RSV_OK);
     program_is_sound(c, p);
     REQUIRE(p.instr.size() / INSTR_WORDS == 15 - 4 && c.run(nullptr) == RSV_OK);
+    const uint32_t* r = p.tables.flow.data();  // invocation 0 defines 8 and 9, invocation 1 defines 12 and 13 and links r1 to 0's r4
+    REQUIRE(r[4] == 8 && r[5] == 9 && r[FLOW_MASK] == (5u | 3u << FLOW_DEFINES) && r[FLOW_LINK] == 0 && r[FLOW_LINK + 1] == 0);
+    r += FLOW_WORDS;
+    REQUIRE(r[4] == 12 && r[5] == 13 && r[FLOW_MASK] == (4u | 3u << FLOW_DEFINES) && r[FLOW_SWAP_ADDR] == 4 && r[FLOW_LINK] == 2 && r[FLOW_LINK + 1] == 0);
     const Program kept = p;
     auto refused = [&](const Circuit& bad, int code) {
         REQUIRE(bad.run(&p) == code);
-        REQUIRE(p.instr == kept.instr && p.flow == kept.flow && p.flow_order == kept.flow_order);  // nothing is written on a refusal
+        REQUIRE(p.instr == kept.instr && p.tables.flow == kept.tables.flow && p.tables.rows == kept.tables.rows &&
+                p.flow_order == kept.flow_order);  // nothing is written on a refusal
     };
     Circuit b = c; b.gates.clear(); refused(b, RSV_E_SIZE);                // user_circuit_host.hpp's checks come first
     b = c; b.n_vars = 14; refused(b, RSV_E_RANGE);
@@ -174,7 +185,7 @@ static int recorded(const char* path, uint64_t seed, int rounds) {
         const int rc = b.run(&pb);
         if (rc == RSV_OK) program_is_sound(b, pb);
         else {
-            REQUIRE((rc == RSV_E_RANGE || rc == RSV_E_SIZE) && pb.instr.empty() && pb.flow.empty());
+            REQUIRE((rc == RSV_E_RANGE || rc == RSV_E_SIZE) && pb.instr.empty() && pb.tables.flow.empty() && pb.tables.rows.empty());
             refusals++;
         }
     }

@@ -5,8 +5,8 @@ lanes 63 and 64 masked) that differ in seed, public input and witness bit, under
 variables, flow and swap are the oracle's, word for word, the chain's 0xffffffff prefill shows that no word of an accepted
 witness stays unwritten, and a skipped witness keeps the prefill.  2: input words at or above P.  3: a wrong free input is
 data — Chain.evaluate(check=True) names the row or invocation the numpy model of the reference's two checks names on the
-evaluated vector.  4: evaluate -> ... -> pack for S1 to S3 under both configurations of tests/test_user_circuit_gpu.py.  5:
-the level10-1 recursion circuit as a created evaluation program reproduces rsv_witness_eval_dev's vector and flow and the
+evaluated vector.  3b: a swap variable that is no bit, which the evaluation and the check treat differently.  4: evaluate
+-> ... -> pack for S1 to S3 under both configurations of tests/test_user_circuit_gpu.py.  5: the level10-1 recursion circuit as a created evaluation program reproduces rsv_witness_eval_dev's vector and flow and the
 chain puts out level11-1.bin byte for byte."""
 import numpy as np
 import pytest
@@ -141,6 +141,52 @@ def test_a_wrong_free_input_is_reported_by_the_checks(rsv, ctx, kind):
     a = ch.numpy()
     assert a["bad_input"].tolist() == [NONE] * 3 and a["bad_row"].tolist() == want_row and a["bad_flow"].tolist() == want_flow
     assert a["acc"].tolist() == [1, 0, 0]
+    circ.close()
+
+
+# ---------------------------------------------------------------- 3b. a swap variable that is no bit
+@pytest.mark.parametrize("form", FORMS)
+@pytest.mark.parametrize("layout", LAYOUTS)
+def test_a_swap_variable_that_is_no_bit(rsv, ctx, layout, form):
+    """The one thing the evaluation and the check do differently with the same invocation.  S1's swapped invocation; witness
+    0: the swap variable is 2, witness 1: it is 1 + 5 i, witness 2: untouched.  rsv_circuit_eval_dev takes the low bit of
+    the first coordinate, permutes, and keeps ok; rsv_circuit_flow_dev on the variables it wrote asks for the QM31 0 or 1:
+    it names the invocation, writes the record of a zero state and clears ok, for the first two witnesses only."""
+    import torch
+    b = witness("S1", 0)
+    circ = _circuit(rsv, b)
+    at = int(np.flatnonzero(b.flow_wires[:, 4])[0])
+    slot = _slot_of(b, int(b.flow_wires[at, 4]))
+    inputs, flow_in = np.stack([E.inputs_of(b)] * 3), np.stack([E.flow_in_of(b)] * 3)
+    inputs[0, slot] = (2, 0, 0, 0)
+    inputs[1, slot] = (1, 5, 0, 0)
+    ch, variables, flow, swap = _evaluate(rsv, ctx, circ, inputs, flow_in, layout, form)
+    a = ch.numpy()
+    assert a["acc"].tolist() == [1, 1, 1] and a["bad_input"].tolist() == [NONE] * 3
+    tables = (b.gates, b.flow_wires, E.links_of(b.cs), b.n_vars)
+    exported = circ.eval_export()
+    for k in range(3):
+        want_vars, want_flow, want_swap = E.model_eval(*exported, tables, inputs[k], flow_in[k])
+        assert np.array_equal(variables[k], want_vars) and np.array_equal(flow[k], want_flow) and np.array_equal(swap[k], want_swap), k
+    assert swap[:, at].tolist() == [0, 1, 1]
+    assert np.array_equal(variables[2], b.variables) and np.array_equal(flow[2], b.flow)
+    # the check, on the same variables and the flow the evaluation left
+    want = [U.model_flow(b.gates, b.flow_wires, variables[k], flow[k]) for k in range(3)]
+    assert [w[0] for w in want] == [at, at, NONE]
+    zero_out = U.permute([0] * 16)
+    assert want[0][1][at, 16:].tolist() == zero_out and want[1][1][at, 16:].tolist() == zero_out
+    d_flow, d_swap = ch._flow.clone(), torch.full_like(ch._swap, 7)
+    ok, bad = torch.ones(3, dtype=torch.uint8, device=DEV), torch.zeros(3, dtype=torch.int32, device=DEV)
+    ctx.set_option("witness_layout", layout)
+    try:
+        ctx.circuit_flow(circ, ch._vars, 3, d_flow, d_swap, ok, bad)
+        ctx.synchronize()
+    finally:
+        ctx.set_option("witness_layout", "by_proof")
+    assert u32(bad).tolist() == [at, at, NONE] and ok.cpu().tolist() == [0, 0, 1]
+    got_flow, got_swap = u32(d_flow), d_swap.cpu().numpy()
+    for k in range(3):
+        assert np.array_equal(got_flow[k], want[k][1]) and np.array_equal(got_swap[k], want[k][2]), k
     circ.close()
 
 

@@ -40,6 +40,7 @@ static void tables_point_inside(const Circuit& c, const Tables& t) {
     for (size_t f = 0; f < t.flow.size() / FLOW_WORDS; f++) {
         for (int k = 0; k < 8; k++) REQUIRE(t.flow[f * FLOW_WORDS + k] < c.n_vars);
         REQUIRE(t.flow[f * FLOW_WORDS + FLOW_MASK] < 16 && t.flow[f * FLOW_WORDS + FLOW_SWAP_ADDR] < c.n_vars);
+        REQUIRE(t.flow[f * FLOW_WORDS + FLOW_LINK] == 0 && t.flow[f * FLOW_WORDS + FLOW_LINK + 1] == 0);  // an evaluation program's
     }
 }
 
