@@ -364,6 +364,38 @@ int rsv_verify_batch_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_
                          size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
                          size_t n_pi, uint8_t* d_accept, uint8_t* d_reason);
 
+/* ---- a batch in which every proof has its own public inputs ---------------------------------------------------------
+ * rsv_verify_batch_inputs_dev is rsv_verify_batch_dev with d_pi [n][n_pi] records IN HBM (4-byte aligned), proof i's own
+ * inputs at d_pi[i * n_pi .. (i + 1) * n_pi); n_pi is the same for every proof.  Host synchronisation, mixed
+ * configurations (cfg_of) and the verdicts are exactly rsv_verify_batch_dev's; a batch under one configuration is
+ * enqueued without waiting for the device.  The inputs enter in one place, the logup balance
+ *     plonk_sum + poseidon_sum + sum_i 1 / (value_i + (idx_i mod P) alpha - z) = 0        (else RSV_R_LOGUP),
+ * whose last term a kernel of its own (one wave per proof, batched inversions) computes per proof behind the transcript
+ * and ahead of the OODS check.  Two rules:
+ *   - a zero denominator adds nothing, which is what the shared form's per-term inverse (1 / 0 = 0) adds;
+ *   - the inputs are in HBM and cannot be refused without a synchronisation: a value word >= P is data.  It counts as 0
+ *     and the proof gets RSV_R_PARSE (a non-canonical field element); its neighbours are unaffected.  (The shared form,
+ *     and rsv_verify_batch_inputs below, refuse such a word on the host with RSV_E_RANGE.)
+ * Given every proof the same records, the call returns rsv_verify_batch_dev's accept and reason byte for byte.
+ * Refusals before any device work: a NULL pointer (d_pi may be NULL with n_pi = 0; d_reason may be NULL): RSV_E_NULL;
+ * n_pi > 4096, n * n_pi > RSV_MAX_INPUT_RECORDS, a pointer not aligned as above: RSV_E_SIZE.
+ * rsv_verify_hints_inputs_dev is the same for rsv_verify_hints_dev; rsv_verify_batch_inputs is the host-memory form of
+ * rsv_verify_batch (pi [n][n_pi] host records; a value word >= P: RSV_E_RANGE).
+ * Not built: per-proof inputs in rsv_witness_eval* / rsv_witness_program_build (the builder makes the inputs constants
+ * of the program), in aggregation groups, in rsv_verify_batch_host, rsv_multi_* and rsv_exchange_*; a differing n_pi
+ * within a batch. */
+#define RSV_MAX_INPUT_RECORDS 1073741824 /* 2^30: n * n_pi of the per-proof entry points (the records' words are indexed in 64 bits) */
+int rsv_verify_batch_inputs_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
+                                const rsv_public_input* d_pi, size_t n_pi, uint8_t* d_accept, uint8_t* d_reason);
+int rsv_verify_batch_inputs(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                            const rsv_public_input* pi, size_t n_pi, uint8_t* accept, uint8_t* reason, int device);
+/* The statement sum alone (a per-operation entry point, as rsv_oods_eval): d_sum[i] = sum_k 1 / (value_ik + (idx_ik mod P)
+ * alpha_i - z_i) over proof i's n_pi records, (z_i, alpha_i) = d_z_alpha[i][0..3], [4..7].  d_bad [n] (may be NULL): 1 where
+ * a value word, or a word of z or alpha, is >= P (the word counts as 0), else 0.  All pointers 4-byte aligned.  Refusals as
+ * above, with n <= 2^26.  Enqueued on the context's stream. */
+int rsv_public_input_sum_dev(rsv_ctx* ctx, const rsv_public_input* d_pi, size_t n, size_t n_pi, const uint32_t* d_z_alpha,
+                             uint32_t* d_sum, uint8_t* d_bad);
+
 /* Proofs that start in HOST memory, as the reference's callers hold them: one serialized buffer per proof
  * (bincode::serialize(&proof) -> Vec<u8>, examples/multi-proofs/src/main.rs:69-139).  Chunks of about
  * RSV_OPT_HOST_CHUNK_MB (default 256) MB are gathered into pinned staging memory by worker threads
@@ -490,6 +522,11 @@ typedef struct {
 int rsv_verify_hints_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept,
                          uint8_t* d_reason);
+/* rsv_verify_hints_dev on a batch in which every proof has its own public inputs: d_pi [n][n_pi] in HBM, as
+ * rsv_verify_batch_inputs_dev takes them, with its rules and refusals. */
+int rsv_verify_hints_inputs_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
+                                const rsv_public_input* d_pi, size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept,
+                                uint8_t* d_reason);
 /* Same with every pointer (blob, offsets, the outputs named in *out, accept, reason) in HOST memory: the library
  * stages them through HBM.  rsv_trace_paths, rsv_fri_paths and rsv_transcript_batch are special cases of it. */
 int rsv_verify_hints(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
@@ -643,6 +680,14 @@ int rsv_circuit_check_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const u
                           uint32_t* d_bad_row);
 int rsv_circuit_flow_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, uint32_t* d_flow,
                          uint8_t* d_flow_swap, uint8_t* d_ok, uint32_t* d_bad_flow);
+/* The statement of each of n witnesses in HBM: d_pi [n][num_input] records (k, variables[k]) for k = 1 .. num_input, what
+ * rsv_verify_batch_inputs_dev takes for the proofs the chain makes of these witnesses.  d_variables in the layout
+ * RSV_OPT_WITNESS_LAYOUT names, 16-byte aligned; d_pi 4-byte aligned.  Any program with a gate list, built (num_input = 3:
+ * the constants 1, i, j) or made from a circuit; RSV_E_SIZE otherwise, for a program of another device and for n above
+ * 2^20; a NULL pointer: RSV_E_NULL.  Enqueued on the context's stream with no host synchronisation.
+ * rsv_circuit_program_num_input: the program's num_input (RSV_E_SIZE for a program without a gate list). */
+int rsv_circuit_program_num_input(const rsv_witness_program* prog, uint32_t* num_input);
+int rsv_circuit_inputs_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, rsv_public_input* d_pi);
 
 /* ---- a caller's circuit evaluated on the GPU: `variables` and the flow from the free inputs ---------------------------
  * rsv_circuit_program_create_eval is rsv_circuit_program_create — the same checks first, with the same statuses, the same

@@ -196,6 +196,13 @@ def _load() -> ctypes.CDLL:
                                             sz, _u8p, _u8p, ctypes.c_int]),
         "rsv_verify_batch_dev": (ctypes.c_int, [vp, vp, vp, sz, ctypes.POINTER(CfgSet),
                                                 ctypes.POINTER(PublicInput), sz, vp, vp]),
+        "rsv_verify_batch_inputs_dev": (ctypes.c_int, [vp, vp, vp, sz, ctypes.POINTER(CfgSet), vp, sz, vp, vp]),
+        "rsv_verify_batch_inputs": (ctypes.c_int, [_u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, _u8p, _u8p,
+                                                   ctypes.c_int]),
+        "rsv_verify_hints_inputs_dev": (ctypes.c_int, [vp, vp, vp, sz, ctypes.POINTER(CfgSet), vp, sz, ctypes.POINTER(HintsOut), vp, vp]),
+        "rsv_public_input_sum_dev": (ctypes.c_int, [vp, vp, sz, sz, vp, vp, vp]),
+        "rsv_circuit_program_num_input": (ctypes.c_int, [vp, _u32p]),
+        "rsv_circuit_inputs_dev": (ctypes.c_int, [vp, vp, vp, sz, vp]),
         "rsv_accept_bitmap_dev": (ctypes.c_int, [vp, vp, sz, vp, vp]),
         "rsv_trace_paths_dev": (ctypes.c_int, [vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                                ctypes.c_uint32, vp, vp, vp, vp]),
@@ -346,6 +353,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_trace_preprocessed_inputs", "rsv_circuit_program_create", "rsv_circuit_check_dev", "rsv_circuit_flow_dev",
            "rsv_circuit_program_create_eval", "rsv_circuit_eval_info", "rsv_circuit_eval_export", "rsv_circuit_eval_scratch_bytes",
            "rsv_circuit_eval_dev",
+           "rsv_verify_batch_inputs_dev", "rsv_verify_batch_inputs", "rsv_verify_hints_inputs_dev", "rsv_public_input_sum_dev",
+           "rsv_circuit_program_num_input", "rsv_circuit_inputs_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -570,15 +579,38 @@ def pack(proofs: Sequence[bytes]):
     return blob, offsets
 
 
-def verify_batch(proofs: Sequence[bytes], cfg, inputs=STANDARD_INPUTS, device: int = 0):
+def make_inputs_per_proof(inputs_per_proof, n: int):
+    """n lists of (idx, value) pairs of one length -> (PublicInput array [n * n_pi], n_pi)."""
+    per = [list(x) for x in inputs_per_proof]
+    if len(per) != n:
+        raise ValueError("inputs_per_proof: one list of inputs per proof expected")
+    n_pi = len(per[0]) if per else 0
+    if any(len(x) != n_pi for x in per):
+        raise ValueError("inputs_per_proof: every proof needs the same number of inputs")
+    return make_inputs([item for x in per for item in x]), n_pi
+
+
+def inputs_array(inputs_per_proof, n: int) -> np.ndarray:
+    """The same as uint32[n, n_pi, 5] records (idx, value[4]): the layout Context.verify_batch takes in HBM as d_inputs."""
+    arr, n_pi = make_inputs_per_proof(inputs_per_proof, n)
+    return np.frombuffer(arr, dtype=np.uint32, count=5 * n * n_pi).reshape(n, n_pi, 5).copy()
+
+
+def verify_batch(proofs: Sequence[bytes], cfg, inputs=STANDARD_INPUTS, device: int = 0, inputs_per_proof=None):
     """Verify a batch of serialized proofs on the GPU under the configuration(s) `cfg` (required: one PcsConfig, or
-    one per proof).  Returns (accept uint8[n], reason uint8[n])."""
+    one per proof).  inputs: the public inputs the whole batch shares; inputs_per_proof: instead, a list of n input lists of
+    equal length, every proof its own (rsv_verify_batch_inputs).  Returns (accept uint8[n], reason uint8[n])."""
     blob, offsets = pack(proofs)
     n = len(proofs)
     accept = np.zeros(n, np.uint8)
     reason = np.zeros(n, np.uint8)
-    pi = make_inputs(inputs)
     pc = prepare_cfg(cfg, n)
+    if inputs_per_proof is not None:
+        pi, n_pi = make_inputs_per_proof(inputs_per_proof, n)
+        _check(lib.rsv_verify_batch_inputs(blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, pc.ref(), pi, n_pi,
+                                           accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_verify_batch_inputs")
+        return accept, reason
+    pi = make_inputs(inputs)
     _check(lib.rsv_verify_batch(blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n,
                                 pc.ref(), pi, len(list(inputs)),
                                 accept.ctypes.data_as(_u8p), reason.ctypes.data_as(_u8p), device), "rsv_verify_batch")
@@ -1187,11 +1219,18 @@ class Context:
                                               d_swap.data_ptr() if d_swap is not None else None, d_rows.data_ptr(), n,
                                               d_bad.data_ptr() if d_bad is not None else None), "rsv_poseidon2_emulated_dev")
 
-    def verify_batch(self, d_blob, d_offsets, n: int, d_accept, d_reason=None, cfg=None, inputs=STANDARD_INPUTS):
-        pi = make_inputs(inputs)
+    def verify_batch(self, d_blob, d_offsets, n: int, d_accept, d_reason=None, cfg=None, inputs=STANDARD_INPUTS, d_inputs=None, n_inputs: int = 0):
+        """rsv_verify_batch_dev with the inputs the batch shares; with d_inputs (a device tensor of [n, n_inputs, 5] uint32
+        records idx, value[4]: every proof its own, what Context.circuit_inputs writes) rsv_verify_batch_inputs_dev."""
         pc = self.prepare_cfg(cfg, n)
         self.acquire_from_torch()
         self._keep(pc, cfg)
+        if d_inputs is not None:
+            _check(lib.rsv_verify_batch_inputs_dev(self._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), d_inputs.data_ptr(), n_inputs,
+                                                   d_accept.data_ptr(), d_reason.data_ptr() if d_reason is not None else None),
+                   "rsv_verify_batch_inputs_dev")
+            return
+        pi = make_inputs(inputs)
         _check(lib.rsv_verify_batch_dev(self._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), pi, len(list(inputs)),
                                         d_accept.data_ptr(), d_reason.data_ptr() if d_reason is not None else None),
                "rsv_verify_batch_dev")
@@ -1222,18 +1261,22 @@ class Context:
     def verify_hints(self, d_blob, d_offsets, n: int, d_accept, d_reason=None, cfg=None, inputs=STANDARD_INPUTS, shape=(0, 0, 0),
                      d_transcript=None, d_trace_sib=None, d_trace_pos=None, d_trace_cols=None, d_fri_sib=None,
                      d_fri_cols=None, d_fri_folded=None, d_query_values=None, d_flow=None, d_flow_swap=None, d_flow_count=None,
-                     d_accept_bitmap=None, d_accept_count=None):
-        """One verifying pass that also fills whichever hint outputs are given (rsv_verify_hints_dev).
-        shape = (n_queries, max_log, n_inner), needed for the path outputs."""
+                     d_accept_bitmap=None, d_accept_count=None, d_inputs=None, n_inputs: int = 0):
+        """One verifying pass that also fills whichever hint outputs are given (rsv_verify_hints_dev; with d_inputs, as
+        verify_batch takes them, rsv_verify_hints_inputs_dev).  shape = (n_queries, max_log, n_inner), needed for the path outputs."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         ho = HintsOut(int(shape[0]), int(shape[1]), int(shape[2]), ptr(d_transcript), ptr(d_trace_sib), ptr(d_trace_pos),
                       ptr(d_trace_cols), ptr(d_fri_sib), ptr(d_fri_cols), ptr(d_fri_folded), ptr(d_query_values),
                       ptr(d_flow), ptr(d_flow_swap), ptr(d_flow_count), int(d_flow.shape[1]) if d_flow is not None else 0,
                       ptr(d_accept_bitmap), ptr(d_accept_count))
-        pi = make_inputs(inputs)
         pc = self.prepare_cfg(cfg, n)
         self.acquire_from_torch()
         self._keep(pc, cfg)
+        if d_inputs is not None:
+            _check(lib.rsv_verify_hints_inputs_dev(self._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), d_inputs.data_ptr(), n_inputs,
+                                                   ctypes.byref(ho), d_accept.data_ptr(), ptr(d_reason)), "rsv_verify_hints_inputs_dev")
+            return
+        pi = make_inputs(inputs)
         _check(lib.rsv_verify_hints_dev(self._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), pi, len(list(inputs)),
                                         ctypes.byref(ho), d_accept.data_ptr(), ptr(d_reason)), "rsv_verify_hints_dev")
 
@@ -1275,6 +1318,21 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_circuit_flow_dev(self._h, program._h, d_variables.data_ptr(), n, d_flow.data_ptr(), d_flow_swap.data_ptr(),
                                         d_ok.data_ptr(), d_bad_flow.data_ptr()), "rsv_circuit_flow_dev")
+
+    def public_input_sum(self, d_inputs, n: int, n_inputs: int, d_z_alpha, d_sum, d_bad=None):
+        """rsv_public_input_sum_dev, the statement sum alone: d_inputs [n, n_inputs, 5] records (None with no inputs),
+        d_z_alpha uint32[n, 8] = z | alpha, d_sum uint32[n, 4] = sum_k 1 / (value_k + (idx_k mod P) alpha - z), d_bad uint8[n]
+        (optional): 1 where a word is not below P; enqueued on the context's stream."""
+        self.acquire_from_torch()
+        _check(lib.rsv_public_input_sum_dev(self._h, d_inputs.data_ptr() if d_inputs is not None else None, n, n_inputs, d_z_alpha.data_ptr(),
+                                            d_sum.data_ptr(), d_bad.data_ptr() if d_bad is not None else None), "rsv_public_input_sum_dev")
+
+    def circuit_inputs(self, program: WitnessProgram, d_variables, n: int, d_inputs):
+        """rsv_circuit_inputs_dev: the statement of each witness, d_inputs [n, program.num_input, 5] records (k,
+        variables[k]) for k = 1 .. num_input, from d_variables (in the context's witness_layout); enqueued on the context's
+        stream."""
+        self.acquire_from_torch()
+        _check(lib.rsv_circuit_inputs_dev(self._h, program._h, d_variables.data_ptr(), n, d_inputs.data_ptr()), "rsv_circuit_inputs_dev")
 
     def circuit_eval(self, program: WitnessProgram, d_inputs, n: int, d_variables, d_flow, d_flow_swap, d_ok, d_bad_input):
         """rsv_circuit_eval_dev: n witnesses of a Circuit made with hints from d_inputs uint32[n, n_inputs, 4] (None with

@@ -92,6 +92,7 @@ class Chain:
         self.done = set()
         self.pow_bits = None
         self._blob = self._vars = self._flow = self._swap = None
+        self._inputs = self._packed = None
         for name in _WRITTEN:
             setattr(self, name, None)
 
@@ -132,6 +133,7 @@ class Chain:
         else:
             self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
             self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
+            self._gather_inputs()
         self.done = {"witness"}
 
     def load(self, variables, flow=None, swap=None, check=True, by_variable=False):
@@ -164,6 +166,7 @@ class Chain:
             self.bad_row, self.bad_flow = self._new(n), self._new(n)
             self.ctx.circuit_check(wp, self._vars, n, self.acc, self.bad_row)
             self.ctx.circuit_flow(wp, self._vars, n, self._flow, self._swap, self.acc, self.bad_flow)
+        self._gather_inputs()
         self.done = {"witness"}
 
     def evaluate(self, inputs, flow_in=None, check=True, by_variable=False, mask=None):
@@ -202,7 +205,38 @@ class Chain:
             self.bad_row, self.bad_flow = self._new(n), self._new(n)
             self.ctx.circuit_check(wp, self._vars, n, self.acc, self.bad_row)
             self.ctx.circuit_flow(wp, self._vars, n, self._flow, self._swap, self.acc, self.bad_flow)
+        self._gather_inputs()
         self.done = {"witness"}
+
+    def _gather_inputs(self):
+        """The statements, while the variables are there (trace() drops them): Context.circuit_inputs into the chain's own
+        tensor [n, num_input, 5]."""
+        import torch
+        self._packed = None
+        self._inputs = torch.zeros((self.n, self.program.num_input, 5), dtype=torch.int32, device=self.device)
+        self.ctx.circuit_inputs(self.program, self._vars, self.n, self._inputs)
+
+    def inputs(self):
+        """-> the device tensor of the chain's own statements, int32[n, num_input, 5]: per witness the records (k,
+        variables[k]) for k = 1 .. num_input, in the layout Context.verify_batch takes as d_inputs.  Written by witness(),
+        load() or evaluate() on the context's stream (Context.circuit_inputs); a built program's are the three constants.
+        Not with aggregate."""
+        if self._inputs is None:
+            raise ValueError("Chain.inputs() needs witness(), load() or evaluate() first" + (" and is not for aggregate=True" if self.aggregate else ""))
+        return self._inputs
+
+    def verify(self, cfg):
+        """pack(), if not yet packed, then ONE verifying call on the packed pair with the chain's own statements
+        (Context.verify_batch with d_inputs = inputs()): neither the proofs nor the statements leave the device.
+        -> (d_accept, d_reason) uint8[n], complete after synchronize() / release_to_torch(); a slot that pack() left empty (ok
+        = 0) is rejected with the parser's reason."""
+        d_inputs = self.inputs()
+        if self._packed is None:
+            self._packed = self.pack()
+        d_blob, d_offsets = self._packed
+        d_accept, d_reason = self._new(self.n, flag=True), self._new(self.n, flag=True)
+        self.ctx.verify_batch(d_blob, d_offsets, self.n, d_accept, d_reason, cfg=cfg, d_inputs=d_inputs, n_inputs=int(d_inputs.shape[1]))
+        return d_accept, d_reason
 
     def trace(self, plonk=True, poseidon=True, ops=True):
         """Context.witness_trace (an output may be skipped), then the blob, the variables and the flow are dropped: torch's
@@ -296,6 +330,7 @@ class Chain:
         self.ctx.draw_queries(n, n_queries, M, max(self.lp, self.lq) + self.log_blowup, self.channel, self.queries, self.queries_low, d_mask=self.ok)
         self.done.discard("open")
         self.done.discard("fri_open")
+        self._packed = None
         self.done.add("pow")
 
     def open(self, caps=True):

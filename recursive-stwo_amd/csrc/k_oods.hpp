@@ -1,5 +1,6 @@
 // k_oods.hpp — logup sum and OODS composition identity (k_oods).  Part of the pipeline described in verify.hpp.
 #pragma once
+#include <type_traits>
 #include "verify_common.hpp"
 
 namespace rsv {
@@ -403,10 +404,14 @@ __device__ __noinline__ void oods_eval_row(const uint32_t* w, uint32_t lp, uint3
 // Merkle wave for as long.
 // (255 registers, one wave per SIMD: neither a launch bound nor amdgpu_waves_per_eu brings it down without spilling what the
 // LDS state just saved; beside the FRI trees — whose waves leave a SIMD 32 registers free — its waves start as those retire)
+// (PI: where the statement's share of the logup sum comes from — PiShared: the in-kernel loop over the batch's one table;
+// PiOwn: the per-proof sum k_pi_sum left, no loop.  The same pattern as the grouped witness kernels, DESIGN "Aggregation".)
+struct PiShared { const PubInput* pi; uint32_t n_pi; };
+struct PiOwn { const uint32_t* sum; };  // [n][4]
+template <class PI>
 __global__ __launch_bounds__(64, 4) void k_oods(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ offsets,
                                              uint32_t n, const ProofMeta* __restrict__ metas,
-                                             ProofCtx* __restrict__ ctxs, const PubInput* __restrict__ pi,
-                                             uint32_t n_pi) {
+                                             ProofCtx* __restrict__ ctxs, const PI src) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     const ProofMeta& m = metas[p];
@@ -417,9 +422,14 @@ __global__ __launch_bounds__(64, 4) void k_oods(const uint8_t* __restrict__ blob
     QM31 z = ldq(c.z), alpha = ldq(c.alpha), plonk_sum = ldq(w + W_PLONK_SUM), poseidon_sum = ldq(w + W_POSEIDON_SUM);
     {  // fiat_shamir/src/lib.rs:133-141
         QM31 sum = q_zero();
-        for (uint32_t i = 0; i < n_pi; i++) {
-            QM31 dnm = q_sub(q_add(ldq(pi[i].value), q_mul_m(alpha, pi[i].idx % P)), z);
-            sum = q_add(sum, q_inv(dnm));
+        if constexpr (std::is_same<PI, PiOwn>::value) sum = ldq(src.sum + (size_t)p * 4);
+        else {
+            const PubInput* __restrict__ pi = src.pi;
+            const uint32_t n_pi = src.n_pi;
+            for (uint32_t i = 0; i < n_pi; i++) {
+                QM31 dnm = q_sub(q_add(ldq(pi[i].value), q_mul_m(alpha, pi[i].idx % P)), z);
+                sum = q_add(sum, q_inv(dnm));
+            }
         }
         if (!q_eq(q_add(q_add(sum, poseidon_sum), plonk_sum), q_zero())) flags |= 1u << R_LOGUP;
     }
@@ -433,10 +443,10 @@ __global__ __launch_bounds__(64, 4) void k_oods(const uint8_t* __restrict__ blob
 }
 
 // Row-form pipeline kernel: 16 lanes per proof; whole rows leave together (DPP needs every lane of a live row).
+template <class PI>
 __global__ __launch_bounds__(256) void k_oods_row(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ offsets,
                                                   uint32_t n, const ProofMeta* __restrict__ metas,
-                                                  ProofCtx* __restrict__ ctxs, const PubInput* __restrict__ pi,
-                                                  uint32_t n_pi) {
+                                                  ProofCtx* __restrict__ ctxs, const PI src) {
     const uint32_t i = threadIdx.x & 15u;
     const uint32_t p = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     if (p >= n) return;
@@ -449,11 +459,16 @@ __global__ __launch_bounds__(256) void k_oods_row(const uint8_t* __restrict__ bl
     QM31 z = ldq(c.z), alpha = ldq(c.alpha), plonk_sum = ldq(w + W_PLONK_SUM), poseidon_sum = ldq(w + W_POSEIDON_SUM);
     {  // fiat_shamir/src/lib.rs:133-141: the public inputs are dealt to the lanes, their fractions added over the row
         QM31 sum = q_zero();
-        for (uint32_t k = i; k < n_pi; k += 16u) {
-            QM31 dnm = q_sub(q_add(ldq(pi[k].value), q_mul_m(alpha, pi[k].idx % P)), z);
-            sum = q_add(sum, q_inv(dnm));
+        if constexpr (std::is_same<PI, PiOwn>::value) sum = ldq(src.sum + (size_t)p * 4);  // (row-uniform)
+        else {
+            const PubInput* __restrict__ pi = src.pi;
+            const uint32_t n_pi = src.n_pi;
+            for (uint32_t k = i; k < n_pi; k += 16u) {
+                QM31 dnm = q_sub(q_add(ldq(pi[k].value), q_mul_m(alpha, pi[k].idx % P)), z);
+                sum = q_add(sum, q_inv(dnm));
+            }
+            sum = q_sum_row(sum);
         }
-        sum = q_sum_row(sum);
         if (!q_eq(q_add(q_add(sum, poseidon_sum), plonk_sum), q_zero())) flags |= 1u << R_LOGUP;
     }
     QM31 acc, expected;

@@ -123,4 +123,25 @@ int rsv_circuit_flow_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint
     return RSV_OK;
 }
 
+int rsv_circuit_program_num_input(const rsv_witness_program* prog, uint32_t* num_input) {
+    if (!prog || !num_input) return RSV_E_NULL;
+    if (prog->gates.empty()) return RSV_E_SIZE;
+    *num_input = prog->num_input;
+    return RSV_OK;
+}
+
+int rsv_circuit_inputs_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, rsv_public_input* d_pi) {
+    if (!c || !prog || !d_variables || !d_pi) return RSV_E_NULL;
+    if (prog->gates.empty() || n > (1u << 20) || ((uintptr_t)d_variables & 15) || ((uintptr_t)d_pi & 3)) return RSV_E_SIZE;
+    if (prog->device != c->device) return RSV_E_SIZE;
+    if (n == 0) return RSV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t words = n * prog->num_input * rsv::PI_WORDS;  // (num_input < n_vars <= 2^26, n <= 2^20)
+    if ((words + 255) / 256 >= (1u << 31)) return RSV_E_SIZE;
+    hipLaunchKernelGGL(rsv::k_circuit_inputs, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, d_variables, (uint32_t)n, prog->n_vars,
+                       prog->num_input, c->opt.witness_layout == 2, reinterpret_cast<uint32_t*>(d_pi));
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
 }  // extern "C"

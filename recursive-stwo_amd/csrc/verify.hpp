@@ -7,6 +7,7 @@
 // canonicity       (in the kernel that reads a word)  —                            M31 words must be < P: layout.hpp; fallback in k_finalize
 // transcript       k_transcript[_row] (k_transcript)  1 lane or 1 DPP row / proof  components/recursive/fiat_shamir/src/lib.rs:31-176
 // OODS identity    k_oods (k_oods.hpp)                1 lane / proof               components/recursive/composition/src/**
+// statement sum    k_pi_sum (k_pi_sum.hpp)            1 wave / proof               fiat_shamir/src/lib.rs:133-141, per-proof public inputs only
 // decommit plan    k_plan_par (k_plan.hpp)            1 lane / (proof, query)      components/hints/src/decommit.rs:53-142, folding.rs:107-212
 // quotient consts  k_qconst (k_plan.hpp)              1 lane / proof               components/recursive/answer/src/data_structures.rs:132-189
 // quotients+folds  k_query<QB> (k_query.hpp)          1 lane / (proof, query)      components/recursive/answer/src/**, folding/src/lib.rs:57-204
@@ -26,6 +27,7 @@
 #include "k_parse.hpp"
 #include "k_transcript.hpp"
 #include "k_oods.hpp"
+#include "k_pi_sum.hpp"
 #include "k_plan.hpp"
 #include "k_query.hpp"
 #include "k_merkle.hpp"

@@ -11,7 +11,8 @@
 //   4. per group of buckets (a group = what fits the workspace budget, normally the whole batch):
 //      M: k_plan -> k_trace_merkle;  S: k_query -> k_pair_merkle (single-group batches: the FRI trees run next to the
 //      trace trees; with several groups k_pair_merkle follows k_trace_merkle on M, the groups share the workspace);
-//   5. k_oods, which only feeds k_finalize: on M behind the trace trees (single group) or last on S;
+//   5. k_oods, which only feeds k_finalize: on M behind the trace trees (single group) or last on S; with per-proof public
+//      inputs (rsv_verify_batch_inputs_dev) k_pi_sum right in front of it on the same stream;
 //   6. M, behind everything on S: k_finalize over the whole batch — verdicts, the canonicity fallback for proofs whose
 //      witness lists had the wrong length (layout.hpp), optionally the accept bitmap.
 // No hipMalloc happens after the two workspaces have grown to the batch shape once.
@@ -149,8 +150,10 @@ static void launch_oods_probe(const uint32_t* d_prefix, uint32_t prefix_words, c
 }
 
 static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
-                       const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept,
-                       uint8_t* d_reason, const PathsOut* po) {
+                       const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_own_pi,
+                       uint8_t* d_accept, uint8_t* d_reason, const PathsOut* po) {
+    // d_own_pi: nullptr — `pi` is the batch's one table, in host memory; else [n][n_pi] records in HBM, every proof its own
+    // (`pi` is unused): k_pi_sum sums them per proof and the OODS kernel reads that sum (k_pi_sum.hpp)
     if (!c) return RSV_E_NULL;
     CfgSet co;
     {
@@ -159,10 +162,12 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     }
     if (n == 0) return RSV_OK;
     if (!d_blob || !d_offsets || !d_accept) return RSV_E_NULL;
-    if (n_pi && !pi) return RSV_E_NULL;
+    const bool own = d_own_pi != nullptr;
+    if (n_pi && !pi && !own) return RSV_E_NULL;
     if (n > (1u << 26) || n_pi > 4096) return RSV_E_SIZE;
-    if (((uintptr_t)d_blob & 3) || ((uintptr_t)d_offsets & 7)) return RSV_E_SIZE;
-    for (size_t i = 0; i < n_pi; i++)
+    if (own && (uint64_t)n * n_pi > RSV_MAX_INPUT_RECORDS) return RSV_E_SIZE;
+    if (((uintptr_t)d_blob & 3) || ((uintptr_t)d_offsets & 7) || ((uintptr_t)d_own_pi & 3)) return RSV_E_SIZE;
+    for (size_t i = 0; i < n_pi && !own; i++)
         for (int k = 0; k < 4; k++)
             if (pi[i].value[k] >= RSV_M31_P) return RSV_E_RANGE;
     HIP_TRY(hipSetDevice(c->device));
@@ -200,7 +205,7 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         HIP_TRY(hipMalloc((void**)&c->d_pi, sizeof(rsv_public_input) * (n_pi + 16)));
         c->d_pi_cap = n_pi + 16;
     }
-    if (n_pi) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
+    if (n_pi && !own) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
     // rsv_hints_out::d_query_values: "absent groups and rejected proofs are zero" holds for the caller's buffer as it is
     if (po && po->d_count) HIP_TRY(hipMemsetAsync(po->d_count, 0, 8, st));
     if (po && po->d_qv)
@@ -216,6 +221,7 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     fixed.take<uint32_t>(N);
     fixed.take<ClassTable>(1);
     fixed.take<uint8_t>(N);
+    fixed.take<uint32_t>(own ? 4 * (size_t)N : 0);
     int rc = ensure_buf(c, &c->ws_fixed, &c->ws_fixed_bytes, fixed.off);
     if (rc != RSV_OK) return rc;
     Carve cv{static_cast<char*>(c->ws_fixed)};
@@ -227,6 +233,7 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     uint32_t* d_ids = cv.take<uint32_t>(N);
     ClassTable* d_classes = cv.take<ClassTable>(1);
     uint8_t* d_cls = cv.take<uint8_t>(N);
+    uint32_t* d_pi_sum = cv.take<uint32_t>(own ? 4 * (size_t)N : 0);  // k_pi_sum -> k_oods<PiOwn>
 
     // small batches: one proof per 16-lane DPP row (latency form of the transcript); large ones: one proof per lane
     // (throughput form).  RSV_OPT_TRANSCRIPT_FORM overrides (tests).
@@ -403,12 +410,19 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         bool oods_launched = false;
         auto launch_oods = [&](hipStream_t on) {
             begin_on(2, on);
-            if (oods_row_form(opt, N))
-                hipLaunchKernelGGL(k_oods_row, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, on, d_blob, d_offsets, N, metas, ctxs,
-                                   reinterpret_cast<const PubInput*>(c->d_pi), (uint32_t)n_pi);
-            else
-                hipLaunchKernelGGL(k_oods, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs,
-                                   reinterpret_cast<const PubInput*>(c->d_pi), (uint32_t)n_pi);
+            const PiShared shared{reinterpret_cast<const PubInput*>(c->d_pi), (uint32_t)n_pi};
+            const PiOwn sums{d_pi_sum};
+            // per-proof inputs: the statement sums first, on the same stream (behind the transcript, as the OODS kernel is)
+            if (own)
+                hipLaunchKernelGGL(k_pi_sum<true>, dim3(grid_for(N, PI_WAVES)), dim3(64 * PI_WAVES), 0, on, reinterpret_cast<const uint32_t*>(d_own_pi),
+                                   N, (uint32_t)n_pi, metas, ctxs, (const uint32_t*)nullptr, d_pi_sum, (uint8_t*)nullptr);
+            if (oods_row_form(opt, N)) {
+                if (own) hipLaunchKernelGGL(k_oods_row<PiOwn>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, on, d_blob, d_offsets, N, metas, ctxs, sums);
+                else hipLaunchKernelGGL(k_oods_row<PiShared>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, on, d_blob, d_offsets, N, metas, ctxs, shared);
+            } else {
+                if (own) hipLaunchKernelGGL(k_oods<PiOwn>, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs, sums);
+                else hipLaunchKernelGGL(k_oods<PiShared>, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs, shared);
+            }
             end_on(on);
             oods_launched = true;
         };
@@ -705,7 +719,7 @@ extern "C" {
 int rsv_verify_batch_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept,
                          uint8_t* d_reason) {
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, nullptr);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, nullptr);
 }
 
 int rsv_trace_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
@@ -714,7 +728,7 @@ int rsv_trace_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_off
     if (!d_sib || !d_pos) return RSV_E_NULL;
     if (n_queries < 4 || n_queries > (uint32_t)MAXQ || max_log > (uint32_t)MAX_LOG) return RSV_E_SIZE;
     PathsOut po{d_sib, d_pos, n_queries, max_log, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, FlowArgs{}, nullptr, nullptr};
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, &po);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po);
 }
 
 int rsv_fri_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
@@ -723,7 +737,7 @@ int rsv_fri_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offse
     if (!d_sib || !d_cols) return RSV_E_NULL;
     if (n_queries < 4 || n_queries > (uint32_t)MAXQ || max_log > (uint32_t)MAX_LOG || n_inner > (uint32_t)MAX_INNER) return RSV_E_SIZE;
     PathsOut po{nullptr, nullptr, n_queries, max_log, d_sib, d_cols, n_inner, nullptr, nullptr, nullptr, nullptr, FlowArgs{}, nullptr, nullptr};
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, &po);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po);
 }
 
 int rsv_verify_batch(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
@@ -762,8 +776,11 @@ int rsv_verify_batch(const uint8_t* blob, const uint64_t* offsets, size_t n, con
     return rc;
 }
 
-int rsv_verify_hints_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
-                         size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept, uint8_t* d_reason) {
+}  // extern "C"
+
+// rsv_verify_hints_dev and rsv_verify_hints_inputs_dev (d_own_pi: verify_impl)
+static int verify_hints_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
+                             size_t n_pi, const rsv_public_input* d_own_pi, const rsv_hints_out* out, uint8_t* d_accept, uint8_t* d_reason) {
     if (!out) return RSV_E_NULL;
     if ((out->d_trace_sib == nullptr) != (out->d_trace_pos == nullptr)) return RSV_E_NULL;
     if (out->d_fri_sib && !out->d_fri_cols) return RSV_E_NULL;  // (the column values alone are fine: rsv_witness_eval_dev asks for just them)
@@ -778,7 +795,109 @@ int rsv_verify_hints_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_of
     if (po.paths() && (po.n_queries < 4 || po.n_queries > (uint32_t)MAXQ || po.max_log > (uint32_t)MAX_LOG ||
                        po.n_inner > (uint32_t)MAX_INNER))
         return RSV_E_SIZE;
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_accept, d_reason, &po);
+    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, d_own_pi, d_accept, d_reason, &po);
+}
+
+// what the per-proof entry points check of their inputs before anything else (include/rsv.h)
+static int check_own_inputs(const void* d_pi, size_t n, size_t n_pi) {
+    if (n_pi && !d_pi) return RSV_E_NULL;
+    if (n_pi > 4096 || (n_pi && n > RSV_MAX_INPUT_RECORDS / n_pi)) return RSV_E_SIZE;
+    return RSV_OK;
+}
+// verify_impl keeps host vectors (buckets, groups): a std::bad_alloc out of it is RSV_E_NOMEM, as in the circuit entry points
+template <class F> static int nomem_guard(F f) {
+    try {
+        return f();
+    } catch (const std::bad_alloc&) {
+        return RSV_E_NOMEM;
+    }
+}
+
+extern "C" {
+
+int rsv_verify_hints_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
+                         size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept, uint8_t* d_reason) {
+    return verify_hints_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, out, d_accept, d_reason);
+}
+
+// (no inputs at all is the shared form with an empty table: the same sum, 0, and no extra launch)
+int rsv_verify_batch_inputs_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
+                                const rsv_public_input* d_pi, size_t n_pi, uint8_t* d_accept, uint8_t* d_reason) {
+    if (!c) return RSV_E_NULL;
+    const int rc = check_own_inputs(d_pi, n, n_pi);
+    if (rc != RSV_OK) return rc;
+    return nomem_guard([&] { return verify_impl(c, d_blob, d_offsets, n, cfg, nullptr, n_pi, n_pi ? d_pi : nullptr, d_accept, d_reason, nullptr); });
+}
+
+int rsv_verify_hints_inputs_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
+                                const rsv_public_input* d_pi, size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept, uint8_t* d_reason) {
+    if (!c || !out) return RSV_E_NULL;
+    const int rc = check_own_inputs(d_pi, n, n_pi);
+    if (rc != RSV_OK) return rc;
+    return nomem_guard([&] { return verify_hints_impl(c, d_blob, d_offsets, n, cfg, nullptr, n_pi, n_pi ? d_pi : nullptr, out, d_accept, d_reason); });
+}
+
+int rsv_verify_batch_inputs(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
+                            size_t n_pi, uint8_t* accept, uint8_t* reason, int device) {
+    if (n && (!blob || !offsets || !accept)) return RSV_E_NULL;
+    if (n && n_pi && !pi) return RSV_E_NULL;
+    { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
+    if (n > (1u << 26)) return RSV_E_SIZE;
+    { const int rc0 = check_own_inputs(pi, n, n_pi); if (rc0 != RSV_OK) return rc0; }
+    for (size_t i = 0; i < n * n_pi; i++)
+        for (int k = 0; k < 4; k++)
+            if (pi[i].value[k] >= RSV_M31_P) return RSV_E_RANGE;
+    int rc = select_device(device);
+    if (rc != RSV_OK) return rc;
+    DevCfgSet dcfg;
+    rc = dcfg.init(cfg, n);
+    if (rc != RSV_OK) return rc;
+    if (n == 0) return RSV_OK;
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
+    const uint64_t base = offsets[0], total = offsets[n] - base;
+    std::vector<uint64_t> rel;
+    try {
+        rel.resize(n + 1);
+    } catch (const std::bad_alloc&) {
+        return RSV_E_NOMEM;
+    }
+    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
+    DevBuf dblob, doffs, dacc, dreason, dpi;
+    HIP_TRY(dblob.alloc(total + 16));
+    HIP_TRY(doffs.alloc(8 * (n + 1)));
+    HIP_TRY(dacc.alloc(n));
+    HIP_TRY(dreason.alloc(n));
+    HIP_TRY(dpi.alloc(sizeof(rsv_public_input) * n * n_pi + 16));
+    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
+    if (n_pi) HIP_TRY(hipMemcpy(dpi.p, pi, sizeof(rsv_public_input) * n * n_pi, hipMemcpyHostToDevice));
+    rsv_ctx* c = nullptr;
+    rc = rsv_ctx_create(device, &c);
+    if (rc != RSV_OK) return rc;
+    rc = rsv_verify_batch_inputs_dev(c, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, &dcfg.dev, dpi.as<const rsv_public_input>(), n_pi,
+                                     dacc.as<uint8_t>(), dreason.as<uint8_t>());
+    if (rc == RSV_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = RSV_E_DEVICE;
+    if (rc == RSV_OK && hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
+    if (rc == RSV_OK && reason && hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
+    rsv_ctx_destroy(c);
+    return rc;
+}
+
+int rsv_public_input_sum_dev(rsv_ctx* c, const rsv_public_input* d_pi, size_t n, size_t n_pi, const uint32_t* d_z_alpha, uint32_t* d_sum,
+                             uint8_t* d_bad) {
+    if (!c || (n && (!d_z_alpha || !d_sum))) return RSV_E_NULL;
+    if (n && n_pi && !d_pi) return RSV_E_NULL;
+    if (n > (1u << 26)) return RSV_E_SIZE;
+    const int rc = check_own_inputs(d_pi, n, n_pi);
+    if (rc != RSV_OK) return rc;
+    if (((uintptr_t)d_pi & 3) || ((uintptr_t)d_z_alpha & 3) || ((uintptr_t)d_sum & 3)) return RSV_E_SIZE;
+    if (n == 0) return RSV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_pi_sum<false>, dim3(grid_for(n, PI_WAVES)), dim3(64 * PI_WAVES), 0, c->stream, reinterpret_cast<const uint32_t*>(d_pi),
+                       (uint32_t)n, (uint32_t)n_pi, (const ProofMeta*)nullptr, (ProofCtx*)nullptr, d_z_alpha, d_sum, d_bad);
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
 }
 
 int rsv_verify_hints(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,

@@ -676,6 +676,34 @@ struct Verifier {
                                     pi.size(), accept.data(), reason.data()),
               "rsv_verify_batch_host");
     }
+    // A batch in which every proof has its own public inputs (what a caller's own circuit gives: one statement per
+    // witness): inputs[i] are proof i's, all of one length (rsv_verify_batch_inputs).  Proofs already in HBM, with their
+    // statements beside them, go through rsv_verify_batch_inputs_dev / rsv_verify_hints_inputs_dev on a context
+    // (rsv_circuit_inputs_dev gathers the statements of a batch of witnesses; rsv_public_input_sum_dev is the sum alone).
+    static void verify_batch_inputs(const std::vector<std::vector<uint8_t>>& proofs, const std::vector<PcsConfig>& configs,
+                                    const std::vector<Inputs>& inputs, std::vector<uint8_t>& accept, std::vector<uint8_t>& reason,
+                                    int device = default_device()) {
+        Job job(proofs, configs);
+        if (inputs.size() != proofs.size()) throw DeviceError("verify_batch_inputs: one list of inputs per proof", RSV_E_SIZE);
+        const size_t n_pi = inputs.empty() ? 0 : inputs[0].size();
+        std::vector<rsv_public_input> pi;
+        for (const Inputs& in : inputs) {
+            if (in.size() != n_pi) throw DeviceError("verify_batch_inputs: every proof needs the same number of inputs", RSV_E_SIZE);
+            const auto one = abi_inputs(in);
+            pi.insert(pi.end(), one.begin(), one.end());
+        }
+        std::vector<uint8_t> blob;
+        std::vector<uint64_t> offsets(1, 0);
+        for (auto& p : proofs) {
+            blob.insert(blob.end(), p.begin(), p.end());
+            offsets.push_back(blob.size());
+        }
+        accept.assign(proofs.size(), 0);
+        reason.assign(proofs.size(), 0);
+        check(rsv_verify_batch_inputs(blob.data(), offsets.data(), proofs.size(), &job.cfg_set, pi.data(), n_pi, accept.data(), reason.data(),
+                                      device),
+              "rsv_verify_batch_inputs");
+    }
     // The same job over several devices from this ONE process — the reference's driver is one process that walks the whole
     // chain (examples/multi-proofs/src/main.rs:198-295): contiguous shards balanced by bytes (rsv_shard_plan), one host thread per device,
     // verdicts + accept bitmap + count assembled on the host (rsv_multi_verify_batch_host; nothing is exchanged between
