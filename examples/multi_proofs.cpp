@@ -7,6 +7,14 @@
 //   g++ -std=c++17 -O1 -o multi_proofs examples/multi_proofs.cpp -Lrecursive-stwo_amd/csrc -lrsv_hip \
 //       -Wl,-rpath,$PWD/recursive-stwo_amd/csrc -Wl,-rpath,/opt/rocm/lib
 //   ./multi_proofs tests/golden/proofs/level*.bin
+//
+// --own-inputs: the RECURSING step over a batch in which every proof has its own statement.  The files are proofs of ONE
+// shape and configuration; each may be followed by `:v`, the M31 value of its own public input (1 .. 2^31 - 2; default 1).
+// The records are (2, i), (3, u) — shared, constants of the circuit — and (1, v): the proof's own, a PublicInput variable
+// of the circuit that verifies it.  One program, built from the first file, serves every proof; variable 4 of proof k's
+// witness is its v, and the next proof would carry it as its fourth public input.
+//   ./multi_proofs --own-inputs tests/golden/proofs/level10-1.bin tests/golden/proofs/level11-1.bin:2
+// accepts the first (its statement is (1, 1)) and rejects the second (stage 3: the logup balance does not close under (1, 2)).
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -33,7 +41,40 @@ static PcsConfig config_of_level(int k) {
     }
 }
 
+static int own_inputs(int argc, char** argv) {
+    std::vector<std::vector<uint8_t>> proofs;
+    std::vector<Inputs> own;
+    PcsConfig config = standard_config;
+    for (int i = 2; i < argc; i++) {
+        std::string name = argv[i];
+        uint32_t v = 1;
+        const size_t colon = name.rfind(':');
+        if (colon != std::string::npos) { v = (uint32_t)strtoul(name.c_str() + colon + 1, nullptr, 10); name.resize(colon); }
+        const size_t at = name.rfind("level");
+        if (i == 2) config = config_of_level(at == std::string::npos ? 0 : atoi(name.c_str() + at + 5));
+        std::ifstream f(name, std::ios::binary);
+        if (!f) { fprintf(stderr, "cannot read %s\n", name.c_str()); return 2; }
+        proofs.emplace_back((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        own.push_back({{1, QM31{v, 0, 0, 0}}});
+    }
+    if (proofs.empty()) return 0;
+    const Inputs fixed = {{2, QM31{0, 1, 0, 0}}, {3, QM31{0, 0, 1, 0}}};
+    Inputs of_template = fixed;
+    of_template.push_back(own[0][0]);
+    const WitnessProgram program = WitnessProgram::build_inputs(proofs[0], config, of_template, fixed.size());
+    std::vector<uint8_t> accept, reason;
+    const auto variables = program.variables(proofs, fixed, own, accept, reason);
+    int bad = 0;
+    for (size_t i = 0; i < proofs.size(); i++) {
+        if (accept[i]) printf("%-40s accepted: %u variables, variable 4 = %u\n", argv[i + 2], program.n_vars, (unsigned)variables[i][4][0]);
+        else printf("%-40s REJECTED (stage %u)\n", argv[i + 2], (unsigned)reason[i]);
+        bad += !accept[i];
+    }
+    return bad ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "--own-inputs") return own_inputs(argc, argv);
     std::vector<std::vector<uint8_t>> proofs;
     std::vector<PcsConfig> configs;
     for (int i = 1; i < argc; i++) {

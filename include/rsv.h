@@ -381,9 +381,9 @@ int rsv_verify_batch_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_
  * n_pi > 4096, n * n_pi > RSV_MAX_INPUT_RECORDS, a pointer not aligned as above: RSV_E_SIZE.
  * rsv_verify_hints_inputs_dev is the same for rsv_verify_hints_dev; rsv_verify_batch_inputs is the host-memory form of
  * rsv_verify_batch (pi [n][n_pi] host records; a value word >= P: RSV_E_RANGE).
- * Not built: per-proof inputs in rsv_witness_eval* / rsv_witness_program_build (the builder makes the inputs constants
- * of the program), in aggregation groups, in rsv_verify_batch_host, rsv_multi_* and rsv_exchange_*; a differing n_pi
- * within a batch. */
+ * Recursing over such a batch: rsv_witness_program_build_inputs, rsv_witness_eval_inputs_dev and
+ * rsv_witness_eval_groups_inputs_dev, below.  Not built: per-proof inputs in rsv_verify_batch_host, rsv_multi_* and
+ * rsv_exchange_*; a differing n_pi within a batch. */
 #define RSV_MAX_INPUT_RECORDS 1073741824 /* 2^30: n * n_pi of the per-proof entry points (the records' words are indexed in 64 bits) */
 int rsv_verify_batch_inputs_dev(rsv_ctx* ctx, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg,
                                 const rsv_public_input* d_pi, size_t n_pi, uint8_t* d_accept, uint8_t* d_reason);
@@ -586,6 +586,24 @@ void rsv_witness_program_destroy(rsv_witness_program* prog);
  * otherwise (a fault of the library's mirror of the gadgets, never of the template). */
 int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
                               uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out);
+/* PER-PROOF PUBLIC INPUTS.  rsv_witness_program_build makes every public input a constant of the program, so a program fits
+ * one statement.  rsv_witness_program_build_inputs is the same builder with pi[0 .. n_fixed) constants of the program and
+ * pi[n_fixed .. n_pi) the proof's OWN inputs (n_own = n_pi - n_fixed <= 4096; n_fixed > n_pi: RSV_E_SIZE): each becomes a
+ * PublicInput variable of the circuit (constraint_system/src/plonk_with_poseidon.rs:236-252), so the gate list is the same
+ * for every statement, one program serves a batch of proofs that differ in their own inputs (rsv_witness_eval_inputs_dev),
+ * and the next proof carries the inner statement as part of its own.  The reference wants public inputs allocated before
+ * anything else, so all of them come first: record k of the proof copy c verifies is variable 4 + c * n_own + k, with the
+ * row (v, 0, v, op 1, poseidon_wire 0, enforce_c_m31 1) and the instruction W_INPUT, imm0 = k; num_input (rsv_circuit_program_num_input)
+ * is 3 + copies * n_own.  A record's idx stays a constant of the program.  `pi` holds the template's own values.
+ * THE REFERENCE'S QUIRK STANDS: a PublicInput row enforces M31, so only a statement whose own values are M31 (words 1..3
+ * zero) can be recursed; one with a non-zero word 1..3 cannot, and rsv_witness_eval_inputs_dev rejects its proof.
+ * With n_fixed == n_pi the program is rsv_witness_program_build's: _info, _export and _gates give the same bytes.
+ * rsv_witness_program_inputs: the counts a built program was made for and idx_out [n_own] = the own records' idx (any
+ * pointer may be NULL; RSV_E_SIZE for a program made from instructions or from a circuit, which has them not on record).
+ * rsv_witness_program_create accepts W_INPUT with imm0 < 4096 (RSV_E_RANGE otherwise). */
+int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
+                                     size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out);
+int rsv_witness_program_inputs(const rsv_witness_program* prog, uint32_t* n_fixed, uint32_t* n_own, uint32_t* idx_out);
 /* Sizes, then the arrays (any pointer may be NULL): instr [n_vars][8], level_offsets [n_levels + 1], flow_wires
  * [copies * flow_count][5] = PoseidonEntry::wire of r1..r4 and SwapOption::addr of every invocation (constants of the
  * shape; known to built programs and to those made from a circuit, RSV_E_SIZE otherwise) — what
@@ -636,6 +654,34 @@ int rsv_witness_eval_groups_dev(rsv_ctx* ctx, const rsv_witness_program* prog, c
                                 uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept,
                                 uint8_t* d_member_reason);
 int rsv_witness_group_scratch_bytes(const rsv_witness_program* prog, size_t n_groups, size_t* bytes);
+/* A batch in which every proof has its own public inputs, for a program with own inputs (rsv_witness_program_build_inputs).
+ * rsv_witness_eval_inputs_dev is rsv_witness_eval_dev with pi_fixed [n_fixed]: the shared records (host memory) and d_pi
+ * [n][n_own]: proof i's own records IN HBM, 4-byte aligned, as rsv_verify_batch_inputs_dev takes them.  Proof i is
+ * verified (rsv_verify_hints_inputs_dev) under the n_fixed shared records followed by its own; the array is assembled on
+ * the device, nothing synchronises with the host.  W_INPUT k of row i is d_pi[i][k].value.
+ * d_accept[i] = 1 iff proof i verified under its own statement AND is of the program's shape AND every own record's idx is
+ * the program's AND every own value is an M31 (words 1..3 zero, word 0 below P).  An idx that differs or a value that is no
+ * M31 is RSV_R_PARSE in d_reason[i], as bad statement data is in rsv_verify_batch_inputs_dev.
+ * Refused before any device work: a NULL pointer (RSV_E_NULL); n_fixed, n_own or a shared record's idx that differ from
+ * what the program was built for, for a program made from instructions a W_INPUT whose imm0 is not below n_own, n * (n_fixed
+ * + n_own) > RSV_MAX_INPUT_RECORDS, n_fixed + n_own > 4096, d_pi not 4-byte aligned, a configuration that is not the program's, d_blob or d_offsets not
+ * aligned as rsv_verify_batch_dev wants them (RSV_E_SIZE).  With n_own == 0 the
+ * call is rsv_witness_eval_dev under pi_fixed.  rsv_witness_eval_dev / rsv_witness_eval_groups_dev refuse a program with
+ * own inputs (RSV_E_SIZE).  rsv_witness_eval_inputs: the same on host buffers, pi_own [n][n_own].
+ * rsv_witness_eval_groups_inputs_dev is rsv_witness_eval_groups_dev in the same way: d_pi [n_groups * copies][n_own], member
+ * g * copies + c brings the records that variables 4 + c * n_own + k of group g hold; a member whose statement the circuit
+ * cannot hold is rejected in d_member_accept / d_member_reason, and its group with it. */
+int rsv_witness_eval_inputs_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
+                                const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* d_pi,
+                                size_t n_own, uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept,
+                                uint8_t* d_reason);
+int rsv_witness_eval_inputs(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                            const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* pi_own, size_t n_own,
+                            uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept, uint8_t* reason, int device);
+int rsv_witness_eval_groups_inputs_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets,
+                                       size_t n_groups, const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed,
+                                       const rsv_public_input* d_pi, size_t n_own, uint32_t* d_variables, uint32_t* d_flow,
+                                       uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason);
 
 /* ---- a caller's own Plonk-with-Poseidon circuit through the chain -----------------------------------------------------
  * The reference's prove_plonk_with_poseidon proves whatever circuit the constraint system holds; so does the chain from

@@ -231,6 +231,15 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_program_destroy": (None, [vp]),
         "rsv_witness_program_build": (ctypes.c_int, [_u8p, sz, ctypes.POINTER(PcsConfig), ctypes.POINTER(PublicInput), sz, ctypes.c_uint32,
                                                      _u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+        "rsv_witness_program_build_inputs": (ctypes.c_int, [_u8p, sz, ctypes.POINTER(PcsConfig), ctypes.POINTER(PublicInput), sz, sz,
+                                                            ctypes.c_uint32, _u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+        "rsv_witness_program_inputs": (ctypes.c_int, [vp, _u32p, _u32p, _u32p]),
+        "rsv_witness_eval_inputs_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, sz, vp, vp,
+                                                       vp, vp, vp]),
+        "rsv_witness_eval_inputs": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz,
+                                                   ctypes.POINTER(PublicInput), sz, _u32p, _u32p, _u8p, _u8p, _u8p, ctypes.c_int]),
+        "rsv_witness_eval_groups_inputs_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, sz,
+                                                              vp, vp, vp, vp, vp, vp]),
         "rsv_witness_program_info": (ctypes.c_int, [vp, _u32p, _u32p, ctypes.POINTER(WitnessShape)]),
         "rsv_witness_program_export": (ctypes.c_int, [vp, _u32p, _u32p, _u32p]),
         "rsv_witness_program_gates": (ctypes.c_int, [vp, _u32p, _u32p, _u32p, _u32p]),
@@ -355,6 +364,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_circuit_eval_dev",
            "rsv_verify_batch_inputs_dev", "rsv_verify_batch_inputs", "rsv_verify_hints_inputs_dev", "rsv_public_input_sum_dev",
            "rsv_circuit_program_num_input", "rsv_circuit_inputs_dev",
+           "rsv_witness_program_build_inputs", "rsv_witness_program_inputs", "rsv_witness_eval_inputs_dev", "rsv_witness_eval_inputs",
+           "rsv_witness_eval_groups_inputs_dev",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -693,7 +704,7 @@ class WitnessProgram:
     library's mirror of the reference's circuit gadgets over a template proof (rsv_witness_program_build);
     WitnessProgram(program) loads arrays made earlier (witness_program.Program, e.g. from a file)."""
 
-    num_input = 3  # the recursion circuit allocates no public input
+    num_input = 3  # the recursion circuit allocates no public input, unless built with own inputs (build(n_fixed=...))
 
     def __init__(self, program=None, device: int = 0, _handle=None):
         self._h = None
@@ -715,10 +726,16 @@ class WitnessProgram:
         _check(lib.rsv_witness_program_info(self._h, ctypes.byref(n_vars), ctypes.byref(n_levels), ctypes.byref(self.shape)),
                "rsv_witness_program_info")
         self.n_vars, self.n_levels = int(n_vars.value), int(n_levels.value)
+        num_input = ctypes.c_uint32(0)
+        if lib.rsv_circuit_program_num_input(self._h, ctypes.byref(num_input)) == 0:  # (a program made from instructions has no gate list)
+            self.num_input = int(num_input.value)
 
     @classmethod
-    def build(cls, proof: bytes, cfg, inputs=STANDARD_INPUTS, copies: int = 1, device: int = 0, set_walks=None) -> "WitnessProgram":
-        """set_walks: per copy, which of the four orders the reference's two HashSet walks took (rsv.h); default 0 for all."""
+    def build(cls, proof: bytes, cfg, inputs=STANDARD_INPUTS, copies: int = 1, device: int = 0, set_walks=None, n_fixed=None) -> "WitnessProgram":
+        """set_walks: per copy, which of the four orders the reference's two HashSet walks took (rsv.h); default 0 for all.
+        n_fixed: None — every input is a constant of the program (rsv_witness_program_build); else inputs[:n_fixed] are, and
+        inputs[n_fixed:] are the proof's own: PublicInput variables 4 + c * n_own + k of the circuit
+        (rsv_witness_program_build_inputs), whose values Context.witness(d_inputs=...) takes per proof."""
         b = np.frombuffer(proof, dtype=np.uint8)
         walks = None if set_walks is None else np.ascontiguousarray(set_walks, dtype=np.uint8)
         if walks is not None and len(walks) != copies:
@@ -726,10 +743,22 @@ class WitnessProgram:
         c = PcsConfig(cfg.pow_bits, cfg.log_blowup_factor, cfg.log_last_layer_degree_bound, cfg.n_queries)
         pi = make_inputs(inputs)
         h = ctypes.c_void_p()
-        _check(lib.rsv_witness_program_build(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), copies,
-                                             walks.ctypes.data_as(_u8p) if walks is not None else None, device, ctypes.byref(h)),
-               "rsv_witness_program_build")
+        wp = walks.ctypes.data_as(_u8p) if walks is not None else None
+        if n_fixed is None:
+            _check(lib.rsv_witness_program_build(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), copies, wp, device,
+                                                 ctypes.byref(h)), "rsv_witness_program_build")
+        else:
+            _check(lib.rsv_witness_program_build_inputs(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), n_fixed, copies,
+                                                        wp, device, ctypes.byref(h)), "rsv_witness_program_build_inputs")
         return cls(_handle=h)
+
+    def inputs(self):
+        """-> (n_fixed, n_own, idx uint32[n_own]): the records a built program was made for (rsv_witness_program_inputs)."""
+        n_fixed, n_own = ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib.rsv_witness_program_inputs(self._h, ctypes.byref(n_fixed), ctypes.byref(n_own), None), "rsv_witness_program_inputs")
+        idx = np.zeros(n_own.value, np.uint32)
+        _check(lib.rsv_witness_program_inputs(self._h, None, None, idx.ctypes.data_as(_u32p)), "rsv_witness_program_inputs")
+        return int(n_fixed.value), int(n_own.value), idx
 
     def export(self):
         """-> witness_program.Program (instr, level_offsets, shape, flow_wires): what save / save_raw write and __init__ takes back."""
@@ -874,6 +903,21 @@ def _witness_batch(proofs: Sequence[bytes], program: WitnessProgram, inputs):
     lead = (program._h, blob.ctypes.data_as(_u8p), offsets.ctypes.data_as(_u64p), n, prepare_cfg(program.cfg(), n).ref(), make_inputs(items),
             len(items))
     return lead, n, np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+
+def _own_records(d_inputs, n: int, what: str) -> None:
+    """d_inputs has to be every proof's own records as the library reads them: a contiguous int32 tensor [n, n_own, 5] (a
+    slice such as inputs()[:, 3:, :] needs .contiguous(); fewer rows than proofs would be read past the end)."""
+    import torch
+    if d_inputs.dtype != torch.int32 or d_inputs.dim() != 3 or d_inputs.shape[0] != n or d_inputs.shape[2] != 5 or not d_inputs.is_contiguous():
+        raise ValueError(f"{what}: d_inputs has to be a contiguous int32 tensor of shape ({n}, n_own, 5), not {d_inputs.dtype} "
+                         f"{tuple(d_inputs.shape)}{'' if d_inputs.is_contiguous() else ', not contiguous'}")
+
+
+def witness_program_build(proof: bytes, cfg, inputs=STANDARD_INPUTS, copies: int = 1, device: int = 0, set_walks=None, n_fixed=None) -> WitnessProgram:
+    """WitnessProgram.build: n_fixed = None makes every input a constant of the program; else inputs[n_fixed:] are the
+    proof's own (rsv_witness_program_build_inputs)."""
+    return WitnessProgram.build(proof, cfg, inputs, copies, device, set_walks, n_fixed)
 
 
 def witness(proofs: Sequence[bytes], program: WitnessProgram, inputs=STANDARD_INPUTS, device: int = 0, with_flow: bool = False):
@@ -1281,13 +1325,22 @@ class Context:
                                         ctypes.byref(ho), d_accept.data_ptr(), ptr(d_reason)), "rsv_verify_hints_dev")
 
     def witness(self, program: WitnessProgram, d_blob, d_offsets, n: int, d_variables, d_accept, d_reason=None, inputs=STANDARD_INPUTS,
-                d_flow=None, d_flow_swap=None):
+                d_flow=None, d_flow_swap=None, d_inputs=None):
         """rsv_witness_eval_dev: d_variables uint32[n, n_vars, 4] in HBM (optionally the PoseidonFlow: d_flow uint32[n, flow_count,
-        32], d_flow_swap uint8[n, flow_count]); enqueued on the context's streams."""
+        32], d_flow_swap uint8[n, flow_count]); enqueued on the context's streams.  d_inputs: int32[n, n_own, 5], every
+        proof's own records behind the shared `inputs` (rsv_witness_eval_inputs_dev, for a program built with n_fixed)."""
         pi = make_inputs(inputs)
         pc = self.prepare_cfg(program.cfg(), n)
         self.acquire_from_torch()
         self._keep(pc, None)
+        if d_inputs is not None:
+            _own_records(d_inputs, n, "Context.witness")
+            _check(lib.rsv_witness_eval_inputs_dev(self._h, program._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), pi, len(list(inputs)),
+                                                   d_inputs.data_ptr(), int(d_inputs.shape[1]), d_variables.data_ptr(),
+                                                   d_flow.data_ptr() if d_flow is not None else None,
+                                                   d_flow_swap.data_ptr() if d_flow_swap is not None else None, d_accept.data_ptr(),
+                                                   d_reason.data_ptr() if d_reason is not None else None), "rsv_witness_eval_inputs_dev")
+            return
         _check(lib.rsv_witness_eval_dev(self._h, program._h, d_blob.data_ptr(), d_offsets.data_ptr(), n, pc.ref(), pi, len(list(inputs)),
                                         d_variables.data_ptr(), d_flow.data_ptr() if d_flow is not None else None,
                                         d_flow_swap.data_ptr() if d_flow_swap is not None else None, d_accept.data_ptr(),
@@ -1346,16 +1399,24 @@ class Context:
                "rsv_circuit_eval_dev")
 
     def witness_groups(self, program: WitnessProgram, d_blob, d_offsets, n_groups: int, d_variables, d_accept, d_member_accept,
-                       d_member_reason=None, inputs=STANDARD_INPUTS, d_flow=None, d_flow_swap=None):
+                       d_member_reason=None, inputs=STANDARD_INPUTS, d_flow=None, d_flow_swap=None, d_inputs=None):
         """rsv_witness_eval_groups_dev: the batch holds n_groups * copies proofs, copy c of group g's circuit verifies proof
         g * copies + c.  d_variables uint32[n_groups, n_vars, 4], d_accept uint8[n_groups], d_member_accept (and
         d_member_reason) uint8[n_groups * copies]; optionally d_flow uint32[n_groups, copies, flow_count, 32] and d_flow_swap
-        uint8[n_groups, copies, flow_count]; enqueued on the context's streams."""
+        uint8[n_groups, copies, flow_count]; enqueued on the context's streams.  d_inputs: int32[n_groups * copies, n_own, 5],
+        every member's own records behind the shared `inputs` (rsv_witness_eval_groups_inputs_dev)."""
         ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
         pi = make_inputs(inputs)
         pc = self.prepare_cfg(program.cfg(), n_groups * program.shape.copies)
         self.acquire_from_torch()
         self._keep(pc, None)
+        if d_inputs is not None:
+            _own_records(d_inputs, n_groups * program.shape.copies, "Context.witness_groups")
+            _check(lib.rsv_witness_eval_groups_inputs_dev(self._h, program._h, d_blob.data_ptr(), d_offsets.data_ptr(), n_groups, pc.ref(), pi,
+                                                          len(list(inputs)), d_inputs.data_ptr(), int(d_inputs.shape[1]), d_variables.data_ptr(),
+                                                          ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(), ptr(d_member_accept),
+                                                          ptr(d_member_reason)), "rsv_witness_eval_groups_inputs_dev")
+            return
         _check(lib.rsv_witness_eval_groups_dev(self._h, program._h, d_blob.data_ptr(), d_offsets.data_ptr(), n_groups, pc.ref(), pi,
                                                len(list(inputs)), d_variables.data_ptr(), ptr(d_flow), ptr(d_flow_swap), d_accept.data_ptr(),
                                                ptr(d_member_accept), ptr(d_member_reason)), "rsv_witness_eval_groups_dev")

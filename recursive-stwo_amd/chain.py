@@ -108,10 +108,13 @@ class Chain:
             if b not in self.done:
                 raise ValueError(f"Chain.{stage}() needs {b}() first")
 
-    def witness(self, proofs_or_blob, inputs, by_variable=False):
+    def witness(self, proofs_or_blob, inputs, by_variable=False, *, d_inputs=None):
         """Context.witness on proofs (a list of bytes) or a packed (blob, offsets): numpy arrays, or device tensors (uint8
         and int64[n + 1], what pack() returns), which are used as they are; by_variable: the context's witness_layout
-        option is "by_variable".  With aggregate: n * copies proofs, group after group."""
+        option is "by_variable".  With aggregate: n * copies proofs, group after group.  d_inputs: a device tensor
+        int32[n, n_own, 5] (with aggregate [n * copies, n_own, 5]), every proof's own records behind the shared `inputs` —
+        what inputs() of the chain that made the proofs returns, minus the shared records — for a program built with
+        n_fixed: the own inputs become this chain's statements."""
         import torch
         if isinstance(self.program, Circuit):
             raise ValueError("Chain.witness() evaluates the recursion circuit: a Circuit's witness comes through load()")
@@ -129,11 +132,11 @@ class Chain:
             self._flow, self._swap = self._new(n, m, F, 32, fill=0), self._new(n, m, F, flag=True, fill=0)
             self.member_accept, self.member_reason = self._new(n, m, flag=True, fill=0), self._new(n, m, flag=True, fill=0)
             self.ctx.witness_groups(wp, *self._blob, n, self._vars, self.acc, self.member_accept, self.member_reason, inputs=inputs,
-                                    d_flow=self._flow, d_flow_swap=self._swap)
+                                    d_flow=self._flow, d_flow_swap=self._swap, d_inputs=d_inputs)
         else:
             self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
-            self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap)
-            self._gather_inputs()
+            self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap, d_inputs=d_inputs)
+        self._gather_inputs()
         self.done = {"witness"}
 
     def load(self, variables, flow=None, swap=None, check=True, by_variable=False):
@@ -219,10 +222,11 @@ class Chain:
     def inputs(self):
         """-> the device tensor of the chain's own statements, int32[n, num_input, 5]: per witness the records (k,
         variables[k]) for k = 1 .. num_input, in the layout Context.verify_batch takes as d_inputs.  Written by witness(),
-        load() or evaluate() on the context's stream (Context.circuit_inputs); a built program's are the three constants.
-        Not with aggregate."""
+        load() or evaluate() on the context's stream (Context.circuit_inputs); a built program's are the three constants,
+        followed by the own inputs of the proofs it verifies where it was built with n_fixed (with aggregate: per group,
+        copy after copy)."""
         if self._inputs is None:
-            raise ValueError("Chain.inputs() needs witness(), load() or evaluate() first" + (" and is not for aggregate=True" if self.aggregate else ""))
+            raise ValueError("Chain.inputs() needs witness(), load() or evaluate() first")
         return self._inputs
 
     def verify(self, cfg):

@@ -9,8 +9,13 @@ extern "C" {
 
 int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
                               uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
+    return rsv_witness_program_build_inputs(proof, len, cfg, pi, n_pi, n_pi, copies, set_walks, device, out);
+}
+
+int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
+                                     size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
     if (!proof || !cfg || !out || (n_pi && !pi)) return RSV_E_NULL;
-    if (copies == 0 || copies > 64) return RSV_E_SIZE;
+    if (copies == 0 || copies > 64 || n_fixed > n_pi || n_pi - n_fixed > MAX_OWN_INPUTS) return RSV_E_SIZE;
     Template d{};
     int rc = parse_template(proof, len, d);
     if (rc != RSV_OK) return rc;
@@ -42,7 +47,7 @@ int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_co
     std::vector<std::pair<uint32_t, Q4>> inputs;
     for (size_t i = 0; i < n_pi; i++) inputs.push_back({pi[i].idx, Q4{pi[i].value[0], pi[i].value[1], pi[i].value[2], pi[i].value[3]}});
     BuiltProgram bp;
-    rc = build_program(d, flow.data(), swap.data(), flow_count, inputs, copies, set_walks, bp, g_debug_log.load() != 0);
+    rc = build_program(d, flow.data(), swap.data(), flow_count, inputs, n_fixed, copies, set_walks, bp, g_debug_log.load() != 0);
     if (rc != RSV_OK) return rc;
     rsv_witness_shape shape{d.lp, d.lq, d.pow_bits, d.blowup, d.log_last, d.nq, d.n_inner, flow_count, copies};
     rsv_witness_program* prog = nullptr;
@@ -53,6 +58,15 @@ int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_co
     prog->gates = std::move(bp.gates);
     prog->witness_ops = std::move(bp.witness_ops);
     prog->copy_of = std::move(bp.copy_of);
+    prog->num_input = bp.num_input;
+    prog->inputs_known = true;
+    for (size_t i = 0; i < n_pi; i++) (i < n_fixed ? prog->fixed_idx : prog->own_idx).push_back(pi[i].idx);
+    if (!prog->own_idx.empty() &&  // the statement check's table (k_witness_statement)
+        (hipMalloc(reinterpret_cast<void**>(&prog->d_own_idx), prog->own_idx.size() * 4) != hipSuccess ||
+         hipMemcpy(prog->d_own_idx, prog->own_idx.data(), prog->own_idx.size() * 4, hipMemcpyHostToDevice) != hipSuccess)) {
+        rsv_witness_program_destroy(prog);
+        return RSV_E_DEVICE;
+    }
     *out = prog;
     return RSV_OK;
 }

@@ -64,7 +64,7 @@ struct FlowRecord {           // one Poseidon2HalfVar::permute invocation (plonk
     uint32_t addr;            // SwapOption::addr
 };
 
-enum Mode { WITNESS, CONSTANT };
+enum Mode { WITNESS, CONSTANT, PUBLIC };  // PUBLIC: AllocationMode::PublicInput (plonk_with_poseidon.rs:236-252)
 
 struct GateRow { uint32_t a, b, c, op, poseidon_wire, enforce_c_m31; };  // one Plonk row (plonk_with_poseidon.rs:23-36)
 struct WitnessOp3 { uint32_t row, bit, constant; };  // a row whose `op` follows the witness: op = variables[bit] ? constant : 0
@@ -80,6 +80,7 @@ struct ConstraintSystem {
     std::vector<GateRow> rows;
     std::vector<WitnessOp3> witness_ops;
     std::unordered_map<std::string, uint32_t> cache;
+    uint32_t num_input = 3;            // 1, i, j and every new_qm31(PUBLIC)
     bool have_hint = false;
     Instr hint{};
 
@@ -149,7 +150,10 @@ struct ConstraintSystem {
     }
     uint32_t new_qm31(const Q4& v, Mode mode) {
         const uint32_t c = push(v, take_origin(mode, v));
-        if (mode == CONSTANT) {
+        if (mode == PUBLIC) {  // the reference's row of a public input enforces M31 (:243-249)
+            row(c, 0, c, 1, 0, 1);
+            num_input++;
+        } else if (mode == CONSTANT) {
             const uint32_t a0 = new_m31(v[0], CONSTANT), a1 = new_m31(v[1], CONSTANT), a2 = new_m31(v[2], CONSTANT), a3 = new_m31(v[3], CONSTANT);
             uint32_t t = mul(a1, 2);
             const uint32_t a = add(a0, t);
@@ -235,6 +239,14 @@ inline Var qm31_one(ConstraintSystem* cs) { return mk(cs, {1, 0, 0, 0}, 1, 4); }
 inline Var qm31_witness(ConstraintSystem* cs, const Q4& v, const Instr& hint) {
     cs->set_hint(hint);
     return mk(cs, v, cs->new_qm31(v, WITNESS), 4);
+}
+// record k of the own public inputs of the proof that copy `copy` verifies: allocated before any copy starts (the reference
+// asserts that public inputs come first), so the copy is written down here
+inline Var qm31_public_input(ConstraintSystem* cs, const Q4& v, uint32_t k, uint32_t copy) {
+    cs->set_hint(mk_instr(W_INPUT, 0, 0, k));
+    const uint32_t c = cs->new_qm31(v, PUBLIC);
+    cs->copy_of[c] = (uint8_t)copy;
+    return mk(cs, v, c, 4);
 }
 inline Var qm31_constant(ConstraintSystem* cs, const Q4& v) {
     const Q4 fixed[4] = {{0, 0, 0, 0}, {1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};

@@ -129,6 +129,7 @@ inline int check_program(const uint32_t* instr, size_t n_instr, const uint32_t* 
             case W_NONCE: ok = i0 < 3; break;
             case W_TRACE_COL: ok = i0 < 4 && i1 < s.n_queries && i2 < 64; break;
             case W_FRI_COL: ok = i0 <= s.n_inner && i1 < s.n_queries && i2 < 24 && (i2 & 3) == 0; break;
+            case W_INPUT: ok = i0 < MAX_OWN_INPUTS; break;  // (below the batch's n_own: input_slots, checked by the evaluating call)
             default: ok = false;
             }
             if (!ok) { if (log) fprintf(stderr, "[rsv] witness program: instruction %u (op %u, dst %u, a %u, b %u, imm %u %u %u) is out of range\n", k, op, dst, a, b, i0, i1, i2); return RSV_E_RANGE; }
@@ -146,19 +147,51 @@ struct BuiltProgram {
     std::vector<uint32_t> instr, level_offsets, flow_wires, gates, witness_ops;
     std::vector<uint8_t> copy_of;  // [n_vars]: the copy of the verifier that allocated the variable (the grouped witness kernels
                                    // read it for hint instructions: copy c's hints are those of the group's proof c)
+    uint32_t num_input = 3;        // 3 + copies * n_own
 };
 
+// The gadgets run copy after copy, so a copy's variables are one contiguous range (marks: [copies + 1]), and every hint (an
+// instruction that reads the proof, its flow or its queried columns) lies in the range of the copy it was recorded for.
+// What copy 1 .. reuses of copy 0 are the cached constants: W_CONST, never a hint.  The own inputs come before every
+// copy: record k of copy c's proof is variable 4 + c * n_own + k, and nothing else is a W_INPUT.
+inline int check_copies(const std::vector<Instr>& origin, const std::vector<uint8_t>& copy_of, const std::vector<uint32_t>& marks,
+                        uint32_t copies, uint32_t n_own, bool log = false) {
+    const size_t n_vars = origin.size();
+    if (marks.size() != (size_t)copies + 1 || copy_of.size() != n_vars || marks[copies] != n_vars) return RSV_E_RANGE;
+    const size_t first = 4, end = first + (size_t)copies * n_own;
+    if (end > n_vars || marks[0] != end) return RSV_E_RANGE;
+    for (size_t k = 0; k < n_vars; k++) {
+        const uint32_t c = copy_of[k];
+        const bool input = k >= first && k < end;
+        if (input ? (origin[k].op != W_INPUT || c != (k - first) / n_own || origin[k].imm[0] != (k - first) % n_own)
+                  : (origin[k].op == W_INPUT ||
+                     (origin[k].op >= W_FLOW && (c >= copies || k < marks[c] || k >= marks[c + 1])))) {
+            if (log) fprintf(stderr, "[rsv] witness program build: hint variable %zu lies outside copy %u\n", k, c);
+            return RSV_E_RANGE;
+        }
+    }
+    return RSV_OK;
+}
+
 // d: the parsed template with its hint pointers set; flow / swap: the PoseidonFlow of ONE copy of the verifier.
+// inputs[0 .. n_fixed) are constants of the program; inputs[n_fixed ..) are the proof's OWN inputs (n_own of them), the
+// template's values: PublicInput variables 4 + c * n_own + k, allocated before the first copy, which the program reads
+// with W_INPUT (imm0 = k).  With n_fixed = inputs.size() the program is the one without own inputs.
 inline int build_program(const Template& d, const uint32_t* flow, const uint8_t* swap, uint32_t flow_count,
-                         const std::vector<std::pair<uint32_t, Q4>>& inputs, uint32_t copies, const uint8_t* set_walks, BuiltProgram& out,
-                         bool log = false) {
+                         const std::vector<std::pair<uint32_t, Q4>>& inputs, size_t n_fixed, uint32_t copies, const uint8_t* set_walks,
+                         BuiltProgram& out, bool log = false) {
+    if (n_fixed > inputs.size() || inputs.size() - n_fixed > MAX_OWN_INPUTS) return RSV_E_SIZE;
+    const uint32_t n_own = (uint32_t)(inputs.size() - n_fixed);
     ConstraintSystem cs;
     FlowSource fsrc{flow, swap, flow_count, 0};
     Gadgets g{&cs, &fsrc};
     try {
+        std::vector<std::vector<Var>> own(copies);
+        for (uint32_t c = 0; c < copies; c++)
+            for (uint32_t k = 0; k < n_own; k++) own[c].push_back(qm31_public_input(&cs, inputs[n_fixed + k].second, k, c));
         for (uint32_t c = 0; c < copies; c++) {
             cs.begin_copy();
-            verify_in_circuit(g, d, inputs, set_walks ? (set_walks[c] & 3u) : 0u);
+            verify_in_circuit(g, d, inputs, own[c], set_walks ? (set_walks[c] & 3u) : 0u);
         }
     } catch (const std::exception& e) {
         if (log) fprintf(stderr, "[rsv] witness program build: %s\n", e.what());
@@ -168,18 +201,9 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
 
     // one instruction per variable, sorted by dependency depth
     const size_t n_vars = cs.variables.size();
-    // The gadgets run copy after copy, so a copy's variables are one contiguous range, and every hint (an instruction that
-    // reads the proof, its flow or its queried columns) lies in the range of the copy it was recorded for.  What copy 1 ..
-    // reuses of copy 0 are the cached constants: W_CONST, never a hint.
     cs.copy_marks.push_back((uint32_t)n_vars);
-    if (cs.copy_marks.size() != (size_t)copies + 1 || cs.copy_of.size() != n_vars) return RSV_E_RANGE;
-    for (size_t k = 0; k < n_vars; k++) {
-        const uint32_t c = cs.copy_of[k];
-        if (cs.origin[k].op >= W_FLOW && (c >= copies || k < cs.copy_marks[c] || k >= cs.copy_marks[c + 1])) {
-            if (log) fprintf(stderr, "[rsv] witness program build: hint variable %zu lies outside copy %u\n", k, c);
-            return RSV_E_RANGE;
-        }
-    }
+    if (check_copies(cs.origin, cs.copy_of, cs.copy_marks, copies, n_own, log) != RSV_OK) return RSV_E_RANGE;
+    out.num_input = cs.num_input;
     std::vector<uint32_t> depth(n_vars, 0);
     uint32_t max_depth = 0;
     for (size_t k = 0; k < n_vars; k++) {
@@ -217,6 +241,12 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
     for (const WitnessOp3& wo : cs.witness_ops)
         for (uint32_t v : {wo.row, wo.bit, wo.constant}) out.witness_ops.push_back(v);
     return RSV_OK;
+}
+// every input a constant of the program
+inline int build_program(const Template& d, const uint32_t* flow, const uint8_t* swap, uint32_t flow_count,
+                         const std::vector<std::pair<uint32_t, Q4>>& inputs, uint32_t copies, const uint8_t* set_walks, BuiltProgram& out,
+                         bool log = false) {
+    return build_program(d, flow, swap, flow_count, inputs, inputs.size(), copies, set_walks, out, log);
 }
 
 }  // namespace rsv::circuit

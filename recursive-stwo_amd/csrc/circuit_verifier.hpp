@@ -724,16 +724,25 @@ inline void folding(Gadgets& g, const ProofVar& pv, const Template& d, const Fia
     }
 }
 
-// One copy of the verifier: the body of the `multipliers` loop (examples/multi-proofs/src/main.rs:66-139)
-inline void verify_in_circuit(Gadgets& g, const Template& d, const std::vector<std::pair<uint32_t, Q4>>& public_inputs, uint32_t walk) {
+// One copy of the verifier: the body of the `multipliers` loop (examples/multi-proofs/src/main.rs:66-139).  The first
+// public_inputs.size() - own.size() records are constants of the circuit; the others are the variables `own` (the proof's own
+// inputs, allocated PublicInput by the caller), whose idx stays a constant.
+inline void verify_in_circuit(Gadgets& g, const Template& d, const std::vector<std::pair<uint32_t, Q4>>& public_inputs, const std::vector<Var>& own,
+                              uint32_t walk) {
     ConstraintSystem* cs = g.cs;
+    if (own.size() > public_inputs.size()) throw std::logic_error("more own inputs than records");
+    const size_t n_fixed = public_inputs.size() - own.size();
     std::vector<std::pair<uint32_t, Var>> inputs;
-    for (const auto& [idx, val] : public_inputs) inputs.push_back({idx, qm31_constant(cs, val)});
+    for (size_t i = 0; i < public_inputs.size(); i++)
+        inputs.push_back({public_inputs[i].first, i < n_fixed ? qm31_constant(cs, public_inputs[i].second) : own[i - n_fixed]});
     ProofVar pv = allocate_proof(cs, d);
     const FiatShamir fs = fiat_shamir(g, pv, d, inputs);
     composition_check(pv, d, fs);
     Answer ans = answer(g, pv, d, fs, walk);
     folding(g, pv, d, fs, ans);
+}
+inline void verify_in_circuit(Gadgets& g, const Template& d, const std::vector<std::pair<uint32_t, Q4>>& public_inputs, uint32_t walk) {
+    verify_in_circuit(g, d, public_inputs, {}, walk);
 }
 
 }  // namespace rsv::circuit

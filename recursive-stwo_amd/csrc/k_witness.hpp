@@ -38,8 +38,23 @@ struct WitnessGroupArgs : WitnessArgs {
     const uint8_t* copy_of;  // [n_vars]: the copy that allocated a variable (circuit_program.hpp), read for hints only
     uint32_t copies;
 };
+// The forms with per-proof public inputs (rsv_witness_eval_inputs_dev, rsv_witness_eval_groups_inputs_dev): W_INPUT reads
+// record imm0 of the proof's (grouped: the member's) own records.  Argument types of their own, so that the kernels above
+// them stay the instructions they were; the launcher takes these only for a program that has a W_INPUT.
+struct WitnessInputArgs : WitnessArgs {
+    const PubInput* own;  // [n][n_own]: the caller's records, as rsv_verify_batch_inputs_dev takes them
+    uint32_t n_own;
+};
+struct WitnessGroupInputArgs : WitnessGroupArgs {
+    const PubInput* own;  // [n * copies][n_own]
+    uint32_t n_own;
+};
 template <class A> struct witness_grouped { static constexpr bool value = false; };
 template <> struct witness_grouped<WitnessGroupArgs> { static constexpr bool value = true; };
+template <> struct witness_grouped<WitnessGroupInputArgs> { static constexpr bool value = true; };
+template <class A> struct witness_inputs { static constexpr bool value = false; };
+template <> struct witness_inputs<WitnessInputArgs> { static constexpr bool value = true; };
+template <> struct witness_inputs<WitnessGroupInputArgs> { static constexpr bool value = true; };
 
 // one instruction (its eight words: w0 = op, dst, a, b; w1 = imm0..3) for one proof
 template <class A>
@@ -51,6 +66,11 @@ __device__ __forceinline__ void witness_exec(const A& a, const uint4 w0, const u
         if (op >= W_FLOW && ok) q = (size_t)p * a.copies + a.copy_of[dst];
     const auto hint = [&]() {  // the ops that read what the verifying pass left
         uint4 r = make_uint4(0, 0, 0, 0);
+        if constexpr (witness_inputs<A>::value)
+            if (op == W_INPUT) {  // (imm0 < n_own: the evaluating call checked the program against the batch's n_own)
+                if (ok) r = u4_words(a.own[q * a.n_own + i0].value);
+                return r;
+            }
         switch (op) {
         case W_FLOW:
             if (ok) r = a.flow[(q * a.flow_stride + i0) * 8 + (i1 >> 2)];
@@ -96,6 +116,8 @@ __device__ __forceinline__ void witness_level(const A& a) {
 }
 __global__ __launch_bounds__(256) void k_witness_level(WitnessArgs a) { witness_level(a); }
 __global__ __launch_bounds__(256) void k_witness_level_g(WitnessGroupArgs a) { witness_level(a); }
+__global__ __launch_bounds__(256) void k_witness_level_i(WitnessInputArgs a) { witness_level(a); }
+__global__ __launch_bounds__(256) void k_witness_level_gi(WitnessGroupInputArgs a) { witness_level(a); }
 
 // the same for batches of at least a wave of proofs: blockIdx.y = the instruction, so that the instruction words are scalar
 // loads and the switch a scalar branch (in the 1-D form a wave may straddle two instructions, and every lane divides)
@@ -107,6 +129,8 @@ __device__ __forceinline__ void witness_level_wide(const A& a) {
 }
 __global__ __launch_bounds__(256) void k_witness_level_wide(WitnessArgs a) { witness_level_wide(a); }
 __global__ __launch_bounds__(256) void k_witness_level_wide_g(WitnessGroupArgs a) { witness_level_wide(a); }
+__global__ __launch_bounds__(256) void k_witness_level_wide_i(WitnessInputArgs a) { witness_level_wide(a); }
+__global__ __launch_bounds__(256) void k_witness_level_wide_gi(WitnessGroupInputArgs a) { witness_level_wide(a); }
 
 // Levels l0 .. l1 walked by ONE workgroup for its own proofs (dependencies never cross proofs): instruction slot `slot` of
 // `n_slots` takes instructions begin + slot, + n_slots, ... of every level, a workgroup barrier ends a level (the waves of
@@ -137,6 +161,15 @@ __global__ __launch_bounds__(256) void k_witness_strip_g(WitnessGroupArgs a, con
     witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
 }
 
+__global__ __launch_bounds__(256) void k_witness_strip_i(WitnessInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
+    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
+}
+__global__ __launch_bounds__(256) void k_witness_strip_gi(WitnessGroupInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
+    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
+}
+
 // Small and medium batches: the WHOLE program in one launch.  A workgroup of 1 024 lanes owns P2 = 2^log_p2 proofs (n <= 4:
 // one workgroup, P2 = n rounded up — the reference's own use is ONE proof per recursion step; larger batches: P2 proofs per
 // workgroup, n / P2 workgroups side by side — dependencies never cross proofs) and walks the levels on its own:
@@ -150,6 +183,17 @@ __global__ __launch_bounds__(1024) void k_witness_small(WitnessArgs a, const uin
 }
 __global__ __launch_bounds__(1024) void k_witness_small_g(WitnessGroupArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
                                                           uint32_t log_p2) {
+    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
+    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
+}
+
+__global__ __launch_bounds__(1024) void k_witness_small_i(WitnessInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
+                                                          uint32_t log_p2) {
+    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
+    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
+}
+__global__ __launch_bounds__(1024) void k_witness_small_gi(WitnessGroupInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
+                                                           uint32_t log_p2) {
     const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
     witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
 }

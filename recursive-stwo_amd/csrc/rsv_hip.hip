@@ -111,6 +111,8 @@ struct rsv_ctx {
     size_t ws_rows_bytes = 0;
     void* ws_witness = nullptr;  // rsv_witness_eval_dev: the hints it asks the verifying pass for, and variables[var][proof]
     size_t ws_witness_bytes = 0;
+    void* ws_inputs = nullptr;   // rsv_witness_eval_inputs_dev: the record array of the verifying pass, the shared records, the statement flags
+    size_t ws_inputs_bytes = 0;
     void* ws_interaction = nullptr;  // rsv_witness_interaction_dev: zero flags, shifts, chunk prefixes
     size_t ws_interaction_bytes = 0;
     void* ws_commit = nullptr;  // rsv_commit_tree_dev: coefficients, LDE blocks, node layers of one pass
@@ -246,6 +248,7 @@ void rsv_ctx_destroy(rsv_ctx* c) {
     if (c->ws_fixed) (void)hipFree(c->ws_fixed);
     if (c->ws_rows) (void)hipFree(c->ws_rows);
     if (c->ws_witness) (void)hipFree(c->ws_witness);
+    if (c->ws_inputs) (void)hipFree(c->ws_inputs);
     if (c->ws_interaction) (void)hipFree(c->ws_interaction);
     if (c->ws_commit) (void)hipFree(c->ws_commit);
     if (c->ws_chain) (void)hipFree(c->ws_chain);

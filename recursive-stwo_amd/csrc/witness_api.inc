@@ -42,6 +42,14 @@ struct rsv_witness_program {
     rsv::ceval::Program ce;
     uint32_t* d_ce_instr = nullptr;
     uint32_t* d_ce_index = nullptr;
+    // Per-proof public inputs (rsv_witness_program_build_inputs, rsv_witness_eval_inputs_dev).  input_slots: 1 + the largest
+    // imm0 of a W_INPUT, 0 for a program without one (every program has it: rsv_witness_program_create).  A built program
+    // also knows the records it was built for (inputs_known): the idx of the n_fixed shared ones and of the n_own own ones;
+    // d_own_idx: the latter on the device, uploaded by the builder.
+    uint32_t input_slots = 0;
+    bool inputs_known = false;
+    std::vector<uint32_t> fixed_idx, own_idx;
+    uint32_t* d_own_idx = nullptr;
 };
 
 namespace {
@@ -77,6 +85,34 @@ __global__ void k_witness_group_accept(const uint8_t* __restrict__ members, uint
     accept[g] = all;
 }
 
+// Per-proof public inputs: rec[p] = the n_fixed shared records (fixed, in HBM), then proof p's n_own own ones — the array
+// the verifying pass takes; one lane per word.  The lanes of an own record's words also check the statement against what
+// the circuit can hold: idx is the program's (own_idx, NULL for a program made from instructions: not checked), and the
+// value is an M31 — words 1..3 zero, word 0 below P (the PublicInput row enforces M31).  bad[p] is set otherwise (zeroed by the caller).
+__global__ __launch_bounds__(256) void k_witness_statement(const uint32_t* __restrict__ fixed, uint32_t n_fixed, const uint32_t* __restrict__ own,
+                                                           uint32_t n_own, const uint32_t* __restrict__ own_idx, uint32_t n,
+                                                           uint32_t* __restrict__ rec, uint8_t* __restrict__ bad) {
+    const uint32_t n_pi = n_fixed + n_own;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)n * n_pi * PI_WORDS) return;
+    const uint32_t w = (uint32_t)(i % PI_WORDS);
+    const size_t kp = i / PI_WORDS;
+    const uint32_t k = (uint32_t)(kp % n_pi), p = (uint32_t)(kp / n_pi);
+    if (k < n_fixed) { rec[i] = fixed[(size_t)k * PI_WORDS + w]; return; }
+    const uint32_t j = k - n_fixed;
+    const uint32_t v = own[((size_t)p * n_own + j) * PI_WORDS + w];
+    rec[i] = v;
+    const bool good = w == 0 ? (!own_idx || v == own_idx[j]) : w == 1 ? v < P : v == 0;
+    if (!good) bad[p] = 1;  // (every writer stores the same byte)
+}
+// ... and behind the verifying pass: a proof whose statement the circuit cannot hold is rejected, as bad statement data is
+__global__ void k_witness_statement_verdict(const uint8_t* __restrict__ bad, uint32_t n, uint8_t* __restrict__ accept, uint8_t* __restrict__ reason) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n || !bad[p]) return;
+    accept[p] = 0;
+    if (reason) reason[p] = (uint8_t)R_PARSE;
+}
+
 // The kernels of the two forms of the evaluation (k_witness.hpp): a batch of proofs, and groups of `copies` proofs.
 struct WitnessKernels {
     static constexpr auto level = k_witness_level, level_wide = k_witness_level_wide;
@@ -87,6 +123,17 @@ struct WitnessGroupKernels {
     static constexpr auto level = k_witness_level_g, level_wide = k_witness_level_wide_g;
     static constexpr auto strip = k_witness_strip_g;
     static constexpr auto small = k_witness_small_g;
+};
+
+struct WitnessInputKernels {
+    static constexpr auto level = k_witness_level_i, level_wide = k_witness_level_wide_i;
+    static constexpr auto strip = k_witness_strip_i;
+    static constexpr auto small = k_witness_small_i;
+};
+struct WitnessGroupInputKernels {
+    static constexpr auto level = k_witness_level_gi, level_wide = k_witness_level_wide_gi;
+    static constexpr auto strip = k_witness_strip_gi;
+    static constexpr auto small = k_witness_small_gi;
 };
 
 // The program over n proofs (or n groups: a.n = n), in the launch form the batch size and the context's options choose.
@@ -151,7 +198,7 @@ struct WitnessStage {
     const uint32_t* flow = nullptr;     // NULL unless eval() was asked to keep the flow records
     const uint8_t* swap = nullptr;
     const uint8_t* accept = nullptr;
-    DevBuf d_blob, d_offsets, d_vars, d_flow, d_swap, d_accept, d_reason;
+    DevBuf d_blob, d_offsets, d_vars, d_flow, d_swap, d_accept, d_reason, d_own;
 
     ~WitnessStage() { rsv_ctx_destroy(c); }
 
@@ -169,8 +216,9 @@ struct WitnessStage {
         return RSV_OK;
     }
 
+    // own, n_own: every proof's own records [n][n_own] (host), behind the n_pi shared ones (rsv_witness_eval_inputs)
     int eval(const rsv_witness_program* prog, const uint8_t* blob, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi,
-             bool keep_flow) {
+             bool keep_flow, const rsv_public_input* own = nullptr, size_t n_own = 0) {
         const uint64_t base = offsets[0], total = offsets[n] - base;
         std::vector<uint64_t> rel(n + 1);
         for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
@@ -192,6 +240,13 @@ struct WitnessStage {
         flow = d_flow.as<uint32_t>();
         swap = d_swap.as<uint8_t>();
         accept = d_accept.as<uint8_t>();
+        if (n_own) {
+            HIP_TRY(d_own.alloc(sizeof(rsv_public_input) * n * n_own));
+            HIP_TRY(hipMemcpy(d_own.p, own, sizeof(rsv_public_input) * n * n_own, hipMemcpyHostToDevice));
+            return rsv_witness_eval_inputs_dev(c, prog, d_blob.as<const uint8_t>(), d_offsets.as<const uint64_t>(), n, cfg, pi, n_pi,
+                                               d_own.as<const rsv_public_input>(), n_own, d_vars.as<uint32_t>(), d_flow.as<uint32_t>(),
+                                               d_swap.as<uint8_t>(), d_accept.as<uint8_t>(), d_reason.as<uint8_t>());
+        }
         return rsv_witness_eval_dev(c, prog, d_blob.as<const uint8_t>(), d_offsets.as<const uint64_t>(), n, cfg, pi, n_pi, d_vars.as<uint32_t>(),
                                     d_flow.as<uint32_t>(), d_swap.as<uint8_t>(), d_accept.as<uint8_t>(), d_reason.as<uint8_t>());
     }
@@ -225,6 +280,8 @@ int rsv_witness_program_create(const uint32_t* instr, size_t n_instr, const uint
     p->n_vars = n_vars;
     p->shape = *shape;
     p->level_offsets.assign(level_offsets, level_offsets + n_levels + 1);
+    for (size_t k = 0; k < n_instr; k++)
+        if (instr[k * 8] == W_INPUT && instr[k * 8 + 4] >= p->input_slots) p->input_slots = instr[k * 8 + 4] + 1;
     p->strip_from = (uint32_t)n_levels;
     while (p->strip_from > 0 && level_offsets[p->strip_from] - level_offsets[p->strip_from - 1] <= STRIP_WIDTH) p->strip_from--;
     if (n_levels - p->strip_from < 8) p->strip_from = (uint32_t)n_levels;  // not worth a launch of its own
@@ -251,6 +308,7 @@ void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (p->d_trace_ops) (void)hipFree(p->d_trace_ops);
     if (p->d_trace_pre) (void)hipFree(p->d_trace_pre);
     if (p->d_copy_of) (void)hipFree(p->d_copy_of);
+    if (p->d_own_idx) (void)hipFree(p->d_own_idx);
     if (p->d_uc_rows) (void)hipFree(p->d_uc_rows);
     if (p->d_uc_flow) (void)hipFree(p->d_uc_flow);
     if (p->d_ce_instr) (void)hipFree(p->d_ce_instr);
@@ -295,22 +353,30 @@ int rsv_witness_group_scratch_bytes(const rsv_witness_program* prog, size_t n_gr
     return RSV_OK;
 }
 
-// What both forms of the evaluation do before the program runs: the configuration check, the scratch, the verifying pass
-// over `members` proofs with the hint outputs the program reads, and the members' verdicts (d_verdict, d_reason: the pass's,
-// then k_witness_gate).  Fills `a` for `rows` vectors, all but a.accept.
-static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
-                         size_t rows, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables,
-                         uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_verdict, uint8_t* d_reason, WitnessArgs& a) {
+// the program belongs to one configuration: the batch has to be verified under exactly that one
+static int witness_check_cfg(const rsv_witness_program* prog, const rsv_cfg_set* cfg) {
     const rsv_witness_shape& s = prog->shape;
-    // the program belongs to one configuration: the batch has to be verified under exactly that one
     if (!cfg || !cfg->cfgs || cfg->n_cfgs != 1 || cfg->cfg_of) return RSV_E_SIZE;
     const rsv_pcs_config& pc = cfg->cfgs[0];
     if (pc.pow_bits != s.pow_bits || pc.log_blowup_factor != s.log_blowup || pc.log_last_layer_degree_bound != s.log_last ||
         pc.n_queries != s.n_queries)
         return RSV_E_SIZE;
+    return RSV_OK;
+}
+
+// What both forms of the evaluation do before the program runs: the configuration check, the scratch, the verifying pass
+// over `members` proofs with the hint outputs the program reads, and the members' verdicts (d_verdict, d_reason: the pass's,
+// then k_witness_gate).  Fills `a` for `rows` vectors, all but a.accept.  d_own_pi: NULL — `pi` is the batch's one table, in
+// host memory; else [members][n_pi] records in HBM, every proof its own (rsv_verify_hints_inputs_dev).
+static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
+                         size_t rows, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_own_pi,
+                         uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_verdict, uint8_t* d_reason, WitnessArgs& a) {
+    const rsv_witness_shape& s = prog->shape;
+    int rc = witness_check_cfg(prog, cfg);
+    if (rc != RSV_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const bool by_variable = c->opt.witness_layout == 2;  // the caller takes vars[variable][row] as the kernels write it
-    int rc = ensure_buf(c, &c->ws_witness, &c->ws_witness_bytes, witness_carve(prog, nullptr, members, rows, !by_variable).bytes);
+    rc = ensure_buf(c, &c->ws_witness, &c->ws_witness_bytes, witness_carve(prog, nullptr, members, rows, !by_variable).bytes);
     if (rc != RSV_OK) return rc;
     const size_t nq = s.n_queries, nt = 1 + (size_t)s.n_inner;
     const uint32_t M = (s.log_size_plonk + 1 > s.log_size_poseidon + 2 ? s.log_size_plonk + 1 : s.log_size_poseidon + 2) + s.log_blowup;
@@ -332,7 +398,8 @@ static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint
     // a proof of another shape may be shorter than the program's columns: nothing of an earlier batch may be read for it
     HIP_TRY(hipMemsetAsync(w.trace_cols, 0, members * 4 * nq * 64 * 4, c->stream));
     HIP_TRY(hipMemsetAsync(w.fri_cols, 0, members * nt * nq * 24 * 4, c->stream));
-    rc = rsv_verify_hints_dev(c, d_blob, d_offsets, members, cfg, pi, n_pi, &ho, d_verdict, d_reason);
+    rc = d_own_pi ? rsv_verify_hints_inputs_dev(c, d_blob, d_offsets, members, cfg, d_own_pi, n_pi, &ho, d_verdict, d_reason)
+                  : rsv_verify_hints_dev(c, d_blob, d_offsets, members, cfg, pi, n_pi, &ho, d_verdict, d_reason);
     if (rc != RSV_OK) return rc;
     hipLaunchKernelGGL(k_witness_gate, dim3(grid_for(members, 256)), dim3(256), 0, c->stream, c->last_metas, (uint32_t)members, s, d_verdict);
     a.instr = prog->d_instr; a.n = (uint32_t)rows; a.vars = w.vars; a.blob = d_blob; a.offsets = d_offsets; a.metas = c->last_metas;
@@ -350,36 +417,119 @@ static int witness_finish(rsv_ctx* c, const rsv_witness_program* prog, const uin
     return RSV_OK;
 }
 
+// What the per-proof forms refuse before any device work (include/rsv.h): members = the proofs of the batch.
+static int witness_check_own(const rsv_witness_program* prog, const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* d_pi,
+                             size_t n_own, size_t members) {
+    if ((n_fixed && !pi_fixed) || (n_own && !d_pi)) return RSV_E_NULL;
+    if (n_fixed > 4096 || n_own > MAX_OWN_INPUTS || n_fixed + n_own > 4096) return RSV_E_SIZE;
+    if (prog->inputs_known) {  // a built program: the records it was built for
+        if (n_fixed != prog->fixed_idx.size() || n_own != prog->own_idx.size()) return RSV_E_SIZE;
+        for (size_t k = 0; k < n_fixed; k++)
+            if (pi_fixed[k].idx != prog->fixed_idx[k]) return RSV_E_SIZE;
+    } else if (prog->input_slots > n_own) return RSV_E_SIZE;  // made from instructions: every W_INPUT's imm0 lies below n_own
+    if ((uint64_t)members * (n_fixed + n_own) > RSV_MAX_INPUT_RECORDS) return RSV_E_SIZE;
+    if ((uintptr_t)d_pi & 3) return RSV_E_SIZE;
+    return RSV_OK;
+}
+// ... and of the batch itself: what the verifying pass would refuse, ahead of the statement kernel, so that a refused call
+// has enqueued nothing
+static int witness_check_batch(const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
+                               const rsv_cfg_set* cfg) {
+    const int rc = witness_check_cfg(prog, cfg);
+    if (rc != RSV_OK) return rc;
+    if (members && (!d_blob || !d_offsets)) return RSV_E_NULL;
+    if (((uintptr_t)d_blob & 3) || ((uintptr_t)d_offsets & 7)) return RSV_E_SIZE;
+    return RSV_OK;
+}
+
+// The per-proof forms, ahead of the verifying pass: the record array it takes, [members][n_fixed + n_own], assembled in the
+// context's scratch from the shared records (host) and the caller's own ones (HBM), and the statement check; no host
+// synchronisation.  -> rec, bad [members] (k_witness_statement).
+static int witness_statement(rsv_ctx* c, const rsv_witness_program* prog, const rsv_public_input* pi_fixed, size_t n_fixed,
+                             const rsv_public_input* d_pi, size_t n_own, size_t members, const rsv_public_input** rec, const uint8_t** bad) {
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t n_pi = n_fixed + n_own, words = members * n_pi * PI_WORDS;
+    Carve sz{nullptr};
+    sz.take<uint32_t>(words); sz.take<uint32_t>(n_fixed * PI_WORDS); sz.take<uint8_t>(members);
+    int rc = ensure_buf(c, &c->ws_inputs, &c->ws_inputs_bytes, sz.off);
+    if (rc != RSV_OK) return rc;
+    Carve cv{static_cast<char*>(c->ws_inputs)};
+    uint32_t* d_rec = cv.take<uint32_t>(words);
+    uint32_t* d_fixed = cv.take<uint32_t>(n_fixed * PI_WORDS);
+    uint8_t* d_bad = cv.take<uint8_t>(members);
+    if (n_fixed) HIP_TRY(hipMemcpyAsync(d_fixed, pi_fixed, sizeof(rsv_public_input) * n_fixed, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(d_bad, 0, members, c->stream));
+    hipLaunchKernelGGL(k_witness_statement, dim3(grid_for(words, 256)), dim3(256), 0, c->stream, d_fixed, (uint32_t)n_fixed,
+                       reinterpret_cast<const uint32_t*>(d_pi), (uint32_t)n_own, prog->d_own_idx, (uint32_t)members, d_rec, d_bad);
+    *rec = reinterpret_cast<const rsv_public_input*>(d_rec);
+    *bad = d_bad;
+    return RSV_OK;
+}
+
+// rsv_witness_eval_dev (d_pi NULL, n_own 0: `pi` is the batch's table) and rsv_witness_eval_inputs_dev (`pi`: the n_pi shared
+// records, d_pi [n][n_own]: every proof's own)
+static int witness_eval_impl(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
+                             const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_pi, size_t n_own,
+                             uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason) {
+    const rsv_public_input* rec = nullptr;
+    const uint8_t* bad = nullptr;
+    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, n, &rec, &bad) : RSV_OK;
+    if (rc != RSV_OK) return rc;
+    WitnessInputArgs a{};
+    rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a);
+    if (rc != RSV_OK) return rc;
+    a.accept = d_accept;
+    if (n_own) {
+        hipLaunchKernelGGL(k_witness_statement_verdict, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, bad, (uint32_t)n, d_accept, d_reason);
+        a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
+        witness_launch<WitnessInputKernels>(c, prog, a, n);
+    } else witness_launch<WitnessKernels>(c, prog, static_cast<const WitnessArgs&>(a), n);
+    return witness_finish(c, prog, a.vars, d_variables, n);
+}
+
 int rsv_witness_eval_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
                          uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason) {
     if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
     if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
     if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;  // (a caller's circuit has no instructions)
+    if (prog->input_slots) return RSV_E_SIZE;  // a program with own inputs: rsv_witness_eval_inputs_dev
     if (n == 0) return RSV_OK;
     if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
     if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
-    WitnessArgs a{};
-    int rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a);
-    if (rc != RSV_OK) return rc;
-    a.accept = d_accept;
-    witness_launch<WitnessKernels>(c, prog, a, n);
-    return witness_finish(c, prog, a.vars, d_variables, n);
+    return witness_eval_impl(c, prog, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, 0, d_variables, d_flow, d_flow_swap, d_accept, d_reason);
 }
 
-int rsv_witness_eval_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n_groups,
-                                const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
-                                uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
-    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
+int rsv_witness_eval_inputs_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
+                                const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* d_pi,
+                                size_t n_own, uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept,
+                                uint8_t* d_reason) {
+    if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
     if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if (prog->copy_of.empty()) return RSV_E_SIZE;  // only a built program knows which copy a hint belongs to
-    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
-    if (n_groups == 0) return RSV_OK;
-    const size_t copies = prog->shape.copies;
-    if (n_groups > (1u << 20) / copies || prog->device != c->device) return RSV_E_SIZE;
-    WitnessGroupArgs a{};  // d_flow is [n_groups][copies][flow_count]: the members' records, one proof after the other
-    int rc = witness_hints(c, prog, d_blob, d_offsets, n_groups * copies, n_groups, cfg, pi, n_pi, d_variables, d_flow, d_flow_swap,
-                           d_member_accept, d_member_reason, a);
+    if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;
+    int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, n);
+    if (rc == RSV_OK && n_own) rc = witness_check_batch(prog, d_blob, d_offsets, n, cfg);
+    if (rc != RSV_OK) return rc;
+    if (n == 0) return RSV_OK;
+    if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
+    if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    return witness_eval_impl(c, prog, d_blob, d_offsets, n, cfg, pi_fixed, n_fixed, n_own ? d_pi : nullptr, n_own, d_variables, d_flow,
+                             d_flow_swap, d_accept, d_reason);
+}
+
+// rsv_witness_eval_groups_dev and rsv_witness_eval_groups_inputs_dev (d_pi [n_groups * copies][n_own]: every member's own)
+static int witness_groups_impl(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n_groups,
+                               const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_pi, size_t n_own,
+                               uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept,
+                               uint8_t* d_member_reason) {
+    const size_t copies = prog->shape.copies, members = n_groups * copies;
+    const rsv_public_input* rec = nullptr;
+    const uint8_t* bad = nullptr;
+    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, members, &rec, &bad) : RSV_OK;
+    if (rc != RSV_OK) return rc;
+    WitnessGroupInputArgs a{};  // d_flow is [n_groups][copies][flow_count]: the members' records, one proof after the other
+    rc = witness_hints(c, prog, d_blob, d_offsets, members, n_groups, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap,
+                       d_member_accept, d_member_reason, a);
     if (rc != RSV_OK) return rc;
     {   // the table of copies goes to the device on the first call
         rsv_witness_program* wp = const_cast<rsv_witness_program*>(prog);
@@ -394,11 +544,58 @@ int rsv_witness_eval_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, con
             wp->d_copy_of = d;
         }
     }
+    if (n_own)
+        hipLaunchKernelGGL(k_witness_statement_verdict, dim3(grid_for(members, 256)), dim3(256), 0, c->stream, bad, (uint32_t)members,
+                           d_member_accept, d_member_reason);
     hipLaunchKernelGGL(k_witness_group_accept, dim3(grid_for(n_groups, 256)), dim3(256), 0, c->stream, d_member_accept, (uint32_t)n_groups,
                        (uint32_t)copies, d_accept);
     a.accept = d_accept; a.copy_of = prog->d_copy_of; a.copies = (uint32_t)copies;
-    witness_launch<WitnessGroupKernels>(c, prog, a, n_groups);
+    if (n_own) {
+        a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
+        witness_launch<WitnessGroupInputKernels>(c, prog, a, n_groups);
+    } else witness_launch<WitnessGroupKernels>(c, prog, static_cast<const WitnessGroupArgs&>(a), n_groups);
     return witness_finish(c, prog, a.vars, d_variables, n_groups);
+}
+
+int rsv_witness_eval_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n_groups,
+                                const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
+                                uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
+    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
+    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
+    if (prog->copy_of.empty()) return RSV_E_SIZE;  // only a built program knows which copy a hint belongs to
+    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (prog->input_slots) return RSV_E_SIZE;  // a program with own inputs: rsv_witness_eval_groups_inputs_dev
+    if (n_groups == 0) return RSV_OK;
+    if (n_groups > (1u << 20) / prog->shape.copies || prog->device != c->device) return RSV_E_SIZE;
+    return witness_groups_impl(c, prog, d_blob, d_offsets, n_groups, cfg, pi, n_pi, nullptr, 0, d_variables, d_flow, d_flow_swap, d_accept,
+                               d_member_accept, d_member_reason);
+}
+
+int rsv_witness_eval_groups_inputs_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets,
+                                       size_t n_groups, const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed,
+                                       const rsv_public_input* d_pi, size_t n_own, uint32_t* d_variables, uint32_t* d_flow,
+                                       uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
+    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
+    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
+    if (prog->copy_of.empty()) return RSV_E_SIZE;
+    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (n_groups > (1u << 20) / prog->shape.copies) return RSV_E_SIZE;
+    int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, n_groups * prog->shape.copies);
+    if (rc == RSV_OK && n_own) rc = witness_check_batch(prog, d_blob, d_offsets, n_groups * prog->shape.copies, cfg);
+    if (rc != RSV_OK) return rc;
+    if (n_groups == 0) return RSV_OK;
+    if (prog->device != c->device) return RSV_E_SIZE;
+    return witness_groups_impl(c, prog, d_blob, d_offsets, n_groups, cfg, pi_fixed, n_fixed, n_own ? d_pi : nullptr, n_own, d_variables, d_flow,
+                               d_flow_swap, d_accept, d_member_accept, d_member_reason);
+}
+
+int rsv_witness_program_inputs(const rsv_witness_program* prog, uint32_t* n_fixed, uint32_t* n_own, uint32_t* idx) {
+    if (!prog) return RSV_E_NULL;
+    if (!prog->inputs_known) return RSV_E_SIZE;  // only a built program knows the records it was built for
+    if (n_fixed) *n_fixed = (uint32_t)prog->fixed_idx.size();
+    if (n_own) *n_own = (uint32_t)prog->own_idx.size();
+    if (idx && !prog->own_idx.empty()) std::memcpy(idx, prog->own_idx.data(), prog->own_idx.size() * 4);
+    return RSV_OK;
 }
 
 int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
@@ -412,6 +609,31 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
     WitnessStage st;
     int rc = st.open(offsets, n, device, false);
     if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr);
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
+    if (rc != RSV_OK) return rc;
+    const size_t flow_records = n * (size_t)prog->shape.flow_count;
+    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
+    if (flow) {
+        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
+    }
+    return RSV_OK;
+}
+
+// the same with every proof's own records [n][n_own] behind the n_fixed shared ones, all in host memory
+int rsv_witness_eval_inputs(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                            const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* pi_own, size_t n_own, uint32_t* variables,
+                            uint32_t* flow, uint8_t* flow_swap, uint8_t* accept, uint8_t* reason, int device) {
+    if (!prog || (n && (!blob || !offsets || !variables || !accept))) return RSV_E_NULL;
+    if ((flow == nullptr) != (flow_swap == nullptr)) return RSV_E_NULL;
+    if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit
+    if (n > (1u << 20)) return RSV_E_SIZE;
+    int rc = witness_check_own(prog, pi_fixed, n_fixed, pi_own, n_own, n);
+    if (rc != RSV_OK) return rc;
+    if (n == 0) return RSV_OK;
+    WitnessStage st;
+    rc = st.open(offsets, n, device, false);
+    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi_fixed, n_fixed, flow != nullptr, pi_own, n_own);
     if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
     const size_t flow_records = n * (size_t)prog->shape.flow_count;

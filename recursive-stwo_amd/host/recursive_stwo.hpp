@@ -443,6 +443,23 @@ struct WitnessProgram {
         check(rsv_witness_program_export(p.handle, nullptr, nullptr, &p.flow_wires[0][0]), "rsv_witness_program_export");
         return p;
     }
+    // the same with inputs[n_fixed ..) the proof's OWN inputs: PublicInput variables 4 + c * n_own + k of the circuit instead
+    // of constants, so that one program serves proofs that differ in them (rsv_witness_program_build_inputs; the values
+    // have to be M31: the reference's PublicInput row enforces it)
+    static WitnessProgram build_inputs(const std::vector<uint8_t>& template_proof, const PcsConfig& config, const Inputs& inputs, size_t n_fixed,
+                                       uint32_t multipliers = 1, const std::vector<uint8_t>& set_walks = {}) {
+        WitnessProgram p;
+        const rsv_pcs_config abi_cfg = config.abi();
+        auto pi = abi_inputs(inputs);
+        if (!set_walks.empty() && set_walks.size() != multipliers) throw std::runtime_error("set_walks: one entry per copy");
+        check(rsv_witness_program_build_inputs(template_proof.data(), template_proof.size(), &abi_cfg, pi.data(), pi.size(), n_fixed, multipliers,
+                                               set_walks.empty() ? nullptr : set_walks.data(), default_device(), &p.handle),
+              "rsv_witness_program_build_inputs");
+        check(rsv_witness_program_info(p.handle, &p.n_vars, nullptr, &p.shape), "rsv_witness_program_info");
+        p.flow_wires.resize((size_t)p.shape.copies * p.shape.flow_count);
+        check(rsv_witness_program_export(p.handle, nullptr, nullptr, &p.flow_wires[0][0]), "rsv_witness_program_export");
+        return p;
+    }
     // the circuit's Plonk rows (a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31) for the proof whose `variables`
     // are given (empty: the template's): built programs only
     std::vector<std::array<uint32_t, 6>> gates(const std::vector<QM31>& variables = {}) const {
@@ -512,6 +529,38 @@ struct WitnessProgram {
         auto pi = abi_inputs(inputs);
         check(rsv_witness_eval(handle, blob.data(), offsets.data(), n, &cfg_set, pi.data(), pi.size(), vars.data(), nullptr, nullptr,
                                accept.data(), reason.data(), default_device()), "rsv_witness_eval");
+        return rows_of(vars, accept);
+    }
+    // for a program made by build_inputs: `fixed` are the shared records, own[i] proof i's own (all of one length)
+    std::vector<std::vector<QM31>> variables(const std::vector<std::vector<uint8_t>>& proofs, const Inputs& fixed, const std::vector<Inputs>& own,
+                                             std::vector<uint8_t>& accept, std::vector<uint8_t>& reason) const {
+        const size_t n = proofs.size();
+        if (own.size() != n) throw std::runtime_error("own inputs: one list per proof");
+        std::vector<uint64_t> offsets(n + 1, 0);
+        for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + proofs[i].size();
+        std::vector<uint8_t> blob(offsets[n]);
+        for (size_t i = 0; i < n; i++) std::memcpy(blob.data() + offsets[i], proofs[i].data(), proofs[i].size());
+        std::vector<rsv_public_input> records;
+        const size_t n_own = n ? own[0].size() : 0;
+        for (const Inputs& one : own) {
+            if (one.size() != n_own) throw std::runtime_error("own inputs: every proof needs the same number");
+            const auto abi = abi_inputs(one);
+            records.insert(records.end(), abi.begin(), abi.end());
+        }
+        std::vector<uint32_t> vars(n * (size_t)n_vars * 4);
+        accept.assign(n, 0);
+        reason.assign(n, 0);
+        const rsv_pcs_config abi_cfg = config().abi();
+        const rsv_cfg_set cfg_set{&abi_cfg, 1, nullptr};
+        auto pi = abi_inputs(fixed);
+        check(rsv_witness_eval_inputs(handle, blob.data(), offsets.data(), n, &cfg_set, pi.data(), pi.size(), records.data(), n_own, vars.data(),
+                                      nullptr, nullptr, accept.data(), reason.data(), default_device()), "rsv_witness_eval_inputs");
+        return rows_of(vars, accept);
+    }
+
+private:
+    std::vector<std::vector<QM31>> rows_of(const std::vector<uint32_t>& vars, const std::vector<uint8_t>& accept) const {
+        const size_t n = accept.size();
         std::vector<std::vector<QM31>> out(n);
         for (size_t i = 0; i < n; i++) {
             if (!accept[i]) continue;
