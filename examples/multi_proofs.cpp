@@ -15,6 +15,10 @@
 // witness is its v, and the next proof would carry it as its fourth public input.
 //   ./multi_proofs --own-inputs tests/golden/proofs/level10-1.bin tests/golden/proofs/level11-1.bin:2
 // accepts the first (its statement is (1, 1)) and rejects the second (stage 3: the logup balance does not close under (1, 2)).
+// --hash-inputs: the same step with a program whose statement is the DIGEST of the proof's own records: eight words
+// (variables 4 .. 11 of the witness) whatever the number of records, so that a tree of such steps keeps its statement's
+// size; the record itself is variable 12.
+//   ./multi_proofs --hash-inputs tests/golden/proofs/level10-1.bin tests/golden/proofs/level11-1.bin
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -41,7 +45,7 @@ static PcsConfig config_of_level(int k) {
     }
 }
 
-static int own_inputs(int argc, char** argv) {
+static int own_inputs(int argc, char** argv, bool hashed) {
     std::vector<std::vector<uint8_t>> proofs;
     std::vector<Inputs> own;
     PcsConfig config = standard_config;
@@ -61,12 +65,16 @@ static int own_inputs(int argc, char** argv) {
     const Inputs fixed = {{2, QM31{0, 1, 0, 0}}, {3, QM31{0, 0, 1, 0}}};
     Inputs of_template = fixed;
     of_template.push_back(own[0][0]);
-    const WitnessProgram program = WitnessProgram::build_inputs(proofs[0], config, of_template, fixed.size());
+    const WitnessProgram program = WitnessProgram::build_inputs(proofs[0], config, of_template, fixed.size(), 1, {}, hashed);
     std::vector<uint8_t> accept, reason;
     const auto variables = program.variables(proofs, fixed, own, accept, reason);
     int bad = 0;
     for (size_t i = 0; i < proofs.size(); i++) {
-        if (accept[i]) printf("%-40s accepted: %u variables, variable 4 = %u\n", argv[i + 2], program.n_vars, (unsigned)variables[i][4][0]);
+        if (accept[i] && hashed) {
+            printf("%-40s accepted: %u variables, variable 12 = %u, statement =", argv[i + 2], program.n_vars, (unsigned)variables[i][12][0]);
+            for (int k = 0; k < 8; k++) printf(" %u", (unsigned)variables[i][4 + k][0]);
+            printf("\n");
+        } else if (accept[i]) printf("%-40s accepted: %u variables, variable 4 = %u\n", argv[i + 2], program.n_vars, (unsigned)variables[i][4][0]);
         else printf("%-40s REJECTED (stage %u)\n", argv[i + 2], (unsigned)reason[i]);
         bad += !accept[i];
     }
@@ -74,7 +82,8 @@ static int own_inputs(int argc, char** argv) {
 }
 
 int main(int argc, char** argv) {
-    if (argc > 1 && std::string(argv[1]) == "--own-inputs") return own_inputs(argc, argv);
+    if (argc > 1 && std::string(argv[1]) == "--own-inputs") return own_inputs(argc, argv, false);
+    if (argc > 1 && std::string(argv[1]) == "--hash-inputs") return own_inputs(argc, argv, true);
     std::vector<std::vector<uint8_t>> proofs;
     std::vector<PcsConfig> configs;
     for (int i = 1; i < argc; i++) {

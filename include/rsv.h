@@ -208,6 +208,9 @@ typedef enum rsv_option {
                                      lane per subtree walks the middle levels (k_cap_mid), k_cap_top the rest; 1 every bucket does, 2 none */
     RSV_OPT_CIRCUIT_EVAL_FORM = 30, /* rsv_circuit_eval_dev: 0 auto (by batch size), 1 one launch per level of the evaluation program, 2 one
                                      launch in which a workgroup per witness walks the levels */
+    RSV_OPT_STATEMENT_ROW_MAX = 31, /* rsv_statement_digest_dev: 0 default (24 576, measured), else 1 + the largest number of groups hashed in the
+                                     row form (16 threads per group share every permutation: a group's permutations depend on
+                                     one another); more groups take one lane each; 1 = never the row form, 0 .. 2^26 + 1 */
     /* 15, 27, 28, 29: retired; rsv_ctx_set_option answers RSV_E_SIZE */
     RSV_OPT_CAP_TOP = 19          /* 0 auto (batches of >= 1 024 proofs), 1 the last two or three levels of every Merkle tree in a
                                      kernel of their own (one lane per tree), 2 inside the tree kernels (dense top-of-tree cap) */
@@ -395,6 +398,22 @@ int rsv_verify_batch_inputs(const uint8_t* blob, const uint64_t* offsets, size_t
  * above, with n <= 2^26.  Enqueued on the context's stream. */
 int rsv_public_input_sum_dev(rsv_ctx* ctx, const rsv_public_input* d_pi, size_t n, size_t n_pi, const uint32_t* d_z_alpha,
                              uint32_t* d_sum, uint8_t* d_bad);
+/* The digest of the statements a recursion step verifies: eight words whatever the number of proofs and records, for a
+ * tree of recursion whose statement must not grow with its depth.  A group is `copies` proofs (a plain batch: copies = 1)
+ * with n_own records each, d_pi [n_groups * copies][n_own] in HBM as above; v[c * n_own + k] = value[0] of record k of the
+ * group's proof c, T = copies * n_own words, and
+ *     digest = Poseidon31MerkleHasherVar::hash_m31_columns_get_rate(v[0 .. T))        (primitives/merkle/src/lib.rs:50-91)
+ * which is what rsv_merkle_hash_node(NULL, NULL, v, T, ...) returns: ceil(T / 8) + 1 permutations.  The records' idx is not
+ * hashed.  d_stmt [n_groups][8] records: idx = 4 + k, value = (digest[k], 0, 0, 0) — the form the entry points above take,
+ * so whoever holds the leaf statements folds them level by level: d_stmt of one level is d_pi (n_own = 8) of the next.
+ * d_bad [n_groups] (may be NULL): 1 where a value[0] is >= P (it counts as 0) or a value[1..3] is not 0 (the circuit
+ * holds a statement in M31 variables), else 0; the neighbouring groups are unaffected.  Pointers 4-byte aligned.  Small
+ * batches run 16 threads per group, large ones a lane per group (RSV_OPT_STATEMENT_ROW_MAX); the result is the same.
+ * Refusals before any device work: a NULL pointer (but d_bad): RSV_E_NULL; copies 0 or > 64, n_own 0 or > 4096,
+ * n_groups > 2^26, n_groups * copies * n_own > RSV_MAX_INPUT_RECORDS, a pointer not aligned: RSV_E_SIZE.  Enqueued on the
+ * context's stream.  The witness program whose statement is this digest: rsv_witness_program_build_inputs_hashed. */
+int rsv_statement_digest_dev(rsv_ctx* ctx, const rsv_public_input* d_pi, size_t n_groups, size_t copies, size_t n_own,
+                             rsv_public_input* d_stmt, uint8_t* d_bad);
 
 /* Proofs that start in HOST memory, as the reference's callers hold them: one serialized buffer per proof
  * (bincode::serialize(&proof) -> Vec<u8>, examples/multi-proofs/src/main.rs:69-139).  Chunks of about
@@ -604,6 +623,36 @@ int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_co
 int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
                                      size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out);
 int rsv_witness_program_inputs(const rsv_witness_program* prog, uint32_t* n_fixed, uint32_t* n_own, uint32_t* idx_out);
+/* A HASHED STATEMENT.  With rsv_witness_program_build_inputs the outer proof carries every inner record: num_input = 3 +
+ * copies * n_own, and a tree of recursion multiplies it at every level.  rsv_witness_program_build_inputs_hashed (the same
+ * arguments; n_own == 0: RSV_E_SIZE; a template whose own value is no M31: RSV_E_RANGE) builds the circuit whose statement
+ * is the DIGEST of the statements it verified (rsv_statement_digest_dev), eight words whatever copies and n_own are.  In
+ * allocation order:
+ *   variables 4 .. 11: eight PublicInput M31 variables, instruction W_STMT (imm0 = the word), num_input = 11;
+ *   the own records: T = copies * n_own M31 WITNESS variables 12 .. 12 + T, copy-major, instruction W_INPUT (imm0 = k) — the
+ *     row enforces M31, so a record with a non-zero word 1..3 is still RSV_R_PARSE at evaluation;
+ *   half_equalverify(half_from_m31(variables 4 .. 11), hash_m31_columns_get_rate(own records));
+ *   the copies of the verifier, as rsv_witness_program_build_inputs runs them, each on its n_own variables.
+ * The hash costs S = ceil(T / 8) + 1 Poseidon invocations (swap 0), which the verifying pass cannot produce.  They take
+ * the flow indices BEHIND the copies' — flow_wires is [copies * flow_count + S][5], a W_FLOW of the hash has imm0 >= copies *
+ * flow_count — and their records lie at the TAIL of the flow buffers: d_flow / d_flow_swap of a hashed program hold the
+ * members' records, [n_groups * copies][flow_count] as for any program, followed by [n_groups][S]; circuit flow index i of
+ * group g is record g * copies * flow_count + i for i < copies * flow_count, and n_groups * copies * flow_count + g * S + (i -
+ * copies * flow_count) otherwise.  The evaluating calls write them (the digest kernel runs ahead of the witness kernels, no
+ * host synchronisation) and rsv_witness_trace_dev and its successors read them there; W_STMT k of row g is word k of the
+ * group's digest.  The statement of the outer proof is then rsv_circuit_inputs_dev's eleven records, of which 4 .. 11 are
+ * what rsv_statement_digest_dev gives for the inner statements.  rsv_witness_eval_inputs_dev takes a hashed program of one
+ * copy, rsv_witness_eval_groups_inputs_dev of any number (several copies hash a group's statements: RSV_E_SIZE from the
+ * former); the calls without per-proof inputs refuse it as they refuse any program with own inputs.
+ * rsv_witness_program_statement: hashed = 1 for such a program (else 0, and the others 0), n_words = 8, stmt_flow_count = S
+ * (any pointer may be NULL).  The builder runs the digest kernel once on the template's own records, on a context it makes
+ * and destroys for the call (the build needs the device anyway: the template's hints come from a verifying pass).
+ * rsv_witness_program_create accepts W_STMT with imm0 < 8 (a program made from instructions has
+ * no tail: the op yields zero). */
+int rsv_witness_program_build_inputs_hashed(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi,
+                                            size_t n_pi, size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device,
+                                            rsv_witness_program** out);
+int rsv_witness_program_statement(const rsv_witness_program* prog, uint32_t* hashed, uint32_t* n_words, uint32_t* stmt_flow_count);
 /* Sizes, then the arrays (any pointer may be NULL): instr [n_vars][8], level_offsets [n_levels + 1], flow_wires
  * [copies * flow_count][5] = PoseidonEntry::wire of r1..r4 and SwapOption::addr of every invocation (constants of the
  * shape; known to built programs and to those made from a circuit, RSV_E_SIZE otherwise) — what

@@ -201,6 +201,7 @@ def _load() -> ctypes.CDLL:
                                                    ctypes.c_int]),
         "rsv_verify_hints_inputs_dev": (ctypes.c_int, [vp, vp, vp, sz, ctypes.POINTER(CfgSet), vp, sz, ctypes.POINTER(HintsOut), vp, vp]),
         "rsv_public_input_sum_dev": (ctypes.c_int, [vp, vp, sz, sz, vp, vp, vp]),
+        "rsv_statement_digest_dev": (ctypes.c_int, [vp, vp, sz, sz, sz, vp, vp]),
         "rsv_circuit_program_num_input": (ctypes.c_int, [vp, _u32p]),
         "rsv_circuit_inputs_dev": (ctypes.c_int, [vp, vp, vp, sz, vp]),
         "rsv_accept_bitmap_dev": (ctypes.c_int, [vp, vp, sz, vp, vp]),
@@ -234,6 +235,9 @@ def _load() -> ctypes.CDLL:
         "rsv_witness_program_build_inputs": (ctypes.c_int, [_u8p, sz, ctypes.POINTER(PcsConfig), ctypes.POINTER(PublicInput), sz, sz,
                                                             ctypes.c_uint32, _u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
         "rsv_witness_program_inputs": (ctypes.c_int, [vp, _u32p, _u32p, _u32p]),
+        "rsv_witness_program_build_inputs_hashed": (ctypes.c_int, [_u8p, sz, ctypes.POINTER(PcsConfig), ctypes.POINTER(PublicInput), sz, sz,
+                                                                   ctypes.c_uint32, _u8p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+        "rsv_witness_program_statement": (ctypes.c_int, [vp, _u32p, _u32p, _u32p]),
         "rsv_witness_eval_inputs_dev": (ctypes.c_int, [vp, vp, vp, vp, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz, vp, sz, vp, vp,
                                                        vp, vp, vp]),
         "rsv_witness_eval_inputs": (ctypes.c_int, [vp, _u8p, _u64p, sz, ctypes.POINTER(CfgSet), ctypes.POINTER(PublicInput), sz,
@@ -365,7 +369,8 @@ EXPORTS = ["rsv_abi_version", "rsv_device_count", "rsv_ctx_create", "rsv_ctx_des
            "rsv_verify_batch_inputs_dev", "rsv_verify_batch_inputs", "rsv_verify_hints_inputs_dev", "rsv_public_input_sum_dev",
            "rsv_circuit_program_num_input", "rsv_circuit_inputs_dev",
            "rsv_witness_program_build_inputs", "rsv_witness_program_inputs", "rsv_witness_eval_inputs_dev", "rsv_witness_eval_inputs",
-           "rsv_witness_eval_groups_inputs_dev",
+           "rsv_witness_eval_groups_inputs_dev", "rsv_statement_digest_dev", "rsv_witness_program_build_inputs_hashed",
+           "rsv_witness_program_statement",
            "rsv_host_alloc", "rsv_host_free", "rsv_shard_range", "rsv_multi_create", "rsv_multi_destroy", "rsv_multi_size", "rsv_multi_ctx", "rsv_multi_verify_batch_host",
            "rsv_multi_verify_batch_dev", "rsv_exchange_available", "rsv_exchange_rccl_version", "rsv_exchange_unique_id",
            "rsv_exchange_create", "rsv_exchange_destroy", "rsv_exchange_layout", "rsv_exchange_run", "rsv_exchange_assemble",
@@ -393,7 +398,7 @@ OPTIONS = {"transcript_form": 1, "transcript_split": 2, "oods_form": 3, "qconst_
            "overlap_trees": 7, "ws_budget_mb": 8, "perm_wg_per_cu": 9, "host_chunk_mb": 10, "host_threads": 11, "debug_log": 12,
            "critical_chain": 13, "device_order": 14,
            "witness_layout": 16, "witness_small_max": 17, "witness_small_log": 18, "cap_top": 19, "witness_walk_log": 20, "flow_cap": 21, "pair_order": 22, "tree_pace": 23, "stage_times": 24, "query_form": 25, "cap_mid": 26,
-           "circuit_eval_form": 30}
+           "circuit_eval_form": 30, "statement_row_max": 31}
 #: the hint kinds of rsv_circuit_program_create_eval (RSV_HINT_*)
 HINT_KINDS = {"input": 0, "copy": 1, "inv": 2, "inv_or_zero": 3, "qinv": 4, "cinv": 5, "coord": 6, "bit": 7}
 OPTION_VALUES = {"auto": 0, "per_level": 1, "walk": 2, "row": 1, "lane": 2, "paced": 1, "unpaced": 2, "row16": 3, "whole": 1, "split": 2, "parallel": 1, "serial": 2, "on": 1, "off": 2, "device": 1, "host": 2,
@@ -705,12 +710,14 @@ class WitnessProgram:
     WitnessProgram(program) loads arrays made earlier (witness_program.Program, e.g. from a file)."""
 
     num_input = 3  # the recursion circuit allocates no public input, unless built with own inputs (build(n_fixed=...))
+    stmt_flow = 0
 
     def __init__(self, program=None, device: int = 0, _handle=None):
         self._h = None
         if _handle is not None:
             self._h = _handle
         else:
+            program._not_hashed("WitnessProgram(program)")
             sh = program.shape
             shape = WitnessShape(sh["lp"], sh["lq"], sh["pow_bits"], sh["blowup"], sh["log_last"], sh["nq"], sh["n_inner"], sh["flow_count"],
                                  sh["copies"])
@@ -729,13 +736,21 @@ class WitnessProgram:
         num_input = ctypes.c_uint32(0)
         if lib.rsv_circuit_program_num_input(self._h, ctypes.byref(num_input)) == 0:  # (a program made from instructions has no gate list)
             self.num_input = int(num_input.value)
+        #: the invocations of the statement hash of a hashed program (build(hashed=True)), whose flow records follow the
+        #: members' in the flow buffers; 0 for every other program
+        self.stmt_flow = self.statement()[2]
 
     @classmethod
-    def build(cls, proof: bytes, cfg, inputs=STANDARD_INPUTS, copies: int = 1, device: int = 0, set_walks=None, n_fixed=None) -> "WitnessProgram":
+    def build(cls, proof: bytes, cfg, inputs=STANDARD_INPUTS, copies: int = 1, device: int = 0, set_walks=None, n_fixed=None,
+              hashed: bool = False) -> "WitnessProgram":
         """set_walks: per copy, which of the four orders the reference's two HashSet walks took (rsv.h); default 0 for all.
         n_fixed: None — every input is a constant of the program (rsv_witness_program_build); else inputs[:n_fixed] are, and
         inputs[n_fixed:] are the proof's own: PublicInput variables 4 + c * n_own + k of the circuit
-        (rsv_witness_program_build_inputs), whose values Context.witness(d_inputs=...) takes per proof."""
+        (rsv_witness_program_build_inputs), whose values Context.witness(d_inputs=...) takes per proof.
+        hashed (with n_fixed): the circuit's statement is the eight words of the digest of the own records
+        (Context.statement_digest; rsv_witness_program_build_inputs_hashed): num_input = 11 whatever copies and n_own are."""
+        if hashed and n_fixed is None:
+            raise ValueError("hashed=True hashes the proof's own inputs: n_fixed is needed")
         b = np.frombuffer(proof, dtype=np.uint8)
         walks = None if set_walks is None else np.ascontiguousarray(set_walks, dtype=np.uint8)
         if walks is not None and len(walks) != copies:
@@ -747,10 +762,21 @@ class WitnessProgram:
         if n_fixed is None:
             _check(lib.rsv_witness_program_build(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), copies, wp, device,
                                                  ctypes.byref(h)), "rsv_witness_program_build")
+        elif hashed:
+            _check(lib.rsv_witness_program_build_inputs_hashed(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), n_fixed,
+                                                               copies, wp, device, ctypes.byref(h)), "rsv_witness_program_build_inputs_hashed")
         else:
             _check(lib.rsv_witness_program_build_inputs(b.ctypes.data_as(_u8p), len(proof), ctypes.byref(c), pi, len(list(inputs)), n_fixed, copies,
                                                         wp, device, ctypes.byref(h)), "rsv_witness_program_build_inputs")
         return cls(_handle=h)
+
+    def statement(self):
+        """-> (hashed, n_words, stmt_flow_count): whether the program's statement is the digest of the statements it verifies
+        (build(hashed=True)), then 8 and the invocations of that hash, else zeros (rsv_witness_program_statement)."""
+        hashed, n_words, count = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib.rsv_witness_program_statement(self._h, ctypes.byref(hashed), ctypes.byref(n_words), ctypes.byref(count)),
+               "rsv_witness_program_statement")
+        return bool(hashed.value), int(n_words.value), int(count.value)
 
     def inputs(self):
         """-> (n_fixed, n_own, idx uint32[n_own]): the records a built program was made for (rsv_witness_program_inputs)."""
@@ -767,7 +793,7 @@ class WitnessProgram:
         s = self.shape
         wires = getattr(self, "_flow_wires", None)
         if wires is None:
-            wires = np.zeros((s.copies * s.flow_count, 5), np.uint32)
+            wires = np.zeros((s.copies * s.flow_count + self.stmt_flow, 5), np.uint32)
             _check(lib.rsv_witness_program_export(self._h, instr.ctypes.data_as(_u32p), levels.ctypes.data_as(_u32p), wires.ctypes.data_as(_u32p)),
                    "rsv_witness_program_export")
         else:
@@ -793,7 +819,7 @@ class WitnessProgram:
     def trace_sizes(self):
         """(log_plonk, log_poseidon) of the circuit's components (rsv_trace_log_sizes of its gate rows and flow)."""
         rows, _ = self.gates()
-        return trace_log_sizes(len(rows), self.shape.copies * self.shape.flow_count)
+        return trace_log_sizes(len(rows), self.shape.copies * self.shape.flow_count + self.stmt_flow)
 
     def preprocessed(self, variables=None):
         """The 10 Plonk and 40 Poseidon preprocessed columns (rsv_trace_preprocessed): uint32[10, 2^lp], uint32[40, 2^lq].
@@ -1379,6 +1405,16 @@ class Context:
         self.acquire_from_torch()
         _check(lib.rsv_public_input_sum_dev(self._h, d_inputs.data_ptr() if d_inputs is not None else None, n, n_inputs, d_z_alpha.data_ptr(),
                                             d_sum.data_ptr(), d_bad.data_ptr() if d_bad is not None else None), "rsv_public_input_sum_dev")
+
+    def statement_digest(self, d_inputs, n_groups: int, copies: int, n_own: int, d_stmt, d_bad=None):
+        """rsv_statement_digest_dev, the digest of the statements a recursion step verifies: d_inputs [n_groups * copies,
+        n_own, 5] records, d_stmt [n_groups, 8, 5] records (idx 4 + k, value (digest[k], 0, 0, 0)) — hash_m31_columns_get_rate
+        of the copies * n_own value words of a group, the form verify_batch(d_inputs=) and the next level's call take;
+        d_bad uint8[n_groups] (optional): 1 where a value is not an M31 below P; enqueued on the context's stream (the option
+        statement_row_max: 1 + the largest n_groups hashed with 16 threads per group)."""
+        self.acquire_from_torch()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _check(lib.rsv_statement_digest_dev(self._h, ptr(d_inputs), n_groups, copies, n_own, ptr(d_stmt), ptr(d_bad)), "rsv_statement_digest_dev")
 
     def circuit_inputs(self, program: WitnessProgram, d_variables, n: int, d_inputs):
         """rsv_circuit_inputs_dev: the statement of each witness, d_inputs [n, program.num_input, 5] records (k,

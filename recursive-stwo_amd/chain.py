@@ -127,14 +127,21 @@ class Chain:
         F = wp.shape.flow_count
         self._vars = self._new(*((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4)), fill=0)
         self.acc = self._new(n, flag=True, fill=0)
+        S = wp.stmt_flow  # a hashed program: the records of the statement hash follow the members', [n, S] behind [n (* m), F]
         if self.aggregate:
             m = wp.shape.copies
-            self._flow, self._swap = self._new(n, m, F, 32, fill=0), self._new(n, m, F, flag=True, fill=0)
+            if S:
+                self._flow, self._swap = self._new(n * (m * F + S), 32, fill=0), self._new(n * (m * F + S), flag=True, fill=0)
+            else:
+                self._flow, self._swap = self._new(n, m, F, 32, fill=0), self._new(n, m, F, flag=True, fill=0)
             self.member_accept, self.member_reason = self._new(n, m, flag=True, fill=0), self._new(n, m, flag=True, fill=0)
             self.ctx.witness_groups(wp, *self._blob, n, self._vars, self.acc, self.member_accept, self.member_reason, inputs=inputs,
                                     d_flow=self._flow, d_flow_swap=self._swap, d_inputs=d_inputs)
         else:
-            self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
+            if S:
+                self._flow, self._swap = self._new(n * (F + S), 32, fill=0), self._new(n * (F + S), flag=True, fill=0)
+            else:
+                self._flow, self._swap = self._new(n, F, 32, fill=0), self._new(n, F, flag=True, fill=0)
             self.ctx.witness(wp, *self._blob, n, self._vars, self.acc, inputs=inputs, d_flow=self._flow, d_flow_swap=self._swap, d_inputs=d_inputs)
         self._gather_inputs()
         self.done = {"witness"}
@@ -151,6 +158,8 @@ class Chain:
         if self.aggregate:
             raise ValueError("Chain.load() is not for aggregate=True")
         n, wp = self.n, self.program
+        if wp.stmt_flow:
+            raise ValueError("Chain.load() is not for a hashed program (its flow buffers end in the records of the statement hash): use witness()")
         F = wp.shape.copies * wp.shape.flow_count
 
         def dev(x, shape, dtype):

@@ -5,17 +5,58 @@
 
 using namespace rsv::circuit;
 
+// The records of the statement hash of the TEMPLATE, for the builder of a hashed program: its own records `copies` times
+// over (every copy of the template circuit verifies the template), hashed by the kernel the evaluation runs.
+static int template_statement_flow(const rsv_public_input* own, size_t n_own, uint32_t copies, int device, std::vector<uint32_t>& flow) {
+    const size_t T = (size_t)copies * n_own, S = (T + 7) / 8 + 1;
+    std::vector<rsv_public_input> rec;
+    for (uint32_t c = 0; c < copies; c++) rec.insert(rec.end(), own, own + n_own);
+    int rc = select_device(device);
+    if (rc != RSV_OK) return rc;
+    DevBuf d_rec, d_stmt, d_flow, d_swap;
+    HIP_TRY(d_rec.alloc(sizeof(rsv_public_input) * T));
+    HIP_TRY(d_stmt.alloc(sizeof(rsv_public_input) * STMT_WORDS));
+    HIP_TRY(d_flow.alloc(S * 128));
+    HIP_TRY(d_swap.alloc(S));
+    HIP_TRY(hipMemcpy(d_rec.p, rec.data(), sizeof(rsv_public_input) * T, hipMemcpyHostToDevice));
+    rsv_ctx* c = nullptr;
+    rc = rsv_ctx_create(device, &c);
+    if (rc != RSV_OK) return rc;
+    statement_digest_launch(c, d_rec.as<const rsv_public_input>(), 1, (uint32_t)T, d_stmt.as<rsv_public_input>(), nullptr, d_flow.as<uint4>(), d_swap.as<uint8_t>());
+    rc = hipGetLastError() == hipSuccess ? rsv_ctx_synchronize(c) : RSV_E_DEVICE;
+    flow.resize(S * 32);
+    if (rc == RSV_OK && hipMemcpy(flow.data(), d_flow.p, S * 128, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
+    rsv_ctx_destroy(c);
+    return rc;
+}
+
+static int witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi, size_t n_fixed,
+                                 uint32_t copies, const uint8_t* set_walks, int device, bool hashed, rsv_witness_program** out);
+
 extern "C" {
+
+int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
+                                     size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
+    return witness_program_build(proof, len, cfg, pi, n_pi, n_fixed, copies, set_walks, device, false, out);
+}
+
+int rsv_witness_program_build_inputs_hashed(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
+                                            size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
+    return witness_program_build(proof, len, cfg, pi, n_pi, n_fixed, copies, set_walks, device, true, out);
+}
 
 int rsv_witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
                               uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
     return rsv_witness_program_build_inputs(proof, len, cfg, pi, n_pi, n_pi, copies, set_walks, device, out);
 }
 
-int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi,
-                                     size_t n_fixed, uint32_t copies, const uint8_t* set_walks, int device, rsv_witness_program** out) {
+}  // extern "C"
+
+static int witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi, size_t n_fixed,
+                                 uint32_t copies, const uint8_t* set_walks, int device, bool hashed, rsv_witness_program** out) {
     if (!proof || !cfg || !out || (n_pi && !pi)) return RSV_E_NULL;
     if (copies == 0 || copies > 64 || n_fixed > n_pi || n_pi - n_fixed > MAX_OWN_INPUTS) return RSV_E_SIZE;
+    if (hashed && n_fixed == n_pi) return RSV_E_SIZE;  // a hashed statement is the hash of own records
     Template d{};
     int rc = parse_template(proof, len, d);
     if (rc != RSV_OK) return rc;
@@ -47,11 +88,20 @@ int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv
     std::vector<std::pair<uint32_t, Q4>> inputs;
     for (size_t i = 0; i < n_pi; i++) inputs.push_back({pi[i].idx, Q4{pi[i].value[0], pi[i].value[1], pi[i].value[2], pi[i].value[3]}});
     BuiltProgram bp;
-    rc = build_program(d, flow.data(), swap.data(), flow_count, inputs, n_fixed, copies, set_walks, bp, g_debug_log.load() != 0);
+    std::vector<uint32_t> stmt_flow;
+    if (hashed) {
+        for (size_t i = n_fixed; i < n_pi; i++)  // the circuit holds a hashed statement in M31 variables
+            if (pi[i].value[0] >= P || pi[i].value[1] || pi[i].value[2] || pi[i].value[3]) return RSV_E_RANGE;
+        rc = template_statement_flow(pi + n_fixed, n_pi - n_fixed, copies, device, stmt_flow);
+        if (rc != RSV_OK) return rc;
+    }
+    rc = build_program(d, flow.data(), swap.data(), flow_count, inputs, n_fixed, copies, set_walks, bp, g_debug_log.load() != 0,
+                       hashed ? stmt_flow.data() : nullptr, (uint32_t)(stmt_flow.size() / 32));
     if (rc != RSV_OK) return rc;
     rsv_witness_shape shape{d.lp, d.lq, d.pow_bits, d.blowup, d.log_last, d.nq, d.n_inner, flow_count, copies};
     rsv_witness_program* prog = nullptr;
-    rc = rsv_witness_program_create(bp.instr.data(), bp.n_vars, bp.level_offsets.data(), bp.level_offsets.size() - 1, (uint32_t)bp.n_vars, &shape, device, &prog);
+    rc = witness_program_create(bp.instr.data(), bp.n_vars, bp.level_offsets.data(), bp.level_offsets.size() - 1, (uint32_t)bp.n_vars, &shape, device,
+                                bp.stmt_flow_count, &prog);
     if (rc != RSV_OK) return rc;
     prog->h_instr = std::move(bp.instr);
     prog->flow_wires = std::move(bp.flow_wires);
@@ -70,6 +120,8 @@ int rsv_witness_program_build_inputs(const uint8_t* proof, size_t len, const rsv
     *out = prog;
     return RSV_OK;
 }
+
+extern "C" {
 
 int rsv_witness_program_gates(const rsv_witness_program* prog, uint32_t* n_rows, uint32_t* n_witness_ops, uint32_t* gates, uint32_t* witness_ops) {
     if (!prog) return RSV_E_NULL;

@@ -144,7 +144,10 @@ struct ConstraintSystem {
     uint32_t new_m31(uint32_t v, Mode mode) {
         const Q4 q{v, 0, 0, 0};
         const uint32_t c = push(q, take_origin(mode, q));
-        if (mode == WITNESS) row(c, 0, c, 1, 0, 1);
+        if (mode == PUBLIC) {  // the same row as a witness's (:243-249), counted as an input
+            row(c, 0, c, 1, 0, 1);
+            num_input++;
+        } else if (mode == WITNESS) row(c, 0, c, 1, 0, 1);
         else row(1, 0, c, v);
         return c;
     }
@@ -247,6 +250,18 @@ inline Var qm31_public_input(ConstraintSystem* cs, const Q4& v, uint32_t k, uint
     const uint32_t c = cs->new_qm31(v, PUBLIC);
     cs->copy_of[c] = (uint8_t)copy;
     return mk(cs, v, c, 4);
+}
+// The hashed statement (build_program, hashed): word k of the digest, a PublicInput M31 variable read by W_STMT ...
+inline Var m31_statement_word(ConstraintSystem* cs, uint32_t v, uint32_t k) {
+    cs->set_hint(mk_instr(W_STMT, 0, 0, k));
+    return mk(cs, {v % MP, 0, 0, 0}, cs->new_m31(v % MP, PUBLIC), 1);
+}
+// ... and record k of the proof that copy `copy` verifies as an M31 WITNESS variable (the reference's new_m31(Witness):
+// the row enforces M31), read by W_INPUT as a public one is
+inline Var m31_own_witness(ConstraintSystem* cs, uint32_t v, uint32_t k, uint32_t copy) {
+    const Var r = m31_witness(cs, v, mk_instr(W_INPUT, 0, 0, k));
+    cs->copy_of[r.variable] = (uint8_t)copy;
+    return r;
 }
 inline Var qm31_constant(ConstraintSystem* cs, const Q4& v) {
     const Q4 fixed[4] = {{0, 0, 0, 0}, {1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}};

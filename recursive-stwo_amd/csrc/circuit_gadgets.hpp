@@ -127,6 +127,7 @@ struct FlowSource {
     const uint32_t* rec = nullptr;  // [count][32]
     const uint8_t* swap = nullptr;  // [count]
     size_t count = 0, cursor = 0;
+    uint32_t base = 0;  // the circuit's flow index of record 0 (the statement hash of a hashed program: behind the copies')
 };
 
 struct Gadgets {
@@ -142,7 +143,7 @@ struct Gadgets {
         for (int i = 0; i < 8; i++)
             if (rec[i] != left.value[i] || rec[8 + i] != right.value[i]) throw std::runtime_error("PoseidonFlow record is not the circuit's invocation");
         if ((flow->swap[k] != 0) != swapped) throw std::runtime_error("PoseidonFlow swap bit is not the circuit's");
-        const uint32_t flow_idx = (uint32_t)k;
+        const uint32_t flow_idx = flow->base + (uint32_t)k;
         flow->cursor++;
         auto result = [&](const uint32_t* vals, bool ignore, uint32_t half) {
             Hash8 h;

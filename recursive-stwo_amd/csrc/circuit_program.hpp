@@ -94,13 +94,16 @@ inline int parse_template(const uint8_t* proof, size_t len, Template& d) {
 
 // Everything a level kernel will index with comes from the program, so the program is checked once, here: a bad one is
 // an API error, never a device fault.
+// stmt_flow: the invocations of the statement hash of a hashed program (0: not hashed), whose flow indices lie behind the
+// copies': [copies * flow_count, copies * flow_count + stmt_flow).
 inline int check_program(const uint32_t* instr, size_t n_instr, const uint32_t* level_offsets, size_t n_levels, uint32_t n_vars,
-                         const rsv_witness_shape& s, bool log = false) {
+                         const rsv_witness_shape& s, bool log = false, uint32_t stmt_flow = 0) {
     if (n_instr != n_vars || n_levels == 0 || level_offsets[0] != 0 || level_offsets[n_levels] != n_instr) return RSV_E_SIZE;
     if (s.n_queries < 4 || s.n_queries > (uint32_t)MAXQ || s.n_inner > (uint32_t)MAX_INNER || s.log_last > 16 || s.flow_count == 0)
         return RSV_E_SIZE;
     const uint32_t M = (s.log_size_plonk + 1 > s.log_size_poseidon + 2 ? s.log_size_plonk + 1 : s.log_size_poseidon + 2) + s.log_blowup;
     if (M > (uint32_t)MAX_LOG) return RSV_E_SIZE;
+    const uint64_t tail = (uint64_t)(s.copies ? s.copies : 1u) * s.flow_count;
     std::vector<uint32_t> level_of(n_vars, 0xFFFFFFFFu);
     for (size_t l = 0; l < n_levels; l++) {
         if (level_offsets[l] > level_offsets[l + 1]) return RSV_E_SIZE;
@@ -121,7 +124,7 @@ inline int check_program(const uint32_t* instr, size_t n_instr, const uint32_t* 
             case W_CINV: ok = before(a) && i0 < 2; break;
             case W_COORD: ok = before(a) && i0 < 4; break;
             case W_BIT: ok = before(a) && i0 < 31; break;
-            case W_FLOW: ok = i0 < s.flow_count && i1 >= 16 && i1 < 32 && (i1 & 3) == 0; break;
+            case W_FLOW: ok = (i0 < s.flow_count || (i0 >= tail && i0 - tail < stmt_flow)) && i1 >= 16 && i1 < 32 && (i1 & 3) == 0; break;
             case W_WORD: ok = i0 < FIXED_PART_WORDS; break;
             case W_WORD4: ok = i0 + 4 <= FIXED_PART_WORDS; break;
             case W_FRI_COMMIT: ok = i0 <= s.n_inner && i1 < 2; break;
@@ -130,6 +133,7 @@ inline int check_program(const uint32_t* instr, size_t n_instr, const uint32_t* 
             case W_TRACE_COL: ok = i0 < 4 && i1 < s.n_queries && i2 < 64; break;
             case W_FRI_COL: ok = i0 <= s.n_inner && i1 < s.n_queries && i2 < 24 && (i2 & 3) == 0; break;
             case W_INPUT: ok = i0 < MAX_OWN_INPUTS; break;  // (below the batch's n_own: input_slots, checked by the evaluating call)
+            case W_STMT: ok = i0 < STMT_WORDS; break;
             default: ok = false;
             }
             if (!ok) { if (log) fprintf(stderr, "[rsv] witness program: instruction %u (op %u, dst %u, a %u, b %u, imm %u %u %u) is out of range\n", k, op, dst, a, b, i0, i1, i2); return RSV_E_RANGE; }
@@ -147,24 +151,38 @@ struct BuiltProgram {
     std::vector<uint32_t> instr, level_offsets, flow_wires, gates, witness_ops;
     std::vector<uint8_t> copy_of;  // [n_vars]: the copy of the verifier that allocated the variable (the grouped witness kernels
                                    // read it for hint instructions: copy c's hints are those of the group's proof c)
-    uint32_t num_input = 3;        // 3 + copies * n_own
+    uint32_t num_input = 3;        // 3 + copies * n_own; hashed: 11
+    uint32_t stmt_flow_count = 0;  // hashed: S = ceil(copies * n_own / 8) + 1, the invocations of the statement hash
 };
 
 // The gadgets run copy after copy, so a copy's variables are one contiguous range (marks: [copies + 1]), and every hint (an
 // instruction that reads the proof, its flow or its queried columns) lies in the range of the copy it was recorded for.
 // What copy 1 .. reuses of copy 0 are the cached constants: W_CONST, never a hint.  The own inputs come before every
 // copy: record k of copy c's proof is variable 4 + c * n_own + k, and nothing else is a W_INPUT.
+// A HASHED program (member_flow = copies * flow_count, else 0) has its statement first — variables 4 .. 11, W_STMT with
+// imm0 = the word — then the own inputs from variable 12 on, then the variables of the statement hash up to the first
+// copy: no hint among them but W_FLOW, with a flow index behind the copies' (>= member_flow); a copy's are below it.
 inline int check_copies(const std::vector<Instr>& origin, const std::vector<uint8_t>& copy_of, const std::vector<uint32_t>& marks,
-                        uint32_t copies, uint32_t n_own, bool log = false) {
+                        uint32_t copies, uint32_t n_own, bool log = false, uint32_t member_flow = 0) {
     const size_t n_vars = origin.size();
+    const bool hashed = member_flow != 0;
     if (marks.size() != (size_t)copies + 1 || copy_of.size() != n_vars || marks[copies] != n_vars) return RSV_E_RANGE;
-    const size_t first = 4, end = first + (size_t)copies * n_own;
-    if (end > n_vars || marks[0] != end) return RSV_E_RANGE;
+    const size_t first = hashed ? 4 + STMT_WORDS : 4, end = first + (size_t)copies * n_own;
+    if (end > n_vars || (hashed ? marks[0] < end || n_own == 0 : marks[0] != end)) return RSV_E_RANGE;
     for (size_t k = 0; k < n_vars; k++) {
         const uint32_t c = copy_of[k];
         const bool input = k >= first && k < end;
+        if (hashed && k < marks[0] && !input) {  // the statement and its hash
+            const bool stmt = k >= 4 && k < first;
+            if (stmt ? (origin[k].op != W_STMT || origin[k].imm[0] != k - 4)
+                     : (origin[k].op >= W_FLOW && (origin[k].op != W_FLOW || origin[k].imm[0] < member_flow || c != 0))) {
+                if (log) fprintf(stderr, "[rsv] witness program build: variable %zu is out of place in the statement\n", k);
+                return RSV_E_RANGE;
+            }
+            continue;
+        }
         if (input ? (origin[k].op != W_INPUT || c != (k - first) / n_own || origin[k].imm[0] != (k - first) % n_own)
-                  : (origin[k].op == W_INPUT ||
+                  : (origin[k].op == W_INPUT || origin[k].op == W_STMT || (hashed && origin[k].op == W_FLOW && origin[k].imm[0] >= member_flow) ||
                      (origin[k].op >= W_FLOW && (c >= copies || k < marks[c] || k >= marks[c + 1])))) {
             if (log) fprintf(stderr, "[rsv] witness program build: hint variable %zu lies outside copy %u\n", k, c);
             return RSV_E_RANGE;
@@ -177,18 +195,48 @@ inline int check_copies(const std::vector<Instr>& origin, const std::vector<uint
 // inputs[0 .. n_fixed) are constants of the program; inputs[n_fixed ..) are the proof's OWN inputs (n_own of them), the
 // template's values: PublicInput variables 4 + c * n_own + k, allocated before the first copy, which the program reads
 // with W_INPUT (imm0 = k).  With n_fixed = inputs.size() the program is the one without own inputs.
+// HASHED (stmt_flow != NULL: the stmt_flow_count = ceil(copies * n_own / 8) + 1 records [32] of the hash of the template's own
+// value words, `copies` times over, as k_statement_digest writes them): the statement of the outer circuit is the eight
+// words of that hash — PublicInput M31 variables 4 .. 11 (W_STMT) — the own records are M31 WITNESS variables from 12 on
+// (W_INPUT, copy-major), and half_equalverify(half_from_m31(statement), hash_m31_columns_get_rate(own)) ties them
+// before the first copy.  num_input = 11.  The hash's invocations take the flow indices BEHIND the copies'
+// (copies * flow_count ..): the verifying pass writes a copy's records at a flat stride and knows nothing of them.
 inline int build_program(const Template& d, const uint32_t* flow, const uint8_t* swap, uint32_t flow_count,
                          const std::vector<std::pair<uint32_t, Q4>>& inputs, size_t n_fixed, uint32_t copies, const uint8_t* set_walks,
-                         BuiltProgram& out, bool log = false) {
+                         BuiltProgram& out, bool log = false, const uint32_t* stmt_flow = nullptr, uint32_t stmt_flow_count = 0) {
     if (n_fixed > inputs.size() || inputs.size() - n_fixed > MAX_OWN_INPUTS) return RSV_E_SIZE;
     const uint32_t n_own = (uint32_t)(inputs.size() - n_fixed);
+    const bool hashed = stmt_flow != nullptr;
+    const uint32_t n_hash = hashed ? (copies * n_own + 7) / 8 + 1 : 0;
+    if (hashed && (n_own == 0 || copies == 0 || stmt_flow_count != n_hash || flow_count == 0)) return RSV_E_SIZE;
+    if (hashed)  // the circuit holds a hashed statement in M31 variables
+        for (uint32_t k = 0; k < n_own; k++) {
+            const Q4& v = inputs[n_fixed + k].second;
+            if (v[0] >= MP || v[1] || v[2] || v[3]) return RSV_E_RANGE;
+        }
     ConstraintSystem cs;
     FlowSource fsrc{flow, swap, flow_count, 0};
     Gadgets g{&cs, &fsrc};
+    const std::vector<uint8_t> stmt_swap(n_hash, 0);
+    FlowSource ssrc{stmt_flow, stmt_swap.data(), n_hash, 0, copies * flow_count};
+    Gadgets gs{&cs, &ssrc};
     try {
         std::vector<std::vector<Var>> own(copies);
-        for (uint32_t c = 0; c < copies; c++)
-            for (uint32_t k = 0; k < n_own; k++) own[c].push_back(qm31_public_input(&cs, inputs[n_fixed + k].second, k, c));
+        if (hashed) {
+            std::array<Var, 8> stated;
+            for (uint32_t k = 0; k < STMT_WORDS; k++) stated[k] = m31_statement_word(&cs, stmt_flow[(size_t)(n_hash - 1) * 32 + 16 + k], k);
+            std::vector<Var> all;
+            for (uint32_t c = 0; c < copies; c++)
+                for (uint32_t k = 0; k < n_own; k++) {
+                    own[c].push_back(m31_own_witness(&cs, inputs[n_fixed + k].second[0], k, c));
+                    all.push_back(own[c].back());
+                }
+            const Half left = half_from_m31(stated.data());
+            const Half right = gs.hash_m31_columns_get_rate(all);
+            gs.half_equalverify(left, right);  // (both are the last record's output words)
+        } else
+            for (uint32_t c = 0; c < copies; c++)
+                for (uint32_t k = 0; k < n_own; k++) own[c].push_back(qm31_public_input(&cs, inputs[n_fixed + k].second, k, c));
         for (uint32_t c = 0; c < copies; c++) {
             cs.begin_copy();
             verify_in_circuit(g, d, inputs, own[c], set_walks ? (set_walks[c] & 3u) : 0u);
@@ -197,13 +245,15 @@ inline int build_program(const Template& d, const uint32_t* flow, const uint8_t*
         if (log) fprintf(stderr, "[rsv] witness program build: %s\n", e.what());
         return RSV_E_RANGE;
     }
-    if (fsrc.cursor != (size_t)copies * flow_count) return RSV_E_RANGE;
+    if (fsrc.cursor != (size_t)copies * flow_count || ssrc.cursor != n_hash) return RSV_E_RANGE;
+    std::rotate(cs.flow.begin(), cs.flow.begin() + n_hash, cs.flow.end());  // the hash ran first; its records come last
 
     // one instruction per variable, sorted by dependency depth
     const size_t n_vars = cs.variables.size();
     cs.copy_marks.push_back((uint32_t)n_vars);
-    if (check_copies(cs.origin, cs.copy_of, cs.copy_marks, copies, n_own, log) != RSV_OK) return RSV_E_RANGE;
+    if (check_copies(cs.origin, cs.copy_of, cs.copy_marks, copies, n_own, log, hashed ? copies * flow_count : 0) != RSV_OK) return RSV_E_RANGE;
     out.num_input = cs.num_input;
+    out.stmt_flow_count = n_hash;
     std::vector<uint32_t> depth(n_vars, 0);
     uint32_t max_depth = 0;
     for (size_t k = 0; k < n_vars; k++) {

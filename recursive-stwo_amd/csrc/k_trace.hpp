@@ -41,6 +41,15 @@ struct TraceArgs {
     uint32_t* poseidon;         // [n][48][2^lq]
 };
 
+// A hashed program (rsv_witness_program_build_inputs_hashed): the invocations behind the copies', k = copies * flow_count ..
+// + stmt_flow, are the statement hash's, whose records lie at the tail of the flow buffers: [n][stmt_flow] from record `tail`.
+struct TraceStmtArgs : TraceArgs {
+    uint32_t stmt_flow;
+    size_t tail;
+};
+template <class A> struct trace_stmt { static constexpr bool value = false; };
+template <> struct trace_stmt<TraceStmtArgs> { static constexpr bool value = true; };
+
 // ---------------------------------------------------------------- Plonk
 // Block b: proof b / blocks_per_proof, rows (b % blocks_per_proof) * 256 ...: the workgroups in flight share proofs.
 __global__ __launch_bounds__(256) void k_trace_plonk(TraceArgs a) {
@@ -121,8 +130,8 @@ __device__ __forceinline__ void trace_flush(uint32_t* lds, const uint32_t* r0, c
 // record k % flow_count (every copy of the verifier invokes the same permutations); the padding invocations hash zeros
 // with wires and swap address 0.  GROUPED (rsv_witness_trace_groups_dev): p is a group of `copies` proofs whose records lie
 // one proof after the other, [n][copies][flow_count], and copy c hashes those of the group's proof c: record k of the group.
-template <bool GROUPED>
-__device__ __forceinline__ void trace_poseidon(const TraceArgs& a, uint32_t* lds) {
+template <bool GROUPED, class A>
+__device__ __forceinline__ void trace_poseidon(const A& a, uint32_t* lds) {
     const uint32_t per = (a.n_pad + TRACE_WAVE - 1) / TRACE_WAVE;
     const uint32_t p = blockIdx.x / per, k0 = (blockIdx.x % per) * TRACE_WAVE, k = k0 + threadIdx.x;
     const size_t Q = (size_t)1 << a.log_poseidon;
@@ -149,6 +158,17 @@ __device__ __forceinline__ void trace_poseidon(const TraceArgs& a, uint32_t* lds
         }
         sw = a.swap[rec] != 0;
     }
+    if constexpr (trace_stmt<A>::value)
+        if (k >= a.flow_count * a.copies && k - a.flow_count * a.copies < a.stmt_flow) {
+            const size_t rec = a.tail + (size_t)p * a.stmt_flow + (k - a.flow_count * a.copies);
+            const uint4* f = a.flow + rec * 8;
+#pragma unroll
+            for (int q = 0; q < 4; q++) {
+                const uint4 v = f[q];
+                in[4 * q] = v.x; in[4 * q + 1] = v.y; in[4 * q + 2] = v.z; in[4 * q + 3] = v.w;
+            }
+            sw = a.swap[rec] != 0;
+        }
     // row 0: in = r1 || r2 as given, intermediate[0] = the swap bit, out = external matrix of the (swapped) input
     uint32_t s[16], mid0[16], mid1[16];
 #pragma unroll
@@ -202,6 +222,14 @@ __global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
     trace_poseidon<false>(a, lds);
 }
 __global__ __launch_bounds__(64) void k_trace_poseidon_g(TraceArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
+    trace_poseidon<true>(a, lds);
+}
+__global__ __launch_bounds__(64) void k_trace_poseidon_s(TraceStmtArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
+    trace_poseidon<false>(a, lds);
+}
+__global__ __launch_bounds__(64) void k_trace_poseidon_gs(TraceStmtArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
     trace_poseidon<true>(a, lds);
 }

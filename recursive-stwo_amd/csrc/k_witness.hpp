@@ -49,12 +49,31 @@ struct WitnessGroupInputArgs : WitnessGroupArgs {
     const PubInput* own;  // [n * copies][n_own]
     uint32_t n_own;
 };
+// A HASHED program (rsv_witness_program_build_inputs_hashed): W_STMT reads word imm0 of the statement k_statement_digest
+// left for the proof (grouped: the group), and a W_FLOW whose index lies behind the copies' (>= member_flow) reads the
+// records of the statement hash, [n][stmt_flow] at the tail of the flow buffer.  Argument types of their own again.
+struct WitnessStmtArgs : WitnessInputArgs {
+    const PubInput* stmt;     // [n][8]
+    const uint4* flow_tail;   // [n][stmt_flow][8]
+    uint32_t member_flow, stmt_flow;
+};
+struct WitnessGroupStmtArgs : WitnessGroupInputArgs {
+    const PubInput* stmt;
+    const uint4* flow_tail;
+    uint32_t member_flow, stmt_flow;
+};
 template <class A> struct witness_grouped { static constexpr bool value = false; };
 template <> struct witness_grouped<WitnessGroupArgs> { static constexpr bool value = true; };
 template <> struct witness_grouped<WitnessGroupInputArgs> { static constexpr bool value = true; };
+template <> struct witness_grouped<WitnessGroupStmtArgs> { static constexpr bool value = true; };
 template <class A> struct witness_inputs { static constexpr bool value = false; };
 template <> struct witness_inputs<WitnessInputArgs> { static constexpr bool value = true; };
 template <> struct witness_inputs<WitnessGroupInputArgs> { static constexpr bool value = true; };
+template <> struct witness_inputs<WitnessStmtArgs> { static constexpr bool value = true; };
+template <> struct witness_inputs<WitnessGroupStmtArgs> { static constexpr bool value = true; };
+template <class A> struct witness_stmt { static constexpr bool value = false; };
+template <> struct witness_stmt<WitnessStmtArgs> { static constexpr bool value = true; };
+template <> struct witness_stmt<WitnessGroupStmtArgs> { static constexpr bool value = true; };
 
 // one instruction (its eight words: w0 = op, dst, a, b; w1 = imm0..3) for one proof
 template <class A>
@@ -71,6 +90,16 @@ __device__ __forceinline__ void witness_exec(const A& a, const uint4 w0, const u
                 if (ok) r = u4_words(a.own[q * a.n_own + i0].value);
                 return r;
             }
+        if constexpr (witness_stmt<A>::value) {
+            if (op == W_STMT) {  // (imm0 < 8: check_program)
+                if (ok) r.x = a.stmt[(size_t)p * STMT_WORDS + i0].value[0];
+                return r;
+            }
+            if (op == W_FLOW && i0 >= a.member_flow) {  // (i0 - member_flow < stmt_flow: check_program)
+                if (ok) r = a.flow_tail[((size_t)p * a.stmt_flow + (i0 - a.member_flow)) * 8 + (i1 >> 2)];
+                return r;
+            }
+        }
         switch (op) {
         case W_FLOW:
             if (ok) r = a.flow[(q * a.flow_stride + i0) * 8 + (i1 >> 2)];
@@ -118,6 +147,8 @@ __global__ __launch_bounds__(256) void k_witness_level(WitnessArgs a) { witness_
 __global__ __launch_bounds__(256) void k_witness_level_g(WitnessGroupArgs a) { witness_level(a); }
 __global__ __launch_bounds__(256) void k_witness_level_i(WitnessInputArgs a) { witness_level(a); }
 __global__ __launch_bounds__(256) void k_witness_level_gi(WitnessGroupInputArgs a) { witness_level(a); }
+__global__ __launch_bounds__(256) void k_witness_level_s(WitnessStmtArgs a) { witness_level(a); }
+__global__ __launch_bounds__(256) void k_witness_level_gs(WitnessGroupStmtArgs a) { witness_level(a); }
 
 // the same for batches of at least a wave of proofs: blockIdx.y = the instruction, so that the instruction words are scalar
 // loads and the switch a scalar branch (in the 1-D form a wave may straddle two instructions, and every lane divides)
@@ -131,6 +162,8 @@ __global__ __launch_bounds__(256) void k_witness_level_wide(WitnessArgs a) { wit
 __global__ __launch_bounds__(256) void k_witness_level_wide_g(WitnessGroupArgs a) { witness_level_wide(a); }
 __global__ __launch_bounds__(256) void k_witness_level_wide_i(WitnessInputArgs a) { witness_level_wide(a); }
 __global__ __launch_bounds__(256) void k_witness_level_wide_gi(WitnessGroupInputArgs a) { witness_level_wide(a); }
+__global__ __launch_bounds__(256) void k_witness_level_wide_s(WitnessStmtArgs a) { witness_level_wide(a); }
+__global__ __launch_bounds__(256) void k_witness_level_wide_gs(WitnessGroupStmtArgs a) { witness_level_wide(a); }
 
 // Levels l0 .. l1 walked by ONE workgroup for its own proofs (dependencies never cross proofs): instruction slot `slot` of
 // `n_slots` takes instructions begin + slot, + n_slots, ... of every level, a workgroup barrier ends a level (the waves of
@@ -169,6 +202,14 @@ __global__ __launch_bounds__(256) void k_witness_strip_gi(WitnessGroupInputArgs 
     const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
     witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
 }
+__global__ __launch_bounds__(256) void k_witness_strip_s(WitnessStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
+    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
+}
+__global__ __launch_bounds__(256) void k_witness_strip_gs(WitnessGroupStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
+    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
+}
 
 // Small and medium batches: the WHOLE program in one launch.  A workgroup of 1 024 lanes owns P2 = 2^log_p2 proofs (n <= 4:
 // one workgroup, P2 = n rounded up — the reference's own use is ONE proof per recursion step; larger batches: P2 proofs per
@@ -193,6 +234,16 @@ __global__ __launch_bounds__(1024) void k_witness_small_i(WitnessInputArgs a, co
     witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
 }
 __global__ __launch_bounds__(1024) void k_witness_small_gi(WitnessGroupInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
+                                                           uint32_t log_p2) {
+    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
+    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
+}
+__global__ __launch_bounds__(1024) void k_witness_small_s(WitnessStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
+                                                          uint32_t log_p2) {
+    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
+    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
+}
+__global__ __launch_bounds__(1024) void k_witness_small_gs(WitnessGroupStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
                                                            uint32_t log_p2) {
     const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
     witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);

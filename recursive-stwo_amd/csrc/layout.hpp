@@ -192,8 +192,10 @@ enum WitnessOp : uint32_t {
     W_CONST, W_ADD, W_MUL, W_MULC, W_COPY, W_INV, W_INV0, W_QINV, W_CINV, W_COORD, W_BIT, W_FLOW, W_WORD, W_WORD4,
     W_FRI_COMMIT, W_LAST_POLY, W_NONCE, W_TRACE_COL, W_FRI_COL,
     W_INPUT,  // dst = record imm0 of the proof's OWN public inputs (rsv_witness_program_build_inputs); behind the others: no number moved
+    W_STMT,   // dst = (word imm0 of the digest of the group's statements, 0, 0, 0) (rsv_witness_program_build_inputs_hashed)
     W_N_OPS
 };
+constexpr uint32_t STMT_WORDS = 8;  // the statement of a hashed program: W_STMT's imm0 lies below it
 constexpr uint32_t MAX_OWN_INPUTS = 4096;  // W_INPUT's imm0 lies below it (the per-proof entry points take at most 4 096 records)
 
 }  // namespace rsv

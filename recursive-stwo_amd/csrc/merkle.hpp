@@ -23,9 +23,9 @@ __device__ __forceinline__ uint32_t hash_over(const Hash8& h) {
 // hash_m31_columns_get_capacity (primitives/merkle/src/lib.rs:141-181):
 // d = 0; for each zero-padded chunk of 8 words: d = perm(chunk || d)[8..16].
 // `cols` may be any address space; words are read with plain 4-byte loads.
+// d: the capacity so far, for a caller that absorbs its words in several runs of whole chunks (k_statement.hpp)
 template <int PACE = 1>
-__device__ inline Hash8 sponge_capacity(const uint32_t* cols, uint32_t n) {
-    Hash8 d = zero8();
+__device__ inline Hash8 sponge_capacity(const uint32_t* cols, uint32_t n, Hash8 d = zero8()) {
     for (uint32_t off = 0; off < n; off += 8) {
         Hash8 chunk;
 #pragma unroll
@@ -130,8 +130,7 @@ __device__ inline State16 flow_perm(const FlowSink& f, uint32_t idx, const Hash8
 }
 // hash_m31_columns_get_capacity with records idx, idx + 1, ... (one per 8-word chunk)
 template <int PACE = 1>
-__device__ inline Hash8 flow_sponge_capacity(const FlowSink& f, uint32_t idx, const uint32_t* cols, uint32_t n) {
-    Hash8 d = zero8();
+__device__ inline Hash8 flow_sponge_capacity(const FlowSink& f, uint32_t idx, const uint32_t* cols, uint32_t n, Hash8 d = zero8()) {
     for (uint32_t off = 0; off < n; off += 8) {
         Hash8 chunk;
 #pragma unroll

@@ -27,6 +27,7 @@
 #include "verify.hpp"
 #include "host_logic.hpp"
 #include "k_witness.hpp"
+#include "k_statement.hpp"
 #include "k_trace.hpp"
 #include "k_interaction.hpp"
 #include "k_commit.hpp"
@@ -70,6 +71,7 @@ struct Options {
     int witness_small_log = 0;        // 0 default, else 1 + log2(proofs per workgroup) of that form
     int witness_walk_log = 0;         // level form: 0 auto, 1 off, else 1 + log2(proofs per workgroup) of the one-launch tail
     int circuit_eval_form = 0;        // rsv_circuit_eval_dev: 0 auto (by batch size), 1 a launch per level, 2 a workgroup per witness walks the levels
+    long long statement_row_max = 0;  // rsv_statement_digest_dev: 0 default, else 1 + the largest number of groups hashed in the row form
 };
 static Options g_default_options;
 static std::mutex g_options_mu;
@@ -303,6 +305,9 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_WITNESS_SMALL_MAX:
             if (value < 0 || value > (1ll << 20) + 1) return RSV_E_RANGE;
             o.witness_small_max = value; return RSV_OK;
+        case RSV_OPT_STATEMENT_ROW_MAX:
+            if (value < 0 || value > (1ll << 26) + 1) return RSV_E_RANGE;
+            o.statement_row_max = value; return RSV_OK;
         case RSV_OPT_WITNESS_SMALL_LOG:
             if (value < 0 || value > 7) return RSV_E_RANGE;
             o.witness_small_log = (int)value; return RSV_OK;

@@ -107,7 +107,7 @@ static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint
     if (grouped && (prog->copy_of.empty() || n > (1u << 20) / prog->shape.copies)) return RSV_E_SIZE;  // built programs only (they have at least one copy)
     if (n == 0) return RSV_OK;
     const rsv_witness_shape& s = prog->shape;
-    rsv::TraceArgs a{};
+    rsv::TraceStmtArgs a{};  // (the kernels of a program that is not hashed take its TraceArgs part)
     a.vars = reinterpret_cast<const uint4*>(d_variables);
     a.n_vars = prog->n_vars;
     a.n = (uint32_t)n;
@@ -120,7 +120,9 @@ static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint
     a.swap = d_flow_swap;
     a.flow_count = s.flow_count;
     a.copies = s.copies;
-    a.n_pad = (uint32_t)rsv::trace::padded_flow((uint64_t)s.flow_count * s.copies);
+    a.n_pad = (uint32_t)rsv::trace::padded_flow((uint64_t)s.flow_count * s.copies + prog->stmt_flow);
+    a.stmt_flow = prog->stmt_flow;
+    a.tail = n * (size_t)s.flow_count * (grouped ? s.copies : 1u);  // the hash's records follow the members' (witness_api.inc)
     a.log_poseidon = prog->trace_lq;
     a.poseidon = d_poseidon;
     const uint64_t plonk_blocks = (uint64_t)((((size_t)1 << a.log_plonk) + 255) / 256) * n;
@@ -131,10 +133,12 @@ static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint
     if (plonk_blocks >= (1u << 31) || poseidon_blocks >= (1u << 31) || tail_threads / 256 >= (1u << 31) || (uint64_t)n_ops * n / 256 >= (1u << 31))
         return RSV_E_SIZE;
     hipStream_t st = c->stream;
-    if (d_plonk) hipLaunchKernelGGL(rsv::k_trace_plonk, dim3((unsigned)plonk_blocks), dim3(256), 0, st, a);
-    if (d_ops && n_ops) hipLaunchKernelGGL(rsv::k_trace_ops, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, a, prog->d_trace_ops, (uint32_t)n_ops, d_ops);
+    const rsv::TraceArgs& plain = a;
+    if (d_plonk) hipLaunchKernelGGL(rsv::k_trace_plonk, dim3((unsigned)plonk_blocks), dim3(256), 0, st, plain);
+    if (d_ops && n_ops) hipLaunchKernelGGL(rsv::k_trace_ops, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, plain, prog->d_trace_ops, (uint32_t)n_ops, d_ops);
     if (d_poseidon) {
-        hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_g : rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
+        if (prog->stmt_flow) hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_gs : rsv::k_trace_poseidon_s, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
+        else hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_g : rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, plain);
         if (tail_threads)
             hipLaunchKernelGGL(rsv::k_trace_zero_tail, dim3(grid_for(tail_threads, 256)), dim3(256), 0, st, d_poseidon, a.log_poseidon,
                                (uint32_t)tail_first, (uint64_t)rsv::POSEIDON_COLS_K * n);

@@ -900,6 +900,37 @@ int rsv_public_input_sum_dev(rsv_ctx* c, const rsv_public_input* d_pi, size_t n,
     return RSV_OK;
 }
 
+// The statement digest alone (k_statement.hpp).  The crossover between its two forms, measured (profiles/HISTORY.md,
+// "Statement digests"): the row form is ahead up to 24 576 groups with 8 words and with 1 024, the lane form from 32 768 and
+// 49 152 on — the lane form's 1 024 waves of 65 536 groups are one per SIMD, and a group's chain of permutations is four
+// times as long in it.
+constexpr size_t kStatementRowMax = 24576;
+// The one place that chooses the form.  flow / flow_swap (both or neither): the records of the hash, for the evaluation of a
+// hashed witness program (witness_api.inc), which calls this ahead of its witness kernels.
+static void statement_digest_launch(rsv_ctx* c, const rsv_public_input* d_pi, size_t n_groups, uint32_t T, rsv_public_input* d_stmt, uint8_t* d_bad,
+                                    uint4* flow, uint8_t* flow_swap) {
+    const size_t row_max = c->opt.statement_row_max ? (size_t)c->opt.statement_row_max - 1 : kStatementRowMax;
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(d_pi);
+    uint32_t* stmt = reinterpret_cast<uint32_t*>(d_stmt);
+    const bool row = n_groups <= row_max;
+    const dim3 grid(grid_for(n_groups, row ? 16 : 64)), block(row ? 256 : 64);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, c->stream, rec, (uint32_t)n_groups, T, stmt, d_bad, flow, flow_swap); };
+    if (flow) row ? launch(k_statement_digest<FORM_ROW, true>) : launch(k_statement_digest<0, true>);
+    else row ? launch(k_statement_digest<FORM_ROW, false>) : launch(k_statement_digest<0, false>);
+}
+int rsv_statement_digest_dev(rsv_ctx* c, const rsv_public_input* d_pi, size_t n_groups, size_t copies, size_t n_own, rsv_public_input* d_stmt,
+                             uint8_t* d_bad) {
+    if (!c || (n_groups && (!d_pi || !d_stmt))) return RSV_E_NULL;
+    if (copies == 0 || copies > 64 || n_own == 0 || n_own > 4096 || n_groups > (1u << 26)) return RSV_E_SIZE;
+    if (n_groups > RSV_MAX_INPUT_RECORDS / (copies * n_own)) return RSV_E_SIZE;
+    if (((uintptr_t)d_pi & 3) || ((uintptr_t)d_stmt & 3)) return RSV_E_SIZE;
+    if (n_groups == 0) return RSV_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    statement_digest_launch(c, d_pi, n_groups, (uint32_t)(copies * n_own), d_stmt, d_bad, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
 int rsv_verify_hints(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                      const rsv_public_input* pi, size_t n_pi, const rsv_hints_out* out, uint8_t* accept, uint8_t* reason,
                      int device) {

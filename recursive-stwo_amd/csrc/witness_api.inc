@@ -50,6 +50,10 @@ struct rsv_witness_program {
     bool inputs_known = false;
     std::vector<uint32_t> fixed_idx, own_idx;
     uint32_t* d_own_idx = nullptr;
+    // A hashed program (rsv_witness_program_build_inputs_hashed): stmt_flow = S = ceil(copies * n_own / 8) + 1, the invocations
+    // of the statement hash, whose records follow the members' in the flow buffers ([rows][S] behind [members][flow_count]);
+    // 0 for every other program.
+    uint32_t stmt_flow = 0;
 };
 
 namespace {
@@ -134,6 +138,16 @@ struct WitnessGroupInputKernels {
     static constexpr auto level = k_witness_level_gi, level_wide = k_witness_level_wide_gi;
     static constexpr auto strip = k_witness_strip_gi;
     static constexpr auto small = k_witness_small_gi;
+};
+struct WitnessStmtKernels {
+    static constexpr auto level = k_witness_level_s, level_wide = k_witness_level_wide_s;
+    static constexpr auto strip = k_witness_strip_s;
+    static constexpr auto small = k_witness_small_s;
+};
+struct WitnessGroupStmtKernels {
+    static constexpr auto level = k_witness_level_gs, level_wide = k_witness_level_wide_gs;
+    static constexpr auto strip = k_witness_strip_gs;
+    static constexpr auto small = k_witness_small_gs;
 };
 
 // The program over n proofs (or n groups: a.n = n), in the launch form the batch size and the context's options choose.
@@ -222,7 +236,7 @@ struct WitnessStage {
         const uint64_t base = offsets[0], total = offsets[n] - base;
         std::vector<uint64_t> rel(n + 1);
         for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-        const size_t flow_records = n * (size_t)prog->shape.flow_count;
+        const size_t flow_records = n * ((size_t)prog->shape.flow_count + prog->stmt_flow);
         if (keep_flow) {
             HIP_TRY(d_flow.alloc(flow_records * 128));
             HIP_TRY(d_swap.alloc(flow_records));
@@ -263,13 +277,24 @@ struct WitnessStage {
 
 }  // namespace
 
+// rsv_witness_program_create; stmt_flow: the builder's, for a hashed program (its W_FLOW loads from the tail are in range)
+static int witness_program_create(const uint32_t* instr, size_t n_instr, const uint32_t* level_offsets, size_t n_levels, uint32_t n_vars,
+                                  const rsv_witness_shape* shape, int device, uint32_t stmt_flow, rsv_witness_program** out);
+
 extern "C" {
 
 int rsv_witness_program_create(const uint32_t* instr, size_t n_instr, const uint32_t* level_offsets, size_t n_levels,
                                uint32_t n_vars, const rsv_witness_shape* shape, int device, rsv_witness_program** out) {
+    return witness_program_create(instr, n_instr, level_offsets, n_levels, n_vars, shape, device, 0, out);
+}
+
+}  // extern "C"
+
+static int witness_program_create(const uint32_t* instr, size_t n_instr, const uint32_t* level_offsets, size_t n_levels, uint32_t n_vars,
+                                  const rsv_witness_shape* shape, int device, uint32_t stmt_flow, rsv_witness_program** out) {
     if (!instr || !level_offsets || !shape || !out) return RSV_E_NULL;
     if (n_instr == 0 || n_instr > (1u << 26)) return RSV_E_SIZE;
-    int rc = check_program(instr, n_instr, level_offsets, n_levels, n_vars, *shape, g_debug_log.load() != 0);
+    int rc = check_program(instr, n_instr, level_offsets, n_levels, n_vars, *shape, g_debug_log.load() != 0, stmt_flow);
     if (rc != RSV_OK) return rc;
     rc = select_device(device);
     if (rc != RSV_OK) return rc;
@@ -279,6 +304,7 @@ int rsv_witness_program_create(const uint32_t* instr, size_t n_instr, const uint
     p->n_instr = (uint32_t)n_instr;
     p->n_vars = n_vars;
     p->shape = *shape;
+    p->stmt_flow = stmt_flow;
     p->level_offsets.assign(level_offsets, level_offsets + n_levels + 1);
     for (size_t k = 0; k < n_instr; k++)
         if (instr[k * 8] == W_INPUT && instr[k * 8 + 4] >= p->input_slots) p->input_slots = instr[k * 8 + 4] + 1;
@@ -298,6 +324,8 @@ int rsv_witness_program_create(const uint32_t* instr, size_t n_instr, const uint
     *out = p;
     return RSV_OK;
 }
+
+extern "C" {
 
 void rsv_witness_program_destroy(rsv_witness_program* p) {
     if (!p) return;
@@ -332,8 +360,8 @@ static WitnessScratch witness_carve(const rsv_witness_program* prog, char* base,
     WitnessScratch w{};
     w.trace_cols = cv.take<uint32_t>(members * 4 * nq * 64);
     w.fri_cols = cv.take<uint32_t>(members * nt * nq * 24);
-    w.flow = cv.take<uint4>(members * (size_t)s.flow_count * 8);
-    w.flow_swap = cv.take<uint8_t>(members * (size_t)s.flow_count);
+    w.flow = cv.take<uint4>((members * (size_t)s.flow_count + rows * (size_t)prog->stmt_flow) * 8);  // (a hashed program: the hash's records behind the members')
+    w.flow_swap = cv.take<uint8_t>(members * (size_t)s.flow_count + rows * (size_t)prog->stmt_flow);
     if (with_vars) w.vars = cv.take<uint4>(rows * (size_t)prog->n_vars);
     w.bytes = cv.off + 4096;
     return w;
@@ -370,7 +398,8 @@ static int witness_check_cfg(const rsv_witness_program* prog, const rsv_cfg_set*
 // host memory; else [members][n_pi] records in HBM, every proof its own (rsv_verify_hints_inputs_dev).
 static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
                          size_t rows, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_own_pi,
-                         uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_verdict, uint8_t* d_reason, WitnessArgs& a) {
+                         uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_verdict, uint8_t* d_reason, WitnessArgs& a,
+                         uint8_t** flow_swap_used = nullptr) {
     const rsv_witness_shape& s = prog->shape;
     int rc = witness_check_cfg(prog, cfg);
     if (rc != RSV_OK) return rc;
@@ -405,6 +434,7 @@ static int witness_hints(rsv_ctx* c, const rsv_witness_program* prog, const uint
     a.instr = prog->d_instr; a.n = (uint32_t)rows; a.vars = w.vars; a.blob = d_blob; a.offsets = d_offsets; a.metas = c->last_metas;
     a.flow = w.flow; a.flow_stride = s.flow_count; a.trace_cols = w.trace_cols; a.fri_cols = w.fri_cols;
     a.nq = s.n_queries; a.n_trees = (uint32_t)nt;
+    if (flow_swap_used) *flow_swap_used = w.flow_swap;
     return RSV_OK;
 }
 
@@ -446,16 +476,19 @@ static int witness_check_batch(const rsv_witness_program* prog, const uint8_t* d
 // context's scratch from the shared records (host) and the caller's own ones (HBM), and the statement check; no host
 // synchronisation.  -> rec, bad [members] (k_witness_statement).
 static int witness_statement(rsv_ctx* c, const rsv_witness_program* prog, const rsv_public_input* pi_fixed, size_t n_fixed,
-                             const rsv_public_input* d_pi, size_t n_own, size_t members, const rsv_public_input** rec, const uint8_t** bad) {
+                             const rsv_public_input* d_pi, size_t n_own, size_t members, const rsv_public_input** rec, const uint8_t** bad,
+                             size_t stmt_rows = 0, rsv_public_input** stmt = nullptr) {
     HIP_TRY(hipSetDevice(c->device));
     const size_t n_pi = n_fixed + n_own, words = members * n_pi * PI_WORDS;
     Carve sz{nullptr};
-    sz.take<uint32_t>(words); sz.take<uint32_t>(n_fixed * PI_WORDS); sz.take<uint8_t>(members);
+    sz.take<uint32_t>(words); sz.take<uint32_t>(n_fixed * PI_WORDS); sz.take<uint32_t>(stmt_rows * STMT_WORDS * PI_WORDS); sz.take<uint8_t>(members);
     int rc = ensure_buf(c, &c->ws_inputs, &c->ws_inputs_bytes, sz.off);
     if (rc != RSV_OK) return rc;
     Carve cv{static_cast<char*>(c->ws_inputs)};
     uint32_t* d_rec = cv.take<uint32_t>(words);
     uint32_t* d_fixed = cv.take<uint32_t>(n_fixed * PI_WORDS);
+    uint32_t* d_stmt = cv.take<uint32_t>(stmt_rows * STMT_WORDS * PI_WORDS);  // a hashed program: the statement of every row (k_statement_digest)
+    if (stmt) *stmt = reinterpret_cast<rsv_public_input*>(d_stmt);
     uint8_t* d_bad = cv.take<uint8_t>(members);
     if (n_fixed) HIP_TRY(hipMemcpyAsync(d_fixed, pi_fixed, sizeof(rsv_public_input) * n_fixed, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemsetAsync(d_bad, 0, members, c->stream));
@@ -473,16 +506,27 @@ static int witness_eval_impl(rsv_ctx* c, const rsv_witness_program* prog, const 
                              uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason) {
     const rsv_public_input* rec = nullptr;
     const uint8_t* bad = nullptr;
-    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, n, &rec, &bad) : RSV_OK;
+    rsv_public_input* stmt = nullptr;
+    uint8_t* swap_used = nullptr;
+    const size_t S = prog->stmt_flow;
+    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, n, &rec, &bad, S ? n : 0, &stmt) : RSV_OK;
     if (rc != RSV_OK) return rc;
-    WitnessInputArgs a{};
-    rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a);
+    WitnessStmtArgs a{};
+    rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a, &swap_used);
     if (rc != RSV_OK) return rc;
     a.accept = d_accept;
     if (n_own) {
         hipLaunchKernelGGL(k_witness_statement_verdict, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, bad, (uint32_t)n, d_accept, d_reason);
         a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
-        witness_launch<WitnessInputKernels>(c, prog, a, n);
+        if (S) {  // a hashed program: the statement and the records of its hash, behind the members' (a malformed record
+                  // is the member's R_PARSE above: k_witness_statement checks what the digest kernel would flag)
+            const size_t tail = n * (size_t)prog->shape.flow_count;
+            uint4* flow_tail = const_cast<uint4*>(a.flow) + tail * 8;
+            statement_digest_launch(c, d_pi, n, (uint32_t)n_own, stmt, nullptr, flow_tail, swap_used + tail);
+            a.stmt = reinterpret_cast<const PubInput*>(stmt); a.flow_tail = flow_tail;
+            a.member_flow = prog->shape.flow_count; a.stmt_flow = (uint32_t)S;
+            witness_launch<WitnessStmtKernels>(c, prog, a, n);
+        } else witness_launch<WitnessInputKernels>(c, prog, static_cast<const WitnessInputArgs&>(a), n);
     } else witness_launch<WitnessKernels>(c, prog, static_cast<const WitnessArgs&>(a), n);
     return witness_finish(c, prog, a.vars, d_variables, n);
 }
@@ -507,6 +551,7 @@ int rsv_witness_eval_inputs_dev(rsv_ctx* c, const rsv_witness_program* prog, con
     if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
     if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
     if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;
+    if (prog->stmt_flow && prog->shape.copies != 1) return RSV_E_SIZE;  // a hashed program of several copies hashes a GROUP's statements
     int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, n);
     if (rc == RSV_OK && n_own) rc = witness_check_batch(prog, d_blob, d_offsets, n, cfg);
     if (rc != RSV_OK) return rc;
@@ -525,11 +570,14 @@ static int witness_groups_impl(rsv_ctx* c, const rsv_witness_program* prog, cons
     const size_t copies = prog->shape.copies, members = n_groups * copies;
     const rsv_public_input* rec = nullptr;
     const uint8_t* bad = nullptr;
-    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, members, &rec, &bad) : RSV_OK;
+    rsv_public_input* stmt = nullptr;
+    uint8_t* swap_used = nullptr;
+    const size_t S = prog->stmt_flow;
+    int rc = n_own ? witness_statement(c, prog, pi, n_pi, d_pi, n_own, members, &rec, &bad, S ? n_groups : 0, &stmt) : RSV_OK;
     if (rc != RSV_OK) return rc;
-    WitnessGroupInputArgs a{};  // d_flow is [n_groups][copies][flow_count]: the members' records, one proof after the other
+    WitnessGroupStmtArgs a{};  // d_flow is [n_groups][copies][flow_count]: the members' records, one proof after the other
     rc = witness_hints(c, prog, d_blob, d_offsets, members, n_groups, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap,
-                       d_member_accept, d_member_reason, a);
+                       d_member_accept, d_member_reason, a, &swap_used);
     if (rc != RSV_OK) return rc;
     {   // the table of copies goes to the device on the first call
         rsv_witness_program* wp = const_cast<rsv_witness_program*>(prog);
@@ -552,7 +600,14 @@ static int witness_groups_impl(rsv_ctx* c, const rsv_witness_program* prog, cons
     a.accept = d_accept; a.copy_of = prog->d_copy_of; a.copies = (uint32_t)copies;
     if (n_own) {
         a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
-        witness_launch<WitnessGroupInputKernels>(c, prog, a, n_groups);
+        if (S) {  // a hashed program: as in witness_eval_impl, a group's copies * n_own records hashed in copy-major order
+            const size_t tail = members * (size_t)prog->shape.flow_count;
+            uint4* flow_tail = const_cast<uint4*>(a.flow) + tail * 8;
+            statement_digest_launch(c, d_pi, n_groups, (uint32_t)(copies * n_own), stmt, nullptr, flow_tail, swap_used + tail);
+            a.stmt = reinterpret_cast<const PubInput*>(stmt); a.flow_tail = flow_tail;
+            a.member_flow = (uint32_t)(copies * prog->shape.flow_count); a.stmt_flow = (uint32_t)S;
+            witness_launch<WitnessGroupStmtKernels>(c, prog, a, n_groups);
+        } else witness_launch<WitnessGroupInputKernels>(c, prog, static_cast<const WitnessGroupInputArgs&>(a), n_groups);
     } else witness_launch<WitnessGroupKernels>(c, prog, static_cast<const WitnessGroupArgs&>(a), n_groups);
     return witness_finish(c, prog, a.vars, d_variables, n_groups);
 }
@@ -636,12 +691,20 @@ int rsv_witness_eval_inputs(const rsv_witness_program* prog, const uint8_t* blob
     if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi_fixed, n_fixed, flow != nullptr, pi_own, n_own);
     if (rc == RSV_OK) rc = st.finish(accept, reason);
     if (rc != RSV_OK) return rc;
-    const size_t flow_records = n * (size_t)prog->shape.flow_count;
+    const size_t flow_records = n * ((size_t)prog->shape.flow_count + prog->stmt_flow);
     HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
     if (flow) {
         HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
     }
+    return RSV_OK;
+}
+
+int rsv_witness_program_statement(const rsv_witness_program* prog, uint32_t* hashed, uint32_t* n_words, uint32_t* stmt_flow_count) {
+    if (!prog) return RSV_E_NULL;
+    if (hashed) *hashed = prog->stmt_flow != 0;
+    if (n_words) *n_words = prog->stmt_flow ? STMT_WORDS : 0;
+    if (stmt_flow_count) *stmt_flow_count = prog->stmt_flow;
     return RSV_OK;
 }
 

@@ -446,19 +446,38 @@ struct WitnessProgram {
     // the same with inputs[n_fixed ..) the proof's OWN inputs: PublicInput variables 4 + c * n_own + k of the circuit instead
     // of constants, so that one program serves proofs that differ in them (rsv_witness_program_build_inputs; the values
     // have to be M31: the reference's PublicInput row enforces it)
+    // hashed: the circuit's statement is the eight words of the digest of the own records (variables 4 .. 11; the records
+    // themselves are witness variables from 12 on), whatever their number: rsv_witness_program_build_inputs_hashed
     static WitnessProgram build_inputs(const std::vector<uint8_t>& template_proof, const PcsConfig& config, const Inputs& inputs, size_t n_fixed,
-                                       uint32_t multipliers = 1, const std::vector<uint8_t>& set_walks = {}) {
+                                       uint32_t multipliers = 1, const std::vector<uint8_t>& set_walks = {}, bool hashed = false) {
         WitnessProgram p;
         const rsv_pcs_config abi_cfg = config.abi();
         auto pi = abi_inputs(inputs);
         if (!set_walks.empty() && set_walks.size() != multipliers) throw std::runtime_error("set_walks: one entry per copy");
-        check(rsv_witness_program_build_inputs(template_proof.data(), template_proof.size(), &abi_cfg, pi.data(), pi.size(), n_fixed, multipliers,
-                                               set_walks.empty() ? nullptr : set_walks.data(), default_device(), &p.handle),
-              "rsv_witness_program_build_inputs");
+        if (hashed)
+            check(rsv_witness_program_build_inputs_hashed(template_proof.data(), template_proof.size(), &abi_cfg, pi.data(), pi.size(), n_fixed,
+                                                          multipliers, set_walks.empty() ? nullptr : set_walks.data(), default_device(), &p.handle),
+                  "rsv_witness_program_build_inputs_hashed");
+        else
+            check(rsv_witness_program_build_inputs(template_proof.data(), template_proof.size(), &abi_cfg, pi.data(), pi.size(), n_fixed, multipliers,
+                                                   set_walks.empty() ? nullptr : set_walks.data(), default_device(), &p.handle),
+                  "rsv_witness_program_build_inputs");
         check(rsv_witness_program_info(p.handle, &p.n_vars, nullptr, &p.shape), "rsv_witness_program_info");
-        p.flow_wires.resize((size_t)p.shape.copies * p.shape.flow_count);
+        p.flow_wires.resize((size_t)p.shape.copies * p.shape.flow_count + p.statement().stmt_flow_count);
         check(rsv_witness_program_export(p.handle, nullptr, nullptr, &p.flow_wires[0][0]), "rsv_witness_program_export");
         return p;
+    }
+    static WitnessProgram build_inputs_hashed(const std::vector<uint8_t>& template_proof, const PcsConfig& config, const Inputs& inputs,
+                                              size_t n_fixed, uint32_t multipliers = 1, const std::vector<uint8_t>& set_walks = {}) {
+        return build_inputs(template_proof, config, inputs, n_fixed, multipliers, set_walks, true);
+    }
+    // whether the program's statement is the digest of the statements it verifies, its words (8) and the invocations of the
+    // hash, whose flow records follow the members' (rsv_witness_program_statement); zeros for any other program
+    struct Statement { bool hashed; uint32_t n_words, stmt_flow_count; };
+    Statement statement() const {
+        uint32_t hashed = 0, n_words = 0, count = 0;
+        check(rsv_witness_program_statement(handle, &hashed, &n_words, &count), "rsv_witness_program_statement");
+        return Statement{hashed != 0, n_words, count};
     }
     // the circuit's Plonk rows (a_wire, b_wire, c_wire, op, poseidon_wire, enforce_c_m31) for the proof whose `variables`
     // are given (empty: the template's): built programs only
@@ -473,6 +492,8 @@ struct WitnessProgram {
         return rows;
     }
     void save(const std::string& path) const {
+        // (a hashed program's W_FLOW loads from the tail of the flow buffers, which a program made from arrays does not have)
+        if (statement().hashed) throw std::runtime_error("a hashed witness program cannot be saved: build it again from its template proof");
         uint32_t n_levels = 0;
         check(rsv_witness_program_info(handle, nullptr, &n_levels, nullptr), "rsv_witness_program_info");
         std::vector<uint32_t> instr((size_t)n_vars * 8), levels(n_levels + 1);

@@ -47,7 +47,14 @@ class Program:
         self.instr, self.level_offsets, self.n_vars, self.shape = instr, level_offsets, n_vars, shape
         self.flow_wires = flow_wires if flow_wires is not None else np.zeros((shape["copies"] * shape["flow_count"], 5), np.uint32)
 
+    def _not_hashed(self, what):
+        # a hashed program (WitnessProgram.build(hashed=True)) loads records of its statement hash from the tail of the flow
+        # buffers; a program made from these arrays has no tail (rsv_witness_program_create), so the arrays are for reading only
+        if len(self.flow_wires) != self.shape["copies"] * self.shape["flow_count"]:
+            raise ValueError(f"{what}: a hashed witness program cannot be saved or loaded; build it again from its template proof")
+
     def save(self, path):
+        self._not_hashed("Program.save")
         np.savez_compressed(path, instr=self.instr, level_offsets=self.level_offsets, n_vars=np.array([self.n_vars]),
                             shape=np.array([self.shape[k] for k in SHAPE_KEYS], dtype=np.uint32), flow_wires=self.flow_wires)
 
@@ -56,6 +63,7 @@ class Program:
     def save_raw(self, path):
         """The flat file the C++ host mirror loads (host/recursive_stwo.hpp, WitnessProgram::load): "RSVW", version 1, n_vars,
         n_levels, the 9 shape words, level_offsets, instr, flow_wires."""
+        self._not_hashed("Program.save_raw")
         head = np.array([self.RAW_MAGIC, 1, self.n_vars, len(self.level_offsets) - 1] + [self.shape[k] for k in SHAPE_KEYS], dtype=np.uint32)
         with open(path, "wb") as f:
             f.write(head.tobytes())
