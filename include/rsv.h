@@ -1158,7 +1158,10 @@ int rsv_witness_tree3_dev(rsv_ctx* ctx, const rsv_witness_program* prog, const u
  * rsv_fri_sizes: host arithmetic for the recursion circuit's shape (log sizes lp, lq): sizes[3] the distinct quotient
  * sizes descending (lde of tree 3: max(lp + 1, lq + 2) + log_blowup, then lp + log_blowup and lq + log_blowup), their
  * number, n_inner, and the words per proof of d_quot, d_layers and d_last_poly.  RSV_E_SIZE for what rsv_witness_fri_dev
- * refuses. */
+ * refuses of the sizes, but for one case: min(lp, lq) == log_last + 1 is answered here and refused by rsv_witness_fri_dev
+ * (RSV_E_SIZE) — the smallest column would enter the fold behind the last inner layer, where the reference's prover
+ * asserts and no verifier folds it in (the proof would be RSV_R_FRI_LAST); rsv_fri_commit_dev, which serves no verifier,
+ * takes such sizes. */
 int rsv_fri_sizes(uint32_t lp, uint32_t lq, uint32_t log_blowup, uint32_t log_last, uint32_t* sizes, uint32_t* n_sizes, uint32_t* n_inner,
                   size_t* quot_words, size_t* layer_words, size_t* last_words);
 /* Which points apply to a group's columns: point k (< n_points) to the columns col_lo[k] .. col_hi[k] - 1 (col_hi[k] <=

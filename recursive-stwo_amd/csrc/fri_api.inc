@@ -516,6 +516,11 @@ int witness_fri(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_p
     size_t ns = 0;
     int rc = fr_check_chain(lp, lq, log_blowup, log_last, n, sizes, &ns);
     if (rc != RSV_OK) return rc;
+    // A proof for the verifier: a column enters the fold in front of the inner layer of half its size (the reference's prover
+    // asserts that every column met one; its verifier folds nothing in behind the last inner layer).  The smallest column one
+    // size above the last layer would go into the last polynomial alone, and no verifier accepts that proof (RSV_R_FRI_LAST).
+    // rsv_fri_sizes stays the arithmetic of the sizes and answers there.
+    if (sizes[ns - 1] - log_blowup == log_last + 1) return RSV_E_SIZE;
     if (!o.d_layers && sizes[0] - 1 - log_last - log_blowup > 0) return RSV_E_NULL;
     if (o.tail_log > RSV_MAX_FRI_TAIL_LOG) return RSV_E_SIZE;
     ChainTrees ct;

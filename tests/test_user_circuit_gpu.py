@@ -14,6 +14,7 @@ from tests import oracle_binding as ob
 from tests import user_circuit_ref as U
 from tests.chain_harness import DEV, FILL, chain, dev, inputs_of, pin_of, program_of, u32
 from tests.conftest import fixture_cfg, read_proof
+from tests.verify_grid import _finish, _run
 
 pytestmark = pytest.mark.gpu
 SRC, DST = "level10-1.bin", "level11-1.bin"
@@ -27,15 +28,6 @@ def ctx(rsv):
     c = rsv.Context(0)
     yield c
     c.close()
-
-
-def _finish(ch, cfg):
-    for stage in ("trace", "commit", "tree3", "sample", "fri"):
-        getattr(ch, stage)()
-    ch.pow(cfg.pow_bits, cfg.n_queries)
-    ch.open()
-    ch.fri_open()
-    return ch
 
 
 @pytest.fixture(scope="module")
@@ -174,10 +166,6 @@ def test_circuit_check_names_the_models_row(rsv, ctx, level10, layout):
 
 
 # ---------------------------------------------------------------- 4. the small circuits through the whole chain
-def _cfg(rsv, config):
-    return rsv.PcsConfig(*config)
-
-
 def _verify_both(rsv, ctx, proof, cfg, inputs):
     """-> ((accept, reason) of the library, of the C oracle) for one proof."""
     acc, reason = rsv.verify_batch([proof], cfg, inputs)
@@ -187,14 +175,6 @@ def _verify_both(rsv, ctx, proof, cfg, inputs):
 
 def _circuit(rsv, b):
     return rsv.Circuit(b.gates, b.flow_wires, b.n_vars, b.num_input, b.witness_ops)
-
-
-def _run(rsv, ctx, circ, builts, config, check=True, flows=None):
-    cfg = _cfg(rsv, config)
-    ch = rsv.Chain(ctx, circ, len(builts), cfg.log_blowup_factor, log_last=cfg.log_last_layer_degree_bound, fill=FILL, caps=True, device=DEV)
-    flows = [b.unbound_flow() if check else b.flow for b in builts] if flows is None else flows
-    ch.load(np.stack([b.variables for b in builts]), np.stack(flows), None if check else np.stack([b.swap for b in builts]), check=check)
-    return _finish(ch, cfg), cfg
 
 
 @pytest.mark.parametrize("config", CONFIGS, ids=lambda c: "pow%d-blowup%d-last%d-q%d" % (c[0], c[1], c[2], c[3]))
