@@ -26,6 +26,7 @@ namespace rsv {
 constexpr uint32_t PLONK_COLS_K = 12, POSEIDON_COLS_K = 48;
 
 struct TraceArgs {
+    static constexpr bool hashed = false;  // (TraceStmtArgs)
     const uint4* vars;          // [n][n_vars] (by_variable = 0) or [n_vars][n] QM31
     uint32_t n_vars, n;
     bool by_variable;
@@ -44,11 +45,10 @@ struct TraceArgs {
 // A hashed program (rsv_witness_program_build_inputs_hashed): the invocations behind the copies', k = copies * flow_count ..
 // + stmt_flow, are the statement hash's, whose records lie at the tail of the flow buffers: [n][stmt_flow] from record `tail`.
 struct TraceStmtArgs : TraceArgs {
+    static constexpr bool hashed = true;
     uint32_t stmt_flow;
     size_t tail;
 };
-template <class A> struct trace_stmt { static constexpr bool value = false; };
-template <> struct trace_stmt<TraceStmtArgs> { static constexpr bool value = true; };
 
 // ---------------------------------------------------------------- Plonk
 // Block b: proof b / blocks_per_proof, rows (b % blocks_per_proof) * 256 ...: the workgroups in flight share proofs.
@@ -158,7 +158,7 @@ __device__ __forceinline__ void trace_poseidon(const A& a, uint32_t* lds) {
         }
         sw = a.swap[rec] != 0;
     }
-    if constexpr (trace_stmt<A>::value)
+    if constexpr (A::hashed)
         if (k >= a.flow_count * a.copies && k - a.flow_count * a.copies < a.stmt_flow) {
             const size_t rec = a.tail + (size_t)p * a.stmt_flow + (k - a.flow_count * a.copies);
             const uint4* f = a.flow + rec * 8;
@@ -217,21 +217,10 @@ __device__ __forceinline__ void trace_poseidon(const A& a, uint32_t* lds) {
     trace_flush(lds, mid0, mid1, out, Q, 16, 4, row_base, n_blocks);
     trace_flush(lds, s1, s2, out, Q, 32, 4, row_base, n_blocks);
 }
-__global__ __launch_bounds__(64) void k_trace_poseidon(TraceArgs a) {
+template <bool GROUPED, class A>
+__global__ __launch_bounds__(64) void k_trace_poseidon(A a) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
-    trace_poseidon<false>(a, lds);
-}
-__global__ __launch_bounds__(64) void k_trace_poseidon_g(TraceArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
-    trace_poseidon<true>(a, lds);
-}
-__global__ __launch_bounds__(64) void k_trace_poseidon_s(TraceStmtArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
-    trace_poseidon<false>(a, lds);
-}
-__global__ __launch_bounds__(64) void k_trace_poseidon_gs(TraceStmtArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[TRACE_STAGE];
-    trace_poseidon<true>(a, lds);
+    trace_poseidon<GROUPED>(a, lds);
 }
 
 // The rows behind the padded flow, [6 * n_pad, 2^lq) of all 48 columns of every proof: zero.  The start is a multiple of

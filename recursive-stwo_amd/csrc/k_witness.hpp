@@ -15,8 +15,10 @@
 
 namespace rsv {
 
-// (enum WitnessOp: layout.hpp)
+// (enum WitnessOp: layout.hpp)  The argument types say themselves what witness_exec reads from them: grouped (copy_of, copies),
+// inputs (own, n_own), hashed (stmt, flow_tail, member_flow, stmt_flow), inherited and set where they turn true.
 struct WitnessArgs {
+    static constexpr bool grouped = false, inputs = false, hashed = false;
     const uint32_t* instr;  // [n_instr][8]: op, dst, a, b, imm0..3
     uint32_t begin, end;    // this level's instructions
     uint32_t n;             // proofs
@@ -35,6 +37,7 @@ struct WitnessArgs {
 // group p's circuit verifies proof p * copies + c: vars, dst, accept and the arithmetic ops index the group, blob, offsets,
 // metas, flow, trace_cols and fri_cols the proof.
 struct WitnessGroupArgs : WitnessArgs {
+    static constexpr bool grouped = true;
     const uint8_t* copy_of;  // [n_vars]: the copy that allocated a variable (circuit_program.hpp), read for hints only
     uint32_t copies;
 };
@@ -42,10 +45,12 @@ struct WitnessGroupArgs : WitnessArgs {
 // record imm0 of the proof's (grouped: the member's) own records.  Argument types of their own, so that the kernels above
 // them stay the instructions they were; the launcher takes these only for a program that has a W_INPUT.
 struct WitnessInputArgs : WitnessArgs {
+    static constexpr bool inputs = true;
     const PubInput* own;  // [n][n_own]: the caller's records, as rsv_verify_batch_inputs_dev takes them
     uint32_t n_own;
 };
 struct WitnessGroupInputArgs : WitnessGroupArgs {
+    static constexpr bool inputs = true;
     const PubInput* own;  // [n * copies][n_own]
     uint32_t n_own;
 };
@@ -53,27 +58,17 @@ struct WitnessGroupInputArgs : WitnessGroupArgs {
 // left for the proof (grouped: the group), and a W_FLOW whose index lies behind the copies' (>= member_flow) reads the
 // records of the statement hash, [n][stmt_flow] at the tail of the flow buffer.  Argument types of their own again.
 struct WitnessStmtArgs : WitnessInputArgs {
+    static constexpr bool hashed = true;
     const PubInput* stmt;     // [n][8]
     const uint4* flow_tail;   // [n][stmt_flow][8]
     uint32_t member_flow, stmt_flow;
 };
 struct WitnessGroupStmtArgs : WitnessGroupInputArgs {
+    static constexpr bool hashed = true;
     const PubInput* stmt;
     const uint4* flow_tail;
     uint32_t member_flow, stmt_flow;
 };
-template <class A> struct witness_grouped { static constexpr bool value = false; };
-template <> struct witness_grouped<WitnessGroupArgs> { static constexpr bool value = true; };
-template <> struct witness_grouped<WitnessGroupInputArgs> { static constexpr bool value = true; };
-template <> struct witness_grouped<WitnessGroupStmtArgs> { static constexpr bool value = true; };
-template <class A> struct witness_inputs { static constexpr bool value = false; };
-template <> struct witness_inputs<WitnessInputArgs> { static constexpr bool value = true; };
-template <> struct witness_inputs<WitnessGroupInputArgs> { static constexpr bool value = true; };
-template <> struct witness_inputs<WitnessStmtArgs> { static constexpr bool value = true; };
-template <> struct witness_inputs<WitnessGroupStmtArgs> { static constexpr bool value = true; };
-template <class A> struct witness_stmt { static constexpr bool value = false; };
-template <> struct witness_stmt<WitnessStmtArgs> { static constexpr bool value = true; };
-template <> struct witness_stmt<WitnessGroupStmtArgs> { static constexpr bool value = true; };
 
 // one instruction (its eight words: w0 = op, dst, a, b; w1 = imm0..3) for one proof
 template <class A>
@@ -81,16 +76,16 @@ __device__ __forceinline__ void witness_exec(const A& a, const uint4 w0, const u
     const uint32_t op = w0.x, dst = w0.y, i0 = w1.x, i1 = w1.y, i2 = w1.z;
     const bool ok = a.accept[p] != 0;  // a rejected proof's sections may not be where the program expects them
     size_t q = p;                      // the proof a hint is read from: grouped, the group's member dst's copy verifies
-    if constexpr (witness_grouped<A>::value)
+    if constexpr (A::grouped)
         if (op >= W_FLOW && ok) q = (size_t)p * a.copies + a.copy_of[dst];
     const auto hint = [&]() {  // the ops that read what the verifying pass left
         uint4 r = make_uint4(0, 0, 0, 0);
-        if constexpr (witness_inputs<A>::value)
+        if constexpr (A::inputs)
             if (op == W_INPUT) {  // (imm0 < n_own: the evaluating call checked the program against the batch's n_own)
                 if (ok) r = u4_words(a.own[q * a.n_own + i0].value);
                 return r;
             }
-        if constexpr (witness_stmt<A>::value) {
+        if constexpr (A::hashed) {
             if (op == W_STMT) {  // (imm0 < 8: check_program)
                 if (ok) r.x = a.stmt[(size_t)p * STMT_WORDS + i0].value[0];
                 return r;
@@ -143,12 +138,7 @@ __device__ __forceinline__ void witness_level(const A& a) {
     if (i >= a.end) return;
     witness_exec(a, i, p);
 }
-__global__ __launch_bounds__(256) void k_witness_level(WitnessArgs a) { witness_level(a); }
-__global__ __launch_bounds__(256) void k_witness_level_g(WitnessGroupArgs a) { witness_level(a); }
-__global__ __launch_bounds__(256) void k_witness_level_i(WitnessInputArgs a) { witness_level(a); }
-__global__ __launch_bounds__(256) void k_witness_level_gi(WitnessGroupInputArgs a) { witness_level(a); }
-__global__ __launch_bounds__(256) void k_witness_level_s(WitnessStmtArgs a) { witness_level(a); }
-__global__ __launch_bounds__(256) void k_witness_level_gs(WitnessGroupStmtArgs a) { witness_level(a); }
+template <class A> __global__ __launch_bounds__(256) void k_witness_level(A a) { witness_level(a); }
 
 // the same for batches of at least a wave of proofs: blockIdx.y = the instruction, so that the instruction words are scalar
 // loads and the switch a scalar branch (in the 1-D form a wave may straddle two instructions, and every lane divides)
@@ -158,12 +148,7 @@ __device__ __forceinline__ void witness_level_wide(const A& a) {
     if (p >= a.n) return;
     witness_exec(a, i, p);
 }
-__global__ __launch_bounds__(256) void k_witness_level_wide(WitnessArgs a) { witness_level_wide(a); }
-__global__ __launch_bounds__(256) void k_witness_level_wide_g(WitnessGroupArgs a) { witness_level_wide(a); }
-__global__ __launch_bounds__(256) void k_witness_level_wide_i(WitnessInputArgs a) { witness_level_wide(a); }
-__global__ __launch_bounds__(256) void k_witness_level_wide_gi(WitnessGroupInputArgs a) { witness_level_wide(a); }
-__global__ __launch_bounds__(256) void k_witness_level_wide_s(WitnessStmtArgs a) { witness_level_wide(a); }
-__global__ __launch_bounds__(256) void k_witness_level_wide_gs(WitnessGroupStmtArgs a) { witness_level_wide(a); }
+template <class A> __global__ __launch_bounds__(256) void k_witness_level_wide(A a) { witness_level_wide(a); }
 
 // Levels l0 .. l1 walked by ONE workgroup for its own proofs (dependencies never cross proofs): instruction slot `slot` of
 // `n_slots` takes instructions begin + slot, + n_slots, ... of every level, a workgroup barrier ends a level (the waves of
@@ -185,28 +170,8 @@ __device__ __forceinline__ void witness_walk(const A& a, const uint32_t* __restr
 // dependencies never cross proofs, so a workgroup that owns 64 proofs can walk the levels on its own — its four waves
 // share a level's instructions, a workgroup barrier separates levels (the waves of a workgroup share the CU's L1, so what
 // one wave stored is what the next level's loads see).
-__global__ __launch_bounds__(256) void k_witness_strip(WitnessArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
-    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
-    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
-}
-__global__ __launch_bounds__(256) void k_witness_strip_g(WitnessGroupArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
-    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
-    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
-}
-
-__global__ __launch_bounds__(256) void k_witness_strip_i(WitnessInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
-    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
-    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
-}
-__global__ __launch_bounds__(256) void k_witness_strip_gi(WitnessGroupInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
-    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
-    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
-}
-__global__ __launch_bounds__(256) void k_witness_strip_s(WitnessStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
-    const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
-    witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
-}
-__global__ __launch_bounds__(256) void k_witness_strip_gs(WitnessGroupStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
+template <class A>
+__global__ __launch_bounds__(256) void k_witness_strip(A a, const uint32_t* __restrict__ level_offsets, uint32_t l0, uint32_t l1) {
     const uint32_t p = blockIdx.x * 64 + (threadIdx.x & 63u), wv = threadIdx.x >> 6;
     witness_walk(a, level_offsets, l0, l1, p, wv, 4u);
 }
@@ -217,34 +182,8 @@ __global__ __launch_bounds__(256) void k_witness_strip_gs(WitnessGroupStmtArgs a
 // (1 024 / P2) instruction slots x P2 proofs, a level is a few rounds of slots, a workgroup barrier ends it.  265 barriers
 // instead of 140 launches with a machine-wide drain between them; the price is narrower rows (P2 x 16 B per instruction
 // instead of 1 KB), which is why the level-per-launch form takes over for large batches (witness_api.inc).
-__global__ __launch_bounds__(1024) void k_witness_small(WitnessArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                        uint32_t log_p2) {
-    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
-    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
-}
-__global__ __launch_bounds__(1024) void k_witness_small_g(WitnessGroupArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                          uint32_t log_p2) {
-    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
-    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
-}
-
-__global__ __launch_bounds__(1024) void k_witness_small_i(WitnessInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                          uint32_t log_p2) {
-    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
-    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
-}
-__global__ __launch_bounds__(1024) void k_witness_small_gi(WitnessGroupInputArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                           uint32_t log_p2) {
-    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
-    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
-}
-__global__ __launch_bounds__(1024) void k_witness_small_s(WitnessStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                          uint32_t log_p2) {
-    const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
-    witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
-}
-__global__ __launch_bounds__(1024) void k_witness_small_gs(WitnessGroupStmtArgs a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels,
-                                                           uint32_t log_p2) {
+template <class A>
+__global__ __launch_bounds__(1024) void k_witness_small(A a, const uint32_t* __restrict__ level_offsets, uint32_t n_levels, uint32_t log_p2) {
     const uint32_t p = (blockIdx.x << log_p2) + (threadIdx.x & ((1u << log_p2) - 1u));
     witness_walk(a, level_offsets, 0, n_levels, p, threadIdx.x >> log_p2, 1024u >> log_p2);
 }

@@ -137,8 +137,12 @@ static int witness_trace(rsv_ctx* c, const rsv_witness_program* prog, const uint
     if (d_plonk) hipLaunchKernelGGL(rsv::k_trace_plonk, dim3((unsigned)plonk_blocks), dim3(256), 0, st, plain);
     if (d_ops && n_ops) hipLaunchKernelGGL(rsv::k_trace_ops, dim3(grid_for(n_ops * n, 256)), dim3(256), 0, st, plain, prog->d_trace_ops, (uint32_t)n_ops, d_ops);
     if (d_poseidon) {
-        if (prog->stmt_flow) hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_gs : rsv::k_trace_poseidon_s, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, a);
-        else hipLaunchKernelGGL(grouped ? rsv::k_trace_poseidon_g : rsv::k_trace_poseidon, dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, plain);
+        const auto launch = [&](const auto& args) {  // k_trace_poseidon<grouped, the argument type>
+            using A = std::decay_t<decltype(args)>;
+            hipLaunchKernelGGL((grouped ? rsv::k_trace_poseidon<true, A> : rsv::k_trace_poseidon<false, A>), dim3((unsigned)poseidon_blocks), dim3(rsv::TRACE_WAVE), 0, st, args);
+        };
+        if (prog->stmt_flow) launch(a);
+        else launch(plain);
         if (tail_threads)
             hipLaunchKernelGGL(rsv::k_trace_zero_tail, dim3(grid_for(tail_threads, 256)), dim3(256), 0, st, d_poseidon, a.log_poseidon,
                                (uint32_t)tail_first, (uint64_t)rsv::POSEIDON_COLS_K * n);

@@ -117,41 +117,9 @@ __global__ void k_witness_statement_verdict(const uint8_t* __restrict__ bad, uin
     if (reason) reason[p] = (uint8_t)R_PARSE;
 }
 
-// The kernels of the two forms of the evaluation (k_witness.hpp): a batch of proofs, and groups of `copies` proofs.
-struct WitnessKernels {
-    static constexpr auto level = k_witness_level, level_wide = k_witness_level_wide;
-    static constexpr auto strip = k_witness_strip;
-    static constexpr auto small = k_witness_small;
-};
-struct WitnessGroupKernels {
-    static constexpr auto level = k_witness_level_g, level_wide = k_witness_level_wide_g;
-    static constexpr auto strip = k_witness_strip_g;
-    static constexpr auto small = k_witness_small_g;
-};
-
-struct WitnessInputKernels {
-    static constexpr auto level = k_witness_level_i, level_wide = k_witness_level_wide_i;
-    static constexpr auto strip = k_witness_strip_i;
-    static constexpr auto small = k_witness_small_i;
-};
-struct WitnessGroupInputKernels {
-    static constexpr auto level = k_witness_level_gi, level_wide = k_witness_level_wide_gi;
-    static constexpr auto strip = k_witness_strip_gi;
-    static constexpr auto small = k_witness_small_gi;
-};
-struct WitnessStmtKernels {
-    static constexpr auto level = k_witness_level_s, level_wide = k_witness_level_wide_s;
-    static constexpr auto strip = k_witness_strip_s;
-    static constexpr auto small = k_witness_small_s;
-};
-struct WitnessGroupStmtKernels {
-    static constexpr auto level = k_witness_level_gs, level_wide = k_witness_level_wide_gs;
-    static constexpr auto strip = k_witness_strip_gs;
-    static constexpr auto small = k_witness_small_gs;
-};
-
-// The program over n proofs (or n groups: a.n = n), in the launch form the batch size and the context's options choose.
-template <class K, class A>
+// The program over n proofs (or n groups: a.n = n), in the launch form the batch size and the context's options choose:
+// the kernels of k_witness.hpp over the argument type A.
+template <class A>
 void witness_launch(rsv_ctx* c, const rsv_witness_program* prog, A a, size_t n) {
     hipStream_t st = c->stream;
     const size_t n_levels = prog->level_offsets.size() - 1;
@@ -164,7 +132,7 @@ void witness_launch(rsv_ctx* c, const rsv_witness_program* prog, A a, size_t n) 
     const bool small = c->opt.witness_small_max ? n <= (size_t)c->opt.witness_small_max - 1
                                                 : n <= SMALL_MAX && (((uint64_t)prog->n_instr << log_p2) >> 10) <= SMALL_ROUNDS;
     if (small) {
-        hipLaunchKernelGGL(K::small, dim3(grid_for(n, 1u << log_p2)), dim3(1024), 0, st, a, prog->d_levels, (uint32_t)n_levels, log_p2);
+        hipLaunchKernelGGL(k_witness_small<A>, dim3(grid_for(n, 1u << log_p2)), dim3(1024), 0, st, a, prog->d_levels, (uint32_t)n_levels, log_p2);
     } else {
     // Mid-size batches: the wide head of the program level by level, then EVERYTHING behind it in one launch, a 1 024-lane
     // workgroup per 2^walk_log proofs walking the remaining levels (most of them ~100 instructions wide: a launch each
@@ -186,19 +154,38 @@ void witness_launch(rsv_ctx* c, const rsv_witness_program* prog, A a, size_t n) 
             for (uint32_t b = a.begin; b < end; b += 65535u) {
                 a.begin = b;
                 a.end = end - b > 65535u ? b + 65535u : end;
-                hipLaunchKernelGGL(K::level_wide, dim3(grid_for(n, block), a.end - a.begin), dim3(block), 0, st, a);
+                hipLaunchKernelGGL(k_witness_level_wide<A>, dim3(grid_for(n, block), a.end - a.begin), dim3(block), 0, st, a);
             }
             continue;
         }
         const size_t threads = (size_t)(a.end - a.begin) * n;
-        hipLaunchKernelGGL(K::level, dim3(grid_for(threads, 256)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_witness_level<A>, dim3(grid_for(threads, 256)), dim3(256), 0, st, a);
     }
     if (walk && prog->walk_from < n_levels)
-        hipLaunchKernelGGL(K::small, dim3(grid_for(n, 1u << walk_log)), dim3(1024), 0, st, a, prog->d_levels + prog->walk_from,
+        hipLaunchKernelGGL(k_witness_small<A>, dim3(grid_for(n, 1u << walk_log)), dim3(1024), 0, st, a, prog->d_levels + prog->walk_from,
                            (uint32_t)(n_levels - prog->walk_from), walk_log);
     else if (prog->strip_from < n_levels)
-        hipLaunchKernelGGL(K::strip, dim3(grid_for(n, 64)), dim3(256), 0, st, a, prog->d_levels, prog->strip_from, (uint32_t)n_levels);
+        hipLaunchKernelGGL(k_witness_strip<A>, dim3(grid_for(n, 64)), dim3(256), 0, st, a, prog->d_levels, prog->strip_from, (uint32_t)n_levels);
     }
+}
+
+// The program over `rows` vectors of `per` proofs each (1: a batch of proofs; the copies of a group), in the instantiation it
+// needs: Plain without own records, Input with them (d_pi [rows * per][n_own]), Stmt for a hashed program.  `a` is filled but
+// for the own records and the statement; stmt, swap_used: witness_statement's and witness_hints'.
+template <class Plain, class Input, class Stmt>
+void witness_run(rsv_ctx* c, const rsv_witness_program* prog, Stmt& a, size_t rows, size_t per, const rsv_public_input* d_pi, size_t n_own,
+                 rsv_public_input* stmt, uint8_t* swap_used) {
+    if (!n_own) return witness_launch(c, prog, static_cast<const Plain&>(a), rows);
+    a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
+    if (!prog->stmt_flow) return witness_launch(c, prog, static_cast<const Input&>(a), rows);
+    // A hashed program: the statement of every row (its per * n_own records, copy-major) and the records of its hash, behind
+    // the members' (a malformed record is the member's R_PARSE: k_witness_statement checks what the digest kernel would flag)
+    const size_t tail = rows * per * prog->shape.flow_count;
+    uint4* flow_tail = const_cast<uint4*>(a.flow) + tail * 8;
+    statement_digest_launch(c, d_pi, rows, (uint32_t)(per * n_own), stmt, nullptr, flow_tail, swap_used + tail);
+    a.stmt = reinterpret_cast<const PubInput*>(stmt); a.flow_tail = flow_tail;
+    a.member_flow = (uint32_t)(per * prog->shape.flow_count); a.stmt_flow = prog->stmt_flow;
+    witness_launch(c, prog, a, rows);
 }
 
 // The host-buffer forms of the witness chain (rsv_witness_eval, _trace, _interaction, _commit) on a context of their own:
@@ -461,14 +448,27 @@ static int witness_check_own(const rsv_witness_program* prog, const rsv_public_i
     if ((uintptr_t)d_pi & 3) return RSV_E_SIZE;
     return RSV_OK;
 }
-// ... and of the batch itself: what the verifying pass would refuse, ahead of the statement kernel, so that a refused call
-// has enqueued nothing
-static int witness_check_batch(const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
-                               const rsv_cfg_set* cfg) {
-    const int rc = witness_check_cfg(prog, cfg);
+// The per-proof _dev forms: that, and with own records what the verifying pass would refuse of the batch itself, ahead of the
+// statement kernel, so that a refused call has enqueued nothing
+static int witness_check_inputs(const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t members,
+                                const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* d_pi,
+                                size_t n_own) {
+    int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, members);
+    if (rc != RSV_OK || !n_own) return rc;
+    rc = witness_check_cfg(prog, cfg);
     if (rc != RSV_OK) return rc;
     if (members && (!d_blob || !d_offsets)) return RSV_E_NULL;
     if (((uintptr_t)d_blob & 3) || ((uintptr_t)d_offsets & 7)) return RSV_E_SIZE;
+    return RSV_OK;
+}
+
+// What the four _dev forms of the evaluation refuse first.  Where they differ — d_variables' alignment ahead of or behind the
+// empty batch, the batch limit ahead of or behind the records' checks — the check stands at the entry point.
+static int witness_check_call(const rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, const uint32_t* d_flow,
+                              const uint8_t* d_flow_swap, const uint8_t* d_accept) {
+    if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
+    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
+    if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;  // (a caller's circuit has no instructions)
     return RSV_OK;
 }
 
@@ -515,32 +515,20 @@ static int witness_eval_impl(rsv_ctx* c, const rsv_witness_program* prog, const 
     rc = witness_hints(c, prog, d_blob, d_offsets, n, n, cfg, pi, n_pi + n_own, rec, d_variables, d_flow, d_flow_swap, d_accept, d_reason, a, &swap_used);
     if (rc != RSV_OK) return rc;
     a.accept = d_accept;
-    if (n_own) {
+    if (n_own)
         hipLaunchKernelGGL(k_witness_statement_verdict, dim3(grid_for(n, 256)), dim3(256), 0, c->stream, bad, (uint32_t)n, d_accept, d_reason);
-        a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
-        if (S) {  // a hashed program: the statement and the records of its hash, behind the members' (a malformed record
-                  // is the member's R_PARSE above: k_witness_statement checks what the digest kernel would flag)
-            const size_t tail = n * (size_t)prog->shape.flow_count;
-            uint4* flow_tail = const_cast<uint4*>(a.flow) + tail * 8;
-            statement_digest_launch(c, d_pi, n, (uint32_t)n_own, stmt, nullptr, flow_tail, swap_used + tail);
-            a.stmt = reinterpret_cast<const PubInput*>(stmt); a.flow_tail = flow_tail;
-            a.member_flow = prog->shape.flow_count; a.stmt_flow = (uint32_t)S;
-            witness_launch<WitnessStmtKernels>(c, prog, a, n);
-        } else witness_launch<WitnessInputKernels>(c, prog, static_cast<const WitnessInputArgs&>(a), n);
-    } else witness_launch<WitnessKernels>(c, prog, static_cast<const WitnessArgs&>(a), n);
+    witness_run<WitnessArgs, WitnessInputArgs>(c, prog, a, n, 1, d_pi, n_own, stmt, swap_used);
     return witness_finish(c, prog, a.vars, d_variables, n);
 }
 
 int rsv_witness_eval_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
                          uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_reason) {
-    if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
-    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;  // (a caller's circuit has no instructions)
+    const int rc = witness_check_call(c, prog, d_variables, d_flow, d_flow_swap, d_accept);
+    if (rc != RSV_OK) return rc;
     if (prog->input_slots) return RSV_E_SIZE;  // a program with own inputs: rsv_witness_eval_inputs_dev
     if (n == 0) return RSV_OK;
-    if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
-    if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (n > (1u << 20) || prog->device != c->device || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
     return witness_eval_impl(c, prog, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, 0, d_variables, d_flow, d_flow_swap, d_accept, d_reason);
 }
 
@@ -548,16 +536,13 @@ int rsv_witness_eval_inputs_dev(rsv_ctx* c, const rsv_witness_program* prog, con
                                 const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed, const rsv_public_input* d_pi,
                                 size_t n_own, uint32_t* d_variables, uint32_t* d_flow, uint8_t* d_flow_swap, uint8_t* d_accept,
                                 uint8_t* d_reason) {
-    if (!c || !prog || !d_variables || !d_accept) return RSV_E_NULL;
-    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if (((uintptr_t)d_flow & 15) || prog->n_instr == 0) return RSV_E_SIZE;
+    int rc = witness_check_call(c, prog, d_variables, d_flow, d_flow_swap, d_accept);
+    if (rc != RSV_OK) return rc;
     if (prog->stmt_flow && prog->shape.copies != 1) return RSV_E_SIZE;  // a hashed program of several copies hashes a GROUP's statements
-    int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, n);
-    if (rc == RSV_OK && n_own) rc = witness_check_batch(prog, d_blob, d_offsets, n, cfg);
+    rc = witness_check_inputs(prog, d_blob, d_offsets, n, cfg, pi_fixed, n_fixed, d_pi, n_own);
     if (rc != RSV_OK) return rc;
     if (n == 0) return RSV_OK;
-    if (n > (1u << 20) || prog->device != c->device) return RSV_E_SIZE;
-    if (((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (n > (1u << 20) || prog->device != c->device || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
     return witness_eval_impl(c, prog, d_blob, d_offsets, n, cfg, pi_fixed, n_fixed, n_own ? d_pi : nullptr, n_own, d_variables, d_flow,
                              d_flow_swap, d_accept, d_reason);
 }
@@ -598,27 +583,17 @@ static int witness_groups_impl(rsv_ctx* c, const rsv_witness_program* prog, cons
     hipLaunchKernelGGL(k_witness_group_accept, dim3(grid_for(n_groups, 256)), dim3(256), 0, c->stream, d_member_accept, (uint32_t)n_groups,
                        (uint32_t)copies, d_accept);
     a.accept = d_accept; a.copy_of = prog->d_copy_of; a.copies = (uint32_t)copies;
-    if (n_own) {
-        a.own = reinterpret_cast<const PubInput*>(d_pi); a.n_own = (uint32_t)n_own;
-        if (S) {  // a hashed program: as in witness_eval_impl, a group's copies * n_own records hashed in copy-major order
-            const size_t tail = members * (size_t)prog->shape.flow_count;
-            uint4* flow_tail = const_cast<uint4*>(a.flow) + tail * 8;
-            statement_digest_launch(c, d_pi, n_groups, (uint32_t)(copies * n_own), stmt, nullptr, flow_tail, swap_used + tail);
-            a.stmt = reinterpret_cast<const PubInput*>(stmt); a.flow_tail = flow_tail;
-            a.member_flow = (uint32_t)(copies * prog->shape.flow_count); a.stmt_flow = (uint32_t)S;
-            witness_launch<WitnessGroupStmtKernels>(c, prog, a, n_groups);
-        } else witness_launch<WitnessGroupInputKernels>(c, prog, static_cast<const WitnessGroupInputArgs&>(a), n_groups);
-    } else witness_launch<WitnessGroupKernels>(c, prog, static_cast<const WitnessGroupArgs&>(a), n_groups);
+    witness_run<WitnessGroupArgs, WitnessGroupInputArgs>(c, prog, a, n_groups, copies, d_pi, n_own, stmt, swap_used);
     return witness_finish(c, prog, a.vars, d_variables, n_groups);
 }
 
 int rsv_witness_eval_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n_groups,
                                 const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint32_t* d_variables, uint32_t* d_flow,
                                 uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
-    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
-    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if (prog->copy_of.empty()) return RSV_E_SIZE;  // only a built program knows which copy a hint belongs to
-    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (!d_member_accept) return RSV_E_NULL;
+    const int rc = witness_check_call(c, prog, d_variables, d_flow, d_flow_swap, d_accept);
+    if (rc != RSV_OK) return rc;
+    if (prog->copy_of.empty() || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;  // only a built program knows which copy a hint belongs to
     if (prog->input_slots) return RSV_E_SIZE;  // a program with own inputs: rsv_witness_eval_groups_inputs_dev
     if (n_groups == 0) return RSV_OK;
     if (n_groups > (1u << 20) / prog->shape.copies || prog->device != c->device) return RSV_E_SIZE;
@@ -630,13 +605,12 @@ int rsv_witness_eval_groups_inputs_dev(rsv_ctx* c, const rsv_witness_program* pr
                                        size_t n_groups, const rsv_cfg_set* cfg, const rsv_public_input* pi_fixed, size_t n_fixed,
                                        const rsv_public_input* d_pi, size_t n_own, uint32_t* d_variables, uint32_t* d_flow,
                                        uint8_t* d_flow_swap, uint8_t* d_accept, uint8_t* d_member_accept, uint8_t* d_member_reason) {
-    if (!c || !prog || !d_variables || !d_accept || !d_member_accept) return RSV_E_NULL;
-    if ((d_flow == nullptr) != (d_flow_swap == nullptr)) return RSV_E_NULL;
-    if (prog->copy_of.empty()) return RSV_E_SIZE;
-    if (((uintptr_t)d_flow & 15) || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
-    if (n_groups > (1u << 20) / prog->shape.copies) return RSV_E_SIZE;
-    int rc = witness_check_own(prog, pi_fixed, n_fixed, d_pi, n_own, n_groups * prog->shape.copies);
-    if (rc == RSV_OK && n_own) rc = witness_check_batch(prog, d_blob, d_offsets, n_groups * prog->shape.copies, cfg);
+    if (!d_member_accept) return RSV_E_NULL;
+    int rc = witness_check_call(c, prog, d_variables, d_flow, d_flow_swap, d_accept);
+    if (rc != RSV_OK) return rc;
+    if (prog->copy_of.empty() || ((uintptr_t)d_variables & 15)) return RSV_E_SIZE;
+    if (n_groups > (1u << 20) / prog->shape.copies) return RSV_E_SIZE;  // (here ahead of the records' checks: the members are a product)
+    rc = witness_check_inputs(prog, d_blob, d_offsets, n_groups * prog->shape.copies, cfg, pi_fixed, n_fixed, d_pi, n_own);
     if (rc != RSV_OK) return rc;
     if (n_groups == 0) return RSV_OK;
     if (prog->device != c->device) return RSV_E_SIZE;
@@ -653,6 +627,24 @@ int rsv_witness_program_inputs(const rsv_witness_program* prog, uint32_t* n_fixe
     return RSV_OK;
 }
 
+// What rsv_witness_eval (own NULL, n_own 0) and rsv_witness_eval_inputs do after their own checks: a stage of its own, and
+// the variables and flow_records flow records (the latter form's include a hashed program's statement hash) copied back
+static int witness_eval_host(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
+                             const rsv_public_input* pi, size_t n_pi, const rsv_public_input* own, size_t n_own, size_t flow_records,
+                             uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept, uint8_t* reason, int device) {
+    WitnessStage st;
+    int rc = st.open(offsets, n, device, false);
+    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr, own, n_own);
+    if (rc == RSV_OK) rc = st.finish(accept, reason);
+    if (rc != RSV_OK) return rc;
+    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
+    if (flow) {
+        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
+    }
+    return RSV_OK;
+}
+
 int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                      const rsv_public_input* pi, size_t n_pi, uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept,
                      uint8_t* reason, int device) {
@@ -661,18 +653,8 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
     if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit
     if (n == 0) return RSV_OK;
     if (n > (1u << 20)) return RSV_E_SIZE;
-    WitnessStage st;
-    int rc = st.open(offsets, n, device, false);
-    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr);
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    const size_t flow_records = n * (size_t)prog->shape.flow_count;
-    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
-    if (flow) {
-        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
-    }
-    return RSV_OK;
+    return witness_eval_host(prog, blob, offsets, n, cfg, pi, n_pi, nullptr, 0, n * (size_t)prog->shape.flow_count, variables, flow, flow_swap,
+                             accept, reason, device);
 }
 
 // the same with every proof's own records [n][n_own] behind the n_fixed shared ones, all in host memory
@@ -683,21 +665,11 @@ int rsv_witness_eval_inputs(const rsv_witness_program* prog, const uint8_t* blob
     if ((flow == nullptr) != (flow_swap == nullptr)) return RSV_E_NULL;
     if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit
     if (n > (1u << 20)) return RSV_E_SIZE;
-    int rc = witness_check_own(prog, pi_fixed, n_fixed, pi_own, n_own, n);
+    const int rc = witness_check_own(prog, pi_fixed, n_fixed, pi_own, n_own, n);
     if (rc != RSV_OK) return rc;
     if (n == 0) return RSV_OK;
-    WitnessStage st;
-    rc = st.open(offsets, n, device, false);
-    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi_fixed, n_fixed, flow != nullptr, pi_own, n_own);
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    const size_t flow_records = n * ((size_t)prog->shape.flow_count + prog->stmt_flow);
-    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
-    if (flow) {
-        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
-    }
-    return RSV_OK;
+    return witness_eval_host(prog, blob, offsets, n, cfg, pi_fixed, n_fixed, pi_own, n_own, n * ((size_t)prog->shape.flow_count + prog->stmt_flow),
+                             variables, flow, flow_swap, accept, reason, device);
 }
 
 int rsv_witness_program_statement(const rsv_witness_program* prog, uint32_t* hashed, uint32_t* n_words, uint32_t* stmt_flow_count) {

@@ -1,6 +1,7 @@
 """What the chain's test modules share (no test lives here): the fixture pairs and what is read off them, the oracle's
 circuit and columns of a pair, the device helpers with the tests' prefill, and chain(), which runs rsv.Chain up to a stage.
 Nothing here needs a device to import; torch is imported where a helper touches one."""
+import contextlib
 import ctypes
 import json
 import os
@@ -26,6 +27,28 @@ CASES = [  # random trees: (groups as (log, cols, shared), b, n, mask)
     ([(6, 5, True), (5, 7, False)], 2, 4, [1, 0, 1, 1]),
     ([(3, 10, False), (2, 8, True)], 6, 5, [1, 1, 0, 1, 1]),
 ]
+
+# The witness evaluation's launch forms (csrc/witness_api.inc: witness_launch), as (witness_small_max, witness_small_log,
+# witness_walk_log) with None = the batch size + 1: the level-per-launch form (k_witness_level<A> below 64 proofs or groups,
+# k_witness_level_wide<A> from 64 on) with its tail as a strip (k_witness_strip<A>) / in one launch of 2, 8, 64 per workgroup /
+# by the default rule; the whole program in one launch (k_witness_small<A>) of 1, 4, 64 per workgroup; the default rule.
+# LAUNCH_FORMS_FEW: the same without the forms of 8 and 64 per workgroup.
+LAUNCH_FORMS = ((1, 0, 1), (1, 0, 2), (1, 0, 4), (1, 0, 7), (1, 0, 0), (None, 1, 0), (None, 3, 0), (None, 7, 0), (0, 0, 0))
+LAUNCH_FORMS_FEW = tuple(f for f in LAUNCH_FORMS if f[1] < 7 and f[2] < 4)
+
+
+@contextlib.contextmanager
+def launch_form(ctx, form, n):
+    """Forces a launch form on the context for a batch of n proofs (or groups); the default rule is back on exit."""
+    small_max, small_log, walk_log = form
+    try:
+        ctx.set_option("witness_small_max", n + 1 if small_max is None else small_max)
+        ctx.set_option("witness_small_log", small_log)
+        ctx.set_option("witness_walk_log", walk_log)
+        yield
+    finally:
+        for name in ("witness_small_max", "witness_small_log", "witness_walk_log"):
+            ctx.set_option(name, 0)
 
 
 # ---------------------------------------------------------------- the fixture pairs

@@ -10,15 +10,11 @@ import pytest
 from tests import aggregate_ref as R
 from tests import oracle_binding as ob
 from tests.aggregate_ref import A, B, COPIES
-from tests.chain_harness import DEV, FILL, inputs_of, pin_of, program_of
+from tests.chain_harness import DEV, FILL, LAUNCH_FORMS, inputs_of, launch_form, pin_of, program_of
 from tests.conftest import Cfg, fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
 FOREIGN = "level12-1.bin"  # a proof of another shape
-# (small_max, small_log, walk_log) as tests/test_witness_gpu.py::test_witness_launch_forms_agree forces the launch forms, with
-# n + 1 written as None: level form with its tail as a strip / in one launch of 2, 8, 64 per workgroup / by the default rule;
-# the whole program in one launch of 1, 4, 64 per workgroup; the default rule
-FORMS = ((1, 0, 1), (1, 0, 2), (1, 0, 4), (1, 0, 7), (1, 0, 0), (None, 1, 0), (None, 3, 0), (None, 7, 0), (0, 0, 0))
 
 
 @pytest.fixture(scope="module")
@@ -173,17 +169,15 @@ def test_launch_forms_agree(rsv, wp, n_groups):
     ctx = rsv.Context(0)
     for by_variable in (False, True):
         ctx.set_option("witness_layout", "by_variable" if by_variable else "by_proof")
-        for small_max, small_log, walk_log in FORMS:
-            ctx.set_option("witness_small_max", n_groups + 1 if small_max is None else small_max)
-            ctx.set_option("witness_small_log", small_log)
-            ctx.set_option("witness_walk_log", walk_log)
-            d_vars, d_acc, d_macc, d_mreason, d_flow, d_swap = _eval(rsv, ctx, wp, groups, by_variable=by_variable, batch=batch)
+        for launch in LAUNCH_FORMS:
+            with launch_form(ctx, launch, n_groups):
+                d_vars, d_acc, d_macc, d_mreason, d_flow, d_swap = _eval(rsv, ctx, wp, groups, by_variable=by_variable, batch=batch)
             for t in cols.values():
                 t.fill_(-1)
             ctx.witness_trace_groups(wp, d_vars, d_acc, n_groups, d_plonk=cols["plonk"], d_poseidon=cols["poseidon"], d_ops=cols["ops"],
                                      d_flow=d_flow, d_flow_swap=d_swap)
             ctx.synchronize()
-            form = (by_variable, small_max, small_log, walk_log)
+            form = (by_variable, *launch)
             assert torch.equal(d_acc != 0, good), form
             assert torch.equal(d_macc[:, 0] != 0, good) and bool(d_macc[:, 1].all()), form
             assert torch.equal(d_mreason[:, 0] == 0, good) and not bool(d_mreason[:, 1].any()), form

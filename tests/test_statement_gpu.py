@@ -147,8 +147,8 @@ def test_refusals_leave_the_outputs_alone(rsv, ctx):
 # The inner proofs are tests/test_witness_inputs_gpu.py's: circuit S1 under CONFIG, witness i with the statement 11 + i,
 # proved by the chain itself (a witness that draws a duplicate query is made again from another seed).
 from tests import witness_inputs_ref as W                                                    # noqa: E402
-from tests.chain_harness import FILL                                                         # noqa: E402
-from tests.test_witness_inputs_gpu import FORMS as LAUNCH_FORMS, N, _dev as _dev_any, _finish, _full, _set_form, _upload, inner  # noqa: E402,F401
+from tests.chain_harness import FILL, LAUNCH_FORMS_FEW as LAUNCH_FORMS, launch_form          # noqa: E402
+from tests.test_witness_inputs_gpu import N, _dev as _dev_any, _finish, _full, _upload, inner  # noqa: E402,F401
 
 R_PARSE, R_LOGUP, R_DUP_QUERY = 1, 3, 5
 E_NULL, E_SIZE, E_RANGE = -1, -2, -5
@@ -180,19 +180,18 @@ def _eval_hashed(ctx, wp, pair, n_groups, fixed, d_own, layout="by_proof", form=
     d_macc, d_mreason = _full((n_groups * m,), True), _full((n_groups * m,), True)
     ctx.set_option("witness_layout", layout)
     ctx.set_option("statement_row_max", FORMS[pace] if pace else 0)
-    _set_form(ctx, form, n_groups)
     try:
-        if m == 1:
-            ctx.witness(wp, *pair, n_groups, d_vars, d_acc, d_mreason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
-            ctx.synchronize()
-            d_macc = d_acc
-        else:
-            ctx.witness_groups(wp, *pair, n_groups, d_vars, d_acc, d_macc, d_mreason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
-            ctx.synchronize()
+        with launch_form(ctx, form, n_groups):
+            if m == 1:
+                ctx.witness(wp, *pair, n_groups, d_vars, d_acc, d_mreason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
+                ctx.synchronize()
+                d_macc = d_acc
+            else:
+                ctx.witness_groups(wp, *pair, n_groups, d_vars, d_acc, d_macc, d_mreason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
+                ctx.synchronize()
     finally:
         ctx.set_option("witness_layout", "by_proof")
         ctx.set_option("statement_row_max", 0)
-        _set_form(ctx, (0, 0, 0), n_groups)
     v, flow = u32(d_vars), u32(d_flow)
     cut = n_groups * m * F
     return ((v.transpose(1, 0, 2) if by_variable else v), flow[:cut].reshape(n_groups * m, F, 32), flow[cut:].reshape(n_groups, S_, 32),
@@ -370,7 +369,7 @@ def test_both_forms_of_the_kernel_write_the_hash_records(rsv, ctx, inner, hashed
 
 @pytest.mark.parametrize("n", [3, N])
 def test_every_launch_form_of_the_hashed_program(rsv, ctx, inner, hashed, n):
-    """By the default rule batches this small run the whole program in one launch (k_witness_small_s / _gs): the other
+    """By the default rule batches this small run the whole program in one launch (k_witness_small over WitnessStmtArgs / WitnessGroupStmtArgs): the other
     instantiations over WitnessStmtArgs and WitnessGroupStmtArgs — the level kernels below and from 64 rows on, the strip, the
     one-launch tail — are forced through the options at 3 and 70, for proofs and for groups of two (group g = proofs 2g and
     2g + 1 of the 70, taken round again).  One record has a non-zero word 2: its proof, or its group, is rejected

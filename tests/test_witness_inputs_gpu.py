@@ -12,7 +12,7 @@ import pytest
 from tests import circuit_eval_ref as E
 from tests import oracle_binding as ob
 from tests import witness_inputs_ref as W
-from tests.chain_harness import DEV, FILL, u32
+from tests.chain_harness import DEV, FILL, LAUNCH_FORMS_FEW as FORMS, launch_form, u32
 from tests.conftest import fixture_cfg, read_proof
 
 pytestmark = pytest.mark.gpu
@@ -117,19 +117,6 @@ def _upload(rsv, proofs):
     return torch.from_numpy(blob.copy()).to(DEV), torch.from_numpy(offsets.astype(np.int64)).to(DEV)
 
 
-# (witness_small_max, witness_small_log, witness_walk_log), None = the batch size + 1: the level-per-launch form with its tail
-# as a strip / in one launch of 2 proofs per workgroup / by the default rule; the whole program in one launch of 1 and of 4
-# proofs per workgroup; the default rule (tests/test_witness_gpu.py, tests/test_aggregate_gpu.py)
-FORMS = ((1, 0, 1), (1, 0, 2), (1, 0, 0), (None, 1, 0), (None, 3, 0), (0, 0, 0))
-
-
-def _set_form(ctx, form, n):
-    small_max, small_log, walk_log = form
-    ctx.set_option("witness_small_max", n + 1 if small_max is None else small_max)
-    ctx.set_option("witness_small_log", small_log)
-    ctx.set_option("witness_walk_log", walk_log)
-
-
 def _eval(rsv, ctx, wp, pair, n, fixed, d_own, layout="by_proof", form=(0, 0, 0)):
     """Context.witness with d_inputs under a layout and a launch form, outputs prefilled -> (variables [n, n_vars, 4], flow,
     swap, accept, reason)."""
@@ -138,13 +125,12 @@ def _eval(rsv, ctx, wp, pair, n, fixed, d_own, layout="by_proof", form=(0, 0, 0)
     d_vars = _full((wp.n_vars, n, 4) if by_variable else (n, wp.n_vars, 4))
     d_flow, d_swap, d_acc, d_reason = _full((n, F, 32)), _full((n, F), True), _full((n,), True), _full((n,), True)
     ctx.set_option("witness_layout", layout)
-    _set_form(ctx, form, n)
     try:
-        ctx.witness(wp, *pair, n, d_vars, d_acc, d_reason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
-        ctx.synchronize()
+        with launch_form(ctx, form, n):
+            ctx.witness(wp, *pair, n, d_vars, d_acc, d_reason, inputs=fixed, d_flow=d_flow, d_flow_swap=d_swap, d_inputs=d_own)
+            ctx.synchronize()
     finally:
         ctx.set_option("witness_layout", "by_proof")
-        _set_form(ctx, (0, 0, 0), n)
     v = u32(d_vars)
     return (v.transpose(1, 0, 2) if by_variable else v), u32(d_flow), d_swap.cpu().numpy(), d_acc.cpu().numpy(), d_reason.cpu().numpy()
 
@@ -160,7 +146,7 @@ def test_the_program_knows_its_inputs(rsv, inner):
     at = np.flatnonzero(prog.instr[:, 0] == W.W_INPUT)
     assert prog.instr[at].tolist() == [[W.W_INPUT, 4, 0, 0, 0, 0, 0, 0]] and at[0] < prog.level_offsets[1]
     # the program has the narrow tail the strip form is launched for (at least 8 last levels of at most 32 instructions,
-    # csrc/witness_api.inc) behind wider levels, so the forced forms below do run k_witness_strip_i and the level kernels
+    # csrc/witness_api.inc) behind wider levels, so the forced forms below do run k_witness_strip<WitnessInputArgs> and the level kernels
     widths = np.diff(prog.level_offsets.astype(np.int64))
     tail = len(widths) - (np.flatnonzero(widths > 32)[-1] + 1)
     assert 8 <= tail < len(widths) and widths[0] > 1536
@@ -194,10 +180,11 @@ def test_rows_are_the_oracles_variables(rsv, ctx, inner, n, layout):
 @pytest.mark.parametrize("layout", ["by_proof", "by_variable"])
 @pytest.mark.parametrize("n", [3, N])
 def test_every_launch_form_reads_the_inputs(rsv, ctx, inner, n, layout):
-    """By the default rule batches this small run the whole program in one launch (k_witness_small_i), so the other
+    """By the default rule batches this small run the whole program in one launch (k_witness_small<WitnessInputArgs>), so the other
     instantiations over WitnessInputArgs are forced through the options, as the constant form's tests force theirs: the
-    level-per-launch form — below 64 proofs k_witness_level_i, from 64 on k_witness_level_wide_i with a partly filled
-    second block, level 0 with its W_INPUT among them — with the tail as a strip (k_witness_strip_i) and in one launch.
+    level-per-launch form — below 64 proofs k_witness_level<WitnessInputArgs>, from 64 on k_witness_level_wide<WitnessInputArgs>
+    with a partly filled second block, level 0 with its W_INPUT among them — with the tail as a strip
+    (k_witness_strip<WitnessInputArgs>) and in one launch.
     One proof is given a neighbour's statement, so that a rejected row sits among the accepted ones.  Under every form: the
     verdicts, variable 4, every byte of the default form's outputs for the accepted proofs, and the oracle's rows."""
     pair = _upload(rsv, inner.proofs[:n])
@@ -440,8 +427,8 @@ def _eval_groups(rsv, ctx, wp, pair, n_groups, fixed, d_own):
 
 @pytest.mark.parametrize("n_groups", [3, N])
 def test_every_launch_form_of_the_groups_reads_the_inputs(rsv, ctx, inner, n_groups):
-    """The grouped instantiations over WitnessGroupInputArgs under the same forms: 3 groups (k_witness_level_gi) and 70
-    (k_witness_level_wide_gi, a partly filled second block), group g = proofs 2g and 2g + 1 of the 70, taken round again.
+    """The grouped instantiations over WitnessGroupInputArgs under the same forms: 3 groups (k_witness_level<A>) and 70
+    (k_witness_level_wide<A>, a partly filled second block), group g = proofs 2g and 2g + 1 of the 70, taken round again.
     One member has a neighbour's statement.  Under every form: the verdicts, variables 4 and 5 of every accepted group, the
     default form's rows, and for two groups the oracle's two-member circuit."""
     members = [(2 * g + c) % N for g in range(n_groups) for c in range(2)]
@@ -462,11 +449,8 @@ def test_every_launch_form_of_the_groups_reads_the_inputs(rsv, ctx, inner, n_gro
             c = W.group_circuit([inner.proofs[m] for m in pick], [inner.inputs[m] for m in pick], 3)
             assert np.array_equal(want[0][g], np.array(c.variables, dtype=np.uint32)), g
         for form in FORMS[:-1]:
-            _set_form(ctx, form, n_groups)
-            try:
+            with launch_form(ctx, form, n_groups):
                 got = _eval_groups(rsv, ctx, wp2, pair, n_groups, inner.fixed, d_own)
-            finally:
-                _set_form(ctx, (0, 0, 0), n_groups)
             assert all(np.array_equal(a, b) for a, b in zip(want[1:], got[1:])), form
             assert np.array_equal(want[0][good], got[0][good]), form
     finally:
