@@ -211,6 +211,20 @@ typedef enum rsv_option {
     RSV_OPT_STATEMENT_ROW_MAX = 31, /* rsv_statement_digest_dev: 0 default (24 576, measured), else 1 + the largest number of groups hashed in the
                                      row form (16 threads per group share every permutation: a group's permutations depend on
                                      one another); more groups take one lane each; 1 = never the row form, 0 .. 2^26 + 1 */
+    RSV_OPT_WS_FILL = 32,         /* DIAGNOSTIC, the one knob that is no choice between kernel forms.  0 off: exactly the code path without
+                                     it.  v = 1 .. 256: every byte of the library's own device scratch holds v - 1 before the first
+                                     kernel of a call can touch it — each context workspace (all of its capacity, on every call that
+                                     carves it, grown or not), the public-input table in front of its upload, the proof-pack map
+                                     where it is rebuilt, and (process default only) the per-call device temporaries of the
+                                     host-pointer probes and convenience forms (rsv_poseidon2_permute, rsv_verify_batch,
+                                     rsv_verify_hints, ...) as each is allocated.  Left alone: tables that are uploaded whole
+                                     (twiddles, programs, wires), the caller's own scratch, and the device slots that
+                                     rsv_verify_batch_host and the multi-GPU contexts keep between calls (blob, offsets, verdicts,
+                                     bitmap: they hold a call's own uploads and outputs, no intermediate state).  A
+                                     result that changes under any fill byte read a word
+                                     the call did not write.  It SYNCHRONISES: each fill waits on the host for all three streams of
+                                     the context and for the fill itself, so no entry point's "no host synchronisation" holds
+                                     while it is set.  Anything else: RSV_E_RANGE */
     /* 15, 27, 28, 29: retired; rsv_ctx_set_option answers RSV_E_SIZE */
     RSV_OPT_CAP_TOP = 19          /* 0 auto (batches of >= 1 024 proofs), 1 the last two or three levels of every Merkle tree in a
                                      kernel of their own (one lane per tree), 2 inside the tree kernels (dense top-of-tree cap) */
@@ -489,8 +503,9 @@ int rsv_fri_paths(const uint8_t* blob, const uint64_t* offsets, size_t n, const 
  *                                           their circle-to-line folds (folding/src/lib.rs:57-90); the value entering
  *                                           inner layer i, i < n_inner (:135-144); the value entering the last-layer
  *                                           check and the last-layer polynomial evaluated at the query's point (:194-204)
- *                                           (the library zeroes this buffer first: absent groups and the rows of rejected
- *                                           proofs are zero)
+ *                                           (the library zeroes this buffer first: absent groups, and the rows of a proof
+ *                                           the parser rejected, are zero; a proof rejected behind the parser keeps what
+ *                                           its failing verification computed, as its flow records do)
  * Path outputs need a uniform batch of the declared shape (n_queries >= 4, max_log, n_inner), else RSV_E_SIZE.
  *
  * SURVEY 8f.1, second half — the value side of the recursion circuit's Poseidon accelerator:

@@ -398,7 +398,7 @@ OPTIONS = {"transcript_form": 1, "transcript_split": 2, "oods_form": 3, "qconst_
            "overlap_trees": 7, "ws_budget_mb": 8, "perm_wg_per_cu": 9, "host_chunk_mb": 10, "host_threads": 11, "debug_log": 12,
            "critical_chain": 13, "device_order": 14,
            "witness_layout": 16, "witness_small_max": 17, "witness_small_log": 18, "cap_top": 19, "witness_walk_log": 20, "flow_cap": 21, "pair_order": 22, "tree_pace": 23, "stage_times": 24, "query_form": 25, "cap_mid": 26,
-           "circuit_eval_form": 30, "statement_row_max": 31}
+           "circuit_eval_form": 30, "statement_row_max": 31, "ws_fill": 32}
 #: the hint kinds of rsv_circuit_program_create_eval (RSV_HINT_*)
 HINT_KINDS = {"input": 0, "copy": 1, "inv": 2, "inv_or_zero": 3, "qinv": 4, "cinv": 5, "coord": 6, "bit": 7}
 OPTION_VALUES = {"auto": 0, "per_level": 1, "walk": 2, "row": 1, "lane": 2, "paced": 1, "unpaced": 2, "row16": 3, "whole": 1, "split": 2, "parallel": 1, "serial": 2, "on": 1, "off": 2, "device": 1, "host": 2,

@@ -72,9 +72,11 @@ struct Options {
     int witness_walk_log = 0;         // level form: 0 auto, 1 off, else 1 + log2(proofs per workgroup) of the one-launch tail
     int circuit_eval_form = 0;        // rsv_circuit_eval_dev: 0 auto (by batch size), 1 a launch per level, 2 a workgroup per witness walks the levels
     long long statement_row_max = 0;  // rsv_statement_digest_dev: 0 default, else 1 + the largest number of groups hashed in the row form
+    int ws_fill = 0;                  // diagnostic: 0 off, else 1 + the byte every workspace is filled with before a call carves it (ensure_buf)
 };
 static Options g_default_options;
 static std::mutex g_options_mu;
+static std::atomic<int> g_default_ws_fill{0};  // g_default_options.ws_fill, for DevBuf (no context there, and no lock on the off path)
 static std::atomic<int> g_debug_log{0};
 
 #define HIP_TRY(expr)                                                                              \
@@ -141,7 +143,17 @@ namespace {
 struct DevBuf {
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 4); }
+    // RSV_OPT_WS_FILL (process default): the fresh allocation holds the fill byte before anything is copied or launched into it
+    hipError_t alloc(size_t bytes) {
+        const size_t want = bytes ? bytes : 4;
+        hipError_t e = hipMalloc(&p, want);
+        const int fill = g_default_ws_fill.load(std::memory_order_relaxed);
+        if (e == hipSuccess && fill) {
+            e = hipMemset(p, fill - 1, want);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+        }
+        return e;
+    }
     template <class T> T* as() { return static_cast<T*>(p); }
 };
 
@@ -311,6 +323,11 @@ int rsv_ctx_set_option(rsv_ctx* c, int option, long long value) {
         case RSV_OPT_WITNESS_SMALL_LOG:
             if (value < 0 || value > 7) return RSV_E_RANGE;
             o.witness_small_log = (int)value; return RSV_OK;
+        case RSV_OPT_WS_FILL:
+            if (value < 0 || value > 256) return RSV_E_RANGE;
+            o.ws_fill = (int)value;
+            if (!c) g_default_ws_fill.store((int)value, std::memory_order_relaxed);
+            return RSV_OK;
         case RSV_OPT_WS_BUDGET_MB:
             if (value < 1 || value > (1ll << 20)) return RSV_E_RANGE;
             o.ws_budget_mb = value; return RSV_OK;

@@ -62,16 +62,39 @@ void destroy_verify_state(VerifyState* v) {
     delete v;
 }
 
-int ensure_buf(rsv_ctx* c, void** buf, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return RSV_OK;
+// every stream of the context is idle: what ensure_buf waits for before it frees, and before it fills (RSV_OPT_WS_FILL).
+// The aux stream is joined into the main one by every call that uses it (ev_fork), except on an error exit taken between
+// the parser's launch and that join: a buffer freed behind such an exit could still be the parser's target.
+int ws_idle(rsv_ctx* c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipStreamSynchronize(c->side));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    size_t want = bytes + (bytes >> 3) + 4096;
-    HIP_TRY(hipMalloc(buf, want));
-    *cap = want;
+    HIP_TRY(hipStreamSynchronize(c->aux));
+    return RSV_OK;
+}
+
+// RSV_OPT_WS_FILL (diagnostic): every byte of `bytes` at `p` holds the fill byte before the call goes on.  Host-synchronous
+// on purpose: the streams are idle in front of the fill and the fill is over behind it, whatever stream touches `p` next.
+int ws_fill(rsv_ctx* c, void* p, size_t bytes) {
+    if (!p || !bytes) return RSV_OK;
+    const int rc = ws_idle(c);
+    if (rc != RSV_OK) return rc;
+    HIP_TRY(hipMemsetAsync(p, c->opt.ws_fill - 1, bytes, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return RSV_OK;
+}
+
+int ensure_buf(rsv_ctx* c, void** buf, size_t* cap, size_t bytes) {
+    if (*cap < bytes) {
+        const int rc = ws_idle(c);
+        if (rc != RSV_OK) return rc;
+        if (*buf) (void)hipFree(*buf);
+        *buf = nullptr;
+        *cap = 0;
+        size_t want = bytes + (bytes >> 3) + 4096;
+        HIP_TRY(hipMalloc(buf, want));
+        *cap = want;
+    }
+    if (c->opt.ws_fill) return ws_fill(c, *buf, *cap);  // the whole capacity, slack included, grown or not
     return RSV_OK;
 }
 
@@ -205,8 +228,12 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         HIP_TRY(hipMalloc((void**)&c->d_pi, sizeof(rsv_public_input) * (n_pi + 16)));
         c->d_pi_cap = n_pi + 16;
     }
+    if (opt.ws_fill) {  // in front of the copy (the shared table) or of nothing (per-proof inputs never read it)
+        const int rcf = ws_fill(c, c->d_pi, sizeof(rsv_public_input) * c->d_pi_cap);
+        if (rcf != RSV_OK) return rcf;
+    }
     if (n_pi && !own) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
-    // rsv_hints_out::d_query_values: "absent groups and rejected proofs are zero" holds for the caller's buffer as it is
+    // rsv_hints_out::d_query_values: "absent groups, and the rows of a proof the parser rejected, are zero" holds for the caller's buffer as it is
     if (po && po->d_count) HIP_TRY(hipMemsetAsync(po->d_count, 0, 8, st));
     if (po && po->d_qv)
         HIP_TRY(hipMemsetAsync(po->d_qv, 0, (size_t)N * po->n_queries * 4 * (8 + (size_t)po->n_inner) * sizeof(uint32_t), st));

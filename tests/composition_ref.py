@@ -89,3 +89,12 @@ def eval_m31(coeffs, log, x, y):
         v = v.reshape(v.shape[0], -1, 2)
         v = (v[:, :, 0] + v[:, :, 1] * f) % P
     return v[:, 0]
+
+
+# The shapes of tests/test_composition_gpu.py::test_composition_bit_for_bit
+SHAPES = [  # (lp, lq, n, mask, shared preprocessed columns)
+    (4, 3, 2, None, False),       # clb = 6 from the Plonk term
+    (3, 5, 3, [1, 0, 1], False),  # clb = 8 from the Poseidon term, Plonk over-extended by 2^5; one proof masked
+    (6, 6, 2, None, True),        # preprocessed columns shared by every proof (stride 0)
+    (11, 10, 2, None, False),     # clb = 13: just past the 4 096-point switch between the LDS and the global FFT stages
+]

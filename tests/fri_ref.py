@@ -9,6 +9,7 @@ import numpy as np
 from tests import commit_ref as C
 from tests import composition_ref as K
 from tests import interaction_ref as R
+from tests.chain_harness import masked_past_64
 
 P = C.P
 
@@ -165,3 +166,60 @@ def commit(cols, log_last, b, ch, ob):
     mix_last(ch, last)
     return {"roots": np.array(roots, dtype=np.uint32), "alphas": np.array(alphas, dtype=np.uint32), "layers": layers, "last_poly": last,
             "low_degree": int(not co[:, 1 << log_last:].any())}
+
+
+# The cases of tests/test_fri_gpu.py::test_commit_bit_for_bit
+CCASES = {  # name: (sizes, log_last, b, n, mask, low degree input)
+    "three_columns": ([7, 6, 5], 2, 1, 2, None, False),
+    "joins_at_the_last_fold": ([6, 4], 1, 2, 3, [1, 0, 1], False),
+    "log_last_0": ([5, 3], 0, 1, 1, None, False),
+    "no_inner_layer": ([4], 2, 1, 1, None, False),
+    "levels_past_one_workgroup": ([11, 9], 1, 1, 1, None, False),
+    "low_degree": ([8, 7, 5], 2, 2, 2, None, True),
+    "past_one_workgroup_of_proofs": ([5, 3], 0, 1, 70, masked_past_64(), False),  # k_fr_draw, k_fr_mix_last
+}
+
+
+# ---- what tests/test_fri_gpu.py and tests/test_workspace_fill_gpu.py share of rsv_fri_quotients_dev: the restatement of one
+# proof's d_quot, the cases, and their random inputs
+def ref_quotients(groups, gpoints, b, points, samples, after):
+    """One proof.  groups [(log, int64[n_cols, 2^log])], gpoints per group per point (lo, hi) or None, points uint32[k, 8],
+    samples uint32[k, total, 4] -> uint32 words of d_quot: the columns in descending size, each [4][2^(log + b)]."""
+    out, col0 = [], np.cumsum([0] + [g[1].shape[0] for g in groups])
+    for size in sorted({log for log, _ in groups}, reverse=True):
+        mine = [i for i, (log, _) in enumerate(groups) if log == size]
+        first = np.cumsum([0] + [groups[i][1].shape[0] for i in mine])
+        batches = []
+        for k in range(points.shape[0]):
+            terms = []
+            for j, i in enumerate(mine):
+                r = gpoints[i][k] if k < len(gpoints[i]) else None
+                if r is not None:
+                    terms += [(first[j] + c, samples[k, col0[i] + c]) for c in range(r[0], r[1])]
+            batches.append(((points[k, :4], points[k, 4:]), terms))
+        rows = np.concatenate([C.lde(groups[i][1], size, b) for i in mine])
+        x, y = domain_xy(size + b)
+        out.append(row_quotient(rows, quotient_consts(batches, after), x, y).reshape(-1))
+    return np.concatenate(out).astype(np.uint32)
+
+
+ALL = lambda nc: (0, nc)  # noqa: E731
+QCASES = {  # name: (b, n, mask, [(log, n_cols, shared, [per point (lo, hi) or None])])
+    "three_sizes_A_above_B": (1, 2, None, [(6, 8, False, [ALL(8)]), (5, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
+                                           (5, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), None, (1, 3)])]),
+    "three_sizes_A_below_B": (2, 3, [1, 0, 1], [(6, 8, False, [ALL(8)]), (3, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
+                                                (3, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), None, (1, 3)])]),
+    "equal_sizes_merge": (1, 2, None, [(6, 8, False, [ALL(8)]), (4, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
+                                       (4, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), (0, 4)])]),
+    "shared_group": (1, 3, None, [(5, 6, True, [ALL(6)]), (5, 2, False, [ALL(2), (1, 2)])]),
+    "past_the_lds_fft": (1, 1, None, [(11, 2, False, [ALL(2), (0, 1)])]),
+    "past_one_workgroup_of_proofs": (1, 70, None, [(4, 3, False, [ALL(3), (1, 3)]), (3, 2, False, [ALL(2)])]),  # k_fr_consts
+}
+
+
+def qinputs(rng, spec, n, value=None):
+    draw = (lambda shape: rng.integers(0, P, shape)) if value is None else (lambda shape: np.full(shape, value, np.int64))
+    groups = [(log, draw((1 if sh else n, nc, 1 << log))) for log, nc, sh, _ in spec]
+    k = max(len(g[3]) for g in spec)
+    total = sum(g[1] for g in spec)
+    return groups, [g[3] for g in spec], draw((n, k, 8)).astype(np.uint32), draw((n, k, total, 4)).astype(np.uint32), draw((n, 4)).astype(np.uint32)

@@ -9,6 +9,7 @@ import numpy as np
 from tests import oracle_binding as ob
 
 GARBAGE = 0xDEADBEEF
+CAPS = ([3, 5, 4, 6], [4, 3, 5, 2], 3, 4)  # the capacities of the random parts' buffers, in caps_list's form
 
 
 def header_of(proof):

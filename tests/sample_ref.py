@@ -63,3 +63,14 @@ def witness_samples(trees, oods):
 def flatten_samples(sampled_values):
     """parse_proof's sampled_values[0..2] -> uint32[134, 4] in the proof's order."""
     return np.array([v for t in range(3) for col in sampled_values[t] for v in col], dtype=np.uint32)
+
+
+# The trees of tests/test_sample_gpu.py::test_sample_tree_path_switches, as chain_harness.CASES: (groups as (log, cols, shared), b, n, mask)
+SWITCHES = [  # both sides of 2^8 (idle lanes), 2^10 (the unrolled loop) and 2^13 (chunks per column), up to 2^16
+    ([(7, 2, False), (8, 3, False)], 1, 2, None),
+    ([(9, 2, False), (10, 2, False), (11, 1, False)], 1, 2, [1, 0]),
+    ([(12, 2, False), (13, 2, False)], 1, 2, None),
+    ([(14, 2, True), (13, 1, False)], 1, 3, [1, 1, 0]),
+    ([(15, 1, False)], 1, 2, None),
+    ([(16, 1, False)], 1, 1, None),
+]

@@ -89,6 +89,9 @@ def test_options_are_explicit_validated_and_retired_ids_refused(rsv):
                             ("debug_log", 2, 0), ("witness_small_max", (1 << 20) + 2, 0), ("witness_small_log", 8, 0), ("witness_walk_log", 8, 0)):
         assert lib.rsv_ctx_set_option(None, rsv.OPTIONS[name], bad) == -5, name
         assert lib.rsv_ctx_set_option(None, rsv.OPTIONS[name], good) == 0, name
+    # the workspace fill (diagnostic): 0 off, 1 .. 256 = 1 + the fill byte; 0 is left set
+    for v, want in ((-1, -5), (257, -5), (256, 0), (1, 0), (0, 0)):
+        assert lib.rsv_ctx_set_option(None, rsv.OPTIONS["ws_fill"], v) == want, v
     # no getenv anywhere in the product sources, no RSV_ variable in the library's strings
     import subprocess
     for root, _, files in os.walk(os.path.join(ROOT, "recursive-stwo_amd", "csrc")):

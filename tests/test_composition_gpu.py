@@ -104,12 +104,7 @@ def _ref(plonk, poseidon, lp, lq, sums, draws, p):
     return K.composition(mine(plonk), mine(poseidon), lp, lq, sums[p], draws[p])
 
 
-SHAPES = [  # (lp, lq, n, mask, shared preprocessed columns)
-    (4, 3, 2, None, False),       # clb = 6 from the Plonk term
-    (3, 5, 3, [1, 0, 1], False),  # clb = 8 from the Poseidon term, Plonk over-extended by 2^5; one proof masked
-    (6, 6, 2, None, True),        # preprocessed columns shared by every proof (stride 0)
-    (11, 10, 2, None, False),     # clb = 13: just past the 4 096-point switch between the LDS and the global FFT stages
-]
+SHAPES = K.SHAPES
 
 
 def _check_shape(rsv, lp, lq, n, mask, shared, seed):

@@ -82,27 +82,6 @@ def test_batch_with_a_rejected_proof(rsv):
 
 
 # ---------------------------------------------------------------- rsv_fri_quotients_dev on random columns
-def _ref_quotients(groups, gpoints, b, points, samples, after):
-    """One proof.  groups [(log, int64[n_cols, 2^log])], gpoints per group per point (lo, hi) or None, points uint32[k, 8],
-    samples uint32[k, total, 4] -> uint32 words of d_quot: the columns in descending size, each [4][2^(log + b)]."""
-    out, col0 = [], np.cumsum([0] + [g[1].shape[0] for g in groups])
-    for size in sorted({log for log, _ in groups}, reverse=True):
-        mine = [i for i, (log, _) in enumerate(groups) if log == size]
-        first = np.cumsum([0] + [groups[i][1].shape[0] for i in mine])
-        batches = []
-        for k in range(points.shape[0]):
-            terms = []
-            for j, i in enumerate(mine):
-                r = gpoints[i][k] if k < len(gpoints[i]) else None
-                if r is not None:
-                    terms += [(first[j] + c, samples[k, col0[i] + c]) for c in range(r[0], r[1])]
-            batches.append(((points[k, :4], points[k, 4:]), terms))
-        rows = np.concatenate([C.lde(groups[i][1], size, b) for i in mine])
-        x, y = F.domain_xy(size + b)
-        out.append(F.row_quotient(rows, F.quotient_consts(batches, after), x, y).reshape(-1))
-    return np.concatenate(out).astype(np.uint32)
-
-
 def _run_quotients(ctx, groups, gpoints, b, n, points, samples, after, mask=None, shared=(), source=0):
     import torch
     gs = []
@@ -117,26 +96,8 @@ def _run_quotients(ctx, groups, gpoints, b, n, points, samples, after, mask=None
     return u32(d_quot)
 
 
-ALL = lambda nc: (0, nc)  # noqa: E731
-QCASES = {  # name: (b, n, mask, [(log, n_cols, shared, [per point (lo, hi) or None])])
-    "three_sizes_A_above_B": (1, 2, None, [(6, 8, False, [ALL(8)]), (5, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
-                                           (5, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), None, (1, 3)])]),
-    "three_sizes_A_below_B": (2, 3, [1, 0, 1], [(6, 8, False, [ALL(8)]), (3, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
-                                                (3, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), None, (1, 3)])]),
-    "equal_sizes_merge": (1, 2, None, [(6, 8, False, [ALL(8)]), (4, 3, False, [ALL(3)]), (4, 5, False, [ALL(5)]),
-                                       (4, 4, False, [ALL(4), (2, 4)]), (4, 4, False, [ALL(4), (0, 4)])]),
-    "shared_group": (1, 3, None, [(5, 6, True, [ALL(6)]), (5, 2, False, [ALL(2), (1, 2)])]),
-    "past_the_lds_fft": (1, 1, None, [(11, 2, False, [ALL(2), (0, 1)])]),
-    "past_one_workgroup_of_proofs": (1, 70, None, [(4, 3, False, [ALL(3), (1, 3)]), (3, 2, False, [ALL(2)])]),  # k_fr_consts
-}
-
-
-def _qinputs(rng, spec, n, value=None):
-    draw = (lambda shape: rng.integers(0, P, shape)) if value is None else (lambda shape: np.full(shape, value, np.int64))
-    groups = [(log, draw((1 if sh else n, nc, 1 << log))) for log, nc, sh, _ in spec]
-    k = max(len(g[3]) for g in spec)
-    total = sum(g[1] for g in spec)
-    return groups, [g[3] for g in spec], draw((n, k, 8)).astype(np.uint32), draw((n, k, total, 4)).astype(np.uint32), draw((n, 4)).astype(np.uint32)
+ALL = F.ALL
+QCASES = F.QCASES
 
 
 @pytest.mark.parametrize("case", list(QCASES))
@@ -145,7 +106,7 @@ def test_quotients_bit_for_bit(rsv, case):
     coefficients source gives the same words as the evaluations source, a masked proof is zero."""
     b, n, mask, spec = QCASES[case]
     rng = np.random.default_rng(1800 + list(QCASES).index(case))
-    groups, gp, points, samples, after = _qinputs(rng, spec, n)
+    groups, gp, points, samples, after = F.qinputs(rng, spec, n)
     shared = {i for i, g in enumerate(spec) if g[2]}
     ctx = rsv.Context(0)
     got = _run_quotients(ctx, groups, gp, b, n, points, samples, after, mask, shared)
@@ -158,17 +119,17 @@ def test_quotients_bit_for_bit(rsv, case):
             assert not got[p].any(), p
             continue
         mine = [(log, cols[0 if i in shared else p]) for i, (log, cols) in enumerate(groups)]
-        assert np.array_equal(got[p], _ref_quotients(mine, gp, b, points[p], samples[p], after[p])), (case, p)
+        assert np.array_equal(got[p], F.ref_quotients(mine, gp, b, points[p], samples[p], after[p])), (case, p)
 
 
 def test_quotients_largest_words(rsv):
     """Every column, point, sample and `after` word at P - 1."""
     b, n, _, spec = QCASES["three_sizes_A_above_B"]
-    groups, gp, points, samples, after = _qinputs(None, spec, 1, value=P - 1)
+    groups, gp, points, samples, after = F.qinputs(None, spec, 1, value=P - 1)
     ctx = rsv.Context(0)
     got = _run_quotients(ctx, groups, gp, b, 1, points, samples, after)
     ctx.close()
-    assert np.array_equal(got[0], _ref_quotients([(log, c[0]) for log, c in groups], gp, b, points[0], samples[0], after[0]))
+    assert np.array_equal(got[0], F.ref_quotients([(log, c[0]) for log, c in groups], gp, b, points[0], samples[0], after[0]))
 
 
 def _pass_size(spec, n_points, b, n, budget):
@@ -206,7 +167,7 @@ def test_quotients_under_a_small_workspace_budget(rsv):
     assert _pass_size(spec, 2, b, n, 8192 << 20)[:2] == (n, 4)
     assert _pass_size(spec, 2, b, n, 1 << 21)[:2] == (n, 1)
     rng = np.random.default_rng(1820)
-    groups, gp, points, samples, after = _qinputs(rng, spec, n)
+    groups, gp, points, samples, after = F.qinputs(rng, spec, n)
     mask = [0 if p in (0, 19, 39) else 1 for p in range(n)]
     ctx = rsv.Context(0)
     whole = _run_quotients(ctx, groups, gp, b, n, points, samples, after, mask, {0})
@@ -219,19 +180,11 @@ def test_quotients_under_a_small_workspace_budget(rsv):
             assert not whole[p].any(), p
             continue
         mine = [(log, cols[0 if i == 0 else p]) for i, (log, cols) in enumerate(groups)]
-        assert np.array_equal(whole[p], _ref_quotients(mine, gp, b, points[p], samples[p], after[p])), p
+        assert np.array_equal(whole[p], F.ref_quotients(mine, gp, b, points[p], samples[p], after[p])), p
 
 
 # ---------------------------------------------------------------- rsv_fri_commit_dev on random quotient columns
-CCASES = {  # name: (sizes, log_last, b, n, mask, low degree input)
-    "three_columns": ([7, 6, 5], 2, 1, 2, None, False),
-    "joins_at_the_last_fold": ([6, 4], 1, 2, 3, [1, 0, 1], False),
-    "log_last_0": ([5, 3], 0, 1, 1, None, False),
-    "no_inner_layer": ([4], 2, 1, 1, None, False),
-    "levels_past_one_workgroup": ([11, 9], 1, 1, 1, None, False),
-    "low_degree": ([8, 7, 5], 2, 2, 2, None, True),
-    "past_one_workgroup_of_proofs": ([5, 3], 0, 1, 70, masked_past_64(), False),  # k_fr_draw, k_fr_mix_last
-}
+CCASES = F.CCASES
 
 
 @pytest.mark.parametrize("case", list(CCASES))

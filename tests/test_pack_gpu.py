@@ -82,7 +82,7 @@ def test_fixtures_of_one_shape_as_a_batch(rsv, ctx, names):
 
 
 # ---------------------------------------------------------------- 2. random parts at the smallest shapes
-CAPS = ([3, 5, 4, 6], [4, 3, 5, 2], 3, 4)
+CAPS = PR.CAPS
 
 
 def _random_batch(rng, hdr, n):

@@ -156,14 +156,7 @@ def test_sample_tree_bit_for_bit(rsv, case):
     ctx.close()
 
 
-SWITCHES = [  # both sides of 2^8 (idle lanes), 2^10 (the unrolled loop) and 2^13 (chunks per column), up to 2^16
-    ([(7, 2, False), (8, 3, False)], 1, 2, None),
-    ([(9, 2, False), (10, 2, False), (11, 1, False)], 1, 2, [1, 0]),
-    ([(12, 2, False), (13, 2, False)], 1, 2, None),
-    ([(14, 2, True), (13, 1, False)], 1, 3, [1, 1, 0]),
-    ([(15, 1, False)], 1, 2, None),
-    ([(16, 1, False)], 1, 1, None),
-]
+SWITCHES = S.SWITCHES
 
 
 def test_sample_tree_path_switches(rsv):
