@@ -1,9 +1,11 @@
 // host_logic.hpp — the HOST-side decisions of a verify call that touch no device: how a mixed batch is bucketed by
-// shape, how the per-query stages are cut into groups that fit the workspace budget, and (plan_pass) how a stage of the
-// next proof sizes a pass of proofs and blocks to that budget.  Plain C++ (no HIP): included by
+// shape, how the per-query stages are cut into groups that fit the workspace budget, which form of every kernel a batch
+// runs and on which stream (VerifyPlan: plan_batch before the groups are known, plan_launches and plan_group after), and
+// (plan_pass) how a stage of the next proof sizes a pass of proofs and blocks to that budget.  Plain C++ (no HIP): included by
 // verify_api.inc, and compiled on its own by g++ with AddressSanitizer + UBSan for tests/host_logic_asan.cpp, which drives
-// it from recorded and adversarial shape arrays — the host code of the mixed-batch path had never seen a sanitizer
-// before round 4 (the r3a crash pointed at exactly this code or at the test's own threads).
+// it from recorded and adversarial shape arrays and pins the plan of every batch size at which a form changes — the host
+// code of the mixed-batch path had never seen a sanitizer before round 4 (the r3a crash pointed at exactly
+// this code or at the test's own threads).
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -12,6 +14,7 @@
 #include <vector>
 
 #include "layout.hpp"
+#include "options.hpp"
 
 namespace rsv::host {
 
@@ -189,6 +192,179 @@ inline size_t plan_groups(const std::vector<Bucket>& buckets, const GroupPolicy&
     }
     flush();
     return need;
+}
+
+// ---------------------------------------------------------------- the launch plan of a verify call
+// Every form decision of verify_impl (verify_api.inc) depends only on the batch size, the configuration, the options and the
+// outputs asked for.  They are taken here, in two steps — plan_batch before the groups are known, plan_launches (and
+// plan_group, per group) after — and the launcher only reads the result.
+
+constexpr int kBlock = 256;
+// Row form of the tree kernels (k_merkle.hpp): 512 threads = 32 virtual lanes per workgroup (two waves per SIMD: 256 registers); chosen while the FRI-tree
+// launch holds at most this many paths (proofs x queries x trees).
+constexpr int kRowTreeBlock = 512;
+constexpr uint64_t kRowTreeLanes = 256ull * 16 * 9;
+constexpr uint64_t kRowQueryLanes = 256ull * 16;  // k_query's row form: up to this many queries (proofs x queries) in the launch
+
+// what a verify call is asked for, as far as a form depends on it
+struct PlanInputs {
+    uint32_t N;                              // proofs of the batch
+    uint32_t n_cfgs;                         // the configuration set: how many, ...
+    bool cfg_of;                             // ... whether every proof names its own, ...
+    uint32_t log_blowup, log_last, n_queries;  // ... and configuration 0
+    bool flow;                               // the pass writes PoseidonFlow records
+    bool paths;                              // outputs indexed by one declared shape (PathsOut::paths)
+    bool trace_sib, pair_sib;                // sibling outputs of the trace trees / of the FRI trees
+    bool own;                                // every proof has its own public inputs
+    size_t max_fused;                        // entries per launch (Fused<>)
+};
+
+struct VerifyPlan {
+    // plan_batch
+    bool transcript_row, transcript_split, transcript_paced;
+    bool device_order;   // slot order on the device, nothing read back
+    int tree_form;       // the PACE / FORM template argument of the tree kernels: 1 paced, 0 unpaced, 2 row
+    bool small_trees;    // the row hashes on the unpaced permutation instances
+    bool qconst_row, qconst4;
+    bool oods_row;
+    bool cap_top;
+    bool serial_plan;    // one-lane-per-proof original (tests)
+    bool pair_deal;      // the FRI trees of a small launch dealt out over the compute units (pair_layer_order)
+    GroupPolicy policy;
+    // plan_launches
+    uint32_t tree_lanes;  // lanes of the tree kernels' indexing per workgroup
+    bool overlap_trees, chain, query_row, qconst_in_plan;
+    bool oods_on_main;    // the OODS kernel inside the one group, on the main stream; else last on the side stream
+};
+
+// the OODS evaluation has a lane form and a row form
+// small batches: one proof per 16-lane row (latency form); large ones: one proof per lane (throughput form).
+// RSV_OPT_OODS_FORM overrides (tests).  The row form is a latency form: it pays while the kernel is on the step's chain
+// of dependent kernels; since it runs behind the trace trees beside k_pair_merkle (and costs three times the issue slots
+// per proof) the lane form wins from 8 192 proofs on (4 096: 2.82 vs 2.97 ms; 8 192: 5.43 vs 5.38; 16 384: 10.31 vs
+// 10.14; 24 576: 15.09 vs 14.67).
+inline bool oods_row_form(const Options& o, size_t n) { return o.oods_form ? o.oods_form == 1 : n <= 6144; }
+
+inline VerifyPlan plan_batch(const Options& o, const PlanInputs& in) {
+    VerifyPlan p{};
+    const uint32_t N = in.N;
+    // small batches: one proof per 16-lane DPP row (latency form of the transcript); large ones: one proof per lane
+    // (throughput form).  RSV_OPT_TRANSCRIPT_FORM overrides (tests).
+    // measured crossover on MI355X: 16 384 proofs 1.41 M/s (row) vs 1.26 M/s (lane), 32 768: 1.32 vs 1.36
+    p.transcript_row = o.transcript_form ? o.transcript_form == 1 : N <= 24576;
+    // Up to one wave per SIMD (4 096 proofs) the row form runs as two launches: the front half needs nothing from the
+    // parser and starts next to it on the aux stream (k_transcript.hpp): 1 024 proofs 1.67 -> 1.63 ms, 4 096 2.89 -> 2.82;
+    // at 8 192 it is a wash and beyond that the two halves and the parser get in each other's way (12 288: +12 %).
+    // RSV_OPT_TRANSCRIPT_SPLIT overrides (tests).  The lane form (large batches) always runs as one launch (split the same
+    // way, it measured 35.46 vs 35.20 ms at 65 536 proofs: inside run-to-run noise), and so does a pass that writes the flow.
+    p.transcript_split = p.transcript_row && !in.flow && (o.transcript_split ? o.transcript_split == 2 : N <= 4096);
+    // the lane form without flow: up to one wave per SIMD on the unpaced channel (k_transcript.hpp)
+    p.transcript_paced = !p.transcript_row && !in.flow && N > 49152;
+    // A batch under ONE configuration is one launch geometry of known size (n_queries is the configuration's, every
+    // proof either carries it or is rejected by the parser): nothing has to come back to the host.  The slot order by
+    // shape class is made on the device (k_parse.hpp) and the tables are sized for the largest trees the parser lets
+    // through, so the call enqueues everything and returns: no host synchronisation anywhere in it.  Batches under
+    // several configurations (several n_queries buckets whose sizes only the device knows) and calls with per-query path
+    // outputs (one declared shape, checked on the host) keep the round trip of rounds 1-2.
+    p.device_order = in.n_cfgs == 1 && !in.cfg_of && !in.paths && o.device_order != 2 && in.n_queries >= 1 && in.n_queries <= (uint32_t)MAXQ &&
+                     in.log_blowup >= 1 && in.log_blowup <= 16 && in.log_last <= 16;
+    // A batch whose FRI-tree launch puts fewer than about two and a half waves on a SIMD (at most 1 024 proofs of 16 queries
+    // and nine trees; measured: one proof 1.31 -> 1.21 ms, 512 proofs 1.43 -> 1.34, 768: 1.45 -> 1.35, 1 024: 1.467 -> 1.457,
+    // 2 048: 1.906 -> 1.945, slower) runs the
+    // tree kernels on the unpaced permutation instances.  An estimate from the configuration (the batch's real depth is on
+    // the device only): proofs x queries x (FRI trees of the common depth M = 22).
+    // Up to 256 proofs of 16 queries the trees go one step further, to the ROW form on virtual lanes (k_merkle.hpp): 16 threads per
+    // path, every permutation shared by a DPP row.  RSV_OPT_TREE_PACE overrides (1 paced, 2 unpaced, 3 row).
+    const uint32_t nq_est = in.n_queries < 4 ? 4u : in.n_queries, fold_est = in.log_blowup + in.log_last;
+    const uint64_t lanes = (uint64_t)N * nq_est * (22u > fold_est ? 22u - fold_est : 1u);
+    p.tree_form = 1;
+    if (o.tree_pace) p.tree_form = o.tree_pace == 1 ? 1 : (o.tree_pace == 2 ? 0 : 2);
+    else if (in.n_cfgs == 1 && lanes <= kRowTreeLanes) p.tree_form = 2;
+    else if (in.n_cfgs == 1 && lanes <= 1024ull * 16 * 9) p.tree_form = 0;
+    if (in.flow && p.tree_form == 0) p.tree_form = 1;  // (the FLOW instantiations: paced lane form and row form)
+    // a small batch's launches leave a wave nearly alone on its SIMD: the unpaced permutation instances (poseidon2.hpp)
+    p.small_trees = p.tree_form != 1;  // (the row hashes: lane forms only; they run underneath the transcript)
+    // the quotient constants, small batches: one proof per 16-lane row (latency form); RSV_OPT_QCONST_FORM overrides (tests)
+    p.qconst_row = o.qconst_form ? o.qconst_form == 1 : N <= 24576;
+    // the row form of the quotient constants on four rows per proof (k_plan.hpp: qconst_row_body); RSV_OPT_QCONST_FORM = 1
+    // forces the row form with ONE row per proof (what batches of 4 097 .. 24 576 proofs run), so that tests reach it
+    p.qconst4 = N <= 4096 && o.qconst_form != 1;
+    p.oods_row = oods_row_form(o, N);
+    // The top of the cap in its own kernel (k_cap_top: one lane per tree instead of a part-filled wave per workgroup):
+    // fewer permutation slots, two more launches — from 1 024 proofs on (measured: 1 024 proofs 1.663 -> 1.652 ms, 16 384: 9.98 -> 9.84, 65 536: 34.96 -> 34.37; a single proof would wait for three sequential hashes of a 17-lane launch),
+    // and not while per-query paths are emitted (the cap writes the top of every path as it goes).
+    p.cap_top = !(in.trace_sib || in.pair_sib) && (o.cap_top ? o.cap_top == 1 : N >= 1024);
+    p.serial_plan = o.plan_form == 2;
+    p.pair_deal = o.pair_order != 2;
+    p.policy = GroupPolicy{(size_t)o.ws_budget_mb << 20, in.max_fused, o.tree_cap == 2, in.flow, o.flow_cap == 2, p.cap_top, o.cap_mid};
+    return p;
+}
+
+// Step two: what depends on how plan_groups cut the batch.
+inline void plan_launches(VerifyPlan& p, const Options& o, const PlanInputs& in, const std::vector<std::vector<Entry>>& groups) {
+    bool wide = false;  // an entry with more queries than a workgroup of the row forms has virtual lanes
+    for (const std::vector<Entry>& grp : groups)
+        for (const Entry& en : grp) wide = wide || en.G > (uint32_t)kRowTreeBlock / 16u;
+    if (p.tree_form == 2 && wide) p.tree_form = in.flow ? 1 : 0;
+    p.tree_lanes = p.tree_form == 2 ? (uint32_t)kRowTreeBlock / 16u : (uint32_t)kBlock;
+    // The FRI trees go to the SIDE stream right behind k_query (the only thing they wait for) and run next to the
+    // trace trees instead of after them; the two kernels that only feed k_finalize (OODS check, canonicity scan)
+    // follow the trace trees on the main stream.  A small batch leaves most of the chip idle and its step is a
+    // chain of dependent kernels, so the overlap shortens it (1 024 proofs -3 %, 2 048 -4 %, 8 192 -2.4 %); a
+    // large one fills the chip with either kernel and gains 0.4 % (65 536 proofs: 35.7 vs 35.9 ms).  Batches cut
+    // into several groups keep the serial order: the groups share one workspace.
+    p.overlap_trees = groups.size() == 1 && o.overlap_trees != 2;
+    // Stream layout of a single-group batch.  "Chain" (RSV_OPT_CRITICAL_CHAIN): every kernel the verdict waits for
+    // longest sits on ONE stream, in order — transcript, quotient constants, plan, k_query, FRI trees, finalize — and
+    // the side stream takes what finishes early anyway (row hashes, then — behind the plan — trace trees and the OODS
+    // check).  A kernel that waits for another stream's event starts ~20 us after it (measured on MI355X: 18-28 us
+    // against 5-11 us behind a kernel of its own stream); the two-stream layout of rounds 1-2 had three such waits
+    // on the path of a small batch (transcript -> k_qconst, k_plan -> k_query, FRI trees -> finalize).
+    // measured: +1..4 % from 512 to 16 384 proofs, -2 % at 32 768 and beyond
+    p.chain = p.overlap_trees && (o.critical_chain ? o.critical_chain == 1 : in.N <= 24576);
+    // k_query on virtual lanes (k_query.hpp: 16 threads per query split its sums): RSV_OPT_QUERY_FORM, or by size
+    p.query_row = p.chain && !wide &&
+                  (o.query_form ? o.query_form == 1 : (uint64_t)in.N * (in.n_queries < 4 ? 4u : in.n_queries) <= kRowQueryLanes && in.n_cfgs == 1);
+    // the row-form quotient constants of a chain-layout batch ride in the plan's launch (k_plan_par<.., true>)
+    p.qconst_in_plan = p.chain && !p.serial_plan && p.qconst_row;
+    // The OODS composition check only raises failure flags (atomicOr) for k_finalize.  Single-group batch outside the chain
+    // layout: on the main stream in front of the trace trees' last levels, which wait for the FRI trees to leave them room —
+    // so it runs underneath the FRI trees, not behind them.  Else last on the side stream (chain: behind the trace trees;
+    // several groups: behind k_query).
+    p.oods_on_main = p.overlap_trees && !p.chain;
+}
+
+struct GroupPlan {
+    bool tm_t, tm_p;         // item order of the cap kernels over the trace / FRI trees: tree-major
+    size_t pair_lds;         // dynamic LDS of k_pair_merkle
+    uint32_t group_M, live;  // the weights of pair_layer_order: tree depth, grid rows that have work
+};
+
+inline GroupPlan plan_group(const VerifyPlan& p, const PlanInputs& in, const std::vector<Bucket>& buckets, const std::vector<Entry>& grp) {
+    GroupPlan g{};
+    uint64_t top_t = 0, top_p = 0;  // workgroups of k_cap_top over the trace / FRI trees
+    uint32_t max_inner = 0;
+    for (const Entry& en : grp) {
+        const Bucket& b = buckets[en.bi];
+        top_t += ((uint64_t)en.cn * 4 + 255) / 256;
+        top_p += ((uint64_t)en.cn * (1 + b.maxInner) + 255) / 256;
+        max_inner = std::max(max_inner, b.maxInner);
+        g.group_M = std::max(g.group_M, b.maxM);
+    }
+    // item order of the cap kernels (k_merkle.hpp: CapTopIndex): tree-major for launches of >= 2^19 lanes
+    g.tm_t = top_t * 256 >= (1u << 19);
+    g.tm_p = top_p * 256 >= (1u << 19);
+    g.pair_lds = (in.pair_sib || in.flow) ? (size_t)kBlock * 32 : 0;
+    g.live = 1 + max_inner;
+    if (p.device_order) {
+        // the launch is sized for MAX_LOG; what the batch really holds is on the device only.  The weights assume
+        // the common depth of the reference's proofs (M = 22): a batch of deeper or shallower trees is still dealt
+        // out better than row y = tree y, and any order is a correct one.
+        g.group_M = 22;
+        const uint32_t fold = in.log_blowup + in.log_last;
+        g.live = g.group_M > fold ? g.group_M - fold : 1u;
+    }
+    return g;
 }
 
 // One pass of a stage that streams the next proof's column groups (commit_api.inc): P proofs times nb blocks.

@@ -1,5 +1,7 @@
-// verify_api.inc — host launcher of the verify pipeline (included by rsv_hip.hip).  The decisions that touch no device
-// (shape buckets, workspace groups) live in host_logic.hpp, where a sanitizer can reach them.
+// verify_api.inc — host launcher of the verify pipeline (included by rsv_hip.hip).  Every decision that touches no device
+// lives in host_logic.hpp, where a sanitizer can reach it: the shape buckets, the workspace groups, and the launch plan
+// (VerifyPlan) — which form of each kernel a batch runs and on which stream.  verify_impl checks its arguments, builds the
+// plan and then only enqueues, stage function by stage function; none of them decides a form, each reads the plan.
 //
 // Launch plan for one batch (M = main stream, S = side stream):
 //   1. M: k_parse over the whole batch, then ONE 32-byte read-back of the batch summary (max queries / log size /
@@ -19,14 +21,11 @@
 
 namespace {
 
-constexpr int kBlock = 256;
-// Row form of the tree kernels (k_merkle.hpp): 512 threads = 32 virtual lanes per workgroup (two waves per SIMD: 256 registers); chosen while the FRI-tree
-// launch holds at most this many paths (proofs x queries x trees).
-constexpr int kRowTreeBlock = 512;
-constexpr uint64_t kRowTreeLanes = 256ull * 16 * 9;
-constexpr uint64_t kRowQueryLanes = 256ull * 16;  // k_query's row form: up to this many queries (proofs x queries) in the launch
-
+using rsv::host::kBlock;
+using rsv::host::kRowTreeBlock;
+using rsv::host::Bucket;
 using rsv::host::Carve;
+using rsv::host::Entry;
 
 struct StageClock {
     std::vector<hipEvent_t> pool;
@@ -158,29 +157,543 @@ static int make_cfg_set(const rsv_cfg_set* cfg, CfgSet* out) {
     return RSV_OK;
 }
 
-// the OODS evaluation has a lane form and (later) a row form; both entry points launch through here
-// small batches: one proof per 16-lane row (latency form); large ones: one proof per lane (throughput form).
-// RSV_OPT_OODS_FORM overrides (tests).  The row form is a latency form: it pays while the kernel is on the step's chain
-// of dependent kernels; since it runs behind the trace trees beside k_pair_merkle (and costs three times the issue slots
-// per proof) the lane form wins from 8 192 proofs on (4 096: 2.82 vs 2.97 ms; 8 192: 5.43 vs 5.38; 16 384: 10.31 vs
-// 10.14; 24 576: 15.09 vs 14.67).
-static bool oods_row_form(const Options& o, size_t n) { return o.oods_form ? o.oods_form == 1 : n <= 6144; }
+// the OODS evaluation's two forms (host_logic.hpp: oods_row_form): one proof per 16-lane row, or one proof per lane
 static void launch_oods_probe(const uint32_t* d_prefix, uint32_t prefix_words, const uint32_t* d_params, uint32_t* d_out, uint32_t n) {
-    if (oods_row_form(default_options(), n))
-        hipLaunchKernelGGL(k_oods_row_probe, dim3(grid_for((size_t)n * 16, 256)), dim3(256), 0, 0, d_prefix, prefix_words, d_params, d_out, n);
+    const bool row = rsv::host::oods_row_form(default_options(), n);
+    const unsigned block = row ? 256 : 64;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for((size_t)n * (row ? 16 : 1), block)), dim3(block), 0, 0, d_prefix, prefix_words, d_params, d_out, n);
+    };
+    row ? launch(k_oods_row_probe) : launch(k_oods_probe);
+}
+
+namespace {
+// One verify call, as its stage functions share it: the context, the arguments, the plan (host_logic.hpp), the records
+// carved out of the fixed workspace, what one stage leaves for the next, and the stage clock.
+struct VerifyCall {
+    rsv_ctx* c;
+    hipStream_t st;  // the main stream (the other two: c->side, c->aux)
+    VerifyState* vs;
+    const uint8_t* d_blob;
+    const uint64_t* d_offsets;
+    uint32_t N;
+    CfgSet co;
+    size_t n_pi;
+    // nullptr — the batch's one table, copied to c->d_pi; else [n][n_pi] records in HBM, every proof its own: k_pi_sum
+    // sums them per proof and the OODS kernel reads that sum (k_pi_sum.hpp)
+    const rsv_public_input* d_own_pi;
+    uint8_t *d_accept, *d_reason;
+    const PathsOut* po;
+    FlowArgs fargs;
+    rsv::host::PlanInputs in;
+    rsv::host::VerifyPlan plan;
+    // whole-batch records (ws_fixed)
+    uint32_t* summary;
+    ProofMeta* metas;
+    ProofCtx* ctxs;
+    uint32_t *d_shape, *d_ids;
+    ClassTable* d_classes;
+    uint8_t* d_cls;
+    uint32_t* d_pi_sum;  // k_pi_sum -> k_oods<PiOwn>
+    // the slot order: shape buckets, one launch geometry per distinct n_queries (host_logic.hpp)
+    bool live;     // some proof has a lane somewhere
+    bool uniform;  // one bucket in natural order: no slot -> proof list
+    std::vector<Bucket> buckets;
+    // the row hashes, addressed by slot: where each bucket's begin
+    uint32_t* rowh;
+    std::vector<size_t> row_base;
+    bool joined;  // the main stream has waited for the row hashes
+
+    // Stage clock: opt-in (RSV_OPT_STAGE_TIMES).  Two event records around a stage cost ~8 us of queue time EACH STAGE
+    // (tools/chain_lab.hip: 5.3 us per dependent empty launch, 13.3 with the two records) — on a small batch's chain of
+    // seven stages that was 4 % of the call, paid by every caller for a diagnostic only bench.py reads.
+    bool timing;
+    void begin_on(int stage, hipStream_t on) {
+        if (!timing) return;
+        hipEvent_t b = vs->clock.next();
+        if (b) (void)hipEventRecord(b, on);
+        vs->spans.push_back({stage, b, nullptr});
+    }
+    void end_on(hipStream_t on) {
+        if (!timing) return;
+        hipEvent_t e = vs->clock.next();
+        if (e) (void)hipEventRecord(e, on);
+        for (size_t i = vs->spans.size(); i-- > 0;)  // the span opened last and not yet closed
+            if (!vs->spans[i].e) { vs->spans[i].e = e; break; }
+    }
+};
+}  // namespace
+
+// Stages 1 and 2: the parser and the transcript.
+static int enqueue_parse_transcript(VerifyCall& v) {
+    rsv_ctx* c = v.c;
+    hipStream_t st = v.st;
+    const uint32_t N = v.N;
+    const bool row = v.plan.transcript_row, split = v.plan.transcript_split, flow = v.in.flow;
+    if (flow && v.fargs.count) HIP_TRY(hipMemsetAsync(v.fargs.count, 0, sizeof(uint32_t) * (size_t)N, st));
+    // Split: the PARSER goes to the aux stream and the front half stays on the main stream, in front of the back half — the
+    // parser (0.04-0.1 ms) is long over when the front half (0.16-0.19 ms) ends, so the back half's wait for it is a wait
+    // for an event signalled long ago, and front -> back is a boundary inside one stream (~5 us) instead of a fresh
+    // cross-stream wait (15 us; until the end of round 4 the front half was the one on the aux stream).
+    hipStream_t parse_on = split ? c->aux : st;
+    if (split) {
+        HIP_TRY(hipEventRecord(c->ev_begin, st));  // behind whatever produced the blob, the offsets and the inputs
+        HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_begin, 0));
+    }
+    v.begin_on(0, parse_on);
+    HIP_TRY(hipMemsetAsync(v.summary, 0, 256, parse_on));
+    hipLaunchKernelGGL(k_parse, dim3(grid_for(N, 64)), dim3(64), 0, parse_on, v.d_blob, v.d_offsets, N, v.co, v.metas, v.ctxs, v.summary, v.d_shape);
+    v.end_on(parse_on);
+    HIP_TRY(hipGetLastError());
+    // The transcript needs nothing from the host: it is enqueued right behind the parser, and the parse summary
+    // (and, for mixed batches, the shape words) travel back through the side stream while it runs.
+    HIP_TRY(hipEventRecord(c->ev_fork, parse_on));
+    const unsigned block = row ? 256 : 64;
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for((size_t)N * (row ? 16 : 1), block)), dim3(block), 0, st, v.d_blob, v.d_offsets, N, v.metas, v.ctxs, v.fargs);
+    };
+    if (split) {
+        launch(k_transcript_row<1>);
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_fork, 0));  // everything behind this on the main stream may read the parser's tables
+    }
+    v.begin_on(1, st);
+    if (split) launch(k_transcript_row<2>);
+    else if (row) flow ? launch(k_transcript_row<0, true>) : launch(k_transcript_row<0>);
+    else if (flow) launch(k_transcript<true>);
+    else !v.plan.transcript_paced ? launch(k_transcript<false, false>) : launch(k_transcript<false, true>);
+    v.end_on(st);
+    HIP_TRY(hipEventRecord(c->ev_tr, st));
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+// Stage 3: the slot order and the shape buckets — on the device with nothing read back (the plan's device_order), or from
+// the parse summary on the host.  RSV_E_SIZE: path outputs were asked for and the batch is not of the one declared shape.
+static int enqueue_slot_order(VerifyCall& v) {
+    rsv_ctx* c = v.c;
+    const uint32_t N = v.N;
+    const PathsOut* po = v.po;
+    const bool device_order = v.plan.device_order;
+    uint32_t sum[8] = {0};
+    HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+    if (device_order) {
+        HIP_TRY(hipMemsetAsync(v.d_classes, 0, sizeof(ClassTable), c->side));
+        hipLaunchKernelGGL(k_classify, dim3(grid_for(N, CLASSIFY_PER_BLOCK)), dim3(256), 0, c->side, N, v.d_shape, v.d_classes, v.d_cls);
+        hipLaunchKernelGGL(k_class_offsets, dim3(1), dim3(64), 0, c->side, v.d_classes);
+        hipLaunchKernelGGL(k_scatter_ids, dim3(grid_for(N, 256)), dim3(256), 0, c->side, N, v.d_cls, v.d_classes, v.d_ids);
+        sum[0] = 1;
+    } else {
+        HIP_TRY(hipMemcpyAsync(sum, v.summary, 32, hipMemcpyDeviceToHost, c->side));
+        HIP_TRY(hipStreamSynchronize(c->side));
+    }
+    v.live = sum[0] > 0;
+    if (!v.live) return RSV_OK;
+    v.uniform = !device_order && sum[4] == ~sum[5] && sum[6] == ~sum[7];
+    if (device_order) {
+        // every slot of the batch (rejected proofs have no live lane), the deepest trees the parser admits
+        const uint32_t b = v.co.c[0][1], last = v.co.c[0][2];
+        const uint32_t inner_bound = (uint32_t)MAX_LOG - 1u - (last + b);
+        v.buckets.push_back({v.co.c[0][3], (uint32_t)MAX_LOG, inner_bound > (uint32_t)MAX_INNER ? (uint32_t)MAX_INNER : inner_bound, last + b + 1u, N, 0});
+    } else if (po && po->paths() && (!v.uniform || (sum[4] & 0xFFu) != po->n_queries || ((sum[4] >> 8) & 0xFFu) != po->max_log || po->n_queries < 4 ||
+                                     ((po->d_pair_sib || po->d_pair_cols || po->d_qv) && ((sum[4] >> 16) & 0xFFu) != po->n_inner))) {
+        return RSV_E_SIZE;  // path emission needs one shape for the whole batch, as declared by the caller
+    } else if (v.uniform) {
+        v.buckets.push_back({sum[4] & 0xFFu, (sum[4] >> 8) & 0xFFu, (sum[4] >> 16) & 0xFFu, sum[4] >> 24, N, 0});
+    } else {
+        // Mixed batch: 8 bytes per proof come back, the host buckets them (rsv::host::bucket_by_shape) and uploads the
+        // slot -> proof list.
+        std::vector<uint32_t>& shape = v.vs->h_shape;
+        shape.resize(2 * (size_t)N);
+        HIP_TRY(hipMemcpyAsync(shape.data(), v.d_shape, 8 * (size_t)N, hipMemcpyDeviceToHost, c->side));
+        HIP_TRY(hipStreamSynchronize(c->side));
+        std::vector<uint32_t>& ids = v.vs->h_ids;
+        rsv::host::bucket_by_shape(shape.data(), N, v.buckets, ids, v.vs->h_class);
+        if (!ids.empty()) HIP_TRY(hipMemcpyAsync(v.d_ids, ids.data(), 4 * ids.size(), hipMemcpyHostToDevice, c->side));
+    }
+    // the slot -> proof list was uploaded on the side stream: k_plan (main stream) waits for it
+    HIP_TRY(hipEventRecord(c->ev_ids, c->side));
+    HIP_TRY(hipStreamWaitEvent(v.st, c->ev_ids, 0));
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+// Side stream: trace-tree column hashing (independent of the transcript), so that it fills the issue slots the
+// one-wave-per-SIMD transcript kernel leaves idle.  Row hashes are addressed by SLOT and sized per bucket
+// (count x that bucket's n_queries): one well-formed 128-query header in a batch of 16-query proofs must not
+// inflate the allocation of the whole batch.  All buckets go into ONE launch (Fused<>, at most MAX_FUSED each).
+static int enqueue_row_hashes(VerifyCall& v) {
+    rsv_ctx* c = v.c;
+    const std::vector<Bucket>& buckets = v.buckets;
+    v.row_base.resize(buckets.size());
+    size_t row_words = 0;
+    for (size_t bi = 0; bi < buckets.size(); bi++) {
+        v.row_base[bi] = row_words;
+        row_words += (size_t)buckets[bi].count * 4 * 2 * rsv::host::padded_lanes(buckets[bi]) * 8;
+    }
+    const int rc = ensure_buf(c, &c->ws_rows, &c->ws_rows_bytes, row_words * 4);
+    if (rc != RSV_OK) return rc;
+    v.rowh = static_cast<uint32_t*>(c->ws_rows);
+    v.begin_on(9, c->side);
+    for (size_t b0 = 0; b0 < buckets.size(); b0 += MAX_FUSED) {
+        Fused<RowHashArgs> fr{};
+        uint32_t blocks = 0;
+        for (size_t bi = b0; bi < buckets.size() && bi < b0 + MAX_FUSED; bi++) {
+            const Bucket& b = buckets[bi];
+            const uint32_t gq = rsv::host::padded_lanes(b);
+            fr.first_block[fr.nb] = blocks;
+            fr.a[fr.nb++] = RowHashArgs{v.d_blob, v.d_offsets, b.count, gq, v.metas, v.rowh + v.row_base[bi], v.uniform ? nullptr : v.d_ids + b.first, v.ctxs};
+            blocks += grid_for((size_t)b.count * gq, kBlock);
+        }
+        fr.first_block[fr.nb] = blocks;
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(blocks, 4), dim3(kBlock), 0, c->side, fr); };
+        v.plan.small_trees ? launch(k_row_hash<false>) : launch(k_row_hash<true>);
+    }
+    v.end_on(c->side);
+    HIP_TRY(hipEventRecord(c->ev_join, c->side));
+    return RSV_OK;
+}
+
+// the row form of the quotient constants, in k_qconst_row or inside the plan's launch: its workgroups, and its proof count
+// with the four-rows-per-proof flag
+static unsigned qconst_row_blocks(const VerifyCall& v) { return grid_for((size_t)v.N * (v.plan.qconst4 ? 64 : 16), 256); }
+static uint32_t qconst_row_n(const VerifyCall& v) { return v.N | (v.plan.qconst4 ? 0x80000000u : 0u); }
+
+// query-independent quotient constants: need only the transcript
+static void launch_qconst(VerifyCall& v, hipStream_t on) {
+    v.begin_on(10, on);
+    if (v.plan.qconst_row)
+        hipLaunchKernelGGL(k_qconst_row, dim3(qconst_row_blocks(v)), dim3(256), 0, on, v.d_blob, v.d_offsets, qconst_row_n(v), v.metas, v.ctxs);
     else
-        hipLaunchKernelGGL(k_oods_probe, dim3(grid_for(n, 64)), dim3(64), 0, 0, d_prefix, prefix_words, d_params, d_out, n);
+        hipLaunchKernelGGL(k_qconst, dim3(grid_for(v.N, 64)), dim3(64), 0, on, v.d_blob, v.d_offsets, v.N, v.metas, v.ctxs);
+    v.end_on(on);
+}
+
+// Stage 5: the OODS composition check, behind the transcript on whichever stream the plan puts it.
+static void launch_oods(VerifyCall& v, hipStream_t on) {
+    const uint32_t N = v.N;
+    const bool row = v.plan.oods_row, own = v.in.own;
+    v.begin_on(2, on);
+    const PiShared shared{reinterpret_cast<const PubInput*>(v.c->d_pi), (uint32_t)v.n_pi};
+    const PiOwn sums{v.d_pi_sum};
+    // per-proof inputs: the statement sums first, on the same stream (behind the transcript, as the OODS kernel is)
+    if (own)
+        hipLaunchKernelGGL(k_pi_sum<true>, dim3(grid_for(N, PI_WAVES)), dim3(64 * PI_WAVES), 0, on, reinterpret_cast<const uint32_t*>(v.d_own_pi),
+                           N, (uint32_t)v.n_pi, v.metas, v.ctxs, (const uint32_t*)nullptr, v.d_pi_sum, (uint8_t*)nullptr);
+    const unsigned block = row ? 256 : 64;
+    auto launch = [&](auto kernel, auto inputs) {
+        hipLaunchKernelGGL(kernel, dim3(grid_for((size_t)N * (row ? 16 : 1), block)), dim3(block), 0, on, v.d_blob, v.d_offsets, N, v.metas, v.ctxs, inputs);
+    };
+    if (row) own ? launch(k_oods_row<PiOwn>, sums) : launch(k_oods_row<PiShared>, shared);
+    else own ? launch(k_oods<PiOwn>, sums) : launch(k_oods<PiShared>, shared);
+    v.end_on(on);
+}
+
+namespace {
+// The launches of one group: the argument tables of its entries (a group is ONE launch per stage) and their grids.
+struct GroupLaunch {
+    Fused<PlanArgs> fp;
+    Fused<QueryArgs> fq;
+    Fused<MerkleArgs> fm;
+    CapTopIndex ix_t, ix_p, ix_mt, ix_mp;  // k_cap_top / k_cap_mid over the trace (t) and the FRI (p) trees
+    uint32_t blocks, blocks_m, blocks_q;   // workgroups of kBlock lanes / of the tree kernels / of k_query's row form
+    uint32_t max_inner, top_t, top_p, mid_t, mid_p;
+    bool any_top, any_mid;
+    rsv::host::GroupPlan plan;
+};
+}  // namespace
+
+// carves the group's workspace (the groups share c->ws) and fills the argument tables
+static void fill_group(VerifyCall& v, const std::vector<Entry>& grp, GroupLaunch& g) {
+    const PathsOut* po = v.po;
+    const bool query_row = v.plan.query_row;
+    const uint32_t row_lanes = (uint32_t)kRowTreeBlock / 16u;
+    Carve wq{static_cast<char*>(v.c->ws)};
+    uint32_t pbmax = 1;
+    for (const Entry& en : grp) {
+        const Bucket& b = v.buckets[en.bi];
+        PlanPtrs pl{};
+        pl.hdr = wq.take<PlanHdr>(en.cn);
+        pl.ent = wq.take<uint32_t>((size_t)en.cn * (b.maxM + 1) * en.G);
+        pl.fl = wq.take<uint32_t>((size_t)en.cn * 2 * en.G);
+        pl.G = en.G;
+        pl.maxM = b.maxM;
+        uint32_t* leafv = wq.take<uint32_t>((size_t)en.cn * (3 + b.maxInner) * en.G * 8);
+        pl.ids = v.uniform ? nullptr : v.d_ids + b.first + en.c0;
+        pl.p0 = v.uniform ? (uint32_t)en.c0 : 0u;
+        const size_t c0 = en.c0;
+        QueryArgs qa{v.d_blob, v.d_offsets, en.cn, v.metas, v.ctxs, pl, leafv, b.maxInner,
+                     (po && po->d_folded) ? po->d_folded + c0 * 3 * en.G * 4 : nullptr,
+                     (po && po->d_qv) ? po->d_qv + c0 * en.G * 4 * (8 + b.maxInner) : nullptr, 4 * (8 + b.maxInner)};
+        MerkleArgs ma{v.d_blob, v.d_offsets, en.cn, v.metas, v.ctxs, pl, leafv, b.maxInner, en.Lc,
+                      v.rowh + v.row_base[en.bi] + c0 * 4 * 2 * (size_t)en.G * 8, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      en.Lt, en.Lt2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (en.Lt) {
+            ma.tcapn = wq.take<uint32_t>(((size_t)en.cn * 4 << en.Lt) * 8);
+            ma.tcapm = wq.take<unsigned long long>((size_t)en.cn * 4);
+            ma.pcapn = wq.take<uint32_t>(((size_t)en.cn * (1 + b.maxInner) << en.Lt) * 8);
+            ma.pcapm = wq.take<unsigned long long>((size_t)en.cn * (1 + b.maxInner));
+            g.any_top = true;
+        }
+        if (en.Lt2 != en.Lt) {  // the levels between the hand-over and k_cap_top's: k_cap_mid
+            ma.tcapn2 = wq.take<uint32_t>(((size_t)en.cn * 4 << en.Lt2) * 8);
+            ma.tcapm2 = wq.take<unsigned long long>((size_t)en.cn * 4);
+            ma.pcapn2 = wq.take<uint32_t>(((size_t)en.cn * (1 + b.maxInner) << en.Lt2) * 8);
+            ma.pcapm2 = wq.take<unsigned long long>((size_t)en.cn * (1 + b.maxInner));
+            g.any_mid = true;
+        }
+        if (po && po->d_sib) {
+            ma.path_sib = po->d_sib + c0 * 4 * en.G * b.maxM * 8;
+            ma.path_pos = po->d_pos + c0 * 4 * en.G;
+        }
+        if (po && po->d_cols) ma.path_cols = po->d_cols + c0 * 4 * en.G * 64;
+        if (po && po->d_pair_sib) ma.pair_sib = po->d_pair_sib + c0 * (1 + b.maxInner) * en.G * b.maxM * 8;
+        if (po && po->d_pair_cols) ma.pair_cols = po->d_pair_cols + c0 * (1 + b.maxInner) * en.G * 3 * 8;
+        const uint32_t k = g.fp.nb;
+        g.fp.first_block[k] = g.blocks;
+        g.fq.first_block[k] = query_row ? g.blocks_q : g.blocks;
+        g.fm.first_block[k] = g.blocks_m;
+        g.ix_t.first_block[k] = g.top_t;
+        g.ix_p.first_block[k] = g.top_p;
+        g.top_t += grid_for((size_t)en.cn * 4, 256);
+        g.top_p += grid_for((size_t)en.cn * (1 + b.maxInner), 256);
+        g.ix_mt.first_block[k] = g.mid_t;
+        g.ix_mp.first_block[k] = g.mid_p;
+        if (en.Lt2 != en.Lt) {
+            g.mid_t += grid_for((size_t)en.cn * 4 << en.Lt2, 256);
+            g.mid_p += grid_for((size_t)en.cn * (1 + b.maxInner) << en.Lt2, 256);
+        }
+        g.fp.a[k] = PlanArgs{en.cn, pl};
+        g.fq.a[k] = qa;
+        g.fm.a[k] = ma;
+        g.fp.nb = g.fq.nb = g.fm.nb = k + 1;
+        const uint32_t per_block = kBlock / en.G, per_block_m = v.plan.tree_lanes / en.G;
+        g.blocks += (en.cn + per_block - 1) / per_block;
+        g.blocks_m += (en.cn + per_block_m - 1) / per_block_m;
+        if (query_row) g.blocks_q += (en.cn + row_lanes / en.G - 1) / (row_lanes / en.G);
+        g.max_inner = std::max(g.max_inner, b.maxInner);
+        pbmax = std::max<uint32_t>(pbmax, kBlock / en.G);
+    }
+    g.fp.lds_proofs = pbmax;  // (k_plan_par's LDS; the serial k_plan does not see the table)
+    g.fp.first_block[g.fp.nb] = g.blocks;
+    g.fq.first_block[g.fq.nb] = query_row ? g.blocks_q : g.blocks;
+    g.fm.first_block[g.fm.nb] = g.blocks_m;
+    g.ix_t.first_block[g.fm.nb] = g.top_t;
+    g.ix_p.first_block[g.fm.nb] = g.top_p;
+    g.ix_mt.first_block[g.fm.nb] = g.mid_t;
+    g.ix_mp.first_block[g.fm.nb] = g.mid_p;
+    g.plan = rsv::host::plan_group(v.plan, v.in, v.buckets, grp);
+    // which FRI tree each grid row of k_pair_merkle hashes: dealt out over the compute units for a launch that is
+    // resident all at once (host_logic.hpp), the identity otherwise (and with RSV_OPT_PAIR_ORDER = 2)
+    for (uint32_t k = 0; k < 32; k++) g.fm.y_of[k] = (uint8_t)k;
+    if (v.plan.pair_deal)
+        rsv::host::pair_layer_order(g.blocks_m, 1 + g.max_inner, g.plan.live, g.plan.group_M, (uint32_t)v.c->n_cu, (uint32_t)RSV_PAIR_WAVES, g.fm.y_of);
+}
+
+static void launch_plan(VerifyCall& v, const GroupLaunch& g) {
+    v.begin_on(3, v.st);
+    if (v.plan.serial_plan) {
+        for (uint32_t k = 0; k < g.fp.nb; k++)
+            hipLaunchKernelGGL(k_plan, dim3(grid_for(g.fp.a[k].n, 64)), dim3(64), 0, v.st, v.d_blob, v.d_offsets, g.fp.a[k].n, v.metas, v.ctxs, g.fp.a[k].pl);
+    } else {
+        // the row-form quotient constants of a chain-layout batch ride in the plan's launch: their workgroups behind the plan's
+        auto launch = [&](auto kernel, unsigned qconst_blocks, uint32_t qconst_n) {
+            hipLaunchKernelGGL(kernel, dim3(g.blocks + qconst_blocks), dim3(kBlock), plan_lds_bytes(g.fp.lds_proofs), v.st, v.d_blob, v.d_offsets, v.metas,
+                               v.ctxs, g.fp, qconst_n);
+        };
+        v.plan.qconst_in_plan ? launch(k_plan_par<kBlock, true>, qconst_row_blocks(v), qconst_row_n(v)) : launch(k_plan_par<kBlock, false>, 0u, 0u);
+    }
+    v.end_on(v.st);
+}
+
+static void launch_pair_merkle(VerifyCall& v, const GroupLaunch& g, hipStream_t on) {
+    const int form = v.plan.tree_form;
+    v.begin_on(6, on);
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(g.blocks_m, 1 + g.max_inner), dim3(form == 2 ? kRowTreeBlock : kBlock), g.plan.pair_lds, on, g.fm, v.fargs);
+    };
+    if (v.in.flow) form == 2 ? launch(k_pair_merkle<kRowTreeBlock, true, FORM_ROW>) : launch(k_pair_merkle<kBlock, true>);
+    else if (form == 2) launch(k_pair_merkle<kRowTreeBlock, false, FORM_ROW>);
+    else form == 0 ? launch(k_pair_merkle<kBlock, false, 0>) : launch(k_pair_merkle<kBlock, false, 1>);
+    v.end_on(on);
+}
+
+static void launch_trace_merkle(VerifyCall& v, const GroupLaunch& g, hipStream_t on) {
+    const int form = v.plan.tree_form;
+    v.begin_on(5, on);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(g.blocks_m, 4), dim3(form == 2 ? kRowTreeBlock : kBlock), 0, on, g.fm, v.fargs); };
+    if (v.in.flow) form == 2 ? launch(k_trace_merkle<kRowTreeBlock, true, FORM_ROW>) : launch(k_trace_merkle<kBlock, true>);
+    else if (form == 2) launch(k_trace_merkle<kRowTreeBlock, false, FORM_ROW>);
+    else form == 0 ? launch(k_trace_merkle<kBlock, false, 0>) : launch(k_trace_merkle<kBlock, false, 1>);
+    v.end_on(on);
+}
+
+// the last levels of the trees of a kernel, right behind it on its stream (stage 8)
+static void launch_cap(VerifyCall& v, const GroupLaunch& g, hipStream_t on, bool pair) {
+    if (!g.any_top) return;
+    v.begin_on(8, on);
+    // (fast: a small batch's few waves: the permutation instance without wait states, as the tree kernels in front of it)
+    const bool tm = pair ? g.plan.tm_p : g.plan.tm_t, fast = v.plan.tree_form == 0;
+    const uint32_t mid = pair ? g.mid_p : g.mid_t, top = pair ? g.top_p : g.top_t;
+    auto launch = [&](auto kernel, uint32_t blocks, const CapTopIndex& ix) { hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, on, g.fm, ix, pair ? 1u : 0u); };
+    if (g.any_mid && mid) {  // buckets that hand over at the cap level: the levels down to k_cap_top's first
+        const CapTopIndex& ix = pair ? g.ix_mp : g.ix_mt;
+        if (fast) tm ? launch(k_cap_mid<0, true>, mid, ix) : launch(k_cap_mid<0, false>, mid, ix);
+        else tm ? launch(k_cap_mid<1, true>, mid, ix) : launch(k_cap_mid<1, false>, mid, ix);
+    }
+    const CapTopIndex& ix = pair ? g.ix_p : g.ix_t;
+    if (fast) tm ? launch(k_cap_top<0, true>, top, ix) : launch(k_cap_top<0, false>, top, ix);
+    else tm ? launch(k_cap_top<1, true>, top, ix) : launch(k_cap_top<1, false>, top, ix);
+    v.end_on(on);
+}
+
+// (behind the tree kernels in this file: the library keeps its kernels in the order of their first mention)
+static void launch_query(VerifyCall& v, const GroupLaunch& g, hipStream_t on) {
+    const bool row = v.plan.query_row;  // a row of 16 threads per query
+    v.begin_on(4, on);
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(row ? g.blocks_q : g.blocks), dim3(row ? kRowTreeBlock : kBlock), 0, on, g.fq); };
+    if (row) launch(k_query<kRowTreeBlock, 4, true>);
+    else v.plan.chain ? launch(k_query<kBlock, 4>) : launch(k_query<kBlock, 2>);  // chain layout = small batch: the latency form
+    v.end_on(on);
+}
+
+// Stage 4, one group.  k_plan needs only the transcript, k_trace_merkle needs the plan and the row hashes, k_query
+// (quotients + folds) is needed only by k_pair_merkle.
+static int enqueue_group(VerifyCall& v, const std::vector<Entry>& grp) {
+    rsv_ctx* c = v.c;
+    hipStream_t st = v.st;
+    GroupLaunch g{};
+    fill_group(v, grp, g);
+    launch_plan(v, g);
+    HIP_TRY(hipEventRecord(c->ev_plan, st));
+    HIP_TRY(hipStreamWaitEvent(c->side, c->ev_plan, 0));
+    if (v.plan.chain) {
+        // side: trace trees behind the row hashes (same stream) and the plan (event); main: k_query, FRI trees
+        launch_trace_merkle(v, g, c->side);
+        launch_cap(v, g, c->side, false);
+        launch_query(v, g, st);
+        launch_pair_merkle(v, g, st);
+        launch_cap(v, g, st, true);
+        HIP_TRY(hipGetLastError());
+        return RSV_OK;
+    }
+    // k_query on the side stream underneath k_trace_merkle
+    launch_query(v, g, c->side);
+    HIP_TRY(hipEventRecord(c->ev_query, c->side));
+    if (!v.joined) { HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0)); v.joined = true; }
+    if (v.plan.overlap_trees) {
+        launch_pair_merkle(v, g, c->side);
+        launch_cap(v, g, c->side, true);
+    }
+    launch_trace_merkle(v, g, st);
+    if (v.plan.oods_on_main) launch_oods(v, st);  // in front of the trace trees' last levels: underneath the FRI trees
+    launch_cap(v, g, st, false);
+    if (!v.plan.overlap_trees) {
+        HIP_TRY(hipStreamWaitEvent(st, c->ev_query, 0));
+        launch_pair_merkle(v, g, st);
+        launch_cap(v, g, st, true);
+    }
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+// Stages 4 and 5.  The batch is cut into GROUPS of at most MAX_FUSED (bucket, slot range) entries whose workspaces fit the
+// budget together; a group is ONE launch per stage.  A uniform batch is one entry (several groups only when it exceeds
+// the budget), a mixed batch normally one group with an entry per n_queries.
+static int enqueue_query_stages(VerifyCall& v) {
+    rsv_ctx* c = v.c;
+    std::vector<std::vector<Entry>> groups;
+    const size_t need = rsv::host::plan_groups(v.buckets, v.plan.policy, groups);
+    int rc = ensure_buf(c, &c->ws, &c->ws_bytes, need);
+    if (rc != RSV_OK) return rc;
+    rsv::host::plan_launches(v.plan, c->opt, v.in, groups);
+    if (!v.plan.qconst_in_plan) {
+        if (v.plan.chain) launch_qconst(v, v.st);
+        else {
+            HIP_TRY(hipStreamWaitEvent(c->side, c->ev_tr, 0));
+            launch_qconst(v, c->side);
+        }
+    }
+    for (const std::vector<Entry>& grp : groups) {
+        rc = enqueue_group(v, grp);
+        if (rc != RSV_OK) return rc;
+    }
+    if (!v.plan.oods_on_main) launch_oods(v, c->side);
+    HIP_TRY(hipEventRecord(c->ev_scan, c->side));
+    return RSV_OK;
+}
+
+// Stage 6: verdicts (+ the canonicity fallback for proofs whose witness lists some stage found of the wrong length, + the
+// accept bitmap when the caller asked for it): ONE launch behind the Merkle stages
+static int enqueue_finalize(VerifyCall& v) {
+    const PathsOut* po = v.po;
+    if (v.live) HIP_TRY(hipStreamWaitEvent(v.st, v.c->ev_scan, 0));
+    v.begin_on(7, v.st);
+    hipLaunchKernelGGL(k_finalize, dim3(grid_for(v.N, 256)), dim3(256), 0, v.st, v.d_blob, v.d_offsets, v.N, v.metas, v.ctxs, v.d_accept, v.d_reason, 0u,
+                       po ? po->d_bitmap : nullptr, reinterpret_cast<unsigned long long*>(po ? po->d_count : nullptr));
+    v.end_on(v.st);
+    if (po && po->d_transcript)  // behind every stage that can find a non-canonical word: such a proof's row says RSV_R_PARSE
+        hipLaunchKernelGGL(k_export_transcript, dim3(grid_for((size_t)v.N * TR_WORDS, 256)), dim3(256), 0, v.st, v.N, v.metas, v.ctxs, po->d_transcript);
+    HIP_TRY(hipGetLastError());
+    return RSV_OK;
+}
+
+// The shared table of public inputs, the outputs that start from zero, and the whole-batch records.
+static int enqueue_inputs(VerifyCall& v, const rsv_public_input* pi) {
+    rsv_ctx* c = v.c;
+    hipStream_t st = v.st;
+    const PathsOut* po = v.po;
+    const uint32_t N = v.N;
+    const size_t n_pi = v.n_pi;
+    const bool own = v.in.own;
+    if (c->d_pi_cap < n_pi + 1) {
+        if (c->d_pi) (void)hipFree(c->d_pi);
+        c->d_pi = nullptr;
+        c->d_pi_cap = 0;
+        HIP_TRY(hipMalloc((void**)&c->d_pi, sizeof(rsv_public_input) * (n_pi + 16)));
+        c->d_pi_cap = n_pi + 16;
+    }
+    if (c->opt.ws_fill) {  // in front of the copy (the shared table) or of nothing (per-proof inputs never read it)
+        const int rcf = ws_fill(c, c->d_pi, sizeof(rsv_public_input) * c->d_pi_cap);
+        if (rcf != RSV_OK) return rcf;
+    }
+    if (n_pi && !own) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
+    // rsv_hints_out::d_query_values: "absent groups, and the rows of a proof the parser rejected, are zero" holds for the caller's buffer as it is
+    if (po && po->d_count) HIP_TRY(hipMemsetAsync(po->d_count, 0, 8, st));
+    if (po && po->d_qv)
+        HIP_TRY(hipMemsetAsync(po->d_qv, 0, (size_t)N * po->n_queries * 4 * (8 + (size_t)po->n_inner) * sizeof(uint32_t), st));
+    static_assert(sizeof(rsv_public_input) == sizeof(PubInput), "layout");
+
+    // whole-batch records (their own allocation: growing the per-query workspace never moves them)
+    const size_t pi_sum_words = own ? 4 * (size_t)N : 0;
+    auto carve_fixed = [&](Carve& cv) {
+        v.summary = cv.take<uint32_t>(64);
+        v.metas = cv.take<ProofMeta>(N);
+        v.ctxs = cv.take<ProofCtx>(N);
+        v.d_shape = cv.take<uint32_t>(2 * (size_t)N);
+        v.d_ids = cv.take<uint32_t>(N);
+        v.d_classes = cv.take<ClassTable>(1);
+        v.d_cls = cv.take<uint8_t>(N);
+        v.d_pi_sum = cv.take<uint32_t>(pi_sum_words);
+    };
+    Carve probe{nullptr};
+    carve_fixed(probe);
+    const int rc = ensure_buf(c, &c->ws_fixed, &c->ws_fixed_bytes, probe.off);
+    if (rc != RSV_OK) return rc;
+    Carve cv{static_cast<char*>(c->ws_fixed)};
+    carve_fixed(cv);
+    c->last_metas = v.metas;
+    return RSV_OK;
 }
 
 static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                        const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, const rsv_public_input* d_own_pi,
                        uint8_t* d_accept, uint8_t* d_reason, const PathsOut* po) {
     // d_own_pi: nullptr — `pi` is the batch's one table, in host memory; else [n][n_pi] records in HBM, every proof its own
-    // (`pi` is unused): k_pi_sum sums them per proof and the OODS kernel reads that sum (k_pi_sum.hpp)
+    // (`pi` is unused)
     if (!c) return RSV_E_NULL;
-    CfgSet co;
+    VerifyCall v{};
     {
-        int rc0 = make_cfg_set(cfg, &co);  // required even for an empty batch: a caller that forgot it learns at once
+        int rc0 = make_cfg_set(cfg, &v.co);  // required even for an empty batch: a caller that forgot it learns at once
         if (rc0 != RSV_OK) return rc0;
     }
     if (n == 0) return RSV_OK;
@@ -194,530 +707,32 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
         for (int k = 0; k < 4; k++)
             if (pi[i].value[k] >= RSV_M31_P) return RSV_E_RANGE;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const Options opt = c->opt;
-    VerifyState* vs = state_of(c);
-    vs->clock.used = 0;
-    vs->spans.clear();
-    // Stage clock: opt-in (RSV_OPT_STAGE_TIMES).  Two event records around a stage cost ~8 us of queue time EACH STAGE
-    // (tools/chain_lab.hip: 5.3 us per dependent empty launch, 13.3 with the two records) — on a small batch's chain of
-    // seven stages that was 4 % of the call, paid by every caller for a diagnostic only bench.py reads.
-    const bool timing = opt.stage_times == 1;
-    auto begin_on = [&](int stage, hipStream_t on) {
-        if (!timing) return;
-        hipEvent_t b = vs->clock.next();
-        if (b) (void)hipEventRecord(b, on);
-        vs->spans.push_back({stage, b, nullptr});
-    };
-    auto end_on = [&](hipStream_t on) {
-        if (!timing) return;
-        hipEvent_t e = vs->clock.next();
-        if (e) (void)hipEventRecord(e, on);
-        for (size_t i = vs->spans.size(); i-- > 0;)  // the span opened last and not yet closed
-            if (!vs->spans[i].e) { vs->spans[i].e = e; break; }
-    };
-    auto begin = [&](int stage) { begin_on(stage, st); };
-    auto end = [&]() { end_on(st); };
-
     const uint32_t N = (uint32_t)n;
-    // public inputs
-    if (c->d_pi_cap < n_pi + 1) {
-        if (c->d_pi) (void)hipFree(c->d_pi);
-        c->d_pi = nullptr;
-        c->d_pi_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_pi, sizeof(rsv_public_input) * (n_pi + 16)));
-        c->d_pi_cap = n_pi + 16;
-    }
-    if (opt.ws_fill) {  // in front of the copy (the shared table) or of nothing (per-proof inputs never read it)
-        const int rcf = ws_fill(c, c->d_pi, sizeof(rsv_public_input) * c->d_pi_cap);
-        if (rcf != RSV_OK) return rcf;
-    }
-    if (n_pi && !own) HIP_TRY(hipMemcpyAsync(c->d_pi, pi, sizeof(rsv_public_input) * n_pi, hipMemcpyHostToDevice, st));
-    // rsv_hints_out::d_query_values: "absent groups, and the rows of a proof the parser rejected, are zero" holds for the caller's buffer as it is
-    if (po && po->d_count) HIP_TRY(hipMemsetAsync(po->d_count, 0, 8, st));
-    if (po && po->d_qv)
-        HIP_TRY(hipMemsetAsync(po->d_qv, 0, (size_t)N * po->n_queries * 4 * (8 + (size_t)po->n_inner) * sizeof(uint32_t), st));
-    static_assert(sizeof(rsv_public_input) == sizeof(PubInput), "layout");
-
-    // whole-batch records (their own allocation: growing the per-query workspace never moves them)
-    Carve fixed{nullptr};
-    fixed.take<uint32_t>(64);
-    fixed.take<ProofMeta>(N);
-    fixed.take<ProofCtx>(N);
-    fixed.take<uint32_t>(2 * (size_t)N);
-    fixed.take<uint32_t>(N);
-    fixed.take<ClassTable>(1);
-    fixed.take<uint8_t>(N);
-    fixed.take<uint32_t>(own ? 4 * (size_t)N : 0);
-    int rc = ensure_buf(c, &c->ws_fixed, &c->ws_fixed_bytes, fixed.off);
-    if (rc != RSV_OK) return rc;
-    Carve cv{static_cast<char*>(c->ws_fixed)};
-    uint32_t* summary = cv.take<uint32_t>(64);
-    ProofMeta* metas = cv.take<ProofMeta>(N);
-    c->last_metas = metas;
-    ProofCtx* ctxs = cv.take<ProofCtx>(N);
-    uint32_t* d_shape = cv.take<uint32_t>(2 * (size_t)N);
-    uint32_t* d_ids = cv.take<uint32_t>(N);
-    ClassTable* d_classes = cv.take<ClassTable>(1);
-    uint8_t* d_cls = cv.take<uint8_t>(N);
-    uint32_t* d_pi_sum = cv.take<uint32_t>(own ? 4 * (size_t)N : 0);  // k_pi_sum -> k_oods<PiOwn>
-
-    // small batches: one proof per 16-lane DPP row (latency form of the transcript); large ones: one proof per lane
-    // (throughput form).  RSV_OPT_TRANSCRIPT_FORM overrides (tests).
-    bool row = N <= 24576;  // measured crossover on MI355X: 16 384 proofs 1.41 M/s (row) vs 1.26 M/s (lane), 32 768: 1.32 vs 1.36
-    if (opt.transcript_form) row = opt.transcript_form == 1;
     const bool flow = po && po->flow.rec;
-    const FlowArgs fargs = flow ? po->flow : FlowArgs{nullptr, nullptr, nullptr, 0};
-    if (flow) {
-        if (fargs.count) HIP_TRY(hipMemsetAsync(fargs.count, 0, sizeof(uint32_t) * (size_t)N, st));
-    }
-    // Up to one wave per SIMD (4 096 proofs) the row form runs as two launches: the front half needs nothing from the
-    // parser and starts next to it on the aux stream (k_transcript.hpp): 1 024 proofs 1.67 -> 1.63 ms, 4 096 2.89 -> 2.82;
-    // at 8 192 it is a wash and beyond that the two halves and the parser get in each other's way (12 288: +12 %).
-    // RSV_OPT_TRANSCRIPT_SPLIT overrides (tests).  The lane form (large batches) always runs as one launch (split the same
-    // way, it measured 35.46 vs 35.20 ms at 65 536 proofs: inside run-to-run noise), and so does a pass that writes the flow.
-    const bool split = row && !flow && (opt.transcript_split ? opt.transcript_split == 2 : N <= 4096);
-    // Split: the PARSER goes to the aux stream and the front half stays on the main stream, in front of the back half — the
-    // parser (0.04-0.1 ms) is long over when the front half (0.16-0.19 ms) ends, so the back half's wait for it is a wait
-    // for an event signalled long ago, and front -> back is a boundary inside one stream (~5 us) instead of a fresh
-    // cross-stream wait (15 us; until the end of round 4 the front half was the one on the aux stream).
-    hipStream_t parse_on = split ? c->aux : st;
-    if (split) {
-        HIP_TRY(hipEventRecord(c->ev_begin, st));  // behind whatever produced the blob, the offsets and the inputs
-        HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_begin, 0));
-    }
-    begin_on(0, parse_on);
-    HIP_TRY(hipMemsetAsync(summary, 0, 256, parse_on));
-    hipLaunchKernelGGL(k_parse, dim3(grid_for(N, 64)), dim3(64), 0, parse_on, d_blob, d_offsets, N, co, metas, ctxs, summary, d_shape);
-    end_on(parse_on);
-    HIP_TRY(hipGetLastError());
-    // The transcript needs nothing from the host: it is enqueued right behind the parser, and the parse summary
-    // (and, for mixed batches, the shape words) travel back through the side stream while it runs.
-    HIP_TRY(hipEventRecord(c->ev_fork, parse_on));
-    if (split) {
-        hipLaunchKernelGGL(k_transcript_row<1>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_fork, 0));  // everything behind this on the main stream may read the parser's tables
-    }
-    begin(1);
-    if (split)
-        hipLaunchKernelGGL(k_transcript_row<2>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else if (row && flow)
-        hipLaunchKernelGGL((k_transcript_row<0, true>), dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else if (row)
-        hipLaunchKernelGGL(k_transcript_row<0>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else if (flow)
-        hipLaunchKernelGGL(k_transcript<true>, dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else if (N <= 49152)  // (one wave per SIMD: the unpaced channel, k_transcript.hpp)
-        hipLaunchKernelGGL((k_transcript<false, false>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    else
-        hipLaunchKernelGGL((k_transcript<false, true>), dim3(grid_for(N, 64)), dim3(64), 0, st, d_blob, d_offsets, N, metas, ctxs, fargs);
-    end();
-    HIP_TRY(hipEventRecord(c->ev_tr, st));
-    HIP_TRY(hipGetLastError());
-    uint32_t sum[8] = {0};
-    HIP_TRY(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-    // A batch under ONE configuration is one launch geometry of known size (n_queries is the configuration's, every
-    // proof either carries it or is rejected by the parser): nothing has to come back to the host.  The slot order by
-    // shape class is made on the device (k_parse.hpp) and the tables are sized for the largest trees the parser lets
-    // through, so the call enqueues everything and returns: no host synchronisation anywhere in it.  Batches under
-    // several configurations (several n_queries buckets whose sizes only the device knows) and calls with per-query path
-    // outputs (one declared shape, checked on the host) keep the round trip of rounds 1-2 below.
-    const bool device_order = co.n == 1 && !co.cfg_of && !(po && po->paths()) && opt.device_order != 2 && co.c[0][3] >= 1 &&
-                              co.c[0][3] <= (uint32_t)MAXQ && co.c[0][1] >= 1 && co.c[0][1] <= 16 && co.c[0][2] <= 16;
-    if (device_order) {
-        HIP_TRY(hipMemsetAsync(d_classes, 0, sizeof(ClassTable), c->side));
-        hipLaunchKernelGGL(k_classify, dim3(grid_for(N, CLASSIFY_PER_BLOCK)), dim3(256), 0, c->side, N, d_shape, d_classes, d_cls);
-        hipLaunchKernelGGL(k_class_offsets, dim3(1), dim3(64), 0, c->side, d_classes);
-        hipLaunchKernelGGL(k_scatter_ids, dim3(grid_for(N, 256)), dim3(256), 0, c->side, N, d_cls, d_classes, d_ids);
-        sum[0] = 1;
-    } else {
-        HIP_TRY(hipMemcpyAsync(sum, summary, 32, hipMemcpyDeviceToHost, c->side));
-        HIP_TRY(hipStreamSynchronize(c->side));
-    }
+    v.c = c; v.st = c->stream; v.vs = state_of(c);
+    v.d_blob = d_blob; v.d_offsets = d_offsets; v.N = N; v.n_pi = n_pi; v.d_own_pi = d_own_pi;
+    v.d_accept = d_accept; v.d_reason = d_reason; v.po = po;
+    v.fargs = flow ? po->flow : FlowArgs{nullptr, nullptr, nullptr, 0};
+    v.timing = c->opt.stage_times == 1;
+    v.vs->clock.used = 0;
+    v.vs->spans.clear();
+    v.in = rsv::host::PlanInputs{N, v.co.n, v.co.cfg_of != nullptr, v.co.c[0][1], v.co.c[0][2], v.co.c[0][3], flow, po && po->paths(),
+                                 po && po->d_sib, po && po->d_pair_sib, own, (size_t)MAX_FUSED};
+    v.plan = rsv::host::plan_batch(c->opt, v.in);
 
-    // A batch whose FRI-tree launch puts fewer than about two and a half waves on a SIMD (at most 1 024 proofs of 16 queries
-    // and nine trees; measured: one proof 1.31 -> 1.21 ms, 512 proofs 1.43 -> 1.34, 768: 1.45 -> 1.35, 1 024: 1.467 -> 1.457,
-    // 2 048: 1.906 -> 1.945, slower) runs the
-    // tree kernels on the unpaced permutation instances.  An estimate from the configuration (the batch's real depth is on
-    // the device only): proofs x queries x (FRI trees of the common depth M = 22).
-    // Up to 256 proofs of 16 queries the trees go one step further, to the ROW form on virtual lanes (k_merkle.hpp): 16 threads per
-    // path, every permutation shared by a DPP row.  RSV_OPT_TREE_PACE overrides (1 paced, 2 unpaced, 3 row).
-    int tree_form = 1;  // the PACE / FORM template argument of the tree kernels: 1 paced, 0 unpaced, 2 row
-    {
-        const uint32_t nq_est = co.c[0][3] < 4 ? 4u : co.c[0][3], fold_est = co.c[0][1] + co.c[0][2];
-        const uint64_t lanes = (uint64_t)N * nq_est * (22u > fold_est ? 22u - fold_est : 1u);
-        if (opt.tree_pace) tree_form = opt.tree_pace == 1 ? 1 : (opt.tree_pace == 2 ? 0 : 2);
-        else if (co.n == 1 && lanes <= (uint64_t)kRowTreeLanes) tree_form = 2;
-        else if (co.n == 1 && lanes <= 1024ull * 16 * 9) tree_form = 0;
-        if (flow && tree_form == 0) tree_form = 1;  // (the FLOW instantiations: paced lane form and row form)
-    }
-    const bool small_trees = tree_form != 1;  // (the row hashes: lane forms only; they run underneath the transcript)
-    if (sum[0] > 0) {
-        // shape buckets: one launch geometry per distinct n_queries (host_logic.hpp)
-        using rsv::host::Bucket;
-        std::vector<Bucket> buckets;
-        const bool uniform = !device_order && sum[4] == ~sum[5] && sum[6] == ~sum[7];
-        if (device_order) {
-            // every slot of the batch (rejected proofs have no live lane), the deepest trees the parser admits
-            const uint32_t b = co.c[0][1], last = co.c[0][2];
-            const uint32_t inner_bound = (uint32_t)MAX_LOG - 1u - (last + b);
-            buckets.push_back({co.c[0][3], (uint32_t)MAX_LOG, inner_bound > (uint32_t)MAX_INNER ? (uint32_t)MAX_INNER : inner_bound, last + b + 1u, N, 0});
-        } else
-        if (po && po->paths() && (!uniform || (sum[4] & 0xFFu) != po->n_queries || ((sum[4] >> 8) & 0xFFu) != po->max_log || po->n_queries < 4 ||
-                   ((po->d_pair_sib || po->d_pair_cols || po->d_qv) && ((sum[4] >> 16) & 0xFFu) != po->n_inner)))
-            return RSV_E_SIZE;  // path emission needs one shape for the whole batch, as declared by the caller
-        if (device_order) {
-        } else if (uniform) {
-            buckets.push_back({sum[4] & 0xFFu, (sum[4] >> 8) & 0xFFu, (sum[4] >> 16) & 0xFFu, sum[4] >> 24, N, 0});
-        } else {
-            // Mixed batch: 8 bytes per proof come back, the host buckets them (rsv::host::bucket_by_shape) and uploads the
-            // slot -> proof list.
-            std::vector<uint32_t>& shape = vs->h_shape;
-            shape.resize(2 * (size_t)N);
-            HIP_TRY(hipMemcpyAsync(shape.data(), d_shape, 8 * (size_t)N, hipMemcpyDeviceToHost, c->side));
-            HIP_TRY(hipStreamSynchronize(c->side));
-            std::vector<uint32_t>& ids = vs->h_ids;
-            rsv::host::bucket_by_shape(shape.data(), N, buckets, ids, vs->h_class);
-            if (!ids.empty()) HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), 4 * ids.size(), hipMemcpyHostToDevice, c->side));
-        }
-        // the slot -> proof list was uploaded on the side stream: k_plan (main stream) waits for it
-        HIP_TRY(hipEventRecord(c->ev_ids, c->side));
-        HIP_TRY(hipStreamWaitEvent(st, c->ev_ids, 0));
-        HIP_TRY(hipGetLastError());
-        // Side stream: trace-tree column hashing (independent of the transcript), so that it fills the issue slots the
-        // one-wave-per-SIMD transcript kernel leaves idle.  Row hashes are addressed by SLOT and sized per bucket
-        // (count x that bucket's n_queries): one well-formed 128-query header in a batch of 16-query proofs must not
-        // inflate the allocation of the whole batch.  All buckets go into ONE launch (Fused<>, at most MAX_FUSED each).
-        std::vector<size_t> row_base(buckets.size());
-        size_t row_words = 0;
-        for (size_t bi = 0; bi < buckets.size(); bi++) {
-            const uint32_t gq = buckets[bi].G < 4 ? 4u : buckets[bi].G;
-            row_base[bi] = row_words;
-            row_words += (size_t)buckets[bi].count * 4 * 2 * gq * 8;
-        }
-        rc = ensure_buf(c, &c->ws_rows, &c->ws_rows_bytes, row_words * 4);
+    int rc = enqueue_inputs(v, pi);
+    if (rc != RSV_OK) return rc;
+    rc = enqueue_parse_transcript(v);
+    if (rc != RSV_OK) return rc;
+    rc = enqueue_slot_order(v);
+    if (rc != RSV_OK) return rc;
+    if (v.live) {
+        rc = enqueue_row_hashes(v);
         if (rc != RSV_OK) return rc;
-        uint32_t* rowh = static_cast<uint32_t*>(c->ws_rows);
-        {
-            begin_on(9, c->side);
-            for (size_t b0 = 0; b0 < buckets.size(); b0 += MAX_FUSED) {
-                Fused<RowHashArgs> fr{};
-                uint32_t blocks = 0;
-                for (size_t bi = b0; bi < buckets.size() && bi < b0 + MAX_FUSED; bi++) {
-                    const Bucket& b = buckets[bi];
-                    const uint32_t gq = b.G < 4 ? 4u : b.G;
-                    fr.first_block[fr.nb] = blocks;
-                    fr.a[fr.nb++] = RowHashArgs{d_blob, d_offsets, b.count, gq, metas, rowh + row_base[bi], uniform ? nullptr : d_ids + b.first, ctxs};
-                    blocks += grid_for((size_t)b.count * gq, kBlock);
-                }
-                fr.first_block[fr.nb] = blocks;
-                // a small batch's launches leave a wave nearly alone on its SIMD: the unpaced permutation instances (poseidon2.hpp)
-                if (small_trees) hipLaunchKernelGGL(k_row_hash<false>, dim3(blocks, 4), dim3(kBlock), 0, c->side, fr);
-                else hipLaunchKernelGGL(k_row_hash<true>, dim3(blocks, 4), dim3(kBlock), 0, c->side, fr);
-            }
-            end_on(c->side);
-            HIP_TRY(hipEventRecord(c->ev_join, c->side));
-        }
-        // query-independent quotient constants: need only the transcript (launched below, once the stream layout is known)
-        // the row form of the quotient constants on four rows per proof (k_plan.hpp: qconst_row_body); RSV_OPT_QCONST_FORM = 1
-        // forces the row form with ONE row per proof (what batches of 4 097 .. 24 576 proofs run), so that tests reach it
-        const bool qconst4 = N <= 4096 && opt.qconst_form != 1;
-        auto launch_qconst = [&](hipStream_t on) {
-            begin_on(10, on);
-            // small batches: one proof per 16-lane row (latency form); RSV_OPT_QCONST_FORM overrides (tests)
-            const bool qrow = opt.qconst_form ? opt.qconst_form == 1 : N <= 24576;
-            if (qrow)
-                hipLaunchKernelGGL(k_qconst_row, dim3(grid_for((size_t)N * (qconst4 ? 64 : 16), 256)), dim3(256), 0, on, d_blob, d_offsets,
-                                   N | (qconst4 ? 0x80000000u : 0u), metas, ctxs);
-            else
-                hipLaunchKernelGGL(k_qconst, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs);
-            end_on(on);
-        };
-
-        bool oods_launched = false;
-        auto launch_oods = [&](hipStream_t on) {
-            begin_on(2, on);
-            const PiShared shared{reinterpret_cast<const PubInput*>(c->d_pi), (uint32_t)n_pi};
-            const PiOwn sums{d_pi_sum};
-            // per-proof inputs: the statement sums first, on the same stream (behind the transcript, as the OODS kernel is)
-            if (own)
-                hipLaunchKernelGGL(k_pi_sum<true>, dim3(grid_for(N, PI_WAVES)), dim3(64 * PI_WAVES), 0, on, reinterpret_cast<const uint32_t*>(d_own_pi),
-                                   N, (uint32_t)n_pi, metas, ctxs, (const uint32_t*)nullptr, d_pi_sum, (uint8_t*)nullptr);
-            if (oods_row_form(opt, N)) {
-                if (own) hipLaunchKernelGGL(k_oods_row<PiOwn>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, on, d_blob, d_offsets, N, metas, ctxs, sums);
-                else hipLaunchKernelGGL(k_oods_row<PiShared>, dim3(grid_for((size_t)N * 16, 256)), dim3(256), 0, on, d_blob, d_offsets, N, metas, ctxs, shared);
-            } else {
-                if (own) hipLaunchKernelGGL(k_oods<PiOwn>, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs, sums);
-                else hipLaunchKernelGGL(k_oods<PiShared>, dim3(grid_for(N, 64)), dim3(64), 0, on, d_blob, d_offsets, N, metas, ctxs, shared);
-            }
-            end_on(on);
-            oods_launched = true;
-        };
-
-        // Per-query stages.  The batch is cut into GROUPS of at most MAX_FUSED (bucket, slot range) entries whose
-        // workspaces fit the budget together; a group is ONE launch per stage.  A uniform batch is one entry (several
-        // groups only when it exceeds the budget), a mixed batch normally one group with an entry per n_queries.
-        using rsv::host::Entry;
-        // The top of the cap in its own kernel (k_cap_top: one lane per tree instead of a part-filled wave per workgroup):
-        // fewer permutation slots, two more launches — from 1 024 proofs on (measured: 1 024 proofs 1.663 -> 1.652 ms, 16 384: 9.98 -> 9.84, 65 536: 34.96 -> 34.37; a single proof would wait for three sequential hashes of a 17-lane launch),
-        // and not while per-query paths are emitted (the cap writes the top of every path as it goes).
-        const bool cap_top = !(po && (po->d_sib || po->d_pair_sib)) && (opt.cap_top ? opt.cap_top == 1 : N >= 1024);
-        std::vector<std::vector<Entry>> groups;
-        const rsv::host::GroupPolicy policy{ws_budget(c), (size_t)MAX_FUSED, opt.tree_cap == 2, flow, opt.flow_cap == 2, cap_top, opt.cap_mid};
-        const size_t need = rsv::host::plan_groups(buckets, policy, groups);
-        rc = ensure_buf(c, &c->ws, &c->ws_bytes, need);
+        rc = enqueue_query_stages(v);
         if (rc != RSV_OK) return rc;
-
-        // Per group.  k_plan needs only the transcript, k_trace_merkle needs the plan and the row hashes, k_query
-        // (quotients + folds) is needed only by k_pair_merkle: it runs on the side stream underneath k_trace_merkle.
-        bool joined = false;
-        const bool serial_plan = opt.plan_form == 2;  // one-lane-per-proof original (tests)
-        for (const std::vector<Entry>& grp : groups)
-            for (const Entry& en : grp)
-                if (tree_form == 2 && en.G > (uint32_t)kRowTreeBlock / 16u) tree_form = flow ? 1 : 0;  // more queries than virtual lanes in a workgroup
-        const uint32_t tree_lanes = tree_form == 2 ? (uint32_t)kRowTreeBlock / 16u : (uint32_t)kBlock;  // lanes of the tree kernels' indexing per workgroup
-        // The FRI trees go to the SIDE stream right behind k_query (the only thing they wait for) and run next to the
-        // trace trees instead of after them; the two kernels that only feed k_finalize (OODS check, canonicity scan)
-        // follow the trace trees on the main stream.  A small batch leaves most of the chip idle and its step is a
-        // chain of dependent kernels, so the overlap shortens it (1 024 proofs -3 %, 2 048 -4 %, 8 192 -2.4 %); a
-        // large one fills the chip with either kernel and gains 0.4 % (65 536 proofs: 35.7 vs 35.9 ms).  Batches cut
-        // into several groups keep the serial order: the groups share one workspace.
-        bool overlap_trees = groups.size() == 1;
-        if (opt.overlap_trees == 2) overlap_trees = false;
-        // Stream layout of a single-group batch.  "Chain" (RSV_OPT_CRITICAL_CHAIN): every kernel the verdict waits for
-        // longest sits on ONE stream, in order — transcript, quotient constants, plan, k_query, FRI trees, finalize — and
-        // the side stream takes what finishes early anyway (row hashes, then — behind the plan — trace trees and the OODS
-        // check).  A kernel that waits for another stream's event starts ~20 us after it (measured on MI355X: 18-28 us
-        // against 5-11 us behind a kernel of its own stream); the two-stream layout of rounds 1-2 had three such waits
-        // on the path of a small batch (transcript -> k_qconst, k_plan -> k_query, FRI trees -> finalize).
-        const bool chain = overlap_trees && (opt.critical_chain ? opt.critical_chain == 1 : N <= 24576);  // measured: +1..4 % from 512 to 16 384 proofs, -2 % at 32 768 and beyond
-        // the row-form quotient constants of a chain-layout batch ride in the plan's launch (k_plan_par<.., true>)
-        // k_query on virtual lanes (k_query.hpp: 16 threads per query split its sums): RSV_OPT_QUERY_FORM, or by size
-        bool query_row = chain && (opt.query_form ? opt.query_form == 1 : (uint64_t)N * (co.c[0][3] < 4 ? 4u : co.c[0][3]) <= (uint64_t)kRowQueryLanes && co.n == 1);
-        for (const std::vector<Entry>& grp : groups)
-            for (const Entry& en : grp)
-                if (en.G > (uint32_t)kRowTreeBlock / 16u) query_row = false;
-        const bool qconst_in_plan = chain && !serial_plan && (opt.qconst_form ? opt.qconst_form == 1 : N <= 24576);
-        if (qconst_in_plan) {
-        } else if (chain) launch_qconst(st);
-        else {
-            HIP_TRY(hipStreamWaitEvent(c->side, c->ev_tr, 0));
-            launch_qconst(c->side);
-        }
-        for (const std::vector<Entry>& grp : groups) {
-            Fused<PlanArgs> fp{};
-            Fused<QueryArgs> fq{};
-            Fused<MerkleArgs> fm{};
-            CapTopIndex ix_t{}, ix_p{}, ix_mt{}, ix_mp{};
-            uint32_t blocks = 0, blocks_m = 0, blocks_q = 0, max_inner = 0, top_t = 0, top_p = 0, mid_t = 0, mid_p = 0;  // blocks_m / _q: workgroups of the tree kernels / of k_query's row form
-            bool any_top = false, any_mid = false;
-            Carve wq{static_cast<char*>(c->ws)};
-            for (const Entry& en : grp) {
-                const Bucket& b = buckets[en.bi];
-                PlanPtrs pl{};
-                pl.hdr = wq.take<PlanHdr>(en.cn);
-                pl.ent = wq.take<uint32_t>((size_t)en.cn * (b.maxM + 1) * en.G);
-                pl.fl = wq.take<uint32_t>((size_t)en.cn * 2 * en.G);
-                pl.G = en.G;
-                pl.maxM = b.maxM;
-                uint32_t* leafv = wq.take<uint32_t>((size_t)en.cn * (3 + b.maxInner) * en.G * 8);
-                pl.ids = uniform ? nullptr : d_ids + b.first + en.c0;
-                pl.p0 = uniform ? (uint32_t)en.c0 : 0u;
-                const size_t c0 = en.c0;
-                QueryArgs qa{d_blob, d_offsets, en.cn, metas, ctxs, pl, leafv, b.maxInner,
-                             (po && po->d_folded) ? po->d_folded + c0 * 3 * en.G * 4 : nullptr,
-                             (po && po->d_qv) ? po->d_qv + c0 * en.G * 4 * (8 + b.maxInner) : nullptr, 4 * (8 + b.maxInner)};
-                MerkleArgs ma{d_blob, d_offsets, en.cn, metas, ctxs, pl, leafv, b.maxInner, en.Lc,
-                              rowh + row_base[en.bi] + c0 * 4 * 2 * (size_t)en.G * 8, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              en.Lt, en.Lt2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-                if (en.Lt) {
-                    ma.tcapn = wq.take<uint32_t>(((size_t)en.cn * 4 << en.Lt) * 8);
-                    ma.tcapm = wq.take<unsigned long long>((size_t)en.cn * 4);
-                    ma.pcapn = wq.take<uint32_t>(((size_t)en.cn * (1 + b.maxInner) << en.Lt) * 8);
-                    ma.pcapm = wq.take<unsigned long long>((size_t)en.cn * (1 + b.maxInner));
-                    any_top = true;
-                }
-                if (en.Lt2 != en.Lt) {  // the levels between the hand-over and k_cap_top's: k_cap_mid
-                    ma.tcapn2 = wq.take<uint32_t>(((size_t)en.cn * 4 << en.Lt2) * 8);
-                    ma.tcapm2 = wq.take<unsigned long long>((size_t)en.cn * 4);
-                    ma.pcapn2 = wq.take<uint32_t>(((size_t)en.cn * (1 + b.maxInner) << en.Lt2) * 8);
-                    ma.pcapm2 = wq.take<unsigned long long>((size_t)en.cn * (1 + b.maxInner));
-                    any_mid = true;
-                }
-                if (po && po->d_sib) {
-                    ma.path_sib = po->d_sib + c0 * 4 * en.G * b.maxM * 8;
-                    ma.path_pos = po->d_pos + c0 * 4 * en.G;
-                }
-                if (po && po->d_cols) ma.path_cols = po->d_cols + c0 * 4 * en.G * 64;
-                if (po && po->d_pair_sib) ma.pair_sib = po->d_pair_sib + c0 * (1 + b.maxInner) * en.G * b.maxM * 8;
-                if (po && po->d_pair_cols) ma.pair_cols = po->d_pair_cols + c0 * (1 + b.maxInner) * en.G * 3 * 8;
-                const uint32_t k = fp.nb;
-                fp.first_block[k] = blocks;
-                fq.first_block[k] = query_row ? blocks_q : blocks;
-                fm.first_block[k] = blocks_m;
-                ix_t.first_block[k] = top_t;
-                ix_p.first_block[k] = top_p;
-                top_t += grid_for((size_t)en.cn * 4, 256);
-                top_p += grid_for((size_t)en.cn * (1 + b.maxInner), 256);
-                ix_mt.first_block[k] = mid_t;
-                ix_mp.first_block[k] = mid_p;
-                if (en.Lt2 != en.Lt) {
-                    mid_t += grid_for((size_t)en.cn * 4 << en.Lt2, 256);
-                    mid_p += grid_for((size_t)en.cn * (1 + b.maxInner) << en.Lt2, 256);
-                }
-                fp.a[k] = PlanArgs{en.cn, pl};
-                fq.a[k] = qa;
-                fm.a[k] = ma;
-                fp.nb = fq.nb = fm.nb = k + 1;
-                const uint32_t per_block = kBlock / en.G, per_block_m = tree_lanes / en.G;
-                blocks += (en.cn + per_block - 1) / per_block;
-                blocks_m += (en.cn + per_block_m - 1) / per_block_m;
-                if (query_row) blocks_q += (en.cn + (uint32_t)kRowTreeBlock / 16u / en.G - 1) / ((uint32_t)kRowTreeBlock / 16u / en.G);
-                max_inner = std::max(max_inner, b.maxInner);
-            }
-            fp.first_block[fp.nb] = blocks;
-            fq.first_block[fq.nb] = query_row ? blocks_q : blocks;
-            fm.first_block[fm.nb] = blocks_m;
-            {   // which FRI tree each grid row of k_pair_merkle hashes: dealt out over the compute units for a launch that is
-                // resident all at once (host_logic.hpp), the identity otherwise (and with RSV_OPT_PAIR_ORDER = 2)
-                uint32_t group_M = 0, live = 1 + max_inner;
-                for (const Entry& en : grp) group_M = std::max(group_M, buckets[en.bi].maxM);
-                if (device_order) {
-                    // the launch is sized for MAX_LOG; what the batch really holds is on the device only.  The weights assume
-                    // the common depth of the reference's proofs (M = 22): a batch of deeper or shallower trees is still dealt
-                    // out better than row y = tree y, and any order is a correct one.
-                    group_M = 22;
-                    const uint32_t fold = co.c[0][1] + co.c[0][2];
-                    live = group_M > fold ? group_M - fold : 1u;
-                }
-                for (uint32_t k = 0; k < 32; k++) fm.y_of[k] = (uint8_t)k;
-                if (opt.pair_order != 2)
-                    rsv::host::pair_layer_order(blocks_m, 1 + max_inner, live, group_M, (uint32_t)c->n_cu, (uint32_t)RSV_PAIR_WAVES, fm.y_of);
-            }
-            ix_t.first_block[fm.nb] = top_t;
-            ix_p.first_block[fm.nb] = top_p;
-            ix_mt.first_block[fm.nb] = mid_t;
-            ix_mp.first_block[fm.nb] = mid_p;
-            // item order of the cap kernels (k_merkle.hpp: CapTopIndex): tree-major for launches of >= 2^19 lanes
-            const bool tm_t = (uint64_t)top_t * 256 >= (1u << 19), tm_p = (uint64_t)top_p * 256 >= (1u << 19);
-            begin(3);
-            if (serial_plan) {
-                for (uint32_t k = 0; k < fp.nb; k++)
-                    hipLaunchKernelGGL(k_plan, dim3(grid_for(fp.a[k].n, 64)), dim3(64), 0, st, d_blob, d_offsets, fp.a[k].n, metas, ctxs,
-                                       fp.a[k].pl);
-            } else {
-                uint32_t pbmax = 1;
-                for (uint32_t k = 0; k < fp.nb; k++) pbmax = std::max<uint32_t>(pbmax, kBlock / fp.a[k].pl.G);
-                fp.lds_proofs = pbmax;
-                if (qconst_in_plan)
-                    hipLaunchKernelGGL((k_plan_par<kBlock, true>), dim3(blocks + grid_for((size_t)N * (qconst4 ? 64 : 16), 256)), dim3(kBlock), plan_lds_bytes(pbmax), st,
-                                       d_blob, d_offsets, metas, ctxs, fp, N | (qconst4 ? 0x80000000u : 0u));
-                else
-                    hipLaunchKernelGGL((k_plan_par<kBlock, false>), dim3(blocks), dim3(kBlock), plan_lds_bytes(pbmax), st, d_blob, d_offsets, metas, ctxs, fp, 0u);
-            }
-            end();
-            HIP_TRY(hipEventRecord(c->ev_plan, st));
-            HIP_TRY(hipStreamWaitEvent(c->side, c->ev_plan, 0));
-            const size_t pair_lds = ((po && po->d_pair_sib) || flow) ? (size_t)kBlock * 32 : 0;
-            auto launch_pair = [&](hipStream_t on) {
-                if (flow && tree_form == 2) hipLaunchKernelGGL((k_pair_merkle<kRowTreeBlock, true, FORM_ROW>), dim3(blocks_m, 1 + max_inner), dim3(kRowTreeBlock), pair_lds, on, fm, fargs);
-                else if (flow) hipLaunchKernelGGL((k_pair_merkle<kBlock, true>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
-                else if (tree_form == 2) hipLaunchKernelGGL((k_pair_merkle<kRowTreeBlock, false, FORM_ROW>), dim3(blocks_m, 1 + max_inner), dim3(kRowTreeBlock), pair_lds, on, fm, fargs);
-                else if (tree_form == 0) hipLaunchKernelGGL((k_pair_merkle<kBlock, false, 0>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
-                else hipLaunchKernelGGL((k_pair_merkle<kBlock, false, 1>), dim3(blocks_m, 1 + max_inner), dim3(kBlock), pair_lds, on, fm, fargs);
-            };
-            auto launch_trace = [&](hipStream_t on) {
-                if (flow && tree_form == 2) hipLaunchKernelGGL((k_trace_merkle<kRowTreeBlock, true, FORM_ROW>), dim3(blocks_m, 4), dim3(kRowTreeBlock), 0, on, fm, fargs);
-                else if (flow) hipLaunchKernelGGL((k_trace_merkle<kBlock, true>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
-                else if (tree_form == 2) hipLaunchKernelGGL((k_trace_merkle<kRowTreeBlock, false, FORM_ROW>), dim3(blocks_m, 4), dim3(kRowTreeBlock), 0, on, fm, fargs);
-                else if (tree_form == 0) hipLaunchKernelGGL((k_trace_merkle<kBlock, false, 0>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
-                else hipLaunchKernelGGL((k_trace_merkle<kBlock, false, 1>), dim3(blocks_m, 4), dim3(kBlock), 0, on, fm, fargs);
-            };
-            // the last levels of the trees of a kernel, right behind it on its stream (stage 8)
-            auto launch_top = [&](hipStream_t on, bool pair) {
-                if (!any_top) return;
-                begin_on(8, on);
-                const bool tm = pair ? tm_p : tm_t, fast = tree_form == 0;  // (fast: a small batch's few waves: the permutation instance without wait states, as the tree kernels in front of it)
-                const dim3 blk(256);
-                if (any_mid && (pair ? mid_p : mid_t)) {  // buckets that hand over at the cap level: the levels down to k_cap_top's first
-                    const dim3 grid(pair ? mid_p : mid_t);
-                    const CapTopIndex& ixm = pair ? ix_mp : ix_mt;
-                    if (fast && tm) hipLaunchKernelGGL((k_cap_mid<0, true>), grid, blk, 0, on, fm, ixm, pair ? 1u : 0u);
-                    else if (fast) hipLaunchKernelGGL((k_cap_mid<0, false>), grid, blk, 0, on, fm, ixm, pair ? 1u : 0u);
-                    else if (tm) hipLaunchKernelGGL((k_cap_mid<1, true>), grid, blk, 0, on, fm, ixm, pair ? 1u : 0u);
-                    else hipLaunchKernelGGL((k_cap_mid<1, false>), grid, blk, 0, on, fm, ixm, pair ? 1u : 0u);
-                }
-                {
-                    const dim3 grid(pair ? top_p : top_t);
-                    const CapTopIndex& ixt = pair ? ix_p : ix_t;
-                    if (fast && tm) hipLaunchKernelGGL((k_cap_top<0, true>), grid, blk, 0, on, fm, ixt, pair ? 1u : 0u);
-                    else if (fast) hipLaunchKernelGGL((k_cap_top<0, false>), grid, blk, 0, on, fm, ixt, pair ? 1u : 0u);
-                    else if (tm) hipLaunchKernelGGL((k_cap_top<1, true>), grid, blk, 0, on, fm, ixt, pair ? 1u : 0u);
-                    else hipLaunchKernelGGL((k_cap_top<1, false>), grid, blk, 0, on, fm, ixt, pair ? 1u : 0u);
-                }
-                end_on(on);
-            };
-            if (chain) {
-                // side: trace trees behind the row hashes (same stream) and the plan (event); main: k_query, FRI trees
-                begin_on(5, c->side);
-                launch_trace(c->side);
-                end_on(c->side);
-                launch_top(c->side, false);
-                begin(4);
-                if (query_row) hipLaunchKernelGGL((k_query<kRowTreeBlock, 4, true>), dim3(blocks_q), dim3(kRowTreeBlock), 0, st, fq);  // a row of 16 threads per query
-                else hipLaunchKernelGGL((k_query<kBlock, 4>), dim3(blocks), dim3(kBlock), 0, st, fq);  // chain layout = small batch: the latency form
-                end();
-                begin(6);
-                launch_pair(st);
-                end();
-                launch_top(st, true);
-                HIP_TRY(hipGetLastError());
-                continue;
-            }
-            begin_on(4, c->side);
-            hipLaunchKernelGGL((k_query<kBlock, 2>), dim3(blocks), dim3(kBlock), 0, c->side, fq);
-            end_on(c->side);
-            HIP_TRY(hipEventRecord(c->ev_query, c->side));
-            if (!joined) { HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0)); joined = true; }
-            if (overlap_trees) {
-                begin_on(6, c->side);
-                launch_pair(c->side);
-                end_on(c->side);
-                launch_top(c->side, true);
-            }
-            begin(5);
-            launch_trace(st);
-            end();
-            // single-group batch: the OODS check goes in front of the trace trees' last levels, which wait for the FRI
-            // trees to leave them room — so it runs underneath the FRI trees, not behind them
-            if (overlap_trees && !oods_launched) launch_oods(st);
-            launch_top(st, false);
-            if (!overlap_trees) {
-                HIP_TRY(hipStreamWaitEvent(st, c->ev_query, 0));
-                begin(6);
-                launch_pair(st);
-                end();
-                launch_top(st, true);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        // The OODS composition check only raises failure flags (atomicOr) for k_finalize: behind the trace trees on the
-        // main stream when the FRI trees run on the side stream (overlap_trees), else on the side stream behind k_query.
-        if (!oods_launched) launch_oods((overlap_trees && !chain) ? st : c->side);
-        HIP_TRY(hipEventRecord(c->ev_scan, c->side));
     }
-    if (sum[0] > 0) HIP_TRY(hipStreamWaitEvent(st, c->ev_scan, 0));
-    // verdicts (+ the canonicity fallback for proofs whose witness lists some stage found of the wrong length, + the
-    // accept bitmap when the caller asked for it): ONE launch behind the Merkle stages
-    begin(7);
-    hipLaunchKernelGGL(k_finalize, dim3(grid_for(N, 256)), dim3(256), 0, st, d_blob, d_offsets, N, metas, ctxs, d_accept, d_reason, 0u,
-                       po ? po->d_bitmap : nullptr, reinterpret_cast<unsigned long long*>(po ? po->d_count : nullptr));
-    end();
-    if (po && po->d_transcript)  // behind every stage that can find a non-canonical word: such a proof's row says RSV_R_PARSE
-        hipLaunchKernelGGL(k_export_transcript, dim3(grid_for((size_t)N * TR_WORDS, 256)), dim3(256), 0, st, N, metas, ctxs,
-                           po->d_transcript);
-    HIP_TRY(hipGetLastError());
-    return RSV_OK;
+    return enqueue_finalize(v);
 }
 
 namespace {

@@ -12,6 +12,10 @@
 //                                                     and the blocks of a pass — block counts that are powers of two and that
 //                                                     are not, budgets from below the smallest pass to above the largest —
 //                                                     against the two loops every streaming driver used to carry
+//   host_logic_asan plan                              host_logic.hpp: the launch plan of a verify call (plan_batch, plan_launches,
+//                                                     plan_group), one line per case over every batch size at which a form
+//                                                     changes, for comparison with the restatement of what the launcher
+//                                                     used to decide inline (tests/verify_plan_ref.py)
 //
 // The hints file: 16 header words (magic, proof bytes, nq, M, n_inner, flow_count, n_pi, copies, 0...), then the proof
 // (padded to words), trace_sib, trace_pos, trace_cols, fri_sib, fri_cols, flow [flow_count][32], swap (bytes, padded),
@@ -306,10 +310,78 @@ static int run_passes(uint32_t seed, int rounds) {
     return 0;
 }
 
+// The launch plan of a verify call (host_logic.hpp: plan_batch, plan_launches, plan_group) over the full product of batch
+// sizes, configurations, requested outputs, options (one at a time away from its default) and sets of group entries: one
+// line per case, the case first, then every field of both steps and of every group.  tests/test_host_logic_asan.py holds
+// the same product and compares each line with tests/verify_plan_ref.py.
+static int run_plan() {
+    const uint32_t Ns[] = {1, 256, 257, 1023, 1024, 1025, 2048, 4096, 4097, 6144, 6145, 8192, 24576, 24577, 49152, 49153, 65536};
+    const uint32_t queries[] = {1, 3, 4, 16, 32, 33, 80, 128};
+    const uint32_t folds[][2] = {{1, 0}, {1, 16}, {4, 3}, {16, 0}, {16, 16}};  // (log_blowup, log_last)
+    struct IntOpt { const char* name; int Options::*field; int max; };
+    const IntOpt int_opts[] = {{"transcript_form", &Options::transcript_form, 2}, {"transcript_split", &Options::transcript_split, 2},
+                               {"oods_form", &Options::oods_form, 2}, {"qconst_form", &Options::qconst_form, 2}, {"plan_form", &Options::plan_form, 2},
+                               {"tree_cap", &Options::tree_cap, 2}, {"overlap_trees", &Options::overlap_trees, 2},
+                               {"critical_chain", &Options::critical_chain, 2}, {"device_order", &Options::device_order, 2},
+                               {"flow_cap", &Options::flow_cap, 2}, {"query_form", &Options::query_form, 2}, {"tree_pace", &Options::tree_pace, 3},
+                               {"pair_order", &Options::pair_order, 2}, {"cap_mid", &Options::cap_mid, 2}, {"cap_top", &Options::cap_top, 2}};
+    const long long budgets_mb[] = {1, 512, 1ll << 20};  // RSV_OPT_WS_BUDGET_MB: both ends of its range and one between
+    struct Setting { const char* name; long long value; Options o; };
+    std::vector<Setting> settings;
+    settings.push_back({"default", 0, Options{}});
+    for (const IntOpt& io : int_opts)
+        for (int val = 1; val <= io.max; val++) {
+            Options o;
+            o.*io.field = val;
+            settings.push_back({io.name, val, o});
+        }
+    for (long long mb : budgets_mb) {
+        Options o;
+        o.ws_budget_mb = mb;
+        settings.push_back({"ws_budget_mb", mb, o});
+    }
+    size_t cases = 0;
+    for (uint32_t N : Ns) {
+    // the three sets of group entries.  0: one entry of G = 16;  1: one entry of G = 33;  2: two groups, the first of two entries
+    const std::vector<host::Bucket> bucket_sets[3] = {{{16, 22, 10, 8, N, 0}}, {{33, 21, 9, 8, N, 0}}, {{16, 22, 10, 8, 2 * N, 0}, {27, 24, 12, 8, 3 * N, 2 * (size_t)N}}};
+    const std::vector<std::vector<host::Entry>> group_sets[3] = {
+        {{host::Entry{0, 0, N, 16, 0, 0, 0, 0}}}, {{host::Entry{0, 0, N, 33, 0, 0, 0, 0}}},
+        {{host::Entry{0, 0, N, 16, 0, 0, 0, 0}, host::Entry{1, 0, 3 * N, 27, 0, 0, 0, 0}}, {host::Entry{0, N, N, 16, 0, 0, 0, 0}}}};
+    for (uint32_t nq : queries) for (const auto& fold : folds) for (int cfg_mode = 0; cfg_mode < 3; cfg_mode++)
+    for (int flow = 0; flow < 2; flow++) for (int paths = 0; paths < 2; paths++) for (int sib = 0; sib < 3; sib++) for (int own = 0; own < 2; own++)
+    for (const Setting& s : settings) {
+        // cfg_mode: 0 one configuration, 1 two, 2 one with cfg_of set;  sib: 0 none, 1 the trace trees', 2 the FRI trees'
+        const host::PlanInputs in{N, cfg_mode == 1 ? 2u : 1u, cfg_mode == 2, fold[0], fold[1], nq, flow != 0, paths != 0, sib == 1, sib == 2, own != 0, 16};
+        const host::VerifyPlan one = host::plan_batch(s.o, in);
+        for (int gset = 0; gset < 3; gset++) {
+            const std::vector<host::Bucket>& buckets = bucket_sets[gset];
+            const std::vector<std::vector<host::Entry>>& groups = group_sets[gset];
+            host::VerifyPlan p = one;
+            host::plan_launches(p, s.o, in, groups);
+            printf("%u %u %u %u %d %d %d %d %d %s %lld %d :", N, nq, fold[0], fold[1], cfg_mode, flow, paths, sib, own, s.name, s.value, gset);
+            printf(" %d %d %d %d %d %d %d %d %d %d %d %d", one.transcript_row, one.transcript_split, one.transcript_paced, one.device_order, one.tree_form,
+                   one.small_trees, one.qconst_row, one.qconst4, one.oods_row, one.cap_top, one.serial_plan, one.pair_deal);
+            printf(" %zu %zu %d %d %d %d %d :", one.policy.budget, one.policy.max_fused, one.policy.tree_cap_off, one.policy.flow, one.policy.flow_cap_off,
+                   one.policy.cap_top, one.policy.cap_mid);
+            printf(" %d %u %d %d %d %d %d", p.tree_form, p.tree_lanes, p.overlap_trees, p.chain, p.query_row, p.qconst_in_plan, p.oods_on_main);
+            for (const auto& grp : groups) {
+                const host::GroupPlan g = host::plan_group(p, in, buckets, grp);
+                printf(" : %d %d %zu %u %u", g.tm_t, g.tm_p, g.pair_lds, g.group_M, g.live);
+            }
+            printf("\n");
+            cases++;
+        }
+    }
+    }
+    fprintf(stderr, "plan: %zu cases\n", cases);
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc == 2 && std::string(argv[1]) == "plan") return run_plan();
     if (argc == 4 && std::string(argv[1]) == "program") return run_program(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "buckets") return run_buckets((uint32_t)atoi(argv[2]), atoi(argv[3]));
     if (argc == 4 && std::string(argv[1]) == "passes") return run_passes((uint32_t)atoi(argv[2]), atoi(argv[3]));
-    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds> | passes <seed> <rounds>\n");
+    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds> | passes <seed> <rounds> | plan\n");
     return 2;
 }

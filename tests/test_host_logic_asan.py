@@ -12,7 +12,9 @@ the C++ mirror of the reference's gadgets) are plain C++ headers that g++ compil
   * with truncated / misaligned / absurd templates, hints that do not belong to the template, mutated programs;
   * with seeded shape arrays (the fixture chain's mix, one shape per proof, everything rejected, tiny query counts) against
     the invariants the launcher relies on;
-  * with seeded workspace costs and budgets against the pass sizing of the next proof's streaming stages (plan_pass)."""
+  * with seeded workspace costs and budgets against the pass sizing of the next proof's streaming stages (plan_pass);
+  * with every batch size at which a verify call changes the form of a kernel or its stream layout, under every option
+    that bears on it, against the decisions as the launcher took them before they became one plan (verify_plan_ref.py)."""
 import os
 import subprocess
 
@@ -47,6 +49,58 @@ def test_pass_sizing_under_sanitizers(harness):
         out = subprocess.run([harness, "passes", str(seed), str(rounds)], capture_output=True, text=True, env=SAN_ENV, timeout=600)
         assert out.returncode == 0 and "invariants hold" in out.stdout, out.stdout + out.stderr
         assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
+def test_launch_plan_is_what_the_launcher_decided_inline(harness):
+    """The launch plan of a verify call (host_logic.hpp: plan_batch, plan_launches, plan_group — every form decision of
+    verify_impl, which only enqueues) against tests/verify_plan_ref.py, the restatement of the decisions as verify_impl took
+    them inline until commit 4da6cb5.  The harness prints one line per case with every field of both steps; every line must
+    be the restatement's.  The product: 17 batch sizes (each threshold, and one either side) x 8 query counts x 5 (log_blowup,
+    log_last) x 3 configuration sets (one, two, one with cfg_of) x flow x paths x sibling output (none, the trace trees', the
+    FRI trees') x own inputs x 35 option settings (the default; every option the plan reads, one at a time, at every other
+    value it accepts — for the workspace budget both ends of its range and one between) x 3 sets of group entries (one
+    entry of G = 16, one of G = 33, two groups) = 5 140 800 cases."""
+    from tests import verify_plan_ref as ref
+    sizes = (1, 256, 257, 1023, 1024, 1025, 2048, 4096, 4097, 6144, 6145, 8192, 24576, 24577, 49152, 49153, 65536)
+    queries = (1, 3, 4, 16, 32, 33, 80, 128)
+    folds = ((1, 0), (1, 16), (4, 3), (16, 0), (16, 16))
+    settings = [("default", 0, dict(ref.DEFAULTS))]
+    for name in ref.DEFAULTS:  # (in the order of the harness's table)
+        settings += [(name, val, dict(ref.DEFAULTS, **{name: val})) for val in ref.ACCEPTED[name]]
+    assert len(settings) == 35
+    expected_cases = len(sizes) * len(queries) * len(folds) * 3 * 2 * 2 * 3 * 2 * len(settings) * 3
+    assert expected_cases == 5140800
+    proc = subprocess.Popen([harness, "plan"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=SAN_ENV)
+    lines = iter(proc.stdout)
+    cases = 0
+    for N in sizes:
+        # entries (G, cn, maxM, maxInner) of the three sets, as the harness builds them
+        group_sets = ([[(16, N, 22, 10)]], [[(33, N, 21, 9)]], [[(16, N, 22, 10), (27, 3 * N, 24, 12)], [(16, N, 22, 10)]])
+        for nq in queries:
+            for lb, ll in folds:
+                for cfg_mode in range(3):
+                    n_cfgs, cfg_of = (2 if cfg_mode == 1 else 1), cfg_mode == 2
+                    for flow in (False, True):
+                        for paths in (False, True):
+                            for sib in range(3):
+                                for own in (0, 1):
+                                    head = "%d %d %d %d %d %d %d %d %d " % (N, nq, lb, ll, cfg_mode, flow, paths, sib, own)
+                                    for name, val, o in settings:
+                                        one = ref.step_one(o, N, n_cfgs, cfg_of, lb, ll, nq, flow, paths, sib == 1, sib == 2)
+                                        one_text = ref.ONE_FMT % one
+                                        for gset, groups in enumerate(group_sets):
+                                            two = ref.step_two(o, one, N, n_cfgs, lb, ll, nq, flow, sib == 2, groups)
+                                            want = ref.plan_line("%s%s %d %d :" % (head, name, val, gset), one_text, two)
+                                            got = next(lines, "").rstrip("\n")
+                                            if got != want:
+                                                proc.kill()
+                                                raise AssertionError("case %d: the plan says\n  %s\nthe launcher decided\n  %s" % (cases, got, want))
+                                            cases += 1
+    assert next(lines, None) is None, "the harness printed more cases than the product has"
+    err = proc.stderr.read()
+    assert proc.wait(timeout=60) == 0, err
+    assert cases == expected_cases and "plan: %d cases" % expected_cases in err, (cases, err)  # none skipped, on either side
+    assert "runtime error" not in err and "AddressSanitizer" not in err, err
 
 
 def _write_hints(path, proof, inputs, copies, walks):
