@@ -369,7 +369,8 @@ int rsv_verify_batch(const uint8_t* blob, const uint64_t* offsets, size_t n,
 
 /* Same, inputs and outputs resident in HBM (d_ = device pointers); enqueued on ctx's streams.  d_offsets must be 8-byte
  * aligned, d_blob 4-byte aligned and every offset a multiple of 4 (bincode proofs of this type always have
- * 4-byte-multiple lengths).
+ * 4-byte-multiple lengths).  d_blob needs no padding: no kernel reads a byte at or past d_blob + offsets[n] (every read
+ * is bounded by the parser's section lengths, which lie inside the proof's own bytes).
  * Host synchronisation: a batch under ONE configuration (cfg->n_cfgs == 1, cfg_of NULL) is enqueued completely and the
  * call returns without waiting for the device (after the first call has grown the workspaces).  A batch under several
  * configurations is bucketed by n_queries on the host: the call waits for the parser (a few hundred microseconds),

@@ -8,26 +8,25 @@ using namespace rsv::circuit;
 // The records of the statement hash of the TEMPLATE, for the builder of a hashed program: its own records `copies` times
 // over (every copy of the template circuit verifies the template), hashed by the kernel the evaluation runs.
 static int template_statement_flow(const rsv_public_input* own, size_t n_own, uint32_t copies, int device, std::vector<uint32_t>& flow) {
-    const size_t T = (size_t)copies * n_own, S = (T + 7) / 8 + 1;
-    std::vector<rsv_public_input> rec;
-    for (uint32_t c = 0; c < copies; c++) rec.insert(rec.end(), own, own + n_own);
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    DevBuf d_rec, d_stmt, d_flow, d_swap;
-    HIP_TRY(d_rec.alloc(sizeof(rsv_public_input) * T));
-    HIP_TRY(d_stmt.alloc(sizeof(rsv_public_input) * STMT_WORDS));
-    HIP_TRY(d_flow.alloc(S * 128));
-    HIP_TRY(d_swap.alloc(S));
-    HIP_TRY(hipMemcpy(d_rec.p, rec.data(), sizeof(rsv_public_input) * T, hipMemcpyHostToDevice));
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    statement_digest_launch(c, d_rec.as<const rsv_public_input>(), 1, (uint32_t)T, d_stmt.as<rsv_public_input>(), nullptr, d_flow.as<uint4>(), d_swap.as<uint8_t>());
-    rc = hipGetLastError() == hipSuccess ? rsv_ctx_synchronize(c) : RSV_E_DEVICE;
-    flow.resize(S * 32);
-    if (rc == RSV_OK && hipMemcpy(flow.data(), d_flow.p, S * 128, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    rsv_ctx_destroy(c);
-    return rc;
+    return nomem_guard([&]() -> int {
+        const size_t T = (size_t)copies * n_own, S = (T + 7) / 8 + 1;
+        std::vector<rsv_public_input> rec;
+        for (uint32_t c = 0; c < copies; c++) rec.insert(rec.end(), own, own + n_own);
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        flow.resize(S * 32);
+        BatchStage b;  // (no batch: the context of its own, and the teardown order)
+        const rsv_public_input* d_rec = b.s.upload<rsv_public_input>(rec.data(), sizeof(rsv_public_input) * T);
+        rsv_public_input* d_stmt = b.s.scratch<rsv_public_input>(sizeof(rsv_public_input) * STMT_WORDS);
+        uint4* d_flow = b.s.output<uint4>(flow.data(), S * 128);
+        uint8_t* d_swap = b.s.scratch<uint8_t>(S);
+        if (b.s.rc != RSV_OK) return b.s.rc;
+        rc = b.create(device);
+        if (rc != RSV_OK) return rc;
+        statement_digest_launch(b.c(), d_rec, 1, (uint32_t)T, d_stmt, nullptr, d_flow, d_swap);
+        rc = hipGetLastError() == hipSuccess ? rsv_ctx_synchronize(b.c()) : RSV_E_DEVICE;
+        return rc == RSV_OK ? b.s.finish() : rc;
+    });
 }
 
 static int witness_program_build(const uint8_t* proof, size_t len, const rsv_pcs_config* cfg, const rsv_public_input* pi, size_t n_pi, size_t n_fixed,

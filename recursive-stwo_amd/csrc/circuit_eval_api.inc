@@ -51,7 +51,7 @@ int rsv_circuit_program_create_eval(const uint32_t* gates, size_t n_rows, const 
                                     size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, const uint32_t* hints, size_t n_hints,
                                     const uint32_t* flow_links, uint32_t n_inputs, int device, rsv_witness_program** out) {
     if (!out) return RSV_E_NULL;
-    try {
+    return nomem_guard([&]() -> int {
         rsv::ceval::Program e;
         const int rc = rsv::ceval::compile(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, hints, n_hints,
                                            flow_links, n_inputs, &e);
@@ -59,10 +59,8 @@ int rsv_circuit_program_create_eval(const uint32_t* gates, size_t n_rows, const 
         rsv_witness_program* p = uc_new_program(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, device, std::move(e.tables));
         p->ce = std::move(e);
         *out = p;
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-    return RSV_OK;
+        return RSV_OK;
+    });
 }
 
 int rsv_circuit_eval_info(const rsv_witness_program* prog, uint32_t* n_inputs, uint32_t* n_levels, uint32_t* n_instr) {

@@ -401,42 +401,35 @@ int rsv_witness_commit_caps_dev(rsv_ctx* c, const rsv_witness_program* prog, con
 int rsv_witness_commit(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                        const rsv_public_input* pi, size_t n_pi, uint32_t log_blowup, uint32_t* roots, uint32_t* draws, uint32_t* sums,
                        uint8_t* ok, uint8_t* accept, uint8_t* reason, int device) {
-    if (!prog || (n && (!blob || !offsets || !roots || !draws || !sums || !accept))) return RSV_E_NULL;
-    if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
-    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
-    if (n == 0) return RSV_OK;
-    WitnessStage st;
-    int rc = st.open(offsets, n, device, true);
-    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
-    if (rc != RSV_OK) return rc;
-    if (std::max(prog->trace_lp, prog->trace_lq) + log_blowup > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
-    const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
-    const size_t n_ops = prog->witness_ops.size() / 3;
-    DevBuf dplonk, dposeidon, dops, dip, diq, droots, ddraws, dsums, dok;
-    HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
-    HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
-    HIP_TRY(dops.alloc(n * n_ops * 4));
-    HIP_TRY(dip.alloc(n * rsv::INT_COLS * N * 4));
-    HIP_TRY(diq.alloc(n * rsv::INT_COLS * Q * 4));
-    HIP_TRY(droots.alloc(n * 96));
-    HIP_TRY(ddraws.alloc(n * 48));
-    HIP_TRY(dsums.alloc(n * 32));
-    HIP_TRY(dok.alloc(n));
-    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
-    if (rc == RSV_OK)
-        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(),
-                                   dops.as<uint32_t>());
-    if (rc == RSV_OK)
-        rc = rsv_witness_commit_dev(st.c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), dops.as<const uint32_t>(),
-                                    st.accept, n, log_blowup, droots.as<uint32_t>(), ddraws.as<uint32_t>(), dip.as<uint32_t>(),
-                                    diq.as<uint32_t>(), dsums.as<uint32_t>(), nullptr, dok.as<uint8_t>());
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    HIP_TRY(hipMemcpy(roots, droots.p, n * 96, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(draws, ddraws.p, n * 48, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sums, dsums.p, n * 32, hipMemcpyDeviceToHost));
-    if (ok) HIP_TRY(hipMemcpy(ok, dok.p, n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!prog || (n && (!blob || !offsets || !roots || !draws || !sums || !accept))) return RSV_E_NULL;
+        if (log_blowup < 1 || log_blowup > RSV_MAX_LOG_BLOWUP) return RSV_E_SIZE;
+        if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
+        if (n == 0) return RSV_OK;
+        WitnessStage st;
+        int rc = st.open(offsets, n, device, true);
+        if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
+        if (rc != RSV_OK) return rc;
+        if (std::max(prog->trace_lp, prog->trace_lq) + log_blowup > RSV_MAX_LOG_SIZE) return RSV_E_SIZE;
+        const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
+        const size_t n_ops = prog->witness_ops.size() / 3;
+        HostStage& s = st.b.s;
+        uint32_t* dplonk = s.scratch<uint32_t>(n * rsv::PLONK_COLS_K * N * 4);
+        uint32_t* dposeidon = s.scratch<uint32_t>(n * rsv::POSEIDON_COLS_K * Q * 4);
+        uint32_t* dops = s.scratch<uint32_t>(n * n_ops * 4);
+        uint32_t* dip = s.scratch<uint32_t>(n * rsv::INT_COLS * N * 4);
+        uint32_t* diq = s.scratch<uint32_t>(n * rsv::INT_COLS * Q * 4);
+        uint32_t* droots = s.output<uint32_t>(roots, n * 96);
+        uint32_t* ddraws = s.output<uint32_t>(draws, n * 48);
+        uint32_t* dsums = s.output<uint32_t>(sums, n * 32);
+        uint8_t* dok = ok ? s.output<uint8_t>(ok, n) : s.scratch<uint8_t>(n);
+        if (s.rc != RSV_OK) return s.rc;
+        rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+        if (rc == RSV_OK) rc = rsv_witness_trace_dev(st.c(), prog, st.vars, st.flow, st.swap, st.accept, n, dplonk, dposeidon, dops);
+        if (rc == RSV_OK)
+            rc = rsv_witness_commit_dev(st.c(), prog, dplonk, dposeidon, dops, st.accept, n, log_blowup, droots, ddraws, dip, diq, dsums, nullptr, dok);
+        return rc == RSV_OK ? st.finish(accept, reason) : rc;
+    });
 }
 
 }  // extern "C"

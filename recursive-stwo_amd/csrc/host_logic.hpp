@@ -10,9 +10,12 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <new>
+#include <stdexcept>
 #include <unordered_map>
 #include <vector>
 
+#include "../../include/rsv.h"
 #include "layout.hpp"
 #include "options.hpp"
 
@@ -29,6 +32,22 @@ struct Carve {
         return p;
     }
 };
+
+// The offsets of a batch as the host-pointer forms stage them (host_stage.inc): rel[i] = offsets[i] - offsets[0] for
+// i = 0 .. n, so that proof 0 starts at byte 0 of the staged blob.  RSV_E_SIZE exactly when some offsets[i + 1] < offsets[i].
+inline int rebase_offsets(const uint64_t* offsets, size_t n, std::vector<uint64_t>& rel) {
+    for (size_t i = 0; i < n; i++)
+        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
+    try {
+        rel.resize(n + 1);
+    } catch (const std::bad_alloc&) {
+        return RSV_E_NOMEM;
+    } catch (const std::length_error&) {
+        return RSV_E_NOMEM;
+    }
+    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - offsets[0];
+    return RSV_OK;
+}
 
 // One launch geometry: every proof of a bucket has n_queries = G.  maxM / maxInner / minLevel bound its trees.
 struct Bucket { uint32_t G, maxM, maxInner, minLevel, count; size_t first; };

@@ -92,37 +92,29 @@ int rsv_witness_interaction_dev(rsv_ctx* c, const rsv_witness_program* prog, con
 int rsv_witness_interaction(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                             const rsv_public_input* pi, size_t n_pi, const uint32_t* lookup, uint32_t* int_plonk, uint32_t* int_poseidon,
                             uint32_t* sums, uint8_t* ok, uint8_t* accept, uint8_t* reason, int device) {
-    if (!prog || (n && (!blob || !offsets || !lookup || !int_plonk || !int_poseidon || !sums || !accept))) return RSV_E_NULL;
-    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
-    if (n == 0) return RSV_OK;
-    WitnessStage st;
-    int rc = st.open(offsets, n, device, true);
-    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
-    if (rc != RSV_OK) return rc;
-    const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
-    DevBuf dplonk, dposeidon, dlookup, dip, diq, dsums, dok;
-    HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
-    HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
-    HIP_TRY(dlookup.alloc(n * 32));
-    HIP_TRY(dip.alloc(n * rsv::INT_COLS * N * 4));
-    HIP_TRY(diq.alloc(n * rsv::INT_COLS * Q * 4));
-    HIP_TRY(dsums.alloc(n * 32));
-    HIP_TRY(dok.alloc(n));
-    HIP_TRY(hipMemcpy(dlookup.p, lookup, n * 32, hipMemcpyHostToDevice));
-    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
-    if (rc == RSV_OK)
-        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(), nullptr);
-    if (rc == RSV_OK)
-        rc = rsv_witness_interaction_dev(st.c, prog, dplonk.as<const uint32_t>(), dposeidon.as<const uint32_t>(), st.accept,
-                                         dlookup.as<const uint32_t>(), n, dip.as<uint32_t>(), diq.as<uint32_t>(), dsums.as<uint32_t>(),
-                                         dok.as<uint8_t>());
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    HIP_TRY(hipMemcpy(int_plonk, dip.p, n * rsv::INT_COLS * N * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(int_poseidon, diq.p, n * rsv::INT_COLS * Q * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sums, dsums.p, n * 32, hipMemcpyDeviceToHost));
-    if (ok) HIP_TRY(hipMemcpy(ok, dok.p, n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!prog || (n && (!blob || !offsets || !lookup || !int_plonk || !int_poseidon || !sums || !accept))) return RSV_E_NULL;
+        if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
+        if (n == 0) return RSV_OK;
+        WitnessStage st;
+        int rc = st.open(offsets, n, device, true);
+        if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), true);
+        if (rc != RSV_OK) return rc;
+        const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq;
+        HostStage& s = st.b.s;
+        uint32_t* dplonk = s.scratch<uint32_t>(n * rsv::PLONK_COLS_K * N * 4);
+        uint32_t* dposeidon = s.scratch<uint32_t>(n * rsv::POSEIDON_COLS_K * Q * 4);
+        const uint32_t* dlookup = s.upload<uint32_t>(lookup, n * 32);
+        uint32_t* dip = s.output<uint32_t>(int_plonk, n * rsv::INT_COLS * N * 4);
+        uint32_t* diq = s.output<uint32_t>(int_poseidon, n * rsv::INT_COLS * Q * 4);
+        uint32_t* dsums = s.output<uint32_t>(sums, n * 32);
+        uint8_t* dok = ok ? s.output<uint8_t>(ok, n) : s.scratch<uint8_t>(n);
+        if (s.rc != RSV_OK) return s.rc;
+        rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+        if (rc == RSV_OK) rc = rsv_witness_trace_dev(st.c(), prog, st.vars, st.flow, st.swap, st.accept, n, dplonk, dposeidon, nullptr);
+        if (rc == RSV_OK) rc = rsv_witness_interaction_dev(st.c(), prog, dplonk, dposeidon, st.accept, dlookup, n, dip, diq, dsums, dok);
+        return rc == RSV_OK ? st.finish(accept, reason) : rc;
+    });
 }
 
 }  // extern "C"

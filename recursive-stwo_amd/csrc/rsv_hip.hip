@@ -2,7 +2,8 @@
 //
 // This translation unit is the whole product library (librsv_hip.so).  It
 // contains no CPU verification path: every entry point either runs the HIP
-// kernels or fails with RSV_E_DEVICE.
+// kernels or fails with RSV_E_DEVICE.  The host-pointer entry points (the probes
+// below among them) stage their arguments through host_stage.inc.
 #include "../../include/rsv.h"
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -108,32 +110,9 @@ struct rsv_ctx {
     Options opt;
 };
 
+#include "host_stage.inc"
+
 namespace {
-
-// RAII device buffer for the host-pointer convenience entry points.
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    // RSV_OPT_WS_FILL (process default): the fresh allocation holds the fill byte before anything is copied or launched into it
-    hipError_t alloc(size_t bytes) {
-        const size_t want = bytes ? bytes : 4;
-        hipError_t e = hipMalloc(&p, want);
-        const int fill = g_default_ws_fill.load(std::memory_order_relaxed);
-        if (e == hipSuccess && fill) {
-            e = hipMemset(p, fill - 1, want);
-            if (e == hipSuccess) e = hipDeviceSynchronize();
-        }
-        return e;
-    }
-    template <class T> T* as() { return static_cast<T*>(p); }
-};
-
-int select_device(int device) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || device < 0 || device >= n) return RSV_E_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return RSV_E_DEVICE;
-    return RSV_OK;
-}
 
 Options default_options() {
     std::lock_guard<std::mutex> lk(g_options_mu);
@@ -349,59 +328,40 @@ int rsv_poseidon2_permute_dev(rsv_ctx* c, const uint32_t* d_in, uint32_t* d_out,
 }
 
 int rsv_poseidon2_permute(const uint32_t* in16, uint32_t* out16, size_t n, int device) {
-    if (n && (!in16 || !out16)) return RSV_E_NULL;
-    if (n > ((size_t)1 << 28)) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf din, dout, dbad;
-    HIP_TRY(din.alloc(64 * n));
-    HIP_TRY(dout.alloc(64 * n));
-    HIP_TRY(dbad.alloc(4));
-    HIP_TRY(hipMemset(dbad.p, 0, 4));
-    HIP_TRY(hipMemcpy(din.p, in16, 64 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_permute, dim3(permute_grid(n, default_options().perm_wg_per_cu)), dim3(256), 0, 0, din.as<const uint4>(),
-                       dout.as<uint4>(), n, dbad.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
-    if (bad) return RSV_E_RANGE;
-    HIP_TRY(hipMemcpy(out16, dout.p, 64 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!in16 || !out16)) return RSV_E_NULL;
+        if (n > ((size_t)1 << 28)) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint4* din = s.upload<uint4>(in16, 64 * n);
+        uint4* dout = s.output<uint4>(out16, 64 * n);
+        uint32_t* dbad = s.bad_flag();
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_permute, dim3(permute_grid(n, default_options().perm_wg_per_cu)), dim3(256), 0, 0, din, dout, n, dbad);
+        return s.finish();
+    });
 }
 
 // ---------------------------------------------------------------- a4
 int rsv_poseidon2_half_permute(const uint32_t* left8, const uint32_t* right8, const uint8_t* swap,
                                uint32_t* out_rate8, uint32_t* out_cap8, size_t n, int device) {
-    if (n && (!left8 || !right8)) return RSV_E_NULL;
-    if (n > ((size_t)1 << 28)) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dl, dr, ds, drate, dcap, dbad;
-    HIP_TRY(dl.alloc(32 * n));
-    HIP_TRY(dr.alloc(32 * n));
-    HIP_TRY(dbad.alloc(4));
-    HIP_TRY(hipMemset(dbad.p, 0, 4));
-    HIP_TRY(hipMemcpy(dl.p, left8, 32 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dr.p, right8, 32 * n, hipMemcpyHostToDevice));
-    if (swap) {
-        HIP_TRY(ds.alloc(n));
-        HIP_TRY(hipMemcpy(ds.p, swap, n, hipMemcpyHostToDevice));
-    }
-    if (out_rate8) HIP_TRY(drate.alloc(32 * n));
-    if (out_cap8) HIP_TRY(dcap.alloc(32 * n));
-    hipLaunchKernelGGL(k_half_permute, dim3(grid_for(n, 256)), dim3(256), 0, 0, dl.as<const uint32_t>(),
-                       dr.as<const uint32_t>(), swap ? ds.as<const uint8_t>() : nullptr,
-                       out_rate8 ? drate.as<uint32_t>() : nullptr, out_cap8 ? dcap.as<uint32_t>() : nullptr, n,
-                       dbad.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
-    if (bad) return RSV_E_RANGE;
-    if (out_rate8) HIP_TRY(hipMemcpy(out_rate8, drate.p, 32 * n, hipMemcpyDeviceToHost));
-    if (out_cap8) HIP_TRY(hipMemcpy(out_cap8, dcap.p, 32 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!left8 || !right8)) return RSV_E_NULL;
+        if (n > ((size_t)1 << 28)) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t *dl = s.upload<uint32_t>(left8, 32 * n), *dr = s.upload<uint32_t>(right8, 32 * n);
+        const uint8_t* ds = s.upload<uint8_t>(swap, n);
+        uint32_t *drate = s.output<uint32_t>(out_rate8, 32 * n), *dcap = s.output<uint32_t>(out_cap8, 32 * n);
+        uint32_t* dbad = s.bad_flag();
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_half_permute, dim3(grid_for(n, 256)), dim3(256), 0, 0, dl, dr, ds, drate, dcap, n, dbad);
+        return s.finish();
+    });
 }
 
 // ---------------------------------------------------------------- f4
@@ -423,101 +383,71 @@ int rsv_poseidon2_emulated_dev(rsv_ctx* c, const uint32_t* d_left, const uint32_
 
 int rsv_poseidon2_emulated(const uint32_t* left8, const uint32_t* right8, const uint8_t* swap, uint32_t* rows, size_t n,
                            int device) {
-    if (n && (!left8 || !right8 || !rows)) return RSV_E_NULL;
-    if (n > ((size_t)1 << 22)) return RSV_E_SIZE;  // 2^22 permutations = 27.9 GB of rows
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    const size_t row_bytes = (size_t)EMU_STRIDE * 16 * n;
-    DevBuf dl, dr, ds, drows, dbad;
-    HIP_TRY(dl.alloc(32 * n));
-    HIP_TRY(dr.alloc(32 * n));
-    HIP_TRY(drows.alloc(row_bytes));
-    HIP_TRY(dbad.alloc(4));
-    HIP_TRY(hipMemset(dbad.p, 0, 4));
-    HIP_TRY(hipMemcpy(dl.p, left8, 32 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dr.p, right8, 32 * n, hipMemcpyHostToDevice));
-    if (swap) {
-        HIP_TRY(ds.alloc(n));
-        HIP_TRY(hipMemcpy(ds.p, swap, n, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_emulated, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dl.as<const uint32_t>(),
-                       dr.as<const uint32_t>(), swap ? ds.as<const uint8_t>() : nullptr, drows.as<uint4>(), n,
-                       dbad.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
-    if (bad) return RSV_E_RANGE;
-    HIP_TRY(hipMemcpy(rows, drows.p, row_bytes, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!left8 || !right8 || !rows)) return RSV_E_NULL;
+        if (n > ((size_t)1 << 22)) return RSV_E_SIZE;  // 2^22 permutations = 27.9 GB of rows
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t *dl = s.upload<uint32_t>(left8, 32 * n), *dr = s.upload<uint32_t>(right8, 32 * n);
+        const uint8_t* ds = s.upload<uint8_t>(swap, n);
+        uint4* drows = s.output<uint4>(rows, (size_t)EMU_STRIDE * 16 * n);
+        uint32_t* dbad = s.bad_flag();
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_emulated, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, dl, dr, ds, drows, n, dbad);
+        return s.finish();
+    });
 }
 
 // ---------------------------------------------------------------- a5
 int rsv_merkle_hash_node(const uint32_t* left8, const uint32_t* right8, const uint32_t* cols, size_t n_cols,
                          uint32_t* out8, size_t n, int device) {
-    if (n && !out8) return RSV_E_NULL;
-    if ((left8 == nullptr) != (right8 == nullptr)) return RSV_E_NULL;
-    if (n_cols && !cols) return RSV_E_NULL;
-    if (!left8 && n_cols == 0) return RSV_E_SIZE;
-    if (n > ((size_t)1 << 26) || n_cols > 4096) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dl, dr, dc, dout, dbad;
-    HIP_TRY(dbad.alloc(4));
-    HIP_TRY(hipMemset(dbad.p, 0, 4));
-    if (left8) {
-        HIP_TRY(dl.alloc(32 * n));
-        HIP_TRY(dr.alloc(32 * n));
-        HIP_TRY(hipMemcpy(dl.p, left8, 32 * n, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(dr.p, right8, 32 * n, hipMemcpyHostToDevice));
-    }
-    if (n_cols) {
-        HIP_TRY(dc.alloc(4 * n_cols * n));
-        HIP_TRY(hipMemcpy(dc.p, cols, 4 * n_cols * n, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(dout.alloc(32 * n));
-    hipLaunchKernelGGL(k_hash_node, dim3(grid_for(n, 256)), dim3(256), 0, 0,
-                       left8 ? dl.as<const uint32_t>() : nullptr, left8 ? dr.as<const uint32_t>() : nullptr,
-                       n_cols ? dc.as<const uint32_t>() : nullptr, (uint32_t)n_cols, dout.as<uint32_t>(), n,
-                       dbad.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, dbad.p, 4, hipMemcpyDeviceToHost));
-    if (bad) return RSV_E_RANGE;
-    HIP_TRY(hipMemcpy(out8, dout.p, 32 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && !out8) return RSV_E_NULL;
+        if ((left8 == nullptr) != (right8 == nullptr)) return RSV_E_NULL;
+        if (n_cols && !cols) return RSV_E_NULL;
+        if (!left8 && n_cols == 0) return RSV_E_SIZE;
+        if (n > ((size_t)1 << 26) || n_cols > 4096) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        uint32_t* dbad = s.bad_flag();
+        const uint32_t *dl = s.upload<uint32_t>(left8, 32 * n), *dr = s.upload<uint32_t>(right8, 32 * n);
+        const uint32_t* dc = n_cols ? s.upload<uint32_t>(cols, 4 * n_cols * n) : nullptr;
+        uint32_t* dout = s.output<uint32_t>(out8, 32 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_hash_node, dim3(grid_for(n, 256)), dim3(256), 0, 0, dl, dr, dc, (uint32_t)n_cols, dout, n, dbad);
+        return s.finish();
+    });
 }
 
 // ---------------------------------------------------------------- a9
 int rsv_merkle_path_root(const uint32_t* query, const uint32_t* sib8, const uint32_t* cols,
                          const uint32_t* n_cols_at, uint32_t depth, uint32_t* out_root8, size_t n, int device) {
-    if (!query || !n_cols_at || !out_root8 || !cols || (depth && !sib8)) return RSV_E_NULL;
-    if (depth > 31 || n_cols_at[depth] == 0 || n > ((size_t)1 << 24)) return RSV_E_SIZE;
-    size_t per_path = 0;
-    for (uint32_t h = 0; h <= depth; h++) {
-        if (n_cols_at[h] > 4096) return RSV_E_SIZE;
-        per_path += n_cols_at[h];
-    }
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dq, ds, dc, dn, dout;
-    HIP_TRY(dq.alloc(4 * n));
-    HIP_TRY(ds.alloc(32 * (size_t)depth * n));
-    HIP_TRY(dc.alloc(4 * per_path * n));
-    HIP_TRY(dn.alloc(4 * (depth + 1)));
-    HIP_TRY(dout.alloc(32 * n));
-    HIP_TRY(hipMemcpy(dq.p, query, 4 * n, hipMemcpyHostToDevice));
-    if (depth) HIP_TRY(hipMemcpy(ds.p, sib8, 32 * (size_t)depth * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dc.p, cols, 4 * per_path * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dn.p, n_cols_at, 4 * (depth + 1), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_path_root, dim3(grid_for(n, 256)), dim3(256), 0, 0, dq.as<const uint32_t>(),
-                       ds.as<const uint32_t>(), dc.as<const uint32_t>(), dn.as<const uint32_t>(), depth,
-                       (uint32_t)per_path, dout.as<uint32_t>(), n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out_root8, dout.p, 32 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!query || !n_cols_at || !out_root8 || !cols || (depth && !sib8)) return RSV_E_NULL;
+        if (depth > 31 || n_cols_at[depth] == 0 || n > ((size_t)1 << 24)) return RSV_E_SIZE;
+        size_t per_path = 0;
+        for (uint32_t h = 0; h <= depth; h++) {
+            if (n_cols_at[h] > 4096) return RSV_E_SIZE;
+            per_path += n_cols_at[h];
+        }
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t* dq = s.upload<uint32_t>(query, 4 * n);
+        // (depth 0: no sibling is read, and the kernel still takes a pointer)
+        const uint32_t* ds = depth ? s.upload<uint32_t>(sib8, 32 * (size_t)depth * n) : s.scratch<uint32_t>(0);
+        const uint32_t* dc = s.upload<uint32_t>(cols, 4 * per_path * n);
+        const uint32_t* dn = s.upload<uint32_t>(n_cols_at, 4 * (depth + 1));
+        uint32_t* dout = s.output<uint32_t>(out_root8, 32 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_path_root, dim3(grid_for(n, 256)), dim3(256), 0, 0, dq, ds, dc, dn, depth, (uint32_t)per_path, dout, n);
+        return s.finish();
+    });
 }
 
 }  // extern "C"

@@ -84,12 +84,10 @@ int rsv_trace_preprocessed(const uint32_t* gates, size_t n_rows, const uint32_t*
 
 int rsv_trace_preprocessed_inputs(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, uint32_t log_plonk,
                                   uint32_t log_poseidon, uint32_t num_input, uint32_t* plonk_pre, uint32_t* poseidon_pre) {
-    try {
+    return nomem_guard([&] {
         return rsv::trace::preprocessed(gates, n_rows, flow_wires, n_flow, log_plonk, log_poseidon, num_input, rsv::RC_FULL_K,
                                         rsv::RC_PARTIAL_K, rsv::RC_FULL_K + 4, plonk_pre, poseidon_pre);
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
+    });
 }
 
 // rsv_witness_trace_dev (n proofs) and rsv_witness_trace_groups_dev (n groups, `grouped`): only the flow records differ
@@ -166,28 +164,24 @@ int rsv_witness_trace_groups_dev(rsv_ctx* c, const rsv_witness_program* prog, co
 int rsv_witness_trace(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                       const rsv_public_input* pi, size_t n_pi, uint32_t* plonk, uint32_t* poseidon, uint32_t* ops, uint8_t* accept,
                       uint8_t* reason, int device) {
-    if (!prog || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
-    if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
-    if (n == 0) return RSV_OK;
-    WitnessStage st;
-    int rc = st.open(offsets, n, device, true);
-    if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), false);
-    if (rc != RSV_OK) return rc;
-    const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq, n_ops = prog->witness_ops.size() / 3;
-    DevBuf dplonk, dposeidon, dops;
-    if (plonk) HIP_TRY(dplonk.alloc(n * rsv::PLONK_COLS_K * N * 4));
-    if (poseidon) HIP_TRY(dposeidon.alloc(n * rsv::POSEIDON_COLS_K * Q * 4));
-    if (ops) HIP_TRY(dops.alloc(n * n_ops * 4));
-    rc = st.eval(prog, blob, cfg, pi, n_pi, true);
-    if (rc == RSV_OK)
-        rc = rsv_witness_trace_dev(st.c, prog, st.vars, st.flow, st.swap, st.accept, n, dplonk.as<uint32_t>(), dposeidon.as<uint32_t>(),
-                                   dops.as<uint32_t>());
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    if (plonk) HIP_TRY(hipMemcpy(plonk, dplonk.p, n * rsv::PLONK_COLS_K * N * 4, hipMemcpyDeviceToHost));
-    if (poseidon) HIP_TRY(hipMemcpy(poseidon, dposeidon.p, n * rsv::POSEIDON_COLS_K * Q * 4, hipMemcpyDeviceToHost));
-    if (ops && n_ops) HIP_TRY(hipMemcpy(ops, dops.p, n * n_ops * 4, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!prog || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
+        if (prog->gates.empty() || prog->n_instr == 0 || n > (1u << 20)) return RSV_E_SIZE;  // built programs only: the witness is evaluated
+        if (n == 0) return RSV_OK;
+        WitnessStage st;
+        int rc = st.open(offsets, n, device, true);
+        if (rc == RSV_OK) rc = program_upload(const_cast<rsv_witness_program*>(prog), false);
+        if (rc != RSV_OK) return rc;
+        const size_t N = (size_t)1 << prog->trace_lp, Q = (size_t)1 << prog->trace_lq, n_ops = prog->witness_ops.size() / 3;
+        HostStage& s = st.b.s;
+        uint32_t* dplonk = s.output<uint32_t>(plonk, n * rsv::PLONK_COLS_K * N * 4);
+        uint32_t* dposeidon = s.output<uint32_t>(poseidon, n * rsv::POSEIDON_COLS_K * Q * 4);
+        uint32_t* dops = s.output<uint32_t>(ops, n * n_ops * 4);
+        if (s.rc != RSV_OK) return s.rc;
+        rc = st.eval(prog, blob, cfg, pi, n_pi, true);
+        if (rc == RSV_OK) rc = rsv_witness_trace_dev(st.c(), prog, st.vars, st.flow, st.swap, st.accept, n, dplonk, dposeidon, dops);
+        return rc == RSV_OK ? st.finish(accept, reason) : rc;
+    });
 }
 
 }  // extern "C"

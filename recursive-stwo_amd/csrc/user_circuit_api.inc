@@ -11,13 +11,10 @@ int uc_upload(rsv_witness_program* prog) {
     if (prog->d_uc_rows) return RSV_OK;
     rsv::ucircuit::Tables& t = prog->uc;
     if (t.rows.empty()) {
-        int rc;
-        try {
-            rc = rsv::ucircuit::check(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5,
-                                      prog->witness_ops.data(), prog->witness_ops.size() / 3, prog->n_vars, prog->num_input, &t);
-        } catch (const std::bad_alloc&) {
-            return RSV_E_NOMEM;
-        }
+        const int rc = nomem_guard([&] {
+            return rsv::ucircuit::check(prog->gates.data(), prog->gates.size() / 6, prog->flow_wires.data(), prog->flow_wires.size() / 5,
+                                        prog->witness_ops.data(), prog->witness_ops.size() / 3, prog->n_vars, prog->num_input, &t);
+        });
         if (rc != RSV_OK) return rc;
     }
     uint32_t *dr = nullptr, *df = nullptr;
@@ -82,15 +79,13 @@ extern "C" {
 int rsv_circuit_program_create(const uint32_t* gates, size_t n_rows, const uint32_t* flow_wires, size_t n_flow, const uint32_t* witness_ops,
                                size_t n_witness_ops, uint32_t n_vars, uint32_t num_input, int device, rsv_witness_program** out) {
     if (!out) return RSV_E_NULL;
-    try {
+    return nomem_guard([&]() -> int {
         rsv::ucircuit::Tables t;
         const int rc = rsv::ucircuit::check(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, &t);
         if (rc != RSV_OK) return rc;
         *out = uc_new_program(gates, n_rows, flow_wires, n_flow, witness_ops, n_witness_ops, n_vars, num_input, device, std::move(t));
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-    return RSV_OK;
+        return RSV_OK;
+    });
 }
 
 int rsv_circuit_check_dev(rsv_ctx* c, const rsv_witness_program* prog, const uint32_t* d_variables, size_t n, uint8_t* d_ok,

@@ -2,6 +2,7 @@
 // lives in host_logic.hpp, where a sanitizer can reach it: the shape buckets, the workspace groups, and the launch plan
 // (VerifyPlan) — which form of each kernel a batch runs and on which stream.  verify_impl checks its arguments, builds the
 // plan and then only enqueues, stage function by stage function; none of them decides a form, each reads the plan.
+// The host-pointer forms behind it (rsv_verify_batch, _inputs, _hints, the probes) stage through host_stage.inc.
 //
 // Launch plan for one batch (M = main stream, S = side stream):
 //   1. M: k_parse over the whole batch, then ONE 32-byte read-back of the batch summary (max queries / log size /
@@ -735,33 +736,12 @@ static int verify_impl(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs
     return enqueue_finalize(v);
 }
 
-namespace {
-// host-resident rsv_cfg_set -> the same set with cfg_of staged in device memory (host-pointer entry points)
-struct DevCfgSet {
-    DevBuf of;
-    rsv_cfg_set dev{};
-    int init(const rsv_cfg_set* host, size_t n) {
-        {
-            const int rc0 = check_cfg_set(host);
-            if (rc0 != RSV_OK) return rc0;
-        }
-        dev = *host;
-        if (host->cfg_of && n) {
-            HIP_TRY(of.alloc(n));
-            HIP_TRY(hipMemcpy(of.p, host->cfg_of, n, hipMemcpyHostToDevice));
-            dev.cfg_of = of.as<const uint8_t>();
-        } else dev.cfg_of = nullptr;
-        return RSV_OK;
-    }
-};
-}  // namespace
-
 extern "C" {
 
 int rsv_verify_batch_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
                          const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi, uint8_t* d_accept,
                          uint8_t* d_reason) {
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, nullptr);
+    return nomem_guard([&] { return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, nullptr); });
 }
 
 int rsv_trace_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n,
@@ -770,7 +750,7 @@ int rsv_trace_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_off
     if (!d_sib || !d_pos) return RSV_E_NULL;
     if (n_queries < 4 || n_queries > (uint32_t)MAXQ || max_log > (uint32_t)MAX_LOG) return RSV_E_SIZE;
     PathsOut po{d_sib, d_pos, n_queries, max_log, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, FlowArgs{}, nullptr, nullptr};
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po);
+    return nomem_guard([&] { return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po); });
 }
 
 int rsv_fri_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
@@ -779,43 +759,26 @@ int rsv_fri_paths_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offse
     if (!d_sib || !d_cols) return RSV_E_NULL;
     if (n_queries < 4 || n_queries > (uint32_t)MAXQ || max_log > (uint32_t)MAX_LOG || n_inner > (uint32_t)MAX_INNER) return RSV_E_SIZE;
     PathsOut po{nullptr, nullptr, n_queries, max_log, d_sib, d_cols, n_inner, nullptr, nullptr, nullptr, nullptr, FlowArgs{}, nullptr, nullptr};
-    return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po);
+    return nomem_guard([&] { return verify_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, d_accept, d_reason, &po); });
 }
 
 int rsv_verify_batch(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                      const rsv_public_input* pi, size_t n_pi, uint8_t* accept, uint8_t* reason, int device) {
-    if (n && (!blob || !offsets || !accept)) return RSV_E_NULL;
-    if (n_pi && !pi) return RSV_E_NULL;
-    { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    DevCfgSet dcfg;
-    rc = dcfg.init(cfg, n);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    // device copies: the blob is rebased so that proof 0 starts at byte 0
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dacc, dreason;
-    HIP_TRY(dblob.alloc(total + 16));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    rc = rsv_verify_batch_dev(c, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, &dcfg.dev, pi, n_pi,
-                              dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc == RSV_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && reason && hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    rsv_ctx_destroy(c);
-    return rc;
+    return nomem_guard([&]() -> int {
+        if (n && (!blob || !offsets || !accept)) return RSV_E_NULL;
+        if (n_pi && !pi) return RSV_E_NULL;
+        { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        BatchStage b;
+        rc = b.stage_cfg(cfg, n);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        rc = b.open(blob, offsets, n, device);
+        if (rc != RSV_OK) return rc;
+        rc = rsv_verify_batch_dev(b.c(), b.d_blob, b.d_offsets, n, &b.cfg, pi, n_pi, b.d_accept, b.d_reason);
+        return rc == RSV_OK ? b.finish(accept, reason) : rc;
+    });
 }
 
 }  // extern "C"
@@ -846,20 +809,11 @@ static int check_own_inputs(const void* d_pi, size_t n, size_t n_pi) {
     if (n_pi > 4096 || (n_pi && n > RSV_MAX_INPUT_RECORDS / n_pi)) return RSV_E_SIZE;
     return RSV_OK;
 }
-// verify_impl keeps host vectors (buckets, groups): a std::bad_alloc out of it is RSV_E_NOMEM, as in the circuit entry points
-template <class F> static int nomem_guard(F f) {
-    try {
-        return f();
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-}
-
 extern "C" {
 
 int rsv_verify_hints_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_t* d_offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
                          size_t n_pi, const rsv_hints_out* out, uint8_t* d_accept, uint8_t* d_reason) {
-    return verify_hints_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, out, d_accept, d_reason);
+    return nomem_guard([&] { return verify_hints_impl(c, d_blob, d_offsets, n, cfg, pi, n_pi, nullptr, out, d_accept, d_reason); });
 }
 
 // (no inputs at all is the shared form with an empty table: the same sum, 0, and no extra launch)
@@ -881,49 +835,28 @@ int rsv_verify_hints_inputs_dev(rsv_ctx* c, const uint8_t* d_blob, const uint64_
 
 int rsv_verify_batch_inputs(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg, const rsv_public_input* pi,
                             size_t n_pi, uint8_t* accept, uint8_t* reason, int device) {
-    if (n && (!blob || !offsets || !accept)) return RSV_E_NULL;
-    if (n && n_pi && !pi) return RSV_E_NULL;
-    { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
-    if (n > (1u << 26)) return RSV_E_SIZE;
-    { const int rc0 = check_own_inputs(pi, n, n_pi); if (rc0 != RSV_OK) return rc0; }
-    for (size_t i = 0; i < n * n_pi; i++)
-        for (int k = 0; k < 4; k++)
-            if (pi[i].value[k] >= RSV_M31_P) return RSV_E_RANGE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    DevCfgSet dcfg;
-    rc = dcfg.init(cfg, n);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel;
-    try {
-        rel.resize(n + 1);
-    } catch (const std::bad_alloc&) {
-        return RSV_E_NOMEM;
-    }
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    DevBuf dblob, doffs, dacc, dreason, dpi;
-    HIP_TRY(dblob.alloc(total + 16));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
-    HIP_TRY(dpi.alloc(sizeof(rsv_public_input) * n * n_pi + 16));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    if (n_pi) HIP_TRY(hipMemcpy(dpi.p, pi, sizeof(rsv_public_input) * n * n_pi, hipMemcpyHostToDevice));
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    rc = rsv_verify_batch_inputs_dev(c, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, &dcfg.dev, dpi.as<const rsv_public_input>(), n_pi,
-                                     dacc.as<uint8_t>(), dreason.as<uint8_t>());
-    if (rc == RSV_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && reason && hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    rsv_ctx_destroy(c);
-    return rc;
+    return nomem_guard([&]() -> int {
+        if (n && (!blob || !offsets || !accept)) return RSV_E_NULL;
+        if (n && n_pi && !pi) return RSV_E_NULL;
+        { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
+        if (n > (1u << 26)) return RSV_E_SIZE;
+        { const int rc0 = check_own_inputs(pi, n, n_pi); if (rc0 != RSV_OK) return rc0; }
+        for (size_t i = 0; i < n * n_pi; i++)
+            for (int k = 0; k < 4; k++)
+                if (pi[i].value[k] >= RSV_M31_P) return RSV_E_RANGE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        BatchStage b;
+        rc = b.stage_cfg(cfg, n);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        rc = b.open(blob, offsets, n, device);
+        if (rc != RSV_OK) return rc;
+        const rsv_public_input* dpi = b.s.upload<rsv_public_input>(pi, sizeof(rsv_public_input) * n * n_pi, 16);
+        if (b.s.rc != RSV_OK) return b.s.rc;
+        rc = rsv_verify_batch_inputs_dev(b.c(), b.d_blob, b.d_offsets, n, &b.cfg, dpi, n_pi, b.d_accept, b.d_reason);
+        return rc == RSV_OK ? b.finish(accept, reason) : rc;
+    });
 }
 
 int rsv_public_input_sum_dev(rsv_ctx* c, const rsv_public_input* d_pi, size_t n, size_t n_pi, const uint32_t* d_z_alpha, uint32_t* d_sum,
@@ -976,77 +909,49 @@ int rsv_statement_digest_dev(rsv_ctx* c, const rsv_public_input* d_pi, size_t n_
 int rsv_verify_hints(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
                      const rsv_public_input* pi, size_t n_pi, const rsv_hints_out* out, uint8_t* accept, uint8_t* reason,
                      int device) {
-    if (!out || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
-    if (n_pi && !pi) return RSV_E_NULL;
-    { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
-    if (n > (1u << 20)) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    DevCfgSet dcfg;
-    rc = dcfg.init(cfg, n);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    for (size_t i = 0; i < n; i++)
-        if (offsets[i + 1] < offsets[i]) return RSV_E_SIZE;
-    const uint64_t base = offsets[0], total = offsets[n] - base;
-    std::vector<uint64_t> rel(n + 1);
-    for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-    // the same struct, device side: one allocation per requested output
-    const size_t nq = out->n_queries, M = out->max_log, nt = 1 + (size_t)out->n_inner;
-    struct Out { uint32_t* host; uint32_t* rsv_hints_out::*field; size_t words; DevBuf buf; };
-    Out outs[] = {{out->d_transcript, &rsv_hints_out::d_transcript, n * (size_t)RSV_TRANSCRIPT_WORDS, {}},
-                  {out->d_trace_sib, &rsv_hints_out::d_trace_sib, n * 4 * nq * M * 8, {}},
-                  {out->d_trace_pos, &rsv_hints_out::d_trace_pos, n * 4 * nq, {}},
-                  {out->d_trace_cols, &rsv_hints_out::d_trace_cols, n * 4 * nq * 64, {}},
-                  {out->d_fri_sib, &rsv_hints_out::d_fri_sib, n * nt * nq * M * 8, {}},
-                  {out->d_fri_cols, &rsv_hints_out::d_fri_cols, n * nt * nq * 3 * 8, {}},
-                  {out->d_fri_folded, &rsv_hints_out::d_fri_folded, n * 3 * nq * 4, {}},
-                  {out->d_query_values, &rsv_hints_out::d_query_values, n * nq * 4 * (8 + (size_t)out->n_inner), {}},
-                  {out->d_flow, &rsv_hints_out::d_flow, n * (size_t)out->flow_stride * FLOW_WORDS, {}},
-                  {out->d_flow_count, &rsv_hints_out::d_flow_count, n, {}},
-                  {out->d_accept_bitmap, &rsv_hints_out::d_accept_bitmap, (n + 31) / 32, {}}};
-    rsv_hints_out dev = *out;
-    DevBuf dcount;  // the u64 output
-    if (out->d_accept_count) {
-        HIP_TRY(dcount.alloc(8));
-        dev.d_accept_count = dcount.as<uint64_t>();
-    }
-    DevBuf dswap;  // the one byte-typed output
-    if (out->d_flow_swap) {
-        if (out->flow_stride == 0) return RSV_E_SIZE;
-        HIP_TRY(dswap.alloc(n * (size_t)out->flow_stride));
-        HIP_TRY(hipMemset(dswap.p, 0, n * (size_t)out->flow_stride));
-        dev.d_flow_swap = dswap.as<uint8_t>();
-    }
-    for (Out& o : outs) {
-        if (!o.host) continue;
-        if (o.words == 0) return RSV_E_SIZE;  // a path output without a declared shape
-        HIP_TRY(o.buf.alloc(4 * o.words));
-        HIP_TRY(hipMemset(o.buf.p, 0, 4 * o.words));
-        dev.*(o.field) = o.buf.as<uint32_t>();
-    }
-    DevBuf dblob, doffs, dacc, dreason;
-    HIP_TRY(dblob.alloc(total + 16));
-    HIP_TRY(doffs.alloc(8 * (n + 1)));
-    HIP_TRY(dacc.alloc(n));
-    HIP_TRY(dreason.alloc(n));
-    HIP_TRY(hipMemcpy(dblob.p, blob + base, total, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-    rsv_ctx* c = nullptr;
-    rc = rsv_ctx_create(device, &c);
-    if (rc != RSV_OK) return rc;
-    rc = rsv_verify_hints_dev(c, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), n, &dcfg.dev, pi, n_pi, &dev, dacc.as<uint8_t>(),
-                              dreason.as<uint8_t>());
-    if (rc == RSV_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = RSV_E_DEVICE;
-    for (Out& o : outs)
-        if (rc == RSV_OK && o.host && hipMemcpy(o.host, o.buf.p, 4 * o.words, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && out->d_accept_count && hipMemcpy(out->d_accept_count, dcount.p, 8, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && out->d_flow_swap &&
-        hipMemcpy(out->d_flow_swap, dswap.p, n * (size_t)out->flow_stride, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && hipMemcpy(accept, dacc.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    if (rc == RSV_OK && reason && hipMemcpy(reason, dreason.p, n, hipMemcpyDeviceToHost) != hipSuccess) rc = RSV_E_DEVICE;
-    rsv_ctx_destroy(c);
-    return rc;
+    return nomem_guard([&]() -> int {
+        if (!out || (n && (!blob || !offsets || !accept))) return RSV_E_NULL;
+        if (n_pi && !pi) return RSV_E_NULL;
+        { const int rc0 = check_cfg_set(cfg); if (rc0 != RSV_OK) return rc0; }  // (before any device work: misuse shows without a GPU)
+        if (n > (1u << 20)) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        BatchStage b;
+        rc = b.stage_cfg(cfg, n);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        rc = b.rebase(offsets, n);
+        if (rc != RSV_OK) return rc;
+        // the same struct, device side: one zero-filled allocation per requested output
+        const size_t nq = out->n_queries, M = out->max_log, nt = 1 + (size_t)out->n_inner;
+        rsv_hints_out dev = *out;
+        bool shapeless = false;  // a requested output without a declared shape
+        auto words = [&](uint32_t* host, size_t count) {
+            if (host && count == 0) shapeless = true;
+            return shapeless ? nullptr : b.s.output<uint32_t>(host, 4 * count, true);
+        };
+        if (out->d_flow_swap && out->flow_stride == 0) return RSV_E_SIZE;
+        dev.d_accept_count = b.s.output<uint64_t>(out->d_accept_count, 8);
+        dev.d_flow_swap = b.s.output<uint8_t>(out->d_flow_swap, n * (size_t)out->flow_stride, true);
+        dev.d_transcript = words(out->d_transcript, n * (size_t)RSV_TRANSCRIPT_WORDS);
+        dev.d_trace_sib = words(out->d_trace_sib, n * 4 * nq * M * 8);
+        dev.d_trace_pos = words(out->d_trace_pos, n * 4 * nq);
+        dev.d_trace_cols = words(out->d_trace_cols, n * 4 * nq * 64);
+        dev.d_fri_sib = words(out->d_fri_sib, n * nt * nq * M * 8);
+        dev.d_fri_cols = words(out->d_fri_cols, n * nt * nq * 3 * 8);
+        dev.d_fri_folded = words(out->d_fri_folded, n * 3 * nq * 4);
+        dev.d_query_values = words(out->d_query_values, n * nq * 4 * (8 + (size_t)out->n_inner));
+        dev.d_flow = words(out->d_flow, n * (size_t)out->flow_stride * FLOW_WORDS);
+        dev.d_flow_count = words(out->d_flow_count, n);
+        dev.d_accept_bitmap = words(out->d_accept_bitmap, (n + 31) / 32);
+        if (b.s.rc != RSV_OK) return b.s.rc;
+        if (shapeless) return RSV_E_SIZE;
+        rc = b.create(device);
+        if (rc == RSV_OK) rc = b.upload(blob);
+        if (rc != RSV_OK) return rc;
+        rc = rsv_verify_hints_dev(b.c(), b.d_blob, b.d_offsets, n, &b.cfg, pi, n_pi, &dev, b.d_accept, b.d_reason);
+        return rc == RSV_OK ? b.finish(accept, reason) : rc;
+    });
 }
 
 // PoseidonFlow: records of one proof of this shape (pure host arithmetic, the same functions the kernels index with)
@@ -1084,141 +989,128 @@ int rsv_fri_paths(const uint8_t* blob, const uint64_t* offsets, size_t n, const 
 
 int rsv_transcript_batch(const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg, uint32_t* out,
                          int device) {
-    if (n && !out) return RSV_E_NULL;
-    std::vector<uint8_t> accept(n ? n : 1);
-    rsv_hints_out ho{};
-    ho.d_transcript = out;
-    return rsv_verify_hints(blob, offsets, n, cfg, nullptr, 0, &ho, accept.data(), nullptr, device);
+    return nomem_guard([&]() -> int {
+        if (n && !out) return RSV_E_NULL;
+        std::vector<uint8_t> accept(n ? n : 1);
+        rsv_hints_out ho{};
+        ho.d_transcript = out;
+        return rsv_verify_hints(blob, offsets, n, cfg, nullptr, 0, &ho, accept.data(), nullptr, device);
+    });
 }
 
 
 // ---------------------------------------------------------------- a1 / a2 / a8 / line: arithmetic probes
 int rsv_field_op(int op, const uint32_t* a4, const uint32_t* b4, uint32_t* out4, size_t n, int device) {
-    if (n && (!a4 || !out4)) return RSV_E_NULL;
-    if (op < 0 || op > RSV_F_QPOW) return RSV_E_SIZE;
-    const bool binary = op == RSV_F_QADD || op == RSV_F_QSUB || op == RSV_F_QMUL || op == RSV_F_MMUL || op == RSV_F_CMUL || op == RSV_F_QPOW;
-    if (n && binary && !b4) return RSV_E_NULL;
-    if (n > ((size_t)1 << 26)) return RSV_E_SIZE;
-    for (size_t i = 0; i < 4 * n; i++)
-        if (a4[i] >= RSV_M31_P || (binary && op != RSV_F_QPOW && b4[i] >= RSV_M31_P)) return RSV_E_RANGE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf da, db, dout;
-    HIP_TRY(da.alloc(16 * n));
-    HIP_TRY(dout.alloc(16 * n));
-    HIP_TRY(hipMemcpy(da.p, a4, 16 * n, hipMemcpyHostToDevice));
-    if (binary) {
-        HIP_TRY(db.alloc(16 * n));
-        HIP_TRY(hipMemcpy(db.p, b4, 16 * n, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_field_op, dim3(grid_for(n, 256)), dim3(256), 0, 0, op, da.as<const uint32_t>(),
-                       binary ? db.as<const uint32_t>() : nullptr, dout.as<uint32_t>(), n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out4, dout.p, 16 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!a4 || !out4)) return RSV_E_NULL;
+        if (op < 0 || op > RSV_F_QPOW) return RSV_E_SIZE;
+        const bool binary = op == RSV_F_QADD || op == RSV_F_QSUB || op == RSV_F_QMUL || op == RSV_F_MMUL || op == RSV_F_CMUL || op == RSV_F_QPOW;
+        if (n && binary && !b4) return RSV_E_NULL;
+        if (n > ((size_t)1 << 26)) return RSV_E_SIZE;
+        for (size_t i = 0; i < 4 * n; i++)
+            if (a4[i] >= RSV_M31_P || (binary && op != RSV_F_QPOW && b4[i] >= RSV_M31_P)) return RSV_E_RANGE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t* da = s.upload<uint32_t>(a4, 16 * n);
+        const uint32_t* db = binary ? s.upload<uint32_t>(b4, 16 * n) : nullptr;
+        uint32_t* dout = s.output<uint32_t>(out4, 16 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_field_op, dim3(grid_for(n, 256)), dim3(256), 0, 0, op, da, db, dout, n);
+        return s.finish();
+    });
 }
 
 int rsv_domain_points(uint32_t log_size, const uint32_t* q, uint32_t* xy, size_t n, int device) {
-    if (n && (!q || !xy)) return RSV_E_NULL;
-    if (log_size < 1 || log_size > (uint32_t)MAX_LOG || n > ((size_t)1 << 26)) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dq, dxy;
-    HIP_TRY(dq.alloc(4 * n));
-    HIP_TRY(dxy.alloc(8 * n));
-    HIP_TRY(hipMemcpy(dq.p, q, 4 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_domain_points, dim3(grid_for(n, 256)), dim3(256), 0, 0, log_size, dq.as<const uint32_t>(),
-                       dxy.as<uint32_t>(), n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(xy, dxy.p, 8 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!q || !xy)) return RSV_E_NULL;
+        if (log_size < 1 || log_size > (uint32_t)MAX_LOG || n > ((size_t)1 << 26)) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t* dq = s.upload<uint32_t>(q, 4 * n);
+        uint32_t* dxy = s.output<uint32_t>(xy, 8 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_domain_points, dim3(grid_for(n, 256)), dim3(256), 0, 0, log_size, dq, dxy, n);
+        return s.finish();
+    });
 }
 
 int rsv_line_eval(const uint32_t* coeffs4, uint32_t log_n, const uint32_t* x, uint32_t* out4, size_t n, int device) {
-    if (!coeffs4 || (n && (!x || !out4))) return RSV_E_NULL;
-    if (log_n > 16 || n > ((size_t)1 << 26)) return RSV_E_SIZE;
-    const size_t nc = (size_t)1 << log_n;
-    for (size_t i = 0; i < 4 * nc; i++)
-        if (coeffs4[i] >= RSV_M31_P) return RSV_E_RANGE;
-    for (size_t i = 0; i < n; i++)
-        if (x[i] >= RSV_M31_P) return RSV_E_RANGE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dc, dx, dout;
-    HIP_TRY(dc.alloc(16 * nc));
-    HIP_TRY(dx.alloc(4 * n));
-    HIP_TRY(dout.alloc(16 * n));
-    HIP_TRY(hipMemcpy(dc.p, coeffs4, 16 * nc, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dx.p, x, 4 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_line_eval, dim3(grid_for(n, 256)), dim3(256), 0, 0, dc.as<const uint32_t>(), log_n,
-                       dx.as<const uint32_t>(), dout.as<uint32_t>(), n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out4, dout.p, 16 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!coeffs4 || (n && (!x || !out4))) return RSV_E_NULL;
+        if (log_n > 16 || n > ((size_t)1 << 26)) return RSV_E_SIZE;
+        const size_t nc = (size_t)1 << log_n;
+        for (size_t i = 0; i < 4 * nc; i++)
+            if (coeffs4[i] >= RSV_M31_P) return RSV_E_RANGE;
+        for (size_t i = 0; i < n; i++)
+            if (x[i] >= RSV_M31_P) return RSV_E_RANGE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t *dc = s.upload<uint32_t>(coeffs4, 16 * nc), *dx = s.upload<uint32_t>(x, 4 * n);
+        uint32_t* dout = s.output<uint32_t>(out4, 16 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_line_eval, dim3(grid_for(n, 256)), dim3(256), 0, 0, dc, log_n, dx, dout, n);
+        return s.finish();
+    });
 }
 
 int rsv_last_layer_check(const uint32_t* coeffs4, uint32_t log_n, const uint32_t* x, const uint32_t* folded4, uint8_t* ok,
                          size_t n, int device) {
-    if (!coeffs4 || (n && (!x || !folded4 || !ok))) return RSV_E_NULL;
-    if (log_n > 16 || n > ((size_t)1 << 26)) return RSV_E_SIZE;
-    const size_t nc = (size_t)1 << log_n;
-    for (size_t i = 0; i < 4 * nc; i++)
-        if (coeffs4[i] >= RSV_M31_P) return RSV_E_RANGE;
-    for (size_t i = 0; i < n; i++)
-        if (x[i] >= RSV_M31_P) return RSV_E_RANGE;
-    for (size_t i = 0; i < 4 * n; i++)
-        if (folded4[i] >= RSV_M31_P) return RSV_E_RANGE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    DevBuf dc, dx, df, dok;
-    HIP_TRY(dc.alloc(16 * nc));
-    HIP_TRY(dx.alloc(4 * n));
-    HIP_TRY(df.alloc(16 * n));
-    HIP_TRY(dok.alloc(n));
-    HIP_TRY(hipMemcpy(dc.p, coeffs4, 16 * nc, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dx.p, x, 4 * n, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(df.p, folded4, 16 * n, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_last_layer_check, dim3(grid_for(n, 256)), dim3(256), 0, 0, dc.as<const uint32_t>(), log_n,
-                       dx.as<const uint32_t>(), df.as<const uint32_t>(), dok.as<uint8_t>(), n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(ok, dok.p, n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!coeffs4 || (n && (!x || !folded4 || !ok))) return RSV_E_NULL;
+        if (log_n > 16 || n > ((size_t)1 << 26)) return RSV_E_SIZE;
+        const size_t nc = (size_t)1 << log_n;
+        for (size_t i = 0; i < 4 * nc; i++)
+            if (coeffs4[i] >= RSV_M31_P) return RSV_E_RANGE;
+        for (size_t i = 0; i < n; i++)
+            if (x[i] >= RSV_M31_P) return RSV_E_RANGE;
+        for (size_t i = 0; i < 4 * n; i++)
+            if (folded4[i] >= RSV_M31_P) return RSV_E_RANGE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        HostStage s;
+        const uint32_t *dc = s.upload<uint32_t>(coeffs4, 16 * nc), *dx = s.upload<uint32_t>(x, 4 * n), *df = s.upload<uint32_t>(folded4, 16 * n);
+        uint8_t* dok = s.output<uint8_t>(ok, n);
+        if (s.rc != RSV_OK) return s.rc;
+        hipLaunchKernelGGL(k_last_layer_check, dim3(grid_for(n, 256)), dim3(256), 0, 0, dc, log_n, dx, df, dok, n);
+        return s.finish();
+    });
 }
 
 // a10 probe: scatter the flattened samples to the word offsets the kernels read them from (a proof prefix per item)
 int rsv_oods_eval(const uint32_t* samples4, const uint32_t* params26, uint32_t* out8, size_t n, int device) {
-    if (n && (!samples4 || !params26 || !out8)) return RSV_E_NULL;
-    if (n > ((size_t)1 << 20)) return RSV_E_SIZE;
-    static constexpr SampleTable tab = make_sample_table();
-    const size_t pw = tab.end;
-    for (size_t i = 0; i < n * N_SAMPLES * 4; i++)
-        if (samples4[i] >= RSV_M31_P) return RSV_E_RANGE;
-    for (size_t i = 0; i < n; i++) {
-        const uint32_t* pr = params26 + OODS_PARAM_WORDS * i;
-        if (pr[0] < 1 || pr[0] > 28 || pr[1] < 1 || pr[1] > 28) return RSV_E_RANGE;
-        for (int k = 2; k < (int)OODS_PARAM_WORDS; k++)
-            if (pr[k] >= RSV_M31_P) return RSV_E_RANGE;
-    }
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    if (n == 0) return RSV_OK;
-    std::vector<uint32_t> prefix(n * pw, 0u);
-    for (size_t i = 0; i < n; i++)
-        for (int k = 0; k < N_SAMPLES; k++) memcpy(&prefix[i * pw + tab.off[k]], samples4 + (i * N_SAMPLES + k) * 4, 16);
-    DevBuf dp, dpar, dout;
-    HIP_TRY(dp.alloc(4 * prefix.size()));
-    HIP_TRY(dpar.alloc(4 * OODS_PARAM_WORDS * n));
-    HIP_TRY(dout.alloc(32 * n));
-    HIP_TRY(hipMemcpy(dp.p, prefix.data(), 4 * prefix.size(), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dpar.p, params26, 4 * OODS_PARAM_WORDS * n, hipMemcpyHostToDevice));
-    launch_oods_probe(dp.as<const uint32_t>(), (uint32_t)pw, dpar.as<const uint32_t>(), dout.as<uint32_t>(), (uint32_t)n);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out8, dout.p, 32 * n, hipMemcpyDeviceToHost));
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (n && (!samples4 || !params26 || !out8)) return RSV_E_NULL;
+        if (n > ((size_t)1 << 20)) return RSV_E_SIZE;
+        static constexpr SampleTable tab = make_sample_table();
+        const size_t pw = tab.end;
+        for (size_t i = 0; i < n * N_SAMPLES * 4; i++)
+            if (samples4[i] >= RSV_M31_P) return RSV_E_RANGE;
+        for (size_t i = 0; i < n; i++) {
+            const uint32_t* pr = params26 + OODS_PARAM_WORDS * i;
+            if (pr[0] < 1 || pr[0] > 28 || pr[1] < 1 || pr[1] > 28) return RSV_E_RANGE;
+            for (int k = 2; k < (int)OODS_PARAM_WORDS; k++)
+                if (pr[k] >= RSV_M31_P) return RSV_E_RANGE;
+        }
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        if (n == 0) return RSV_OK;
+        std::vector<uint32_t> prefix(n * pw, 0u);
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < N_SAMPLES; k++) memcpy(&prefix[i * pw + tab.off[k]], samples4 + (i * N_SAMPLES + k) * 4, 16);
+        HostStage s;
+        const uint32_t *dp = s.upload<uint32_t>(prefix.data(), 4 * prefix.size()), *dpar = s.upload<uint32_t>(params26, 4 * OODS_PARAM_WORDS * n);
+        uint32_t* dout = s.output<uint32_t>(out8, 32 * n);
+        if (s.rc != RSV_OK) return s.rc;
+        launch_oods_probe(dp, (uint32_t)pw, dpar, dout, (uint32_t)n);
+        return s.finish();
+    });
 }
 
 #ifdef RSV_COUNT_PERMS
@@ -1330,66 +1222,58 @@ int rsv_accept_bitmap_dev(rsv_ctx* c, const uint8_t* d_accept, size_t n, uint32_
 // Transcript parity probe: runs parse + transcript for one proof and returns
 // the challenges (layout documented in include/rsv.h).
 int rsv_transcript(const uint8_t* proof, size_t len, uint32_t* out, size_t cap, int device) {
-    if (!proof || !out) return RSV_E_NULL;
-    if (cap < 1) return RSV_E_CAP;
-    if (len > (1u << 30)) return RSV_E_SIZE;
-    int rc = select_device(device);
-    if (rc != RSV_OK) return rc;
-    DevBuf dblob, doffs, dmeta, dctx, dsum, dshape;
-    uint64_t offs[2] = {0, len};
-    HIP_TRY(dblob.alloc(len + 16));
-    HIP_TRY(doffs.alloc(16));
-    HIP_TRY(dmeta.alloc(sizeof(ProofMeta)));
-    HIP_TRY(dctx.alloc(sizeof(ProofCtx)));
-    HIP_TRY(dsum.alloc(256));
-    HIP_TRY(dshape.alloc(16));
-    HIP_TRY(hipMemset(dsum.p, 0, 256));
-    HIP_TRY(hipMemcpy(dblob.p, proof, len, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(doffs.p, offs, 16, hipMemcpyHostToDevice));
-    // probe: the configuration words serialized in the proof itself (documented in rsv.h: not a verdict)
-    CfgSet co{};
-    co.n = 1;
-    if (len >= 4 * (W_NQ + 1)) {
-        uint32_t hw[W_NQ + 1];
-        memcpy(hw, proof, sizeof(hw));
-        co.c[0][0] = hw[W_POW_BITS]; co.c[0][1] = hw[W_BLOWUP]; co.c[0][2] = hw[W_LOG_LAST]; co.c[0][3] = hw[W_NQ];
-    }
-    hipLaunchKernelGGL(k_parse, dim3(1), dim3(64), 0, 0, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), 1u, co,
-                       dmeta.as<ProofMeta>(), dctx.as<ProofCtx>(), dsum.as<uint32_t>(), dshape.as<uint32_t>());
-    // (the prefixes inside sampled_values are the OODS kernels' to check in the pipeline; no OODS evaluation runs here)
-    hipLaunchKernelGGL(k_prefix_check, dim3(1), dim3(64), 0, 0, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), 1u,
-                       dmeta.as<const ProofMeta>(), dctx.as<ProofCtx>());
-    {
-        const bool row = default_options().transcript_form != 2;
-        if (row)
-            hipLaunchKernelGGL(k_transcript_row<0>, dim3(1), dim3(256), 0, 0, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(),
-                               1u, dmeta.as<const ProofMeta>(), dctx.as<ProofCtx>(), FlowArgs{nullptr, nullptr, nullptr, 0});
-        else
-            hipLaunchKernelGGL(k_transcript<false>, dim3(1), dim3(64), 0, 0, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), 1u,
-                               dmeta.as<const ProofMeta>(), dctx.as<ProofCtx>(), FlowArgs{nullptr, nullptr, nullptr, 0});
-    }
-    // no Merkle stage runs here: the whole proof is read for canonicity (k_finalize, force)
-    hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, 0, dblob.as<const uint8_t>(), doffs.as<const uint64_t>(), 1u,
-                       dmeta.as<const ProofMeta>(), dctx.as<ProofCtx>(), (uint8_t*)nullptr, (uint8_t*)nullptr, 1u, (uint32_t*)nullptr,
-                       (unsigned long long*)nullptr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    std::vector<char> hm(sizeof(ProofMeta)), hc(sizeof(ProofCtx));
-    HIP_TRY(hipMemcpy(hm.data(), dmeta.p, sizeof(ProofMeta), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hc.data(), dctx.p, sizeof(ProofCtx), hipMemcpyDeviceToHost));
-    const ProofMeta* m = reinterpret_cast<const ProofMeta*>(hm.data());
-    const ProofCtx* x = reinterpret_cast<const ProofCtx*>(hc.data());
-    if (m->reason != R_OK || (x->flags & (1u << R_PARSE))) { out[0] = RSV_R_PARSE; return RSV_OK; }
-    size_t need = 40 + 4 * (size_t)(m->n_inner + 1) + m->nq;
-    if (cap < need) return RSV_E_CAP;
-    out[0] = (x->flags & (1u << R_POW)) ? RSV_R_POW : RSV_R_OK;
-    out[1] = m->n_inner + 1; out[2] = m->nq; out[3] = m->M;
-    memcpy(out + 4, x->z, 16); memcpy(out + 8, x->alpha, 16); memcpy(out + 12, x->rc, 16);
-    memcpy(out + 16, x->oods_t, 16); memcpy(out + 20, x->oods_x, 16); memcpy(out + 24, x->oods_y, 16);
-    memcpy(out + 28, x->after, 16); memcpy(out + 32, x->pow_digest, 32);
-    memcpy(out + 40, x->fri_alpha, 16 * (m->n_inner + 1));
-    memcpy(out + 40 + 4 * (m->n_inner + 1), x->raw_q, 4 * m->nq);
-    return RSV_OK;
+    return nomem_guard([&]() -> int {
+        if (!proof || !out) return RSV_E_NULL;
+        if (cap < 1) return RSV_E_CAP;
+        if (len > (1u << 30)) return RSV_E_SIZE;
+        int rc = select_device(device);
+        if (rc != RSV_OK) return rc;
+        const uint64_t offs[2] = {0, len};
+        std::vector<char> hm(sizeof(ProofMeta)), hc(sizeof(ProofCtx));
+        HostStage s;
+        const uint8_t* dblob = s.upload<uint8_t>(proof, len, BatchStage::kBlobSlack);
+        const uint64_t* doffs = s.upload<uint64_t>(offs, 16);
+        ProofMeta* dmeta = s.output<ProofMeta>(hm.data(), sizeof(ProofMeta));
+        ProofCtx* dctx = s.output<ProofCtx>(hc.data(), sizeof(ProofCtx));
+        uint32_t *dsum = s.scratch<uint32_t>(256, true), *dshape = s.scratch<uint32_t>(16);
+        if (s.rc != RSV_OK) return s.rc;
+        // probe: the configuration words serialized in the proof itself (documented in rsv.h: not a verdict)
+        CfgSet co{};
+        co.n = 1;
+        if (len >= 4 * (W_NQ + 1)) {
+            uint32_t hw[W_NQ + 1];
+            memcpy(hw, proof, sizeof(hw));
+            co.c[0][0] = hw[W_POW_BITS]; co.c[0][1] = hw[W_BLOWUP]; co.c[0][2] = hw[W_LOG_LAST]; co.c[0][3] = hw[W_NQ];
+        }
+        hipLaunchKernelGGL(k_parse, dim3(1), dim3(64), 0, 0, dblob, doffs, 1u, co, dmeta, dctx, dsum, dshape);
+        // (the prefixes inside sampled_values are the OODS kernels' to check in the pipeline; no OODS evaluation runs here)
+        hipLaunchKernelGGL(k_prefix_check, dim3(1), dim3(64), 0, 0, dblob, doffs, 1u, (const ProofMeta*)dmeta, dctx);
+        {
+            const bool row = default_options().transcript_form != 2;
+            if (row)
+                hipLaunchKernelGGL(k_transcript_row<0>, dim3(1), dim3(256), 0, 0, dblob, doffs, 1u, (const ProofMeta*)dmeta, dctx, FlowArgs{nullptr, nullptr, nullptr, 0});
+            else
+                hipLaunchKernelGGL(k_transcript<false>, dim3(1), dim3(64), 0, 0, dblob, doffs, 1u, (const ProofMeta*)dmeta, dctx, FlowArgs{nullptr, nullptr, nullptr, 0});
+        }
+        // no Merkle stage runs here: the whole proof is read for canonicity (k_finalize, force)
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, 0, dblob, doffs, 1u, (const ProofMeta*)dmeta, dctx, (uint8_t*)nullptr, (uint8_t*)nullptr, 1u,
+                           (uint32_t*)nullptr, (unsigned long long*)nullptr);
+        rc = s.finish();
+        if (rc != RSV_OK) return rc;
+        const ProofMeta* m = reinterpret_cast<const ProofMeta*>(hm.data());
+        const ProofCtx* x = reinterpret_cast<const ProofCtx*>(hc.data());
+        if (m->reason != R_OK || (x->flags & (1u << R_PARSE))) { out[0] = RSV_R_PARSE; return RSV_OK; }
+        size_t need = 40 + 4 * (size_t)(m->n_inner + 1) + m->nq;
+        if (cap < need) return RSV_E_CAP;
+        out[0] = (x->flags & (1u << R_POW)) ? RSV_R_POW : RSV_R_OK;
+        out[1] = m->n_inner + 1; out[2] = m->nq; out[3] = m->M;
+        memcpy(out + 4, x->z, 16); memcpy(out + 8, x->alpha, 16); memcpy(out + 12, x->rc, 16);
+        memcpy(out + 16, x->oods_t, 16); memcpy(out + 20, x->oods_x, 16); memcpy(out + 24, x->oods_y, 16);
+        memcpy(out + 28, x->after, 16); memcpy(out + 32, x->pow_digest, 32);
+        memcpy(out + 40, x->fri_alpha, 16 * (m->n_inner + 1));
+        memcpy(out + 40 + 4 * (m->n_inner + 1), x->raw_q, 4 * m->nq);
+        return RSV_OK;
+    });
 }
 
 }  // extern "C"

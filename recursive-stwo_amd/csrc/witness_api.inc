@@ -1,6 +1,6 @@
 // witness_api.inc — rsv_witness_program_* and rsv_witness_eval_dev (include/rsv.h): the recursion circuit's `variables`
 // vector for a batch of proofs of one shape, evaluated level by level on the GPU (k_witness.hpp) from the hints of the
-// verifying pass.  Included at the end of rsv_hip.hip.
+// verifying pass.  Included at the end of rsv_hip.hip.  The host-buffer forms stage through host_stage.inc (WitnessStage).
 
 struct rsv_witness_program {
     int device = 0;
@@ -188,78 +188,57 @@ void witness_run(rsv_ctx* c, const rsv_witness_program* prog, Stmt& a, size_t ro
     witness_launch(c, prog, a, rows);
 }
 
-// The host-buffer forms of the witness chain (rsv_witness_eval, _trace, _interaction, _commit) on a context of their own:
-// open(), the form's program upload and output buffers, eval(), the form's _dev calls on vars / flow / swap / accept,
-// finish(), the form's own outputs copied back.
+// The host-buffer forms of the witness chain (rsv_witness_eval, _trace, _interaction, _commit) on a batch stage
+// (host_stage.inc): open(), the form's program upload and its outputs registered on b.s, eval(), the form's _dev calls on
+// vars / flow / swap / accept, finish(), which copies every registered output back.
 struct WitnessStage {
-    rsv_ctx* c = nullptr;
-    const uint64_t* offsets = nullptr;  // the batch as open() took it (host)
-    size_t n = 0;
+    BatchStage b;
     const uint32_t* vars = nullptr;     // eval()'s outputs on the device
-    const uint32_t* flow = nullptr;     // NULL unless eval() was asked to keep the flow records
+    const uint32_t* flow = nullptr;     // NULL unless eval() was given flow buffers
     const uint8_t* swap = nullptr;
     const uint8_t* accept = nullptr;
-    DevBuf d_blob, d_offsets, d_vars, d_flow, d_swap, d_accept, d_reason, d_own;
-
-    ~WitnessStage() { rsv_ctx_destroy(c); }
+    rsv_ctx* c() const { return b.c(); }
 
     // batch_offsets [batch_n + 1] have to be monotonic; by_variable: RSV_OPT_WITNESS_LAYOUT = 2, which the chain's kernels
     // read as they are written (no transpose, no second copy of the variables), else the default
     int open(const uint64_t* batch_offsets, size_t batch_n, int device, bool by_variable) {
-        for (size_t i = 0; i < batch_n; i++)
-            if (batch_offsets[i + 1] < batch_offsets[i]) return RSV_E_SIZE;
-        int rc = select_device(device);
-        if (rc == RSV_OK) rc = rsv_ctx_create(device, &c);
+        int rc = b.rebase(batch_offsets, batch_n);
+        if (rc == RSV_OK) rc = b.create(device);
         if (rc != RSV_OK) return rc;
-        if (by_variable) c->opt.witness_layout = 2;
-        offsets = batch_offsets;
-        n = batch_n;
+        if (by_variable) b.c()->opt.witness_layout = 2;
         return RSV_OK;
     }
 
-    // own, n_own: every proof's own records [n][n_own] (host), behind the n_pi shared ones (rsv_witness_eval_inputs)
+    // variables, flow_out, swap_out: host buffers the results are copied back to, or NULL — then keep_flow says whether the
+    // flow records are kept on the device at all (the chain's next stage reads them).  own, n_own: every proof's own records
+    // [n][n_own] (host), behind the n_pi shared ones (rsv_witness_eval_inputs)
     int eval(const rsv_witness_program* prog, const uint8_t* blob, const rsv_cfg_set* cfg, const rsv_public_input* pi, size_t n_pi,
-             bool keep_flow, const rsv_public_input* own = nullptr, size_t n_own = 0) {
-        const uint64_t base = offsets[0], total = offsets[n] - base;
-        std::vector<uint64_t> rel(n + 1);
-        for (size_t i = 0; i <= n; i++) rel[i] = offsets[i] - base;
-        const size_t flow_records = n * ((size_t)prog->shape.flow_count + prog->stmt_flow);
+             bool keep_flow, uint32_t* variables = nullptr, uint32_t* flow_out = nullptr, uint8_t* swap_out = nullptr,
+             const rsv_public_input* own = nullptr, size_t n_own = 0) {
+        const size_t n = b.n, flow_records = n * ((size_t)prog->shape.flow_count + prog->stmt_flow);
+        uint32_t* d_flow = nullptr;
+        uint8_t* d_swap = nullptr;
         if (keep_flow) {
-            HIP_TRY(d_flow.alloc(flow_records * 128));
-            HIP_TRY(d_swap.alloc(flow_records));
-            HIP_TRY(hipMemset(d_flow.p, 0, flow_records * 128));
-            HIP_TRY(hipMemset(d_swap.p, 0, flow_records));
+            d_flow = flow_out ? b.s.output<uint32_t>(flow_out, flow_records * 128, true) : b.s.scratch<uint32_t>(flow_records * 128, true);
+            d_swap = swap_out ? b.s.output<uint8_t>(swap_out, flow_records, true) : b.s.scratch<uint8_t>(flow_records, true);
         }
-        HIP_TRY(d_blob.alloc(total));
-        HIP_TRY(d_offsets.alloc(8 * (n + 1)));
-        HIP_TRY(d_vars.alloc(n * (size_t)prog->n_vars * 16));
-        HIP_TRY(d_accept.alloc(n));
-        HIP_TRY(d_reason.alloc(n));
-        HIP_TRY(hipMemcpy(d_blob.p, blob + base, total, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_offsets.p, rel.data(), 8 * (n + 1), hipMemcpyHostToDevice));
-        vars = d_vars.as<uint32_t>();
-        flow = d_flow.as<uint32_t>();
-        swap = d_swap.as<uint8_t>();
-        accept = d_accept.as<uint8_t>();
-        if (n_own) {
-            HIP_TRY(d_own.alloc(sizeof(rsv_public_input) * n * n_own));
-            HIP_TRY(hipMemcpy(d_own.p, own, sizeof(rsv_public_input) * n * n_own, hipMemcpyHostToDevice));
-            return rsv_witness_eval_inputs_dev(c, prog, d_blob.as<const uint8_t>(), d_offsets.as<const uint64_t>(), n, cfg, pi, n_pi,
-                                               d_own.as<const rsv_public_input>(), n_own, d_vars.as<uint32_t>(), d_flow.as<uint32_t>(),
-                                               d_swap.as<uint8_t>(), d_accept.as<uint8_t>(), d_reason.as<uint8_t>());
-        }
-        return rsv_witness_eval_dev(c, prog, d_blob.as<const uint8_t>(), d_offsets.as<const uint64_t>(), n, cfg, pi, n_pi, d_vars.as<uint32_t>(),
-                                    d_flow.as<uint32_t>(), d_swap.as<uint8_t>(), d_accept.as<uint8_t>(), d_reason.as<uint8_t>());
+        (void)b.upload(blob);  // (its status is b.s.rc, looked at below)
+        const size_t var_bytes = n * (size_t)prog->n_vars * 16;
+        uint32_t* d_vars = variables ? b.s.output<uint32_t>(variables, var_bytes) : b.s.scratch<uint32_t>(var_bytes);
+        const rsv_public_input* d_own = n_own ? b.s.upload<rsv_public_input>(own, sizeof(rsv_public_input) * n * n_own) : nullptr;
+        if (b.s.rc != RSV_OK) return b.s.rc;
+        vars = d_vars;
+        flow = d_flow;
+        swap = d_swap;
+        accept = b.d_accept;
+        if (n_own)
+            return rsv_witness_eval_inputs_dev(b.c(), prog, b.d_blob, b.d_offsets, n, cfg, pi, n_pi, d_own, n_own, d_vars, d_flow, d_swap,
+                                               b.d_accept, b.d_reason);
+        return rsv_witness_eval_dev(b.c(), prog, b.d_blob, b.d_offsets, n, cfg, pi, n_pi, d_vars, d_flow, d_swap, b.d_accept, b.d_reason);
     }
 
-    // Waits for the context, then copies accept and reason (may be NULL) back.
-    int finish(uint8_t* h_accept, uint8_t* h_reason) {
-        int rc = rsv_ctx_synchronize(c);
-        if (rc != RSV_OK) return rc;
-        HIP_TRY(hipMemcpy(h_accept, d_accept.p, n, hipMemcpyDeviceToHost));
-        if (h_reason) HIP_TRY(hipMemcpy(h_reason, d_reason.p, n, hipMemcpyDeviceToHost));
-        return RSV_OK;
-    }
+    // Waits for the context, then copies the registered outputs, accept and reason (may be NULL) back.
+    int finish(uint8_t* h_accept, uint8_t* h_reason) { return b.finish(h_accept, h_reason); }
 };
 
 }  // namespace
@@ -628,21 +607,16 @@ int rsv_witness_program_inputs(const rsv_witness_program* prog, uint32_t* n_fixe
 }
 
 // What rsv_witness_eval (own NULL, n_own 0) and rsv_witness_eval_inputs do after their own checks: a stage of its own, and
-// the variables and flow_records flow records (the latter form's include a hashed program's statement hash) copied back
+// the variables and the flow records (the latter form's include a hashed program's statement hash) copied back
 static int witness_eval_host(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
-                             const rsv_public_input* pi, size_t n_pi, const rsv_public_input* own, size_t n_own, size_t flow_records,
-                             uint32_t* variables, uint32_t* flow, uint8_t* flow_swap, uint8_t* accept, uint8_t* reason, int device) {
-    WitnessStage st;
-    int rc = st.open(offsets, n, device, false);
-    if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr, own, n_own);
-    if (rc == RSV_OK) rc = st.finish(accept, reason);
-    if (rc != RSV_OK) return rc;
-    HIP_TRY(hipMemcpy(variables, st.vars, n * (size_t)prog->n_vars * 16, hipMemcpyDeviceToHost));
-    if (flow) {
-        HIP_TRY(hipMemcpy(flow, st.flow, flow_records * 128, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(flow_swap, st.swap, flow_records, hipMemcpyDeviceToHost));
-    }
-    return RSV_OK;
+                             const rsv_public_input* pi, size_t n_pi, const rsv_public_input* own, size_t n_own, uint32_t* variables,
+                             uint32_t* flow, uint8_t* flow_swap, uint8_t* accept, uint8_t* reason, int device) {
+    return nomem_guard([&]() -> int {
+        WitnessStage st;
+        int rc = st.open(offsets, n, device, false);
+        if (rc == RSV_OK) rc = st.eval(prog, blob, cfg, pi, n_pi, flow != nullptr, variables, flow, flow_swap, own, n_own);
+        return rc == RSV_OK ? st.finish(accept, reason) : rc;
+    });
 }
 
 int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const uint64_t* offsets, size_t n, const rsv_cfg_set* cfg,
@@ -653,8 +627,7 @@ int rsv_witness_eval(const rsv_witness_program* prog, const uint8_t* blob, const
     if (prog->n_instr == 0) return RSV_E_SIZE;  // a caller's circuit
     if (n == 0) return RSV_OK;
     if (n > (1u << 20)) return RSV_E_SIZE;
-    return witness_eval_host(prog, blob, offsets, n, cfg, pi, n_pi, nullptr, 0, n * (size_t)prog->shape.flow_count, variables, flow, flow_swap,
-                             accept, reason, device);
+    return witness_eval_host(prog, blob, offsets, n, cfg, pi, n_pi, nullptr, 0, variables, flow, flow_swap, accept, reason, device);
 }
 
 // the same with every proof's own records [n][n_own] behind the n_fixed shared ones, all in host memory
@@ -668,8 +641,7 @@ int rsv_witness_eval_inputs(const rsv_witness_program* prog, const uint8_t* blob
     const int rc = witness_check_own(prog, pi_fixed, n_fixed, pi_own, n_own, n);
     if (rc != RSV_OK) return rc;
     if (n == 0) return RSV_OK;
-    return witness_eval_host(prog, blob, offsets, n, cfg, pi_fixed, n_fixed, pi_own, n_own, n * ((size_t)prog->shape.flow_count + prog->stmt_flow),
-                             variables, flow, flow_swap, accept, reason, device);
+    return witness_eval_host(prog, blob, offsets, n, cfg, pi_fixed, n_fixed, pi_own, n_own, variables, flow, flow_swap, accept, reason, device);
 }
 
 int rsv_witness_program_statement(const rsv_witness_program* prog, uint32_t* hashed, uint32_t* n_words, uint32_t* stmt_flow_count) {

@@ -16,6 +16,11 @@
 //                                                     plan_group), one line per case over every batch size at which a form
 //                                                     changes, for comparison with the restatement of what the launcher
 //                                                     used to decide inline (tests/verify_plan_ref.py)
+//   host_logic_asan offsets <seed> <rounds>          host_logic.hpp: rebase_offsets, which every host-pointer batch form stages its
+//                                                     offsets through, on seeded offset arrays in exact-size heap copies — 0 to a
+//                                                     few thousand proofs, base 0 and not, equal neighbours, one decreasing pair at
+//                                                     every position of a short array, offsets near 2^63 — against the property:
+//                                                     rel[i] == offsets[i] - offsets[0], or RSV_E_SIZE exactly when a pair decreases
 //
 // The hints file: 16 header words (magic, proof bytes, nq, M, n_inner, flow_count, n_pi, copies, 0...), then the proof
 // (padded to words), trace_sib, trace_pos, trace_cols, fri_sib, fri_cols, flow [flow_count][32], swap (bytes, padded),
@@ -377,11 +382,57 @@ static int run_plan() {
     return 0;
 }
 
+// rel[i] == offsets[i] - offsets[0] for i = 0 .. n, or RSV_E_SIZE exactly when some offsets[i + 1] < offsets[i]
+static void check_rebase(const std::vector<uint64_t>& offsets, size_t& refused) {
+    const size_t n = offsets.size() - 1;
+    bool decreases = false;
+    for (size_t i = 0; i < n; i++) decreases |= offsets[i + 1] < offsets[i];
+    std::vector<uint64_t> rel(3, 0xDEADu);  // (whatever it held is replaced)
+    const int rc = host::rebase_offsets(offsets.data(), n, rel);
+    CHECK(rc == (decreases ? RSV_E_SIZE : RSV_OK));
+    refused += decreases;
+    if (decreases) return;
+    CHECK(rel.size() == n + 1);
+    for (size_t i = 0; i <= n; i++) CHECK(rel[i] == offsets[i] - offsets[0]);
+}
+
+static int run_offsets(uint32_t seed, int rounds) {
+    std::mt19937_64 rng(seed);
+    size_t cases = 0, refused = 0;
+    const uint64_t bases[] = {0, 7, 1ull << 32, (1ull << 63) - (1ull << 40), 1ull << 63};
+    for (int r = 0; r < rounds; r++) {
+        const size_t n = r < 4 ? (size_t)r : (r % 5 == 0 ? 2000 + rng() % 3000 : rng() % 64);
+        std::vector<uint64_t> offsets(n + 1);  // exact size: a read of offsets[n + 1] is a heap overflow
+        offsets[0] = bases[r % 5];
+        const uint64_t step = r % 3 == 0 ? 1 : (r % 3 == 1 ? 500000 : 1ull << 36);
+        for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + (rng() % 4 == 0 ? 0 : rng() % step);  // a quarter of the neighbours equal
+        check_rebase(offsets, refused);
+        cases++;
+    }
+    // one decreasing pair at every position of a short array, at every base; the pair decreases by one, or down to zero
+    for (const uint64_t base : bases)
+        for (size_t n = 1; n <= 9; n++)
+            for (size_t at = 0; at < n; at++)
+                for (int to_zero = 0; to_zero < 2; to_zero++) {
+                    std::vector<uint64_t> offsets(n + 1);
+                    for (size_t i = 0; i <= n; i++) offsets[i] = base + 1 + 100 * i;
+                    offsets[at + 1] = to_zero ? 0 : offsets[at] - 1;
+                    const size_t before = refused;
+                    check_rebase(offsets, refused);
+                    CHECK(refused == before + 1);
+                    cases++;
+                }
+    CHECK(refused < cases);
+    printf("offsets: %zu arrays, %zu refused, the property holds\n", cases, refused);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 2 && std::string(argv[1]) == "plan") return run_plan();
     if (argc == 4 && std::string(argv[1]) == "program") return run_program(argv[2], argv[3]);
     if (argc == 4 && std::string(argv[1]) == "buckets") return run_buckets((uint32_t)atoi(argv[2]), atoi(argv[3]));
     if (argc == 4 && std::string(argv[1]) == "passes") return run_passes((uint32_t)atoi(argv[2]), atoi(argv[3]));
-    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds> | passes <seed> <rounds> | plan\n");
+    if (argc == 4 && std::string(argv[1]) == "offsets") return run_offsets((uint32_t)atoi(argv[2]), atoi(argv[3]));
+    fprintf(stderr, "usage: host_logic_asan program <hints> <out> | buckets <seed> <rounds> | passes <seed> <rounds> | offsets <seed> <rounds> | plan\n");
     return 2;
 }

@@ -13,6 +13,7 @@ the C++ mirror of the reference's gadgets) are plain C++ headers that g++ compil
   * with seeded shape arrays (the fixture chain's mix, one shape per proof, everything rejected, tiny query counts) against
     the invariants the launcher relies on;
   * with seeded workspace costs and budgets against the pass sizing of the next proof's streaming stages (plan_pass);
+  * with seeded offset arrays against the rebasing every host-pointer batch form does (rebase_offsets);
   * with every batch size at which a verify call changes the form of a kernel or its stream layout, under every option
     that bears on it, against the decisions as the launcher took them before they became one plan (verify_plan_ref.py)."""
 import os
@@ -48,6 +49,14 @@ def test_pass_sizing_under_sanitizers(harness):
     for seed, rounds in ((1, 64), (2, 200)):
         out = subprocess.run([harness, "passes", str(seed), str(rounds)], capture_output=True, text=True, env=SAN_ENV, timeout=600)
         assert out.returncode == 0 and "invariants hold" in out.stdout, out.stdout + out.stderr
+        assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
+
+
+def test_offset_rebasing_under_sanitizers(harness):
+    """rebase_offsets (host_logic.hpp), through which every host-pointer batch form stages its offsets (csrc/host_stage.inc)."""
+    for seed, rounds in ((1, 60), (2, 300)):
+        out = subprocess.run([harness, "offsets", str(seed), str(rounds)], capture_output=True, text=True, env=SAN_ENV, timeout=600)
+        assert out.returncode == 0 and "the property holds" in out.stdout, out.stdout + out.stderr
         assert "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr, out.stderr
 
 
